@@ -7,10 +7,12 @@ density -> force+integrate) over all particles.  State is resident in HBM before
 timed region; timing uses HIP events on the simulation's own stream (C ABI
 fs_timed_steps / fs_profile_*), bracketed by barrier + device sync, MAX over ranks.
 
-Prints ONE JSON line on rank 0 (contract fields + `roofline` + `cpu_baseline`), plus — never as
-the headline — `alt_modes` (opt-in engine modes), `alt_windows` (the same engine over later windows
-of the same scene, where the fluid is disordered / dense) and `alt_workloads` (the other
-single-GPU configs of BASELINE.json).
+Prints ONE JSON line on rank 0.  A plain run (`--gpus 1 --steps K --warmup W`) only sets up, warms up,
+times the K steps, writes the last step's outputs if `--dump-outputs DIR` is given, and prints the
+contract fields.  `--full` adds everything else the benchmark measures: `roofline` (a second, profiled
+run of the window, at most its first 100 + 100 steps), `cpu_baseline`, and — never as the headline — `alt_modes` (opt-in engine modes),
+`alt_windows` (the same engine over later windows of the same scene, where the fluid is disordered /
+dense) and `alt_workloads` (the other single-GPU configs of BASELINE.json).
 
 Profiling: `rocprofv3 ... -- python3 bench.py --no-build ...` — never build inside a profiled
 process (the profiler's preload has initialised the GPU; a build would exec compilers from it).
@@ -41,6 +43,17 @@ WORKLOADS = {
 }
 ALG_BYTES_3D = {"sort": 40 + 12, "reorder": 72 + 4, "density": 20, "force": 68}   # 216 B; predict + key (40 B) run inside the first sort kernel, as in 2D
 ALG_TOTAL_3D = 216
+
+# --dump-outputs: arrays longer than this are cut to a fixed seeded sample of rows, so that the files stay under
+# 64 MB (2^20 rows x (<= 48 B of particle fields + 8 B of start_indices)) whatever the workload's size
+DUMP_ROWS = 1 << 20
+DUMP_SEED = 0
+
+# --full: the roofline and alt_modes legs re-run the headline window, each on a fresh handle; a window longer than
+# FULL_WARMUP + FULL_STEPS is cut to its first FULL_STEPS steps after at most FULL_WARMUP warm-up steps, so that a long
+# headline window (the step count is chosen from ms_per_step) does not multiply the cost of every leg
+FULL_WARMUP = 100
+FULL_STEPS = 100
 
 # which kernel carries a pass: EXACT names as rocprofv3 prints them (profiles/counters_latest.json keys), first match wins
 PASS_KERNEL = {"force": ["fsd::k_force<0, false>"], "density": ["fsd::k_density<false, true>", "fsd::k_density<false, false>", "fsd::k_density<false>"],
@@ -106,18 +119,19 @@ def under_profiler():
 
 def load_product(no_build):
     """Build (default) or only load the HIP extension.  Under a profiler, or with --no-build, nothing is ever
-    compiled: a missing or stale library is an error (exit 3), not a fallback."""
+    compiled: a missing or stale library is an error (exit 3), not a fallback.  A library that is up to date is
+    loaded without the build lock: a built checkout may be read-only to the user who runs the benchmark."""
     import __graft_entry__ as ge
-    if no_build or under_profiler():
-        if ge.product_is_stale() and not os.environ.get("FS_ALLOW_STALE"):
-            sys.stderr.write("bench.py --no-build: gpu-fluid-simulation_amd/libfluidsim_hip.so is missing or older than its "
-                             "sources; run `python __graft_entry__.py` first (FS_ALLOW_STALE=1 overrides)\n")
-            raise SystemExit(3)
-        import gpu_fluid_simulation_amd as g
-        g.load_library()
-        return g
-    ge.build_product()
+    if ge.product_is_stale():
+        if no_build or under_profiler():
+            if not os.environ.get("FS_ALLOW_STALE"):
+                sys.stderr.write("bench.py --no-build: gpu-fluid-simulation_amd/libfluidsim_hip.so is missing or older than its "
+                                 "sources; run `python __graft_entry__.py` first (FS_ALLOW_STALE=1 overrides)\n")
+                raise SystemExit(3)
+        else:
+            ge.build_product()
     import gpu_fluid_simulation_amd as g
+    g.load_library()
     return g
 
 
@@ -151,6 +165,24 @@ def run_window(make_sim, tick, warmup, steps, n, alg_bytes, profiled=True):
         sim.profile(False)
     sim.close()
     return ms / steps, table
+
+
+def dump_outputs(sim, outdir):
+    """What a caller of the timed path receives after its last step, as DIR/<array>_<field>.npy: every field of the
+    particle records and, in 2D, start_indices.  Floats stay float32; u32 values (cell keys, cell starts) become
+    float64, which holds them exactly.  An array longer than DUMP_ROWS is cut to the same seeded sample of rows in
+    every run (sorted row indices), so two builds can be compared file for file."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {"particles": sim.download_particles()}
+    if hasattr(sim, "download_start_indices"):          # FluidSimulation3D has no start_indices download
+        arrays["start_indices"] = sim.download_start_indices()
+    for name, a in arrays.items():
+        if a.shape[0] > DUMP_ROWS:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], DUMP_ROWS, replace=False))]
+        cols = {f"{name}_{f}": a[f] for f in a.dtype.names if f != "pad"} if a.dtype.names else {name: a}
+        for col, v in cols.items():
+            np.save(os.path.join(outdir, col + ".npy"), v.astype(np.float32 if v.dtype.kind == "f" else np.float64))
 
 
 def load_json(name):
@@ -244,17 +276,25 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="dam_break_2d_16M", choices=sorted(WORKLOADS))
     ap.add_argument("--sort", default="bitonic", choices=["bitonic", "counting"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="skip alt_modes / alt_windows / alt_workloads")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline, cpu_baseline and alt_modes / alt_windows / alt_workloads (single-GPU line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip cpu_baseline (--gpus 1 measures it only with --full)")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip alt_modes / alt_windows / alt_workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's particles and start_indices to DIR/*.npy (single-GPU line)")
     ap.add_argument("--no-build", action="store_true",
                     help="never compile: load the prebuilt library or exit 3 (use under rocprofv3)")
     ap.add_argument("--pmc-traffic", type=float, default=None,
-                    help="HBM bytes per launch of the dominant kernel from a separate rocprofv3 --pmc run")
+                    help="with --full: HBM bytes per launch of the dominant kernel from a separate rocprofv3 --pmc run")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and max(args.gpus, world) > 1:
+        ap.error("--dump-outputs is implemented for the single-GPU line only")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # bare `python3 bench.py --gpus N`: this process becomes the launcher.  Nothing here imports torch, loads the
         # HIP library or initialises the GPU; the build (hipcc child processes) happens before any rank exists.
@@ -303,13 +343,34 @@ def main():
     t_wall = (time.perf_counter() - t_wall) * 1e3
     # which late-stage plan the sorts of this handle took (csrc/kernels_sort.hip; the result does not depend on it)
     sort_plan = sim.sort_plan() if (not is3d and args.sort == "bitonic") else None
+    if args.dump_outputs:
+        dump_outputs(sim, args.dump_outputs)
     sim.close()
     ms_per_step = ms / args.steps
     value = n / (ms_per_step * 1e-3) / 1e6            # M particle-steps/s
+    out = {
+        "metric": "M particle-steps/s", "value": round(value, 2), "unit": "M particle-steps/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": args.workload, "particles": n, "scene": "SURVEY.md §8d " + ("dam_break_3d (no reference counterpart)" if is3d else "dam_break_2d"),
+                   "sort": args.sort, "ref_quirks": not is3d, "parallelism": "1 GPU",
+                   "window": f"steps {args.warmup}..{args.warmup + args.steps} from the lattice (--full: alt_windows for later regimes)"},
+        "host_wall_ms_per_step": round(t_wall / args.steps, 4),
+    }
+    if sort_plan is not None:
+        out["config"]["sort_plan"] = dict(sort_plan, note="sorts of the warm-up + timed steps by late-stage plan: 'shifted' = one "
+                                          "shifted merge replaced stages >= 'stage' (device-side certificate held), 'per_stage' = it "
+                                          "failed and the per-stage passes ran; bit-identical arrangement either way")
+    if not args.full:
+        # a plain run is repeated for every change: it stops at the headline, everything below takes runs of its own
+        print(json.dumps(out), flush=True)
+        return
 
-    # roofline: the SAME window once more on a fresh handle, now with a HIP event at every pass boundary
-    # (they serialise the kernel boundaries and cost ~1 %, which is why the headline window runs without them)
-    ms_profiled, per_pass = run_window(make_sim, tick, args.warmup, args.steps, n, alg_bytes)
+    xw, xs = min(args.warmup, FULL_WARMUP), min(args.steps, FULL_STEPS)
+    x_window = f"steps {xw}..{xw + xs} from the lattice"
+    # roofline: the same window (or its start, see FULL_STEPS) once more on a fresh handle, now with a HIP event at every
+    # pass boundary (they serialise the kernel boundaries and cost ~1 %, which is why the headline window runs without them)
+    ms_profiled, per_pass = run_window(make_sim, tick, xw, xs, n, alg_bytes)
     # the dominant pass = the longest event interval of THIS run (force = the lean kernel + the general one; the per-kernel
     # split of the same command is the committed rocprofv3 summary, profiles/*_kernel_stats.csv)
     dom = max(per_pass, key=lambda k: per_pass[k]["ms"])
@@ -328,7 +389,7 @@ def main():
     roofline = {
         "bound": bound, "kernel": dom + (" (k_force + k_force_general)" if dom == "force" and not is3d else ""),
         "achieved": per_pass[dom]["alg_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "profiled_ms_per_step": round(ms_profiled, 4),
+        "profiled_ms_per_step": round(ms_profiled, 4), "profiled_window": x_window,
         "frac": per_pass[dom]["frac"],
         "traffic": traffic, "traffic_source": traffic_src,
         "alg_bytes_per_particle": alg_bytes[dom],
@@ -345,25 +406,12 @@ def main():
                                   "waves_per_simd": crow.get("waves_per_simd"), "lds_busy_frac": crow.get("lds_busy_frac"),
                                   "wait_frac": crow.get("wait_frac"), "kernel": crow.get("kernel"),
                                   "source": crow.get("source") or counters.get("source")}
-    out = {
-        "metric": "M particle-steps/s", "value": round(value, 2), "unit": "M particle-steps/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": args.workload, "particles": n, "scene": "SURVEY.md §8d " + ("dam_break_3d (no reference counterpart)" if is3d else "dam_break_2d"),
-                   "sort": args.sort, "ref_quirks": not is3d, "parallelism": "1 GPU",
-                   "window": f"steps {args.warmup}..{args.warmup + args.steps} from the lattice (see alt_windows for later regimes)"},
-        "host_wall_ms_per_step": round(t_wall / args.steps, 4),
-        "roofline": roofline,
-    }
-    if sort_plan is not None:
-        out["config"]["sort_plan"] = dict(sort_plan, note="sorts of the warm-up + timed steps by late-stage plan: 'shifted' = one "
-                                          "shifted merge replaced stages >= 'stage' (device-side certificate held), 'per_stage' = it "
-                                          "failed and the per-stage passes ran; bit-identical arrangement either way")
+    out["roofline"] = roofline
     if not is3d and args.sort == "bitonic" and not args.no_alt:
         # extras (NOT the headline): the same scene and protocol in the engine's opt-in modes
         def alt_run(**kw):
             mk = lambda: g.FluidSimulation(st, device=local_rank, initial_offset=off, **kw)
-            t, _ = run_window(mk, tick, args.warmup, args.steps, n, alg_bytes, profiled=False)
+            t, _ = run_window(mk, tick, xw, xs, n, alg_bytes, profiled=False)
             return {"value": round(n / (t * 1e-3) / 1e6, 2), "unit": "M particle-steps/s", "ms_per_step": round(t, 4)}
         out["alt_modes"] = {
             "counting_sort": dict(alt_run(sort_mode=g.FS_SORT_COUNTING),
@@ -378,6 +426,7 @@ def main():
                                         "1/rho precomputed): within rtol 1e-5 / atol 1e-4*h of the IEEE oracle per step, cell keys and "
                                         "start_indices bit-exact (north_star's float contract); reference sort"),
             "counting_sort+tolerance_math": alt_run(sort_mode=g.FS_SORT_COUNTING, math_mode=g.FS_MATH_TOLERANCE),
+            "window": x_window,
         }
         # the same strict engine over later windows of the same scene: the block stays a near lattice for the
         # first ~25 steps; by step 100 it is disordered, from step ~150 the bottom of the column is dense
