@@ -126,7 +126,7 @@ class FluidSimulation:
     """FluidSimulation (src/simulation.rs:10-37) on one MI355X, driven through the C ABI."""
 
     def __init__(self, settings, device=0, sort_mode=FS_SORT_BITONIC, ref_quirks=True, initial_offset=(0.0, 0.0),
-                 capacity=0, math_mode=FS_MATH_IEEE):
+                 capacity=0, math_mode=FS_MATH_IEEE, surface_tension=False):
         self._lib = load_library()
         self._h = C.c_void_p()
         self.settings = settings
@@ -139,6 +139,8 @@ class FluidSimulation:
         opts.initial_offset = Vec2(float(initial_offset[0]), float(initial_offset[1]))
         opts.capacity = int(capacity)
         _check(self._lib, self._lib.fs_create_ex(C.byref(settings), C.byref(opts), C.byref(self._h)))
+        if surface_tension:
+            self.set_surface_tension(True)
 
     @classmethod
     def new(cls, settings, device=0, **kw):
@@ -181,6 +183,21 @@ class FluidSimulation:
         w, h = C.c_uint32(), C.c_uint32()
         _check(self._lib, self._lib.fs_grid_dims(self._h, C.byref(w), C.byref(h)))
         return int(w.value), int(h.value)
+
+    # -- surface tension (build extension, opt-in) ---------
+    def set_surface_tension(self, enable=True):
+        """Colour-field surface tension from the tick's surface_tension_coefficient / _treshold, for the steps after this call."""
+        _check(self._lib, self._lib.fs_set_surface_tension(self._h, 1 if enable else 0))
+
+    @property
+    def surface_tension_enabled(self):
+        return bool(self._lib.fs_surface_tension_enabled(self._h))
+
+    def surface_tension_forces(self):
+        """The last step's surface-tension force per particle, (N, 2) float32 in download_particles() order."""
+        out = np.empty((self.particle_count, 2), dtype=np.float32)
+        _check(self._lib, self._lib.fs_download_surface_tension(self._h, out.ctypes.data_as(C.c_void_p), out.shape[0]))
+        return out
 
     def timed_steps(self, tick_settings, steps):
         ms = C.c_double()

@@ -211,6 +211,9 @@ PROTOTYPES = {
     "fs_profile_enable": (C.c_int, [_P, C.c_int]),
     "fs_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]),
     "fs_timed_steps": (C.c_int, [_P, C.POINTER(TickSettings), C.c_uint32, C.POINTER(C.c_double)]),
+    "fs_set_surface_tension": (C.c_int, [_P, C.c_int]),
+    "fs_surface_tension_enabled": (C.c_int, [_P]),
+    "fs_download_surface_tension": (C.c_int, [_P, _P, C.c_size_t]),
     "fs_export_handle": (C.c_int, [_P, C.c_int, _P]),
     "fs_import_open": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "fs_import_read": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t]),

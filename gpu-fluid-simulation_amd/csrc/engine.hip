@@ -131,6 +131,10 @@ struct fs_sim {
     DevArray<fs_particle> aos;      // lazily allocated 32-byte view
     bool aos_live = false;          // a hand-off is registered: the force pass writes the AoS records itself
     uint32_t aos_tick = 0xFFFFFFFFu;   // tick whose state the AoS view holds (only meaningful with aos_live)
+    // surface tension (build extension; single-domain handles): fs_set_surface_tension
+    DevArray<float2> stf;           // per sorted slot: the last ST step's force (allocated on first enable)
+    bool st_on = false;
+    bool st_valid = false;          // an ST step has been enqueued since create / since ST was last enabled
 
     fsd::ConstDiv div_2h3{}, div_h2{};   // exact constant divisions of the force pass, proven at create
     fsd::ConstDiv div_h{};               // ... and of the cell coordinates (x / h), over the numerators clamped positions give
@@ -204,7 +208,7 @@ struct fs_sim {
     void release() {
         pos.release(); vel.release(); pos_s.release(); vel_s.release(); pred.release(); rho.release(); rho2.release();
         key.release(); safe.release(); fdefer.release(); fwork.release(); bbounds.release(); pairs.release(); sort_dirty.release(); csort.release(); cs.release(); start_ref.release(); tex.release(); work.release();
-        counter.release(); aos.release();
+        counter.release(); aos.release(); stf.release();
         owned.release(); blockcnt.release(); stage.release(); msg_state.release(); slab_counters.release();
         hist.release(); strip.release();
         if (ev_packed) (void)hipEventDestroy(ev_packed);
@@ -470,10 +474,19 @@ fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
     s->rho_in_rho2 = P.fast_math != 2;
     fsd::launch_density(st, P, s->pred.p, s->cs.p, s->start_ref.p, s->pairs.p, s->safe.p, s->rho_in_rho2 ? (float*)nullptr : s->rho.p, s->rho2.p, s->fdefer.p, s->fwork.p, s->counter.p + 4);
     if (prof) FS_HIP(hipEventRecord(ev[4], st));
+    const float2* st_in = nullptr;     // surface tension: its pass runs inside the FS_PASS_FORCE interval of the profile
+    if (s->st_on) {
+        fsd::launch_surface_tension(st, P, s->uniform.surface_tension_coefficient, s->uniform.surface_tension_treshold,
+                                    s->uniform.poly6_kernel_derivative, s->pred.p, s->rho2.p, s->rho_in_rho2 ? nullptr : s->rho.p,
+                                    s->cs.p, s->start_ref.p, s->pairs.p, s->stf.p);
+        st_in = s->stf.p;
+        s->st_valid = true;
+    }
     fsd::launch_force(st, P, pos_by_src ? s->pos.p : s->pos_s.p, s->vel_s.p, s->pred.p, s->rho2.p, s->cs.p, s->start_ref.p, s->pairs.p,
                       s->tex.p, pos_by_src ? s->pos_s.p : s->pos.p, s->vel.p, s->rho.p, s->fdefer.p, s->fwork.p, s->counter.p + 4,
                       s->aos_live ? (void*)s->aos.p : nullptr, s->side, s->ev_fork, s->ev_join,
-                      s->sortp.general_grid(), s->sortp.general_hint(), 0u, prof ? nullptr : s->sortp.flight_event(), s->sortp.quad_entries());
+                      s->sortp.general_grid(), s->sortp.general_hint(), 0u, prof ? nullptr : s->sortp.flight_event(), s->sortp.quad_entries(),
+                      st_in);
     if (pos_by_src) { float2* t = s->pos.p; s->pos.p = s->pos_s.p; s->pos_s.p = t; }   // the spare buffer now holds the state
     if (s->aos_live) s->aos_tick = s->tick;
     if (prof) {
@@ -924,6 +937,33 @@ fs_status fs_render_density(fs_sim* s, const fs_view* view, float* rgba_host) {
     (void)hipFree(dimg);
     if (e != hipSuccess) return fail(FS_ERR_DEVICE, hipGetErrorString(e));
     return FS_OK;
+}
+
+fs_status fs_set_surface_tension(fs_sim* s, int enable) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    if (s->slab) return fail(FS_ERR_UNSUPPORTED, "surface tension: single-domain handles only (not built for slab handles)");
+    if (enable && !s->st_on) {
+        if (!s->stf.p) {
+            FS_HIP(hipSetDevice(s->device));
+            FS_HIP(s->stf.alloc(s->capacity));
+        }
+        s->st_valid = false;        // fs_download_surface_tension waits for a step of this enable
+    }
+    s->st_on = enable != 0;
+    return FS_OK;
+}
+
+int fs_surface_tension_enabled(const fs_sim* s) { return (s && s->st_on) ? 1 : 0; }
+
+fs_status fs_download_surface_tension(fs_sim* s, fs_vec2* dst, size_t n) {
+    if (!s || !dst) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->st_valid) return fail(FS_ERR_INVALID, "surface tension: no step with surface tension since the handle was created or ST was last enabled");
+    if (n != s->n) return fail(FS_ERR_INVALID, "surface tension: n must equal the particle count");
+    FS_HIP(hipSetDevice(s->device));
+    static_assert(sizeof(fs_vec2) == sizeof(float2), "fs_vec2 is two f32");
+    if (n) FS_HIP(hipMemcpyAsync(dst, s->stf.p, n * sizeof(fs_vec2), hipMemcpyDeviceToHost, s->stream));
+    FS_HIP(hipStreamSynchronize(s->stream));
+    return sort_health(s);
 }
 
 fs_status fs_profile_enable(fs_sim* s, int enable) {

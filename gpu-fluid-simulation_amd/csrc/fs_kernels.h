@@ -32,7 +32,15 @@ void launch_force(hipStream_t st, const StepParams& P, const float2* pos_s, cons
                   uint32_t edge_grid = 0 /* != 0: the lean kernel walks only the blocks of the edge columns with this many workgroups */,
                   hipEvent_t done = nullptr /* completes with the LAST launch of the pass (its own completion signal: no marker packet) */,
                   uint32_t quad_entries = 0 /* != 0: the pre-registered list is expected to hold about this many blocks, few enough for
-                                               k_force_quad (four lanes per particle) */);
+                                               k_force_quad (four lanes per particle) */,
+                  const float2* st_in = nullptr /* != nullptr (single-domain handles): the surface-tension force of each sorted slot,
+                                                   launch_surface_tension's output, is added to the force sum (the ST instantiations) */);
+// Surface tension (build extension): st_out[i] = the colour-field CSF force of sorted slot i, from this step's
+// densities (rho2; rho != nullptr: tolerance mode, densities in rho) over the density pass's neighbour walk.  Single-domain handles.
+// cg = poly6_kernel_derivative (24/(pi h^8)); sigma = surface_tension_coefficient, tau = surface_tension_treshold.
+void launch_surface_tension(hipStream_t st, const StepParams& P, float sigma, float tau, float cg, const float2* pred,
+                            const float2* rho2, const float* rho, const uint32_t* cs, const uint32_t* start_ref, const u64* pairs,
+                            float2* st_out);
 // pairs != nullptr: the keys are the high words of the sorted pairs (the state of the last step; launch_reorder with
 // key_s == nullptr does not store them a second time), else `key` (an uploaded state).
 void launch_export_aos(hipStream_t st, uint32_t n, const float2* pos, const float2* pred, const float2* vel,

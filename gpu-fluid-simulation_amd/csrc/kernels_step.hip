@@ -288,6 +288,110 @@ __global__ __launch_bounds__(FS_BLOCK) void k_density_edge(FS_DENSITY_ARGS) {
     }
 }
 
+// ---------------------------------------------------------- surface tension (build extension, NOT in the reference)
+// Continuum surface force (Mueller, Charypar & Gross 2003, §4.4) with the density pass's 2D poly6 kernel
+// W = 4/(pi h^8) (h^2 - r^2)^3, normative statement in DESIGN.md §11.  Per sorted slot i, over the candidates the density pass
+// visits (same rows, same order, the particle itself and the stale-start quirk included), all f32 without contraction:
+//   o = q_j - q_i, r2 = o.o;  skip if r2 > h2;  d = h2 - r2;  w = m / rho_j
+//   n += w * (((Cg d) d) o)                      Cg = 24/(pi h^8): n = sum m/rho_j grad W(q_i - q_j)
+//   L += w * ((Cl d) (3 r2 - h2))                Cl = 48/(pi h^8): the 2D Laplacian -48/(pi h^8)(h^2-r^2)(h^2-3r^2)
+// then |n| = sqrt(n.n) (IEEE) and st = |n| > tau && |n| > 0 ? ((-sigma L) / |n|) n : 0.  The reference's own
+// calculate_surface_tension (compute.wgsl:303-498) is dead code and its gradient vanishes identically.
+// w_j is formed once per staged candidate (with MASS1 it is the density pass's |rho2.y| = RN(1/rho_j)), next to q_j in LDS.
+// One pass after k_density, before the force pass; it reads rho2 / rho and the cell tables and writes st[] only.
+struct StConsts { float h2, cg, cl, sigma, tau; };
+
+__device__ __forceinline__ void st_term(const StConsts& C, float2 me, float2 q, float w, float& nx, float& ny, float& L) {
+    const float ox = q.x - me.x, oy = q.y - me.y;
+    const float r2 = ox * ox + oy * oy;
+    const bool in = !(r2 > C.h2);                   // a NaN candidate is not skipped (the statement's test, as written)
+    const float d = C.h2 - r2;
+    const float k = (C.cg * d) * d;
+    const float lk = (C.cl * d) * ((3.0f * r2) - C.h2);
+    // an accumulator that starts at +0.0f is never -0.0f, so adding +0.0f for a skipped candidate IS skipping it
+    nx += in ? w * (k * ox) : 0.0f;
+    ny += in ? w * (k * oy) : 0.0f;
+    L += in ? w * lk : 0.0f;
+}
+
+template <bool MASS1>
+__device__ __forceinline__ float st_weight(const StepParams& P, const float2* __restrict__ rho2, const float* __restrict__ rho_arr,
+                                           uint32_t j) {
+    if (MASS1) return fabsf(rho2[j].y);             // RN(1/rho_j) == RN(1.0f / rho_j): the sign is the density pass's safe bit
+    return __fdiv_rn(P.mass, rho_arr ? rho_arr[j] : rho2[j].x);   // rho_arr: tolerance mode (rho2 = {pressure, 1/rho})
+}
+
+template <bool MASS1>
+__global__ __launch_bounds__(FS_BLOCK) void k_surface_tension(StepParams P, StConsts C, const float2* __restrict__ pred,
+                                                              const float2* __restrict__ rho2, const float* __restrict__ rho_arr,
+                                                              const uint32_t* __restrict__ cs, const uint32_t* __restrict__ start_ref,
+                                                              const u64* __restrict__ pairs, float2* __restrict__ st_out) {
+    __shared__ float2 s_q[3][NB_TILE];
+    __shared__ float s_w[3][NB_TILE];
+    __shared__ uint32_t s_red[24];
+    const uint32_t n = P.n;
+    uint32_t blk;
+    if (!xcd_block(P, (n + FS_BLOCK - 1) / FS_BLOCK, &blk)) return;   // uniform
+    const uint32_t i = blk * FS_BLOCK + threadIdx.x;
+    const bool live = i < n;
+    const uint32_t lo_fix = quirk_lo_fix(P, pairs, cs, start_ref);
+    const float2 me = pred[live ? i : n - 1];
+    uint32_t cx, cy;
+    int32_t cg;
+    uv_local(P, me, &cx, &cy, &cg);
+    RowRanges R;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        R.lo[r] = 0; R.hi[r] = 0;
+        if (live) (void)row_range(P, cs, cx, cy + (uint32_t)(r - 1), lo_fix, &R.lo[r], &R.hi[r]);
+        if (R.hi[r] < R.lo[r]) R.hi[r] = R.lo[r];
+    }
+    uint32_t blo[3], bhi[3];
+    bool fit;
+    if (P.block_bounds) {       // this step's density pass reduced the same ranges over the same 256 particles
+        const uint32_t* bb = P.block_bounds + 8u * blk;
+        blo[0] = bb[0]; blo[1] = bb[1]; blo[2] = bb[2]; bhi[0] = bb[3]; bhi[1] = bb[4]; bhi[2] = bb[5];
+        fit = bhi[0] - blo[0] <= NB_TILE && bhi[1] - blo[1] <= NB_TILE && bhi[2] - blo[2] <= NB_TILE;
+    } else {
+        fit = block_tile_bounds(R, s_red, blo, bhi, NB_TILE);
+    }
+    float nx = 0.0f, ny = 0.0f, L = 0.0f;
+    if (fit) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            for (uint32_t j = threadIdx.x; j < bhi[r] - blo[r]; j += FS_BLOCK) {
+                s_q[r][j] = pred[blo[r] + j];
+                s_w[r][j] = st_weight<MASS1>(P, rho2, rho_arr, blo[r] + j);
+            }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const bool any = R.lo[r] < R.hi[r];
+            const uint32_t hi = any ? R.hi[r] - blo[r] : 0u;
+            uint32_t k = any ? R.lo[r] - blo[r] : 0u;
+            for (; k + 2u <= hi; k += 2u) {          // two candidates per trip: independent LDS reads, adds in index order
+                const float2 q0 = s_q[r][k], q1 = s_q[r][k + 1u];
+                const float w0 = s_w[r][k], w1 = s_w[r][k + 1u];
+                st_term(C, me, q0, w0, nx, ny, L);
+                st_term(C, me, q1, w1, nx, ny, L);
+            }
+            if (k < hi) st_term(C, me, s_q[r][k], s_w[r][k], nx, ny, L);
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            for (uint32_t k = R.lo[r]; k < R.hi[r]; ++k) st_term(C, me, pred[k], st_weight<MASS1>(P, rho2, rho_arr, k), nx, ny, L);
+    }
+    if (!live) return;
+    const float nl = sqrt_rn(nx * nx + ny * ny);
+    float2 f = make_float2(0.0f, 0.0f);
+    if (nl > C.tau && nl > 0.0f) {
+        const float sc = __fdiv_rn(-C.sigma * L, nl);
+        f = make_float2(sc * nx, sc * ny);
+    }
+    st_out[i] = f;
+}
+
 // ---------------------------------------------------------- force + integrate
 // Two phases per lane so the expensive body (pressure + viscosity terms of one in-radius neighbour)
 // runs with dense lanes:
@@ -706,19 +810,26 @@ __device__ __forceinline__ bool force_sweep_masks(const StepParams& P, const Row
 struct AosParticle { float2 position, predicted, velocity; float density; uint32_t grid; };   // ParticleInstance, 32 B
 
 // Integration of one particle from its accumulated force sums (compute.wgsl:93-153, :298) and the stores of its new state.
-template <int MODE, bool AOS>
+// ST (compile-time, single-domain handles with fs_set_surface_tension on): the surface-tension force k_surface_tension wrote for
+// this sorted slot is added to the force sum, `ax = (fp.x + fv.x) + st.x`; nothing else changes.
+template <int MODE, bool AOS, bool ST = false>
 __device__ __forceinline__ void integrate_store(const StepParams& P, uint32_t i, const float2 me, const float2 mv, const float2 mrec,
                                                 float mrho, const float2 p_own, const ForceAcc& A, uint32_t cx, uint32_t cy,
                                                 const float2* __restrict__ tex, float2* __restrict__ pos_out,
                                                 float2* __restrict__ vel_out, AosParticle* __restrict__ aos_out,
-                                                const float* __restrict__ rho_arr) {
+                                                const float* __restrict__ rho_arr, const float2* __restrict__ st_in) {
     const float fvx = A.fvx * P.visc_coeff;                             // compute.wgsl:298
     const float fvy = A.fvy * P.visc_coeff;
 
     // integrate (compute.wgsl:93-153)
     float2 v = mv;
     float2 p = p_own;
-    const float ax = A.fpx + fvx, ay = A.fpy + fvy;
+    float ax = A.fpx + fvx, ay = A.fpy + fvy;
+    if (ST) {
+        const float2 fs = st_in[i];
+        ax = ax + fs.x;
+        ay = ay + fs.y;
+    }
     if (MODE == 2) {
         v.x = __builtin_fmaf(ax * mrec.y, P.dt, v.x);
         v.y = __builtin_fmaf(ay * mrec.y, P.dt, v.y);
@@ -805,7 +916,7 @@ __device__ __forceinline__ void integrate_store(const StepParams& P, uint32_t i,
 // spilled, force 0.72 -> 0.67 ms at 16M (profiles/r02_c_force_split.txt).
 // defer_bits[2 blk] / worklist[0 .. nblk) / work_count[0]: waves named by k_density before the launch ("pre");
 // defer_bits[2 blk + 1] / worklist[nblk ..) / work_count[1]: waves the lean path gives up on itself ("late").
-template <int MODE, bool AOS, bool GENERAL>
+template <int MODE, bool AOS, bool GENERAL, bool ST>
 __device__ __forceinline__ void force_block(const StepParams& P, uint32_t blk, uint32_t n, uint32_t wave_bits,
                                             const float2* __restrict__ pos_s, const float2* __restrict__ vel_s,
                                             const float2* __restrict__ pred, const float2* __restrict__ rho2,
@@ -814,8 +925,8 @@ __device__ __forceinline__ void force_block(const StepParams& P, uint32_t blk, u
                                             float2* __restrict__ pos_out, float2* __restrict__ vel_out,
                                             AosParticle* __restrict__ aos_out, const float* __restrict__ rho_arr,
                                             uint32_t* __restrict__ defer_bits, uint32_t* __restrict__ worklist,
-                                            uint32_t* __restrict__ work_count, float2 (*s_pred)[NBF_ROW],
-                                            uint32_t* s_red) {
+                                            uint32_t* __restrict__ work_count, const float2* __restrict__ st_in,
+                                            float2 (*s_pred)[NBF_ROW], uint32_t* s_red) {
     const uint32_t tid = threadIdx.x;
     const uint32_t i = blk * FS_BLOCK + tid;
     bool live = i < n;
@@ -888,7 +999,7 @@ __device__ __forceinline__ void force_block(const StepParams& P, uint32_t blk, u
         return;
     }
     if (!live) return;
-    integrate_store<MODE, AOS>(P, i, me, mv, mrec, mrho, p_own, A, cx, cy, tex, pos_out, vel_out, aos_out, rho_arr);
+    integrate_store<MODE, AOS, ST>(P, i, me, mv, mrec, mrho, p_own, A, cx, cy, tex, pos_out, vel_out, aos_out, rho_arr, st_in);
 }
 
 // Slab ranks with column-major cell ids (StepParams::transposed): a block's 256 consecutive sorted particles span the cell
@@ -911,26 +1022,29 @@ __device__ __forceinline__ bool block_may_advance(const StepParams& P, const u64
         const u64* __restrict__ pairs, const float2* __restrict__ tex, float2* __restrict__ pos_out,                   \
         float2* __restrict__ vel_out, AosParticle* __restrict__ aos_out, const float* __restrict__ rho_arr,            \
         uint32_t* __restrict__ defer_bits, uint32_t* __restrict__ worklist, uint32_t* __restrict__ work_count
+// (the ST instantiations' input, the per-slot surface-tension force, is each kernel's LAST argument: the other arguments keep
+// their kernarg offsets)
 
 // Lean main kernel: every block once — mask sweep + shared reciprocals only, skipping the waves k_density
 // pre-registered.  (Folding the general workgroups into this launch was tried: the kernel then carries the general
 // body's spills and scratch set-up and the strict lean path ran 1.7x slower; two kernels on two streams instead.)
-template <int MODE, bool AOS>
-__global__ __launch_bounds__(FS_BLOCK) __attribute__((amdgpu_waves_per_eu(FS_FORCE_WAVES, FS_FORCE_WAVES))) void k_force(FS_FORCE_ARGS, uint32_t which) {
+template <int MODE, bool AOS, bool ST>
+__global__ __launch_bounds__(FS_BLOCK) __attribute__((amdgpu_waves_per_eu(FS_FORCE_WAVES, FS_FORCE_WAVES))) void k_force(FS_FORCE_ARGS, uint32_t which, const float2* __restrict__ st_in) {
     __shared__ float2 s_pred[3][NBF_ROW];
     __shared__ uint32_t s_red[24];
     const uint32_t n = P.n_live ? *P.n_live : P.n;
     uint32_t blk;
     if (!xcd_block(P, (n + FS_BLOCK - 1) / FS_BLOCK, &blk)) return;   // uniform: no live particle in this block
     if (!block_may_advance(P, pairs, blk, n)) return;                 // uniform: none of its columns belongs to this launch
-    force_block<MODE, AOS, false>(P, blk, n, defer_bits[2u * blk], pos_s, vel_s, pred, rho2, cs, start_ref, pairs, tex,
-                                  pos_out, vel_out, aos_out, rho_arr, defer_bits, worklist, work_count, s_pred, s_red);
+    force_block<MODE, AOS, false, ST>(P, blk, n, defer_bits[2u * blk], pos_s, vel_s, pred, rho2, cs, start_ref, pairs, tex,
+                                      pos_out, vel_out, aos_out, rho_arr, defer_bits, worklist, work_count, st_in, s_pred, s_red);
 }
 
 // Edge-first slab step, column-major ids: the lean kernel over the blocks that hold the edge columns only (fs_device.h
 // EdgeBlocks), a small fixed grid walking them.
-template <int MODE, bool AOS>
-__global__ __launch_bounds__(FS_BLOCK) __attribute__((amdgpu_waves_per_eu(FS_FORCE_WAVES, FS_FORCE_WAVES))) void k_force_edge(FS_FORCE_ARGS, uint32_t which) {
+template <int MODE, bool AOS, bool ST>
+__global__ __launch_bounds__(FS_BLOCK) __attribute__((amdgpu_waves_per_eu(FS_FORCE_WAVES, FS_FORCE_WAVES))) void k_force_edge(FS_FORCE_ARGS, uint32_t which, const float2* __restrict__ st_in) {
+    static_assert(!ST, "surface tension: single-domain handles only");
     __shared__ float2 s_pred[3][NBF_ROW];
     __shared__ uint32_t s_red[24];
     const uint32_t n = *P.n_live;
@@ -938,8 +1052,8 @@ __global__ __launch_bounds__(FS_BLOCK) __attribute__((amdgpu_waves_per_eu(FS_FOR
     for (uint32_t t = blockIdx.x; t < edge_block_count(E); t += gridDim.x) {
         const uint32_t blk = edge_block_at(E, t);
         if (block_may_advance(P, pairs, blk, n))         // uniform (the ghost columns' blocks at the very ends)
-            force_block<MODE, AOS, false>(P, blk, n, defer_bits[2u * blk], pos_s, vel_s, pred, rho2, cs, start_ref, pairs, tex,
-                                          pos_out, vel_out, aos_out, rho_arr, defer_bits, worklist, work_count, s_pred, s_red);
+            force_block<MODE, AOS, false, false>(P, blk, n, defer_bits[2u * blk], pos_s, vel_s, pred, rho2, cs, start_ref, pairs, tex,
+                                                 pos_out, vel_out, aos_out, rho_arr, defer_bits, worklist, work_count, st_in, s_pred, s_red);
         __syncthreads();                                 // the LDS stage is reused
     }
 }
@@ -955,8 +1069,8 @@ __global__ __launch_bounds__(FS_BLOCK) __attribute__((amdgpu_waves_per_eu(FS_FOR
 #ifndef FS_GENERAL_WAVES
 #define FS_GENERAL_WAVES 5
 #endif
-template <int MODE, bool AOS>
-__global__ __launch_bounds__(FS_BLOCK) __attribute__((amdgpu_waves_per_eu(FS_GENERAL_WAVES, FS_GENERAL_WAVES))) void k_force_general(FS_FORCE_ARGS, uint32_t which, uint32_t* __restrict__ hint) {
+template <int MODE, bool AOS, bool ST>
+__global__ __launch_bounds__(FS_BLOCK) __attribute__((amdgpu_waves_per_eu(FS_GENERAL_WAVES, FS_GENERAL_WAVES))) void k_force_general(FS_FORCE_ARGS, uint32_t which, uint32_t* __restrict__ hint, const float2* __restrict__ st_in) {
     __shared__ float2 s_pred[3][NBF_ROW];
     __shared__ uint32_t s_red[24];
     const uint32_t n = P.n_live ? *P.n_live : P.n;
@@ -979,9 +1093,9 @@ __global__ __launch_bounds__(FS_BLOCK) __attribute__((amdgpu_waves_per_eu(FS_GEN
             const uint32_t blk = list[e];
             if (!block_may_advance(P, pairs, blk, n)) continue;          // uniform
             const uint32_t bits = defer_bits[2u * blk + w];
-            force_block<MODE, AOS, true>(P, blk, n, bits, pos_s, vel_s, pred, rho2, cs, start_ref, pairs,
-                                         tex, pos_out, vel_out, aos_out, rho_arr, defer_bits, worklist, work_count, s_pred,
-                                         s_red);
+            force_block<MODE, AOS, true, ST>(P, blk, n, bits, pos_s, vel_s, pred, rho2, cs, start_ref, pairs,
+                                             tex, pos_out, vel_out, aos_out, rho_arr, defer_bits, worklist, work_count, st_in, s_pred,
+                                             s_red);
             __syncthreads();                         // the LDS stage is reused by the next entry
         }
     }
@@ -1012,8 +1126,8 @@ __device__ __forceinline__ void mask64_clear_top(uint32_t& hi, uint32_t& lo) {
     const uint32_t bit = t ? 0x80000000u >> __builtin_clz(t) : 0u;
     if (hi) hi ^= bit; else lo ^= bit;
 }
-template <int MODE, bool AOS>
-__global__ __launch_bounds__(FS_BLOCK) void k_force_quad(FS_FORCE_ARGS, uint32_t* __restrict__ hint) {
+template <int MODE, bool AOS, bool ST>
+__global__ __launch_bounds__(FS_BLOCK) void k_force_quad(FS_FORCE_ARGS, uint32_t* __restrict__ hint, const float2* __restrict__ st_in) {
     constexpr bool FAST = MODE == 1;
     const uint32_t n = P.n_live ? *P.n_live : P.n;
     const uint32_t count = work_count[0];                // written by k_density earlier in the stream
@@ -1135,7 +1249,7 @@ __global__ __launch_bounds__(FS_BLOCK) void k_force_quad(FS_FORCE_ARGS, uint32_t
             continue;
         }
         if (live && l == 0u)
-            integrate_store<MODE, AOS>(P, i, me, mv, mrec, mrho, p_own, A, cx, cy, tex, pos_out, vel_out, aos_out, rho_arr);
+            integrate_store<MODE, AOS, ST>(P, i, me, mv, mrec, mrho, p_own, A, cx, cy, tex, pos_out, vel_out, aos_out, rho_arr, st_in);
     }
 }
 
@@ -1318,22 +1432,45 @@ void launch_density(hipStream_t st, const StepParams& P, const float2* pred, con
 #undef FS_LAUNCH_DENSITY
 }
 
+void launch_surface_tension(hipStream_t st, const StepParams& P, float sigma, float tau, float cg, const float2* pred,
+                            const float2* rho2, const float* rho, const uint32_t* cs, const uint32_t* start_ref, const u64* pairs,
+                            float2* st_out) {
+    if (P.n == 0) return;
+    StConsts C;
+    C.h2 = P.sqr_radius;
+    C.cg = cg;
+    C.cl = 2.0f * cg;                                 // 48/(pi h^8): x2 is exact
+    C.sigma = sigma;
+    C.tau = tau;
+    const uint32_t grid = xcd_grid(nblk(P.n), P.xcd_chunk_log2);
+    if (P.mass == 1.0f && !rho)
+        hipLaunchKernelGGL(k_surface_tension<true>, dim3(grid), dim3(FS_BLOCK), 0, st, P, C, pred, rho2, rho, cs, start_ref, pairs, st_out);
+    else
+        hipLaunchKernelGGL(k_surface_tension<false>, dim3(grid), dim3(FS_BLOCK), 0, st, P, C, pred, rho2, rho, cs, start_ref, pairs, st_out);
+}
+
 void launch_force(hipStream_t st, const StepParams& P, const float2* pos_s, const float2* vel_s, const float2* pred,
                   const float2* rho2, const uint32_t* cs, const uint32_t* start_ref, const u64* pairs, const float2* tex,
                   float2* pos_out, float2* vel_out, const float* rho_arr, uint32_t* defer_bits, uint32_t* worklist,
                   uint32_t* work_count, void* aos_out, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join,
-                  uint32_t general_grid, uint32_t* general_hint, uint32_t edge_grid, hipEvent_t done, uint32_t quad_entries) {
+                  uint32_t general_grid, uint32_t* general_hint, uint32_t edge_grid, hipEvent_t done, uint32_t quad_entries,
+                  const float2* st_in) {
     const uint32_t nb = nblk(P.n), grid = xcd_grid(nb, P.xcd_chunk_log2);
     hipEvent_t stop_ev = nullptr;      // set for the pass's last launch only
-#define FS_LAUNCH_FORCE(K, M, A, G, S, ...)                                                                         \
-    hipExtLaunchKernelGGL((K<M, A>), dim3(G), dim3(FS_BLOCK), 0, S, nullptr, stop_ev, 0, P, pos_s, vel_s, pred, rho2, cs, start_ref, pairs, tex, \
-                       pos_out, vel_out, (AosParticle*)aos_out, rho_arr, defer_bits, worklist, work_count, __VA_ARGS__)
-#define FS_LAUNCH_FORCE_MODE(K, G, S, ...)                                                                          \
+#define FS_LAUNCH_FORCE(K, M, A, T, G, S, ...)                                                                      \
+    hipExtLaunchKernelGGL((K<M, A, T>), dim3(G), dim3(FS_BLOCK), 0, S, nullptr, stop_ev, 0, P, pos_s, vel_s, pred, rho2, cs, start_ref, pairs, tex, \
+                       pos_out, vel_out, (AosParticle*)aos_out, rho_arr, defer_bits, worklist, work_count, __VA_ARGS__, st_in)
+#define FS_LAUNCH_FORCE_AOS(K, M, T, G, S, ...)                                                                     \
+    do { if (aos_out) FS_LAUNCH_FORCE(K, M, true, T, G, S, __VA_ARGS__); else FS_LAUNCH_FORCE(K, M, false, T, G, S, __VA_ARGS__); } while (0)
+#define FS_LAUNCH_FORCE_MODE_T(K, T, G, S, ...)                                                                     \
     do {                                                                                                            \
-        if (P.fast_math == 2) { if (aos_out) FS_LAUNCH_FORCE(K, 2, true, G, S, __VA_ARGS__); else FS_LAUNCH_FORCE(K, 2, false, G, S, __VA_ARGS__); } \
-        else if (P.fast_math == 1) { if (aos_out) FS_LAUNCH_FORCE(K, 1, true, G, S, __VA_ARGS__); else FS_LAUNCH_FORCE(K, 1, false, G, S, __VA_ARGS__); } \
-        else { if (aos_out) FS_LAUNCH_FORCE(K, 0, true, G, S, __VA_ARGS__); else FS_LAUNCH_FORCE(K, 0, false, G, S, __VA_ARGS__); }      \
+        if (P.fast_math == 2) FS_LAUNCH_FORCE_AOS(K, 2, T, G, S, __VA_ARGS__);                                      \
+        else if (P.fast_math == 1) FS_LAUNCH_FORCE_AOS(K, 1, T, G, S, __VA_ARGS__);                                 \
+        else FS_LAUNCH_FORCE_AOS(K, 0, T, G, S, __VA_ARGS__);                                                       \
     } while (0)
+    // the surface-tension instantiations (ST) are chosen here, like AOS: st_in != nullptr only on single-domain handles
+#define FS_LAUNCH_FORCE_MODE(K, G, S, ...)                                                                          \
+    do { if (st_in) FS_LAUNCH_FORCE_MODE_T(K, true, G, S, __VA_ARGS__); else FS_LAUNCH_FORCE_MODE_T(K, false, G, S, __VA_ARGS__); } while (0)
 #ifndef FS_GENERAL_GRID
 #define FS_GENERAL_GRID 4080u   // 16M, steps 150-250: force 1.175 (1024) -> 1.126 (2048) -> 1.117 ms (4096); steps 10-110 unchanged
 #endif
@@ -1345,7 +1482,7 @@ void launch_force(hipStream_t st, const StepParams& P, const float2* pos_s, cons
         FS_LAUNCH_FORCE_MODE(k_force_general, gg, side, 0u, (uint32_t*)nullptr);
         (void)hipEventRecord(ev_join, side);
     }
-    if (edge_grid) FS_LAUNCH_FORCE_MODE(k_force_edge, edge_grid, st, 0u);      // edge-first slab step: the edge columns' blocks only
+    if (edge_grid) FS_LAUNCH_FORCE_MODE_T(k_force_edge, false, edge_grid, st, 0u);      // edge-first slab step: the edge columns' blocks only
     else FS_LAUNCH_FORCE_MODE(k_force, grid, st, 0u);
     if (side) {
         (void)hipStreamWaitEvent(st, ev_join, 0);
@@ -1364,6 +1501,8 @@ void launch_force(hipStream_t st, const StepParams& P, const float2* pos_s, cons
         FS_LAUNCH_FORCE_MODE(k_force_general, gg, st, 2u, general_hint);      // both lists in one follow-up launch
     }
 #undef FS_LAUNCH_FORCE_MODE
+#undef FS_LAUNCH_FORCE_MODE_T
+#undef FS_LAUNCH_FORCE_AOS
 #undef FS_LAUNCH_FORCE
 }
 

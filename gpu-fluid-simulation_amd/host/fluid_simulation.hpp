@@ -87,6 +87,14 @@ public:
         return v;
     }
     void upload(const std::vector<ParticleInstance>& v) { check(fs_upload_particles(h_, v.data(), v.size())); }
+    // Build extension, NOT in the reference: colour-field surface tension (include/fluidsim.h), single-domain handles.
+    void set_surface_tension(bool enable) { check(fs_set_surface_tension(h_, enable ? 1 : 0)); }
+    bool surface_tension_enabled() const { return fs_surface_tension_enabled(h_) != 0; }
+    std::vector<fs_vec2> surface_tension_forces() {
+        std::vector<fs_vec2> v(particle_count());
+        check(fs_download_surface_tension(h_, v.data(), v.size()));
+        return v;
+    }
     fs_sim* handle() { return h_; }
 
 private:

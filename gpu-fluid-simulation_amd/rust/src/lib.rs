@@ -145,6 +145,10 @@ extern "C" {
     fn fs_profile_enable(sim: *mut fs_sim, enable: c_int) -> c_int;
     fn fs_profile_read(sim: *mut fs_sim, ms: *mut f64, steps: *mut u64, reset: c_int) -> c_int;
     fn fs_timed_steps(sim: *mut fs_sim, tick: *const TickSettings, steps: u32, ms_total: *mut f64) -> c_int;
+    // surface tension (build extension, opt-in)
+    fn fs_set_surface_tension(sim: *mut fs_sim, enable: c_int) -> c_int;
+    fn fs_surface_tension_enabled(sim: *const fs_sim) -> c_int;
+    fn fs_download_surface_tension(sim: *mut fs_sim, dst: *mut Vec2, n: usize) -> c_int;
     // multi-GPU slab mode
     fn fs_slab_create(global_settings: *const SimulationSettings, device: c_int, cfg: *const SlabConfig, out: *mut *mut fs_sim) -> c_int;
     fn fs_slab_upload_owned(sim: *mut fs_sim, src: *const ParticleInstance, n: usize) -> c_int;
@@ -278,6 +282,15 @@ impl FluidSimulation {
         check(unsafe { fs_download_particles(self.raw, v.as_mut_ptr(), v.len()) }); v
     }
     pub fn upload_particles(&mut self, src: &[ParticleInstance]) { check(unsafe { fs_upload_particles(self.raw, src.as_ptr(), src.len()) }); }
+    /// Build extension, NOT in the reference: colour-field surface tension from the tick's surface_tension_* knobs
+    /// (include/fluidsim.h), for the steps enqueued after this call.  Single-domain handles.
+    pub fn set_surface_tension(&mut self, enable: bool) { check(unsafe { fs_set_surface_tension(self.raw, enable as c_int) }); }
+    pub fn surface_tension_enabled(&self) -> bool { unsafe { fs_surface_tension_enabled(self.raw) != 0 } }
+    /// The last step's surface-tension force per particle, in `download_particles` order.
+    pub fn surface_tension_forces(&mut self) -> Vec<Vec2> {
+        let mut v = vec![Vec2 { x: 0.0, y: 0.0 }; self.particle_count() as usize];
+        check(unsafe { fs_download_surface_tension(self.raw, v.as_mut_ptr(), v.len()) }); v
+    }
     /// `start_indices` to the host (the renderer's second storage binding; u32[grid_w * grid_h]).
     pub fn download_start_indices(&mut self) -> Vec<u32> {
         let (w, h) = self.grid_dims();

@@ -268,6 +268,27 @@ fs_status fs_profile_read(fs_sim* sim, double ms[FS_PASS_COUNT], uint64_t* steps
 /* Time `steps` consecutive fs_step calls with one hipEvent pair on the stream. */
 fs_status fs_timed_steps(fs_sim* sim, const fs_tick_settings* tick, uint32_t steps, double* ms_total);
 
+/* ------------------------------------------------ surface tension (build extension, opt-in) */
+/* NOT in the reference: its calculate_surface_tension (compute.wgsl:303-498) is dead code whose gradient is identically
+ * zero.  Enabled, every step runs a colour-field continuum-surface-force pass (Mueller, Charypar & Gross 2003, §4.4) with
+ * the density pass's 2D poly6 kernel, after the density pass and before the force pass, and move_particle adds its force:
+ * ax = (fp.x + fv.x) + st.x.  For sorted slot i with predicted position x, over the neighbours j the density pass visits
+ * (same cells, same order, same start-index rules, i itself included), in f32 without contraction:
+ *     o = q_j - x, r2 = o.o, skipped when r2 > h2;  d = h2 - r2;  w = m / rho_j (this step's clamped density)
+ *     n += w * (((Cg*d)*d) * o)          Cg = poly6_kernel_derivative = 24/(pi h^8)
+ *     L += w * ((Cl*d) * (3*r2 - h2))    Cl = 2 Cg
+ *     |n| = sqrt(n.n);  st = (|n| > surface_tension_treshold && |n| > 0) ? ((-surface_tension_coefficient * L) / |n|) n : 0
+ * Bit-exact in FS_MATH_IEEE; the other math modes keep their per-step contract.  Off by default (the knobs alone change
+ * nothing).  Single-domain 2D handles only: a slab handle gets FS_ERR_UNSUPPORTED.  The pass's time falls inside the
+ * FS_PASS_FORCE interval of fs_profile_read.  See DESIGN.md §11.
+ * fs_set_surface_tension: takes effect for steps enqueued after the call (the first enable allocates 8 B per particle).
+ * fs_download_surface_tension: the last step's st, one fs_vec2 per particle in fs_download_particles' slot order; n must equal
+ * the particle count.  FS_ERR_INVALID when no step with surface tension has been enqueued since the handle was created or
+ * since surface tension was last enabled.  Blocking. */
+fs_status fs_set_surface_tension(fs_sim* sim, int enable);
+int fs_surface_tension_enabled(const fs_sim* sim);
+fs_status fs_download_surface_tension(fs_sim* sim, fs_vec2* dst, size_t n);
+
 /* ------------------------------------------------ multi-GPU slab mode (build extension) */
 /* NOT in the reference (single wgpu device, src/renderer.rs:108-133).  SURVEY.md §8e: a rank
  * owns the global cell columns [own_lo, own_hi) of the grid (src/simulation.rs:140-141) and
