@@ -126,7 +126,7 @@ class FluidSimulation:
     """FluidSimulation (src/simulation.rs:10-37) on one MI355X, driven through the C ABI."""
 
     def __init__(self, settings, device=0, sort_mode=FS_SORT_BITONIC, ref_quirks=True, initial_offset=(0.0, 0.0),
-                 capacity=0, math_mode=FS_MATH_IEEE, surface_tension=False):
+                 capacity=0, math_mode=FS_MATH_IEEE, surface_tension=False, track=None):
         self._lib = load_library()
         self._h = C.c_void_p()
         self.settings = settings
@@ -141,6 +141,8 @@ class FluidSimulation:
         _check(self._lib, self._lib.fs_create_ex(C.byref(settings), C.byref(opts), C.byref(self._h)))
         if surface_tension:
             self.set_surface_tension(True)
+        if track is not None:
+            self.track(track)
 
     @classmethod
     def new(cls, settings, device=0, **kw):
@@ -198,6 +200,58 @@ class FluidSimulation:
         out = np.empty((self.particle_count, 2), dtype=np.float32)
         _check(self._lib, self._lib.fs_download_surface_tension(self._h, out.ctypes.data_as(C.c_void_p), out.shape[0]))
         return out
+
+    # -- particle tracking (build extension, opt-in) --------
+    def track(self, channels=0):
+        """Give every particle an id (= its current slot) and `channels` float attributes (all 0) that follow it through the
+        sort of every later step.  Calling it again re-initialises."""
+        _check(self._lib, self._lib.fs_track_enable(self._h, int(channels)))
+
+    def untrack(self):
+        _check(self._lib, self._lib.fs_track_disable(self._h))
+
+    @property
+    def track_channels(self):
+        """-1 when tracking is off, else the number of attribute channels."""
+        return int(self._lib.fs_track_channels(self._h))
+
+    def particle_ids(self):
+        """uint32 id of the particle in every slot, in download_particles() order."""
+        out = np.empty(self.particle_count, dtype=np.uint32)
+        _check(self._lib, self._lib.fs_track_download_ids(self._h, out.ctypes.data_as(C.c_void_p), out.shape[0]))
+        return out
+
+    def set_particle_ids(self, ids):
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        _check(self._lib, self._lib.fs_track_upload_ids(self._h, ids.ctypes.data_as(C.c_void_p), ids.shape[0]))
+
+    def attribute(self, channel):
+        """float32 attribute `channel` of the particle in every slot, in download_particles() order."""
+        out = np.empty(self.particle_count, dtype=np.float32)
+        _check(self._lib, self._lib.fs_track_download_attr(self._h, int(channel), out.ctypes.data_as(C.c_void_p), out.shape[0]))
+        return out
+
+    def set_attribute(self, channel, values):
+        """`values` is copied bit for bit when it already is float32 (NaN payloads survive)."""
+        values = np.ascontiguousarray(values, dtype=np.float32)
+        _check(self._lib, self._lib.fs_track_upload_attr(self._h, int(channel), values.ctypes.data_as(C.c_void_p), values.shape[0]))
+
+    def download_particles_by_id(self):
+        """The records in id order: out[id] is the particle with that id (ids >= particle_count are skipped; entries that no
+        id names stay zero)."""
+        out = np.zeros(self.particle_count, dtype=PARTICLE_DTYPE)
+        _check(self._lib, self._lib.fs_download_particles_by_id(self._h, out.ctypes.data_as(C.c_void_p), out.shape[0]))
+        return out
+
+    def particle_ids_device_ptr(self):
+        p = C.c_void_p()
+        _check(self._lib, self._lib.fs_track_ids_device(self._h, C.byref(p)))
+        return p.value
+
+    def attribute_device_ptr(self, channel):
+        p = C.c_void_p()
+        _check(self._lib, self._lib.fs_track_attr_device(self._h, int(channel), C.byref(p)))
+        return p.value
 
     def timed_steps(self, tick_settings, steps):
         ms = C.c_double()

@@ -214,6 +214,16 @@ PROTOTYPES = {
     "fs_set_surface_tension": (C.c_int, [_P, C.c_int]),
     "fs_surface_tension_enabled": (C.c_int, [_P]),
     "fs_download_surface_tension": (C.c_int, [_P, _P, C.c_size_t]),
+    "fs_track_enable": (C.c_int, [_P, C.c_int]),
+    "fs_track_disable": (C.c_int, [_P]),
+    "fs_track_channels": (C.c_int, [_P]),
+    "fs_track_download_ids": (C.c_int, [_P, _P, C.c_size_t]),
+    "fs_track_upload_ids": (C.c_int, [_P, _P, C.c_size_t]),
+    "fs_track_download_attr": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
+    "fs_track_upload_attr": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
+    "fs_track_ids_device": (C.c_int, [_P, C.POINTER(_P)]),
+    "fs_track_attr_device": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
+    "fs_download_particles_by_id": (C.c_int, [_P, _P, C.c_size_t]),
     "fs_export_handle": (C.c_int, [_P, C.c_int, _P]),
     "fs_import_open": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "fs_import_read": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t]),

@@ -135,6 +135,13 @@ struct fs_sim {
     DevArray<float2> stf;           // per sorted slot: the last ST step's force (allocated on first enable)
     bool st_on = false;
     bool st_valid = false;          // an ST step has been enqueued since create / since ST was last enabled
+    // particle tracking (build extension; single-domain handles): fs_track_enable.  Two sets that swap roles
+    // every step: [trk_cur] holds the ids / channels in the order of the last enqueued step.  Channel c: trk_attr[..] + c * capacity.
+    DevArray<uint32_t> trk_id[2];
+    DevArray<float> trk_attr[2];
+    int trk_channels = -1;          // -1: off
+    int trk_alloc_channels = 0;     // channels the attr arrays were allocated for
+    int trk_cur = 0;
 
     fsd::ConstDiv div_2h3{}, div_h2{};   // exact constant divisions of the force pass, proven at create
     fsd::ConstDiv div_h{};               // ... and of the cell coordinates (x / h), over the numerators clamped positions give
@@ -209,6 +216,7 @@ struct fs_sim {
         pos.release(); vel.release(); pos_s.release(); vel_s.release(); pred.release(); rho.release(); rho2.release();
         key.release(); safe.release(); fdefer.release(); fwork.release(); bbounds.release(); pairs.release(); sort_dirty.release(); csort.release(); cs.release(); start_ref.release(); tex.release(); work.release();
         counter.release(); aos.release(); stf.release();
+        trk_id[0].release(); trk_id[1].release(); trk_attr[0].release(); trk_attr[1].release();
         owned.release(); blockcnt.release(); stage.release(); msg_state.release(); slab_counters.release();
         hist.release(); strip.release();
         if (ev_packed) (void)hipEventDestroy(ev_packed);
@@ -469,6 +477,12 @@ fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
         fsd::launch_reorder(st, P, s->pairs.p, s->pos.p, s->vel.p, pos_by_src ? (float2*)nullptr : s->pos_s.p, s->vel_s.p, s->pred.p,
                             (uint32_t*)nullptr, s->cs.p, s->start_ref.p, s->work.p, s->counter.p, s->work_cap, s->safe.p, s->fdefer.p,
                             s->counter.p + 4);
+    if (s->trk_channels >= 0) {    // particle tracking: ids / channels follow this step's permutation (inside the FS_PASS_REORDER interval)
+        const int in = s->trk_cur, out = in ^ 1;
+        fsd::launch_track_carry(st, s->n, s->trk_channels, s->pairs.p, s->trk_id[in].p, s->trk_id[out].p, s->trk_attr[in].p,
+                                s->trk_attr[out].p, s->capacity);
+        s->trk_cur = out;
+    }
     if (prof) FS_HIP(hipEventRecord(ev[3], st));
     // strict / ulp modes: rho2.x IS the density; the separate 4-byte copy is only written in tolerance mode (rho2 = {P, 1/rho})
     s->rho_in_rho2 = P.fast_math != 2;
@@ -964,6 +978,106 @@ fs_status fs_download_surface_tension(fs_sim* s, fs_vec2* dst, size_t n) {
     if (n) FS_HIP(hipMemcpyAsync(dst, s->stf.p, n * sizeof(fs_vec2), hipMemcpyDeviceToHost, s->stream));
     FS_HIP(hipStreamSynchronize(s->stream));
     return sort_health(s);
+}
+
+// ---- particle tracking ----------------------------------------------------------------------------
+fs_status fs_track_enable(fs_sim* s, int channels) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    if (s->slab) return fail(FS_ERR_UNSUPPORTED, "tracking: single-domain handles only (not built for slab handles)");
+    if (channels < 0 || channels > FS_TRACK_MAX_CHANNELS) return fail(FS_ERR_INVALID, "tracking: channels must be in [0, FS_TRACK_MAX_CHANNELS]");
+    FS_HIP(hipSetDevice(s->device));
+    if (!s->trk_id[0].p) {
+        for (int k = 0; k < 2; ++k)
+            if (s->trk_id[k].alloc(s->capacity) != hipSuccess) {
+                (void)hipGetLastError();
+                s->trk_id[0].release(); s->trk_id[1].release();
+                return fail(FS_ERR_OOM, "tracking: id arrays");
+            }
+    }
+    if (channels > s->trk_alloc_channels) {
+        FS_HIP(hipStreamSynchronize(s->stream));      // steps in flight may still read the arrays about to be replaced
+        s->trk_attr[0].release(); s->trk_attr[1].release();
+        s->trk_alloc_channels = 0;
+        for (int k = 0; k < 2; ++k)
+            if (s->trk_attr[k].alloc((size_t)channels * s->capacity) != hipSuccess) {
+                (void)hipGetLastError();
+                s->trk_attr[0].release(); s->trk_attr[1].release();
+                s->trk_channels = -1;
+                return fail(FS_ERR_OOM, "tracking: channel arrays");
+            }
+        s->trk_alloc_channels = channels;
+    }
+    // on the simulation's stream: ordered after every step already enqueued, before every step enqueued from now on
+    s->trk_cur = 0;
+    fsd::launch_track_iota(s->stream, s->n, s->trk_id[0].p);
+    FS_HIP(hipGetLastError());
+    if (channels && s->n) FS_HIP(hipMemsetAsync(s->trk_attr[0].p, 0, (size_t)channels * s->capacity * sizeof(float), s->stream));
+    s->trk_channels = channels;
+    return FS_OK;
+}
+
+fs_status fs_track_disable(fs_sim* s) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    s->trk_channels = -1;           // the arrays stay allocated until the handle is destroyed
+    return FS_OK;
+}
+
+int fs_track_channels(const fs_sim* s) { return s ? s->trk_channels : -1; }
+
+namespace {
+// ids (attr = false) or one channel, host <-> the arrays of the last enqueued step.  Blocking.
+fs_status track_copy(fs_sim* s, int channel, bool attr, void* host, size_t n, bool upload) {
+    if (!s || !host) return fail(FS_ERR_INVALID, "null argument");
+    if (s->trk_channels < 0) return fail(FS_ERR_INVALID, "tracking is off (fs_track_enable)");
+    if (attr && (channel < 0 || channel >= s->trk_channels)) return fail(FS_ERR_INVALID, "tracking: no such channel");
+    if (n != s->n) return fail(FS_ERR_INVALID, "tracking: n must equal the particle count");
+    FS_HIP(hipSetDevice(s->device));
+    void* dev = attr ? (void*)(s->trk_attr[s->trk_cur].p + (size_t)channel * s->capacity) : (void*)s->trk_id[s->trk_cur].p;
+    if (n) {
+        if (upload) FS_HIP(hipMemcpyAsync(dev, host, n * 4, hipMemcpyHostToDevice, s->stream));
+        else FS_HIP(hipMemcpyAsync(host, dev, n * 4, hipMemcpyDeviceToHost, s->stream));
+    }
+    FS_HIP(hipStreamSynchronize(s->stream));
+    return upload ? FS_OK : sort_health(s);
+}
+}  // namespace
+
+fs_status fs_track_download_ids(fs_sim* s, uint32_t* dst, size_t n) { return track_copy(s, 0, false, dst, n, false); }
+fs_status fs_track_upload_ids(fs_sim* s, const uint32_t* src, size_t n) { return track_copy(s, 0, false, (void*)src, n, true); }
+fs_status fs_track_download_attr(fs_sim* s, int channel, float* dst, size_t n) { return track_copy(s, channel, true, dst, n, false); }
+fs_status fs_track_upload_attr(fs_sim* s, int channel, const float* src, size_t n) { return track_copy(s, channel, true, (void*)src, n, true); }
+
+fs_status fs_track_ids_device(fs_sim* s, const uint32_t** out) {
+    if (!s || !out) return fail(FS_ERR_INVALID, "null argument");
+    if (s->trk_channels < 0) return fail(FS_ERR_INVALID, "tracking is off (fs_track_enable)");
+    *out = s->trk_id[s->trk_cur].p;
+    return FS_OK;
+}
+
+fs_status fs_track_attr_device(fs_sim* s, int channel, const float** out) {
+    if (!s || !out) return fail(FS_ERR_INVALID, "null argument");
+    if (s->trk_channels < 0) return fail(FS_ERR_INVALID, "tracking is off (fs_track_enable)");
+    if (channel < 0 || channel >= s->trk_channels) return fail(FS_ERR_INVALID, "tracking: no such channel");
+    *out = s->trk_attr[s->trk_cur].p + (size_t)channel * s->capacity;
+    return FS_OK;
+}
+
+/* Off the step path: two downloads and a scatter on the host, so entries of dst that no id names are never written. */
+fs_status fs_download_particles_by_id(fs_sim* s, fs_particle* dst, size_t n) {
+    if (!s || (!dst && n)) return fail(FS_ERR_INVALID, "null argument");
+    if (s->trk_channels < 0) return fail(FS_ERR_INVALID, "tracking is off (fs_track_enable)");
+    std::vector<fs_particle> rec;
+    std::vector<uint32_t> ids;
+    try { rec.resize(s->n); ids.resize(s->n); } catch (const std::bad_alloc&) { return fail(FS_ERR_OOM, "host staging"); }
+    fs_status r = fs_download_particles(s, rec.data(), rec.size());
+    if (r != FS_OK) return r;
+    if (s->n) {
+        r = fs_track_download_ids(s, ids.data(), ids.size());
+        if (r != FS_OK) return r;
+    }
+    for (size_t i = 0; i < ids.size(); ++i)
+        if (ids[i] < n) dst[ids[i]] = rec[i];
+    return FS_OK;
 }
 
 fs_status fs_profile_enable(fs_sim* s, int enable) {

@@ -41,6 +41,11 @@ void launch_force(hipStream_t st, const StepParams& P, const float2* pos_s, cons
 void launch_surface_tension(hipStream_t st, const StepParams& P, float sigma, float tau, float cg, const float2* pred,
                             const float2* rho2, const float* rho, const uint32_t* cs, const uint32_t* start_ref, const u64* pairs,
                             float2* st_out);
+// Particle tracking (build extension): after the reorder pass of a step, id_out[i] = id_in[src] and, for c < channels,
+// attr_out[c * stride + i] = attr_in[c * stride + src], src = the low word of pairs[i] (the slot before the step).  channels in [0, 4].
+void launch_track_carry(hipStream_t st, uint32_t n, int channels, const u64* pairs, const uint32_t* id_in, uint32_t* id_out,
+                        const float* attr_in, float* attr_out, uint32_t stride);
+void launch_track_iota(hipStream_t st, uint32_t n, uint32_t* id);   // id[i] = i
 // pairs != nullptr: the keys are the high words of the sorted pairs (the state of the last step; launch_reorder with
 // key_s == nullptr does not store them a second time), else `key` (an uploaded state).
 void launch_export_aos(hipStream_t st, uint32_t n, const float2* pos, const float2* pred, const float2* vel,

@@ -95,6 +95,27 @@ public:
         check(fs_download_surface_tension(h_, v.data(), v.size()));
         return v;
     }
+    // Build extension, NOT in the reference: particle tracking (include/fluidsim.h), single-domain handles.  Every particle gets
+    // an id (its current slot) and `channels` float attributes (all 0) that follow it through the sort of every later step.
+    void track(int channels = 0) { check(fs_track_enable(h_, channels)); }
+    void untrack() { check(fs_track_disable(h_)); }
+    int track_channels() const { return fs_track_channels(h_); }   // -1: off
+    std::vector<uint32_t> particle_ids() {
+        std::vector<uint32_t> v(particle_count());
+        check(fs_track_download_ids(h_, v.data(), v.size()));
+        return v;
+    }
+    void set_particle_ids(const std::vector<uint32_t>& v) { check(fs_track_upload_ids(h_, v.data(), v.size())); }
+    std::vector<float> attribute(int channel) {
+        std::vector<float> v(particle_count());
+        check(fs_track_download_attr(h_, channel, v.data(), v.size()));
+        return v;
+    }
+    void set_attribute(int channel, const std::vector<float>& v) { check(fs_track_upload_attr(h_, channel, v.data(), v.size())); }
+    const uint32_t* particle_ids_device() { const uint32_t* p = nullptr; check(fs_track_ids_device(h_, &p)); return p; }
+    const float* attribute_device(int channel) { const float* p = nullptr; check(fs_track_attr_device(h_, channel, &p)); return p; }
+    // dst[id] = the record of the particle with that id; entries that no id names are left as they are
+    void download_by_id(std::vector<ParticleInstance>& dst) { check(fs_download_particles_by_id(h_, dst.data(), dst.size())); }
     fs_sim* handle() { return h_; }
 
 private:

@@ -149,6 +149,17 @@ extern "C" {
     fn fs_set_surface_tension(sim: *mut fs_sim, enable: c_int) -> c_int;
     fn fs_surface_tension_enabled(sim: *const fs_sim) -> c_int;
     fn fs_download_surface_tension(sim: *mut fs_sim, dst: *mut Vec2, n: usize) -> c_int;
+    // particle tracking (build extension, opt-in)
+    fn fs_track_enable(sim: *mut fs_sim, channels: c_int) -> c_int;
+    fn fs_track_disable(sim: *mut fs_sim) -> c_int;
+    fn fs_track_channels(sim: *const fs_sim) -> c_int;
+    fn fs_track_download_ids(sim: *mut fs_sim, dst: *mut u32, n: usize) -> c_int;
+    fn fs_track_upload_ids(sim: *mut fs_sim, src: *const u32, n: usize) -> c_int;
+    fn fs_track_download_attr(sim: *mut fs_sim, channel: c_int, dst: *mut f32, n: usize) -> c_int;
+    fn fs_track_upload_attr(sim: *mut fs_sim, channel: c_int, src: *const f32, n: usize) -> c_int;
+    fn fs_track_ids_device(sim: *mut fs_sim, out: *mut *const u32) -> c_int;
+    fn fs_track_attr_device(sim: *mut fs_sim, channel: c_int, out: *mut *const f32) -> c_int;
+    fn fs_download_particles_by_id(sim: *mut fs_sim, dst: *mut ParticleInstance, n: usize) -> c_int;
     // multi-GPU slab mode
     fn fs_slab_create(global_settings: *const SimulationSettings, device: c_int, cfg: *const SlabConfig, out: *mut *mut fs_sim) -> c_int;
     fn fs_slab_upload_owned(sim: *mut fs_sim, src: *const ParticleInstance, n: usize) -> c_int;
@@ -290,6 +301,41 @@ impl FluidSimulation {
     pub fn surface_tension_forces(&mut self) -> Vec<Vec2> {
         let mut v = vec![Vec2 { x: 0.0, y: 0.0 }; self.particle_count() as usize];
         check(unsafe { fs_download_surface_tension(self.raw, v.as_mut_ptr(), v.len()) }); v
+    }
+    /// Build extension, NOT in the reference: particle tracking (include/fluidsim.h).  Every particle gets an id (its current
+    /// slot) and `channels` f32 attributes (all 0.0) that follow it through the sort of every later step.  Single-domain handles.
+    pub fn track(&mut self, channels: u32) { check(unsafe { fs_track_enable(self.raw, channels as c_int) }); }
+    pub fn untrack(&mut self) { check(unsafe { fs_track_disable(self.raw) }); }
+    /// `None` when tracking is off.
+    pub fn track_channels(&self) -> Option<u32> {
+        let c = unsafe { fs_track_channels(self.raw) };
+        if c < 0 { None } else { Some(c as u32) }
+    }
+    /// The id of the particle in every slot, in `download_particles` order.
+    pub fn particle_ids(&mut self) -> Vec<u32> {
+        let mut v = vec![0u32; self.particle_count() as usize];
+        check(unsafe { fs_track_download_ids(self.raw, v.as_mut_ptr(), v.len()) }); v
+    }
+    pub fn set_particle_ids(&mut self, ids: &[u32]) { check(unsafe { fs_track_upload_ids(self.raw, ids.as_ptr(), ids.len()) }); }
+    pub fn attribute(&mut self, channel: u32) -> Vec<f32> {
+        let mut v = vec![0f32; self.particle_count() as usize];
+        check(unsafe { fs_track_download_attr(self.raw, channel as c_int, v.as_mut_ptr(), v.len()) }); v
+    }
+    pub fn set_attribute(&mut self, channel: u32, values: &[f32]) {
+        check(unsafe { fs_track_upload_attr(self.raw, channel as c_int, values.as_ptr(), values.len()) });
+    }
+    /// Device pointers to the arrays of the last enqueued step; valid until the next tick / upload / `track`.
+    pub fn particle_ids_device(&mut self) -> *const u32 {
+        let mut p: *const u32 = std::ptr::null();
+        check(unsafe { fs_track_ids_device(self.raw, &mut p) }); p
+    }
+    pub fn attribute_device(&mut self, channel: u32) -> *const f32 {
+        let mut p: *const f32 = std::ptr::null();
+        check(unsafe { fs_track_attr_device(self.raw, channel as c_int, &mut p) }); p
+    }
+    /// `dst[id]` = the record of the particle with that id; entries of `dst` that no id names are left as they are.
+    pub fn download_particles_by_id(&mut self, dst: &mut [ParticleInstance]) {
+        check(unsafe { fs_download_particles_by_id(self.raw, dst.as_mut_ptr(), dst.len()) });
     }
     /// `start_indices` to the host (the renderer's second storage binding; u32[grid_w * grid_h]).
     pub fn download_start_indices(&mut self) -> Vec<u32> {

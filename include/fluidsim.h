@@ -289,6 +289,49 @@ fs_status fs_set_surface_tension(fs_sim* sim, int enable);
 int fs_surface_tension_enabled(const fs_sim* sim);
 fs_status fs_download_surface_tension(fs_sim* sim, fs_vec2* dst, size_t n);
 
+/* ------------------------------------------------ particle tracking (build extension, opt-in) */
+/* NOT in the reference: every step cell-sorts the records and they carry no id, so "index i" names a different particle after
+ * every tick.  With tracking on, the handle keeps per particle a uint32_t id and C float channels (0 <= C <=
+ * FS_TRACK_MAX_CHANNELS), stored in slot order (fs_download_particles' order) and permuted by every step exactly as the
+ * records are.  Let src[i] be the slot, in the order before a step, of the particle which that step places in slot i (the
+ * permutation the step's sort applies: the bitonic network's in FS_SORT_BITONIC, the stable sort's in FS_SORT_COUNTING).
+ * After the step:
+ *     id[i]      = id_before[src[i]]
+ *     attr[c][i] = attr_before[c][src[i]]      for c < C      (bit copies: NaN payloads, -0 and denormals survive)
+ * Nothing else reads or writes them: the simulation state is bit-identical with tracking on or off, in every math mode, with
+ * or without surface tension.  One gather pass per step, timed inside the FS_PASS_REORDER interval of fs_profile_read; with
+ * tracking off no launch and no allocation.  Single-domain 2D handles only: a slab handle gets FS_ERR_UNSUPPORTED from
+ * fs_track_enable.  See DESIGN.md §12.
+ *
+ * fs_upload_particles does NOT touch ids or channels: it replaces the records of slots, and identity stays with the slot, so
+ * download -> edit -> upload keeps every id.
+ *
+ * fs_track_enable: allocates on first use (8 B + 8 B per channel, per particle) and (re)initialises id[i] = i (the slot held
+ *   at the moment of the call, i.e. fs_download_particles' current order) and every channel to +0.0f.  Calling it again
+ *   re-initialises, also with another channel count.  channels < 0 or > FS_TRACK_MAX_CHANNELS: FS_ERR_INVALID.  Takes effect
+ *   for steps enqueued after the call and is ordered after the steps already in flight.
+ * fs_track_disable: later steps do not carry; the read calls below then return FS_ERR_INVALID.  Off is the default.
+ * fs_track_channels: -1 when off, else C.
+ * fs_track_download_* / fs_track_upload_*: blocking host copies in slot order.  n must equal the particle count and channel must
+ *   be < C, else FS_ERR_INVALID.  Uploaded ids are the caller's business (any uint32_t, duplicates allowed).
+ * fs_track_ids_device / fs_track_attr_device: device pointers to the arrays of the last enqueued step (stream-ordered on
+ *   fs_stream), for a renderer on the same device.  Valid until the next fs_step / fs_timed_steps / upload / enable: the
+ *   arrays ping-pong, as fs_particles_device's view may.
+ * fs_download_particles_by_id: dst[id[i]] = particle[i] for every slot with id[i] < n; entries of dst that no id names are
+ *   left exactly as the caller passed them; with duplicate ids it is unspecified which record wins.  n is the length of dst
+ *   and need not equal the particle count.  Blocking; off the step path. */
+#define FS_TRACK_MAX_CHANNELS 4
+fs_status fs_track_enable(fs_sim* sim, int channels);
+fs_status fs_track_disable(fs_sim* sim);
+int fs_track_channels(const fs_sim* sim);
+fs_status fs_track_download_ids(fs_sim* sim, uint32_t* dst, size_t n);
+fs_status fs_track_upload_ids(fs_sim* sim, const uint32_t* src, size_t n);
+fs_status fs_track_download_attr(fs_sim* sim, int channel, float* dst, size_t n);
+fs_status fs_track_upload_attr(fs_sim* sim, int channel, const float* src, size_t n);
+fs_status fs_track_ids_device(fs_sim* sim, const uint32_t** out);
+fs_status fs_track_attr_device(fs_sim* sim, int channel, const float** out);
+fs_status fs_download_particles_by_id(fs_sim* sim, fs_particle* dst, size_t n);
+
 /* ------------------------------------------------ multi-GPU slab mode (build extension) */
 /* NOT in the reference (single wgpu device, src/renderer.rs:108-133).  SURVEY.md §8e: a rank
  * owns the global cell columns [own_lo, own_hi) of the grid (src/simulation.rs:140-141) and

@@ -1,0 +1,116 @@
+"""CPU-side checks of the opt-in particle tracking: the checker of tests/track_ref.py is sound (its permutation
+is the one the oracle's sort applies, for both sorts), ids stay a permutation, every host binding names every new call, and the
+calls refuse a NULL handle without touching a device.  No GPU."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TRACK_CALLS = ("fs_track_enable", "fs_track_disable", "fs_track_channels", "fs_track_download_ids", "fs_track_upload_ids",
+               "fs_track_download_attr", "fs_track_upload_attr", "fs_track_ids_device", "fs_track_attr_device",
+               "fs_download_particles_by_id")
+
+
+def make_checker(fs, n, seed, **kw):
+    from tests.track_ref import TrackChecker, jitter_velocities
+    st, off, tick = fs.dam_break_2d(n)
+    chk = TrackChecker(st, off, **kw)
+    chk.set_particles(jitter_velocities(chk.particles(), seed))
+    return chk, tick
+
+
+@pytest.mark.parametrize("n,stable", [(4096, False), (4096, True), (5000, False), (5000, True)])
+def test_checker_permutation_reproduces_the_oracles_sort(fs, orc, n, stable):
+    """before[perm] is byte-equal to the oracle's sorted records at every step (verify=True asserts it inside step()), the
+    checker's state stays the plain oracle's, and the scene is not vacuous: most slots change occupant."""
+    chk, tick = make_checker(fs, n, seed=n, verify=True)
+    st, off, _ = fs.dam_break_2d(n)
+    ref = orc.OracleSim(st, off)
+    ref.set_particles(chk.particles())
+    moved = []
+    for _ in range(8):
+        perm = chk.step(tick, stable_sort=stable)
+        ref.step(tick, stable_sort=stable)
+        assert chk.particles_view().tobytes() == ref.particles_view().tobytes()
+        assert np.array_equal(chk.start_indices_view(), ref.start_indices_view())
+        moved.append(float((perm != np.arange(n)).mean()))
+    assert sum(m > 0.5 for m in moved) >= 6, moved
+    assert (chk.ids != np.arange(n)).mean() > 0.5
+
+
+@pytest.mark.parametrize("stable", [False, True])
+def test_ids_stay_a_permutation_and_compose(fs, orc, stable):
+    """ids are a permutation of 0..N-1 after every step, and composing the per-step permutations equals tracking the ids;
+    a channel initialised to float(id) still equals the ids."""
+    n = 5000
+    chk, tick = make_checker(fs, n, seed=11, channels=2)
+    chk.attr[0] = np.arange(n, dtype=np.float32)
+    composed = np.arange(n, dtype=np.uint32)
+    for _ in range(8):
+        perm = chk.step(tick, stable_sort=stable)
+        composed = composed[perm]
+        assert np.array_equal(np.sort(chk.ids), np.arange(n, dtype=np.uint32))
+        assert np.array_equal(chk.ids, composed)
+    assert np.array_equal(chk.attr[0], chk.ids.astype(np.float32))
+    assert not chk.attr[1].any()
+    assert (chk.ids != np.arange(n)).mean() > 0.5
+
+
+def test_reset_restarts_the_ids_at_the_current_slots(fs, orc):
+    chk, tick = make_checker(fs, 4096, seed=3, channels=1)
+    for _ in range(3):
+        chk.step(tick)
+    chk.reset(channels=3)
+    assert np.array_equal(chk.ids, np.arange(4096, dtype=np.uint32)) and chk.attr.shape == (3, 4096)
+    perm = chk.step(tick)
+    assert np.array_equal(chk.ids, perm)
+
+
+def _strip_c_comments(s):
+    s = re.sub(r"/\*.*?\*/", " ", s, flags=re.S)
+    return re.sub(r"//[^\n]*", " ", s)
+
+
+def test_every_layer_names_every_tracking_call(fs):
+    header = _strip_c_comments(open(os.path.join(ROOT, "include", "fluidsim.h")).read())
+    pkg = os.path.join(ROOT, "gpu-fluid-simulation_amd")
+    rust = _strip_c_comments(open(os.path.join(pkg, "rust", "src", "lib.rs")).read())
+    rust_extern = re.search(r'extern\s+"C"\s*\{(.*?)\n\}', rust, flags=re.S).group(1)
+    rust_rest = rust.replace(rust_extern, "")
+    cpp = _strip_c_comments(open(os.path.join(pkg, "host", "fluid_simulation.hpp")).read())
+    py = open(os.path.join(pkg, "__init__.py")).read()
+    lib = fs.load_library()
+    for name in TRACK_CALLS:
+        assert re.search(rf"\b{name}\s*\(", header), f"{name} not declared in include/fluidsim.h"
+        assert name in fs._abi.PROTOTYPES, f"{name} has no ctypes prototype"
+        assert hasattr(lib, name), f"{name} not exported by the library"
+        assert re.search(rf"\bfn\s+{name}\s*\(", rust_extern), f"{name} not in the Rust extern block"
+        assert re.search(rf"\b{name}\s*\(", rust_rest), f"{name} bound but never called by the Rust wrapper"
+        assert re.search(rf"\b{name}\s*\(", cpp), f"{name} not used by the C++ mirror"
+        assert re.search(rf"\.{name}\s*\(", py), f"{name} not used by the Python wrapper"
+    assert re.search(r"#define\s+FS_TRACK_MAX_CHANNELS\s+4\b", header)
+    for method in ("track", "untrack", "track_channels", "particle_ids", "set_particle_ids", "attribute", "set_attribute",
+                   "download_particles_by_id", "particle_ids_device_ptr", "attribute_device_ptr"):
+        assert hasattr(fs.FluidSimulation, method), f"FluidSimulation.{method} missing"
+    assert lib.fs_abi_version() == 2
+
+
+def test_null_handle_is_invalid_without_a_device(fs):
+    lib = fs.load_library()
+    inv = fs._abi.FS_ERR_INVALID
+    buf = (C.c_uint32 * 4)()
+    out = C.c_void_p()
+    assert lib.fs_track_enable(None, 0) == inv
+    assert lib.fs_track_disable(None) == inv
+    assert lib.fs_track_channels(None) == -1
+    assert lib.fs_track_download_ids(None, buf, 4) == inv
+    assert lib.fs_track_upload_ids(None, buf, 4) == inv
+    assert lib.fs_track_download_attr(None, 0, buf, 4) == inv
+    assert lib.fs_track_upload_attr(None, 0, buf, 4) == inv
+    assert lib.fs_track_ids_device(None, C.byref(out)) == inv
+    assert lib.fs_track_attr_device(None, 0, C.byref(out)) == inv
+    assert lib.fs_download_particles_by_id(None, buf, 4) == inv
+    assert b"null" in lib.fs_last_error()
