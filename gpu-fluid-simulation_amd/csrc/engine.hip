@@ -9,11 +9,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/fluidsim.h"
+#include "fs_host.h"
 #include "fs_kernels.h"
 #include "sort_policy.h"
 
@@ -28,25 +30,12 @@ static_assert(offsetof(fs_uniform, gravity) == 16 && offsetof(fs_uniform, smooth
               "SimulationUniform offsets");
 
 namespace {
-
 thread_local std::string g_err;
-
-fs_status fail(fs_status st, const std::string& msg) {
-    g_err = msg;
-    return st;
-}
 }  // namespace
-namespace fsd { void set_last_error(const std::string& msg) { g_err = msg; } }   // used by sim3d.hip
+namespace fsd { void set_last_error(const std::string& msg) { g_err = msg; } }   // fs_host.h: fail()
+using fsd::DevArray;
+using fsd::fail;
 namespace {
-
-#define FS_HIP(expr)                                                                                     \
-    do {                                                                                                 \
-        hipError_t e__ = (expr);                                                                         \
-        if (e__ != hipSuccess) {                                                                         \
-            return fail(e__ == hipErrorOutOfMemory ? FS_ERR_OOM : FS_ERR_DEVICE,                         \
-                        std::string(#expr) + ": " + hipGetErrorString(e__));                             \
-        }                                                                                                \
-    } while (0)
 
 const float PI_F = 3.14159265359f;   // funcs.wgsl:54 == std::f32::consts::PI in f32
 
@@ -81,52 +70,82 @@ bool settings_valid(const fs_settings& s, std::string* why) {
     return true;
 }
 
-template <class T>
-struct DevArray {
-    T* p = nullptr;
-    size_t n = 0;
-    hipError_t alloc(size_t count) {
-        n = count;
-        if (count == 0) { p = nullptr; return hipSuccess; }
-        return hipMalloc((void**)&p, count * sizeof(T));
+// The arrays one particle array's sort-reorder, density and force passes work on: the main array of every handle (fs_sim) and
+// the boundary strip of an overlapped slab step (fs_sim::Strip) each hold one set.
+struct ParticleArrays {
+    // SoA state.  pos/vel: current state (cell order of the last step).  *_s: the
+    // cell-sorted snapshot the density/force passes read (Jacobi semantics).
+    DevArray<float2> pos, vel, pos_s, vel_s, pred;
+    DevArray<float> rho;
+    DevArray<float2> rho2;          // {density, RN(1/density)}: what the force pass gathers per neighbour
+    DevArray<uint32_t> fdefer, fwork;   // force pass: per-block deferred-wave bits and the worklist (counter[3] = its length)
+    DevArray<uint32_t> bbounds;         // 8 words per 256-particle block: the density pass's block-wide sweep ranges, read by the force pass
+    DevArray<unsigned long long> safe;   // one bit per sorted particle: coordinates / velocity inside the exact-quotient ranges (fs_device.h)
+    DevArray<fsd::u64> pairs;
+    DevArray<uint32_t> csort;       // scratch of the counting sort (FS_SORT_COUNTING)
+    DevArray<uint32_t> cs;          // dense cell-start table, ncell+1
+    DevArray<uint32_t> start_ref;   // reference start_indices (persistent, never cleared)
+    DevArray<uint32_t> counter;     // the passes' work counters: from [0] the reorder's gap worklist, [4..5] the force pass
+    DevArray<unsigned char> owned;  // slab mode
+
+    // the arrays every handle and every strip has, for `cap` slots
+    hipError_t alloc_common(size_t cap) {
+        hipError_t e = hipSuccess;
+        auto ok = [&e](hipError_t r) { e = r; return r == hipSuccess; };
+        (void)(ok(pos.alloc(cap)) && ok(vel.alloc(cap)) && ok(pos_s.alloc(cap)) && ok(vel_s.alloc(cap)) &&
+               ok(pred.alloc(cap + FS_PRED_SLACK)) && ok(rho.alloc(cap)) && ok(rho2.alloc(cap)) && ok(safe.alloc((cap + 63) / 64 + 1)) &&
+               ok(fdefer.alloc(2 * ((cap + 255) / 256 + 8))) && ok(fwork.alloc(2 * (cap / 256 + 8) + 16)) &&
+               ok(bbounds.alloc(8 * ((cap + 255) / 256 + 8))) && ok(pairs.alloc(cap)) && ok(counter.alloc(8)));
+        return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+    // What the step launchers see of this set (fs_kernels.h); the force pass writes the new state over pos / vel.
+    fsd::StepArrays step_arrays() const {
+        fsd::StepArrays A;
+        A.pos = pos.p; A.vel = vel.p; A.pos_s = pos_s.p; A.vel_s = vel_s.p; A.pred = pred.p;
+        A.rho = rho.p; A.rho2 = rho2.p; A.pairs = pairs.p; A.cs = cs.p; A.start_ref = start_ref.p; A.safe = safe.p;
+        A.fdefer = fdefer.p; A.fwork = fwork.p; A.fcount = counter.p + 4;
+        A.pos_out = pos.p; A.vel_out = vel.p;
+        A.owned = owned.p; A.csort = csort.p; A.counter = counter.p;
+        return A;
+    }
+};
+
+// Streams, events and the other things of a handle that are not device arrays.
+struct HandleQueues {
+    fsd::Stream stream;
+    fsd::Stream side;               // second stream of the force pass (general workgroups beside the lean kernel)
+    fsd::Stream comm;               // slab: the exchange's stream (fs_slab_exchange, or the caller's transport between comm_begin / comm_end)
+    fsd::Event ev_fork, ev_join;    // ... of `side`
+    fsd::Event ev_packed;           // main stream: both outgoing messages are complete
+    fsd::Event ev_exch;             // comm stream: both incoming messages have arrived
+    fsd::Event ev_fork2;            // edge-first: the density pass is done, the edge columns' chain may start on `comm`
+    fsd::Event t0, t1;              // fs_timed_steps
+    fsd::SortPolicy sortp;          // host side of the sort's late-stage plan (sort_policy.h)
+    fsd::PassRing prof;             // per-pass timing (fs_host.h)
 };
 
 }  // namespace
 
-struct fs_sim {
+// Every resource is held by an owner (fs_host.h) and freed by `delete`.  Teardown order: members go in reverse order of
+// declaration, then the bases from right to left — so first the device arrays (the members below, then ParticleArrays), then
+// HandleQueues backwards: the events (profile ring, sort policy, the named ones), and the streams last.
+struct fs_sim : HandleQueues, ParticleArrays {
     fs_settings settings{};
     fs_options opts{};
     uint32_t n = 0, capacity = 0;
     uint32_t grid_w = 0, grid_h = 0, ncell = 0;
     uint32_t tick = 0;
     fs_uniform uniform{};
-    hipStream_t stream = nullptr;
-    hipStream_t side = nullptr;     // second stream of the force pass (general workgroups beside the lean kernel)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int device = 0;
 
-    // SoA state.  pos/vel: current state (cell order of the last step).  *_s: the
-    // cell-sorted snapshot the density/force passes read (Jacobi semantics).
-    DevArray<float2> pos, vel, pos_s, vel_s, pred;
-    DevArray<float> rho;
-    DevArray<float2> rho2;          // {density, RN(1/density)}: what the force pass gathers per neighbour
+    // the main array: ParticleArrays, and
     DevArray<uint32_t> key;         // keys of an uploaded / initial state; after a step they live in `pairs` (key_in_pairs)
     bool key_in_pairs = false;
     bool rho_in_rho2 = false;       // likewise the densities: rho2.x after a strict / ulp step, `rho` after an upload or a tolerance step
-    DevArray<uint32_t> fdefer, fwork;   // force pass: per-block deferred-wave bits and the worklist (counter[3] = its length)
-    DevArray<uint32_t> bbounds;         // 8 words per 256-particle block: the density pass's block-wide sweep ranges, read by the force pass
-    DevArray<unsigned long long> safe;   // one bit per sorted particle: coordinates / velocity inside the exact-quotient ranges (fs_device.h)
-    DevArray<fsd::u64> pairs;
     DevArray<uint32_t> sort_dirty;  // per-tile flags of the bitonic sort
-    DevArray<uint32_t> csort;       // scratch of the counting sort (FS_SORT_COUNTING)
-    DevArray<uint32_t> cs;          // dense cell-start table, ncell+1
-    DevArray<uint32_t> start_ref;   // reference start_indices (persistent, never cleared)
     DevArray<float2> tex;           // force field
     bool tex_zero = true;           // the host knows every entry is +-0 (zero-initialised, or an all-zero upload)
     DevArray<unsigned char> work;   // gap worklist
-    DevArray<uint32_t> counter;
     uint32_t work_cap = 0;
     DevArray<fs_particle> aos;      // lazily allocated 32-byte view
     bool aos_live = false;          // a hand-off is registered: the force pass writes the AoS records itself
@@ -147,20 +166,16 @@ struct fs_sim {
     fsd::ConstDiv div_h{};               // ... and of the cell coordinates (x / h), over the numerators clamped positions give
     bool rcp_ok = false, sqrt_ok = false; // rcp_rn_fast / sqrt_rn_fast proven on this device at create
 
-    fsd::SortPolicy sortp;          // host side of the sort's late-stage plan (sort_policy.h)
-
     // slab (multi-GPU) mode
     bool slab = false;
     fs_slab_config slab_cfg{};
     uint32_t slab_main = 0;         // capacity - 2 * recv_capacity
-    DevArray<unsigned char> owned;
     DevArray<uint2> blockcnt;           // per 256-slot block: records for the left / right message (k_slab_pack)
     DevArray<uint32_t> stage;           // ... and the slots themselves, 2 x 256 entries per block
     DevArray<fsd::u64> msg_state;       // k_slab_msg's look-back words
     DevArray<uint32_t> slab_counters;   // [0] n_live, [2] lost, [3] overflow, [4] far_halo
     DevArray<uint32_t> hist;
     bool slab_packed = false;
-    bool slab_prof = false;                // profiling state latched by fs_slab_pack for the matching fs_slab_step
     uint32_t state_lo = 0, state_hi = 0;   // the owned window the current keys / cell starts were built with
 
     // Overlapped slab step (counting sort only): fs_slab_pack enqueues the pack AND the whole step of the
@@ -175,10 +190,6 @@ struct fs_sim {
     uint32_t pp_lo = 0, pp_hi = 0;         // ... and this owned window
     uint32_t msg_epoch = 0;                // one number per k_slab_msg launch (its look-back state is never cleared)
     fs_tick_settings last_tick{};
-    hipStream_t comm = nullptr;            // the exchange's stream (fs_slab_exchange, or the caller's transport between comm_begin / comm_end)
-    hipEvent_t ev_packed = nullptr;        // main stream: both outgoing messages are complete
-    hipEvent_t ev_exch = nullptr;          // comm stream: both incoming messages have arrived
-    hipEvent_t ev_fork2 = nullptr;         // edge-first: the density pass is done, the edge columns' chain may start on `comm`
     bool exch_pending = false;             // fs_slab_step must wait for ev_exch
     bool join_pending = false;             // edge-first: the simulation's stream has not yet waited for the edge columns' chain of the last step (slab_join)
     bool edge_classified = false;          // edge-first: that chain also classified its particles' slots for the next pack
@@ -187,53 +198,34 @@ struct fs_sim {
     uint32_t adv_lo = 0, adv_hi = 0;       // interior columns of the step being enqueued
     uint32_t strip_win[4] = {0, 0, 0, 0};
     bool strip_active = false;
-    struct Strip {
-        DevArray<float2> pos, vel, pos_s, vel_s, pred, rho2, pos_out, vel_out;
-        DevArray<float> rho;
-        DevArray<fsd::u64> pairs;
-        DevArray<uint32_t> csort, cs, start_ref, fdefer, fwork, counter, back, rowbase, counters, bbounds;
-        DevArray<unsigned long long> safe;
-        DevArray<unsigned char> owned;
+    // The strip's own particle array (ParticleArrays; its force pass writes pos_out / vel_out, which the write-back scatters
+    // into the main array through `back`).
+    struct Strip : ParticleArrays {
+        DevArray<float2> pos_out, vel_out;
+        DevArray<uint32_t> back, rowbase, counters;
         uint32_t cap = 0;
-        void release() {
-            pos.release(); vel.release(); pos_s.release(); vel_s.release(); pred.release(); rho2.release(); pos_out.release();
-            vel_out.release(); rho.release(); pairs.release(); csort.release(); cs.release(); start_ref.release(); fdefer.release();
-            fwork.release(); counter.release(); back.release(); rowbase.release(); counters.release(); safe.release(); owned.release(); bbounds.release();
+        fsd::StepArrays step_arrays() const {
+            fsd::StepArrays A = ParticleArrays::step_arrays();
+            A.pos_out = pos_out.p; A.vel_out = vel_out.p;
+            A.n_dev = counters.p + 2;      // strip_counters[2]: slots in use
+            return A;
         }
     } strip;
 
-    // Per-pass timing: a ring of event sets recorded on the stream; drained (synchronised
-    // and accumulated) only when read or when the ring is full, never per step.
-    static const uint32_t PROF_RING = 256;
-    bool profile = false;
-    std::vector<hipEvent_t> ev;     // PROF_RING * (FS_PASS_COUNT + 1)
-    uint32_t prof_pending = 0;
-    double prof_ms[FS_PASS_COUNT] = {};
-    uint64_t prof_steps = 0;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
+    bool slab_prof = false;                // profiling state latched by fs_slab_pack for the matching fs_slab_step
 
-    void release() {
-        pos.release(); vel.release(); pos_s.release(); vel_s.release(); pred.release(); rho.release(); rho2.release();
-        key.release(); safe.release(); fdefer.release(); fwork.release(); bbounds.release(); pairs.release(); sort_dirty.release(); csort.release(); cs.release(); start_ref.release(); tex.release(); work.release();
-        counter.release(); aos.release(); stf.release();
-        trk_id[0].release(); trk_id[1].release(); trk_attr[0].release(); trk_attr[1].release();
-        owned.release(); blockcnt.release(); stage.release(); msg_state.release(); slab_counters.release();
-        hist.release(); strip.release();
-        if (ev_packed) (void)hipEventDestroy(ev_packed);
-        if (ev_exch) (void)hipEventDestroy(ev_exch);
-        if (ev_fork2) (void)hipEventDestroy(ev_fork2);
-        if (comm) (void)hipStreamDestroy(comm);
-        comm = nullptr; ev_packed = ev_exch = ev_fork2 = nullptr;
-        for (auto& e : ev) (void)hipEventDestroy(e);
-        ev.clear();
-        sortp.release();
-        if (t0) (void)hipEventDestroy(t0);
-        if (t1) (void)hipEventDestroy(t1);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        if (ev_join) (void)hipEventDestroy(ev_join);
-        if (side) (void)hipStreamDestroy(side);
-        if (stream) (void)hipStreamDestroy(stream);
-        stream = nullptr; side = nullptr; ev_fork = ev_join = nullptr;
+    // the main array as the step launchers see it
+    fsd::StepArrays step_arrays() const {
+        fsd::StepArrays A = ParticleArrays::step_arrays();
+        A.tex = tex.p; A.work = work.p; A.key_s = key.p;
+        return A;
+    }
+    // the side stream of the force pass and what the sort policy's reports of a few steps ago suggest for its follow-up launches
+    fsd::ForceLaunch force_launch() const {
+        fsd::ForceLaunch L;
+        L.side = side; L.ev_fork = ev_fork; L.ev_join = ev_join;
+        L.general_grid = sortp.general_grid(); L.general_hint = sortp.general_hint();
+        return L;
     }
 };
 
@@ -411,27 +403,52 @@ fs_status prove_force_constants(fs_sim* s) {
     return FS_OK;
 }
 
-fs_status ensure_events(fs_sim* s) {
-    if (s->ev.empty()) {
-        s->ev.resize((size_t)fs_sim::PROF_RING * (FS_PASS_COUNT + 1));
-        for (auto& e : s->ev) FS_HIP(hipEventCreate(&e));
+// What fs_create_ex and fs_slab_create share, once settings, sort mode, capacity and grid are set: the streams and events,
+// the arrays every handle has, and the zeroes the reference's buffers start with.
+fs_status create_common(fs_sim* s) {
+    FS_HIP(hipStreamCreateWithFlags(&s->stream.h, hipStreamNonBlocking));
+    // The pre-registered general work can run beside the lean force kernel on a second stream (FS_SIDE_STREAM=1).
+    // Measured at 16M: force 0.725 -> 0.711 ms in the bench window and 1.10 -> 0.99 ms in the dense regime, but every
+    // launch of the following sort then pays ~1 us more behind the cross-stream join (sort 0.70 -> 0.73 ms): a net
+    // loss in the bench window, so it is off by default.
+    if (getenv("FS_SIDE_STREAM")) {
+        FS_HIP(hipStreamCreateWithFlags(&s->side.h, hipStreamNonBlocking));
+        FS_HIP(hipEventCreateWithFlags(&s->ev_fork.h, hipEventDisableTiming));
+        FS_HIP(hipEventCreateWithFlags(&s->ev_join.h, hipEventDisableTiming));
     }
+    FS_HIP(hipEventCreate(&s->t0.h));
+    FS_HIP(hipEventCreate(&s->t1.h));
+    FS_HIP(s->sortp.init(8));   // slab handles use the pinned words for the force pass's work report only (sort: per-stage plan)
+    const size_t cap = s->capacity;
+    FS_HIP(s->alloc_common(cap));
+    FS_HIP(s->key.alloc(cap));
+    FS_HIP(s->aos.alloc(cap));
+    FS_HIP(s->sort_dirty.alloc(fsd::sort_tile_count((uint32_t)cap)));
+    FS_HIP(hipMemsetAsync(s->sort_dirty.p, 0, s->sort_dirty.n * sizeof(uint32_t), s->stream));
+    FS_HIP(s->cs.alloc((size_t)s->ncell + 1));
+    FS_HIP(s->start_ref.alloc(s->ncell));
+    FS_HIP(s->tex.alloc((size_t)s->settings.texture_size.x * s->settings.texture_size.y));
+    FS_HIP(s->work.alloc((size_t)s->work_cap * fsd::gap_entry_size()));
+    if (s->slab || s->opts.sort_mode == FS_SORT_COUNTING) {
+        FS_HIP(s->csort.alloc(fsd::counting_sort_scratch_words((uint32_t)cap, s->ncell)));
+        FS_HIP(hipMemsetAsync(s->csort.p, 0, s->csort.n * sizeof(uint32_t), s->stream));   // histogram / tickets: zero between steps
+    }
+    // wgpu zero-initialises buffers: start_indices (simulation.rs:204-209), force field (:213-218)
+    FS_HIP(hipMemsetAsync(s->start_ref.p, 0, s->start_ref.n * sizeof(uint32_t), s->stream));
+    FS_HIP(hipMemsetAsync(s->cs.p, 0, s->cs.n * sizeof(uint32_t), s->stream));
+    if (s->tex.n) FS_HIP(hipMemsetAsync(s->tex.p, 0, s->tex.n * sizeof(float2), s->stream));
+    FS_HIP(hipMemsetAsync(s->counter.p, 0, 8 * sizeof(uint32_t), s->stream));
+    FS_HIP(hipMemsetAsync(s->rho.p, 0, cap * sizeof(float), s->stream));
     return FS_OK;
 }
 
-fs_status drain_profile(fs_sim* s) {
-    if (s->prof_pending == 0) return FS_OK;
-    const size_t stride = FS_PASS_COUNT + 1;
-    FS_HIP(hipEventSynchronize(s->ev[(size_t)(s->prof_pending - 1) * stride + FS_PASS_COUNT]));
-    for (uint32_t j = 0; j < s->prof_pending; ++j) {
-        for (int k = 0; k < FS_PASS_COUNT; ++k) {
-            float ms = 0.0f;
-            FS_HIP(hipEventElapsedTime(&ms, s->ev[j * stride + k], s->ev[j * stride + k + 1]));
-            s->prof_ms[k] += ms;
-        }
-    }
-    s->prof_steps += s->prof_pending;
-    s->prof_pending = 0;
+// ... and what both end with, after the initial state is in place: the create-time proofs and the uniform of tick 0.
+fs_status create_finish(fs_sim* s) {
+    const fs_status r = prove_force_constants(s);
+    if (r != FS_OK) return r;
+    fs_tick_settings t0;
+    std::memset(&t0, 0, sizeof t0);
+    host_uniform(s->settings, t0, 0, &s->uniform);
     return FS_OK;
 }
 
@@ -446,13 +463,12 @@ fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
     const bool pos_by_src = pos_by_src_env && s->opts.sort_mode != FS_SORT_COUNTING;
     P.pos_by_src = pos_by_src ? 1 : 0;
     hipStream_t st = s->stream;
-    const bool prof = s->profile;
+    const bool prof = s->prof.on;
     hipEvent_t* ev = nullptr;
     if (prof) {
-        fs_status r = ensure_events(s);
+        const fs_status r = s->prof.begin();
         if (r != FS_OK) return r;
-        if (s->prof_pending == fs_sim::PROF_RING) { r = drain_profile(s); if (r != FS_OK) return r; }
-        ev = &s->ev[(size_t)s->prof_pending * (FS_PASS_COUNT + 1)];
+        ev = s->prof.current();
     }
     if (s->n == 0) return FS_OK;
     FS_HIP(s->sortp.throttle());                       // at most SortPolicy::FLIGHT steps ahead of the device
@@ -469,14 +485,14 @@ fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
         fsd::launch_bitonic_sort(st, s->pairs.p, s->n, s->sort_dirty.p, &P, s->pos.p, s->vel.p, s->counter.p, &plan);
     }
     if (prof) FS_HIP(hipEventRecord(ev[2], st));
+    fsd::StepArrays A = s->step_arrays();
     s->key_in_pairs = true;        // the 4 B / particle of a second copy of the keys stay unwritten
+    A.key_s = nullptr;
+    if (pos_by_src) A.pos_s = nullptr;     // ... and so does the sorted copy of the positions
     if (counting)      // rank fix-up of the counting sort fused with the reorder pass (kernels_csort.hip)
-        fsd::launch_counting_reorder(st, P, s->csort.p, s->pairs.p, s->cs.p, s->pos.p, s->vel.p, s->pos_s.p, s->vel_s.p, s->pred.p,
-                                     (uint32_t*)nullptr, s->start_ref.p, s->safe.p, s->fdefer.p, s->counter.p + 4);
+        fsd::launch_counting_reorder(st, P, A);
     else
-        fsd::launch_reorder(st, P, s->pairs.p, s->pos.p, s->vel.p, pos_by_src ? (float2*)nullptr : s->pos_s.p, s->vel_s.p, s->pred.p,
-                            (uint32_t*)nullptr, s->cs.p, s->start_ref.p, s->work.p, s->counter.p, s->work_cap, s->safe.p, s->fdefer.p,
-                            s->counter.p + 4);
+        fsd::launch_reorder(st, P, A, s->work_cap);
     if (s->trk_channels >= 0) {    // particle tracking: ids / channels follow this step's permutation (inside the FS_PASS_REORDER interval)
         const int in = s->trk_cur, out = in ^ 1;
         fsd::launch_track_carry(st, s->n, s->trk_channels, s->pairs.p, s->trk_id[in].p, s->trk_id[out].p, s->trk_attr[in].p,
@@ -486,27 +502,28 @@ fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
     if (prof) FS_HIP(hipEventRecord(ev[3], st));
     // strict / ulp modes: rho2.x IS the density; the separate 4-byte copy is only written in tolerance mode (rho2 = {P, 1/rho})
     s->rho_in_rho2 = P.fast_math != 2;
-    fsd::launch_density(st, P, s->pred.p, s->cs.p, s->start_ref.p, s->pairs.p, s->safe.p, s->rho_in_rho2 ? (float*)nullptr : s->rho.p, s->rho2.p, s->fdefer.p, s->fwork.p, s->counter.p + 4);
+    if (s->rho_in_rho2) A.rho = nullptr;
+    fsd::launch_density(st, P, A);
     if (prof) FS_HIP(hipEventRecord(ev[4], st));
-    const float2* st_in = nullptr;     // surface tension: its pass runs inside the FS_PASS_FORCE interval of the profile
-    if (s->st_on) {
-        fsd::launch_surface_tension(st, P, s->uniform.surface_tension_coefficient, s->uniform.surface_tension_treshold,
-                                    s->uniform.poly6_kernel_derivative, s->pred.p, s->rho2.p, s->rho_in_rho2 ? nullptr : s->rho.p,
-                                    s->cs.p, s->start_ref.p, s->pairs.p, s->stf.p);
-        st_in = s->stf.p;
+    fsd::ForceLaunch L = s->force_launch();
+    if (s->st_on) {                    // surface tension: its pass runs inside the FS_PASS_FORCE interval of the profile
+        fsd::launch_surface_tension(st, P, A, s->uniform.surface_tension_coefficient, s->uniform.surface_tension_treshold,
+                                    s->uniform.poly6_kernel_derivative, s->stf.p);
+        L.st_in = s->stf.p;
         s->st_valid = true;
     }
-    fsd::launch_force(st, P, pos_by_src ? s->pos.p : s->pos_s.p, s->vel_s.p, s->pred.p, s->rho2.p, s->cs.p, s->start_ref.p, s->pairs.p,
-                      s->tex.p, pos_by_src ? s->pos_s.p : s->pos.p, s->vel.p, s->rho.p, s->fdefer.p, s->fwork.p, s->counter.p + 4,
-                      s->aos_live ? (void*)s->aos.p : nullptr, s->side, s->ev_fork, s->ev_join,
-                      s->sortp.general_grid(), s->sortp.general_hint(), 0u, prof ? nullptr : s->sortp.flight_event(), s->sortp.quad_entries(),
-                      st_in);
-    if (pos_by_src) { float2* t = s->pos.p; s->pos.p = s->pos_s.p; s->pos_s.p = t; }   // the spare buffer now holds the state
+    A.rho = s->rho.p;                  // (the force kernels take the array whatever the mode)
+    if (pos_by_src) { A.pos_s = s->pos.p; A.pos_out = s->pos_s.p; }    // the role swap described above
+    if (s->aos_live) L.aos_out = s->aos.p;
+    if (!prof) L.done = s->sortp.flight_event();
+    L.quad_entries = s->sortp.quad_entries();
+    fsd::launch_force(st, P, A, L);
+    if (pos_by_src) std::swap(s->pos, s->pos_s);   // the spare buffer now holds the state
     if (s->aos_live) s->aos_tick = s->tick;
     if (prof) {
         FS_HIP(hipEventRecord(ev[5], st));
         FS_HIP(hipEventRecord(ev[6], st));             // FS_PASS_BOUNDARY: slab handles only
-        s->prof_pending += 1;
+        s->prof.pending += 1;
     }
     if (prof) FS_HIP(s->sortp.step_enqueued(st));      // (the profile's own events are markers anyway)
     else s->sortp.step_bound();                        // the general force launch carried the step's completion event
@@ -556,13 +573,12 @@ fs_status slab_interior(fs_sim* s) {
     FS_HIP(hipEventRecord(s->ev_packed, st));      // the outgoing messages are complete: the exchange may start
     plan_overlap(s);
     const fsd::StepParams P = overlap_params(*s, false);
-    hipEvent_t* ev = s->slab_prof ? &s->ev[(size_t)s->prof_pending * (FS_PASS_COUNT + 1)] : nullptr;
+    hipEvent_t* ev = s->slab_prof ? s->prof.current() : nullptr;
     if (ev) FS_HIP(hipEventRecord(ev[1], st));
     fsd::launch_counting_sort_pairs(st, s->capacity, P.ncell, s->ncell, s->cs.p, s->csort.p, s->slab_counters.p, s->tick, nullptr, s->safe.p);
     if (ev) FS_HIP(hipEventRecord(ev[2], st));
-    fsd::launch_counting_reorder_slab(st, P, s->capacity, s->ncell, s->csort.p, s->pairs.p, s->cs.p, s->pos.p, s->vel.p, s->pos_s.p,
-                                      s->vel_s.p, s->pred.p, s->key.p, s->owned.p, s->start_ref.p, s->safe.p, s->fdefer.p,
-                                      s->counter.p + 4);
+    const fsd::StepArrays A = s->step_arrays();
+    fsd::launch_counting_reorder_slab(st, P, A, s->capacity, s->ncell);
     if (s->strip_active) {                          // the main array's share of the strips: also independent of the messages
         fs_sim::Strip& T = s->strip;
         fsd::launch_strip_gather(st, P, s->strip_win, s->slab_cfg.recv_capacity, T.cap, s->cs.p, T.rowbase.p, s->pairs.p, s->pos_s.p,
@@ -570,11 +586,9 @@ fs_status slab_interior(fs_sim* s) {
                                  fsd::counting_sort_hist(T.csort.p), T.back.p, T.safe.p, T.counters.p, s->slab_counters.p);
     }
     if (ev) FS_HIP(hipEventRecord(ev[3], st));
-    fsd::launch_density(st, P, s->pred.p, s->cs.p, s->start_ref.p, s->pairs.p, s->safe.p, s->rho.p, s->rho2.p, s->fdefer.p, s->fwork.p, s->counter.p + 4);
+    fsd::launch_density(st, P, A);
     if (ev) FS_HIP(hipEventRecord(ev[4], st));
-    fsd::launch_force(st, P, s->pos_s.p, s->vel_s.p, s->pred.p, s->rho2.p, s->cs.p, s->start_ref.p, s->pairs.p,
-                      s->tex.p, s->pos.p, s->vel.p, s->rho.p, s->fdefer.p, s->fwork.p, s->counter.p + 4, nullptr, s->side,
-                      s->ev_fork, s->ev_join, s->sortp.general_grid(), s->sortp.general_hint());
+    fsd::launch_force(st, P, A, s->force_launch());
     if (ev) FS_HIP(hipEventRecord(ev[5], st));
     FS_HIP(hipGetLastError());
     return FS_OK;
@@ -584,7 +598,7 @@ fs_status slab_interior(fs_sim* s) {
 fs_status slab_boundary(fs_sim* s, const void* recv_left, const void* recv_right) {
     hipStream_t st = s->stream;
     if (s->exch_pending) { FS_HIP(hipStreamWaitEvent(st, s->ev_exch, 0)); s->exch_pending = false; }
-    hipEvent_t* ev = s->slab_prof ? &s->ev[(size_t)s->prof_pending * (FS_PASS_COUNT + 1)] : nullptr;
+    hipEvent_t* ev = s->slab_prof ? s->prof.current() : nullptr;
     if (s->strip_active) {
         fs_sim::Strip& T = s->strip;
         const fsd::StepParams P = overlap_params(*s, false), PS = overlap_params(*s, true);
@@ -593,16 +607,17 @@ fs_status slab_boundary(fs_sim* s, const void* recv_left, const void* recv_right
                                  s->slab_cfg.has_right ? recv_right : nullptr, T.pos.p, T.vel.p, kt, fsd::counting_sort_hist(T.csort.p),
                                  T.back.p, T.counters.p, s->slab_counters.p);
         fsd::launch_counting_sort_pairs(st, T.cap, PS.ncell, s->ncell, T.cs.p, T.csort.p, T.counters.p, s->tick, T.counters.p + 2);
-        fsd::launch_counting_reorder_slab(st, PS, T.cap, s->ncell, T.csort.p, T.pairs.p, T.cs.p, T.pos.p, T.vel.p, T.pos_s.p, T.vel_s.p,
-                                          T.pred.p, (uint32_t*)nullptr, T.owned.p, T.start_ref.p, T.safe.p, T.fdefer.p, T.counter.p + 4,
-                                          T.counters.p + 2);
-        fsd::launch_density(st, PS, T.pred.p, T.cs.p, T.start_ref.p, T.pairs.p, T.safe.p, T.rho.p, T.rho2.p, T.fdefer.p, T.fwork.p, T.counter.p + 4);
-        fsd::launch_force(st, PS, T.pos_s.p, T.vel_s.p, T.pred.p, T.rho2.p, T.cs.p, T.start_ref.p, T.pairs.p, s->tex.p, T.pos_out.p,
-                          T.vel_out.p, T.rho.p, T.fdefer.p, T.fwork.p, T.counter.p + 4, nullptr, nullptr, nullptr, nullptr, 256u, nullptr);
+        fsd::StepArrays TA = T.step_arrays();
+        TA.tex = s->tex.p;
+        fsd::launch_counting_reorder_slab(st, PS, TA, T.cap, s->ncell);
+        fsd::launch_density(st, PS, TA);
+        fsd::ForceLaunch L;
+        L.general_grid = 256u;
+        fsd::launch_force(st, PS, TA, L);
         fsd::launch_strip_writeback(st, PS, s->slab_main, T.cap, T.pairs.p, T.back.p, T.pos_out.p, T.vel_out.p, T.pred.p, T.rho.p,
                                     s->pos.p, s->vel.p, s->pred.p, s->rho.p, s->key.p, s->owned.p, s->slab_counters.p);
     }
-    if (ev) { FS_HIP(hipEventRecord(ev[6], st)); s->prof_pending += 1; }
+    if (ev) { FS_HIP(hipEventRecord(ev[6], st)); s->prof.pending += 1; }
     FS_HIP(hipGetLastError());
     s->slab_packed = false;
     return FS_OK;
@@ -657,77 +672,30 @@ fs_status fs_create_ex(const fs_settings* settings, const fs_options* opts, fs_s
     if (opts->device < 0 || opts->device >= ndev) return fail(FS_ERR_INVALID, "device ordinal out of range");
     FS_HIP(hipSetDevice(opts->device));
 
-    fs_sim* s = new (std::nothrow) fs_sim();
+    std::unique_ptr<fs_sim> s(new (std::nothrow) fs_sim());     // an error exit frees whatever the handle holds by then
     if (!s) return fail(FS_ERR_OOM, "host allocation failed");
     s->settings = *settings;
     s->opts = *opts;
     s->device = opts->device;
     s->n = settings->particle_count;
     s->capacity = opts->capacity > s->n ? opts->capacity : s->n;
-    if (s->capacity > (1u << 28)) { delete s; return fail(FS_ERR_INVALID, "capacity > 2^28"); }
+    if (s->capacity > (1u << 28)) return fail(FS_ERR_INVALID, "capacity > 2^28");
     grid_dims(*settings, &s->grid_w, &s->grid_h);
     s->ncell = s->grid_w * s->grid_h;
     s->work_cap = s->ncell / 16u + 1024u;
-
-    auto bail = [&](fs_status st) { s->release(); delete s; return st; };
-#define FS_TRY(expr)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e__ = (expr);                                                                              \
-        if (e__ != hipSuccess)                                                                                \
-            return bail(fail(e__ == hipErrorOutOfMemory ? FS_ERR_OOM : FS_ERR_DEVICE,                         \
-                             std::string(#expr) + ": " + hipGetErrorString(e__)));                            \
-    } while (0)
-
-    FS_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    // The pre-registered general work can run beside the lean force kernel on a second stream (FS_SIDE_STREAM=1).
-    // Measured at 16M: force 0.725 -> 0.711 ms in the bench window and 1.10 -> 0.99 ms in the dense regime, but every
-    // launch of the following sort then pays ~1 us more behind the cross-stream join (sort 0.70 -> 0.73 ms): a net
-    // loss in the bench window, so it is off by default.
-    if (getenv("FS_SIDE_STREAM")) {
-        FS_TRY(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
-        FS_TRY(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
-        FS_TRY(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
-    }
-    const size_t cap = s->capacity;
-    FS_TRY(s->pos.alloc(cap)); FS_TRY(s->vel.alloc(cap)); FS_TRY(s->pos_s.alloc(cap)); FS_TRY(s->vel_s.alloc(cap));
-    FS_TRY(s->pred.alloc(cap + FS_PRED_SLACK)); FS_TRY(s->rho.alloc(cap)); FS_TRY(s->rho2.alloc(cap)); FS_TRY(s->key.alloc(cap)); FS_TRY(s->safe.alloc((cap + 63) / 64 + 1)); FS_TRY(s->fdefer.alloc(2 * ((cap + 255) / 256 + 8))); FS_TRY(s->fwork.alloc(2 * (cap / 256 + 8) + 16)); FS_TRY(s->bbounds.alloc(8 * ((cap + 255) / 256 + 8))); FS_TRY(s->pairs.alloc(cap));
-    FS_TRY(s->sort_dirty.alloc(fsd::sort_tile_count((uint32_t)cap)));
-    FS_TRY(hipMemsetAsync(s->sort_dirty.p, 0, s->sort_dirty.n * sizeof(uint32_t), s->stream));
-    FS_TRY(s->cs.alloc((size_t)s->ncell + 1));
-    FS_TRY(s->start_ref.alloc(s->ncell));
-    FS_TRY(s->tex.alloc((size_t)settings->texture_size.x * settings->texture_size.y));
-    FS_TRY(s->work.alloc((size_t)s->work_cap * fsd::gap_entry_size()));
-    FS_TRY(s->counter.alloc(8));
-    if (opts->sort_mode == FS_SORT_COUNTING) {
-        FS_TRY(s->csort.alloc(fsd::counting_sort_scratch_words((uint32_t)cap, s->ncell)));
-        FS_TRY(hipMemsetAsync(s->csort.p, 0, s->csort.n * sizeof(uint32_t), s->stream));   // histogram / tickets: zero between steps
-    }
-    FS_TRY(hipEventCreate(&s->t0));
-    FS_TRY(hipEventCreate(&s->t1));
-    FS_TRY(s->sortp.init(8));
-    // wgpu zero-initialises buffers: start_indices (simulation.rs:204-209), force field (:213-218)
-    FS_TRY(hipMemsetAsync(s->start_ref.p, 0, s->start_ref.n * sizeof(uint32_t), s->stream));
-    FS_TRY(hipMemsetAsync(s->cs.p, 0, s->cs.n * sizeof(uint32_t), s->stream));
-    if (s->tex.n) FS_TRY(hipMemsetAsync(s->tex.p, 0, s->tex.n * sizeof(float2), s->stream));
-    FS_TRY(hipMemsetAsync(s->counter.p, 0, 8 * sizeof(uint32_t), s->stream));
-    FS_TRY(hipMemsetAsync(s->rho.p, 0, cap * sizeof(float), s->stream));
-    FS_TRY(hipMemsetAsync(s->key.p, 0, cap * sizeof(uint32_t), s->stream));
+    { const fs_status r = create_common(s.get()); if (r != FS_OK) return r; }
+    FS_HIP(hipMemsetAsync(s->key.p, 0, s->capacity * sizeof(uint32_t), s->stream));
 
     // initial lattice (simulation.rs:147-163) -> AoS staging -> SoA
     {
         std::vector<fs_particle> host(s->n);
         host_lattice(*settings, opts->initial_offset, host.data(), host.size());
-        FS_TRY(s->aos.alloc(cap));
-        FS_TRY(hipMemcpyAsync(s->aos.p, host.data(), host.size() * sizeof(fs_particle), hipMemcpyHostToDevice, s->stream));
+        FS_HIP(hipMemcpyAsync(s->aos.p, host.data(), host.size() * sizeof(fs_particle), hipMemcpyHostToDevice, s->stream));
         fsd::launch_import_aos(s->stream, s->n, s->aos.p, s->pos.p, s->pred.p, s->vel.p, s->rho.p, s->key.p);
-        FS_TRY(hipStreamSynchronize(s->stream));
+        FS_HIP(hipStreamSynchronize(s->stream));
     }
-#undef FS_TRY
-    { fs_status r = prove_force_constants(s); if (r != FS_OK) { s->release(); delete s; return r; } }
-    fs_tick_settings t0;
-    std::memset(&t0, 0, sizeof t0);
-    host_uniform(*settings, t0, 0, &s->uniform);
-    *out = s;
+    { const fs_status r = create_finish(s.get()); if (r != FS_OK) return r; }
+    *out = s.release();
     return FS_OK;
 }
 
@@ -736,7 +704,6 @@ void fs_destroy(fs_sim* s) {
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     if (s->comm) (void)hipStreamSynchronize(s->comm);        // an exchange / edge chain still in flight reads this handle's buffers
-    s->release();
     delete s;
 }
 
@@ -1082,19 +1049,14 @@ fs_status fs_download_particles_by_id(fs_sim* s, fs_particle* dst, size_t n) {
 
 fs_status fs_profile_enable(fs_sim* s, int enable) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
-    s->profile = enable != 0;
+    s->prof.on = enable != 0;
     return FS_OK;
 }
 
 fs_status fs_profile_read(fs_sim* s, double ms[FS_PASS_COUNT], uint64_t* steps, int reset) {
     if (!s || !ms) return fail(FS_ERR_INVALID, "null argument");
     FS_JOIN(s);
-    fs_status r = drain_profile(s);
-    if (r != FS_OK) return r;
-    for (int k = 0; k < FS_PASS_COUNT; ++k) ms[k] = s->prof_ms[k];
-    if (steps) *steps = s->prof_steps;
-    if (reset) { for (auto& m : s->prof_ms) m = 0.0; s->prof_steps = 0; }
-    return FS_OK;
+    return s->prof.read(ms, steps, reset);
 }
 
 fs_status fs_timed_steps(fs_sim* s, const fs_tick_settings* t, uint32_t steps, double* ms_total) {
@@ -1288,7 +1250,7 @@ fs_status fs_slab_create(const fs_settings* settings, int device, const fs_slab_
     if (device < 0 || device >= ndev) return fail(FS_ERR_INVALID, "device ordinal out of range");
     FS_HIP(hipSetDevice(device));
 
-    fs_sim* s = new (std::nothrow) fs_sim();
+    std::unique_ptr<fs_sim> s(new (std::nothrow) fs_sim());     // an error exit frees whatever the handle holds by then
     if (!s) return fail(FS_ERR_OOM, "host allocation failed");
     s->settings = *settings;
     fs_options_default(&s->opts);
@@ -1322,55 +1284,25 @@ fs_status fs_slab_create(const fs_settings* settings, int device, const fs_slab_
     const uint32_t wmax = cfg->max_cols + 6u;
     s->ncell = wmax * gh;                       // allocation size of the local grid
     s->work_cap = s->ncell / 16u + 1024u;
-    auto bail = [&](fs_status st) { s->release(); delete s; return st; };
-#define FS_TRY(expr)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e__ = (expr);                                                                              \
-        if (e__ != hipSuccess)                                                                                \
-            return bail(fail(e__ == hipErrorOutOfMemory ? FS_ERR_OOM : FS_ERR_DEVICE,                         \
-                             std::string(#expr) + ": " + hipGetErrorString(e__)));                            \
-    } while (0)
-    FS_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    // The pre-registered general work can run beside the lean force kernel on a second stream (FS_SIDE_STREAM=1).
-    // Measured at 16M: force 0.725 -> 0.711 ms in the bench window and 1.10 -> 0.99 ms in the dense regime, but every
-    // launch of the following sort then pays ~1 us more behind the cross-stream join (sort 0.70 -> 0.73 ms): a net
-    // loss in the bench window, so it is off by default.
-    if (getenv("FS_SIDE_STREAM")) {
-        FS_TRY(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
-        FS_TRY(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
-        FS_TRY(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
-    }
-    FS_TRY(s->sortp.init(8));   // slab handles use the pinned words for the force pass's work report only (sort: per-stage plan)
+    { const fs_status r = create_common(s.get()); if (r != FS_OK) return r; }
     const size_t cap = s->capacity;
-    FS_TRY(s->pos.alloc(cap)); FS_TRY(s->vel.alloc(cap)); FS_TRY(s->pos_s.alloc(cap)); FS_TRY(s->vel_s.alloc(cap));
-    FS_TRY(s->pred.alloc(cap + FS_PRED_SLACK)); FS_TRY(s->rho.alloc(cap)); FS_TRY(s->rho2.alloc(cap)); FS_TRY(s->key.alloc(cap)); FS_TRY(s->safe.alloc((cap + 63) / 64 + 1)); FS_TRY(s->fdefer.alloc(2 * ((cap + 255) / 256 + 8))); FS_TRY(s->fwork.alloc(2 * (cap / 256 + 8) + 16)); FS_TRY(s->bbounds.alloc(8 * ((cap + 255) / 256 + 8))); FS_TRY(s->pairs.alloc(cap));
-    FS_TRY(s->sort_dirty.alloc(fsd::sort_tile_count((uint32_t)cap)));
-    FS_TRY(hipMemsetAsync(s->sort_dirty.p, 0, s->sort_dirty.n * sizeof(uint32_t), s->stream));
-    FS_TRY(s->owned.alloc(cap));
+    FS_HIP(s->owned.alloc(cap));
     const size_t nblocks = (cap + 255) / 256;
-    FS_TRY(s->blockcnt.alloc(2 * (nblocks + 1)));      // per 256-slot block: message counts, then message offsets (k_slab_msg)
-    FS_TRY(s->stage.alloc(fsd::slab_stage_words((uint32_t)cap)));
-    FS_TRY(s->msg_state.alloc(fsd::slab_msg_groups((uint32_t)cap) + 1));
-    FS_TRY(hipMemsetAsync(s->msg_state.p, 0, s->msg_state.n * sizeof(fsd::u64), s->stream));
-    FS_TRY(s->slab_counters.alloc(16));
-    FS_TRY(s->hist.alloc(gw));
-    FS_TRY(s->csort.alloc(fsd::counting_sort_scratch_words((uint32_t)cap, s->ncell)));
-    FS_TRY(hipMemsetAsync(s->csort.p, 0, s->csort.n * sizeof(uint32_t), s->stream));       // histogram / tickets: zero between steps
-    FS_TRY(s->cs.alloc((size_t)s->ncell + 1)); FS_TRY(s->start_ref.alloc(s->ncell));
-    FS_TRY(s->tex.alloc((size_t)settings->texture_size.x * settings->texture_size.y));
-    FS_TRY(s->work.alloc((size_t)s->work_cap * fsd::gap_entry_size()));
-    FS_TRY(s->counter.alloc(8));
-    FS_TRY(s->aos.alloc(cap));
-    FS_TRY(hipEventCreate(&s->t0)); FS_TRY(hipEventCreate(&s->t1));
+    FS_HIP(s->blockcnt.alloc(2 * (nblocks + 1)));      // per 256-slot block: message counts, then message offsets (k_slab_msg)
+    FS_HIP(s->stage.alloc(fsd::slab_stage_words((uint32_t)cap)));
+    FS_HIP(s->msg_state.alloc(fsd::slab_msg_groups((uint32_t)cap) + 1));
+    FS_HIP(hipMemsetAsync(s->msg_state.p, 0, s->msg_state.n * sizeof(fsd::u64), s->stream));
+    FS_HIP(s->slab_counters.alloc(16));
+    FS_HIP(s->hist.alloc(gw));
     if (s->overlap || s->edge_first) {
         int lo_prio = 0, hi_prio = 0;          // the exchange's kernel should not queue behind the interior columns' workgroups
         (void)hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio);
-        FS_TRY(hipStreamCreateWithPriority(&s->comm, hipStreamNonBlocking, hi_prio));
-        FS_TRY(hipEventCreateWithFlags(&s->ev_packed, hipEventDisableTiming));
-        FS_TRY(hipEventCreateWithFlags(&s->ev_exch, hipEventDisableTiming));
+        FS_HIP(hipStreamCreateWithPriority(&s->comm.h, hipStreamNonBlocking, hi_prio));
+        FS_HIP(hipEventCreateWithFlags(&s->ev_packed.h, hipEventDisableTiming));
+        FS_HIP(hipEventCreateWithFlags(&s->ev_exch.h, hipEventDisableTiming));
         // waited for by the exchange stream of this same device only: no system-scope fence (a write-back of every L2 behind the
         // reorder kernel, which the simulation's own stream would sit out)
-        FS_TRY(hipEventCreateWithFlags(&s->ev_fork2, hipEventDisableTiming | hipEventDisableSystemFence));
+        FS_HIP(hipEventCreateWithFlags(&s->ev_fork2.h, hipEventDisableTiming | hipEventDisableSystemFence));
         if (const char* e = getenv("FS_SLAB_BOUNDARY_COLS")) s->boundary_cols = (uint32_t)atoi(e) < 3u ? 3u : (uint32_t)atoi(e);
     }
     if (s->overlap) {
@@ -1378,39 +1310,26 @@ fs_status fs_slab_create(const fs_settings* settings, int device, const fs_slab_
         // same capacity as the main array (memory is not the constraint: ~100 B per slot); its kernels cover the slots in use only.
         fs_sim::Strip& T = s->strip;
         T.cap = (uint32_t)cap;
-        FS_TRY(T.pos.alloc(cap)); FS_TRY(T.vel.alloc(cap)); FS_TRY(T.pos_s.alloc(cap)); FS_TRY(T.vel_s.alloc(cap));
-        FS_TRY(T.pred.alloc(cap + FS_PRED_SLACK)); FS_TRY(T.rho2.alloc(cap)); FS_TRY(T.pos_out.alloc(cap)); FS_TRY(T.vel_out.alloc(cap));
-        FS_TRY(T.rho.alloc(cap)); FS_TRY(T.pairs.alloc(cap)); FS_TRY(T.safe.alloc((cap + 63) / 64 + 1)); FS_TRY(T.owned.alloc(cap));
-        FS_TRY(T.fdefer.alloc(2 * ((cap + 255) / 256 + 8))); FS_TRY(T.fwork.alloc(2 * (cap / 256 + 8) + 16));
-        FS_TRY(T.bbounds.alloc(8 * ((cap + 255) / 256 + 8)));
-        FS_TRY(T.csort.alloc(fsd::counting_sort_scratch_words((uint32_t)cap, s->ncell)));
-        FS_TRY(hipMemsetAsync(T.csort.p, 0, T.csort.n * sizeof(uint32_t), s->stream));
-        FS_TRY(T.cs.alloc((size_t)s->ncell + 1)); FS_TRY(T.start_ref.alloc(s->ncell));
-        FS_TRY(T.counter.alloc(8)); FS_TRY(T.counters.alloc(8)); FS_TRY(T.back.alloc(cap)); FS_TRY(T.rowbase.alloc(2 * (size_t)gh + 2));
-        FS_TRY(hipMemsetAsync(T.cs.p, 0, T.cs.n * sizeof(uint32_t), s->stream));
-        FS_TRY(hipMemsetAsync(T.counter.p, 0, 8 * sizeof(uint32_t), s->stream));
-        FS_TRY(hipMemsetAsync(T.counters.p, 0, 8 * sizeof(uint32_t), s->stream));
-        FS_TRY(hipMemsetAsync(T.pred.p, 0, (cap + FS_PRED_SLACK) * sizeof(float2), s->stream));
-        FS_TRY(hipMemsetAsync(T.pairs.p, 0xFF, cap * sizeof(fsd::u64), s->stream));
+        FS_HIP(T.alloc_common(cap)); FS_HIP(T.pos_out.alloc(cap)); FS_HIP(T.vel_out.alloc(cap)); FS_HIP(T.owned.alloc(cap));
+        FS_HIP(T.csort.alloc(fsd::counting_sort_scratch_words((uint32_t)cap, s->ncell)));
+        FS_HIP(hipMemsetAsync(T.csort.p, 0, T.csort.n * sizeof(uint32_t), s->stream));
+        FS_HIP(T.cs.alloc((size_t)s->ncell + 1)); FS_HIP(T.start_ref.alloc(s->ncell));
+        FS_HIP(T.counters.alloc(8)); FS_HIP(T.back.alloc(cap)); FS_HIP(T.rowbase.alloc(2 * (size_t)gh + 2));
+        FS_HIP(hipMemsetAsync(T.cs.p, 0, T.cs.n * sizeof(uint32_t), s->stream));
+        FS_HIP(hipMemsetAsync(T.counter.p, 0, 8 * sizeof(uint32_t), s->stream));
+        FS_HIP(hipMemsetAsync(T.counters.p, 0, 8 * sizeof(uint32_t), s->stream));
+        FS_HIP(hipMemsetAsync(T.pred.p, 0, (cap + FS_PRED_SLACK) * sizeof(float2), s->stream));
+        FS_HIP(hipMemsetAsync(T.pairs.p, 0xFF, cap * sizeof(fsd::u64), s->stream));
     }
-    FS_TRY(hipMemsetAsync(s->start_ref.p, 0, s->start_ref.n * sizeof(uint32_t), s->stream));
-    FS_TRY(hipMemsetAsync(s->cs.p, 0, s->cs.n * sizeof(uint32_t), s->stream));
-    if (s->tex.n) FS_TRY(hipMemsetAsync(s->tex.p, 0, s->tex.n * sizeof(float2), s->stream));
-    FS_TRY(hipMemsetAsync(s->counter.p, 0, 8 * sizeof(uint32_t), s->stream));
-    FS_TRY(hipMemsetAsync(s->slab_counters.p, 0, 16 * sizeof(uint32_t), s->stream));
-    FS_TRY(hipMemsetAsync(s->owned.p, 0, cap, s->stream));
-    FS_TRY(hipMemsetAsync(s->rho.p, 0, cap * sizeof(float), s->stream));
-    FS_TRY(hipMemsetAsync(s->pos.p, 0, cap * sizeof(float2), s->stream));
-    FS_TRY(hipMemsetAsync(s->vel.p, 0, cap * sizeof(float2), s->stream));
-    FS_TRY(hipMemsetAsync(s->pred.p, 0, cap * sizeof(float2), s->stream));
-    FS_TRY(hipMemsetAsync(s->key.p, 0xFF, cap * sizeof(uint32_t), s->stream));
-    FS_TRY(hipStreamSynchronize(s->stream));
-#undef FS_TRY
-    { fs_status r = prove_force_constants(s); if (r != FS_OK) { s->release(); delete s; return r; } }
-    fs_tick_settings t0;
-    std::memset(&t0, 0, sizeof t0);
-    host_uniform(*settings, t0, 0, &s->uniform);
-    *out = s;
+    FS_HIP(hipMemsetAsync(s->slab_counters.p, 0, 16 * sizeof(uint32_t), s->stream));
+    FS_HIP(hipMemsetAsync(s->owned.p, 0, cap, s->stream));
+    FS_HIP(hipMemsetAsync(s->pos.p, 0, cap * sizeof(float2), s->stream));
+    FS_HIP(hipMemsetAsync(s->vel.p, 0, cap * sizeof(float2), s->stream));
+    FS_HIP(hipMemsetAsync(s->pred.p, 0, cap * sizeof(float2), s->stream));
+    FS_HIP(hipMemsetAsync(s->key.p, 0xFF, cap * sizeof(uint32_t), s->stream));
+    FS_HIP(hipStreamSynchronize(s->stream));
+    { const fs_status r = create_finish(s.get()); if (r != FS_OK) return r; }
+    *out = s.release();
     return FS_OK;
 }
 
@@ -1503,12 +1422,11 @@ fs_status fs_slab_pack(fs_sim* s, const fs_tick_settings* t, void* send_left, vo
     s->tick += 1;
     host_uniform(s->settings, *t, s->tick, &s->uniform);
     const fsd::StepParams P = make_params(*s);
-    s->slab_prof = s->profile;             // a toggle between pack and step must not leave ev[0] unrecorded
+    s->slab_prof = s->prof.on;             // a toggle between pack and step must not leave ev[0] unrecorded
     if (s->slab_prof) {
-        fs_status r = ensure_events(s);
+        const fs_status r = s->prof.begin();
         if (r != FS_OK) return r;
-        if (s->prof_pending == fs_sim::PROF_RING) { r = drain_profile(s); if (r != FS_OK) return r; }
-        FS_HIP(hipEventRecord(s->ev[(size_t)s->prof_pending * (FS_PASS_COUNT + 1)], s->stream));
+        FS_HIP(hipEventRecord(s->prof.current()[0], s->stream));
     }
     const bool counting = s->opts.sort_mode == FS_SORT_COUNTING;
     // edge-first step: are the messages of this tick already in the send buffers (built by the last fs_slab_step)?  Only if
@@ -1553,7 +1471,7 @@ fs_status fs_slab_step(fs_sim* s, const void* recv_left, const void* recv_right)
     if (s->overlap) return slab_boundary(s, recv_left, recv_right);
     const fsd::StepParams P = make_params(*s);
     hipStream_t st = s->stream;
-    hipEvent_t* ev = s->slab_prof ? &s->ev[(size_t)s->prof_pending * (FS_PASS_COUNT + 1)] : nullptr;
+    hipEvent_t* ev = s->slab_prof ? s->prof.current() : nullptr;
     const bool counting = s->opts.sort_mode == FS_SORT_COUNTING;
     // the exchange was enqueued on the exchange stream behind the edge columns' chain: its event stands for the join as well
     if (s->exch_pending) { FS_HIP(hipStreamWaitEvent(st, s->ev_exch, 0)); s->exch_pending = false; s->join_pending = false; }
@@ -1577,14 +1495,11 @@ fs_status fs_slab_step(fs_sim* s, const void* recv_left, const void* recv_right)
         plan_overlap(s);
         forked = s->transposed && s->adv_lo < s->adv_hi;      // the edge columns' chain forks off behind the reorder pass (below)
     }
+    const fsd::StepArrays A = s->step_arrays();
     if (counting)
-        fsd::launch_counting_reorder_slab(st, P, s->capacity, s->ncell, s->csort.p, s->pairs.p, s->cs.p, s->pos.p, s->vel.p, s->pos_s.p,
-                                          s->vel_s.p, s->pred.p, s->key.p, s->owned.p, s->start_ref.p, s->safe.p, s->fdefer.p,
-                                          s->counter.p + 4, nullptr, forked ? s->ev_fork2 : nullptr);
+        fsd::launch_counting_reorder_slab(st, P, A, s->capacity, s->ncell, forked ? s->ev_fork2.h : nullptr);
     else
-        fsd::launch_slab_reorder(st, P, s->capacity, s->pairs.p, s->pos.p, s->vel.p, s->pos_s.p, s->vel_s.p, s->pred.p,
-                                 s->key.p, s->owned.p, s->cs.p, s->start_ref.p, s->work.p, s->counter.p, s->work_cap,
-                                 s->slab_counters.p, s->safe.p, s->fdefer.p, s->counter.p + 4);
+        fsd::launch_slab_reorder(st, P, A, s->capacity, s->work_cap, s->slab_counters.p);
     if (ev) FS_HIP(hipEventRecord(ev[3], st));
     if (edge_step) {
         if (forked) {
@@ -1595,12 +1510,13 @@ fs_status fs_slab_step(fs_sim* s, const void* recv_left, const void* recv_right)
             fsd::StepParams PD = P;
             PD.adv_lo = s->adv_lo; PD.adv_hi = s->adv_hi;
             FS_HIP(hipStreamWaitEvent(s->comm, s->ev_fork2, 0));     // signalled by the reorder kernel itself
-            fsd::launch_density(s->comm, PD, s->pred.p, s->cs.p, s->start_ref.p, s->pairs.p, s->safe.p, s->rho.p, s->rho2.p, s->fdefer.p,
-                                s->fwork.p, s->counter.p + 4, FS_EDGE_GRID);
+            fsd::launch_density(s->comm, PD, A, FS_EDGE_GRID);
         }
     }
-    fsd::launch_density(st, P, s->pred.p, s->cs.p, s->start_ref.p, s->pairs.p, s->safe.p, s->rho.p, s->rho2.p, s->fdefer.p, s->fwork.p, s->counter.p + 4);
+    fsd::launch_density(st, P, A);
     if (ev) FS_HIP(hipEventRecord(ev[4], st));
+    fsd::ForceLaunch LI = s->force_launch();     // the launch on the simulation's stream: every owned column, or the interior ones
+    LI.quad_entries = s->sortp.quad_entries();
     if (edge_step) {
         // Edge-first step.  Behind the density pass the stream forks: the handle's exchange stream (high priority) advances
         // the owned columns within boundary_cols of a neighboured edge — a few hundred blocks, latency-bound — then builds the
@@ -1617,15 +1533,12 @@ fs_status fs_slab_step(fs_sim* s, const void* recv_left, const void* recv_right)
         if (!forked) FS_HIP(hipEventRecord(s->ev_fork2, st));
         // the simulation's stream first (its force launch is the long one: the host must not leave that stream empty while it
         // enqueues the six launches of the edge chain — seen under the profiler, where a launch costs 10 us), then the chain
-        if (s->adv_lo < s->adv_hi)
-            fsd::launch_force(st, PI, s->pos_s.p, s->vel_s.p, s->pred.p, s->rho2.p, s->cs.p, s->start_ref.p, s->pairs.p,
-                              s->tex.p, s->pos.p, s->vel.p, s->rho.p, s->fdefer.p, s->fwork.p, s->counter.p + 4, nullptr, s->side,
-                              s->ev_fork, s->ev_join, s->sortp.general_grid(), s->sortp.general_hint(), 0u, nullptr, s->sortp.quad_entries());
+        if (s->adv_lo < s->adv_hi) fsd::launch_force(st, PI, A, LI);
         if (ev) FS_HIP(hipEventRecord(ev[5], st));      // FS_PASS_FORCE: the interior launch
         if (!forked) FS_HIP(hipStreamWaitEvent(es, s->ev_fork2, 0));
-        fsd::launch_force(es, PE, s->pos_s.p, s->vel_s.p, s->pred.p, s->rho2.p, s->cs.p, s->start_ref.p, s->pairs.p,
-                          s->tex.p, s->pos.p, s->vel.p, s->rho.p, s->fdefer.p, s->fwork.p, s->counter.p + 4, nullptr, nullptr,
-                          nullptr, nullptr, 256u, nullptr, eg);
+        fsd::ForceLaunch LE;                 // the chain's own launches: one stream, a small general grid
+        LE.general_grid = 256u; LE.edge_grid = eg;
+        fsd::launch_force(es, PE, A, LE);
         {   // what fs_slab_pack will see at tick + 1, if nothing changes in between (it checks)
             fs_uniform un;
             host_uniform(s->settings, s->last_tick, s->tick + 1, &un);
@@ -1647,12 +1560,10 @@ fs_status fs_slab_step(fs_sim* s, const void* recv_left, const void* recv_right)
         // no join here: the next fs_slab_pack leaves the edge columns' slots alone, and fs_slab_step waits for the exchange that
         // follows their chain on the exchange stream; anything else that touches the state joins first (slab_join)
         s->join_pending = true;
-        if (ev) { FS_HIP(hipEventRecord(ev[6], st)); s->prof_pending += 1; }     // FS_PASS_BOUNDARY: nothing left on this stream
+        if (ev) { FS_HIP(hipEventRecord(ev[6], st)); s->prof.pending += 1; }     // FS_PASS_BOUNDARY: nothing left on this stream
     } else {
-        fsd::launch_force(st, P, s->pos_s.p, s->vel_s.p, s->pred.p, s->rho2.p, s->cs.p, s->start_ref.p, s->pairs.p,
-                          s->tex.p, s->pos.p, s->vel.p, s->rho.p, s->fdefer.p, s->fwork.p, s->counter.p + 4, nullptr, s->side,
-                          s->ev_fork, s->ev_join, s->sortp.general_grid(), s->sortp.general_hint(), 0u, nullptr, s->sortp.quad_entries());
-        if (ev) { FS_HIP(hipEventRecord(ev[5], st)); FS_HIP(hipEventRecord(ev[6], st)); s->prof_pending += 1; }
+        fsd::launch_force(st, P, A, LI);
+        if (ev) { FS_HIP(hipEventRecord(ev[5], st)); FS_HIP(hipEventRecord(ev[6], st)); s->prof.pending += 1; }
     }
     FS_HIP(hipGetLastError());
     s->slab_packed = false;

@@ -8,39 +8,61 @@
 
 namespace fsd {
 
-void launch_reorder(hipStream_t st, const StepParams& P, const u64* pairs, const float2* pos_in, const float2* vel_in,
-                    float2* pos_s, float2* vel_s, float2* pred_s, uint32_t* key_s, uint32_t* cs, uint32_t* start_ref,
-                    void* work, uint32_t* counter, uint32_t work_cap, unsigned long long* safe /* kin_safe: one bit per sorted particle, a word per wave */,
-                    uint32_t* force_defer /* two words per 256-particle block */, uint32_t* force_work_count /* [2] */,
-                    bool cs_ready = false);
+// The device arrays the sort-reorder, density, surface-tension and force passes of ONE particle array read and write (the main
+// array of a handle, or the boundary strip of an overlapped slab step).  Fields carry the name of the role the passes see;
+// a handle fills the set in one place and a call site overrides what differs for its launch.  Host side only: the launchers
+// unpack it into the kernels' own parameter lists.
+struct StepArrays {
+    const float2* pos = nullptr;       // state before the step (cell order of the last step): what the reorder passes gather from
+    const float2* vel = nullptr;
+    float2* pos_s = nullptr;           // cell-sorted snapshot the density / force passes read (Jacobi semantics); pos_s == nullptr:
+    float2* vel_s = nullptr;           //   the reorder pass keeps no sorted copy of the positions (StepParams::pos_by_src)
+    float2* pred = nullptr;            // sorted predicted positions, + FS_PRED_SLACK entries
+    float* rho = nullptr;              // densities; nullptr: the density pass leaves them in rho2.x only (strict / ulp modes)
+    float2* rho2 = nullptr;            // {rho, +-RN(1/rho)}: the sign is the particle's safe-operand classification
+    u64* pairs = nullptr;              // sorted (key << 32 | source slot)
+    uint32_t* cs = nullptr;            // dense cell-start table, ncell + 1
+    uint32_t* start_ref = nullptr;     // reference start_indices (persistent, never cleared)
+    unsigned long long* safe = nullptr;   // kin_safe: one bit per sorted particle, a word per wave
+    uint32_t* fdefer = nullptr;        // force pass: per-block deferred-wave bits, two words per 256-particle block
+    uint32_t* fwork = nullptr;         // ... its worklist (per block)
+    uint32_t* fcount = nullptr;        // ... and its work counters [2]: pre-registered waves
+    float2* pos_out = nullptr;         // the force pass's output: the new state
+    float2* vel_out = nullptr;
+    const float2* tex = nullptr;       // obstacle push-out field
+    uint32_t* key_s = nullptr;         // sorted keys, or nullptr: they stay in the high words of `pairs` only
+    unsigned char* owned = nullptr;    // slab reorders: owned flag per sorted slot
+    uint32_t* csort = nullptr;         // counting sort: its scratch (launch_counting_reorder*)
+    const uint32_t* n_dev = nullptr;   // launch_counting_reorder_slab: device word holding the number of slots in use (<= cap;
+                                       //   the grids still cover `cap`), or nullptr
+    void* work = nullptr;              // network sort: the gap worklist of the reorder pass ...
+    uint32_t* counter = nullptr;       // ... and its counter
+};
+
+void launch_reorder(hipStream_t st, const StepParams& P, const StepArrays& A, uint32_t work_cap, bool cs_ready = false);
 // the chunked sweep of k_force reads up to 35 candidates past a row range when it scans global memory
 #define FS_PRED_SLACK 64
-void launch_density(hipStream_t st, const StepParams& P, const float2* pred, const uint32_t* cs,
-                    const uint32_t* start_ref, const u64* pairs, const unsigned long long* safe, float* rho,
-                    float2* rho2 /* {rho, +-RN(1/rho)}: the sign is the particle's safe-operand classification */,
-                    uint32_t* force_defer, uint32_t* force_work, uint32_t* force_count /* force pass: pre-registered waves */,
+void launch_density(hipStream_t st, const StepParams& P, const StepArrays& A,
                     uint32_t edge_grid = 0 /* != 0: edge-first slab step, column-major ids: only the blocks of the edge columns (+1), walked by this many workgroups */);
-void launch_force(hipStream_t st, const StepParams& P, const float2* pos_s, const float2* vel_s, const float2* pred,
-                  const float2* rho2, const uint32_t* cs, const uint32_t* start_ref, const u64* pairs, const float2* tex,
-                  float2* pos_out, float2* vel_out, const float* rho_arr, uint32_t* defer_bits /* per block */,
-                  uint32_t* worklist /* per block */, uint32_t* work_count,
-                  void* aos_out = nullptr /* 32-B ParticleInstance records, or none */,
-                  hipStream_t side = nullptr /* second stream: the pre-registered general work runs beside the lean kernel */,
-                  hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr,
-                  uint32_t general_grid = 0 /* workgroups of the general kernel; 0: the full grid */,
-                  uint32_t* general_hint = nullptr /* host-visible word: entries the general kernel found in its lists */,
-                  uint32_t edge_grid = 0 /* != 0: the lean kernel walks only the blocks of the edge columns with this many workgroups */,
-                  hipEvent_t done = nullptr /* completes with the LAST launch of the pass (its own completion signal: no marker packet) */,
-                  uint32_t quad_entries = 0 /* != 0: the pre-registered list is expected to hold about this many blocks, few enough for
-                                               k_force_quad (four lanes per particle) */,
-                  const float2* st_in = nullptr /* != nullptr (single-domain handles): the surface-tension force of each sorted slot,
-                                                   launch_surface_tension's output, is added to the force sum (the ST instantiations) */);
+// Per-launch choices of the force pass (not state): name what a call site sets.
+struct ForceLaunch {
+    void* aos_out = nullptr;           // 32-B ParticleInstance records, or none
+    hipStream_t side = nullptr;        // second stream: the pre-registered general work runs beside the lean kernel
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    uint32_t general_grid = 0;         // workgroups of the general kernel; 0: the full grid
+    uint32_t* general_hint = nullptr;  // host-visible word: entries the general kernel found in its lists
+    uint32_t edge_grid = 0;            // != 0: the lean kernel walks only the blocks of the edge columns with this many workgroups
+    hipEvent_t done = nullptr;         // completes with the LAST launch of the pass (its own completion signal: no marker packet)
+    uint32_t quad_entries = 0;         // != 0: the pre-registered list is expected to hold about this many blocks, few enough for
+                                       // k_force_quad (four lanes per particle)
+    const float2* st_in = nullptr;     // != nullptr (single-domain handles): the surface-tension force of each sorted slot,
+                                       // launch_surface_tension's output, is added to the force sum (the ST instantiations)
+};
+void launch_force(hipStream_t st, const StepParams& P, const StepArrays& A, const ForceLaunch& L = ForceLaunch());
 // Surface tension (build extension): st_out[i] = the colour-field CSF force of sorted slot i, from this step's
-// densities (rho2; rho != nullptr: tolerance mode, densities in rho) over the density pass's neighbour walk.  Single-domain handles.
+// densities (rho2; A.rho != nullptr: tolerance mode, densities in rho) over the density pass's neighbour walk.  Single-domain handles.
 // cg = poly6_kernel_derivative (24/(pi h^8)); sigma = surface_tension_coefficient, tau = surface_tension_treshold.
-void launch_surface_tension(hipStream_t st, const StepParams& P, float sigma, float tau, float cg, const float2* pred,
-                            const float2* rho2, const float* rho, const uint32_t* cs, const uint32_t* start_ref, const u64* pairs,
-                            float2* st_out);
+void launch_surface_tension(hipStream_t st, const StepParams& P, const StepArrays& A, float sigma, float tau, float cg, float2* st_out);
 // Particle tracking (build extension): after the reorder pass of a step, id_out[i] = id_in[src] and, for c < channels,
 // attr_out[c * stride + i] = attr_in[c * stride + src], src = the low word of pairs[i] (the slot before the step).  channels in [0, 4].
 void launch_track_carry(hipStream_t st, uint32_t n, int channels, const u64* pairs, const uint32_t* id_in, uint32_t* id_out,
@@ -112,11 +134,7 @@ size_t slab_msg_groups(uint32_t cap);
 void launch_slab_unpack(hipStream_t st, const StepParams& P, uint32_t main_slots, uint32_t R, const void* msg_left,
                         const void* msg_right, float2* pos, float2* vel, u64* out, uint32_t* hist, uint32_t* counters,
                         bool counting);
-void launch_slab_reorder(hipStream_t st, const StepParams& P, uint32_t cap, const u64* pairs, const float2* pos_in,
-                         const float2* vel_in, float2* pos_s, float2* vel_s, float2* pred_s, uint32_t* key_s,
-                         unsigned char* owned, uint32_t* cs, uint32_t* start_ref, void* work, uint32_t* counter,
-                         uint32_t work_cap, uint32_t* n_live_out, unsigned long long* safe, uint32_t* force_defer,
-                         uint32_t* force_work_count);
+void launch_slab_reorder(hipStream_t st, const StepParams& P, const StepArrays& A, uint32_t cap, uint32_t work_cap, uint32_t* n_live_out);
 void launch_slab_export(hipStream_t st, const StepParams& P, uint32_t cap, const float2* pos, const float2* pred,
                         const float2* vel, const float* rho, const uint32_t* key, void* out);
 void launch_slab_import(hipStream_t st, const StepParams& P, uint32_t n, uint32_t cap, const void* in, float2* pos,
@@ -164,18 +182,12 @@ u64* counting_sort_kt(uint32_t* scratch, uint32_t n, uint32_t ncell_alloc);
 uint32_t* counting_sort_hist(uint32_t* scratch);
 void launch_counting_sort(hipStream_t st, const StepParams& P, const float2* pos, const float2* vel, uint32_t* cs,
                           uint32_t* scratch, uint32_t* gap_counter, unsigned long long* safe, uint32_t epoch);
-void launch_counting_reorder(hipStream_t st, const StepParams& P, uint32_t* scratch, u64* pairs, const uint32_t* cs,
-                             const float2* pos_in, const float2* vel_in, float2* pos_s, float2* vel_s, float2* pred_s,
-                             uint32_t* key_s, uint32_t* start_ref, unsigned long long* safe, uint32_t* force_defer,
-                             uint32_t* force_work_count);
-// n_dev (may be null): device word holding the number of slots in use (<= cap); the grids still cover `cap`
+void launch_counting_reorder(hipStream_t st, const StepParams& P, const StepArrays& A);
+// n_dev (may be null): as StepArrays::n_dev
 void launch_counting_sort_pairs(hipStream_t st, uint32_t cap, uint32_t ncell, uint32_t ncell_alloc, uint32_t* cs, uint32_t* scratch,
                                 uint32_t* n_live_out, uint32_t epoch, const uint32_t* n_dev = nullptr,
                                 unsigned long long* safe_preset = nullptr /* the slots' "safe operand" words, set to all-ones for k_cs_fixreorder */);
-void launch_counting_reorder_slab(hipStream_t st, const StepParams& P, uint32_t cap, uint32_t ncell_alloc, uint32_t* scratch, u64* pairs,
-                                  const uint32_t* cs, const float2* pos_in, const float2* vel_in, float2* pos_s, float2* vel_s,
-                                  float2* pred_s, uint32_t* key_s, unsigned char* owned, uint32_t* start_ref,
-                                  unsigned long long* safe, uint32_t* force_defer, uint32_t* force_work_count,
-                                  const uint32_t* n_dev = nullptr, hipEvent_t done = nullptr /* signalled by the kernel's completion */);
+void launch_counting_reorder_slab(hipStream_t st, const StepParams& P, const StepArrays& A, uint32_t cap, uint32_t ncell_alloc,
+                                  hipEvent_t done = nullptr /* signalled by the kernel's completion */);
 
 }  // namespace fsd

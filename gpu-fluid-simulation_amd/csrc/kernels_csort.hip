@@ -309,22 +309,19 @@ void launch_counting_sort_pairs(hipStream_t st, uint32_t cap, uint32_t ncell, ui
     hipLaunchKernelGGL(k_cs_scatter, dim3((cap + CS_BLOCK * SC_ITEMS - 1) / (CS_BLOCK * SC_ITEMS)), dim3(CS_BLOCK), 0, st, cap, ncell, L.kt, cs, L.slot_src, n_dev, safe_preset);
 }
 uint32_t* counting_sort_slot_src(uint32_t* scratch, uint32_t n, uint32_t ncell_alloc) { return cs_layout(scratch, n, ncell_alloc).slot_src; }
-void launch_counting_reorder_slab(hipStream_t st, const StepParams& P, uint32_t cap, uint32_t ncell_alloc, uint32_t* scratch, u64* pairs,
-                                  const uint32_t* cs, const float2* pos_in, const float2* vel_in, float2* pos_s, float2* vel_s,
-                                  float2* pred_s, uint32_t* key_s, unsigned char* owned, uint32_t* start_ref,
-                                  unsigned long long* safe, uint32_t* force_defer, uint32_t* force_work_count,
-                                  const uint32_t* n_dev, hipEvent_t done) {
-    const CsLayout L = cs_layout(scratch, cap, ncell_alloc);
+void launch_counting_reorder_slab(hipStream_t st, const StepParams& P, const StepArrays& A, uint32_t cap, uint32_t ncell_alloc,
+                                  hipEvent_t done) {
+    const CsLayout L = cs_layout(A.csort, cap, ncell_alloc);
     if (done) {   // the kernel's own completion signal is the event: no separate barrier packet in the stream (hipEventRecord costs
                   // the following kernel ~6 us of idle queue)
         hipExtLaunchKernelGGL(k_cs_fixreorder<true>, dim3((cap + CS_BLOCK - 1) / CS_BLOCK), dim3(CS_BLOCK), 0, st, nullptr, done, 0, P, cap,
-                              L.kt, cs, L.slot_src, pairs, pos_in, vel_in, pos_s, vel_s, pred_s, key_s, owned, start_ref, safe, force_defer,
-                              force_work_count, n_dev);
+                              L.kt, (const uint32_t*)A.cs, L.slot_src, A.pairs, A.pos, A.vel, A.pos_s, A.vel_s, A.pred, A.key_s, A.owned,
+                              A.start_ref, A.safe, A.fdefer, A.fcount, A.n_dev);
         return;
     }
-    hipLaunchKernelGGL(k_cs_fixreorder<true>, dim3((cap + CS_BLOCK - 1) / CS_BLOCK), dim3(CS_BLOCK), 0, st, P, cap, L.kt, cs,
-                       L.slot_src, pairs, pos_in, vel_in, pos_s, vel_s, pred_s, key_s, owned, start_ref, safe, force_defer, force_work_count,
-                       n_dev);
+    hipLaunchKernelGGL(k_cs_fixreorder<true>, dim3((cap + CS_BLOCK - 1) / CS_BLOCK), dim3(CS_BLOCK), 0, st, P, cap, L.kt, A.cs,
+                       L.slot_src, A.pairs, A.pos, A.vel, A.pos_s, A.vel_s, A.pred, A.key_s, A.owned, A.start_ref, A.safe, A.fdefer, A.fcount,
+                       A.n_dev);
 }
 
 void launch_counting_sort(hipStream_t st, const StepParams& P, const float2* pos, const float2* vel, uint32_t* cs,
@@ -337,14 +334,11 @@ void launch_counting_sort(hipStream_t st, const StepParams& P, const float2* pos
                        epoch, (uint32_t*)nullptr);
     hipLaunchKernelGGL(k_cs_scatter, dim3((n + CS_BLOCK * SC_ITEMS - 1) / (CS_BLOCK * SC_ITEMS)), block, 0, st, n, ncell, L.kt, cs, L.slot_src, (const uint32_t*)nullptr, (unsigned long long*)nullptr);
 }
-void launch_counting_reorder(hipStream_t st, const StepParams& P, uint32_t* scratch, u64* pairs, const uint32_t* cs,
-                             const float2* pos_in, const float2* vel_in, float2* pos_s, float2* vel_s, float2* pred_s,
-                             uint32_t* key_s, uint32_t* start_ref, unsigned long long* safe, uint32_t* force_defer,
-                             uint32_t* force_work_count) {
-    const CsLayout L = cs_layout(scratch, P.n, P.ncell);
-    hipLaunchKernelGGL(k_cs_fixreorder<false>, dim3((P.n + CS_BLOCK - 1) / CS_BLOCK), dim3(CS_BLOCK), 0, st, P, P.n, L.kt, cs,
-                       L.slot_src, pairs, pos_in, vel_in, pos_s, vel_s, pred_s, key_s, (unsigned char*)nullptr, start_ref, safe,
-                       force_defer, force_work_count, (const uint32_t*)nullptr);
+void launch_counting_reorder(hipStream_t st, const StepParams& P, const StepArrays& A) {
+    const CsLayout L = cs_layout(A.csort, P.n, P.ncell);
+    hipLaunchKernelGGL(k_cs_fixreorder<false>, dim3((P.n + CS_BLOCK - 1) / CS_BLOCK), dim3(CS_BLOCK), 0, st, P, P.n, L.kt, A.cs,
+                       L.slot_src, A.pairs, A.pos, A.vel, A.pos_s, A.vel_s, A.pred, A.key_s, (unsigned char*)nullptr, A.start_ref, A.safe,
+                       A.fdefer, A.fcount, (const uint32_t*)nullptr);
 }
 
 }  // namespace fsd

@@ -759,14 +759,10 @@ void launch_slab_unpack(hipStream_t st, const StepParams& P, uint32_t main_slots
 }
 
 // bitonic slab mode only (the counting sort's k_cs_fixreorder<true> does the reorder itself)
-void launch_slab_reorder(hipStream_t st, const StepParams& P, uint32_t cap, const u64* pairs, const float2* pos_in,
-                         const float2* vel_in, float2* pos_s, float2* vel_s, float2* pred_s, uint32_t* key_s,
-                         unsigned char* owned, uint32_t* cs, uint32_t* start_ref, void* work, uint32_t* counter,
-                         uint32_t work_cap, uint32_t* n_live_out, unsigned long long* safe, uint32_t* force_defer,
-                         uint32_t* force_work_count) {
-    hipLaunchKernelGGL(k_slab_reorder, dim3(nb(cap)), dim3(SL_BLOCK), 0, st, P, cap, pairs, pos_in, vel_in, pos_s,
-                       vel_s, pred_s, key_s, owned, cs, start_ref, (GapEntry*)work, counter, work_cap, n_live_out, safe, force_defer, force_work_count);
-    launch_fill_gaps(st, cs, work, counter, work_cap);
+void launch_slab_reorder(hipStream_t st, const StepParams& P, const StepArrays& A, uint32_t cap, uint32_t work_cap, uint32_t* n_live_out) {
+    hipLaunchKernelGGL(k_slab_reorder, dim3(nb(cap)), dim3(SL_BLOCK), 0, st, P, cap, A.pairs, A.pos, A.vel, A.pos_s,
+                       A.vel_s, A.pred, A.key_s, A.owned, A.cs, A.start_ref, (GapEntry*)A.work, A.counter, work_cap, n_live_out, A.safe, A.fdefer, A.fcount);
+    launch_fill_gaps(st, A.cs, A.work, A.counter, work_cap);
 }
 
 void launch_slab_export(hipStream_t st, const StepParams& P, uint32_t cap, const float2* pos, const float2* pred,

@@ -1398,30 +1398,26 @@ static inline uint32_t xcd_grid(uint32_t nb, uint32_t c) {      // blocks to lau
     return (((chunks + 7u) >> 3) << 3) << c;
 }
 
-void launch_reorder(hipStream_t st, const StepParams& P, const u64* pairs, const float2* pos_in, const float2* vel_in,
-                    float2* pos_s, float2* vel_s, float2* pred_s, uint32_t* key_s, uint32_t* cs, uint32_t* start_ref,
-                    void* work, uint32_t* counter, uint32_t work_cap, unsigned long long* safe, uint32_t* force_defer,
-                    uint32_t* force_work_count, bool cs_ready) {
+// The launchers unpack StepArrays in the kernel's parameter order.
+void launch_reorder(hipStream_t st, const StepParams& P, const StepArrays& A, uint32_t work_cap, bool cs_ready) {
     if (cs_ready) {   // counting sort already produced the dense table
-        hipLaunchKernelGGL(k_reorder<false>, dim3(nblk(P.n)), dim3(FS_BLOCK), 0, st, P, pairs, pos_in, vel_in, pos_s,
-                           vel_s, pred_s, key_s, cs, start_ref, (GapEntry*)work, counter, work_cap, safe, force_defer, force_work_count);
+        hipLaunchKernelGGL(k_reorder<false>, dim3(nblk(P.n)), dim3(FS_BLOCK), 0, st, P, A.pairs, A.pos, A.vel, A.pos_s,
+                           A.vel_s, A.pred, A.key_s, A.cs, A.start_ref, (GapEntry*)A.work, A.counter, work_cap, A.safe, A.fdefer, A.fcount);
         return;
     }
-    hipLaunchKernelGGL(k_reorder<true>, dim3(nblk(P.n)), dim3(FS_BLOCK), 0, st, P, pairs, pos_in, vel_in, pos_s, vel_s,
-                       pred_s, key_s, cs, start_ref, (GapEntry*)work, counter, work_cap, safe, force_defer, force_work_count);
-    hipLaunchKernelGGL(k_fill_gaps, dim3(1024), dim3(FS_BLOCK), 0, st, cs, (const GapEntry*)work, counter, work_cap);
+    hipLaunchKernelGGL(k_reorder<true>, dim3(nblk(P.n)), dim3(FS_BLOCK), 0, st, P, A.pairs, A.pos, A.vel, A.pos_s, A.vel_s,
+                       A.pred, A.key_s, A.cs, A.start_ref, (GapEntry*)A.work, A.counter, work_cap, A.safe, A.fdefer, A.fcount);
+    hipLaunchKernelGGL(k_fill_gaps, dim3(1024), dim3(FS_BLOCK), 0, st, A.cs, (const GapEntry*)A.work, A.counter, work_cap);
 }
 
-void launch_density(hipStream_t st, const StepParams& P, const float2* pred, const uint32_t* cs,
-                    const uint32_t* start_ref, const u64* pairs, const unsigned long long* safe, float* rho, float2* rho2,
-                    uint32_t* force_defer, uint32_t* force_work, uint32_t* force_count, uint32_t edge_grid) {
+void launch_density(hipStream_t st, const StepParams& P, const StepArrays& A, uint32_t edge_grid) {
     static const bool no_mass1 = getenv("FS_NO_MASS1") != nullptr;          // A/B: always the general form
     const bool tol = P.fast_math == 2, mass1 = P.mass == 1.0f && !tol && !no_mass1;     // (the tolerance form applies the constant factor once anyway)
 #define FS_LAUNCH_DENSITY(K, G)                                                                                        \
     do {                                                                                                               \
-        if (tol) hipLaunchKernelGGL((K<true, false>), dim3(G), dim3(FS_BLOCK), 0, st, P, pred, cs, start_ref, pairs, safe, rho, rho2, force_defer, force_work, force_count); \
-        else if (mass1) hipLaunchKernelGGL((K<false, true>), dim3(G), dim3(FS_BLOCK), 0, st, P, pred, cs, start_ref, pairs, safe, rho, rho2, force_defer, force_work, force_count); \
-        else hipLaunchKernelGGL((K<false, false>), dim3(G), dim3(FS_BLOCK), 0, st, P, pred, cs, start_ref, pairs, safe, rho, rho2, force_defer, force_work, force_count); \
+        if (tol) hipLaunchKernelGGL((K<true, false>), dim3(G), dim3(FS_BLOCK), 0, st, P, A.pred, A.cs, A.start_ref, A.pairs, A.safe, A.rho, A.rho2, A.fdefer, A.fwork, A.fcount); \
+        else if (mass1) hipLaunchKernelGGL((K<false, true>), dim3(G), dim3(FS_BLOCK), 0, st, P, A.pred, A.cs, A.start_ref, A.pairs, A.safe, A.rho, A.rho2, A.fdefer, A.fwork, A.fcount); \
+        else hipLaunchKernelGGL((K<false, false>), dim3(G), dim3(FS_BLOCK), 0, st, P, A.pred, A.cs, A.start_ref, A.pairs, A.safe, A.rho, A.rho2, A.fdefer, A.fwork, A.fcount); \
     } while (0)
     if (edge_grid) {   // edge-first slab step: the edge columns' blocks only (k_density_edge)
         FS_LAUNCH_DENSITY(k_density_edge, edge_grid);
@@ -1432,9 +1428,7 @@ void launch_density(hipStream_t st, const StepParams& P, const float2* pred, con
 #undef FS_LAUNCH_DENSITY
 }
 
-void launch_surface_tension(hipStream_t st, const StepParams& P, float sigma, float tau, float cg, const float2* pred,
-                            const float2* rho2, const float* rho, const uint32_t* cs, const uint32_t* start_ref, const u64* pairs,
-                            float2* st_out) {
+void launch_surface_tension(hipStream_t st, const StepParams& P, const StepArrays& A, float sigma, float tau, float cg, float2* st_out) {
     if (P.n == 0) return;
     StConsts C;
     C.h2 = P.sqr_radius;
@@ -1443,18 +1437,27 @@ void launch_surface_tension(hipStream_t st, const StepParams& P, float sigma, fl
     C.sigma = sigma;
     C.tau = tau;
     const uint32_t grid = xcd_grid(nblk(P.n), P.xcd_chunk_log2);
-    if (P.mass == 1.0f && !rho)
-        hipLaunchKernelGGL(k_surface_tension<true>, dim3(grid), dim3(FS_BLOCK), 0, st, P, C, pred, rho2, rho, cs, start_ref, pairs, st_out);
+    if (P.mass == 1.0f && !A.rho)
+        hipLaunchKernelGGL(k_surface_tension<true>, dim3(grid), dim3(FS_BLOCK), 0, st, P, C, A.pred, A.rho2, A.rho, A.cs, A.start_ref, A.pairs, st_out);
     else
-        hipLaunchKernelGGL(k_surface_tension<false>, dim3(grid), dim3(FS_BLOCK), 0, st, P, C, pred, rho2, rho, cs, start_ref, pairs, st_out);
+        hipLaunchKernelGGL(k_surface_tension<false>, dim3(grid), dim3(FS_BLOCK), 0, st, P, C, A.pred, A.rho2, A.rho, A.cs, A.start_ref, A.pairs, st_out);
 }
 
-void launch_force(hipStream_t st, const StepParams& P, const float2* pos_s, const float2* vel_s, const float2* pred,
-                  const float2* rho2, const uint32_t* cs, const uint32_t* start_ref, const u64* pairs, const float2* tex,
-                  float2* pos_out, float2* vel_out, const float* rho_arr, uint32_t* defer_bits, uint32_t* worklist,
-                  uint32_t* work_count, void* aos_out, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join,
-                  uint32_t general_grid, uint32_t* general_hint, uint32_t edge_grid, hipEvent_t done, uint32_t quad_entries,
-                  const float2* st_in) {
+void launch_force(hipStream_t st, const StepParams& P, const StepArrays& A, const ForceLaunch& L) {
+    // hipExtLaunchKernelGGL deduces the kernel's parameter types from its arguments: locals of exactly those types
+    const float2 *pos_s = A.pos_s, *vel_s = A.vel_s, *pred = A.pred, *rho2 = A.rho2;
+    const uint32_t *cs = A.cs, *start_ref = A.start_ref;
+    const u64* pairs = A.pairs;
+    const float2* tex = A.tex;
+    float2 *pos_out = A.pos_out, *vel_out = A.vel_out;
+    const float* rho_arr = A.rho;
+    uint32_t *defer_bits = A.fdefer, *worklist = A.fwork, *work_count = A.fcount;
+    void* aos_out = L.aos_out;
+    const hipStream_t side = L.side;
+    const hipEvent_t ev_fork = L.ev_fork, ev_join = L.ev_join, done = L.done;
+    uint32_t* general_hint = L.general_hint;
+    const uint32_t general_grid = L.general_grid, edge_grid = L.edge_grid, quad_entries = L.quad_entries;
+    const float2* st_in = L.st_in;
     const uint32_t nb = nblk(P.n), grid = xcd_grid(nb, P.xcd_chunk_log2);
     hipEvent_t stop_ev = nullptr;      // set for the pass's last launch only
 #define FS_LAUNCH_FORCE(K, M, A, T, G, S, ...)                                                                      \

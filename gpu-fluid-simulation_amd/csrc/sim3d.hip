@@ -11,11 +11,13 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/fluidsim.h"
+#include "fs_host.h"
 #include "fs_kernels.h"
 #include "sort_policy.h"
 
@@ -905,13 +907,9 @@ __global__ __launch_bounds__(B3) void k3_import(uint32_t n, const fs3_particle* 
 }  // namespace fsd
 
 // ------------------------------------------------------------------------------------ host
+using fsd::DevArray;
+using fsd::fail;
 namespace {
-fs_status fail3(fs_status st, const std::string& m) { fsd::set_last_error(m); return st; }
-template <class T> struct Dev3 {
-    T* p = nullptr; size_t n = 0;
-    hipError_t alloc(size_t c) { n = c; return c ? hipMalloc((void**)&p, c * sizeof(T)) : hipSuccess; }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-};
 void lattice3(const fs3_settings& st, fs_vec3 off, fs3_particle* dst, size_t n) {
     const uint32_t side = (uint32_t)std::llround(std::cbrt((double)st.particle_count));
     const float half = (float)side * 0.5f, s = st.particle_spacing;
@@ -928,63 +926,27 @@ void lattice3(const fs3_settings& st, fs_vec3 off, fs3_particle* dst, size_t n) 
 }
 }  // namespace
 
-#define H3(expr)                                                                                         \
-    do {                                                                                                 \
-        hipError_t e__ = (expr);                                                                         \
-        if (e__ != hipSuccess)                                                                           \
-            return fail3(e__ == hipErrorOutOfMemory ? FS_ERR_OOM : FS_ERR_DEVICE,                        \
-                         std::string(#expr) + ": " + hipGetErrorString(e__));                            \
-    } while (0)
-
+// Every resource is held by an owner (fs_host.h) and freed by `delete`; members go in reverse order of declaration: the
+// device arrays first, then the events (profile ring, sort policy, t1 / t0), the stream last.
 struct fs_sim3 {
     fs3_settings st{};
     uint32_t n = 0, gw = 0, gh = 0, gd = 0, ncell = 0, tick = 0, work_cap = 0;
     int device = 0;
     int math_mode = FS_MATH_IEEE;
-    hipStream_t stream = nullptr;
-    Dev3<float4> pos, vel, pos_s, vel_s, pred;
-    Dev3<uint32_t> key, cs, counter, dirty;
-    Dev3<fsd::u64> pairs;
-    Dev3<fsd::u64> masks;        // 9 x n pass masks of the 27-cell sweep, k3_density -> k3_force (Params3::handoff)
+    fsd::Stream stream;
+    fsd::Event t0, t1;
+    fsd::SortPolicy sortp;       // host side of the sort's late-stage plan (sort_policy.h)
+    fsd::PassRing prof;          // per-pass timing
+    DevArray<float4> pos, vel, pos_s, vel_s, pred;
+    DevArray<uint32_t> key, cs, counter, dirty;
+    DevArray<fsd::u64> pairs;
+    DevArray<fsd::u64> masks;        // 9 x n pass masks of the 27-cell sweep, k3_density -> k3_force (Params3::handoff)
     bool handoff = true;
-    Dev3<unsigned char> work;
-    Dev3<fs3_particle> aos;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    bool profile = false;
-    std::vector<hipEvent_t> ev;
-    uint32_t pending = 0;
-    double ms[FS_PASS_COUNT] = {};
-    uint64_t steps = 0;
+    DevArray<unsigned char> work;
+    DevArray<fs3_particle> aos;
     fsd::ConstDiv div_2h3{}, div_h2{};
     bool share_div = false;      // all create-time proofs of the shared-denominator path succeeded
-    fsd::SortPolicy sortp;       // host side of the sort's late-stage plan (sort_policy.h)
-    void release() {
-        sortp.release();
-        pos.release(); vel.release(); pos_s.release(); vel_s.release(); pred.release(); key.release(); cs.release();
-        counter.release(); dirty.release(); pairs.release(); masks.release(); work.release(); aos.release();
-        for (auto& e : ev) (void)hipEventDestroy(e);
-        if (t0) (void)hipEventDestroy(t0);
-        if (t1) (void)hipEventDestroy(t1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
-
-static const uint32_t RING3 = 256;
-
-static fs_status drain3(fs_sim3* s) {
-    if (!s->pending) return FS_OK;
-    const size_t stride = FS_PASS_COUNT + 1;
-    H3(hipEventSynchronize(s->ev[(size_t)(s->pending - 1) * stride + FS_PASS_COUNT]));
-    for (uint32_t j = 0; j < s->pending; ++j)
-        for (int k = 0; k < FS_PASS_COUNT; ++k) {
-            float ms = 0;
-            H3(hipEventElapsedTime(&ms, s->ev[j * stride + k], s->ev[j * stride + k + 1]));
-            s->ms[k] += ms;
-        }
-    s->steps += s->pending;
-    s->pending = 0;
-    return FS_OK;
-}
 
 static fs_status enqueue3(fs_sim3* s, const fs3_tick_settings* t) {
     using namespace fsd;
@@ -1021,55 +983,55 @@ static fs_status enqueue3(fs_sim3* s, const fs3_tick_settings* t) {
     const bool tol = s->math_mode == FS_MATH_TOLERANCE;
     hipStream_t st = s->stream;
     hipEvent_t* ev = nullptr;
-    if (s->profile) {
-        if (s->ev.empty()) { s->ev.resize((size_t)RING3 * (FS_PASS_COUNT + 1)); for (auto& e : s->ev) H3(hipEventCreate(&e)); }
-        if (s->pending == RING3) { fs_status r = drain3(s); if (r != FS_OK) return r; }
-        ev = &s->ev[(size_t)s->pending * (FS_PASS_COUNT + 1)];
+    if (s->prof.on) {
+        const fs_status r = s->prof.begin();
+        if (r != FS_OK) return r;
+        ev = s->prof.current();
     }
     const dim3 grid((s->n + B3 - 1) / B3), block(B3);
-    H3(s->sortp.throttle());                           // at most SortPolicy::FLIGHT steps ahead of the device
-    if (ev) H3(hipEventRecord(ev[0], st));
+    FS_HIP(s->sortp.throttle());                           // at most SortPolicy::FLIGHT steps ahead of the device
+    if (ev) FS_HIP(hipEventRecord(ev[0], st));
     // predict + key are fused into the first sort kernel (k_bitonic_local<true, 2, *>), as in 2D: no separate launch,
     // the unsorted pairs never touch HBM.  FS3_SEPARATE_KEYGEN=1 keeps the round-2 kernel (A/B measurements).
     static const bool separate_keygen = getenv("FS3_SEPARATE_KEYGEN") != nullptr;
     if (separate_keygen) hipLaunchKernelGGL(k3_predict_key, grid, block, 0, st, P, s->pos.p, s->vel.p, s->pairs.p, s->counter.p);
-    if (ev) H3(hipEventRecord(ev[1], st));
+    if (ev) FS_HIP(hipEventRecord(ev[1], st));
     fsd::SortPlan plan;
-    if (!s->sortp.plan(s->n, &plan)) return fail3(FS_ERR_DEVICE, "sort: the stand-by kernel's grid barrier timed out");
+    if (!s->sortp.plan(s->n, &plan)) return fail(FS_ERR_DEVICE, "sort: the stand-by kernel's grid barrier timed out");
     if (separate_keygen) {
         launch_bitonic_sort(st, s->pairs.p, s->n, s->dirty.p, nullptr, nullptr, nullptr, nullptr, &plan);
     } else {
         const fsd::KeyGen3 kg{P.dt, P.h, P.bx, P.by, P.bz, P.gw, P.gh};
         launch_bitonic_sort(st, s->pairs.p, s->n, s->dirty.p, nullptr, nullptr, nullptr, s->counter.p, &plan, &kg, s->pos.p, s->vel.p);
     }
-    if (ev) H3(hipEventRecord(ev[2], st));
+    if (ev) FS_HIP(hipEventRecord(ev[2], st));
     hipLaunchKernelGGL(k3_reorder, grid, block, 0, st, P, s->pairs.p, s->pos.p, s->vel.p, s->pos_s.p, s->vel_s.p,
                        s->pred.p, s->key.p, s->cs.p, (GapEntry*)s->work.p, s->counter.p, s->work_cap);
     launch_fill_gaps(st, s->cs.p, s->work.p, s->counter.p, s->work_cap);
-    if (ev) H3(hipEventRecord(ev[3], st));
+    if (ev) FS_HIP(hipEventRecord(ev[3], st));
     const fsd::u64* fm = s->handoff ? s->masks.p : nullptr;
     const dim3 gridf(xcd_grid3((s->n + B3F - 1) / B3F, P.xcd_chunk_log2)), blockf(B3F);
     if (tol) hipLaunchKernelGGL(k3_density<2>, gridf, blockf, 0, st, P, s->pred.p, s->cs.p, s->vel_s.p, s->masks.p, s->key.p);
     else hipLaunchKernelGGL(k3_density<0>, gridf, blockf, 0, st, P, s->pred.p, s->cs.p, s->vel_s.p, s->masks.p, s->key.p);
-    if (ev) H3(hipEventRecord(ev[4], st));
+    if (ev) FS_HIP(hipEventRecord(ev[4], st));
     // positions ping-pong: read the previous state (s->pos, source order) through the pairs, write the new one into s->pos_s
     // the step's completion event (sort_policy.h: the host stays at most four steps ahead) rides on the force kernel as its
     // completion signal — no marker packet behind it (engine.hip fs_step does the same); a profiled step records markers anyway
     hipEvent_t done = ev ? nullptr : s->sortp.flight_event();
     if (tol) hipExtLaunchKernelGGL(k3_force<2>, gridf, blockf, 0, st, nullptr, done, 0, P, s->pos.p, s->vel_s.p, s->pred.p, s->cs.p, s->pos_s.p, s->vel.p, fm, s->key.p, s->pairs.p);
     else hipExtLaunchKernelGGL(k3_force<0>, gridf, blockf, 0, st, nullptr, done, 0, P, s->pos.p, s->vel_s.p, s->pred.p, s->cs.p, s->pos_s.p, s->vel.p, fm, s->key.p, s->pairs.p);
-    { float4* t = s->pos.p; s->pos.p = s->pos_s.p; s->pos_s.p = t; }
-    if (ev) { H3(hipEventRecord(ev[5], st)); H3(hipEventRecord(ev[6], st)); /* FS_PASS_BOUNDARY: slab handles only */ s->pending += 1; }
-    if (ev) H3(s->sortp.step_enqueued(st));
+    std::swap(s->pos, s->pos_s);
+    if (ev) { FS_HIP(hipEventRecord(ev[5], st)); FS_HIP(hipEventRecord(ev[6], st)); /* FS_PASS_BOUNDARY: slab handles only */ s->prof.pending += 1; }
+    if (ev) FS_HIP(s->sortp.step_enqueued(st));
     else s->sortp.step_bound();
-    H3(hipGetLastError());
+    FS_HIP(hipGetLastError());
     return FS_OK;
 }
 
 extern "C" {
 
 fs_status fs3_reference_lattice(const fs3_settings* st, fs_vec3 off, fs3_particle* dst, size_t n) {
-    if (!st || (!dst && n)) return fail3(FS_ERR_INVALID, "null argument");
+    if (!st || (!dst && n)) return fail(FS_ERR_INVALID, "null argument");
     lattice3(*st, off, dst, n);
     return FS_OK;
 }
@@ -1079,52 +1041,51 @@ fs_status fs3_create(const fs3_settings* st, int device, fs_vec3 off, fs_sim3** 
 }
 
 fs_status fs3_create_ex(const fs3_settings* st, int device, fs_vec3 off, int math_mode, fs_sim3** out) {
-    if (!st || !out) return fail3(FS_ERR_INVALID, "null argument");
+    if (!st || !out) return fail(FS_ERR_INVALID, "null argument");
     *out = nullptr;
     if (math_mode != FS_MATH_IEEE && math_mode != FS_MATH_TOLERANCE)
-        return fail3(FS_ERR_UNSUPPORTED, "3D math_mode must be FS_MATH_IEEE or FS_MATH_TOLERANCE");
-    if (st->particle_count <= 1) return fail3(FS_ERR_INVALID, "particle_count <= 1");
-    if (st->particle_count > (1u << 28)) return fail3(FS_ERR_INVALID, "particle_count > 2^28 (32-bit byte offsets)");
+        return fail(FS_ERR_UNSUPPORTED, "3D math_mode must be FS_MATH_IEEE or FS_MATH_TOLERANCE");
+    if (st->particle_count <= 1) return fail(FS_ERR_INVALID, "particle_count <= 1");
+    if (st->particle_count > (1u << 28)) return fail(FS_ERR_INVALID, "particle_count > 2^28 (32-bit byte offsets)");
     if (!(st->smoothing_radius > 0.0f) || !(st->size.x > 0) || !(st->size.y > 0) || !(st->size.z > 0))
-        return fail3(FS_ERR_INVALID, "bad settings");
+        return fail(FS_ERR_INVALID, "bad settings");
     const uint32_t side = (uint32_t)std::llround(std::cbrt((double)st->particle_count));
-    if ((uint64_t)side * side * side != st->particle_count) return fail3(FS_ERR_INVALID, "particle_count must be a cube");
+    if ((uint64_t)side * side * side != st->particle_count) return fail(FS_ERR_INVALID, "particle_count must be a cube");
     const double gw = std::ceil((double)st->size.x / st->smoothing_radius) + 2, gh = std::ceil((double)st->size.y / st->smoothing_radius) + 2,
                  gd = std::ceil((double)st->size.z / st->smoothing_radius) + 2;
-    if (gw * gh * gd >= 4294967295.0) return fail3(FS_ERR_INVALID, "grid does not fit u32 cell ids");
+    if (gw * gh * gd >= 4294967295.0) return fail(FS_ERR_INVALID, "grid does not fit u32 cell ids");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail3(FS_ERR_DEVICE, "no HIP device: the engine has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail3(FS_ERR_INVALID, "device ordinal out of range");
-    H3(hipSetDevice(device));
-    fs_sim3* s = new (std::nothrow) fs_sim3();
-    if (!s) return fail3(FS_ERR_OOM, "host allocation failed");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(FS_ERR_DEVICE, "no HIP device: the engine has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(FS_ERR_INVALID, "device ordinal out of range");
+    FS_HIP(hipSetDevice(device));
+    std::unique_ptr<fs_sim3> s(new (std::nothrow) fs_sim3());   // an error exit frees whatever the handle holds by then
+    if (!s) return fail(FS_ERR_OOM, "host allocation failed");
     s->st = *st; s->n = st->particle_count; s->device = device; s->math_mode = math_mode;
     s->gw = (uint32_t)((size_t)std::ceil(st->size.x / st->smoothing_radius) + 2);
     s->gh = (uint32_t)((size_t)std::ceil(st->size.y / st->smoothing_radius) + 2);
     s->gd = (uint32_t)((size_t)std::ceil(st->size.z / st->smoothing_radius) + 2);
     s->ncell = s->gw * s->gh * s->gd;
     s->work_cap = s->ncell / 16u + 1024u;
-#define T3(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { s->release(); delete s; return fail3(FS_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e__)); } } while (0)
-    T3(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    FS_HIP(hipStreamCreateWithFlags(&s->stream.h, hipStreamNonBlocking));
     const size_t n = s->n;
-    T3(s->pos.alloc(n)); T3(s->vel.alloc(n)); T3(s->pos_s.alloc(n)); T3(s->vel_s.alloc(n)); T3(s->pred.alloc(n + FS_PRED_SLACK));
-    T3(s->key.alloc(n)); T3(s->pairs.alloc(n)); T3(s->cs.alloc((size_t)s->ncell + 1)); T3(s->counter.alloc(4));
-    T3(s->dirty.alloc(fsd::sort_tile_count((uint32_t)n))); T3(s->work.alloc((size_t)s->work_cap * fsd::gap_entry_size()));
-    T3(s->aos.alloc(n));
+    FS_HIP(s->pos.alloc(n)); FS_HIP(s->vel.alloc(n)); FS_HIP(s->pos_s.alloc(n)); FS_HIP(s->vel_s.alloc(n)); FS_HIP(s->pred.alloc(n + FS_PRED_SLACK));
+    FS_HIP(s->key.alloc(n)); FS_HIP(s->pairs.alloc(n)); FS_HIP(s->cs.alloc((size_t)s->ncell + 1)); FS_HIP(s->counter.alloc(4));
+    FS_HIP(s->dirty.alloc(fsd::sort_tile_count((uint32_t)n))); FS_HIP(s->work.alloc((size_t)s->work_cap * fsd::gap_entry_size()));
+    FS_HIP(s->aos.alloc(n));
     s->handoff = !(getenv("FS3_HANDOFF") && atoi(getenv("FS3_HANDOFF")) == 0);
-    if (s->handoff) T3(s->masks.alloc((FS3_MASK128 ? 18 : 9) * (size_t)n));   // hi words, then the lo words of rows of 65 .. 128
-    T3(hipEventCreate(&s->t0)); T3(hipEventCreate(&s->t1));
-    T3(hipMemsetAsync(s->cs.p, 0, s->cs.n * 4, s->stream));
-    T3(hipMemsetAsync(s->counter.p, 0, 16, s->stream));
-    T3(hipMemsetAsync(s->dirty.p, 0, s->dirty.n * 4, s->stream));
-    T3(s->sortp.init(5));         // a z-plane of the cube holds n^(2/3) particles: the moves are long, start at stage S - 5
+    if (s->handoff) FS_HIP(s->masks.alloc((FS3_MASK128 ? 18 : 9) * (size_t)n));   // hi words, then the lo words of rows of 65 .. 128
+    FS_HIP(hipEventCreate(&s->t0.h)); FS_HIP(hipEventCreate(&s->t1.h));
+    FS_HIP(hipMemsetAsync(s->cs.p, 0, s->cs.n * 4, s->stream));
+    FS_HIP(hipMemsetAsync(s->counter.p, 0, 16, s->stream));
+    FS_HIP(hipMemsetAsync(s->dirty.p, 0, s->dirty.n * 4, s->stream));
+    FS_HIP(s->sortp.init(5));         // a z-plane of the cube holds n^(2/3) particles: the moves are long, start at stage S - 5
     {
         std::vector<fs3_particle> host(n);
         lattice3(*st, off, host.data(), n);
-        T3(hipMemcpyAsync(s->aos.p, host.data(), n * sizeof(fs3_particle), hipMemcpyHostToDevice, s->stream));
+        FS_HIP(hipMemcpyAsync(s->aos.p, host.data(), n * sizeof(fs3_particle), hipMemcpyHostToDevice, s->stream));
         hipLaunchKernelGGL(fsd::k3_import, dim3((s->n + B3 - 1) / B3), dim3(B3), 0, s->stream, s->n, s->aos.p, s->pos.p,
                            s->pred.p, s->vel.p, s->key.p);
-        T3(hipStreamSynchronize(s->stream));
+        FS_HIP(hipStreamSynchronize(s->stream));
     }
     for (int k = 0; k < 2; ++k) {   // prove the two constant divisions for this h (see engine.hip prove_constdiv)
         fsd::ConstDiv& K = k == 0 ? s->div_2h3 : s->div_h2;
@@ -1134,26 +1095,25 @@ fs_status fs3_create_ex(const fs3_settings* st, int device, fs_vec3 off, int mat
         K.ok = 0;
         if (!(K.c > 4.0f * FS_CONSTDIV_MIN) || !std::isfinite(K.c) || !std::isfinite(K.y)) continue;
         uint32_t bad = 1;
-        T3(hipMemsetAsync(s->counter.p + 1, 0, 4, s->stream));
+        FS_HIP(hipMemsetAsync(s->counter.p + 1, 0, 4, s->stream));
         fsd::launch_verify_constdiv(s->stream, K.c, K.y, FS_CONSTDIV_MIN, K.c, s->counter.p + 1);
-        T3(hipMemcpyAsync(&bad, s->counter.p + 1, 4, hipMemcpyDeviceToHost, s->stream));
-        T3(hipStreamSynchronize(s->stream));
+        FS_HIP(hipMemcpyAsync(&bad, s->counter.p + 1, 4, hipMemcpyDeviceToHost, s->stream));
+        FS_HIP(hipStreamSynchronize(s->stream));
         K.ok = bad == 0 ? 1 : 0;
     }
     {   // lean reciprocal / square root of the shared-denominator path, over their whole ranges (engine.hip)
         uint32_t bad[2] = {1, 1};
         const float hh = st->smoothing_radius;
         if (!getenv("FS_NO_SHAREDIV")) {
-            T3(hipMemsetAsync(s->counter.p + 1, 0, 8, s->stream));
+            FS_HIP(hipMemsetAsync(s->counter.p + 1, 0, 8, s->stream));
             fsd::launch_verify_unary(s->stream, 0, FS_RCP_LO, FS_RCP_HI, s->counter.p + 1);
             fsd::launch_verify_unary(s->stream, 1, FS_SQRT_LO, FS_SQRT_HI, s->counter.p + 2);
-            T3(hipMemcpyAsync(bad, s->counter.p + 1, 8, hipMemcpyDeviceToHost, s->stream));
-            T3(hipStreamSynchronize(s->stream));
+            FS_HIP(hipMemcpyAsync(bad, s->counter.p + 1, 8, hipMemcpyDeviceToHost, s->stream));
+            FS_HIP(hipStreamSynchronize(s->stream));
         }
         s->share_div = bad[0] == 0 && bad[1] == 0 && s->div_2h3.ok && s->div_h2.ok && hh >= 0x1p-19f && hh <= 0x1p19f;
     }
-#undef T3
-    *out = s;
+    *out = s.release();
     return FS_OK;
 }
 
@@ -1161,71 +1121,65 @@ void fs3_destroy(fs_sim3* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    s->release();
     delete s;
 }
 
 fs_status fs3_step(fs_sim3* s, const fs3_tick_settings* t) {
-    if (!s || !t) return fail3(FS_ERR_INVALID, "null argument");
-    H3(hipSetDevice(s->device));
+    if (!s || !t) return fail(FS_ERR_INVALID, "null argument");
+    FS_HIP(hipSetDevice(s->device));
     return enqueue3(s, t);
 }
 // a barrier time-out of the sort's stand-by kernel leaves the particle order undefined: reported wherever state is handed over
 static fs_status sort_health3(fs_sim3* s) {
-    H3(s->sortp.check_timeout(s->dirty.p, s->n));
-    if (s->sortp.dead) return fail3(FS_ERR_DEVICE, "sort: the stand-by kernel's grid barrier timed out: the particle order is undefined from that step on; destroy the handle");
+    FS_HIP(s->sortp.check_timeout(s->dirty.p, s->n));
+    if (s->sortp.dead) return fail(FS_ERR_DEVICE, "sort: the stand-by kernel's grid barrier timed out: the particle order is undefined from that step on; destroy the handle");
     return FS_OK;
 }
-fs_status fs3_sync(fs_sim3* s) { if (!s) return fail3(FS_ERR_INVALID, "null"); H3(hipStreamSynchronize(s->stream)); return sort_health3(s); }
+fs_status fs3_sync(fs_sim3* s) { if (!s) return fail(FS_ERR_INVALID, "null"); FS_HIP(hipStreamSynchronize(s->stream)); return sort_health3(s); }
 uint32_t fs3_tick_count(const fs_sim3* s) { return s ? s->tick : 0; }
 uint32_t fs3_particle_count(const fs_sim3* s) { return s ? s->n : 0; }
 fs_status fs3_grid_dims(const fs_sim3* s, uint32_t* w, uint32_t* h, uint32_t* d) {
-    if (!s || !w || !h || !d) return fail3(FS_ERR_INVALID, "null argument");
+    if (!s || !w || !h || !d) return fail(FS_ERR_INVALID, "null argument");
     *w = s->gw; *h = s->gh; *d = s->gd;
     return FS_OK;
 }
 fs_status fs3_download_particles(fs_sim3* s, fs3_particle* dst, size_t n) {
-    if (!s || (!dst && n)) return fail3(FS_ERR_INVALID, "null argument");
+    if (!s || (!dst && n)) return fail(FS_ERR_INVALID, "null argument");
     if (n > s->n) n = s->n;
-    H3(hipSetDevice(s->device));
+    FS_HIP(hipSetDevice(s->device));
     hipLaunchKernelGGL(fsd::k3_export, dim3((s->n + B3 - 1) / B3), dim3(B3), 0, s->stream, s->n, s->pos.p, s->pred.p,
                        s->vel.p, s->key.p, s->aos.p);
-    if (n) H3(hipMemcpyAsync(dst, s->aos.p, n * sizeof(fs3_particle), hipMemcpyDeviceToHost, s->stream));
-    H3(hipStreamSynchronize(s->stream));
+    if (n) FS_HIP(hipMemcpyAsync(dst, s->aos.p, n * sizeof(fs3_particle), hipMemcpyDeviceToHost, s->stream));
+    FS_HIP(hipStreamSynchronize(s->stream));
     return sort_health3(s);
 }
 fs_status fs3_upload_particles(fs_sim3* s, const fs3_particle* src, size_t n) {
-    if (!s || (!src && n)) return fail3(FS_ERR_INVALID, "null argument");
+    if (!s || (!src && n)) return fail(FS_ERR_INVALID, "null argument");
     if (n > s->n) n = s->n;
-    H3(hipSetDevice(s->device));
-    if (n) H3(hipMemcpyAsync(s->aos.p, src, n * sizeof(fs3_particle), hipMemcpyHostToDevice, s->stream));
+    FS_HIP(hipSetDevice(s->device));
+    if (n) FS_HIP(hipMemcpyAsync(s->aos.p, src, n * sizeof(fs3_particle), hipMemcpyHostToDevice, s->stream));
     if (n) hipLaunchKernelGGL(fsd::k3_import, dim3(((uint32_t)n + B3 - 1) / B3), dim3(B3), 0, s->stream, (uint32_t)n,
                               s->aos.p, s->pos.p, s->pred.p, s->vel.p, s->key.p);
-    H3(hipStreamSynchronize(s->stream));
+    FS_HIP(hipStreamSynchronize(s->stream));
     s->sortp.touched();
     return FS_OK;
 }
 fs_status fs3_timed_steps(fs_sim3* s, const fs3_tick_settings* t, uint32_t steps, double* ms_total) {
-    if (!s || !t || !ms_total) return fail3(FS_ERR_INVALID, "null argument");
-    H3(hipSetDevice(s->device));
-    H3(hipEventRecord(s->t0, s->stream));
+    if (!s || !t || !ms_total) return fail(FS_ERR_INVALID, "null argument");
+    FS_HIP(hipSetDevice(s->device));
+    FS_HIP(hipEventRecord(s->t0, s->stream));
     for (uint32_t k = 0; k < steps; ++k) { fs_status r = enqueue3(s, t); if (r != FS_OK) return r; }
-    H3(hipEventRecord(s->t1, s->stream));
-    H3(hipEventSynchronize(s->t1));
+    FS_HIP(hipEventRecord(s->t1, s->stream));
+    FS_HIP(hipEventSynchronize(s->t1));
     float ms = 0;
-    H3(hipEventElapsedTime(&ms, s->t0, s->t1));
+    FS_HIP(hipEventElapsedTime(&ms, s->t0, s->t1));
     *ms_total = ms;
     return sort_health3(s);
 }
-fs_status fs3_profile_enable(fs_sim3* s, int enable) { if (!s) return fail3(FS_ERR_INVALID, "null"); s->profile = enable != 0; return FS_OK; }
+fs_status fs3_profile_enable(fs_sim3* s, int enable) { if (!s) return fail(FS_ERR_INVALID, "null"); s->prof.on = enable != 0; return FS_OK; }
 fs_status fs3_profile_read(fs_sim3* s, double ms[FS_PASS_COUNT], uint64_t* steps, int reset) {
-    if (!s || !ms) return fail3(FS_ERR_INVALID, "null argument");
-    fs_status r = drain3(s);
-    if (r != FS_OK) return r;
-    for (int k = 0; k < FS_PASS_COUNT; ++k) ms[k] = s->ms[k];
-    if (steps) *steps = s->steps;
-    if (reset) { for (auto& m : s->ms) m = 0; s->steps = 0; }
-    return FS_OK;
+    if (!s || !ms) return fail(FS_ERR_INVALID, "null argument");
+    return s->prof.read(ms, steps, reset);
 }
 
 }  // extern "C"

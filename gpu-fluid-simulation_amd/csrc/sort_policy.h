@@ -54,10 +54,12 @@ struct SortPolicy {
         if (r == hipSuccess) memset(fb, 0, 8 * sizeof(uint32_t));
         return r;
     }
-    void release() {
-        for (auto& e : flight) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    SortPolicy() = default;
+    SortPolicy(const SortPolicy&) = delete;
+    SortPolicy& operator=(const SortPolicy&) = delete;
+    ~SortPolicy() {
+        for (auto& e : flight) if (e) (void)hipEventDestroy(e);
         if (fb) (void)hipHostFree(fb);
-        fb = nullptr;
     }
     // the state was replaced from outside: an arbitrary order
     void touched() { trusted = 0; skip_seq = seq + 1; }
