@@ -26,6 +26,7 @@ from ._abi import (  # noqa: F401
     PARTICLE3_DTYPE,
     PARTICLE_DTYPE,
     PASS_NAMES,
+    SAMPLE_DTYPE,
     ExtensionMissing,
     Options,
     Settings,
@@ -44,7 +45,7 @@ from ._abi import (  # noqa: F401
 
 __all__ = [
     "FluidSimulation", "ResizableBuffer", "SimulationSettings", "default_tick_settings", "dam_break_2d",
-    "FluidSimError", "load_library", "PARTICLE_DTYPE",
+    "FluidSimError", "load_library", "PARTICLE_DTYPE", "SAMPLE_DTYPE",
 ]
 
 
@@ -186,6 +187,11 @@ class FluidSimulation:
         _check(self._lib, self._lib.fs_grid_dims(self._h, C.byref(w), C.byref(h)))
         return int(w.value), int(h.value)
 
+    @property
+    def stream_ptr(self):
+        """The HIP stream the steps (and sample_device) are enqueued on, as an integer (torch.cuda.ExternalStream)."""
+        return self._lib.fs_stream(self._h)
+
     # -- surface tension (build extension, opt-in; DESIGN.md §11) ---------
     def set_surface_tension(self, enable=True):
         """Colour-field surface tension from the tick's surface_tension_coefficient / _treshold, for the steps after this call."""
@@ -324,6 +330,51 @@ class FluidSimulation:
         _check(self._lib, self._lib.fs_render_density(self._h, C.byref(view), out.ctypes.data_as(C.c_void_p)))
         return out
 
+    # -- field sampling (build extension) ---------------------
+    def _sample_attr(self, attributes, n):
+        if not attributes:
+            return None
+        ch = self.track_channels
+        if ch <= 0:
+            raise FluidSimError(_abi.FS_ERR_INVALID, "sample(attributes=True) needs track(channels >= 1)")
+        return np.empty((ch, n), dtype=np.float32)
+
+    def sample(self, points, attributes=False, normalise=False):
+        """Density, Shepard weight, velocity sum, neighbour count and cell of the fluid at `points` ((n, 2) float32, any
+        place): a SAMPLE_DTYPE array, and with attributes=True also the (channels, n) float32 channel sums.  The sums are the
+        un-normalised SPH interpolants (include/fluidsim.h); normalise=True divides velocity and channels by `weight` where it
+        is non-zero.  Needs a step since create / the last upload.  Points in a coherent order (sorted by cell, a grid, slot
+        order) are sampled several times faster than shuffled ones."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 2)
+        n = pts.shape[0]
+        out = np.zeros(n, dtype=SAMPLE_DTYPE)
+        attr = self._sample_attr(attributes, n)
+        _check(self._lib, self._lib.fs_sample_points(self._h, pts.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p),
+                                                     attr.ctypes.data_as(C.c_void_p) if attr is not None else None))
+        if normalise:
+            _normalise_samples(out, attr)
+        return (out, attr) if attributes else out
+
+    def sample_grid(self, width, height, world_min=None, world_max=None, attributes=False):
+        """sample() at the pixel centres of render_density()'s view (same defaults): a [height, width] SAMPLE_DTYPE array, and
+        with attributes=True also the (channels, height, width) float32 channel sums.  Bit-identical to sample() on those points."""
+        sx, sy = self.settings.size.x, self.settings.size.y
+        wmin = world_min if world_min is not None else (-sx / 2, -sy / 2)
+        wmax = world_max if world_max is not None else (sx / 2, sy / 2)
+        width, height = int(width), int(height)
+        view = _abi.View(Vec2(float(wmin[0]), float(wmin[1])), Vec2(float(wmax[0]), float(wmax[1])), width, height)
+        out = np.zeros((height, width), dtype=SAMPLE_DTYPE)
+        attr = self._sample_attr(attributes, width * height)
+        _check(self._lib, self._lib.fs_sample_grid(self._h, C.byref(view), out.ctypes.data_as(C.c_void_p),
+                                                   attr.ctypes.data_as(C.c_void_p) if attr is not None else None))
+        return (out, attr.reshape(-1, height, width)) if attributes else out
+
+    def sample_device(self, points_ptr, n, out_ptr, attr_ptr=None):
+        """fs_sample_points_device: device pointers (n fs_vec2 in, n 24-byte fs_sample out, channels * n floats out), enqueued
+        on the simulation's stream after the steps in flight; non-blocking."""
+        _check(self._lib, self._lib.fs_sample_points_device(self._h, C.c_void_p(points_ptr), int(n), C.c_void_p(out_ptr),
+                                                            C.c_void_p(attr_ptr) if attr_ptr else None))
+
     def export_handle(self, which=_abi.FS_EXPORT_PARTICLES):
         """fs_export_handle: interprocess handle of the AoS particle view (switches on the live view) or of start_indices."""
         h = _abi.MemHandle()
@@ -339,6 +390,15 @@ class FluidSimulation:
         p, n = C.c_void_p(), C.c_size_t()
         _check(self._lib, self._lib.fs_start_indices_device(self._h, C.byref(p), C.byref(n)))
         return p.value, int(n.value)
+
+
+def _normalise_samples(out, attr):
+    """Shepard normalisation in place: velocity and channel sums divided by the weight, where that is non-zero."""
+    w = out["weight"]
+    ok = w != 0
+    out["velocity"][ok] /= w[ok, None]
+    if attr is not None:
+        attr[:, ok] /= w[ok]
 
 
 def dam_break_3d(n):

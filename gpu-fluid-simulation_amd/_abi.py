@@ -124,6 +124,12 @@ class View(C.Structure):
     _fields_ = [("world_min", Vec2), ("world_max", Vec2), ("width", C.c_uint32), ("height", C.c_uint32)]
 
 
+class Sample(C.Structure):
+    """fs_sample (include/fluidsim.h): 24 bytes."""
+    _fields_ = [("density", C.c_float), ("weight", C.c_float), ("velocity", Vec2), ("neighbours", C.c_uint32),
+                ("cell", C.c_uint32)]
+
+
 class SlabConfig(C.Structure):
     _fields_ = [
         ("own_lo", C.c_uint32), ("own_hi", C.c_uint32),
@@ -148,6 +154,9 @@ PARTICLE_DTYPE = np.dtype(
     ]
 )
 assert PARTICLE_DTYPE.itemsize == 32
+# fs_sample as a numpy structured dtype (offsets 0/4/8/16/20).
+SAMPLE_DTYPE = np.dtype([("density", "<f4"), ("weight", "<f4"), ("velocity", "<f4", (2,)), ("neighbours", "<u4"), ("cell", "<u4")])
+assert SAMPLE_DTYPE.itemsize == 24 and C.sizeof(Sample) == 24
 assert C.sizeof(Uniform) == 120
 assert C.sizeof(Settings) == 28
 assert C.sizeof(TickSettings) == 60
@@ -224,6 +233,9 @@ PROTOTYPES = {
     "fs_track_ids_device": (C.c_int, [_P, C.POINTER(_P)]),
     "fs_track_attr_device": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "fs_download_particles_by_id": (C.c_int, [_P, _P, C.c_size_t]),
+    "fs_sample_points": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "fs_sample_points_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "fs_sample_grid": (C.c_int, [_P, C.POINTER(View), _P, _P]),
     "fs_export_handle": (C.c_int, [_P, C.c_int, _P]),
     "fs_import_open": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "fs_import_read": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t]),

@@ -13,7 +13,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libfluidsim_hip.so")
-SOURCES = ["engine.hip", "comm.hip", "buffer.hip", "kernels_step.hip", "kernels_sort.hip", "kernels_slab.hip", "kernels_csort.hip", "kernels_field.hip", "kernels_track.hip", "sim3d.hip"]
+SOURCES = ["engine.hip", "comm.hip", "buffer.hip", "kernels_step.hip", "kernels_sort.hip", "kernels_slab.hip", "kernels_csort.hip", "kernels_field.hip", "kernels_track.hip", "kernels_sample.hip", "sim3d.hip"]
 HEADERS = ["fs_device.h", "fs_host.h", "fs_kernels.h", "fs_scan.h", "sort_policy.h", os.path.join("..", "..", "include", "fluidsim.h")]
 FLAGS = [
     "--offload-arch=gfx950",
@@ -28,7 +28,7 @@ FLAGS = [
 
 
 # float-heavy kernels only: the integer sort kernels measured ~1 % faster with the vectoriser on
-NO_SLP = {"kernels_step.hip", "sim3d.hip", "kernels_slab.hip"}
+NO_SLP = {"kernels_step.hip", "sim3d.hip", "kernels_slab.hip", "kernels_sample.hip"}
 
 
 def _flags(src):

@@ -161,6 +161,9 @@ struct fs_sim : HandleQueues, ParticleArrays {
     int trk_channels = -1;          // -1: off
     int trk_alloc_channels = 0;     // channels the attr arrays were allocated for
     int trk_cur = 0;
+    // field sampling (build extension): the records and the cell table belong together — a step has been enqueued
+    // since create and since the last fs_upload_particles / fs_upload_start_indices
+    bool sample_ready = false;
 
     fsd::ConstDiv div_2h3{}, div_h2{};   // exact constant divisions of the force pass, proven at create
     fsd::ConstDiv div_h{};               // ... and of the cell coordinates (x / h), over the numerators clamped positions give
@@ -519,6 +522,7 @@ fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
     L.quad_entries = s->sortp.quad_entries();
     fsd::launch_force(st, P, A, L);
     if (pos_by_src) std::swap(s->pos, s->pos_s);   // the spare buffer now holds the state
+    s->sample_ready = true;
     if (s->aos_live) s->aos_tick = s->tick;
     if (prof) {
         FS_HIP(hipEventRecord(ev[5], st));
@@ -812,6 +816,7 @@ fs_status fs_upload_particles(fs_sim* s, const fs_particle* src, size_t n) {
     FS_HIP(hipStreamSynchronize(s->stream));
     s->aos_tick = 0xFFFFFFFFu;      // the live view (if any) no longer matches the state: re-materialise on demand
     s->sortp.touched();             // an arbitrary order: the per-stage launches stand by until reports pass again
+    s->sample_ready = false;
     return FS_OK;
 }
 
@@ -832,6 +837,7 @@ fs_status fs_upload_start_indices(fs_sim* s, const uint32_t* src, size_t n) {
     FS_HIP(hipSetDevice(s->device));
     if (n) FS_HIP(hipMemcpyAsync(s->start_ref.p, src, n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
     FS_HIP(hipStreamSynchronize(s->stream));
+    s->sample_ready = false;
     return FS_OK;
 }
 
@@ -1045,6 +1051,108 @@ fs_status fs_download_particles_by_id(fs_sim* s, fs_particle* dst, size_t n) {
     for (size_t i = 0; i < ids.size(); ++i)
         if (ids[i] < n) dst[ids[i]] = rec[i];
     return FS_OK;
+}
+
+// ---- field sampling ---------------------------------------------------------------------------------
+namespace {
+// Argument and state checks the three calls share, in the order the header lists them.  *go = false: n == 0, nothing to do.
+fs_status sample_check(fs_sim* s, const void* points_or_view, size_t n, const void* out, const float* attr_out, bool* go) {
+    *go = false;
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    if (s->slab) return fail(FS_ERR_UNSUPPORTED, "sampling: single-domain handles only (not built for slab handles)");
+    if (attr_out && s->trk_channels <= 0) return fail(FS_ERR_INVALID, "sampling: attr_out needs tracking with at least one channel");
+    if (n == 0) return FS_OK;
+    if (!points_or_view || !out) return fail(FS_ERR_INVALID, "null argument");
+    if (n > ((size_t)1 << 28)) return fail(FS_ERR_INVALID, "sampling: more than 2^28 points");
+    if (!s->sample_ready) return fail(FS_ERR_INVALID, "sampling needs a step since create and since the last upload of particles or start indices");
+    *go = true;
+    return FS_OK;
+}
+
+// Enqueue the kernel on the simulation's stream.  points_dev == nullptr: the pixel centres of `view`.
+fs_status sample_enqueue(fs_sim* s, const fs_vec2* points_dev, const fs_view* view, size_t n, fs_sample* out_dev, float* attr_out_dev) {
+    static_assert(sizeof(fs_sample) == 24, "fs_sample is 24 bytes");
+    fsd::SampleQuery Q;
+    Q.n = (uint32_t)n;
+    Q.points = (const float2*)points_dev;
+    if (view) {
+        Q.wmin = make_float2(view->world_min.x, view->world_min.y);
+        Q.wmax = make_float2(view->world_max.x, view->world_max.y);
+        Q.width = view->width; Q.height = view->height;
+    }
+    Q.out = out_dev; Q.attr_out = attr_out_dev;
+    fsd::SampleState S;
+    // after a step: `pred` = its predicted positions, `vel` = its new velocities (as fs_render_density); keys and densities
+    // from where that step left them
+    S.pred = s->pred.p; S.vel = s->vel.p;
+    S.rho2 = s->rho2.p; S.rho = s->rho_in_rho2 ? nullptr : s->rho.p;
+    S.cs = s->cs.p; S.start_ref = s->start_ref.p; S.pairs = s->pairs.p;
+    if (attr_out_dev) {
+        S.channels = s->trk_channels;
+        S.attr = s->trk_attr[s->trk_cur].p; S.attr_stride = s->capacity;
+    }
+    fsd::launch_sample(s->stream, make_params(*s), Q, S);
+    FS_HIP(hipGetLastError());
+    return FS_OK;
+}
+
+// The blocking forms: device staging for the points (none for a grid), the records and the channel sums.
+fs_status sample_host(fs_sim* s, const fs_vec2* points, const fs_view* view, size_t n, fs_sample* out, float* attr_out) {
+    FS_JOIN(s);
+    FS_HIP(hipSetDevice(s->device));
+    const size_t ch = attr_out ? (size_t)s->trk_channels : 0;
+    fs_vec2* dpts = nullptr; fs_sample* dout = nullptr; float* dattr = nullptr;
+    hipError_t e = hipSuccess;
+    if (points) e = hipMalloc((void**)&dpts, n * sizeof(fs_vec2));
+    if (e == hipSuccess) e = hipMalloc((void**)&dout, n * sizeof(fs_sample));
+    if (e == hipSuccess && ch) e = hipMalloc((void**)&dattr, ch * n * sizeof(float));
+    fs_status r = FS_OK;
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        r = fail(FS_ERR_OOM, "sampling: device staging");
+    } else {
+        if (points) e = hipMemcpyAsync(dpts, points, n * sizeof(fs_vec2), hipMemcpyHostToDevice, s->stream);
+        if (e == hipSuccess) {
+            r = sample_enqueue(s, dpts, points ? nullptr : view, n, dout, dattr);
+            if (r == FS_OK) e = hipMemcpyAsync(out, dout, n * sizeof(fs_sample), hipMemcpyDeviceToHost, s->stream);
+            if (r == FS_OK && e == hipSuccess && ch) e = hipMemcpyAsync(attr_out, dattr, ch * n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
+        }
+        const hipError_t es = hipStreamSynchronize(s->stream);      // before the staging is freed, whatever happened
+        if (e == hipSuccess) e = es;
+        if (r == FS_OK && e != hipSuccess) r = fail(FS_ERR_DEVICE, hipGetErrorString(e));
+    }
+    (void)hipFree(dpts); (void)hipFree(dout); (void)hipFree(dattr);
+    if (r != FS_OK) return r;
+    return sort_health(s);
+}
+}  // namespace
+
+fs_status fs_sample_points(fs_sim* s, const fs_vec2* points, size_t n, fs_sample* out, float* attr_out) {
+    bool go;
+    const fs_status r = sample_check(s, points, n, out, attr_out, &go);
+    if (r != FS_OK || !go) return r;
+    return sample_host(s, points, nullptr, n, out, attr_out);
+}
+
+fs_status fs_sample_points_device(fs_sim* s, const fs_vec2* points_dev, size_t n, fs_sample* out_dev, float* attr_out_dev) {
+    bool go;
+    const fs_status r = sample_check(s, points_dev, n, out_dev, attr_out_dev, &go);
+    if (r != FS_OK || !go) return r;
+    FS_HIP(hipSetDevice(s->device));
+    return sample_enqueue(s, points_dev, nullptr, n, out_dev, attr_out_dev);
+}
+
+fs_status fs_sample_grid(fs_sim* s, const fs_view* view, fs_sample* out, float* attr_out) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    if (s->slab) return fail(FS_ERR_UNSUPPORTED, "sampling: single-domain handles only (not built for slab handles)");
+    if (!view) return fail(FS_ERR_INVALID, "null argument");
+    if (view->width == 0 || view->height == 0 || (uint64_t)view->width * view->height > (1ull << 28))
+        return fail(FS_ERR_INVALID, "bad grid size");
+    const size_t n = (size_t)view->width * view->height;
+    bool go;
+    const fs_status r = sample_check(s, view, n, out, attr_out, &go);
+    if (r != FS_OK || !go) return r;
+    return sample_host(s, nullptr, view, n, out, attr_out);
 }
 
 fs_status fs_profile_enable(fs_sim* s, int enable) {

@@ -80,6 +80,29 @@ void launch_import_aos(hipStream_t st, uint32_t n, const void* in, float2* pos, 
 void launch_render_density(hipStream_t st, const StepParams& P, float2 wmin, float2 wmax, uint32_t width,
                            uint32_t height, const float2* pred, const float2* vel, const uint32_t* cs,
                            const uint32_t* start_ref, const u64* pairs, float4* out);
+// Field sampling (build extension; kernels_sample.hip): density, Shepard weight, velocity and channel sums of the
+// state the last step left (SampleState) at the points of a SampleQuery.  All pointers are device pointers.
+struct SampleQuery {
+    uint32_t n = 0;                    // queries; with points == nullptr: width * height
+    const float2* points = nullptr;    // nullptr: the pixel centres of the view below (fs_render_density's mapping), row-major
+    float2 wmin = {0.0f, 0.0f}, wmax = {0.0f, 0.0f};
+    uint32_t width = 0, height = 0;
+    void* out = nullptr;               // n fs_sample records (24 B)
+    float* attr_out = nullptr;         // channels * n floats, channel c at c * n; unused with channels == 0
+};
+struct SampleState {
+    const float2* pred = nullptr;      // sorted predicted positions
+    const float2* vel = nullptr;       // the step's new velocities
+    const float2* rho2 = nullptr;      // {rho, +-RN(1/rho)} (strict / ulp step) ...
+    const float* rho = nullptr;        // ... or, != nullptr, the densities themselves (tolerance step)
+    const uint32_t* cs = nullptr;
+    const uint32_t* start_ref = nullptr;
+    const u64* pairs = nullptr;
+    int channels = 0;                  // 0: no channel sums
+    const float* attr = nullptr;       // channel c at attr + c * attr_stride
+    uint32_t attr_stride = 0;
+};
+void launch_sample(hipStream_t st, const StepParams& P, const SampleQuery& Q, const SampleState& S);
 // Obstacle push-out field (kernels_field.hip); h <= 1024, w < 65536.
 void launch_gradient_field(hipStream_t st, const unsigned char* image, uint32_t w, uint32_t h, float* dist,
                            uint32_t* nearest, float2* field);

@@ -332,6 +332,57 @@ fs_status fs_track_ids_device(fs_sim* sim, const uint32_t** out);
 fs_status fs_track_attr_device(fs_sim* sim, int channel, const float** out);
 fs_status fs_download_particles_by_id(fs_sim* sim, fs_particle* dst, size_t n);
 
+/* ------------------------------------------------ field sampling (build extension, opt-in by being called) */
+/* NOT in the reference: every other read-out is indexed by slot.  These calls evaluate the fluid at arbitrary points: the
+ * reference's calculate_density_at_point (funcs.wgsl:157-203) at a point that need not be a particle, and the SPH interpolants
+ * sum_j (m / rho_j) W_j f_j of the velocity and of the tracking channels.  The result is a pure function of the state the handle
+ * holds after its last step — what fs_download_particles (p[k]), fs_download_start_indices (S), fs_get_uniform and
+ * fs_track_download_attr (attr[c]) return — in every math mode and sort mode.  With n = particle_count, h = smoothing_radius,
+ * h2 = h * h, m = particle_mass, Cv = 4.0f / (PI * powf(h, 8.0f)) (the density pass's coefficient), all f32 without contraction,
+ * for a query point x:
+ *     (cx, cy) = (u32_sat(floor((x.x + bounds.x * 0.5f) / h)) + 1, likewise y)         wrapping + 1 (funcs.wgsl:212-214)
+ *     cell = cy * grid_w + cx                                                          wrapping u32
+ *     density = weight = velocity = a_c = +0.0f;  neighbours = 0
+ *     for oy in -1, 0, 1:  for ox in -1, 0, 1:
+ *         X = (u32)(cx + ox);  Y = (u32)(cy + oy);  skipped when X >= grid_w or Y >= grid_h      (fs_render_density's rule)
+ *         id = Y * grid_w + X;  k = S[id]
+ *         while k < n and p[k].grid == id:                                             (a stale S[id] included: ref_quirks)
+ *             d = p[k].predicted_position - x;  r2 = d.x * d.x + d.y * d.y
+ *             if not (r2 > h2):
+ *                 e = h2 - r2;  W = ((Cv * e) * e) * e
+ *                 density += m * W
+ *                 t = (m / p[k].density) * W                                           IEEE division by the stored density
+ *                 weight += t;  velocity += t * p[k].velocity;  a_c += t * attr[c][k];  neighbours += 1
+ *             k += 1
+ * `velocity` and the channel sums are returned un-normalised; dividing by `weight` gives the Shepard-normalised value.  At a
+ * particle's own predicted position, fmax(fmax(density, EPSILON), 0.1f) is that particle's stored density, bit for bit, in
+ * FS_MATH_IEEE.  Non-finite query coordinates give unspecified values (and no out-of-bounds access).  See DESIGN.md §13.
+ *
+ * fs_sample_points: host pointers, blocking.
+ * fs_sample_points_device: device pointers on the handle's device; enqueued on fs_stream(sim) after the steps in flight;
+ *   non-blocking, no allocation, no host read — for a consumer on the same GPU.  The buffers must stay valid until the stream
+ *   has passed the call.
+ * fs_sample_grid: host output, blocking; pixel (i, j) is fs_render_density's point
+ *   world_min + (((float)i + 0.5f) / (float)width) * (world_max - world_min), stored at out[j * width + i]; bit-identical to
+ *   fs_sample_points on those points.
+ * attr_out may be NULL; else attr_out[c * n + k] = a_c of query k for c < fs_track_channels(sim) (n = width * height for a grid).
+ * Query order decides the speed, not the result: points in a coherent order (a grid, sorted by cell, slot order) are sampled
+ * several times faster than the same points shuffled.  Nothing is sorted behind the caller's back.
+ * Checks, in this order: NULL handle -> FS_ERR_INVALID; slab handle -> FS_ERR_UNSUPPORTED; (grid) NULL or zero-sized view, or
+ * width * height > 2^28 -> FS_ERR_INVALID; attr_out != NULL with tracking off or zero channels -> FS_ERR_INVALID; n == 0 ->
+ * FS_OK, nothing touched; NULL points / out -> FS_ERR_INVALID; n > 2^28 -> FS_ERR_INVALID; no step enqueued since create or since
+ * the last fs_upload_particles / fs_upload_start_indices (records and cell table would not belong together) -> FS_ERR_INVALID. */
+typedef struct fs_sample {        /* 24 bytes */
+    float density;                /* sum m W */
+    float weight;                 /* sum (m / rho_j) W: the Shepard denominator */
+    fs_vec2 velocity;             /* sum (m / rho_j) W v_j, un-normalised */
+    uint32_t neighbours;          /* candidates with r2 <= h2 */
+    uint32_t cell;                /* cell id of the query point */
+} fs_sample;
+fs_status fs_sample_points(fs_sim* sim, const fs_vec2* points, size_t n, fs_sample* out, float* attr_out);
+fs_status fs_sample_points_device(fs_sim* sim, const fs_vec2* points_dev, size_t n, fs_sample* out_dev, float* attr_out_dev);
+fs_status fs_sample_grid(fs_sim* sim, const fs_view* view, fs_sample* out, float* attr_out);
+
 /* ------------------------------------------------ multi-GPU slab mode (build extension) */
 /* NOT in the reference (single wgpu device, src/renderer.rs:108-133).  SURVEY.md §8e: a rank
  * owns the global cell columns [own_lo, own_hi) of the grid (src/simulation.rs:140-141) and
