@@ -1,0 +1,260 @@
+// engine.h — what the host files of the C ABI share beyond fs_host.h: the 2D simulation handle (engine.hip: the plain handle,
+// the opt-in features, the self-tests; engine_slab.hip: the multi-GPU slab handles), the step parameters, and the create-time
+// device check and proofs (also used by sim3d.hip).  Internal: include/fluidsim.h is the interface.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <memory>
+#include <string>
+
+#include "../../include/fluidsim.h"
+#include "fs_host.h"
+#include "fs_kernels.h"
+#include "sort_policy.h"
+
+namespace fsd {
+
+// The arrays one particle array's sort-reorder, density and force passes work on: the main array of every handle (fs_sim) and
+// the boundary strip of an overlapped slab step (SlabState::Strip) each hold one set.
+struct ParticleArrays {
+    // SoA state.  pos/vel: current state (cell order of the last step).  *_s: the
+    // cell-sorted snapshot the density/force passes read (Jacobi semantics).
+    DevArray<float2> pos, vel, pos_s, vel_s, pred;
+    DevArray<float> rho;
+    DevArray<float2> rho2;          // {density, RN(1/density)}: what the force pass gathers per neighbour
+    DevArray<uint32_t> fdefer, fwork;   // force pass: per-block deferred-wave bits and the worklist (counter[3] = its length)
+    DevArray<uint32_t> bbounds;         // 8 words per 256-particle block: the density pass's block-wide sweep ranges, read by the force pass
+    DevArray<unsigned long long> safe;   // one bit per sorted particle: coordinates / velocity inside the exact-quotient ranges (fs_device.h)
+    DevArray<u64> pairs;
+    DevArray<uint32_t> csort;       // scratch of the counting sort (FS_SORT_COUNTING)
+    DevArray<uint32_t> cs;          // dense cell-start table, ncell+1
+    DevArray<uint32_t> start_ref;   // reference start_indices (persistent, never cleared)
+    DevArray<uint32_t> counter;     // the passes' work counters: from [0] the reorder's gap worklist, [4..5] the force pass
+    DevArray<unsigned char> owned;  // slab mode
+
+    // the arrays every handle and every strip has, for `cap` slots
+    hipError_t alloc_common(size_t cap) {
+        hipError_t e = hipSuccess;
+        auto ok = [&e](hipError_t r) { e = r; return r == hipSuccess; };
+        (void)(ok(pos.alloc(cap)) && ok(vel.alloc(cap)) && ok(pos_s.alloc(cap)) && ok(vel_s.alloc(cap)) &&
+               ok(pred.alloc(cap + FS_PRED_SLACK)) && ok(rho.alloc(cap)) && ok(rho2.alloc(cap)) && ok(safe.alloc((cap + 63) / 64 + 1)) &&
+               ok(fdefer.alloc(2 * ((cap + 255) / 256 + 8))) && ok(fwork.alloc(2 * (cap / 256 + 8) + 16)) &&
+               ok(bbounds.alloc(8 * ((cap + 255) / 256 + 8))) && ok(pairs.alloc(cap)) && ok(counter.alloc(8)));
+        return e;
+    }
+    // What the step launchers see of this set (fs_kernels.h); the force pass writes the new state over pos / vel.
+    StepArrays step_arrays() const {
+        StepArrays A;
+        A.pos = pos.p; A.vel = vel.p; A.pos_s = pos_s.p; A.vel_s = vel_s.p; A.pred = pred.p;
+        A.rho = rho.p; A.rho2 = rho2.p; A.pairs = pairs.p; A.cs = cs.p; A.start_ref = start_ref.p; A.safe = safe.p;
+        A.fdefer = fdefer.p; A.fwork = fwork.p; A.fcount = counter.p + 4;
+        A.pos_out = pos.p; A.vel_out = vel.p;
+        A.owned = owned.p; A.csort = csort.p; A.counter = counter.p;
+        return A;
+    }
+};
+
+// Streams, events and the other things of a handle that are not device arrays.
+struct HandleQueues {
+    Stream stream;
+    Stream side;                    // second stream of the force pass (general workgroups beside the lean kernel)
+    Event ev_fork, ev_join;         // ... of `side`
+    Event t0, t1;                   // fs_timed_steps
+    SortPolicy sortp;               // host side of the sort's late-stage plan (sort_policy.h)
+    PassRing prof;                  // per-pass timing (fs_host.h)
+};
+
+// The next step's messages, built by the edge columns' chain of an edge-first step into the send buffers of the last
+// fs_slab_pack.  The next fs_slab_pack sends them as they are if nothing they depend on has changed since.
+struct PrebuiltMessages {
+    void *left = nullptr, *right = nullptr;   // the buffers the last fs_slab_pack was given (nullptr: no neighbour on that side)
+    bool valid = false;                       // they hold the messages of tick + 1 ...
+    float delta = 0.0f;                       // ... built with this delta
+    uint32_t lo = 0, hi = 0;                  // ... and this owned window
+    bool classified = false;                  // that chain also classified its particles' slots for the next pack (the histogram
+                                              // counts it added stand until that pack, whether the messages are still valid or not)
+    bool matches(const fs_slab_config& c, const void* send_left, const void* send_right, float d) const {
+        return valid && left == (c.has_left ? send_left : nullptr) && right == (c.has_right ? send_right : nullptr) && delta == d &&
+               lo == c.own_lo && hi == c.own_hi;
+    }
+    void invalidate() { valid = false; }
+    void built(const fs_slab_config& c, float d) { valid = true; delta = d; lo = c.own_lo; hi = c.own_hi; }
+};
+
+// Everything only a slab (multi-GPU) handle has: engine_slab.hip.  Torn down like the handle itself, in reverse order of
+// declaration: the device arrays, then the events, the exchange stream last.
+struct SlabState {
+    Stream comm;                    // the exchange's stream (fs_slab_exchange, or the caller's transport between comm_begin / comm_end)
+    Event ev_packed;                // main stream: both outgoing messages are complete
+    Event ev_exch;                  // comm stream: both incoming messages have arrived
+    Event ev_fork2;                 // edge-first: the density pass is done, the edge columns' chain may start on `comm`
+
+    fs_slab_config cfg{};
+    uint32_t main_slots = 0;        // capacity - 2 * recv_capacity
+    bool counting = true;           // the handle's sort is the counting sort (else the network: serial step only)
+    bool packed = false;            // between fs_slab_pack and fs_slab_step
+    uint32_t state_lo = 0, state_hi = 0;   // the owned window the current keys / cell starts were built with
+
+    // Overlapped slab step (counting sort only): fs_slab_pack enqueues the pack AND the whole step of the
+    // interior columns; the halo exchange runs beside it on `comm`; fs_slab_step finishes the columns within `boundary_cols`
+    // of a slab edge on the strip arrays (kernels_slab.hip "boundary strips").
+    bool transposed = false;               // cell ids column-major (fs_device.h StepParams::transposed): ranks with neighbours, not the strip step
+    bool overlap = false;                  // FS_SLAB_STRIPS: ghosts stay out of the main array, boundary strips after the exchange
+    bool edge_first = false;               // the default: the next step's messages are built right after the edge columns' force launch
+    PrebuiltMessages pre;                  // edge-first
+    uint32_t msg_epoch = 0;                // one number per k_slab_msg launch (its look-back state is never cleared)
+    fs_tick_settings last_tick{};
+    bool exch_pending = false;             // fs_slab_step must wait for ev_exch
+    bool join_pending = false;             // edge-first: the simulation's stream has not yet waited for the edge columns' chain of the last step (slab_join)
+    uint32_t boundary_cols = 4;            // owned columns per neighboured edge left to the strips (>= 3)
+    uint32_t pending_shift = 0;            // columns a window edge moved since the last pack: that step's migrants land deeper
+    // Columns of the overlapped step last planned (plan_overlap).  A strips step is planned by fs_slab_pack and finished from
+    // this by fs_slab_step; the next fs_slab_pack of an edge-first handle checks its classification against these interior columns.
+    OverlapPlan last_plan;
+    bool prof = false;                     // profiling state latched by fs_slab_pack for the matching fs_slab_step
+
+    DevArray<uint2> blockcnt;           // per 256-slot block: records for the left / right message (k_slab_pack)
+    DevArray<uint32_t> stage;           // ... and the slots themselves, 2 x 256 entries per block
+    DevArray<u64> msg_state;            // k_slab_msg's look-back words
+    DevArray<uint32_t> counters;        // [0] n_live, [2] lost, [3] overflow, [4] far_halo
+    DevArray<uint32_t> hist;
+    // The strip's own particle array (ParticleArrays; its force pass writes pos_out / vel_out, which the write-back scatters
+    // into the main array through `back`).
+    struct Strip : ParticleArrays {
+        DevArray<float2> pos_out, vel_out;
+        DevArray<uint32_t> back, rowbase, counters;
+        uint32_t cap = 0;
+        StepArrays step_arrays() const {
+            StepArrays A = ParticleArrays::step_arrays();
+            A.pos_out = pos_out.p; A.vel_out = vel_out.p;
+            A.n_dev = counters.p + 2;      // strip_counters[2]: slots in use
+            return A;
+        }
+        // what the strip launchers see (fs_kernels.h); ncell_alloc: the handle's allocated cell count
+        StripArrays strip_arrays(uint32_t ncell_alloc) const {
+            StripArrays T;
+            T.cap = cap; T.pos = pos.p; T.vel = vel.p; T.kt = counting_sort_kt(csort.p, cap, ncell_alloc);
+            T.hist = counting_sort_hist(csort.p); T.back = back.p; T.rowbase = rowbase.p; T.safe = safe.p; T.counters = counters.p;
+            T.pairs = pairs.p; T.pos_out = pos_out.p; T.vel_out = vel_out.p; T.pred = pred.p; T.rho = rho.p;
+            return T;
+        }
+    } strip;
+
+    // where last step's migrants sit: an overlapped (strips) step leaves them in the 2R slots past the main ones
+    uint32_t migrant_slots() const { return overlap ? 2u * cfg.recv_capacity : 0u; }
+    // one set of messages as the slab launchers see it; a side without a neighbour has no buffer
+    SlabMessages messages(const void* left, const void* right, uint32_t epoch = 0) const {
+        return {cfg.recv_capacity, (int)cfg.has_left, (int)cfg.has_right, cfg.has_left ? const_cast<void*>(left) : nullptr,
+                cfg.has_right ? const_cast<void*>(right) : nullptr, epoch};      // (the unpack launchers only read the buffers)
+    }
+};
+
+}  // namespace fsd
+
+// Every resource is held by an owner (fs_host.h) and freed by `delete`.  Teardown order: members go in reverse order of
+// declaration, then the bases from right to left — so first a slab handle's own state (SlabState: its device arrays, its events,
+// its stream), then the device arrays (the members below, then ParticleArrays), then HandleQueues backwards: the events (profile
+// ring, sort policy, the named ones), and the streams last.  fs_destroy synchronises both streams before any of it.
+struct fs_sim : fsd::HandleQueues, fsd::ParticleArrays {
+    fs_settings settings{};
+    fs_options opts{};
+    uint32_t n = 0, capacity = 0;
+    uint32_t grid_w = 0, grid_h = 0, ncell = 0;
+    uint32_t tick = 0;
+    fs_uniform uniform{};
+    int device = 0;
+
+    // the main array: ParticleArrays, and
+    fsd::DevArray<uint32_t> key;         // keys of an uploaded / initial state; after a step they live in `pairs` (key_in_pairs)
+    bool key_in_pairs = false;
+    bool rho_in_rho2 = false;       // likewise the densities: rho2.x after a strict / ulp step, `rho` after an upload or a tolerance step
+    fsd::DevArray<uint32_t> sort_dirty;  // per-tile flags of the bitonic sort
+    fsd::DevArray<float2> tex;           // force field
+    bool tex_zero = true;           // the host knows every entry is +-0 (zero-initialised, or an all-zero upload)
+    fsd::DevArray<unsigned char> work;   // gap worklist
+    uint32_t work_cap = 0;
+    fsd::DevArray<fs_particle> aos;      // lazily allocated 32-byte view
+    bool aos_live = false;          // a hand-off is registered: the force pass writes the AoS records itself
+    uint32_t aos_tick = 0xFFFFFFFFu;   // tick whose state the AoS view holds (only meaningful with aos_live)
+    // surface tension (build extension; single-domain handles): fs_set_surface_tension
+    fsd::DevArray<float2> stf;           // per sorted slot: the last ST step's force (allocated on first enable)
+    bool st_on = false;
+    bool st_valid = false;          // an ST step has been enqueued since create / since ST was last enabled
+    // particle tracking (build extension; single-domain handles): fs_track_enable.  Two sets that swap roles
+    // every step: [trk_cur] holds the ids / channels in the order of the last enqueued step.  Channel c: trk_attr[..] + c * capacity.
+    fsd::DevArray<uint32_t> trk_id[2];
+    fsd::DevArray<float> trk_attr[2];
+    int trk_channels = -1;          // -1: off
+    int trk_alloc_channels = 0;     // channels the attr arrays were allocated for
+    int trk_cur = 0;
+    // field sampling (build extension): the records and the cell table belong together — a step has been enqueued
+    // since create and since the last fs_upload_particles / fs_upload_start_indices
+    bool sample_ready = false;
+
+    fsd::ConstDiv div_2h3{}, div_h2{};   // exact constant divisions of the force pass, proven at create
+    fsd::ConstDiv div_h{};               // ... and of the cell coordinates (x / h), over the numerators clamped positions give
+    bool rcp_ok = false, sqrt_ok = false; // rcp_rn_fast / sqrt_rn_fast proven on this device at create
+
+    // the main array as the step launchers see it
+    fsd::StepArrays step_arrays() const {
+        fsd::StepArrays A = ParticleArrays::step_arrays();
+        A.tex = tex.p; A.work = work.p; A.key_s = key.p;
+        return A;
+    }
+    // ... and, on a slab handle, as the slab launchers see it
+    fsd::SlabArrays slab_arrays() const {
+        const fsd::SlabState& S = *slab;
+        fsd::SlabArrays A;
+        static_cast<fsd::StepArrays&>(A) = step_arrays();
+        A.cap = capacity; A.main_slots = S.main_slots; A.counting = S.counting; A.overlap = S.overlap; A.aos = aos.p;
+        A.out = S.counting ? fsd::counting_sort_kt(csort.p, capacity, ncell) : pairs.p;
+        A.hist = fsd::counting_sort_hist(csort.p);
+        A.blockcnt = S.blockcnt.p; A.stage = S.stage.p; A.msg_state = S.msg_state.p; A.counters = S.counters.p;
+        return A;
+    }
+    // the side stream of the force pass and what the sort policy's reports of a few steps ago suggest for its follow-up launches
+    fsd::ForceLaunch force_launch() const {
+        fsd::ForceLaunch L;
+        L.side = side; L.ev_fork = ev_fork; L.ev_join = ev_join;
+        L.general_grid = sortp.general_grid(); L.general_hint = sortp.general_hint();
+        return L;
+    }
+
+    std::unique_ptr<fsd::SlabState> slab;   // slab (multi-GPU) mode; empty on a plain handle
+};
+
+namespace fsd {
+
+// ---- engine.hip ---------------------------------------------------------------------------------------------------
+// src/simulation.rs:140-141
+void grid_dims(const fs_settings& s, uint32_t* gw, uint32_t* gh);
+bool settings_valid(const fs_settings& s, std::string* why);
+// src/simulation.rs:470-497
+void host_uniform(const fs_settings& s, const fs_tick_settings& t, uint32_t tick, fs_uniform* u);
+// Step parameters of the handle for the uniform of some tick and, on a slab handle, some owned window [own_lo, own_hi).
+StepParams make_params(const fs_sim& s, const fs_uniform& u, uint32_t own_lo = 0, uint32_t own_hi = 0);
+// What fs_create_ex and fs_slab_create share, once settings, sort mode, capacity and grid are set (create_common), and what both
+// end with after the initial state is in place (create_finish).
+fs_status create_common(fs_sim* s);
+fs_status create_finish(fs_sim* s);
+// After a synchronisation of the stream: a barrier time-out of the sort's stand-by kernel makes the state undefined from
+// that step on — whoever is about to receive state (or a "finished" signal) must hear about it.
+fs_status sort_health(fs_sim* s);
+// The create calls' device check: `device` names a HIP device of this process, which becomes the current one.
+fs_status use_device(int device);
+// Create-time proofs, exhaustive, on the device; blocking.  prove_constdiv: x / c == div_const_fast(x, c, RN(1/c)) for every f32 x
+// with 2^-60 <= |x| <= hi (hi == 0: c, the force kernel's numerators); out->ok stays 0 where the proof does not apply, fails, or is not `enabled`.
+// prove_rcp_sqrt: the lean reciprocal / square root of the shared-denominator path over their whole ranges (both false under
+// FS_NO_SHAREDIV).  The scratch words are device memory the proof may overwrite.
+fs_status prove_constdiv(hipStream_t st, uint32_t* scratch_word, float c, ConstDiv* out, float hi = 0.0f, bool enabled = true);
+fs_status prove_rcp_sqrt(hipStream_t st, uint32_t* scratch_two_words, bool* rcp_ok, bool* sqrt_ok);
+
+// ---- engine_slab.hip: what a plain entry point asks of a slab handle (no-ops on a plain one) -----------------
+// Edge-first slab step: the edge columns' chain of the last step (exchange stream) has advanced its particles and classified their
+// slots; the simulation's stream only waits for it when something other than the next pack -> exchange -> step cycle needs that
+// state (the cycle itself is ordered by the exchange's event).  Every entry point that reads or replaces the state calls this.
+fs_status slab_join(fs_sim* s);
+#define FS_JOIN(s) FS_TRY(fsd::slab_join(s))
+fs_status slab_sync(fs_sim* s);    // fs_sync: an exchange or edge chain still in flight on the exchange stream
+
+}  // namespace fsd

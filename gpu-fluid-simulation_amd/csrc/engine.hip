@@ -14,10 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/fluidsim.h"
-#include "fs_host.h"
-#include "fs_kernels.h"
-#include "sort_policy.h"
+#include "engine.h"
 
 static_assert(sizeof(fs_particle) == 32, "ParticleInstance is 32 bytes (src/simulation.rs:126-135)");
 static_assert(offsetof(fs_particle, predicted_position) == 8 && offsetof(fs_particle, velocity) == 16 &&
@@ -29,12 +26,9 @@ static_assert(offsetof(fs_uniform, gravity) == 16 && offsetof(fs_uniform, smooth
                   offsetof(fs_uniform, grid_w) == 104 && offsetof(fs_uniform, texture_size) == 112,
               "SimulationUniform offsets");
 
-namespace {
-thread_local std::string g_err;
-}  // namespace
+static thread_local std::string g_err;
 namespace fsd { void set_last_error(const std::string& msg) { g_err = msg; } }   // fs_host.h: fail()
-using fsd::DevArray;
-using fsd::fail;
+using namespace fsd;
 namespace {
 
 const float PI_F = 3.14159265359f;   // funcs.wgsl:54 == std::f32::consts::PI in f32
@@ -51,188 +45,6 @@ float powi_f32(float a, int b) {
     }
     return recip ? 1.0f / r : r;
 }
-
-// src/simulation.rs:140-141
-void grid_dims(const fs_settings& s, uint32_t* gw, uint32_t* gh) {
-    *gw = (uint32_t)((size_t)std::ceil(s.size.x / s.smoothing_radius) + 2);
-    *gh = (uint32_t)((size_t)std::ceil(s.size.y / s.smoothing_radius) + 2);
-}
-
-bool settings_valid(const fs_settings& s, std::string* why) {
-    if (s.particle_count <= 1) { *why = "particle_count <= 1 (reference panics in ilog2, src/simulation.rs:323-324)"; return false; }
-    if (s.particle_count > (1u << 28)) { *why = "particle_count > 2^28 (the kernels use 32-bit byte offsets into 8-byte arrays)"; return false; }
-    if (!(s.smoothing_radius > 0.0f) || !std::isfinite(s.smoothing_radius)) { *why = "smoothing_radius must be finite and > 0"; return false; }
-    if (!(s.size.x > 0.0f) || !(s.size.y > 0.0f) || !std::isfinite(s.size.x) || !std::isfinite(s.size.y)) { *why = "size must be finite and > 0"; return false; }
-    if (!std::isfinite(s.particle_spacing)) { *why = "particle_spacing must be finite"; return false; }
-    const double gw = std::ceil((double)s.size.x / s.smoothing_radius) + 2, gh = std::ceil((double)s.size.y / s.smoothing_radius) + 2;
-    if (gw * gh >= 4294967295.0) { *why = "grid_w*grid_h does not fit u32 cell ids"; return false; }
-    if ((double)s.texture_size.x * s.texture_size.y >= 4294967295.0) { *why = "texture too large"; return false; }
-    return true;
-}
-
-// The arrays one particle array's sort-reorder, density and force passes work on: the main array of every handle (fs_sim) and
-// the boundary strip of an overlapped slab step (fs_sim::Strip) each hold one set.
-struct ParticleArrays {
-    // SoA state.  pos/vel: current state (cell order of the last step).  *_s: the
-    // cell-sorted snapshot the density/force passes read (Jacobi semantics).
-    DevArray<float2> pos, vel, pos_s, vel_s, pred;
-    DevArray<float> rho;
-    DevArray<float2> rho2;          // {density, RN(1/density)}: what the force pass gathers per neighbour
-    DevArray<uint32_t> fdefer, fwork;   // force pass: per-block deferred-wave bits and the worklist (counter[3] = its length)
-    DevArray<uint32_t> bbounds;         // 8 words per 256-particle block: the density pass's block-wide sweep ranges, read by the force pass
-    DevArray<unsigned long long> safe;   // one bit per sorted particle: coordinates / velocity inside the exact-quotient ranges (fs_device.h)
-    DevArray<fsd::u64> pairs;
-    DevArray<uint32_t> csort;       // scratch of the counting sort (FS_SORT_COUNTING)
-    DevArray<uint32_t> cs;          // dense cell-start table, ncell+1
-    DevArray<uint32_t> start_ref;   // reference start_indices (persistent, never cleared)
-    DevArray<uint32_t> counter;     // the passes' work counters: from [0] the reorder's gap worklist, [4..5] the force pass
-    DevArray<unsigned char> owned;  // slab mode
-
-    // the arrays every handle and every strip has, for `cap` slots
-    hipError_t alloc_common(size_t cap) {
-        hipError_t e = hipSuccess;
-        auto ok = [&e](hipError_t r) { e = r; return r == hipSuccess; };
-        (void)(ok(pos.alloc(cap)) && ok(vel.alloc(cap)) && ok(pos_s.alloc(cap)) && ok(vel_s.alloc(cap)) &&
-               ok(pred.alloc(cap + FS_PRED_SLACK)) && ok(rho.alloc(cap)) && ok(rho2.alloc(cap)) && ok(safe.alloc((cap + 63) / 64 + 1)) &&
-               ok(fdefer.alloc(2 * ((cap + 255) / 256 + 8))) && ok(fwork.alloc(2 * (cap / 256 + 8) + 16)) &&
-               ok(bbounds.alloc(8 * ((cap + 255) / 256 + 8))) && ok(pairs.alloc(cap)) && ok(counter.alloc(8)));
-        return e;
-    }
-    // What the step launchers see of this set (fs_kernels.h); the force pass writes the new state over pos / vel.
-    fsd::StepArrays step_arrays() const {
-        fsd::StepArrays A;
-        A.pos = pos.p; A.vel = vel.p; A.pos_s = pos_s.p; A.vel_s = vel_s.p; A.pred = pred.p;
-        A.rho = rho.p; A.rho2 = rho2.p; A.pairs = pairs.p; A.cs = cs.p; A.start_ref = start_ref.p; A.safe = safe.p;
-        A.fdefer = fdefer.p; A.fwork = fwork.p; A.fcount = counter.p + 4;
-        A.pos_out = pos.p; A.vel_out = vel.p;
-        A.owned = owned.p; A.csort = csort.p; A.counter = counter.p;
-        return A;
-    }
-};
-
-// Streams, events and the other things of a handle that are not device arrays.
-struct HandleQueues {
-    fsd::Stream stream;
-    fsd::Stream side;               // second stream of the force pass (general workgroups beside the lean kernel)
-    fsd::Stream comm;               // slab: the exchange's stream (fs_slab_exchange, or the caller's transport between comm_begin / comm_end)
-    fsd::Event ev_fork, ev_join;    // ... of `side`
-    fsd::Event ev_packed;           // main stream: both outgoing messages are complete
-    fsd::Event ev_exch;             // comm stream: both incoming messages have arrived
-    fsd::Event ev_fork2;            // edge-first: the density pass is done, the edge columns' chain may start on `comm`
-    fsd::Event t0, t1;              // fs_timed_steps
-    fsd::SortPolicy sortp;          // host side of the sort's late-stage plan (sort_policy.h)
-    fsd::PassRing prof;             // per-pass timing (fs_host.h)
-};
-
-}  // namespace
-
-// Every resource is held by an owner (fs_host.h) and freed by `delete`.  Teardown order: members go in reverse order of
-// declaration, then the bases from right to left — so first the device arrays (the members below, then ParticleArrays), then
-// HandleQueues backwards: the events (profile ring, sort policy, the named ones), and the streams last.
-struct fs_sim : HandleQueues, ParticleArrays {
-    fs_settings settings{};
-    fs_options opts{};
-    uint32_t n = 0, capacity = 0;
-    uint32_t grid_w = 0, grid_h = 0, ncell = 0;
-    uint32_t tick = 0;
-    fs_uniform uniform{};
-    int device = 0;
-
-    // the main array: ParticleArrays, and
-    DevArray<uint32_t> key;         // keys of an uploaded / initial state; after a step they live in `pairs` (key_in_pairs)
-    bool key_in_pairs = false;
-    bool rho_in_rho2 = false;       // likewise the densities: rho2.x after a strict / ulp step, `rho` after an upload or a tolerance step
-    DevArray<uint32_t> sort_dirty;  // per-tile flags of the bitonic sort
-    DevArray<float2> tex;           // force field
-    bool tex_zero = true;           // the host knows every entry is +-0 (zero-initialised, or an all-zero upload)
-    DevArray<unsigned char> work;   // gap worklist
-    uint32_t work_cap = 0;
-    DevArray<fs_particle> aos;      // lazily allocated 32-byte view
-    bool aos_live = false;          // a hand-off is registered: the force pass writes the AoS records itself
-    uint32_t aos_tick = 0xFFFFFFFFu;   // tick whose state the AoS view holds (only meaningful with aos_live)
-    // surface tension (build extension; single-domain handles): fs_set_surface_tension
-    DevArray<float2> stf;           // per sorted slot: the last ST step's force (allocated on first enable)
-    bool st_on = false;
-    bool st_valid = false;          // an ST step has been enqueued since create / since ST was last enabled
-    // particle tracking (build extension; single-domain handles): fs_track_enable.  Two sets that swap roles
-    // every step: [trk_cur] holds the ids / channels in the order of the last enqueued step.  Channel c: trk_attr[..] + c * capacity.
-    DevArray<uint32_t> trk_id[2];
-    DevArray<float> trk_attr[2];
-    int trk_channels = -1;          // -1: off
-    int trk_alloc_channels = 0;     // channels the attr arrays were allocated for
-    int trk_cur = 0;
-    // field sampling (build extension): the records and the cell table belong together — a step has been enqueued
-    // since create and since the last fs_upload_particles / fs_upload_start_indices
-    bool sample_ready = false;
-
-    fsd::ConstDiv div_2h3{}, div_h2{};   // exact constant divisions of the force pass, proven at create
-    fsd::ConstDiv div_h{};               // ... and of the cell coordinates (x / h), over the numerators clamped positions give
-    bool rcp_ok = false, sqrt_ok = false; // rcp_rn_fast / sqrt_rn_fast proven on this device at create
-
-    // slab (multi-GPU) mode
-    bool slab = false;
-    fs_slab_config slab_cfg{};
-    uint32_t slab_main = 0;         // capacity - 2 * recv_capacity
-    DevArray<uint2> blockcnt;           // per 256-slot block: records for the left / right message (k_slab_pack)
-    DevArray<uint32_t> stage;           // ... and the slots themselves, 2 x 256 entries per block
-    DevArray<fsd::u64> msg_state;       // k_slab_msg's look-back words
-    DevArray<uint32_t> slab_counters;   // [0] n_live, [2] lost, [3] overflow, [4] far_halo
-    DevArray<uint32_t> hist;
-    bool slab_packed = false;
-    uint32_t state_lo = 0, state_hi = 0;   // the owned window the current keys / cell starts were built with
-
-    // Overlapped slab step (counting sort only): fs_slab_pack enqueues the pack AND the whole step of the
-    // interior columns; the halo exchange runs beside it on `comm`; fs_slab_step finishes the columns within `boundary_cols`
-    // of a slab edge on the strip arrays (kernels_slab.hip "boundary strips").
-    bool transposed = false;               // cell ids column-major (fs_device.h StepParams::transposed): ranks with neighbours, not the strip step
-    bool overlap = false;                  // FS_SLAB_STRIPS: ghosts stay out of the main array, boundary strips after the exchange
-    bool edge_first = false;               // the default: the next step's messages are built right after the edge columns' force launch
-    bool prepacked = false;                // edge-first: the send buffers hold the messages of tick + 1 ...
-    void *pp_left = nullptr, *pp_right = nullptr;   // ... these buffers (the ones the last fs_slab_pack was given)
-    float pp_delta = 0.0f;                 // ... built with this delta
-    uint32_t pp_lo = 0, pp_hi = 0;         // ... and this owned window
-    uint32_t msg_epoch = 0;                // one number per k_slab_msg launch (its look-back state is never cleared)
-    fs_tick_settings last_tick{};
-    bool exch_pending = false;             // fs_slab_step must wait for ev_exch
-    bool join_pending = false;             // edge-first: the simulation's stream has not yet waited for the edge columns' chain of the last step (slab_join)
-    bool edge_classified = false;          // edge-first: that chain also classified its particles' slots for the next pack
-    uint32_t boundary_cols = 4;            // owned columns per neighboured edge left to the strips (>= 3)
-    uint32_t pending_shift = 0;            // columns a window edge moved since the last pack: that step's migrants land deeper
-    uint32_t adv_lo = 0, adv_hi = 0;       // interior columns of the step being enqueued
-    uint32_t strip_win[4] = {0, 0, 0, 0};
-    bool strip_active = false;
-    // The strip's own particle array (ParticleArrays; its force pass writes pos_out / vel_out, which the write-back scatters
-    // into the main array through `back`).
-    struct Strip : ParticleArrays {
-        DevArray<float2> pos_out, vel_out;
-        DevArray<uint32_t> back, rowbase, counters;
-        uint32_t cap = 0;
-        fsd::StepArrays step_arrays() const {
-            fsd::StepArrays A = ParticleArrays::step_arrays();
-            A.pos_out = pos_out.p; A.vel_out = vel_out.p;
-            A.n_dev = counters.p + 2;      // strip_counters[2]: slots in use
-            return A;
-        }
-    } strip;
-
-    bool slab_prof = false;                // profiling state latched by fs_slab_pack for the matching fs_slab_step
-
-    // the main array as the step launchers see it
-    fsd::StepArrays step_arrays() const {
-        fsd::StepArrays A = ParticleArrays::step_arrays();
-        A.tex = tex.p; A.work = work.p; A.key_s = key.p;
-        return A;
-    }
-    // the side stream of the force pass and what the sort policy's reports of a few steps ago suggest for its follow-up launches
-    fsd::ForceLaunch force_launch() const {
-        fsd::ForceLaunch L;
-        L.side = side; L.ev_fork = ev_fork; L.ev_join = ev_join;
-        L.general_grid = sortp.general_grid(); L.general_hint = sortp.general_hint();
-        return L;
-    }
-};
-
-namespace {
 
 void host_lattice(const fs_settings& s, fs_vec2 off, fs_particle* dst, size_t n) {
     // src/simulation.rs:147-163 — f32 arithmetic exactly as written.
@@ -251,7 +63,28 @@ void host_lattice(const fs_settings& s, fs_vec2 off, fs_particle* dst, size_t n)
     }
 }
 
-void host_uniform(const fs_settings& s, const fs_tick_settings& t, uint32_t tick, fs_uniform* u) {
+}  // namespace
+
+// ---- shared with engine_slab.hip and sim3d.hip (engine.h) ------------------------------------------------------------
+// src/simulation.rs:140-141
+void fsd::grid_dims(const fs_settings& s, uint32_t* gw, uint32_t* gh) {
+    *gw = (uint32_t)((size_t)std::ceil(s.size.x / s.smoothing_radius) + 2);
+    *gh = (uint32_t)((size_t)std::ceil(s.size.y / s.smoothing_radius) + 2);
+}
+
+bool fsd::settings_valid(const fs_settings& s, std::string* why) {
+    if (s.particle_count <= 1) { *why = "particle_count <= 1 (reference panics in ilog2, src/simulation.rs:323-324)"; return false; }
+    if (s.particle_count > (1u << 28)) { *why = "particle_count > 2^28 (the kernels use 32-bit byte offsets into 8-byte arrays)"; return false; }
+    if (!(s.smoothing_radius > 0.0f) || !std::isfinite(s.smoothing_radius)) { *why = "smoothing_radius must be finite and > 0"; return false; }
+    if (!(s.size.x > 0.0f) || !(s.size.y > 0.0f) || !std::isfinite(s.size.x) || !std::isfinite(s.size.y)) { *why = "size must be finite and > 0"; return false; }
+    if (!std::isfinite(s.particle_spacing)) { *why = "particle_spacing must be finite"; return false; }
+    const double gw = std::ceil((double)s.size.x / s.smoothing_radius) + 2, gh = std::ceil((double)s.size.y / s.smoothing_radius) + 2;
+    if (gw * gh >= 4294967295.0) { *why = "grid_w*grid_h does not fit u32 cell ids"; return false; }
+    if ((double)s.texture_size.x * s.texture_size.y >= 4294967295.0) { *why = "texture too large"; return false; }
+    return true;
+}
+
+void fsd::host_uniform(const fs_settings& s, const fs_tick_settings& t, uint32_t tick, fs_uniform* u) {
     // src/simulation.rs:470-497
     const float h = s.smoothing_radius;
     std::memset(u, 0, sizeof *u);
@@ -284,9 +117,8 @@ void host_uniform(const fs_settings& s, const fs_tick_settings& t, uint32_t tick
     u->texture_size.y = (float)s.texture_size.y;
 }
 
-fsd::StepParams make_params(const fs_sim& s) {
-    const fs_uniform& u = s.uniform;
-    fsd::StepParams P;
+StepParams fsd::make_params(const fs_sim& s, const fs_uniform& u, uint32_t own_lo, uint32_t own_hi) {
+    StepParams P;
     std::memset(&P, 0, sizeof P);
     P.n = s.n;
     P.grid_w = s.grid_w; P.grid_h = s.grid_h; P.ncell = s.ncell;
@@ -335,16 +167,16 @@ fsd::StepParams make_params(const fs_sim& s) {
     P.n_live = nullptr;
     if (s.slab) {
         // local window: 1 padding + 2 ghost columns each side of [own_lo, own_hi)
-        P.grid_w = s.slab_cfg.own_hi - s.slab_cfg.own_lo + 6u;
+        P.grid_w = own_hi - own_lo + 6u;
         P.ncell = P.grid_w * s.grid_h;
-        P.col_origin = (int32_t)s.slab_cfg.own_lo - 3;
-        P.own_lo = s.slab_cfg.own_lo; P.own_hi = s.slab_cfg.own_hi;
+        P.col_origin = (int32_t)own_lo - 3;
+        P.own_lo = own_lo; P.own_hi = own_hi;
         P.n = s.capacity;
-        P.n_live = s.slab_counters.p;
+        P.n_live = s.slab->counters.p;
         P.ref_quirks = 0;   // the global stale-start quirk cannot exist per rank (§8e)
         // the serial step advances every owned column in its one force launch; the overlapped step narrows this per launch
         P.adv_lo = P.own_lo; P.adv_hi = P.own_hi; P.adv_outside = 0;
-        P.transposed = s.transposed ? 1 : 0;
+        P.transposed = s.slab->transposed ? 1 : 0;
     }
     P.grid_u = P.transposed ? P.grid_h : P.grid_w;
     P.grid_v = P.transposed ? P.grid_w : P.grid_h;
@@ -353,23 +185,21 @@ fsd::StepParams make_params(const fs_sim& s) {
     return P;
 }
 
-// Prove (exhaustively, on the device) that x / c == div_const_fast(x, c, RN(1/c)) for every f32 x.
-// Stored keys, cell starts and the column origin belong to the window of the LAST step (or import); a
-// window set since then (fs_slab_set_window) only takes effect at the next pack.  Anything that reads
-// the stored state back in global coordinates must use this.
-fsd::StepParams make_params_of_state(fs_sim& s) {
-    const fs_slab_config cfg = s.slab_cfg;
-    if (s.slab && s.state_hi > s.state_lo) { s.slab_cfg.own_lo = s.state_lo; s.slab_cfg.own_hi = s.state_hi; }
-    const fsd::StepParams P = make_params(s);
-    s.slab_cfg = cfg;
-    return P;
+fs_status fsd::use_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(FS_ERR_DEVICE, "no HIP device: the engine has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(FS_ERR_INVALID, "device ordinal out of range");
+    FS_HIP(hipSetDevice(device));
+    return FS_OK;
 }
 
-fs_status prove_constdiv(hipStream_t st, uint32_t* scratch_word, float c, fsd::ConstDiv* out, float hi = 0.0f) {
+// Prove (exhaustively, on the device) that x / c == div_const_fast(x, c, RN(1/c)) for every f32 x.
+fs_status fsd::prove_constdiv(hipStream_t st, uint32_t* scratch_word, float c, ConstDiv* out, float hi, bool enabled) {
     out->c = c;
     out->y = 1.0f / c;
     out->ok = 0;
-    if (!(c > 4.0f * FS_CONSTDIV_MIN) || !std::isfinite(c) || !std::isfinite(out->y) || getenv("FS_NO_CONSTDIV")) return FS_OK;
+    if (!(c > 4.0f * FS_CONSTDIV_MIN) || !std::isfinite(c) || !std::isfinite(out->y) || !enabled) return FS_OK;
     if (!(hi > 0.0f)) hi = c;                          // the force kernel's numerators: 2^-60 <= |x| <= c
     if (!(hi < 0x1p40f) || !(hi >= FS_CONSTDIV_MIN)) return FS_OK;
     uint32_t bad = 1;
@@ -381,34 +211,35 @@ fs_status prove_constdiv(hipStream_t st, uint32_t* scratch_word, float c, fsd::C
     return FS_OK;
 }
 
-fs_status prove_force_constants(fs_sim* s) {
-    const float h = s->settings.smoothing_radius;
-    fs_status r = prove_constdiv(s->stream, s->counter.p + 1, 2.0f * h * h * h, &s->div_2h3);   // funcs.wgsl:119
-    if (r != FS_OK) return r;
-    r = prove_constdiv(s->stream, s->counter.p + 1, h * h, &s->div_h2);
-    if (r != FS_OK) return r;
-    {   // cell coordinates: (clamped position + half the bounds) / h, numerators 0 .. 2 bs (host_uniform: bs = size / 2 - ...)
-        const float reach = 4.0f * fmaxf(fabsf(s->settings.size.x), fabsf(s->settings.size.y));
-        r = prove_constdiv(s->stream, s->counter.p + 1, h, &s->div_h, reach);
-        if (r != FS_OK) return r;
-    }
-    // the lean reciprocal / square root of the shared-denominator path, over their whole ranges
-    s->rcp_ok = s->sqrt_ok = false;
+// the lean reciprocal / square root of the shared-denominator path, over their whole ranges
+fs_status fsd::prove_rcp_sqrt(hipStream_t st, uint32_t* scratch_two_words, bool* rcp_ok, bool* sqrt_ok) {
+    *rcp_ok = *sqrt_ok = false;
     if (getenv("FS_NO_SHAREDIV")) return FS_OK;
     uint32_t bad[2] = {1, 1};
-    FS_HIP(hipMemsetAsync(s->counter.p + 1, 0, 2 * sizeof(uint32_t), s->stream));
-    fsd::launch_verify_unary(s->stream, 0, FS_RCP_LO, FS_RCP_HI, s->counter.p + 1);
-    fsd::launch_verify_unary(s->stream, 1, FS_SQRT_LO, FS_SQRT_HI, s->counter.p + 2);
-    FS_HIP(hipMemcpyAsync(bad, s->counter.p + 1, sizeof bad, hipMemcpyDeviceToHost, s->stream));
-    FS_HIP(hipStreamSynchronize(s->stream));
-    s->rcp_ok = bad[0] == 0;
-    s->sqrt_ok = bad[1] == 0;
+    FS_HIP(hipMemsetAsync(scratch_two_words, 0, 2 * sizeof(uint32_t), st));
+    launch_verify_unary(st, 0, FS_RCP_LO, FS_RCP_HI, scratch_two_words);
+    launch_verify_unary(st, 1, FS_SQRT_LO, FS_SQRT_HI, scratch_two_words + 1);
+    FS_HIP(hipMemcpyAsync(bad, scratch_two_words, sizeof bad, hipMemcpyDeviceToHost, st));
+    FS_HIP(hipStreamSynchronize(st));
+    *rcp_ok = bad[0] == 0;
+    *sqrt_ok = bad[1] == 0;
     return FS_OK;
+}
+
+static fs_status prove_force_constants(fs_sim* s) {
+    const float h = s->settings.smoothing_radius;
+    const bool on = !getenv("FS_NO_CONSTDIV");     // (read by the 2D handles only)
+    FS_TRY(prove_constdiv(s->stream, s->counter.p + 1, 2.0f * h * h * h, &s->div_2h3, 0.0f, on));   // funcs.wgsl:119
+    FS_TRY(prove_constdiv(s->stream, s->counter.p + 1, h * h, &s->div_h2, 0.0f, on));
+    // cell coordinates: (clamped position + half the bounds) / h, numerators 0 .. 2 bs (host_uniform: bs = size / 2 - ...)
+    const float reach = 4.0f * fmaxf(fabsf(s->settings.size.x), fabsf(s->settings.size.y));
+    FS_TRY(prove_constdiv(s->stream, s->counter.p + 1, h, &s->div_h, reach, on));
+    return prove_rcp_sqrt(s->stream, s->counter.p + 1, &s->rcp_ok, &s->sqrt_ok);
 }
 
 // What fs_create_ex and fs_slab_create share, once settings, sort mode, capacity and grid are set: the streams and events,
 // the arrays every handle has, and the zeroes the reference's buffers start with.
-fs_status create_common(fs_sim* s) {
+fs_status fsd::create_common(fs_sim* s) {
     FS_HIP(hipStreamCreateWithFlags(&s->stream.h, hipStreamNonBlocking));
     // The pre-registered general work can run beside the lean force kernel on a second stream (FS_SIDE_STREAM=1).
     // Measured at 16M: force 0.725 -> 0.711 ms in the bench window and 1.10 -> 0.99 ms in the dense regime, but every
@@ -446,20 +277,26 @@ fs_status create_common(fs_sim* s) {
 }
 
 // ... and what both end with, after the initial state is in place: the create-time proofs and the uniform of tick 0.
-fs_status create_finish(fs_sim* s) {
-    const fs_status r = prove_force_constants(s);
-    if (r != FS_OK) return r;
+fs_status fsd::create_finish(fs_sim* s) {
+    FS_TRY(prove_force_constants(s));
     fs_tick_settings t0;
     std::memset(&t0, 0, sizeof t0);
     host_uniform(s->settings, t0, 0, &s->uniform);
     return FS_OK;
 }
 
-fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
+fs_status fsd::sort_health(fs_sim* s) {
+    if (s->slab || s->opts.sort_mode != FS_SORT_BITONIC) return FS_OK;
+    FS_HIP(s->sortp.check_timeout(s->sort_dirty.p, s->n));
+    if (s->sortp.dead) return fail(FS_ERR_DEVICE, "sort: the stand-by kernel's grid barrier timed out: the particle order is undefined from that step on; destroy the handle");
+    return FS_OK;
+}
+
+static fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
     s->tick += 1;                                              // src/simulation.rs:460
     host_uniform(s->settings, *t, s->tick, &s->uniform);
     s->uniform.particle_count = s->n;
-    fsd::StepParams P = make_params(*s);
+    StepParams P = make_params(*s, s->uniform);
     // reference-sort path: no sorted copy of the positions — the force pass takes its own particle's position from the
     // previous state through the pair's source index and writes the new state into the spare buffer (swapped below)
     static const bool pos_by_src_env = [] { const char* e = getenv("FS_POS_BY_SRC"); return e ? atoi(e) != 0 : true; }();
@@ -469,8 +306,7 @@ fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
     const bool prof = s->prof.on;
     hipEvent_t* ev = nullptr;
     if (prof) {
-        const fs_status r = s->prof.begin();
-        if (r != FS_OK) return r;
+        FS_TRY(s->prof.begin());
         ev = s->prof.current();
     }
     if (s->n == 0) return FS_OK;
@@ -535,112 +371,6 @@ fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
     return FS_OK;
 }
 
-// workgroups of the edge columns' launches in an edge-first step with column-major ids (each walks the device-side block ranges)
-#define FS_EDGE_GRID 1024u
-
-// ---- overlapped slab step --------------------------------------------------------------------------
-// Step parameters of the two force launches of an overlapped step: the interior launch (main array) and the strip launch.
-fsd::StepParams overlap_params(const fs_sim& s, bool strip) {
-    fsd::StepParams P = make_params(s);
-    P.adv_lo = s.adv_lo; P.adv_hi = s.adv_hi;
-    P.adv_outside = strip ? 1 : 0;
-    if (strip) { P.n = s.strip.cap; P.n_live = s.strip.counters.p; if (P.block_bounds) P.block_bounds = s.strip.bbounds.p; }
-    return P;
-}
-
-// Interior columns and strip windows of the step being packed.  Local columns: 0 and W-1 are padding, 1..2 and W-3..W-2 the
-// ghost columns, own_lo is local column 3 (make_params).
-void plan_overlap(fs_sim* s) {
-    const fs_slab_config& c = s->slab_cfg;
-    const uint32_t z = s->boundary_cols + s->pending_shift;
-    s->pending_shift = 0;
-    const uint32_t width = c.own_hi - c.own_lo, W = width + 6u;
-    const uint32_t zl = c.has_left ? z : 0u, zr = c.has_right ? z : 0u;
-    s->strip_active = c.has_left || c.has_right;
-    s->strip_win[0] = s->strip_win[1] = s->strip_win[2] = s->strip_win[3] = 0u;
-    if (zl + zr >= width) {                        // no interior: the strip holds the whole window
-        s->adv_lo = s->adv_hi = c.own_lo;
-        if (s->strip_active) { s->strip_win[0] = 1u; s->strip_win[1] = W - 1u; }
-        return;
-    }
-    s->adv_lo = c.own_lo + zl; s->adv_hi = c.own_hi - zr;
-    // a window = the two ghost columns + the boundary columns + two columns of interior context
-    const uint32_t lhi = 3u + zl + 2u, rlo = (W - 3u) - zr - 2u;
-    if (c.has_left && c.has_right && lhi >= rlo) { s->strip_win[0] = 1u; s->strip_win[1] = W - 1u; return; }
-    if (c.has_left) { s->strip_win[0] = 1u; s->strip_win[1] = lhi < W - 1u ? lhi : W - 1u; }
-    if (c.has_right) { s->strip_win[2] = rlo > 1u ? rlo : 1u; s->strip_win[3] = W - 1u; }
-}
-
-// Second half of fs_slab_pack: everything that does not need the incoming messages.
-fs_status slab_interior(fs_sim* s) {
-    hipStream_t st = s->stream;
-    FS_HIP(hipEventRecord(s->ev_packed, st));      // the outgoing messages are complete: the exchange may start
-    plan_overlap(s);
-    const fsd::StepParams P = overlap_params(*s, false);
-    hipEvent_t* ev = s->slab_prof ? s->prof.current() : nullptr;
-    if (ev) FS_HIP(hipEventRecord(ev[1], st));
-    fsd::launch_counting_sort_pairs(st, s->capacity, P.ncell, s->ncell, s->cs.p, s->csort.p, s->slab_counters.p, s->tick, nullptr, s->safe.p);
-    if (ev) FS_HIP(hipEventRecord(ev[2], st));
-    const fsd::StepArrays A = s->step_arrays();
-    fsd::launch_counting_reorder_slab(st, P, A, s->capacity, s->ncell);
-    if (s->strip_active) {                          // the main array's share of the strips: also independent of the messages
-        fs_sim::Strip& T = s->strip;
-        fsd::launch_strip_gather(st, P, s->strip_win, s->slab_cfg.recv_capacity, T.cap, s->cs.p, T.rowbase.p, s->pairs.p, s->pos_s.p,
-                                 s->vel_s.p, T.pos.p, T.vel.p, fsd::counting_sort_kt(T.csort.p, T.cap, s->ncell),
-                                 fsd::counting_sort_hist(T.csort.p), T.back.p, T.safe.p, T.counters.p, s->slab_counters.p);
-    }
-    if (ev) FS_HIP(hipEventRecord(ev[3], st));
-    fsd::launch_density(st, P, A);
-    if (ev) FS_HIP(hipEventRecord(ev[4], st));
-    fsd::launch_force(st, P, A, s->force_launch());
-    if (ev) FS_HIP(hipEventRecord(ev[5], st));
-    FS_HIP(hipGetLastError());
-    return FS_OK;
-}
-
-// fs_slab_step of an overlapped handle: the boundary strips, after the incoming messages.
-fs_status slab_boundary(fs_sim* s, const void* recv_left, const void* recv_right) {
-    hipStream_t st = s->stream;
-    if (s->exch_pending) { FS_HIP(hipStreamWaitEvent(st, s->ev_exch, 0)); s->exch_pending = false; }
-    hipEvent_t* ev = s->slab_prof ? s->prof.current() : nullptr;
-    if (s->strip_active) {
-        fs_sim::Strip& T = s->strip;
-        const fsd::StepParams P = overlap_params(*s, false), PS = overlap_params(*s, true);
-        fsd::u64* kt = fsd::counting_sort_kt(T.csort.p, T.cap, s->ncell);
-        fsd::launch_strip_unpack(st, P, s->slab_main, s->slab_cfg.recv_capacity, T.cap, s->slab_cfg.has_left ? recv_left : nullptr,
-                                 s->slab_cfg.has_right ? recv_right : nullptr, T.pos.p, T.vel.p, kt, fsd::counting_sort_hist(T.csort.p),
-                                 T.back.p, T.counters.p, s->slab_counters.p);
-        fsd::launch_counting_sort_pairs(st, T.cap, PS.ncell, s->ncell, T.cs.p, T.csort.p, T.counters.p, s->tick, T.counters.p + 2);
-        fsd::StepArrays TA = T.step_arrays();
-        TA.tex = s->tex.p;
-        fsd::launch_counting_reorder_slab(st, PS, TA, T.cap, s->ncell);
-        fsd::launch_density(st, PS, TA);
-        fsd::ForceLaunch L;
-        L.general_grid = 256u;
-        fsd::launch_force(st, PS, TA, L);
-        fsd::launch_strip_writeback(st, PS, s->slab_main, T.cap, T.pairs.p, T.back.p, T.pos_out.p, T.vel_out.p, T.pred.p, T.rho.p,
-                                    s->pos.p, s->vel.p, s->pred.p, s->rho.p, s->key.p, s->owned.p, s->slab_counters.p);
-    }
-    if (ev) { FS_HIP(hipEventRecord(ev[6], st)); s->prof.pending += 1; }
-    FS_HIP(hipGetLastError());
-    s->slab_packed = false;
-    return FS_OK;
-}
-
-}  // namespace
-
-// Edge-first slab step: the edge columns' chain of the last step (exchange stream) has advanced its particles and classified their
-// slots; the simulation's stream only waits for it when something other than the next pack -> exchange -> step cycle needs that
-// state (the cycle itself is ordered by the exchange's event).  Every entry point that reads or replaces the state calls this.
-static fs_status slab_join(fs_sim* s) {
-    if (s && s->slab && s->join_pending) {
-        FS_HIP(hipStreamWaitEvent(s->stream, s->ev_packed, 0));
-        s->join_pending = false;
-    }
-    return FS_OK;
-}
-#define FS_JOIN(s) do { fs_status jr_ = slab_join(s); if (jr_ != FS_OK) return jr_; } while (0)
-
 extern "C" {
 
 int fs_abi_version(void) { return FS_ABI_VERSION; }
@@ -670,11 +400,7 @@ fs_status fs_create_ex(const fs_settings* settings, const fs_options* opts, fs_s
         return fail(FS_ERR_INVALID, "unknown sort_mode");
     if (opts->math_mode != FS_MATH_IEEE && opts->math_mode != FS_MATH_WGSL_ULP && opts->math_mode != FS_MATH_TOLERANCE)
         return fail(FS_ERR_INVALID, "unknown math_mode");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(FS_ERR_DEVICE, "no HIP device: the engine has no CPU fallback");
-    if (opts->device < 0 || opts->device >= ndev) return fail(FS_ERR_INVALID, "device ordinal out of range");
-    FS_HIP(hipSetDevice(opts->device));
+    FS_TRY(use_device(opts->device));
 
     std::unique_ptr<fs_sim> s(new (std::nothrow) fs_sim());     // an error exit frees whatever the handle holds by then
     if (!s) return fail(FS_ERR_OOM, "host allocation failed");
@@ -687,7 +413,7 @@ fs_status fs_create_ex(const fs_settings* settings, const fs_options* opts, fs_s
     grid_dims(*settings, &s->grid_w, &s->grid_h);
     s->ncell = s->grid_w * s->grid_h;
     s->work_cap = s->ncell / 16u + 1024u;
-    { const fs_status r = create_common(s.get()); if (r != FS_OK) return r; }
+    FS_TRY(create_common(s.get()));
     FS_HIP(hipMemsetAsync(s->key.p, 0, s->capacity * sizeof(uint32_t), s->stream));
 
     // initial lattice (simulation.rs:147-163) -> AoS staging -> SoA
@@ -698,7 +424,7 @@ fs_status fs_create_ex(const fs_settings* settings, const fs_options* opts, fs_s
         fsd::launch_import_aos(s->stream, s->n, s->aos.p, s->pos.p, s->pred.p, s->vel.p, s->rho.p, s->key.p);
         FS_HIP(hipStreamSynchronize(s->stream));
     }
-    { const fs_status r = create_finish(s.get()); if (r != FS_OK) return r; }
+    FS_TRY(create_finish(s.get()));
     *out = s.release();
     return FS_OK;
 }
@@ -707,7 +433,7 @@ void fs_destroy(fs_sim* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    if (s->comm) (void)hipStreamSynchronize(s->comm);        // an exchange / edge chain still in flight reads this handle's buffers
+    if (void* comm = fs_slab_comm_stream(s)) (void)hipStreamSynchronize((hipStream_t)comm);   // an exchange / edge chain still in flight reads this handle's buffers
     delete s;
 }
 
@@ -718,20 +444,10 @@ fs_status fs_step(fs_sim* s, const fs_tick_settings* t) {
     return enqueue_step(s, t);
 }
 
-// After a synchronisation of the stream: a barrier time-out of the sort's stand-by kernel makes the state undefined from
-// that step on — whoever is about to receive state (or a "finished" signal) must hear about it.
-static fs_status sort_health(fs_sim* s) {
-    if (s->slab || s->opts.sort_mode != FS_SORT_BITONIC) return FS_OK;
-    FS_HIP(s->sortp.check_timeout(s->sort_dirty.p, s->n));
-    if (s->sortp.dead) return fail(FS_ERR_DEVICE, "sort: the stand-by kernel's grid barrier timed out: the particle order is undefined from that step on; destroy the handle");
-    return FS_OK;
-}
-
 fs_status fs_sync(fs_sim* s) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
     FS_HIP(hipStreamSynchronize(s->stream));
-    // an exchange issued but not yet consumed by fs_slab_step / the edge columns' chain of the last edge-first step
-    if (s->comm && (s->exch_pending || s->join_pending)) { FS_HIP(hipStreamSynchronize(s->comm)); s->join_pending = false; }
+    FS_TRY(slab_sync(s));
     return sort_health(s);
 }
 
@@ -793,8 +509,7 @@ fs_status fs_download_particles(fs_sim* s, fs_particle* dst, size_t n) {
     FS_JOIN(s);
     if (n > s->n) n = s->n;
     const fs_particle* dev = nullptr;
-    fs_status r = fs_particles_device(s, &dev);
-    if (r != FS_OK) return r;
+    FS_TRY(fs_particles_device(s, &dev));
     if (n) FS_HIP(hipMemcpyAsync(dst, dev, n * sizeof(fs_particle), hipMemcpyDeviceToHost, s->stream));
     FS_HIP(hipStreamSynchronize(s->stream));
     return sort_health(s);        // the records are in `dst` either way (diagnosis); FS_ERR_DEVICE says they are not to be trusted
@@ -913,7 +628,7 @@ fs_status fs_render_density(fs_sim* s, const fs_view* view, float* rgba_host) {
     const size_t npix = (size_t)view->width * view->height;
     float4* dimg = nullptr;
     FS_HIP(hipMalloc((void**)&dimg, npix * sizeof(float4)));
-    const fsd::StepParams P = make_params(*s);
+    const fsd::StepParams P = make_params(*s, s->uniform);
     // after a step: `pred` = predicted positions of this step, `vel` = updated velocities (what the
     // reference's fragment shader sees in in_particles at draw time)
     fsd::launch_render_density(s->stream, P, make_float2(view->world_min.x, view->world_min.y),
@@ -1042,11 +757,9 @@ fs_status fs_download_particles_by_id(fs_sim* s, fs_particle* dst, size_t n) {
     std::vector<fs_particle> rec;
     std::vector<uint32_t> ids;
     try { rec.resize(s->n); ids.resize(s->n); } catch (const std::bad_alloc&) { return fail(FS_ERR_OOM, "host staging"); }
-    fs_status r = fs_download_particles(s, rec.data(), rec.size());
-    if (r != FS_OK) return r;
+    FS_TRY(fs_download_particles(s, rec.data(), rec.size()));
     if (s->n) {
-        r = fs_track_download_ids(s, ids.data(), ids.size());
-        if (r != FS_OK) return r;
+        FS_TRY(fs_track_download_ids(s, ids.data(), ids.size()));
     }
     for (size_t i = 0; i < ids.size(); ++i)
         if (ids[i] < n) dst[ids[i]] = rec[i];
@@ -1091,7 +804,7 @@ fs_status sample_enqueue(fs_sim* s, const fs_vec2* points_dev, const fs_view* vi
         S.channels = s->trk_channels;
         S.attr = s->trk_attr[s->trk_cur].p; S.attr_stride = s->capacity;
     }
-    fsd::launch_sample(s->stream, make_params(*s), Q, S);
+    fsd::launch_sample(s->stream, make_params(*s, s->uniform), Q, S);
     FS_HIP(hipGetLastError());
     return FS_OK;
 }
@@ -1173,8 +886,7 @@ fs_status fs_timed_steps(fs_sim* s, const fs_tick_settings* t, uint32_t steps, d
     FS_HIP(hipSetDevice(s->device));
     FS_HIP(hipEventRecord(s->t0, s->stream));
     for (uint32_t k = 0; k < steps; ++k) {
-        fs_status r = enqueue_step(s, t);
-        if (r != FS_OK) return r;
+        FS_TRY(enqueue_step(s, t));
     }
     FS_HIP(hipEventRecord(s->t1, s->stream));
     FS_HIP(hipEventSynchronize(s->t1));
@@ -1288,8 +1000,7 @@ fs_status fs_export_handle(fs_sim* s, int which, fs_mem_handle* out) {
             s->aos_tick = 0xFFFFFFFFu;
         }
         const fs_particle* dev = nullptr;          // make the view current for the state as it is now
-        fs_status r = fs_particles_device(s, &dev);
-        if (r != FS_OK) return r;
+        FS_TRY(fs_particles_device(s, &dev));
         base = s->aos.p;
         out->bytes = (uint64_t)s->n * sizeof(fs_particle);
     } else {
@@ -1334,436 +1045,6 @@ fs_status fs_import_read(const void* dev_ptr, size_t offset, void* dst, size_t b
 fs_status fs_import_close(void* ptr) {
     if (!ptr) return FS_OK;
     FS_HIP(hipIpcCloseMemHandle(ptr));
-    return FS_OK;
-}
-
-/* ------------------------------------------------------------ slab mode */
-fs_status fs_slab_create(const fs_settings* settings, int device, const fs_slab_config* cfg, fs_sim** out) {
-    if (!settings || !cfg || !out) return fail(FS_ERR_INVALID, "null argument");
-    *out = nullptr;
-    std::string why;
-    if (!settings_valid(*settings, &why)) return fail(FS_ERR_INVALID, why);
-    uint32_t gw, gh;
-    grid_dims(*settings, &gw, &gh);
-    if (cfg->own_lo >= cfg->own_hi || cfg->own_hi > gw) return fail(FS_ERR_INVALID, "bad owned window");
-    if (cfg->own_hi - cfg->own_lo < 4) return fail(FS_ERR_INVALID, "slab narrower than 4 columns");
-    if (cfg->max_cols < cfg->own_hi - cfg->own_lo) return fail(FS_ERR_INVALID, "max_cols < window");
-    if (cfg->capacity <= 2 * cfg->recv_capacity || cfg->recv_capacity == 0)
-        return fail(FS_ERR_INVALID, "capacity must exceed 2*recv_capacity");
-    if (cfg->capacity > (1u << 28)) return fail(FS_ERR_INVALID, "capacity > 2^28");
-    if (cfg->recv_capacity >= (1u << 20) - 2u) return fail(FS_ERR_INVALID, "recv_capacity >= 2^20 - 2 (message counters are 20-bit fields)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(FS_ERR_DEVICE, "no HIP device: the engine has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(FS_ERR_INVALID, "device ordinal out of range");
-    FS_HIP(hipSetDevice(device));
-
-    std::unique_ptr<fs_sim> s(new (std::nothrow) fs_sim());     // an error exit frees whatever the handle holds by then
-    if (!s) return fail(FS_ERR_OOM, "host allocation failed");
-    s->settings = *settings;
-    fs_options_default(&s->opts);
-    s->opts.device = device;
-    s->opts.ref_quirks = 0;
-    // per-rank sorts can only be tolerance-parity with a single-domain run, so slabs
-    // default to the O(N) counting sort; cfg->sort_mode = 1 + FS_SORT_BITONIC selects the network
-    s->opts.sort_mode = (cfg->sort_mode & 0xFFu) == 1 + FS_SORT_BITONIC ? FS_SORT_BITONIC : FS_SORT_COUNTING;
-    {   // the overlapped step needs the counting sort (ghosts out of the main array); FS_SLAB_SERIAL / FS_SLAB_OVERLAP=0: the serial step
-        // FS_SLAB_MODE=serial|edge|strips overrides the configuration (A/B runs)
-        const char* e = getenv("FS_SLAB_MODE");
-        uint32_t m = (cfg->sort_mode & FS_SLAB_SERIAL) ? 0u : (cfg->sort_mode & FS_SLAB_STRIPS) ? 2u : 1u;
-        if (e) m = !strcmp(e, "serial") ? 0u : !strcmp(e, "strips") ? 2u : !strcmp(e, "edge") ? 1u : m;
-        if (s->opts.sort_mode != FS_SORT_COUNTING) m = 0u;     // the network's slab mode stays the serial step (bit-identity with the plain engine)
-        s->overlap = m == 2u;
-        s->edge_first = m == 1u;
-        // column-major cell ids wherever a slab edge has a neighbour (the edge columns are then whole blocks at the two ends of the
-        // sorted array); a slab without neighbours keeps the reference layout and stays bit-identical to the plain engine in
-        // FS_SORT_COUNTING mode.  FS_SLAB_TRANSPOSE=0/1 overrides (A/B runs); the strip step's gather is written for rows.
-        const char* te = getenv("FS_SLAB_TRANSPOSE");
-        s->transposed = s->opts.sort_mode == FS_SORT_COUNTING && !s->overlap && (cfg->has_left || cfg->has_right) && !(cfg->sort_mode & FS_SLAB_ROWMAJOR);
-        if (te && s->opts.sort_mode == FS_SORT_COUNTING && !s->overlap) s->transposed = atoi(te) != 0;
-    }
-    s->device = device;
-    s->slab = true;
-    s->slab_cfg = *cfg;
-    s->capacity = cfg->capacity;
-    s->n = 0;
-    s->slab_main = cfg->capacity - 2 * cfg->recv_capacity;
-    s->grid_w = gw; s->grid_h = gh;
-    const uint32_t wmax = cfg->max_cols + 6u;
-    s->ncell = wmax * gh;                       // allocation size of the local grid
-    s->work_cap = s->ncell / 16u + 1024u;
-    { const fs_status r = create_common(s.get()); if (r != FS_OK) return r; }
-    const size_t cap = s->capacity;
-    FS_HIP(s->owned.alloc(cap));
-    const size_t nblocks = (cap + 255) / 256;
-    FS_HIP(s->blockcnt.alloc(2 * (nblocks + 1)));      // per 256-slot block: message counts, then message offsets (k_slab_msg)
-    FS_HIP(s->stage.alloc(fsd::slab_stage_words((uint32_t)cap)));
-    FS_HIP(s->msg_state.alloc(fsd::slab_msg_groups((uint32_t)cap) + 1));
-    FS_HIP(hipMemsetAsync(s->msg_state.p, 0, s->msg_state.n * sizeof(fsd::u64), s->stream));
-    FS_HIP(s->slab_counters.alloc(16));
-    FS_HIP(s->hist.alloc(gw));
-    if (s->overlap || s->edge_first) {
-        int lo_prio = 0, hi_prio = 0;          // the exchange's kernel should not queue behind the interior columns' workgroups
-        (void)hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio);
-        FS_HIP(hipStreamCreateWithPriority(&s->comm.h, hipStreamNonBlocking, hi_prio));
-        FS_HIP(hipEventCreateWithFlags(&s->ev_packed.h, hipEventDisableTiming));
-        FS_HIP(hipEventCreateWithFlags(&s->ev_exch.h, hipEventDisableTiming));
-        // waited for by the exchange stream of this same device only: no system-scope fence (a write-back of every L2 behind the
-        // reorder kernel, which the simulation's own stream would sit out)
-        FS_HIP(hipEventCreateWithFlags(&s->ev_fork2.h, hipEventDisableTiming | hipEventDisableSystemFence));
-        if (const char* e = getenv("FS_SLAB_BOUNDARY_COLS")) s->boundary_cols = (uint32_t)atoi(e) < 3u ? 3u : (uint32_t)atoi(e);
-    }
-    if (s->overlap) {
-        // The strip could hold every particle of a narrow slab (all columns within the boundary zone) plus both messages:
-        // same capacity as the main array (memory is not the constraint: ~100 B per slot); its kernels cover the slots in use only.
-        fs_sim::Strip& T = s->strip;
-        T.cap = (uint32_t)cap;
-        FS_HIP(T.alloc_common(cap)); FS_HIP(T.pos_out.alloc(cap)); FS_HIP(T.vel_out.alloc(cap)); FS_HIP(T.owned.alloc(cap));
-        FS_HIP(T.csort.alloc(fsd::counting_sort_scratch_words((uint32_t)cap, s->ncell)));
-        FS_HIP(hipMemsetAsync(T.csort.p, 0, T.csort.n * sizeof(uint32_t), s->stream));
-        FS_HIP(T.cs.alloc((size_t)s->ncell + 1)); FS_HIP(T.start_ref.alloc(s->ncell));
-        FS_HIP(T.counters.alloc(8)); FS_HIP(T.back.alloc(cap)); FS_HIP(T.rowbase.alloc(2 * (size_t)gh + 2));
-        FS_HIP(hipMemsetAsync(T.cs.p, 0, T.cs.n * sizeof(uint32_t), s->stream));
-        FS_HIP(hipMemsetAsync(T.counter.p, 0, 8 * sizeof(uint32_t), s->stream));
-        FS_HIP(hipMemsetAsync(T.counters.p, 0, 8 * sizeof(uint32_t), s->stream));
-        FS_HIP(hipMemsetAsync(T.pred.p, 0, (cap + FS_PRED_SLACK) * sizeof(float2), s->stream));
-        FS_HIP(hipMemsetAsync(T.pairs.p, 0xFF, cap * sizeof(fsd::u64), s->stream));
-    }
-    FS_HIP(hipMemsetAsync(s->slab_counters.p, 0, 16 * sizeof(uint32_t), s->stream));
-    FS_HIP(hipMemsetAsync(s->owned.p, 0, cap, s->stream));
-    FS_HIP(hipMemsetAsync(s->pos.p, 0, cap * sizeof(float2), s->stream));
-    FS_HIP(hipMemsetAsync(s->vel.p, 0, cap * sizeof(float2), s->stream));
-    FS_HIP(hipMemsetAsync(s->pred.p, 0, cap * sizeof(float2), s->stream));
-    FS_HIP(hipMemsetAsync(s->key.p, 0xFF, cap * sizeof(uint32_t), s->stream));
-    FS_HIP(hipStreamSynchronize(s->stream));
-    { const fs_status r = create_finish(s.get()); if (r != FS_OK) return r; }
-    *out = s.release();
-    return FS_OK;
-}
-
-fs_status fs_slab_upload_owned(fs_sim* s, const fs_particle* src, size_t n) {
-    if (!s || !s->slab || (!src && n)) return fail(FS_ERR_INVALID, "bad argument");
-    if (n > s->slab_main) return fail(FS_ERR_INVALID, "more owned particles than main slots");
-    FS_JOIN(s);
-    s->prepacked = false;                  // the state is replaced: messages built from the old one are void
-    FS_HIP(hipSetDevice(s->device));
-    if (n) FS_HIP(hipMemcpyAsync(s->aos.p, src, n * sizeof(fs_particle), hipMemcpyHostToDevice, s->stream));
-    const fsd::StepParams P = make_params(*s);
-    fsd::launch_slab_import(s->stream, P, (uint32_t)n, s->capacity, s->aos.p, s->pos.p, s->pred.p, s->vel.p, s->rho.p,
-                            s->key.p, s->owned.p);
-    const uint32_t nl = (uint32_t)n;
-    FS_HIP(hipMemcpyAsync(s->slab_counters.p, &nl, sizeof nl, hipMemcpyHostToDevice, s->stream));
-    FS_HIP(hipStreamSynchronize(s->stream));
-    s->state_lo = s->slab_cfg.own_lo; s->state_hi = s->slab_cfg.own_hi;
-    return FS_OK;
-}
-
-fs_status fs_slab_set_window(fs_sim* s, uint32_t own_lo, uint32_t own_hi) {
-    if (!s || !s->slab) return fail(FS_ERR_INVALID, "not a slab handle");
-    FS_JOIN(s);
-    if (own_lo >= own_hi || own_hi > s->grid_w || own_hi - own_lo < 4 || own_hi - own_lo > s->slab_cfg.max_cols)
-        return fail(FS_ERR_INVALID, "bad owned window");
-    if (s->slab_packed) return fail(FS_ERR_INVALID, "window change between pack and step");
-    {   // the particles of a column that changes hands arrive at the new owner as migrants, that many columns deeper than usual:
-        // the next (overlapped) step widens its boundary zone by the shift
-        const uint32_t dl = s->slab_cfg.has_left ? (own_lo > s->slab_cfg.own_lo ? own_lo - s->slab_cfg.own_lo : s->slab_cfg.own_lo - own_lo) : 0u;
-        const uint32_t dr = s->slab_cfg.has_right ? (own_hi > s->slab_cfg.own_hi ? own_hi - s->slab_cfg.own_hi : s->slab_cfg.own_hi - own_hi) : 0u;
-        const uint32_t d = dl > dr ? dl : dr;
-        if (d > s->pending_shift) s->pending_shift = d;
-    }
-    s->slab_cfg.own_lo = own_lo;
-    s->slab_cfg.own_hi = own_hi;
-    return FS_OK;
-}
-
-/* Overlapped step: owned columns per neighboured slab edge that are left to the boundary strips (computed AFTER the halo
- * exchange; everything farther inside runs while the messages are in flight).  A migrant must land at least 3 columns short of
- * the interior — cols >= 3 + the columns the fastest particle crosses in one step; violations are counted in far_halo. */
-fs_status fs_slab_set_boundary_cols(fs_sim* s, uint32_t cols) {
-    if (!s || !s->slab) return fail(FS_ERR_INVALID, "not a slab handle");
-    if (s->slab_packed) return fail(FS_ERR_INVALID, "boundary change between pack and step");
-    s->boundary_cols = cols < 3u ? 3u : cols;
-    return FS_OK;
-}
-uint32_t fs_slab_boundary_cols(const fs_sim* s) { return (s && s->slab && (s->overlap || s->edge_first)) ? s->boundary_cols : 0u; }
-int fs_slab_overlapped(const fs_sim* s) { return (s && s->slab) ? (s->edge_first ? 1 : s->overlap ? 2 : 0) : 0; }
-void* fs_slab_comm_stream(const fs_sim* s) { return (s && s->slab) ? (void*)s->comm : nullptr; }
-
-/* Transport hooks of the overlapped step (a no-op on a serial handle, whose exchange is ordered by the simulation's stream):
- * fs_slab_comm_begin makes the exchange stream wait for the packed messages, the caller then issues its send/recv ON
- * fs_slab_comm_stream(), fs_slab_comm_end records their completion for fs_slab_step to wait on.  fs_slab_exchange does all
- * three itself.  fs_slab_wait_packed blocks the HOST until the outgoing messages are complete (host-staged transports). */
-fs_status fs_slab_comm_begin(fs_sim* s) {
-    if (!s || !s->slab) return fail(FS_ERR_INVALID, "not a slab handle");
-    if (!s->comm) return FS_OK;
-    FS_HIP(hipSetDevice(s->device));
-    if (!s->slab_packed) FS_HIP(hipEventRecord(s->ev_packed, s->stream));   // outside a step: behind whatever the simulation's stream holds
-    FS_HIP(hipStreamWaitEvent(s->comm, s->ev_packed, 0));
-    return FS_OK;
-}
-fs_status fs_slab_comm_end(fs_sim* s) {
-    if (!s || !s->slab) return fail(FS_ERR_INVALID, "not a slab handle");
-    if (!s->comm) return FS_OK;
-    FS_HIP(hipSetDevice(s->device));
-    FS_HIP(hipEventRecord(s->ev_exch, s->comm));
-    s->exch_pending = true;
-    return FS_OK;
-}
-fs_status fs_slab_wait_packed(fs_sim* s) {
-    if (!s || !s->slab) return fail(FS_ERR_INVALID, "not a slab handle");
-    FS_HIP(hipSetDevice(s->device));
-    if (s->comm && s->slab_packed) FS_HIP(hipEventSynchronize(s->ev_packed));
-    else FS_HIP(hipStreamSynchronize(s->stream));
-    return FS_OK;
-}
-
-size_t fs_slab_message_bytes(const fs_sim* s) {
-    return (s && s->slab) ? fsd::slab_message_bytes(s->slab_cfg.recv_capacity) : 0;
-}
-
-fs_status fs_slab_pack(fs_sim* s, const fs_tick_settings* t, void* send_left, void* send_right) {
-    if (!s || !s->slab || !t) return fail(FS_ERR_INVALID, "bad argument");
-    if (s->slab_packed) return fail(FS_ERR_INVALID, "fs_slab_pack called twice without fs_slab_step");
-    if ((s->slab_cfg.has_left && !send_left) || (s->slab_cfg.has_right && !send_right))
-        return fail(FS_ERR_INVALID, "missing outgoing message buffer");
-    FS_HIP(hipSetDevice(s->device));
-    s->tick += 1;
-    host_uniform(s->settings, *t, s->tick, &s->uniform);
-    const fsd::StepParams P = make_params(*s);
-    s->slab_prof = s->prof.on;             // a toggle between pack and step must not leave ev[0] unrecorded
-    if (s->slab_prof) {
-        const fs_status r = s->prof.begin();
-        if (r != FS_OK) return r;
-        FS_HIP(hipEventRecord(s->prof.current()[0], s->stream));
-    }
-    const bool counting = s->opts.sort_mode == FS_SORT_COUNTING;
-    // edge-first step: are the messages of this tick already in the send buffers (built by the last fs_slab_step)?  Only if
-    // nothing they depend on has changed since: buffers, owned window, delta.
-    const bool pre = s->edge_first && s->prepacked && s->pp_left == (s->slab_cfg.has_left ? send_left : nullptr) &&
-                     s->pp_right == (s->slab_cfg.has_right ? send_right : nullptr) && s->pp_delta == t->delta &&
-                     s->pp_lo == s->slab_cfg.own_lo && s->pp_hi == s->slab_cfg.own_hi;
-    s->prepacked = false;
-    // pre: this launch needs nothing of the edge columns' chain (their slots are classified already: skip_edge) — no join; the
-    // chain is waited for through the exchange's event in fs_slab_step.  Otherwise: join, and take back the histogram counts
-    // that chain added with the parameters it expected (the scan has left the table zero everywhere else)
-    const bool skip_edge = pre && s->edge_classified;
-    if (!pre) {
-        FS_JOIN(s);
-        if (s->edge_classified && counting) FS_HIP(hipMemsetAsync(fsd::counting_sort_hist(s->csort.p), 0, (size_t)s->ncell * sizeof(uint32_t), s->stream));
-    }
-    s->edge_classified = false;
-    s->pp_left = s->slab_cfg.has_left ? send_left : nullptr;
-    s->pp_right = s->slab_cfg.has_right ? send_right : nullptr;
-    s->last_tick = *t;
-    fsd::launch_slab_pack(s->stream, P, s->slab_main, s->slab_cfg.recv_capacity, (int)s->slab_cfg.has_left,
-                          (int)s->slab_cfg.has_right, s->pos.p, s->vel.p, s->owned.p,
-                          counting ? fsd::counting_sort_kt(s->csort.p, s->capacity, s->ncell) : s->pairs.p,
-                          fsd::counting_sort_hist(s->csort.p), s->blockcnt.p, s->stage.p, s->msg_state.p, ++s->msg_epoch,
-                          s->pp_left, s->pp_right, s->slab_counters.p, s->counter.p, s->safe.p, counting,
-                          s->overlap, !pre, s->key.p, s->adv_lo, s->adv_hi, skip_edge);
-    FS_HIP(hipGetLastError());
-    s->slab_packed = true;
-    s->state_lo = s->slab_cfg.own_lo; s->state_hi = s->slab_cfg.own_hi;
-    if (s->overlap) return slab_interior(s);
-    // edge-first: a pre-built message set was recorded complete (ev_packed) when it was built; a fresh one is complete now
-    if (s->edge_first && !pre) FS_HIP(hipEventRecord(s->ev_packed, s->stream));
-    return FS_OK;
-}
-
-fs_status fs_slab_step(fs_sim* s, const void* recv_left, const void* recv_right) {
-    if (!s || !s->slab) return fail(FS_ERR_INVALID, "not a slab handle");
-    if (!s->slab_packed) return fail(FS_ERR_INVALID, "fs_slab_step without fs_slab_pack");
-    if ((s->slab_cfg.has_left && !recv_left) || (s->slab_cfg.has_right && !recv_right))
-        return fail(FS_ERR_INVALID, "missing incoming message buffer");
-    FS_HIP(hipSetDevice(s->device));
-    if (s->overlap) return slab_boundary(s, recv_left, recv_right);
-    const fsd::StepParams P = make_params(*s);
-    hipStream_t st = s->stream;
-    hipEvent_t* ev = s->slab_prof ? s->prof.current() : nullptr;
-    const bool counting = s->opts.sort_mode == FS_SORT_COUNTING;
-    // the exchange was enqueued on the exchange stream behind the edge columns' chain: its event stands for the join as well
-    if (s->exch_pending) { FS_HIP(hipStreamWaitEvent(st, s->ev_exch, 0)); s->exch_pending = false; s->join_pending = false; }
-    else FS_JOIN(s);
-    fsd::launch_slab_unpack(st, P, s->slab_main, s->slab_cfg.recv_capacity, s->slab_cfg.has_left ? recv_left : nullptr,
-                            s->slab_cfg.has_right ? recv_right : nullptr, s->pos.p, s->vel.p,
-                            counting ? fsd::counting_sort_kt(s->csort.p, s->capacity, s->ncell) : s->pairs.p,
-                            fsd::counting_sort_hist(s->csort.p), s->slab_counters.p, counting);
-    if (ev) FS_HIP(hipEventRecord(ev[1], st));
-    if (counting) {
-        fsd::launch_counting_sort_pairs(st, s->capacity, P.ncell, s->ncell, s->cs.p, s->csort.p, s->slab_counters.p, s->tick, nullptr, s->safe.p);
-    } else {
-        fsd::SortPlan per_stage;               // ghosts arrive at the end of the array every step: they travel far, no shifted merge
-        per_stage.fuse_stage = 0;
-        fsd::launch_bitonic_sort(st, s->pairs.p, s->capacity, s->sort_dirty.p, nullptr, nullptr, nullptr, nullptr, &per_stage);
-    }
-    if (ev) FS_HIP(hipEventRecord(ev[2], st));
-    const bool edge_step = s->edge_first && (s->slab_cfg.has_left || s->slab_cfg.has_right);
-    bool forked = false;
-    if (edge_step) {
-        plan_overlap(s);
-        forked = s->transposed && s->adv_lo < s->adv_hi;      // the edge columns' chain forks off behind the reorder pass (below)
-    }
-    const fsd::StepArrays A = s->step_arrays();
-    if (counting)
-        fsd::launch_counting_reorder_slab(st, P, A, s->capacity, s->ncell, forked ? s->ev_fork2.h : nullptr);
-    else
-        fsd::launch_slab_reorder(st, P, A, s->capacity, s->work_cap, s->slab_counters.p);
-    if (ev) FS_HIP(hipEventRecord(ev[3], st));
-    if (edge_step) {
-        if (forked) {
-            // column-major ids: the edge columns' chain forks off BEFORE the density pass — their own density launch (the few
-            // hundred blocks that hold the edge columns and one column more on either side; the full launch below computes the
-            // same values again) runs on the exchange stream, so the chain is done, and the exchange under way, early in the
-            // interior columns' force pass
-            fsd::StepParams PD = P;
-            PD.adv_lo = s->adv_lo; PD.adv_hi = s->adv_hi;
-            FS_HIP(hipStreamWaitEvent(s->comm, s->ev_fork2, 0));     // signalled by the reorder kernel itself
-            fsd::launch_density(s->comm, PD, A, FS_EDGE_GRID);
-        }
-    }
-    fsd::launch_density(st, P, A);
-    if (ev) FS_HIP(hipEventRecord(ev[4], st));
-    fsd::ForceLaunch LI = s->force_launch();     // the launch on the simulation's stream: every owned column, or the interior ones
-    LI.quad_entries = s->sortp.quad_entries();
-    if (edge_step) {
-        // Edge-first step.  Behind the density pass the stream forks: the handle's exchange stream (high priority) advances
-        // the owned columns within boundary_cols of a neighboured edge — a few hundred blocks, latency-bound — then builds the
-        // NEXT step's messages from their new state (k_slab_prepack .. k_slab_gather) and carries the exchange of those
-        // messages (fs_slab_exchange / the caller's transport between fs_slab_comm_begin / _end); the simulation's stream
-        // runs the force pass of the interior columns beside all that, and joins before anything reads the new state.
-        fsd::StepParams PE = P, PI = P;
-        PE.adv_lo = PI.adv_lo = s->adv_lo; PE.adv_hi = PI.adv_hi = s->adv_hi;
-        PE.adv_outside = 1; PI.adv_outside = 0;
-        // column-major ids: the edge columns are a few hundred consecutive blocks at the two ends of the sorted array, walked by
-        // small fixed grids (fs_device.h EdgeBlocks)
-        const uint32_t eg = s->transposed ? FS_EDGE_GRID : 0u;
-        hipStream_t es = s->comm;
-        if (!forked) FS_HIP(hipEventRecord(s->ev_fork2, st));
-        // the simulation's stream first (its force launch is the long one: the host must not leave that stream empty while it
-        // enqueues the six launches of the edge chain — seen under the profiler, where a launch costs 10 us), then the chain
-        if (s->adv_lo < s->adv_hi) fsd::launch_force(st, PI, A, LI);
-        if (ev) FS_HIP(hipEventRecord(ev[5], st));      // FS_PASS_FORCE: the interior launch
-        if (!forked) FS_HIP(hipStreamWaitEvent(es, s->ev_fork2, 0));
-        fsd::ForceLaunch LE;                 // the chain's own launches: one stream, a small general grid
-        LE.general_grid = 256u; LE.edge_grid = eg;
-        fsd::launch_force(es, PE, A, LE);
-        {   // what fs_slab_pack will see at tick + 1, if nothing changes in between (it checks)
-            fs_uniform un;
-            host_uniform(s->settings, s->last_tick, s->tick + 1, &un);
-            const fs_uniform keep = s->uniform;
-            s->uniform = un;
-            fsd::StepParams PN = make_params(*s);
-            s->uniform = keep;
-            PN.adv_lo = s->adv_lo; PN.adv_hi = s->adv_hi; PN.adv_outside = 1;
-            fsd::launch_slab_prepack(es, PN, s->capacity, s->slab_cfg.recv_capacity, (int)s->slab_cfg.has_left, (int)s->slab_cfg.has_right,
-                                     s->pos.p, s->vel.p, s->owned.p, s->key.p, s->blockcnt.p, s->stage.p, s->msg_state.p, ++s->msg_epoch,
-                                     s->pp_left, s->pp_right, s->slab_counters.p, s->cs.p, eg, true, counting, s->slab_main,
-                                     counting ? fsd::counting_sort_kt(s->csort.p, s->capacity, s->ncell) : s->pairs.p,
-                                     fsd::counting_sort_hist(s->csort.p));
-            s->edge_classified = true;
-            FS_HIP(hipEventRecord(s->ev_packed, es));       // the next step's messages are complete (and the edge columns advanced)
-            s->prepacked = true;
-            s->pp_delta = s->last_tick.delta; s->pp_lo = s->slab_cfg.own_lo; s->pp_hi = s->slab_cfg.own_hi;
-        }
-        // no join here: the next fs_slab_pack leaves the edge columns' slots alone, and fs_slab_step waits for the exchange that
-        // follows their chain on the exchange stream; anything else that touches the state joins first (slab_join)
-        s->join_pending = true;
-        if (ev) { FS_HIP(hipEventRecord(ev[6], st)); s->prof.pending += 1; }     // FS_PASS_BOUNDARY: nothing left on this stream
-    } else {
-        fsd::launch_force(st, P, A, LI);
-        if (ev) { FS_HIP(hipEventRecord(ev[5], st)); FS_HIP(hipEventRecord(ev[6], st)); s->prof.pending += 1; }
-    }
-    FS_HIP(hipGetLastError());
-    s->slab_packed = false;
-    return FS_OK;
-}
-
-fs_status fs_slab_counters_read(fs_sim* s, fs_slab_counters* out) {
-    if (!s || !s->slab || !out) return fail(FS_ERR_INVALID, "bad argument");
-    FS_JOIN(s);
-    FS_HIP(hipSetDevice(s->device));
-    uint32_t c[8];
-    FS_HIP(hipMemcpyAsync(c, s->slab_counters.p, sizeof c, hipMemcpyDeviceToHost, s->stream));
-    FS_HIP(hipStreamSynchronize(s->stream));
-    out->n_live = c[0]; out->lost = c[2]; out->overflow = c[3]; out->far_halo = c[4];
-    return FS_OK;
-}
-
-fs_status fs_slab_max_speed(fs_sim* s, float* out) {
-    if (!s || !s->slab || !out) return fail(FS_ERR_INVALID, "bad argument");
-    if (s->slab_packed) return fail(FS_ERR_INVALID, "fs_slab_max_speed between pack and step");
-    FS_JOIN(s);
-    FS_HIP(hipSetDevice(s->device));
-    uint32_t bits = 0;
-    FS_HIP(hipMemsetAsync(s->slab_counters.p + 5, 0, sizeof(uint32_t), s->stream));
-    fsd::launch_slab_maxspeed(s->stream, s->slab_counters.p, s->vel.p, s->owned.p, s->slab_counters.p + 5,
-                              s->slab_main, s->overlap ? 2u * s->slab_cfg.recv_capacity : 0u);
-    FS_HIP(hipMemcpyAsync(&bits, s->slab_counters.p + 5, sizeof bits, hipMemcpyDeviceToHost, s->stream));
-    FS_HIP(hipStreamSynchronize(s->stream));
-    std::memcpy(out, &bits, sizeof bits);
-    return FS_OK;
-}
-
-/* Re-balancing inputs left ON THE DEVICE, on the simulation's stream, nothing read back: `hist_dev[grid_w_global]` =
- * particles per global column (zero outside the owned window), `stats_dev[4]` = {lost, overflow, far_halo, bits of the
- * largest owned |velocity|} — all four reduce with MAX as u32 (non-negative floats order like their bits).  The caller
- * all-reduces both buffers (fs_comm_allreduce, or any collective ordered after this stream) and reads them once. */
-fs_status fs_slab_rebalance_stats(fs_sim* s, uint32_t* stats_dev, uint32_t* hist_dev, size_t grid_w_global) {
-    if (!s || !s->slab || !stats_dev || !hist_dev || grid_w_global < s->grid_w) return fail(FS_ERR_INVALID, "bad argument");
-    if (s->slab_packed) return fail(FS_ERR_INVALID, "fs_slab_rebalance_stats between pack and step");
-    FS_JOIN(s);
-    FS_HIP(hipSetDevice(s->device));
-    const fsd::StepParams P = make_params_of_state(*s);
-    FS_HIP(hipMemsetAsync(hist_dev, 0, grid_w_global * sizeof(uint32_t), s->stream));
-    const uint32_t migr = s->overlap ? 2u * s->slab_cfg.recv_capacity : 0u;     // overlapped step: last step's migrants sit past the main slots
-    fsd::launch_slab_colhist(s->stream, P, s->cs.p, hist_dev, s->slab_main, migr, s->owned.p, s->key.p);
-    FS_HIP(hipMemsetAsync(s->slab_counters.p + 5, 0, sizeof(uint32_t), s->stream));
-    fsd::launch_slab_maxspeed(s->stream, s->slab_counters.p, s->vel.p, s->owned.p, s->slab_counters.p + 5, s->slab_main, migr);
-    // counters [2] lost, [3] overflow, [4] far_halo, [5] max-speed bits are adjacent
-    FS_HIP(hipMemcpyAsync(stats_dev, s->slab_counters.p + 2, 4 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
-    FS_HIP(hipGetLastError());
-    return FS_OK;
-}
-
-fs_status fs_slab_download(fs_sim* s, fs_particle* dst, uint8_t* owned, size_t cap, uint32_t* n_live) {
-    if (!s || !s->slab || !dst || !owned || !n_live) return fail(FS_ERR_INVALID, "bad argument");
-    FS_JOIN(s);
-    FS_HIP(hipSetDevice(s->device));
-    const fsd::StepParams P = make_params_of_state(*s);
-    uint32_t nl = 0;
-    FS_HIP(hipMemcpyAsync(&nl, s->slab_counters.p, sizeof nl, hipMemcpyDeviceToHost, s->stream));
-    FS_HIP(hipStreamSynchronize(s->stream));
-    if (nl > s->capacity) nl = s->capacity;
-    // overlapped step: the sorted prefix [0, nl) (owned + this rank's near-leavers) and, past the main slots, the 2R slots
-    // that mirror the incoming messages — the migrants among them carry the owned flag; returned back to back
-    const size_t migr = s->overlap ? 2u * (size_t)s->slab_cfg.recv_capacity : 0u;
-    if (s->overlap && nl > s->slab_main) nl = s->slab_main;
-    const size_t n = nl < cap ? nl : cap;
-    const size_t m = cap - n < migr ? cap - n : migr;
-    *n_live = (uint32_t)(n + m);
-    if (n + m == 0) return FS_OK;
-    // before the first step the state lives in pos/vel (import); afterwards pos/vel hold the advanced state
-    fsd::launch_slab_export(s->stream, P, s->capacity, s->pos.p, s->pred.p, s->vel.p, s->rho.p, s->key.p, s->aos.p);
-    if (n) FS_HIP(hipMemcpyAsync(dst, s->aos.p, n * sizeof(fs_particle), hipMemcpyDeviceToHost, s->stream));
-    if (n) FS_HIP(hipMemcpyAsync(owned, s->owned.p, n, hipMemcpyDeviceToHost, s->stream));
-    if (m) FS_HIP(hipMemcpyAsync(dst + n, s->aos.p + s->slab_main, m * sizeof(fs_particle), hipMemcpyDeviceToHost, s->stream));
-    if (m) FS_HIP(hipMemcpyAsync(owned + n, s->owned.p + s->slab_main, m, hipMemcpyDeviceToHost, s->stream));
-    FS_HIP(hipStreamSynchronize(s->stream));
-    return FS_OK;
-}
-
-fs_status fs_slab_column_histogram(fs_sim* s, uint32_t* hist, size_t grid_w_global) {
-    if (!s || !s->slab || !hist || grid_w_global < s->grid_w) return fail(FS_ERR_INVALID, "bad argument");
-    FS_JOIN(s);
-    FS_HIP(hipSetDevice(s->device));
-    const fsd::StepParams P = make_params_of_state(*s);
-    FS_HIP(hipMemsetAsync(s->hist.p, 0, s->hist.n * sizeof(uint32_t), s->stream));
-    fsd::launch_slab_colhist(s->stream, P, s->cs.p, s->hist.p, s->slab_main, s->overlap ? 2u * s->slab_cfg.recv_capacity : 0u,
-                             s->owned.p, s->key.p);
-    std::vector<uint32_t> tmp(s->grid_w);
-    FS_HIP(hipMemcpyAsync(tmp.data(), s->hist.p, tmp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-    FS_HIP(hipStreamSynchronize(s->stream));
-    for (uint32_t c = P.own_lo; c < P.own_hi; ++c) hist[c] = tmp[c];
     return FS_OK;
 }
 

@@ -32,6 +32,9 @@ inline fs_status fail(fs_status st, const std::string& msg) {
         }                                                                                                \
     } while (0)
 
+// ... and when a call that returns a status does not return FS_OK.
+#define FS_TRY(expr) do { const fs_status r__ = (expr); if (r__ != FS_OK) return r__; } while (0)
+
 // A device array: move-only, freed by the destructor (or at once by release()).
 template <class T>
 struct DevArray {
@@ -110,8 +113,7 @@ struct PassRing {
     }
     // fs_profile_read / fs3_profile_read
     fs_status read(double out_ms[FS_PASS_COUNT], uint64_t* out_steps, int reset) {
-        const fs_status r = drain();
-        if (r != FS_OK) return r;
+        FS_TRY(drain());
         for (int k = 0; k < FS_PASS_COUNT; ++k) out_ms[k] = ms[k];
         if (out_steps) *out_steps = steps;
         if (reset) { for (auto& m : ms) m = 0.0; steps = 0; }

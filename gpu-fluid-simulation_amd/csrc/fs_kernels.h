@@ -115,58 +115,79 @@ size_t gap_entry_size();
 void launch_fill_gaps(hipStream_t st, uint32_t* cs, const void* work, const uint32_t* counter, uint32_t work_cap);
 
 // ---- slab (multi-GPU) mode, kernels_slab.hip -------------------------------------------------
-// `out`: the counting sort's (key, ticket) words (counting_sort_kt) or, in bitonic mode, the pairs; `blockcnt`: one uint2 per
-// 256-slot block; `stage`: slab_stage_words(capacity) words; `state`: one u64 per slab_msg_groups(capacity) (look-back);
-// `epoch`: a number unique to this launch among the handle's launches (the tick).  counters[6] is the look-back's ticket.
-void launch_slab_pack(hipStream_t st, const StepParams& P, uint32_t main_slots, uint32_t R, int has_left,
-                      int has_right, const float2* pos, const float2* vel, const unsigned char* owned, u64* out,
-                      uint32_t* hist, void* blockcnt, uint32_t* stage, void* state, uint32_t epoch,
-                      void* msg_left, void* msg_right, uint32_t* counters, uint32_t* gap_counter, unsigned long long* safe,
-                      bool counting, bool overlap = false /* the slots past main_slots hold last step's migrants (strip step) */,
-                      bool lists = true /* false: the messages were pre-built (launch_slab_prepack): only check that every particle
-                                           the full classification flags was in the edge zone [own_lo, prev_adv_lo) u [prev_adv_hi, own_hi)
-                                           of the last step (key_prev: its sorted keys) */,
-                      const uint32_t* key_prev = nullptr, uint32_t prev_adv_lo = 0, uint32_t prev_adv_hi = 0,
-                      bool skip_edge = false /* with lists == false: the slots of the last step's edge-zone particles were classified by
-                                                launch_slab_prepack(classify) already — leave them alone */);
+// The arrays of a slab handle its launchers work on: the main array's step arrays (the state is read through pos / vel and
+// written through pos_out / vel_out, the same arrays; key_s: the sorted keys of the last step or import) and the slab's own,
+// filled in one place on the handle (engine.h).  Host side only.
+struct SlabArrays : StepArrays {
+    uint32_t cap = 0, main_slots = 0;  // all slots; those before the 2R slots that mirror the incoming messages
+    bool counting = true, overlap = false;   // the handle's sort: the counting sort, or the network; its step: the strips step (the
+                                             // slots past main_slots hold last step's migrants)
+    void* aos = nullptr;               // 32-B records: import / export staging
+    u64* out = nullptr;                // the counting sort's (key, ticket) words (counting_sort_kt) or, in bitonic mode, the pairs
+    uint32_t* hist = nullptr;          // the counting sort's histogram (counting_sort_hist)
+    void* blockcnt = nullptr;          // one uint2 per 256-slot block, twice: message counts, then message offsets (k_slab_msg)
+    uint32_t* stage = nullptr;         // slab_stage_words(cap) words
+    void* msg_state = nullptr;         // one u64 per slab_msg_groups(cap) (look-back)
+    uint32_t* counters = nullptr;      // [0] n_live, [2] lost, [3] overflow, [4] far_halo, [5] max-speed bits, [6] the look-back's ticket
+};
+// One set of halo messages: the outgoing pair a pack launch fills, or the incoming pair an unpack launch reads.
+struct SlabMessages {
+    uint32_t R = 0;                    // records per message (recv_capacity)
+    int has_left = 0, has_right = 0;
+    void *left = nullptr, *right = nullptr;   // nullptr: no neighbour on that side
+    uint32_t epoch = 0;                // outgoing: a number unique to the launch among the handle's k_slab_msg launches
+};
+// Columns of one overlapped step (engine_slab.hip plan_overlap): [adv_lo, adv_hi) = the interior columns (global), advanced while
+// the messages are in flight; win = the two strip windows as LOCAL column ranges [win[0], win[1]) and [win[2], win[3]).
+struct OverlapPlan {
+    uint32_t adv_lo = 0, adv_hi = 0;
+    uint32_t win[4] = {0, 0, 0, 0};
+    bool strip_active = false;
+};
+// Per-launch choices of launch_slab_pack.
+struct SlabPack {
+    bool lists = true;                 // false: the messages were pre-built (launch_slab_prepack): only check that every particle
+                                       // the full classification flags was in the edge zone [own_lo, prev_adv_lo) u [prev_adv_hi, own_hi)
+                                       // of the last step (key_s: its sorted keys)
+    uint32_t prev_adv_lo = 0, prev_adv_hi = 0;
+    bool skip_edge = false;            // with lists == false: the slots of the last step's edge-zone particles were classified by
+                                       // launch_slab_prepack(classify) already — leave them alone
+};
+void launch_slab_pack(hipStream_t st, const StepParams& P, const SlabArrays& A, const SlabMessages& M, const SlabPack& O);
 // Edge-first step: the NEXT step's messages from the particles the StepParams::adv_outside force launch has just advanced.
-// `P_next`: window + tick constants of the next pack, adv_* as in that force launch; `epoch` unique among the handle's k_slab_msg launches.
-void launch_slab_prepack(hipStream_t st, const StepParams& P_next, uint32_t cap, uint32_t R, int has_left, int has_right,
-                         const float2* pos, const float2* vel, const unsigned char* owned, const uint32_t* key_s, void* blockcnt,
-                         uint32_t* stage, void* state, uint32_t epoch, void* msg_left, void* msg_right, uint32_t* counters,
-                         const uint32_t* cs, uint32_t edge_grid = 0 /* != 0 (column-major ids): walk only the edge columns' blocks */,
+// `P_next`: window + tick constants of the next pack, adv_* as in that force launch.
+void launch_slab_prepack(hipStream_t st, const StepParams& P_next, const SlabArrays& A, const SlabMessages& M,
+                         uint32_t edge_grid = 0 /* != 0 (column-major ids): walk only the edge columns' blocks */,
                          bool classify = false /* also do the next launch_slab_pack's work for the slots of the particles it takes:
-                                                  key, histogram ticket (`counting`) and out[] entry, the lost counter */,
-                         bool counting = false, uint32_t main_slots = 0, u64* out = nullptr, uint32_t* hist = nullptr);
-// Overlapped slab step — the boundary strips (kernels_slab.hip).  `P` = the main array's StepParams; win[4] = the two strip
-// windows as LOCAL column ranges [win[0], win[1]) and [win[2], win[3]); strip_counters: [0] live strip particles (written by the
-// strip's scan), [1] slots filled from the main array, [2] slots in use.
-void launch_strip_gather(hipStream_t st, const StepParams& P, const uint32_t win[4], uint32_t R, uint32_t strip_cap,
-                         const uint32_t* cs, uint32_t* rowbase /* 2 * grid_h */, const u64* pairs, const float2* pos_s,
-                         const float2* vel_s, float2* sp_pos, float2* sp_vel, u64* kt, uint32_t* hist, uint32_t* back,
-                         unsigned long long* safe, uint32_t* strip_counters, uint32_t* counters);
-void launch_strip_unpack(hipStream_t st, const StepParams& P, uint32_t main_slots, uint32_t R, uint32_t strip_cap,
-                         const void* msg_left, const void* msg_right, float2* sp_pos, float2* sp_vel, u64* kt, uint32_t* hist,
-                         uint32_t* back, const uint32_t* strip_counters, uint32_t* counters);
-void launch_strip_writeback(hipStream_t st, const StepParams& P_strip, uint32_t main_slots, uint32_t strip_cap, const u64* sp_pairs,
-                            const uint32_t* back, const float2* sp_pos_out, const float2* sp_vel_out, const float2* sp_pred,
-                            const float* sp_rho, float2* pos, float2* vel, float2* pred, float* rho, uint32_t* key,
-                            unsigned char* owned, uint32_t* counters);
+                                                  key, histogram ticket (counting sort) and out[] entry, the lost counter */);
+// Overlapped slab step — the boundary strips (kernels_slab.hip).  `P` = the main array's StepParams, `A` its arrays;
+// StripArrays::counters: [0] live strip particles (written by the strip's scan), [1] slots filled from the main array, [2] slots in use.
+struct StripArrays {
+    uint32_t cap = 0;
+    float2 *pos = nullptr, *vel = nullptr;   // the strip's own particle array before its step ...
+    u64* kt = nullptr;                 // ... its counting sort's words and histogram
+    uint32_t* hist = nullptr;
+    uint32_t* back = nullptr;          // main-array slot of each strip slot
+    uint32_t* rowbase = nullptr;       // 2 * grid_h
+    unsigned long long* safe = nullptr;
+    uint32_t* counters = nullptr;
+    const u64* pairs = nullptr;        // after its step: what the write-back scatters into the main array
+    const float2 *pos_out = nullptr, *vel_out = nullptr, *pred = nullptr;
+    const float* rho = nullptr;
+};
+void launch_strip_gather(hipStream_t st, const StepParams& P, const SlabArrays& A, const StripArrays& T, const OverlapPlan& plan, uint32_t R);
+void launch_strip_unpack(hipStream_t st, const StepParams& P, const SlabArrays& A, const StripArrays& T, const SlabMessages& M);
+void launch_strip_writeback(hipStream_t st, const StepParams& P_strip, const SlabArrays& A, const StripArrays& T);
 size_t slab_stage_words(uint32_t cap);
 size_t slab_msg_groups(uint32_t cap);
-void launch_slab_unpack(hipStream_t st, const StepParams& P, uint32_t main_slots, uint32_t R, const void* msg_left,
-                        const void* msg_right, float2* pos, float2* vel, u64* out, uint32_t* hist, uint32_t* counters,
-                        bool counting);
-void launch_slab_reorder(hipStream_t st, const StepParams& P, const StepArrays& A, uint32_t cap, uint32_t work_cap, uint32_t* n_live_out);
-void launch_slab_export(hipStream_t st, const StepParams& P, uint32_t cap, const float2* pos, const float2* pred,
-                        const float2* vel, const float* rho, const uint32_t* key, void* out);
-void launch_slab_import(hipStream_t st, const StepParams& P, uint32_t n, uint32_t cap, const void* in, float2* pos,
-                        float2* pred, float2* vel, float* rho, uint32_t* key, unsigned char* owned);
-// migr_first / migr_count: the migrant slots of an overlapped step (outside the sorted prefix), or 0 / 0
-void launch_slab_colhist(hipStream_t st, const StepParams& P, const uint32_t* cs, uint32_t* hist_global, uint32_t migr_first = 0,
-                         uint32_t migr_count = 0, const unsigned char* owned = nullptr, const uint32_t* key = nullptr);
-void launch_slab_maxspeed(hipStream_t st, const uint32_t* n_live, const float2* vel, const unsigned char* owned,
-                          uint32_t* out_bits, uint32_t migr_first = 0, uint32_t migr_count = 0);
+void launch_slab_unpack(hipStream_t st, const StepParams& P, const SlabArrays& A, const SlabMessages& M);
+void launch_slab_reorder(hipStream_t st, const StepParams& P, const SlabArrays& A, uint32_t work_cap);
+void launch_slab_export(hipStream_t st, const StepParams& P, const SlabArrays& A);
+void launch_slab_import(hipStream_t st, const StepParams& P, const SlabArrays& A, uint32_t n);
+// migr_count: the migrant slots of an overlapped step (outside the sorted prefix, from SlabArrays::main_slots), or 0
+void launch_slab_colhist(hipStream_t st, const StepParams& P, const SlabArrays& A, uint32_t* hist_global, uint32_t migr_count);
+// the bits of the largest owned |velocity| into counters[5]
+void launch_slab_maxspeed(hipStream_t st, const SlabArrays& A, uint32_t migr_count);
 size_t slab_message_bytes(uint32_t R);
 
 // Bitonic network of sort.wgsl:27-51 / simulation.rs:323-347 on (key<<32 | index) pairs.

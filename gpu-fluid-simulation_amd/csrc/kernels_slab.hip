@@ -679,142 +679,108 @@ __global__ __launch_bounds__(SL_BLOCK) void k_strip_writeback(StepParams P, uint
 
 // ------------------------------------------------------------------ launchers
 static inline uint32_t nb(uint32_t n) { return (n + SL_BLOCK - 1) / SL_BLOCK; }
+// the records of a message follow its header
+static inline float4* records(const SlabHeader* h) { return h ? (float4*)(h + 1) : nullptr; }
 
-void launch_slab_maxspeed(hipStream_t st, const uint32_t* n_live, const float2* vel, const unsigned char* owned,
-                          uint32_t* out_bits, uint32_t migr_first, uint32_t migr_count) {
-    hipLaunchKernelGGL(k_slab_maxspeed, dim3(1024), dim3(SL_BLOCK), 0, st, n_live, vel, owned, out_bits, migr_first, migr_count);
+void launch_slab_maxspeed(hipStream_t st, const SlabArrays& A, uint32_t migr_count) {
+    hipLaunchKernelGGL(k_slab_maxspeed, dim3(1024), dim3(SL_BLOCK), 0, st, A.counters, A.vel, A.owned, A.counters + 5, A.main_slots, migr_count);
 }
+
+// The two halves of `stage` and the message headers, for `blocks` pack blocks.
+struct MsgLayout {
+    uint32_t blocks, groups;
+    uint32_t *stage_l, *stage_r;
+    SlabHeader *hl, *hr;
+    MsgLayout(const SlabArrays& A, const SlabMessages& M, uint32_t cap)
+        : blocks(nb(cap)), groups((blocks + MSG_GROUP - 1u) / MSG_GROUP), stage_l(A.stage), stage_r(A.stage + (size_t)blocks * SL_BLOCK),
+          hl((SlabHeader*)M.left), hr((SlabHeader*)M.right) {}
+};
 
 // offsets + headers, then the parallel gather.  blockcnt holds 2 * (blocks + 1) entries: counts, then offsets.
-static void launch_slab_msg(hipStream_t st, uint32_t blocks, uint32_t groups, uint32_t R, void* blockcnt, const uint32_t* stage_l,
-                            const uint32_t* stage_r, const float2* pos, const float2* vel, void* state, uint32_t epoch,
-                            SlabHeader* hl, SlabHeader* hr, uint32_t* counters, const StepParams& P, const uint32_t* cs_edge = nullptr,
-                            uint32_t edge_grid = 0) {
-    uint2* cnt = (uint2*)blockcnt;
-    uint2* off = cnt + (blocks + 1u);
-    hipLaunchKernelGGL(k_slab_msg, dim3(groups), dim3(64), 0, st, blocks, R, (const uint2*)cnt, off, (u64*)state, counters + 6, epoch,
-                       hl, hr, counters, P, cs_edge);
-    hipLaunchKernelGGL(k_slab_gather, dim3(cs_edge ? edge_grid : blocks), dim3(SL_BLOCK), 0, st, R, (const uint2*)cnt, (const uint2*)off,
-                       stage_l, stage_r, pos, vel, hl ? (float4*)(hl + 1) : nullptr, hr ? (float4*)(hr + 1) : nullptr, P, cs_edge);
+static void launch_slab_msg(hipStream_t st, const StepParams& P, const SlabArrays& A, const SlabMessages& M, const MsgLayout& L,
+                            const uint32_t* cs_edge = nullptr, uint32_t edge_grid = 0) {
+    uint2* cnt = (uint2*)A.blockcnt;
+    uint2* off = cnt + (L.blocks + 1u);
+    hipLaunchKernelGGL(k_slab_msg, dim3(L.groups), dim3(64), 0, st, L.blocks, M.R, (const uint2*)cnt, off, (u64*)A.msg_state, A.counters + 6,
+                       M.epoch, L.hl, L.hr, A.counters, P, cs_edge);
+    hipLaunchKernelGGL(k_slab_gather, dim3(cs_edge ? edge_grid : L.blocks), dim3(SL_BLOCK), 0, st, M.R, (const uint2*)cnt, (const uint2*)off,
+                       L.stage_l, L.stage_r, A.pos, A.vel, records(L.hl), records(L.hr), P, cs_edge);
 }
 
-void launch_slab_pack(hipStream_t st, const StepParams& P, uint32_t main_slots, uint32_t R, int has_left,
-                      int has_right, const float2* pos, const float2* vel, const unsigned char* owned, u64* out,
-                      uint32_t* hist, void* blockcnt, uint32_t* stage /* 2 x capacity words */, void* state, uint32_t epoch,
-                      void* msg_left, void* msg_right, uint32_t* counters, uint32_t* gap_counter, unsigned long long* safe,
-                      bool counting, bool overlap, bool lists, const uint32_t* key_prev, uint32_t prev_adv_lo, uint32_t prev_adv_hi,
-                      bool skip_edge) {
+void launch_slab_pack(hipStream_t st, const StepParams& P, const SlabArrays& A, const SlabMessages& M, const SlabPack& O) {
     // covers ALL slots (P.n = capacity): slots past `main_slots` only check for stranded owned particles
-    const uint32_t cap = P.n > main_slots ? P.n : main_slots;
-    const uint32_t blocks = nb(cap), groups = (blocks + MSG_GROUP - 1u) / MSG_GROUP;
-    uint32_t* stage_l = stage;
-    uint32_t* stage_r = stage + (size_t)blocks * SL_BLOCK;
-    SlabHeader* hl = (SlabHeader*)msg_left;
-    SlabHeader* hr = (SlabHeader*)msg_right;
-    if (counting)
-        hipLaunchKernelGGL(k_slab_pack<true>, dim3(blocks), dim3(SL_BLOCK), 0, st, P, cap, main_slots, overlap ? 1 : 0, lists ? 1 : 0, has_left, has_right, pos,
-                           vel, owned, out, hist, (uint2*)blockcnt, stage_l, stage_r, counters, gap_counter, safe, key_prev, prev_adv_lo, prev_adv_hi, skip_edge ? 1 : 0);
-    else
-        hipLaunchKernelGGL(k_slab_pack<false>, dim3(blocks), dim3(SL_BLOCK), 0, st, P, cap, main_slots, 0, lists ? 1 : 0, has_left, has_right, pos,
-                           vel, owned, out, hist, (uint2*)blockcnt, stage_l, stage_r, counters, gap_counter, safe, key_prev, prev_adv_lo, prev_adv_hi, skip_edge ? 1 : 0);
-    if ((!hl && !hr) || !lists) return;                                 // no neighbour / messages pre-built: nothing to send
-    launch_slab_msg(st, blocks, groups, R, blockcnt, stage_l, stage_r, pos, vel, state, epoch, hl, hr, counters, P);
+    const uint32_t cap = P.n > A.main_slots ? P.n : A.main_slots;
+    const MsgLayout L(A, M, cap);
+    hipLaunchKernelGGL(A.counting ? k_slab_pack<true> : k_slab_pack<false>, dim3(L.blocks), dim3(SL_BLOCK), 0, st, P, cap, A.main_slots,
+                       A.counting && A.overlap ? 1 : 0, O.lists ? 1 : 0, M.has_left, M.has_right, A.pos, A.vel, A.owned, A.out, A.hist, (uint2*)A.blockcnt,
+                       L.stage_l, L.stage_r, A.counters, A.counter, A.safe, A.key_s, O.prev_adv_lo, O.prev_adv_hi, O.skip_edge ? 1 : 0);
+    if ((!L.hl && !L.hr) || !O.lists) return;                           // no neighbour / messages pre-built: nothing to send
+    launch_slab_msg(st, P, A, M, L);
 }
 // words of `stage` and of the look-back state launch_slab_pack needs for `cap` slots
 size_t slab_stage_words(uint32_t cap) { return 2 * (size_t)nb(cap) * SL_BLOCK; }
 size_t slab_msg_groups(uint32_t cap) { return (nb(cap) + MSG_GROUP - 1u) / MSG_GROUP; }
 
-void launch_slab_prepack(hipStream_t st, const StepParams& P_next, uint32_t cap, uint32_t R, int has_left, int has_right,
-                         const float2* pos, const float2* vel, const unsigned char* owned, const uint32_t* key_s, void* blockcnt,
-                         uint32_t* stage, void* state, uint32_t epoch, void* msg_left, void* msg_right, uint32_t* counters,
-                         const uint32_t* cs, uint32_t edge_grid, bool classify, bool counting, uint32_t main_slots, u64* out,
-                         uint32_t* hist) {
-    const uint32_t blocks = nb(cap), groups = (blocks + MSG_GROUP - 1u) / MSG_GROUP;
-    uint32_t* stage_l = stage;
-    uint32_t* stage_r = stage + (size_t)blocks * SL_BLOCK;
-    SlabHeader* hl = (SlabHeader*)msg_left;
-    SlabHeader* hr = (SlabHeader*)msg_right;
-    if (!hl && !hr) return;
+void launch_slab_prepack(hipStream_t st, const StepParams& P_next, const SlabArrays& A, const SlabMessages& M, uint32_t edge_grid,
+                         bool classify) {
+    const MsgLayout L(A, M, A.cap);
+    if (!L.hl && !L.hr) return;
     const bool walk = edge_grid != 0 && P_next.transposed;
-    hipLaunchKernelGGL(k_slab_prepack, dim3(walk ? edge_grid : blocks), dim3(SL_BLOCK), 0, st, P_next, has_left, has_right, walk ? 1 : 0,
-                       pos, vel, owned, key_s, cs, (uint2*)blockcnt, stage_l, stage_r, classify ? 1 : 0, counting ? 1 : 0, main_slots, out,
-                       hist, counters);
-    launch_slab_msg(st, blocks, groups, R, blockcnt, stage_l, stage_r, pos, vel, state, epoch, hl, hr, counters, P_next,
-                    walk ? cs : nullptr, edge_grid);
+    hipLaunchKernelGGL(k_slab_prepack, dim3(walk ? edge_grid : L.blocks), dim3(SL_BLOCK), 0, st, P_next, M.has_left, M.has_right, walk ? 1 : 0,
+                       A.pos, A.vel, A.owned, A.key_s, A.cs, (uint2*)A.blockcnt, L.stage_l, L.stage_r, classify ? 1 : 0, A.counting ? 1 : 0, A.main_slots, A.out, A.hist, A.counters);
+    launch_slab_msg(st, P_next, A, M, L, walk ? A.cs : nullptr, edge_grid);
 }
 
-void launch_slab_unpack(hipStream_t st, const StepParams& P, uint32_t main_slots, uint32_t R, const void* msg_left,
-                        const void* msg_right, float2* pos, float2* vel, u64* out, uint32_t* hist, uint32_t* counters,
-                        bool counting) {
-    const SlabHeader* hl = (const SlabHeader*)msg_left;
-    const SlabHeader* hr = (const SlabHeader*)msg_right;
-    const float4* rl = hl ? (const float4*)(hl + 1) : nullptr;
-    const float4* rr = hr ? (const float4*)(hr + 1) : nullptr;
-    if (counting)
-        hipLaunchKernelGGL(k_slab_unpack<true>, dim3(nb(2 * R)), dim3(SL_BLOCK), 0, st, P, main_slots, R, hl, rl, hr, rr, pos, vel,
-                           out, hist, counters);
-    else
-        hipLaunchKernelGGL(k_slab_unpack<false>, dim3(nb(2 * R)), dim3(SL_BLOCK), 0, st, P, main_slots, R, hl, rl, hr, rr, pos, vel,
-                           out, hist, counters);
+void launch_slab_unpack(hipStream_t st, const StepParams& P, const SlabArrays& A, const SlabMessages& M) {
+    const SlabHeader* hl = (const SlabHeader*)M.left;
+    const SlabHeader* hr = (const SlabHeader*)M.right;
+    hipLaunchKernelGGL(A.counting ? k_slab_unpack<true> : k_slab_unpack<false>, dim3(nb(2 * M.R)), dim3(SL_BLOCK), 0, st, P, A.main_slots, M.R,
+                       hl, records(hl), hr, records(hr), A.pos_out, A.vel_out, A.out, A.hist, A.counters);
 }
 
 // bitonic slab mode only (the counting sort's k_cs_fixreorder<true> does the reorder itself)
-void launch_slab_reorder(hipStream_t st, const StepParams& P, const StepArrays& A, uint32_t cap, uint32_t work_cap, uint32_t* n_live_out) {
-    hipLaunchKernelGGL(k_slab_reorder, dim3(nb(cap)), dim3(SL_BLOCK), 0, st, P, cap, A.pairs, A.pos, A.vel, A.pos_s,
-                       A.vel_s, A.pred, A.key_s, A.owned, A.cs, A.start_ref, (GapEntry*)A.work, A.counter, work_cap, n_live_out, A.safe, A.fdefer, A.fcount);
+void launch_slab_reorder(hipStream_t st, const StepParams& P, const SlabArrays& A, uint32_t work_cap) {
+    hipLaunchKernelGGL(k_slab_reorder, dim3(nb(A.cap)), dim3(SL_BLOCK), 0, st, P, A.cap, A.pairs, A.pos, A.vel, A.pos_s,
+                       A.vel_s, A.pred, A.key_s, A.owned, A.cs, A.start_ref, (GapEntry*)A.work, A.counter, work_cap, A.counters, A.safe, A.fdefer, A.fcount);
     launch_fill_gaps(st, A.cs, A.work, A.counter, work_cap);
 }
 
-void launch_slab_export(hipStream_t st, const StepParams& P, uint32_t cap, const float2* pos, const float2* pred,
-                        const float2* vel, const float* rho, const uint32_t* key, void* out) {
-    hipLaunchKernelGGL(k_slab_export, dim3(nb(cap)), dim3(SL_BLOCK), 0, st, P, cap, pos, pred, vel, rho, key,
-                       (AosParticle*)out);
+void launch_slab_export(hipStream_t st, const StepParams& P, const SlabArrays& A) {
+    hipLaunchKernelGGL(k_slab_export, dim3(nb(A.cap)), dim3(SL_BLOCK), 0, st, P, A.cap, A.pos, A.pred, A.vel, A.rho, A.key_s, (AosParticle*)A.aos);
 }
 
-void launch_slab_import(hipStream_t st, const StepParams& P, uint32_t n, uint32_t cap, const void* in, float2* pos,
-                        float2* pred, float2* vel, float* rho, uint32_t* key, unsigned char* owned) {
-    hipLaunchKernelGGL(k_slab_import, dim3(nb(cap)), dim3(SL_BLOCK), 0, st, P, n, cap, (const AosParticle*)in, pos,
-                       pred, vel, rho, key, owned);
+void launch_slab_import(hipStream_t st, const StepParams& P, const SlabArrays& A, uint32_t n) {
+    hipLaunchKernelGGL(k_slab_import, dim3(nb(A.cap)), dim3(SL_BLOCK), 0, st, P, n, A.cap, (const AosParticle*)A.aos, A.pos_out,
+                       A.pred, A.vel_out, A.rho, A.key_s, A.owned);
 }
 
-void launch_slab_colhist(hipStream_t st, const StepParams& P, const uint32_t* cs, uint32_t* hist_global, uint32_t migr_first,
-                         uint32_t migr_count, const unsigned char* owned, const uint32_t* key) {
-    hipLaunchKernelGGL(k_slab_colhist, dim3(nb(P.grid_w)), dim3(SL_BLOCK), 0, st, P, cs, hist_global);
+void launch_slab_colhist(hipStream_t st, const StepParams& P, const SlabArrays& A, uint32_t* hist_global, uint32_t migr_count) {
+    hipLaunchKernelGGL(k_slab_colhist, dim3(nb(P.grid_w)), dim3(SL_BLOCK), 0, st, P, A.cs, hist_global);
     if (migr_count)
-        hipLaunchKernelGGL(k_slab_colhist_migrants, dim3(nb(migr_count)), dim3(SL_BLOCK), 0, st, P, migr_first, migr_count, owned, key,
-                           hist_global);
+        hipLaunchKernelGGL(k_slab_colhist_migrants, dim3(nb(migr_count)), dim3(SL_BLOCK), 0, st, P, A.main_slots, migr_count, A.owned, A.key_s, hist_global);
 }
 
 size_t slab_message_bytes(uint32_t R) { return sizeof(SlabHeader) + (size_t)R * sizeof(float4); }
 
 // ---- overlapped step: the boundary strips
-void launch_strip_gather(hipStream_t st, const StepParams& P, const uint32_t win[4], uint32_t R, uint32_t strip_cap,
-                         const uint32_t* cs, uint32_t* rowbase, const u64* pairs, const float2* pos_s, const float2* vel_s,
-                         float2* sp_pos, float2* sp_vel, u64* kt, uint32_t* hist, uint32_t* back, unsigned long long* safe,
-                         uint32_t* strip_counters, uint32_t* counters) {
-    const StripWin W{win[0], win[1], win[2], win[3]};
-    hipLaunchKernelGGL(k_strip_rows, dim3(1), dim3(SR_BLOCK), 0, st, P.grid_w, P.grid_h, W, 2u * R, cs, rowbase, strip_counters);
+void launch_strip_gather(hipStream_t st, const StepParams& P, const SlabArrays& A, const StripArrays& T, const OverlapPlan& plan, uint32_t R) {
+    const StripWin W{plan.win[0], plan.win[1], plan.win[2], plan.win[3]};
+    hipLaunchKernelGGL(k_strip_rows, dim3(1), dim3(SR_BLOCK), 0, st, P.grid_w, P.grid_h, W, 2u * R, A.cs, T.rowbase, T.counters);
     const uint32_t waves = 2u * P.grid_h, per_block = SL_BLOCK / 64;
     hipLaunchKernelGGL(k_strip_gather, dim3((waves + per_block - 1) / per_block), dim3(SL_BLOCK), 0, st, P.grid_w, P.grid_h, P.ncell,
-                       W, strip_cap, cs, rowbase, pairs, pos_s, vel_s, sp_pos, sp_vel, kt, hist, back, safe, counters);
+                       W, T.cap, A.cs, T.rowbase, A.pairs, A.pos_s, A.vel_s, T.pos, T.vel, T.kt, T.hist, T.back, T.safe, A.counters);
 }
 
-void launch_strip_unpack(hipStream_t st, const StepParams& P, uint32_t main_slots, uint32_t R, uint32_t strip_cap,
-                         const void* msg_left, const void* msg_right, float2* sp_pos, float2* sp_vel, u64* kt, uint32_t* hist,
-                         uint32_t* back, const uint32_t* strip_counters, uint32_t* counters) {
-    const SlabHeader* hl = (const SlabHeader*)msg_left;
-    const SlabHeader* hr = (const SlabHeader*)msg_right;
-    hipLaunchKernelGGL(k_strip_unpack, dim3(nb(2 * R)), dim3(SL_BLOCK), 0, st, P, main_slots, R, strip_cap, hl,
-                       hl ? (const float4*)(hl + 1) : nullptr, hr, hr ? (const float4*)(hr + 1) : nullptr, sp_pos, sp_vel, kt, hist,
-                       back, strip_counters, counters);
+void launch_strip_unpack(hipStream_t st, const StepParams& P, const SlabArrays& A, const StripArrays& T, const SlabMessages& M) {
+    const SlabHeader* hl = (const SlabHeader*)M.left;
+    const SlabHeader* hr = (const SlabHeader*)M.right;
+    hipLaunchKernelGGL(k_strip_unpack, dim3(nb(2 * M.R)), dim3(SL_BLOCK), 0, st, P, A.main_slots, M.R, T.cap, hl,
+                       records(hl), hr, records(hr), T.pos, T.vel, T.kt, T.hist, T.back, T.counters, A.counters);
 }
 
-void launch_strip_writeback(hipStream_t st, const StepParams& P_strip, uint32_t main_slots, uint32_t strip_cap, const u64* sp_pairs,
-                            const uint32_t* back, const float2* sp_pos_out, const float2* sp_vel_out, const float2* sp_pred,
-                            const float* sp_rho, float2* pos, float2* vel, float2* pred, float* rho, uint32_t* key,
-                            unsigned char* owned, uint32_t* counters) {
-    hipLaunchKernelGGL(k_strip_writeback, dim3(nb(strip_cap)), dim3(SL_BLOCK), 0, st, P_strip, main_slots, sp_pairs, back, sp_pos_out,
-                       sp_vel_out, sp_pred, sp_rho, pos, vel, pred, rho, key, owned, counters);
+void launch_strip_writeback(hipStream_t st, const StepParams& P_strip, const SlabArrays& A, const StripArrays& T) {
+    hipLaunchKernelGGL(k_strip_writeback, dim3(nb(T.cap)), dim3(SL_BLOCK), 0, st, P_strip, A.main_slots, T.pairs, T.back, T.pos_out,
+                       T.vel_out, T.pred, T.rho, A.pos_out, A.vel_out, A.pred, A.rho, A.key_s, A.owned, A.counters);
 }
 
 }  // namespace fsd

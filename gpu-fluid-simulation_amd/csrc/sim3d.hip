@@ -17,9 +17,7 @@
 #include <vector>
 
 #include "../../include/fluidsim.h"
-#include "fs_host.h"
-#include "fs_kernels.h"
-#include "sort_policy.h"
+#include "engine.h"
 
 static_assert(sizeof(fs3_particle) == 48, "fs3_particle is 48 bytes");
 
@@ -1054,10 +1052,7 @@ fs_status fs3_create_ex(const fs3_settings* st, int device, fs_vec3 off, int mat
     const double gw = std::ceil((double)st->size.x / st->smoothing_radius) + 2, gh = std::ceil((double)st->size.y / st->smoothing_radius) + 2,
                  gd = std::ceil((double)st->size.z / st->smoothing_radius) + 2;
     if (gw * gh * gd >= 4294967295.0) return fail(FS_ERR_INVALID, "grid does not fit u32 cell ids");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(FS_ERR_DEVICE, "no HIP device: the engine has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(FS_ERR_INVALID, "device ordinal out of range");
-    FS_HIP(hipSetDevice(device));
+    FS_TRY(fsd::use_device(device));
     std::unique_ptr<fs_sim3> s(new (std::nothrow) fs_sim3());   // an error exit frees whatever the handle holds by then
     if (!s) return fail(FS_ERR_OOM, "host allocation failed");
     s->st = *st; s->n = st->particle_count; s->device = device; s->math_mode = math_mode;
@@ -1087,31 +1082,13 @@ fs_status fs3_create_ex(const fs3_settings* st, int device, fs_vec3 off, int mat
                            s->pred.p, s->vel.p, s->key.p);
         FS_HIP(hipStreamSynchronize(s->stream));
     }
-    for (int k = 0; k < 2; ++k) {   // prove the two constant divisions for this h (see engine.hip prove_constdiv)
-        fsd::ConstDiv& K = k == 0 ? s->div_2h3 : s->div_h2;
+    {   // the create-time proofs of the 2D engine (engine.h): the two constant divisions for this h, the lean reciprocal / square root
         const float hh = st->smoothing_radius;
-        K.c = k == 0 ? 2.0f * hh * hh * hh : hh * hh;
-        K.y = 1.0f / K.c;
-        K.ok = 0;
-        if (!(K.c > 4.0f * FS_CONSTDIV_MIN) || !std::isfinite(K.c) || !std::isfinite(K.y)) continue;
-        uint32_t bad = 1;
-        FS_HIP(hipMemsetAsync(s->counter.p + 1, 0, 4, s->stream));
-        fsd::launch_verify_constdiv(s->stream, K.c, K.y, FS_CONSTDIV_MIN, K.c, s->counter.p + 1);
-        FS_HIP(hipMemcpyAsync(&bad, s->counter.p + 1, 4, hipMemcpyDeviceToHost, s->stream));
-        FS_HIP(hipStreamSynchronize(s->stream));
-        K.ok = bad == 0 ? 1 : 0;
-    }
-    {   // lean reciprocal / square root of the shared-denominator path, over their whole ranges (engine.hip)
-        uint32_t bad[2] = {1, 1};
-        const float hh = st->smoothing_radius;
-        if (!getenv("FS_NO_SHAREDIV")) {
-            FS_HIP(hipMemsetAsync(s->counter.p + 1, 0, 8, s->stream));
-            fsd::launch_verify_unary(s->stream, 0, FS_RCP_LO, FS_RCP_HI, s->counter.p + 1);
-            fsd::launch_verify_unary(s->stream, 1, FS_SQRT_LO, FS_SQRT_HI, s->counter.p + 2);
-            FS_HIP(hipMemcpyAsync(bad, s->counter.p + 1, 8, hipMemcpyDeviceToHost, s->stream));
-            FS_HIP(hipStreamSynchronize(s->stream));
-        }
-        s->share_div = bad[0] == 0 && bad[1] == 0 && s->div_2h3.ok && s->div_h2.ok && hh >= 0x1p-19f && hh <= 0x1p19f;
+        bool rcp_ok, sqrt_ok;
+        FS_TRY(fsd::prove_constdiv(s->stream, s->counter.p + 1, 2.0f * hh * hh * hh, &s->div_2h3));
+        FS_TRY(fsd::prove_constdiv(s->stream, s->counter.p + 1, hh * hh, &s->div_h2));
+        FS_TRY(fsd::prove_rcp_sqrt(s->stream, s->counter.p + 1, &rcp_ok, &sqrt_ok));
+        s->share_div = rcp_ok && sqrt_ok && s->div_2h3.ok && s->div_h2.ok && hh >= 0x1p-19f && hh <= 0x1p19f;
     }
     *out = s.release();
     return FS_OK;

@@ -396,8 +396,10 @@ typedef struct fs_slab_config {
     uint32_t capacity;            /* particle slots of the local array (incl. 2*recv_capacity) */
     uint32_t recv_capacity;       /* records per incoming message */
     uint32_t max_cols;            /* widest owned window this handle must support (re-balancing) */
-    uint32_t sort_mode;           /* low byte: 0 = default (counting sort), 1 + fs_sort_mode selects explicitly; | FS_SLAB_SERIAL:
-                                     the serial step (pack -> exchange -> everything) instead of the overlapped one */
+    uint32_t sort_mode;           /* low byte: 0 = default (counting sort), 1 + fs_sort_mode selects explicitly; flags (counting sort
+                                     only, default: the edge-first step) | FS_SLAB_SERIAL: the serial step (pack -> exchange ->
+                                     everything), | FS_SLAB_STRIPS: the boundary-strips step, | FS_SLAB_ROWMAJOR: row-major cell ids
+                                     even where a slab edge has a neighbour (FS_SLAB_MODE / FS_SLAB_TRANSPOSE override) */
 } fs_slab_config;
 #define FS_SLAB_SERIAL 0x100u
 #define FS_SLAB_STRIPS 0x200u
