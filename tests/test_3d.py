@@ -291,28 +291,67 @@ def test_3d_mask_handoff_does_not_change_a_bit(fs, tmp_path):
     assert np.array_equal(outs[0].view(np.uint8), outs[4].view(np.uint8))
 
 
-@pytest.mark.parametrize("seed,coincident", [(1, False), (2, True)])
-def test_oracle3d_equals_independent_python_restatement(fs, orc, seed, coincident):
+PYREF_VARIANTS = {
+    # name: (side, h, spacing, size, tick overrides) — the settings the path / guard / random tests of test_3d_paths_gpu.py use
+    "rest_density_mass": (5, 0.2, 0.1, (1.6, 1.2, 1.4), dict(rest_density=20.0, mass=1.7)),
+    "viscosity_0_rest_1000": (4, 0.2, 0.1, (1.6, 1.2, 1.4), dict(viscosity_coefficient=0.0, rest_density=1000.0, pressure_constant=5.0)),
+    "h_0.5": (4, 0.5, 0.25, (4.0, 3.0, 3.5), dict(rest_density=1.0)),
+    "h_0.05": (4, 0.05, 0.025, (0.4, 0.3, 0.35), dict(rest_density=1.0, pressure_constant=5.0)),
+    "thin_domain": (4, 0.2, 0.1, (1.6, 0.15, 1.4), dict(rest_density=1.0)),
+    "walls_and_corners": (4, 0.25, 0.1, (1.0, 0.75, 0.5), dict(rest_density=1.0, damping_factor=0.5)),
+    "overfull_cell": (5, 0.25, 0.1, (2.0, 1.5, 1.25), dict(rest_density=3.0, pressure_constant=0.02, viscosity_coefficient=2.0)),
+}
+
+
+@pytest.mark.parametrize("seed,coincident,variant",
+                         [pytest.param(1, False, None, id="1-False"), pytest.param(2, True, None, id="2-True")] +
+                         [pytest.param(10 + k, False, v, id=v) for k, v in enumerate(PYREF_VARIANTS)])
+def test_oracle3d_equals_independent_python_restatement(fs, orc, seed, coincident, variant):
     """The 3D statement has no reference counterpart, so the C++ 3D oracle is cross-checked by a second restatement in
     pure Python with np.float32 scalars (tests/pyref3d.py): 3 steps of ~90 jittered particles with velocities, optionally
-    with a coincident triple (PRNG direction, r = 0 viscosity), bit for bit on every field."""
+    with a coincident triple (PRNG direction, r = 0 viscosity), bit for bit on every field.  The variants pin the oracle on
+    the settings the kernels are compared with elsewhere: non-zero rest density, mass != 1, viscosity 0, h = 0.5 and 0.05, a
+    domain thinner than h, particles on walls, edges and corners, a cell of 70 particles."""
     import pyref3d
     f = np.float32
     side = 4 if coincident else 5
+    h, spacing, size, over = 0.2, 0.1, (1.6, 1.2, 1.4), {}
+    if variant is not None:
+        side, h, spacing, size, over = PYREF_VARIANTS[variant]
     n = side ** 3
-    st = fs.Settings3(n, 0.1, 0.2, fs.Vec3(1.6, 1.2, 1.4))
-    tick = fs.TickSettings3(float(f(1) / f(120)), fs.Vec3(0.3, 9.81, -0.2), 1.0, 50.0, 0.0, 0.1, 25.0)
-    o = orc.OracleSim3D(st, (0.05, 0.1, -0.05))
+    st = fs.Settings3(n, spacing, h, fs.Vec3(*size))
+    kw = dict(delta=float(f(1) / f(120)), gravity=(0.3, 9.81, -0.2), mass=1.0, pressure_constant=50.0, rest_density=0.0,
+              damping_factor=0.1, viscosity_coefficient=25.0)
+    kw.update(over)
+    tick = fs.TickSettings3(kw["delta"], fs.Vec3(*kw["gravity"]), kw["mass"], kw["pressure_constant"], kw["rest_density"],
+                            kw["damping_factor"], kw["viscosity_coefficient"])
+    o = orc.OracleSim3D(st, (0.05, 0.1, -0.05) if variant is None else (0.0, 0.0, 0.0))
     rng = np.random.default_rng(seed)
     p = o.particles()
-    p["position"] += rng.uniform(-0.04, 0.04, size=(n, 3)).astype(f)
+    p["position"] += rng.uniform(-0.4, 0.4, size=(n, 3)).astype(f) * f(spacing)
     if coincident:
         p["position"][1:3] = p["position"][0]
+    if variant == "thin_domain":
+        p["position"][:, 1] = rng.uniform(-0.075, 0.075, size=n).astype(f)
+    if variant == "walls_and_corners":              # every sign pattern of (-b, inside, +b): 6 faces, 12 edges, 8 corners
+        b = np.array([f(x) * f(0.5) for x in size], dtype=f)
+        signs = [(x, y, z) for x in (-1, 0, 1) for y in (-1, 0, 1) for z in (-1, 0, 1) if (x, y, z) != (0, 0, 0)]
+        for k, sg in enumerate(signs):
+            sg = np.array(sg, dtype=f)
+            p["position"][k] = np.where(sg != 0, sg * b, p["position"][k])
+            p["position"][26 + k] = np.where(sg != 0, sg * b * f(3.0), p["position"][26 + k])      # outside the box
+    if variant == "overfull_cell":                  # 70 particles in cell (3, 3, 3): a row of more than 64 candidates
+        corner = np.array([-f(x) * f(0.5) + f(2) * f(h) for x in size], dtype=f)
+        p["position"][:70] = corner + rng.uniform(0.2, 0.8, size=(70, 3)).astype(f) * f(h)
     p["predicted_position"] = p["position"]
     p["velocity"] = rng.uniform(-2, 2, size=(n, 3)).astype(f)
+    if variant == "overfull_cell":
+        p["velocity"] *= f(0.01)
     if coincident:
         p["velocity"][5] = (400.0, -450.0, 300.0)            # the 500 clamp and a wall bounce
     o.set_particles(p)
+    if variant == "thin_domain":
+        assert o.grid_dims[1] == 3
     parts = [dict(pos=tuple(f(x) for x in r["position"]), pred=tuple(f(x) for x in r["predicted_position"]),
                   vel=tuple(f(x) for x in r["velocity"]), density=f(r["density"]), grid=int(r["grid"])) for r in p]
     for s in range(3):
@@ -330,3 +369,88 @@ def test_oracle3d_equals_independent_python_restatement(fs, orc, seed, coinciden
             assert np.array_equal(got.view(np.uint32), want[name].view(np.uint32)), f"step {s}: {name}"
         got = np.array([q["density"] for q in parts], dtype=f)
         assert np.array_equal(got.view(np.uint32), want["density"].view(np.uint32)), f"step {s}: density"
+        if variant == "overfull_cell":
+            assert np.unique(want["grid"], return_counts=True)[1].max() == 70, "the over-full cell did not survive the step"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("math_mode", ["ieee", "tolerance"])
+def test_3d_partial_upload_after_steps_keeps_the_rest(fs, math_mode):
+    """fs3_upload_particles of the first k < n records leaves the other records — keys and densities included — as the last
+    step produced them (3D twin of test_parity_gpu.py::test_partial_upload_after_steps_keeps_the_rest)."""
+    n, k = 16 ** 3, 1000
+    st, off, tick = fs.dam_break_3d(n)
+    mm = fs.FS_MATH_IEEE if math_mode == "ieee" else fs.FS_MATH_TOLERANCE
+    sim = fs.FluidSimulation3D(st, device=0, initial_offset=off, math_mode=mm)
+    for _ in range(5):
+        sim.tick(tick)
+    before = sim.download_particles()
+    assert before["density"].min() > 0 and np.all(before["grid"][:-1] <= before["grid"][1:])
+    rng = np.random.default_rng(3)
+    head = before[:k].copy()
+    head["density"] = rng.uniform(1, 2, size=k).astype(np.float32)
+    head["grid"] = rng.integers(0, 2**32, size=k, dtype=np.uint32)
+    sim.upload_particles(head)
+    after = sim.download_particles()
+    for name in FLOATS + ("grid",):
+        assert np.array_equal(after[name][:k].view(np.uint32), head[name].view(np.uint32)), name
+        assert np.array_equal(after[name][k:].view(np.uint32), before[name][k:].view(np.uint32)), name
+    sim.tick(tick)                                   # and the engine carries on from the mixed state
+    assert np.isfinite(sim.download_particles()["position"]).all()
+    sim.close()
+
+
+@pytest.mark.gpu
+def test_3d_partial_upload_then_step_matches_oracle(fs, orc):
+    """the step after a partial upload equals the oracle stepped from the same mixed state, bit for bit"""
+    n, k = 12 ** 3, 700
+    st, off, tick = fs.dam_break_3d(n)
+    sim = fs.FluidSimulation3D(st, device=0, initial_offset=off)
+    ref = orc.OracleSim3D(st, off)
+    for _ in range(3):
+        sim.tick(tick); ref.step(tick)
+    rng = np.random.default_rng(8)
+    state = ref.particles()
+    head = state[:k].copy()
+    head["position"] += rng.uniform(-0.02, 0.02, size=(k, 3)).astype(np.float32)
+    head["velocity"] = rng.uniform(-1, 1, size=(k, 3)).astype(np.float32)
+    sim.upload_particles(head)
+    state[:k] = head
+    ref.set_particles(state)
+    for s in range(2):
+        sim.tick(tick); ref.step(tick)
+        _assert_equal3(sim.download_particles(), ref.particles(), f"after a partial upload, step {s}")
+    sim.close()
+
+
+@pytest.mark.gpu
+def test_3d_profiled_and_timed_steps_give_the_same_bits(fs, orc):
+    """fs3_profile_enable (event markers between the passes) and fs3_timed_steps (several steps per call) change no bit"""
+    n = 14 ** 3
+    st, off, tick = fs.dam_break_3d(n)
+    tick.rest_density = 20.0
+    rng = np.random.default_rng(12)
+    ref = orc.OracleSim3D(st, off)
+    p = ref.particles()
+    p["position"] += rng.uniform(-0.03, 0.03, size=(n, 3)).astype(np.float32)
+    p["predicted_position"] = p["position"]
+    p["velocity"] = rng.uniform(-1, 1, size=(n, 3)).astype(np.float32)
+    ref.set_particles(p)
+    plain = fs.FluidSimulation3D(st, device=0, initial_offset=off)
+    prof = fs.FluidSimulation3D(st, device=0, initial_offset=off)
+    timed = fs.FluidSimulation3D(st, device=0, initial_offset=off)
+    for sim in (plain, prof, timed):
+        sim.upload_particles(p)
+    prof.profile(True)
+    for _ in range(4):
+        plain.tick(tick); prof.tick(tick); ref.step(tick)
+    assert timed.timed_steps(tick, 4) > 0.0
+    want = ref.particles()
+    _assert_equal3(plain.download_particles(), want, "plain steps")
+    _assert_equal3(prof.download_particles(), want, "profiled steps")
+    _assert_equal3(timed.download_particles(), want, "timed steps")
+    ms, steps = prof.profile_read()
+    assert steps == 4 and sum(ms.values()) > 0.0
+    assert plain.tick_count == prof.tick_count == timed.tick_count == 4
+    for sim in (plain, prof, timed):
+        sim.close()

@@ -55,31 +55,26 @@ for case in range(first, first + cases):
         print(f"cases {first}..{case} ok (last: n={n}, max particles/cell {cnt.max()}) {time.time()-t0:.0f}s", flush=True)
 print("fuzz ok:", cases, "cases x 2 sort modes")
 
-# ---- 3D: random sides, jitter, velocities, compressions, coincident groups --------------------------------------
+# ---- 3D: the generator of tests/test_3d_paths_gpu.py::test_3d_random_configurations (tests/paths3d.py random_case), more cases
+import paths3d
 from test_3d import _assert_equal3
 t0 = time.time()
 cases3 = cases // 3
 for case in range(first, first + cases3):
-    rng = np.random.default_rng(9000 + case)
-    side = int(rng.integers(2, 34))
-    n = side ** 3
-    st, off, tick = fs.dam_break_3d(n)
+    st, off, tick, mutate, desc = paths3d.random_case(fs, case)
     sim = fs.FluidSimulation3D(st, device=0, initial_offset=off)
     ref = orc.OracleSim3D(st, off)
-    p = ref.particles()
-    centre = p["position"].mean(axis=0)
-    squeeze = float(rng.choice([1.0, 1.0, 0.5, 0.25]))      # < 1: denser than the lattice -> long rows, list path
-    p["position"] = ((p["position"] - centre) * np.float32(squeeze) + centre).astype(np.float32)
-    p["position"] += rng.uniform(-0.03, 0.03, size=(n, 3)).astype(np.float32)
-    if case % 4 == 1 and n > 20:
-        p["position"][1:int(rng.integers(2, 6))] = p["position"][0]
-    p["predicted_position"] = p["position"]
-    p["velocity"] = (rng.standard_normal((n, 3)) * float(rng.choice([0.0, 1e-6, 1.0, 100.0]))).astype(np.float32)
+    p = mutate(ref.particles())
     ref.set_particles(p); sim.upload_particles(p)
+    seen = {}
     with np.errstate(all="ignore"):
-        for s in range(3):
+        for s in range(4):
             sim.tick(tick); ref.step(tick)
-            _assert_equal3(sim.download_particles(), ref.particles(), f"fuzz3d case {case} step {s}")
+            want = ref.particles()
+            _assert_equal3(sim.download_particles(), want, f"fuzz3d {desc} step {s}")
+            for k, v in paths3d.PathModel(want["grid"], ref.grid_dims).summary().items():
+                seen[k] = seen.get(k, 0) + v
+    sim.close(); ref.close()
     if (case - first) % 10 == 9:
-        print(f"3D cases {first}..{case} ok (last: side {side}, squeeze {squeeze}) {time.time()-t0:.0f}s", flush=True)
+        print(f"3D cases {first}..{case} ok (last: {desc}; wave-planes per sweep {seen}) {time.time()-t0:.0f}s", flush=True)
 print("fuzz3d ok:", cases3, "cases")
