@@ -8,6 +8,13 @@
 
 namespace fsd {
 
+// Grids of the 256-thread kernels (FS_BLOCK, fs_neighbours.h) over n particles.
+static inline uint32_t nblk(uint32_t n) { return (n + 256u - 1u) / 256u; }
+static inline uint32_t xcd_grid(uint32_t nb, uint32_t c) {      // blocks to launch for xcd_block() (fs_device.h)
+    const uint32_t chunks = (nb + (1u << c) - 1u) >> c;
+    return (((chunks + 7u) >> 3) << 3) << c;
+}
+
 // The device arrays the sort-reorder, density, surface-tension and force passes of ONE particle array read and write (the main
 // array of a handle, or the boundary strip of an overlapped slab step).  Fields carry the name of the role the passes see;
 // a handle fills the set in one place and a call site overrides what differs for its launch.  Host side only: the launchers

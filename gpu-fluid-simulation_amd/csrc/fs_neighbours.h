@@ -1,0 +1,88 @@
+// fs_neighbours.h — the neighbour walk of the 2D passes: the row ranges of the 3x3 sweep in the dense cell-start table, the
+// stale-start quirk, the block-wide candidate tiles.  RowRanges / block_tile_bounds (shared with the 3D kernels): fs_device.h.
+#pragma once
+#include "fs_device.h"
+
+namespace fsd {
+
+#define FS_BLOCK 256
+
+// ------------------------------------------------------------ neighbour ranges
+// Cells (cx-1..cx+1, y) are consecutive ids, and particles are in id order, so a
+// row of the 3x3 sweep is ONE contiguous index range [cs[id_lo], cs[id_lo+3]).
+// Visiting it ascending is exactly the reference order (offset_x inner, index
+// ascending: funcs.wgsl:161-199).
+//
+// Quirk: the cell of sorted index 0 never gets its start written
+// (compute.wgsl:50), so the reference walks it from a stale start v.  Its
+// particles are [0,cnt); the walk sees [min(v,cnt), cnt).  Any row range that
+// begins at index 0 begins with that cell, so `lo == 0 -> lo = lo_fix`.
+__device__ __forceinline__ uint32_t quirk_lo_fix(const StepParams& P, const u64* __restrict__ pairs,
+                                                 const uint32_t* __restrict__ cs,
+                                                 const uint32_t* __restrict__ start_ref) {
+    if (!P.ref_quirks) return 0u;
+    const uint32_t cmin = (uint32_t)(pairs[0] >> 32);
+    if (cmin >= P.ncell) return 0u;
+    const uint32_t v = start_ref[cmin];
+    const uint32_t cnt = cs[cmin + 1];
+    return v < cnt ? v : cnt;
+}
+
+// (cx, y) are the cell's (u, v) of the handle's id layout (fs_device.h StepParams::transposed; the reference layout: u = x, v = y).
+__device__ __forceinline__ bool row_range(const StepParams& P, const uint32_t* __restrict__ cs, uint32_t cx,
+                                          uint32_t y, uint32_t lo_fix, uint32_t* lo, uint32_t* hi) {
+    if (y >= P.grid_v) return false;             // id >= ncell: OOB start_indices read -> nothing
+    const uint32_t id_lo = y * P.grid_u + cx - 1u;
+    if (id_lo >= P.ncell) return false;
+    uint32_t id_hi = id_lo + 3u;
+    if (id_hi > P.ncell) id_hi = P.ncell;
+    uint32_t a = cs[id_lo];
+    const uint32_t b = cs[id_hi];
+    if (a == 0u) a = lo_fix;
+    *lo = a;
+    *hi = b;
+    return a < b;
+}
+
+// The lane's three row ranges: rows cy - 1, cy, cy + 1 of the sweep around its cell (cx, cy).  A dead lane, a row outside the grid
+// and an empty row all come back as lo == hi.
+__device__ __forceinline__ RowRanges lane_row_ranges(const StepParams& P, const uint32_t* cs, uint32_t lo_fix, uint32_t cx,
+                                                     uint32_t cy, bool live) {
+    RowRanges R;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        R.lo[r] = 0; R.hi[r] = 0;
+        if (live) (void)row_range(P, cs, cx, cy + (uint32_t)(r - 1), lo_fix, &R.lo[r], &R.hi[r]);
+        if (R.hi[r] < R.lo[r]) R.hi[r] = R.lo[r];
+    }
+    return R;
+}
+
+// ------------------------------------------------------------ block neighbour tiles
+// A workgroup owns 256 consecutive sorted particles (a strip of cells in one grid row), so
+// the candidates of ALL its lanes for sweep row r form one short contiguous index range
+// [blo_r, bhi_r).  The three ranges are staged into LDS with coalesced loads once and the
+// per-lane loops then read LDS instead of issuing one gather per candidate.  Strips that
+// straddle a grid-row end (or very sparse ones) exceed the tile and take the global path.
+#define NB_TILE 640          // staged candidates per sweep row
+#ifndef NBF_TILE
+#define NBF_TILE 544         // ... of the force pass (k_force).  384 (round 2) left the blocks of the fluid's free surface — half-empty
+                             // cells: 256 particles span 128 cells and their full neighbour row holds 516 - 526 — to the general
+                             // kernel's unstaged sweep: 32 blocks per step at 16 M even on the lattice, a ~15 us tail behind the
+                             // lean kernel in every step (force 0.603 -> 0.595 ms at 16 M; more at 1 M and per slab rank)
+#endif
+
+// The density -> force hand-off (fs_device.h StepParams::block_bounds): the 8-word record of block `blk` holds the block-wide
+// ranges as [lo0, lo1, lo2, hi0, hi1, hi2].
+__device__ __forceinline__ void store_block_bounds(const StepParams& P, uint32_t blk, const uint32_t* blo, const uint32_t* bhi) {
+    uint32_t* bb = P.block_bounds + 8u * blk;
+    bb[0] = blo[0]; bb[1] = blo[1]; bb[2] = blo[2]; bb[3] = bhi[0]; bb[4] = bhi[1]; bb[5] = bhi[2];
+}
+__device__ __forceinline__ void load_block_bounds(const StepParams& P, uint32_t blk, uint32_t* blo, uint32_t* bhi) {
+    const uint32_t* bb = P.block_bounds + 8u * blk;
+    blo[0] = bb[0]; blo[1] = bb[1]; blo[2] = bb[2]; bhi[0] = bb[3]; bhi[1] = bb[4]; bhi[2] = bb[5];
+}
+
+struct AosParticle { float2 position, predicted, velocity; float density; uint32_t grid; };   // ParticleInstance, 32 B
+
+}  // namespace fsd

@@ -1,396 +1,11 @@
-// kernels_step.hip — the non-sort passes of the SPH step as CDNA4 (gfx950) kernels.
-//
-// Device state is SoA (float2 pos / vel / pred, f32 density): coalesced 8-byte
-// per-lane streams instead of the reference's 32-byte AoS records.  Pass map:
-//   (predict_next_position + create_spatial_lookup, compute.wgsl:8-42, are fused into the first
-//    kernel of the sort: kernels_sort.hip k_bitonic_local<INIT, KEYGEN> / kernels_csort.hip k_cs_hist)
-//   k_reorder       = payload gather after the (key,index) sort + compute_start_indices
-//                     (compute.wgsl:45-56) + dense cell-start table
-//   k_density       = calculate_density (compute.wgsl:59-74, funcs.wgsl:157-203)
+// kernels_force.hip — the force pass of the SPH step.
 //   k_force         = move_particle + both force sweeps fused (compute.wgsl:79-299)
 #include <hip/hip_ext.h>
-#include <stdlib.h>
-#include <string.h>
 
-#include <type_traits>
-
-#include "fs_device.h"
 #include "fs_kernels.h"
+#include "fs_neighbours.h"
 
 namespace fsd {
-
-#define FS_BLOCK 256
-
-// --------------------------------------------------- dense cell-start table fill
-// cs[c] = index of the first sorted particle whose key is >= c (c in [0, ncell]).
-// Short gaps are written by the boundary lane; long gaps go to a worklist.
-__global__ __launch_bounds__(FS_BLOCK) void k_fill_gaps(uint32_t* __restrict__ cs, const GapEntry* __restrict__ work,
-                                                        const uint32_t* __restrict__ counter, uint32_t work_cap) {
-    uint32_t count = *counter;
-    if (count > work_cap) count = work_cap;
-    for (uint32_t e = blockIdx.x; e < count; e += gridDim.x) {
-        const GapEntry g = work[e];
-        for (uint32_t c = g.begin + threadIdx.x; c < g.end; c += FS_BLOCK) cs[c] = g.value;
-    }
-}
-
-// -------------------------------------------------------------------- reorder
-// Gathers the payload into cell order (the reference swaps whole 32-byte records
-// inside the sort, sort.wgsl:44-50; sorting (key,index) pairs and gathering once
-// gives the identical arrangement because the network only looks at keys).
-template <bool FILL>
-__global__ __launch_bounds__(FS_BLOCK) void k_reorder(StepParams P, const u64* __restrict__ pairs,
-                                                      const float2* __restrict__ pos_in,
-                                                      const float2* __restrict__ vel_in, float2* __restrict__ pos_s,
-                                                      float2* __restrict__ vel_s, float2* __restrict__ pred_s,
-                                                      uint32_t* __restrict__ key_s, uint32_t* __restrict__ cs,
-                                                      uint32_t* __restrict__ start_ref, GapEntry* __restrict__ work,
-                                                      uint32_t* __restrict__ counter, uint32_t work_cap,
-                                                      unsigned long long* __restrict__ safe, uint32_t* __restrict__ force_defer,
-                                                      uint32_t* __restrict__ force_work_count) {
-    const uint32_t i = blockIdx.x * FS_BLOCK + threadIdx.x;
-    if (threadIdx.x == 0) {                      // the force pass's worklists of this step (same block size and count)
-        force_defer[2u * blockIdx.x] = 0u;       // [2 blk] pre-registered by k_density, [2 blk + 1] found late by k_force
-        force_defer[2u * blockIdx.x + 1u] = 0u;
-        if (blockIdx.x == 0) { force_work_count[0] = 0u; force_work_count[1] = 0u; }
-    }
-    if (i >= P.n) return;
-    const u64 pr = pairs[i];
-    const uint32_t key = (uint32_t)(pr >> 32);
-    const uint32_t src = (uint32_t)pr;
-    const float2 p = pos_in[src];
-    const float2 v = vel_in[src];
-    if (pos_s) pos_s[i] = p;                  // uniform; nullptr: the force pass reads pos_in[src] itself (StepParams::pos_by_src)
-    vel_s[i] = v;
-    const float2 pd = predict_pos(P, p, v);   // same expression as the key generation in the sort -> same bits
-    pred_s[i] = pd;
-    if (key_s) key_s[i] = key;                // uniform; single-domain handles read the key back from `pairs` instead
-    {   // fs_device.h "safe operand" classification (finished by k_density): one 64-bit word per wave
-        const unsigned long long sb = __builtin_amdgcn_ballot_w64(kin_safe(pd, v));   // lanes that returned above: 0
-        if ((threadIdx.x & 63u) == 0u) safe[i >> 6] = sb;
-    }
-
-    const uint32_t kc = key < P.ncell ? key : P.ncell;   // clamp for table writes only
-    if (i == 0) {
-        if (!P.ref_quirks && key < P.ncell) start_ref[key] = 0;   // compute.wgsl:50 skips index 0
-        if (FILL) fill_cells(cs, 0u, kc + 1u, 0u, work, counter, work_cap);
-    } else {
-        const uint32_t prev = (uint32_t)(pairs[i - 1] >> 32);
-        if (key != prev) {
-            if (key < P.ncell) start_ref[key] = i;                // compute.wgsl:53-55
-            const uint32_t pc = prev < P.ncell ? prev : P.ncell;
-            if (FILL) fill_cells(cs, pc + 1u, kc + 1u, i, work, counter, work_cap);
-        }
-    }
-    if (FILL && i == P.n - 1) fill_cells(cs, kc + 1u, P.ncell + 1u, P.n, work, counter, work_cap);
-}
-
-// ------------------------------------------------------------ neighbour ranges
-// Cells (cx-1..cx+1, y) are consecutive ids, and particles are in id order, so a
-// row of the 3x3 sweep is ONE contiguous index range [cs[id_lo], cs[id_lo+3]).
-// Visiting it ascending is exactly the reference order (offset_x inner, index
-// ascending: funcs.wgsl:161-199).
-//
-// Quirk: the cell of sorted index 0 never gets its start written
-// (compute.wgsl:50), so the reference walks it from a stale start v.  Its
-// particles are [0,cnt); the walk sees [min(v,cnt), cnt).  Any row range that
-// begins at index 0 begins with that cell, so `lo == 0 -> lo = lo_fix`.
-__device__ __forceinline__ uint32_t quirk_lo_fix(const StepParams& P, const u64* __restrict__ pairs,
-                                                 const uint32_t* __restrict__ cs,
-                                                 const uint32_t* __restrict__ start_ref) {
-    if (!P.ref_quirks) return 0u;
-    const uint32_t cmin = (uint32_t)(pairs[0] >> 32);
-    if (cmin >= P.ncell) return 0u;
-    const uint32_t v = start_ref[cmin];
-    const uint32_t cnt = cs[cmin + 1];
-    return v < cnt ? v : cnt;
-}
-
-// (cx, y) are the cell's (u, v) of the handle's id layout (fs_device.h StepParams::transposed; the reference layout: u = x, v = y).
-__device__ __forceinline__ bool row_range(const StepParams& P, const uint32_t* __restrict__ cs, uint32_t cx,
-                                          uint32_t y, uint32_t lo_fix, uint32_t* lo, uint32_t* hi) {
-    if (y >= P.grid_v) return false;             // id >= ncell: OOB start_indices read -> nothing
-    const uint32_t id_lo = y * P.grid_u + cx - 1u;
-    if (id_lo >= P.ncell) return false;
-    uint32_t id_hi = id_lo + 3u;
-    if (id_hi > P.ncell) id_hi = P.ncell;
-    uint32_t a = cs[id_lo];
-    const uint32_t b = cs[id_hi];
-    if (a == 0u) a = lo_fix;
-    *lo = a;
-    *hi = b;
-    return a < b;
-}
-
-// ------------------------------------------------------------ block neighbour tiles
-// A workgroup owns 256 consecutive sorted particles (a strip of cells in one grid row), so
-// the candidates of ALL its lanes for sweep row r form one short contiguous index range
-// [blo_r, bhi_r).  The three ranges are staged into LDS with coalesced loads once and the
-// per-lane loops then read LDS instead of issuing one gather per candidate.  Strips that
-// straddle a grid-row end (or very sparse ones) exceed the tile and take the global path.
-#define NB_TILE 640          // staged candidates per sweep row
-#ifndef NBF_TILE
-#define NBF_TILE 544         // ... of the force pass (k_force).  384 (round 2) left the blocks of the fluid's free surface — half-empty
-                             // cells: 256 particles span 128 cells and their full neighbour row holds 516 - 526 — to the general
-                             // kernel's unstaged sweep: 32 blocks per step at 16 M even on the lattice, a ~15 us tail behind the
-                             // lean kernel in every step (force 0.603 -> 0.595 ms at 16 M; more at 1 M and per slab rank)
-#endif
-
-// -------------------------------------------------------------------- density
-__device__ __forceinline__ float density_cube_tol(float h2, float2 me, float2 q, float acc) {
-    const float dx = q.x - me.x, dy = q.y - me.y;
-    const float t = fmaxf(h2 - __builtin_fmaf(dx, dx, dy * dy), 0.0f);      // NaN candidate: contributes nothing
-    return __builtin_fmaf(t * t, t, acc);
-}
-
-// MASS1: the tick's particle_mass is exactly 1.0f (the reference's default, src/renderer.rs:374-388): `mass * kern` IS kern then
-// (x * 1.0f == x for every f32), and the multiplication — one of the ~14 instructions per candidate — is left out.
-template <bool MASS1 = false>
-__device__ __forceinline__ float density_term(const StepParams& P, float h2, float2 me, float2 q) {
-    const float dx = q.x - me.x, dy = q.y - me.y;
-    const float r2 = dx * dx + dy * dy;
-    float kern = 0.0f;
-    if (!(r2 > h2)) {
-        const float diff = h2 - r2;
-        kern = P.poly6_norm * diff * diff * diff;       // funcs.wgsl:77
-    }
-    return MASS1 ? kern : P.mass * kern * 1.0f;         // funcs.wgsl:192
-}
-
-// TOL (fs_options.math_mode = FS_MATH_TOLERANCE): r2 by one fma, max(h2 - r2, 0) instead of the compare/select, the
-// constant factor mass * 4/(pi h^8) applied once to the sum; stores {pressure_i, 1/rho_i} for the merged force terms.
-template <bool TOL, bool MASS1>
-__device__ __forceinline__ void density_block(const StepParams& P, uint32_t blk, uint32_t n, const float2* __restrict__ pred,
-                                              const uint32_t* __restrict__ cs, const uint32_t* __restrict__ start_ref,
-                                              const u64* __restrict__ pairs, const unsigned long long* __restrict__ safe,
-                                              float* __restrict__ rho_out, float2* __restrict__ rho2_out,
-                                              uint32_t* __restrict__ force_defer, uint32_t* __restrict__ force_work,
-                                              uint32_t* __restrict__ force_count, float2 (*s_pred)[NB_TILE], uint32_t* s_red) {
-    const uint32_t i = blk * FS_BLOCK + threadIdx.x;
-    const bool live = i < n;
-    const uint32_t lo_fix = quirk_lo_fix(P, pairs, cs, start_ref);
-    const float2 me = pred[live ? i : n - 1];
-    uint32_t cx, cy;                // (u, v) of the cell-id layout: (x, y) unless the handle is a transposed slab rank
-    int32_t cg;
-    uv_local(P, me, &cx, &cy, &cg);
-    const float h2 = P.h * P.h;     // funcs.wgsl:73
-    RowRanges R;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        R.lo[r] = 0; R.hi[r] = 0;
-        if (live) (void)row_range(P, cs, cx, cy + (uint32_t)(r - 1), lo_fix, &R.lo[r], &R.hi[r]);
-        if (R.hi[r] < R.lo[r]) R.hi[r] = R.lo[r];
-    }
-    uint32_t blo[3], bhi[3];
-    const bool fit = block_tile_bounds(R, s_red, blo, bhi, NB_TILE);
-    if (P.block_bounds && threadIdx.x == 0) {       // the force pass reads these instead of reducing the same ranges again
-        uint32_t* bb = P.block_bounds + 8u * blk;
-        bb[0] = blo[0]; bb[1] = blo[1]; bb[2] = blo[2]; bb[3] = bhi[0]; bb[4] = bhi[1]; bb[5] = bhi[2];
-    }
-    {   // The force pass sweeps the same row ranges: a wave it could not finish on its lean path — a row longer than
-        // 32 candidates, or a block whose rows do not fit ITS LDS stage — is named here already, so that the general
-        // workgroups of the force launch can start on it at once, beside the lean ones (k_force).
-        const bool unfit = bhi[0] - blo[0] > NBF_TILE || bhi[1] - blo[1] > NBF_TILE || bhi[2] - blo[2] > NBF_TILE;
-        const bool long_row = R.hi[0] - R.lo[0] > 32u || R.hi[1] - R.lo[1] > 32u || R.hi[2] - R.lo[2] > 32u;
-        if ((unfit || __any(long_row)) && __builtin_amdgcn_ballot_w64(live) != 0 && (threadIdx.x & 63u) == 0u) {
-            const uint32_t old = atomicOr(&force_defer[2u * blk], 1u << (threadIdx.x >> 6));
-            if (old == 0u) force_work[atomicAdd(&force_count[0], 1u)] = blk;
-        }
-    }
-    float rho = 0.0f;
-    if (fit) {
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            for (uint32_t j = threadIdx.x; j < bhi[r] - blo[r]; j += FS_BLOCK) s_pred[r][j] = pred[blo[r] + j];
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            // four candidates per trip (independent LDS reads and kernel evaluations give the wave
-            // ILP), adds in index order; then a scalar tail
-            const float2* sp = s_pred[r] - 0;
-            const bool any = R.lo[r] < R.hi[r];
-            const uint32_t hi = any ? R.hi[r] - blo[r] : 0u;
-            uint32_t k = any ? R.lo[r] - blo[r] : 0u;
-            if (TOL) {
-                for (; k + 4u <= hi; k += 4u) {
-                    const float2 q0 = sp[k], q1 = sp[k + 1u], q2 = sp[k + 2u], q3 = sp[k + 3u];
-                    rho = density_cube_tol(h2, me, q0, rho); rho = density_cube_tol(h2, me, q1, rho);
-                    rho = density_cube_tol(h2, me, q2, rho); rho = density_cube_tol(h2, me, q3, rho);
-                }
-                for (; k < hi; ++k) rho = density_cube_tol(h2, me, sp[k], rho);
-                continue;
-            }
-            for (; k + 4u <= hi; k += 4u) {
-                const float t0 = density_term<MASS1>(P, h2, me, sp[k]);
-                const float t1 = density_term<MASS1>(P, h2, me, sp[k + 1u]);
-                const float t2 = density_term<MASS1>(P, h2, me, sp[k + 2u]);
-                const float t3 = density_term<MASS1>(P, h2, me, sp[k + 3u]);
-                rho += t0; rho += t1; rho += t2; rho += t3;
-            }
-            for (; k < hi; ++k) rho += density_term<MASS1>(P, h2, me, sp[k]);
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            for (uint32_t k = R.lo[r]; k < R.hi[r]; ++k) {
-                if (TOL) rho = density_cube_tol(h2, me, pred[k], rho);
-                else rho += density_term<MASS1>(P, h2, me, pred[k]);
-            }
-    }
-    if (!live) return;
-    if (TOL) {
-        rho = rho * (P.mass * P.poly6_norm);                    // sum of (h2 - r2)^3 -> density
-        rho = fmaxf(fmaxf(rho, 1.19209290e-07f), 0.1f);
-        rho_out[i] = rho;
-        rho2_out[i] = make_float2(P.pressure_k * (rho - P.rest_density),
-                                  (P.share_div && rho <= FS_RCP_HI) ? rcp_rn_fast(rho) : __fdiv_rn(1.0f, rho));   // same bits (proven range)
-        return;
-    }
-    rho = fmaxf(rho, 1.19209290e-07f);                          // funcs.wgsl:202
-    rho = fmaxf(rho, 0.1f);                                     // compute.wgsl:70
-    if (rho_out) rho_out[i] = rho;                              // uniform; single-domain handles read it back from rho2.x
-    // {rho, +-RN(1/rho)}: the force pass divides by neighbours' densities; the sign carries the particle's
-    // "safe operand" classification (fs_device.h) — negative sends every pair it takes part in to true divisions
-    const float press = P.pressure_k * (rho - P.rest_density);  // the expression the force pass evaluates
-    const bool ok = ((safe[i >> 6] >> (i & 63u)) & 1ull) != 0ull && rho <= FS_RCP_HI && fabsf(press) <= FS_PRESSURE_HI;
-    // rho >= 0.1; the lean reciprocal is proven correctly rounded on [2^-20, 2^20] (share_div implies that proof)
-    const float y = (P.share_div && rho <= FS_RCP_HI) ? rcp_rn_fast(rho) : __fdiv_rn(1.0f, rho);
-    rho2_out[i] = make_float2(rho, ok ? y : -y);
-}
-
-#define FS_DENSITY_ARGS                                                                                                   \
-    StepParams P, const float2* __restrict__ pred, const uint32_t* __restrict__ cs, const uint32_t* __restrict__ start_ref, \
-        const u64* __restrict__ pairs, const unsigned long long* __restrict__ safe, float* __restrict__ rho_out,         \
-        float2* __restrict__ rho2_out, uint32_t* __restrict__ force_defer, uint32_t* __restrict__ force_work,            \
-        uint32_t* __restrict__ force_count
-template <bool TOL, bool MASS1>
-__global__ __launch_bounds__(FS_BLOCK) void k_density(FS_DENSITY_ARGS) {
-    __shared__ float2 s_pred[3][NB_TILE];
-    __shared__ uint32_t s_red[24];
-    const uint32_t n = P.n_live ? *P.n_live : P.n;
-    uint32_t blk;
-    if (!xcd_block(P, (n + FS_BLOCK - 1) / FS_BLOCK, &blk)) return;   // uniform: no live particle in this block
-    density_block<TOL, MASS1>(P, blk, n, pred, cs, start_ref, pairs, safe, rho_out, rho2_out, force_defer, force_work, force_count, s_pred, s_red);
-}
-// Edge-first slab step, column-major ids (fs_device.h EdgeBlocks): the density of the columns the edge columns' force launch
-// reads — the edge columns and one more towards the interior — ahead of the full launch, on the exchange stream.  (The full
-// launch writes the same values again.)
-template <bool TOL, bool MASS1>
-__global__ __launch_bounds__(FS_BLOCK) void k_density_edge(FS_DENSITY_ARGS) {
-    __shared__ float2 s_pred[3][NB_TILE];
-    __shared__ uint32_t s_red[24];
-    const uint32_t n = *P.n_live;
-    const EdgeBlocks E = edge_blocks(P, cs, n, 1u);
-    for (uint32_t t = blockIdx.x; t < edge_block_count(E); t += gridDim.x) {
-        density_block<TOL, MASS1>(P, edge_block_at(E, t), n, pred, cs, start_ref, pairs, safe, rho_out, rho2_out, force_defer, force_work,
-                           force_count, s_pred, s_red);
-        __syncthreads();                             // the LDS stage is reused
-    }
-}
-
-// ---------------------------------------------------------- surface tension (build extension, NOT in the reference)
-// Continuum surface force (Mueller, Charypar & Gross 2003, §4.4) with the density pass's 2D poly6 kernel
-// W = 4/(pi h^8) (h^2 - r^2)^3, normative statement in DESIGN.md §11.  Per sorted slot i, over the candidates the density pass
-// visits (same rows, same order, the particle itself and the stale-start quirk included), all f32 without contraction:
-//   o = q_j - q_i, r2 = o.o;  skip if r2 > h2;  d = h2 - r2;  w = m / rho_j
-//   n += w * (((Cg d) d) o)                      Cg = 24/(pi h^8): n = sum m/rho_j grad W(q_i - q_j)
-//   L += w * ((Cl d) (3 r2 - h2))                Cl = 48/(pi h^8): the 2D Laplacian -48/(pi h^8)(h^2-r^2)(h^2-3r^2)
-// then |n| = sqrt(n.n) (IEEE) and st = |n| > tau && |n| > 0 ? ((-sigma L) / |n|) n : 0.  The reference's own
-// calculate_surface_tension (compute.wgsl:303-498) is dead code and its gradient vanishes identically.
-// w_j is formed once per staged candidate (with MASS1 it is the density pass's |rho2.y| = RN(1/rho_j)), next to q_j in LDS.
-// One pass after k_density, before the force pass; it reads rho2 / rho and the cell tables and writes st[] only.
-struct StConsts { float h2, cg, cl, sigma, tau; };
-
-__device__ __forceinline__ void st_term(const StConsts& C, float2 me, float2 q, float w, float& nx, float& ny, float& L) {
-    const float ox = q.x - me.x, oy = q.y - me.y;
-    const float r2 = ox * ox + oy * oy;
-    const bool in = !(r2 > C.h2);                   // a NaN candidate is not skipped (the statement's test, as written)
-    const float d = C.h2 - r2;
-    const float k = (C.cg * d) * d;
-    const float lk = (C.cl * d) * ((3.0f * r2) - C.h2);
-    // an accumulator that starts at +0.0f is never -0.0f, so adding +0.0f for a skipped candidate IS skipping it
-    nx += in ? w * (k * ox) : 0.0f;
-    ny += in ? w * (k * oy) : 0.0f;
-    L += in ? w * lk : 0.0f;
-}
-
-template <bool MASS1>
-__device__ __forceinline__ float st_weight(const StepParams& P, const float2* __restrict__ rho2, const float* __restrict__ rho_arr,
-                                           uint32_t j) {
-    if (MASS1) return fabsf(rho2[j].y);             // RN(1/rho_j) == RN(1.0f / rho_j): the sign is the density pass's safe bit
-    return __fdiv_rn(P.mass, rho_arr ? rho_arr[j] : rho2[j].x);   // rho_arr: tolerance mode (rho2 = {pressure, 1/rho})
-}
-
-template <bool MASS1>
-__global__ __launch_bounds__(FS_BLOCK) void k_surface_tension(StepParams P, StConsts C, const float2* __restrict__ pred,
-                                                              const float2* __restrict__ rho2, const float* __restrict__ rho_arr,
-                                                              const uint32_t* __restrict__ cs, const uint32_t* __restrict__ start_ref,
-                                                              const u64* __restrict__ pairs, float2* __restrict__ st_out) {
-    __shared__ float2 s_q[3][NB_TILE];
-    __shared__ float s_w[3][NB_TILE];
-    __shared__ uint32_t s_red[24];
-    const uint32_t n = P.n;
-    uint32_t blk;
-    if (!xcd_block(P, (n + FS_BLOCK - 1) / FS_BLOCK, &blk)) return;   // uniform
-    const uint32_t i = blk * FS_BLOCK + threadIdx.x;
-    const bool live = i < n;
-    const uint32_t lo_fix = quirk_lo_fix(P, pairs, cs, start_ref);
-    const float2 me = pred[live ? i : n - 1];
-    uint32_t cx, cy;
-    int32_t cg;
-    uv_local(P, me, &cx, &cy, &cg);
-    RowRanges R;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        R.lo[r] = 0; R.hi[r] = 0;
-        if (live) (void)row_range(P, cs, cx, cy + (uint32_t)(r - 1), lo_fix, &R.lo[r], &R.hi[r]);
-        if (R.hi[r] < R.lo[r]) R.hi[r] = R.lo[r];
-    }
-    uint32_t blo[3], bhi[3];
-    bool fit;
-    if (P.block_bounds) {       // this step's density pass reduced the same ranges over the same 256 particles
-        const uint32_t* bb = P.block_bounds + 8u * blk;
-        blo[0] = bb[0]; blo[1] = bb[1]; blo[2] = bb[2]; bhi[0] = bb[3]; bhi[1] = bb[4]; bhi[2] = bb[5];
-        fit = bhi[0] - blo[0] <= NB_TILE && bhi[1] - blo[1] <= NB_TILE && bhi[2] - blo[2] <= NB_TILE;
-    } else {
-        fit = block_tile_bounds(R, s_red, blo, bhi, NB_TILE);
-    }
-    float nx = 0.0f, ny = 0.0f, L = 0.0f;
-    if (fit) {
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            for (uint32_t j = threadIdx.x; j < bhi[r] - blo[r]; j += FS_BLOCK) {
-                s_q[r][j] = pred[blo[r] + j];
-                s_w[r][j] = st_weight<MASS1>(P, rho2, rho_arr, blo[r] + j);
-            }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const bool any = R.lo[r] < R.hi[r];
-            const uint32_t hi = any ? R.hi[r] - blo[r] : 0u;
-            uint32_t k = any ? R.lo[r] - blo[r] : 0u;
-            for (; k + 2u <= hi; k += 2u) {          // two candidates per trip: independent LDS reads, adds in index order
-                const float2 q0 = s_q[r][k], q1 = s_q[r][k + 1u];
-                const float w0 = s_w[r][k], w1 = s_w[r][k + 1u];
-                st_term(C, me, q0, w0, nx, ny, L);
-                st_term(C, me, q1, w1, nx, ny, L);
-            }
-            if (k < hi) st_term(C, me, s_q[r][k], s_w[r][k], nx, ny, L);
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            for (uint32_t k = R.lo[r]; k < R.hi[r]; ++k) st_term(C, me, pred[k], st_weight<MASS1>(P, rho2, rho_arr, k), nx, ny, L);
-    }
-    if (!live) return;
-    const float nl = sqrt_rn(nx * nx + ny * ny);
-    float2 f = make_float2(0.0f, 0.0f);
-    if (nl > C.tau && nl > 0.0f) {
-        const float sc = __fdiv_rn(-C.sigma * L, nl);
-        f = make_float2(sc * nx, sc * ny);
-    }
-    st_out[i] = f;
-}
 
 // ---------------------------------------------------------- force + integrate
 // Two phases per lane so the expensive body (pressure + viscosity terms of one in-radius neighbour)
@@ -807,7 +422,6 @@ __device__ __forceinline__ bool force_sweep_masks(const StepParams& P, const Row
 // amdgpu_waves_per_eu(8, 8): with the chunked sweep inlined next to the mask sweep the allocator would take
 // 83 VGPRs (5 waves/SIMD) and the common path loses 9 %; capped at 64 it spills in the rarely taken
 // branches instead (measured: 0.77 vs 0.86 ms in the bench window, 2.67 vs 2.82 ms in the dense regime).
-struct AosParticle { float2 position, predicted, velocity; float density; uint32_t grid; };   // ParticleInstance, 32 B
 
 // Integration of one particle from its accumulated force sums (compute.wgsl:93-153, :298) and the stores of its new state.
 // ST (compile-time, single-domain handles with fs_set_surface_tension on): the surface-tension force k_surface_tension wrote for
@@ -954,20 +568,13 @@ __device__ __forceinline__ void force_block(const StepParams& P, uint32_t blk, u
                       // columns between two launches (fs_device.h slab_advances)
         if (!slab_advances(P, cg)) live = false;
     }
-    RowRanges R;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        R.lo[r] = 0; R.hi[r] = 0;
-        if (live) (void)row_range(P, cs, cx, cy + (uint32_t)(r - 1), lo_fix, &R.lo[r], &R.hi[r]);
-        if (R.hi[r] < R.lo[r]) R.hi[r] = R.lo[r];
-    }
+    const RowRanges R = lane_row_ranges(P, cs, lo_fix, cx, cy, live);
     uint32_t blo[3], bhi[3];
     bool staged;
     if (P.block_bounds) {
         // the density pass of this step reduced the same ranges over the same 256 particles (a slab launch that advances only
         // some columns zeroes the other lanes' ranges: the stored bounds are then a superset — more is staged, nothing is missed)
-        const uint32_t* bb = P.block_bounds + 8u * blk;
-        blo[0] = bb[0]; blo[1] = bb[1]; blo[2] = bb[2]; bhi[0] = bb[3]; bhi[1] = bb[4]; bhi[2] = bb[5];
+        load_block_bounds(P, blk, blo, bhi);
         staged = bhi[0] - blo[0] <= NBF_TILE && bhi[1] - blo[1] <= NBF_TILE && bhi[2] - blo[2] <= NBF_TILE;
     } else {
         staged = block_tile_bounds(R, s_red, blo, bhi, NBF_TILE);
@@ -1161,6 +768,7 @@ __global__ __launch_bounds__(FS_BLOCK) void k_force_quad(FS_FORCE_ARGS, uint32_t
         if (P.n_live && !slab_advances(P, cg)) live = false;
         bool bad = live && !FAST && !(mrec.y > 0.0f);     // the particle's own operands are outside the proven ranges
         const wave_mask allm = wm(true);
+        // one row at a time (its range lives only as long as its sweep), not lane_row_ranges: no tile, no block-wide bounds here
 #pragma unroll 1
         for (int r = 0; r < 3; ++r) {
             uint32_t lo = 0, hi = 0;
@@ -1253,196 +861,6 @@ __global__ __launch_bounds__(FS_BLOCK) void k_force_quad(FS_FORCE_ARGS, uint32_t
     }
 }
 
-// --------------------------------------------------------------- AoS <-> SoA
-
-__global__ __launch_bounds__(FS_BLOCK) void k_export_aos(uint32_t n, const float2* __restrict__ pos,
-                                                         const float2* __restrict__ pred,
-                                                         const float2* __restrict__ vel,
-                                                         const float* __restrict__ rho,
-                                                         const uint32_t* __restrict__ key,
-                                                         const u64* __restrict__ pairs,
-                                                         const float2* __restrict__ rho2,
-                                                         AosParticle* __restrict__ out) {
-    const uint32_t i = blockIdx.x * FS_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    AosParticle a;
-    a.position = pos[i]; a.predicted = pred[i]; a.velocity = vel[i]; a.density = rho2 ? rho2[i].x : rho[i];
-    a.grid = pairs ? (uint32_t)(pairs[i] >> 32) : key[i];     // after a step the sorted (key, source) pairs hold the keys
-    out[i] = a;
-}
-
-__global__ __launch_bounds__(FS_BLOCK) void k_import_aos(uint32_t n, const AosParticle* __restrict__ in,
-                                                         float2* __restrict__ pos, float2* __restrict__ pred,
-                                                         float2* __restrict__ vel, float* __restrict__ rho,
-                                                         uint32_t* __restrict__ key) {
-    const uint32_t i = blockIdx.x * FS_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const AosParticle a = in[i];
-    pos[i] = a.position; pred[i] = a.predicted; vel[i] = a.velocity; rho[i] = a.density; key[i] = a.grid;
-}
-
-// ------------------------------------------------------- proof kernel for div_const
-// Enumerates EVERY f32 x with lo <= |x| <= hi (both signs; lo, hi > 0 given as bit patterns) and
-// counts those for which div_const_fast(x, c, y) differs bitwise from the correctly rounded x / c.
-__global__ __launch_bounds__(FS_BLOCK) void k_verify_constdiv(float c, float y, uint32_t lo_bits, uint32_t hi_bits,
-                                                              uint32_t* __restrict__ mismatches) {
-    const uint32_t tid = blockIdx.x * FS_BLOCK + threadIdx.x;
-    const uint32_t total_threads = gridDim.x * FS_BLOCK;
-    uint32_t bad = 0;
-    for (uint64_t b = (uint64_t)lo_bits + tid; b <= (uint64_t)hi_bits; b += total_threads) {
-        const float x = __uint_as_float((uint32_t)b);                 // positive floats are ordered like their bits
-        bad += __float_as_uint(div_const_fast(x, c, y)) != __float_as_uint(__fdiv_rn(x, c)) ? 1u : 0u;
-        bad += __float_as_uint(div_const_fast(-x, c, y)) != __float_as_uint(__fdiv_rn(-x, c)) ? 1u : 0u;
-    }
-    if (bad) atomicAdd(mismatches, bad);
-}
-
-void launch_verify_constdiv(hipStream_t st, float c, float y, float lo, float hi, uint32_t* mismatches) {
-    uint32_t lb, hb;
-    memcpy(&lb, &lo, 4);
-    memcpy(&hb, &hi, 4);
-    hipLaunchKernelGGL(k_verify_constdiv, dim3(256 * 32), dim3(FS_BLOCK), 0, st, c, y, lb, hb, mismatches);
-}
-
-// ------------------------------------------------------- proof kernel for rcp_rn_fast / sqrt_rn_fast
-// Enumerates EVERY f32 in [lo, hi] (bit patterns; positive) and counts inputs whose lean result
-// differs bitwise from the correctly rounded 1.0f / x (which == 0) or __builtin_sqrtf(x) (which == 1).
-__global__ __launch_bounds__(FS_BLOCK) void k_verify_unary(int which, uint32_t lo_bits, uint32_t hi_bits,
-                                                           uint32_t* __restrict__ mismatches) {
-    const uint32_t total_threads = gridDim.x * FS_BLOCK;
-    uint32_t bad = 0;
-    for (uint64_t b = (uint64_t)lo_bits + blockIdx.x * FS_BLOCK + threadIdx.x; b <= (uint64_t)hi_bits; b += total_threads) {
-        const float x = __uint_as_float((uint32_t)b);
-        const uint32_t got = __float_as_uint(which == 0 ? rcp_rn_fast(x) : sqrt_rn_fast(x));
-        const uint32_t ref = __float_as_uint(which == 0 ? __fdiv_rn(1.0f, x) : sqrt_rn(x));
-        bad += got != ref ? 1u : 0u;
-    }
-    if (bad) atomicAdd(mismatches, bad);
-}
-
-void launch_verify_unary(hipStream_t st, int which, float lo, float hi, uint32_t* mismatches) {
-    uint32_t lb, hb;
-    memcpy(&lb, &lo, 4);
-    memcpy(&hb, &hi, 4);
-    hipLaunchKernelGGL(k_verify_unary, dim3(256 * 32), dim3(FS_BLOCK), 0, st, which, lb, hb, mismatches);
-}
-
-// ------------------------------------------------------- density-splat image (fluid_shader.wgsl:27-102)
-__device__ __forceinline__ float smoothstep_f(float a, float b, float x) {
-    float t = __fdiv_rn(x - a, b - a);
-    t = fminf(fmaxf(t, 0.0f), 1.0f);
-    return t * t * (3.0f - 2.0f * t);
-}
-
-__global__ __launch_bounds__(FS_BLOCK) void k_render_density(StepParams P, float2 wmin, float2 wmax, uint32_t width,
-                                                             uint32_t height, const float2* __restrict__ pred,
-                                                             const float2* __restrict__ vel,
-                                                             const uint32_t* __restrict__ cs,
-                                                             const uint32_t* __restrict__ start_ref,
-                                                             const u64* __restrict__ pairs, float4* __restrict__ out) {
-    const uint32_t pix = blockIdx.x * FS_BLOCK + threadIdx.x;
-    if (pix >= width * height) return;
-    const uint32_t i = pix % width, j = pix / width;
-    float2 pt;
-    pt.x = wmin.x + __fdiv_rn((float)i + 0.5f, (float)width) * (wmax.x - wmin.x);
-    pt.y = wmin.y + __fdiv_rn((float)j + 0.5f, (float)height) * (wmax.y - wmin.y);
-    const uint32_t lo_fix = quirk_lo_fix(P, pairs, cs, start_ref);
-    uint32_t cx, cy;
-    xy_local(P, pt, &cx, &cy);
-    float density = 0.0f, vfac = 0.0f;
-    const float denom = P.sqr_radius / 2.0f;                            // fluid_shader.wgsl:66
-    for (int oy = -2; oy < 3; ++oy) {                                   // :39-40 (5x5 cells)
-        const uint32_t y = cy + (uint32_t)oy;
-        if (y >= P.grid_h) continue;
-        const int32_t xl = (int32_t)cx - 2, xh = (int32_t)cx + 3;
-        const uint32_t xlo = xl < 0 ? 0u : (uint32_t)xl;
-        const uint32_t xhi = xh > (int32_t)P.grid_w ? P.grid_w : (uint32_t)xh;
-        if (xlo >= xhi) continue;
-        uint32_t a = cs[y * P.grid_w + xlo];
-        const uint32_t b = cs[y * P.grid_w + xhi];
-        if (a == 0u) a = lo_fix;
-        for (uint32_t k = a; k < b; ++k) {
-            const float2 q = pred[k];
-            const float2 v = vel[k];
-            const float ox = q.x - pt.x, oyv = q.y - pt.y;
-            const float r2 = ox * ox + oyv * oyv;
-            const float contrib = expf(__fdiv_rn(-r2, denom));
-            density += contrib;
-            vfac += contrib * sqrt_rn(v.x * v.x + v.y * v.y);           // :68
-        }
-    }
-    vfac = vfac * 0.01f;                                                // :79-83
-    vfac = __fdiv_rn(logf(1.0f + 5.0f * vfac), logf(1.0f + 5.0f));
-    vfac = fminf(fmaxf(vfac, 0.0f), 1.0f);
-    const float interior = smoothstep_f(0.5f, 1.5f, density);           // :86
-    float edge = smoothstep_f(0.7f, 1.0f, density) - smoothstep_f(1.0f, 1.5f, density);
-    edge = edge * (1.0f + vfac * 2.0f);                                 // :89-90
-    const float br = (0.0f * (1.0f - vfac) + 1.0f * vfac) * interior;   // mix(blue, red, vfac) * interior, :93
-    const float bg = (0.5f * (1.0f - vfac) + 0.0f * vfac) * interior;
-    const float bb = (1.0f * (1.0f - vfac) + 0.0f * vfac) * interior;
-    out[pix] = make_float4(br + edge, bg + edge, bb + edge, fminf(fmaxf(interior, 0.0f), 1.0f));
-}
-
-void launch_render_density(hipStream_t st, const StepParams& P, float2 wmin, float2 wmax, uint32_t width,
-                           uint32_t height, const float2* pred, const float2* vel, const uint32_t* cs,
-                           const uint32_t* start_ref, const u64* pairs, float4* out) {
-    const uint32_t npix = width * height;
-    hipLaunchKernelGGL(k_render_density, dim3((npix + FS_BLOCK - 1) / FS_BLOCK), dim3(FS_BLOCK), 0, st, P, wmin, wmax,
-                       width, height, pred, vel, cs, start_ref, pairs, out);
-}
-
-// ------------------------------------------------------------------ launchers
-static inline uint32_t nblk(uint32_t n) { return (n + FS_BLOCK - 1) / FS_BLOCK; }
-static inline uint32_t xcd_grid(uint32_t nb, uint32_t c) {      // blocks to launch for xcd_block() (fs_device.h)
-    const uint32_t chunks = (nb + (1u << c) - 1u) >> c;
-    return (((chunks + 7u) >> 3) << 3) << c;
-}
-
-// The launchers unpack StepArrays in the kernel's parameter order.
-void launch_reorder(hipStream_t st, const StepParams& P, const StepArrays& A, uint32_t work_cap, bool cs_ready) {
-    if (cs_ready) {   // counting sort already produced the dense table
-        hipLaunchKernelGGL(k_reorder<false>, dim3(nblk(P.n)), dim3(FS_BLOCK), 0, st, P, A.pairs, A.pos, A.vel, A.pos_s,
-                           A.vel_s, A.pred, A.key_s, A.cs, A.start_ref, (GapEntry*)A.work, A.counter, work_cap, A.safe, A.fdefer, A.fcount);
-        return;
-    }
-    hipLaunchKernelGGL(k_reorder<true>, dim3(nblk(P.n)), dim3(FS_BLOCK), 0, st, P, A.pairs, A.pos, A.vel, A.pos_s, A.vel_s,
-                       A.pred, A.key_s, A.cs, A.start_ref, (GapEntry*)A.work, A.counter, work_cap, A.safe, A.fdefer, A.fcount);
-    hipLaunchKernelGGL(k_fill_gaps, dim3(1024), dim3(FS_BLOCK), 0, st, A.cs, (const GapEntry*)A.work, A.counter, work_cap);
-}
-
-void launch_density(hipStream_t st, const StepParams& P, const StepArrays& A, uint32_t edge_grid) {
-    static const bool no_mass1 = getenv("FS_NO_MASS1") != nullptr;          // A/B: always the general form
-    const bool tol = P.fast_math == 2, mass1 = P.mass == 1.0f && !tol && !no_mass1;     // (the tolerance form applies the constant factor once anyway)
-#define FS_LAUNCH_DENSITY(K, G)                                                                                        \
-    do {                                                                                                               \
-        if (tol) hipLaunchKernelGGL((K<true, false>), dim3(G), dim3(FS_BLOCK), 0, st, P, A.pred, A.cs, A.start_ref, A.pairs, A.safe, A.rho, A.rho2, A.fdefer, A.fwork, A.fcount); \
-        else if (mass1) hipLaunchKernelGGL((K<false, true>), dim3(G), dim3(FS_BLOCK), 0, st, P, A.pred, A.cs, A.start_ref, A.pairs, A.safe, A.rho, A.rho2, A.fdefer, A.fwork, A.fcount); \
-        else hipLaunchKernelGGL((K<false, false>), dim3(G), dim3(FS_BLOCK), 0, st, P, A.pred, A.cs, A.start_ref, A.pairs, A.safe, A.rho, A.rho2, A.fdefer, A.fwork, A.fcount); \
-    } while (0)
-    if (edge_grid) {   // edge-first slab step: the edge columns' blocks only (k_density_edge)
-        FS_LAUNCH_DENSITY(k_density_edge, edge_grid);
-        return;
-    }
-    const uint32_t nb = nblk(P.n), grid = xcd_grid(nb, P.xcd_chunk_log2);
-    FS_LAUNCH_DENSITY(k_density, grid);
-#undef FS_LAUNCH_DENSITY
-}
-
-void launch_surface_tension(hipStream_t st, const StepParams& P, const StepArrays& A, float sigma, float tau, float cg, float2* st_out) {
-    if (P.n == 0) return;
-    StConsts C;
-    C.h2 = P.sqr_radius;
-    C.cg = cg;
-    C.cl = 2.0f * cg;                                 // 48/(pi h^8): x2 is exact
-    C.sigma = sigma;
-    C.tau = tau;
-    const uint32_t grid = xcd_grid(nblk(P.n), P.xcd_chunk_log2);
-    if (P.mass == 1.0f && !A.rho)
-        hipLaunchKernelGGL(k_surface_tension<true>, dim3(grid), dim3(FS_BLOCK), 0, st, P, C, A.pred, A.rho2, A.rho, A.cs, A.start_ref, A.pairs, st_out);
-    else
-        hipLaunchKernelGGL(k_surface_tension<false>, dim3(grid), dim3(FS_BLOCK), 0, st, P, C, A.pred, A.rho2, A.rho, A.cs, A.start_ref, A.pairs, st_out);
-}
-
 void launch_force(hipStream_t st, const StepParams& P, const StepArrays& A, const ForceLaunch& L) {
     // hipExtLaunchKernelGGL deduces the kernel's parameter types from its arguments: locals of exactly those types
     const float2 *pos_s = A.pos_s, *vel_s = A.vel_s, *pred = A.pred, *rho2 = A.rho2;
@@ -1507,37 +925,6 @@ void launch_force(hipStream_t st, const StepParams& P, const StepArrays& A, cons
 #undef FS_LAUNCH_FORCE_MODE_T
 #undef FS_LAUNCH_FORCE_AOS
 #undef FS_LAUNCH_FORCE
-}
-
-void launch_export_aos(hipStream_t st, uint32_t n, const float2* pos, const float2* pred, const float2* vel,
-                       const float* rho, const uint32_t* key, void* out, const u64* pairs, const float2* rho2) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_export_aos, dim3(nblk(n)), dim3(FS_BLOCK), 0, st, n, pos, pred, vel, rho, key, pairs, rho2,
-                       (AosParticle*)out);
-}
-
-__global__ __launch_bounds__(FS_BLOCK) void k_keys_from_pairs(uint32_t n, const u64* __restrict__ pairs, uint32_t* __restrict__ key,
-                                                              const float2* __restrict__ rho2, float* __restrict__ rho) {
-    const uint32_t i = blockIdx.x * FS_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    if (pairs) key[i] = (uint32_t)(pairs[i] >> 32);
-    if (rho2) rho[i] = rho2[i].x;
-}
-void launch_keys_from_pairs(hipStream_t st, uint32_t n, const u64* pairs, uint32_t* key, const float2* rho2, float* rho) {
-    if (n) hipLaunchKernelGGL(k_keys_from_pairs, dim3(nblk(n)), dim3(FS_BLOCK), 0, st, n, pairs, key, rho2, rho);
-}
-
-void launch_import_aos(hipStream_t st, uint32_t n, const void* in, float2* pos, float2* pred, float2* vel, float* rho,
-                       uint32_t* key) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_import_aos, dim3(nblk(n)), dim3(FS_BLOCK), 0, st, n, (const AosParticle*)in, pos, pred, vel,
-                       rho, key);
-}
-
-size_t gap_entry_size() { return sizeof(GapEntry); }
-
-void launch_fill_gaps(hipStream_t st, uint32_t* cs, const void* work, const uint32_t* counter, uint32_t work_cap) {
-    hipLaunchKernelGGL(k_fill_gaps, dim3(1024), dim3(FS_BLOCK), 0, st, cs, (const GapEntry*)work, counter, work_cap);
 }
 
 }  // namespace fsd

@@ -10,7 +10,7 @@
 //       d = q_k - x, r2 = d.d;  skipped when r2 > h2;  e = h2 - r2;  W = ((Cv e) e) e
 //       density += m W;  t = (m / rho_k) W;  weight += t;  velocity += t v_k;  a_c += t attr_c[k];  neighbours += 1
 // The valid cells of one sweep row are consecutive ids and the slots are in id order, so a row is ONE contiguous slot range
-// [cs[id_lo], cs[id_hi]) of the dense cell-start table, walked ascending: exactly the order above (kernels_step.hip
+// [cs[id_lo], cs[id_hi]) of the dense cell-start table, walked ascending: exactly the order above (fs_neighbours.h
 // "neighbour ranges").  A skipped candidate adds nothing — a branch, not an added zero: the velocity and channel terms can be -0.
 //
 // One lane per query keeps that order for free.  Nothing is staged: scattered points share no candidates.  What decides the
@@ -19,20 +19,9 @@
 // leave the loop together; randomly ordered points make every lane gather from its own lines and every wave wait for its
 // longest row.  The caller chooses the order; nothing is sorted behind its back.
 #include "fs_kernels.h"
+#include "fs_neighbours.h"
 
 namespace fsd {
-
-// kernels_step.hip quirk_lo_fix, restated: the cell of sorted slot 0 never gets its start written, the reference
-// walks it from a stale start v and sees [min(v, cnt), cnt).  A row range that begins at slot 0 begins with that cell.
-__device__ __forceinline__ uint32_t sample_lo_fix(const StepParams& P, const u64* __restrict__ pairs, const uint32_t* __restrict__ cs,
-                                                  const uint32_t* __restrict__ start_ref) {
-    if (!P.ref_quirks) return 0u;
-    const uint32_t cmin = (uint32_t)(pairs[0] >> 32);
-    if (cmin >= P.ncell) return 0u;
-    const uint32_t v = start_ref[cmin];
-    const uint32_t cnt = cs[cmin + 1];
-    return v < cnt ? v : cnt;
-}
 
 struct SampleRec {                 // fs_sample (include/fluidsim.h), 24 bytes
     float density, weight, vx, vy;
@@ -40,7 +29,6 @@ struct SampleRec {                 // fs_sample (include/fluidsim.h), 24 bytes
 };
 static_assert(sizeof(SampleRec) == 24, "fs_sample is 24 bytes");
 
-#define FS_BLOCK 256
 #define FS_SAMPLE_TILE 16u         // GRID: a workgroup takes a 16 x 16 pixel tile (a wave: 16 x 4)
 
 // C: channels (0..4).  GRID: the points are the pixel centres of a view (fs_render_density's expression) instead of loaded.
@@ -70,9 +58,10 @@ __global__ __launch_bounds__(FS_BLOCK) void k_sample(StepParams P, uint32_t nq, 
         if (q >= nq) return;
         x = points[q];
     }
-    const uint32_t lo_fix = sample_lo_fix(P, pairs, cs, start_ref);
+    const uint32_t lo_fix = quirk_lo_fix(P, pairs, cs, start_ref);
     uint32_t cx, cy;
     xy_local(P, x, &cx, &cy);          // P.div_h.ok == 0 (launch_sample): the true division
+    // not row_range (fs_neighbours.h), on purpose: reference-layout ids, only a row's valid columns (a query may lie outside), hi <= n
     // the valid columns of cx-1 .. cx+1: consecutive, also when cx wrapped to 0
     uint32_t xlo = 0u, xn = 0u;
 #pragma unroll

@@ -2,7 +2,7 @@
 // f32 channels per particle that every step permutes exactly as it permutes the particle records.
 //
 // Both sort modes leave, in the low word of pairs[i], the slot that the particle now in slot i held before the step
-// (k_reorder, kernels_step.hip; k_cs_fixreorder, kernels_csort.hip).  k_track_carry gathers through that word once per step:
+// (k_reorder, kernels_reorder.hip; k_cs_fixreorder, kernels_csort.hip).  k_track_carry gathers through that word once per step:
 //     id_out[i] = id_in[src],  attr_out[c][i] = attr_in[c][src]     (bit copies)
 // It reads no simulation state and writes none, so the step computes the same bits with tracking on or off.
 #include <hip/hip_runtime.h>

@@ -187,7 +187,7 @@ typedef unsigned long long u64m;
 // ---- pass masks of one staged z-plane -----------------------------------------------------------------------
 // A 3D row of three cells holds ~24 candidates at rest (8 particles per cell) and passes 32 as soon as the column
 // compresses, so the pass masks are 64 bits, filled as two 32-bit shift registers: v_cmp + one v_addc_co per candidate shift
-// `!(r2 > h^2)` in (see kernels_step.hip force_sweep_masks for the 2D form).  Candidate t of a row ends up at bit 63 - t.
+// `!(r2 > h^2)` in (see kernels_force.hip force_sweep_masks for the 2D form).  Candidate t of a row ends up at bit 63 - t.
 // Valid for waves whose three rows hold <= 64 candidates each; the rows are read from the LDS stage `s_flat`
 // (TILE3_ROW entries per row).  Both the density and the force pass need exactly these masks: k3_density computes
 // them, walks them for its own sum and (Params3::handoff) stores them — 72 B per particle — so that k3_force does not
@@ -524,7 +524,7 @@ __device__ __forceinline__ Terms3 pair3(const Params3& P, float4 me, float4 mv, 
 #endif
 
 // ---- tolerance mode (fs3_create_ex math_mode = FS_MATH_TOLERANCE): the pressure and viscosity terms of one in-radius
-// neighbour merged algebraically, as kernels_step.hip force_accum_tol does in 2D: one v_rsq_f32, fused multiply-adds,
+// neighbour merged algebraically, as kernels_force.hip force_accum_tol does in 2D: one v_rsq_f32, fused multiply-adds,
 // 1/rho_j from the density pass (vel_s.w), ~32 issue slots per pair instead of ~95.  Coincident particles keep the
 // oracle's xorshift direction.
 struct Tol3 { float cP, c3, c2, hh, kp0; };
@@ -570,7 +570,7 @@ __device__ __forceinline__ void pair3_accum(const Params3& P, const Tol3& C, flo
     else acc3_add(A, pair3(P, me, mv, pressure, q, nv, A));
 }
 
-// Mask sweep of one staged z-plane (see kernels_step.hip force_sweep_masks): every lane walks the set bits of its three
+// Mask sweep of one staged z-plane (see kernels_force.hip force_sweep_masks): every lane walks the set bits of its three
 // 64-bit pass masks, row 0, 1, 2, ascending — the oracle's visiting order.  The masks come from k3_density
 // (Params3::handoff, `masks` != nullptr: three coalesced 8-byte loads) or from a scan of the staged plane.
 // `self_plane`: the lane's own particle sits in row 1 of the middle plane and is skipped (k != i).
@@ -685,7 +685,7 @@ __device__ __forceinline__ void sweep3_masks128(const Params3& P, const Tol3& C,
 
 // General sweep of three rows (one z-plane) for waves that hold a row longer than 64 candidates, or whose
 // plane does not fit the LDS tile: the same machinery one 32-candidate chunk of one row at a time (see
-// kernels_step.hip force_sweep_chunks) — wave-uniform scan into a 32-bit mask, pipelined walk.  Rows and
+// kernels_force.hip force_sweep_chunks) — wave-uniform scan into a 32-bit mask, pipelined walk.  Rows and
 // chunks in order = the oracle's visiting order.  STAGED: candidates from the LDS tile, else from global
 // memory (pred is allocated with FS_PRED_SLACK elements of slack for the read-ahead).
 template <bool STAGED, int MODE>
@@ -704,7 +704,7 @@ __device__ __forceinline__ void sweep3_chunks(const Params3& P, const Tol3& C, c
         const uint32_t b0 = r == 0 ? b00 : r == 1 ? b01 : b02;
         const uint32_t len = hi - lo;
         // FS3_CHUNK_BATCH chunks of 32 candidates are scanned before the walk starts and their masks are walked as one shift
-        // register (kernels_step.hip force_sweep_chunks: a lane then waits for the wave's slowest lane once per 128
+        // register (kernels_force.hip force_sweep_chunks: a lane then waits for the wave's slowest lane once per 128
         // candidates instead of once per 32); the chunks of a batch are consecutive in the row, a refill advances the bases
 #pragma unroll 1
         for (uint32_t c0 = 0; __any(c0 < len); c0 += 32u * FS3_CHUNK_BATCH) {   // c0 is wave-uniform
@@ -835,7 +835,7 @@ __device__ __forceinline__ void force3_body(const Params3& P, const float4* __re
     v.x += P.gx * P.dt; v.y += P.gy * P.dt; v.z += P.gz * P.dt;
     if (!(v.x == v.x && v.y == v.y && v.z == v.z)) { v.x = 0.0f; v.y = 0.0f; v.z = 0.0f; }
     const float s2 = v.x * v.x + v.y * v.y + v.z * v.z;
-    if (s2 > 249000.0f) {                           // below that the root is < 500 whatever the rounding: no clamp (kernels_step.hip)
+    if (s2 > 249000.0f) {                           // below that the root is < 500 whatever the rounding: no clamp (kernels_force.hip)
         const float speed = sqrt_rn(s2);
         if (speed > 500.0f) {
             v.x = __fdiv_rn(v.x, speed) * 500.0f; v.y = __fdiv_rn(v.y, speed) * 500.0f; v.z = __fdiv_rn(v.z, speed) * 500.0f;

@@ -163,3 +163,9 @@ def test_build_recipe_lists_every_included_header():
     assert not missing, f"included under csrc/ but not in build.py HEADERS: {missing}"
     assert all(os.path.exists(p) for p in listed), "build.py lists a header that does not exist"
     assert set(os.listdir(b.CSRC)) >= set(b.SOURCES), "build.py lists a source that does not exist"
+    # and the other way round: a csrc/*.hip that is not built, or a csrc/*.h whose edits trigger no rebuild
+    on_disk = sorted(os.listdir(b.CSRC))
+    unbuilt = [n for n in on_disk if n.endswith(".hip") and n not in b.SOURCES]
+    assert not unbuilt, f"under csrc/ but not in build.py SOURCES: {unbuilt}"
+    unlisted = [n for n in on_disk if n.endswith(".h") and n not in b.HEADERS]
+    assert not unlisted, f"under csrc/ but not in build.py HEADERS: {unlisted}"
