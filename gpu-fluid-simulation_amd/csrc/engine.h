@@ -1,6 +1,6 @@
 // engine.h — what the host files of the C ABI share beyond fs_host.h: the 2D simulation handle (engine.hip: the plain handle,
 // the opt-in features, the self-tests; engine_slab.hip: the multi-GPU slab handles), the step parameters, and the create-time
-// device check and proofs (also used by sim3d.hip).  Internal: include/fluidsim.h is the interface.
+// device check and proofs (also used by engine_3d.hip).  Internal: include/fluidsim.h is the interface.
 #pragma once
 #include <hip/hip_runtime.h>
 

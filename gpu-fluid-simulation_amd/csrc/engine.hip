@@ -65,7 +65,7 @@ void host_lattice(const fs_settings& s, fs_vec2 off, fs_particle* dst, size_t n)
 
 }  // namespace
 
-// ---- shared with engine_slab.hip and sim3d.hip (engine.h) ------------------------------------------------------------
+// ---- shared with engine_slab.hip and engine_3d.hip (engine.h) --------------------------------------------------------
 // src/simulation.rs:140-141
 void fsd::grid_dims(const fs_settings& s, uint32_t* gw, uint32_t* gh) {
     *gw = (uint32_t)((size_t)std::ceil(s.size.x / s.smoothing_radius) + 2);

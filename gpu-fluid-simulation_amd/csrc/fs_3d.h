@@ -1,0 +1,67 @@
+// fs_3d.h — what the two files of the 3D step share (kernels_3d.hip: the kernels and their launchers, engine_3d.hip: the
+// handle and the fs3_* C ABI): the step parameters, the array set of the launchers, the launchers.  A header of its own:
+// fs_kernels.h stays the 2D launchers' list, and kernels_sort.hip takes the predict + cell-key expression from here.
+#pragma once
+#include "fs_kernels.h"
+
+namespace fsd {
+
+struct Params3 {
+    uint32_t n, gw, gh, gd, ncell;
+    float dt, h, h2;
+    float bx, by, bz;            // bounds * 0.5
+    float mass, poly6, pressure_k, rest_density, damping, visc_coeff, spiky, visc_k;
+    float gx, gy, gz;
+    uint32_t frame;
+    ConstDiv div_2h3, div_h2;    // exact constant divisions, proven at create (fs_device.h div_const)
+    int32_t share_div;           // one reciprocal per denominator + div_by_rcp in the force pass (fs_device.h)
+    int32_t handoff;             // k3_density stores its nine 64-bit pass masks per particle, k3_force walks them (no second scan)
+    uint32_t xcd_chunk_log2;     // xcd_block3(): blocks per chunk dealt to one XCD
+};
+
+// The device arrays of a 3D handle as the launchers see them (fs_kernels.h StepArrays is the 2D form).  Host side only.
+struct Arrays3 {
+    float4* pos = nullptr;             // state before the step, source order (the order of the last step)
+    float4* vel = nullptr;             // ... the force pass writes the new velocities over it
+    float4* pos_out = nullptr;         // the spare position buffer: the force pass's new positions
+    float4* vel_s = nullptr;           // sorted {vx, vy, vz, +-RN(1/rho)}: the sign is the particle's safe-operand classification
+    float4* pred = nullptr;            // sorted predicted positions, .w = density; + FS_PRED_SLACK entries
+    uint32_t* key = nullptr;           // sorted keys
+    u64* pairs = nullptr;              // sorted (key << 32 | source slot)
+    uint32_t* cs = nullptr;            // dense cell-start table, ncell + 1
+    u64* masks = nullptr;              // 18 x n pass masks, k3_density -> k3_force (Params3::handoff), or nullptr
+    void* work = nullptr;              // the gap worklist of the reorder pass ...
+    uint32_t* counter = nullptr;       // ... and its counter
+    uint32_t work_cap = 0;
+    void* aos = nullptr;               // n fs3_particle records: import / export staging
+};
+
+// Predict + cell key of the 3D step, defined once for k3_predict_key, k3_reorder (kernels_3d.hip) and the sort's fused key
+// generation (kernels_sort.hip keygen3).  K: anything with dt, h, bx, by, bz, gw, gh (Params3, KeyGen3).
+template <class K>
+__device__ __forceinline__ float4 predict3(const K& P, float4 p, float4 v) {
+    float4 r;
+    r.x = p.x + v.x * P.dt; r.y = p.y + v.y * P.dt; r.z = p.z + v.z * P.dt; r.w = 0.0f;
+    if (fabsf(r.x) > P.bx) r.x = P.bx * sign_f32(r.x);
+    if (fabsf(r.y) > P.by) r.y = P.by * sign_f32(r.y);
+    if (fabsf(r.z) > P.bz) r.z = P.bz * sign_f32(r.z);
+    return r;
+}
+template <class K>
+__device__ __forceinline__ uint32_t cell_key3(const K& P, float4 pt) {
+    const uint32_t cx = f32_to_u32_sat(floorf(__fdiv_rn(pt.x + P.bx, P.h))) + 1u;
+    const uint32_t cy = f32_to_u32_sat(floorf(__fdiv_rn(pt.y + P.by, P.h))) + 1u;
+    const uint32_t cz = f32_to_u32_sat(floorf(__fdiv_rn(pt.z + P.bz, P.h))) + 1u;
+    return (cz * P.gh + cy) * P.gw + cx;
+}
+
+uint32_t blocks3(uint32_t n);          // workgroups of the density / force kernels over n particles (before xcd_block3's padding)
+void launch3_predict_key(hipStream_t st, const Params3& P, const Arrays3& A);   // FS3_SEPARATE_KEYGEN: else fused into the sort
+void launch3_reorder(hipStream_t st, const Params3& P, const Arrays3& A);       // + launch_fill_gaps
+void launch3_density(hipStream_t st, const Params3& P, const Arrays3& A, bool tol);
+// done (may be null): signalled by the kernel's completion
+void launch3_force(hipStream_t st, const Params3& P, const Arrays3& A, bool tol, hipEvent_t done);
+void launch3_import(hipStream_t st, uint32_t n, const Arrays3& A);   // aos -> pos, pred, vel, key
+void launch3_export(hipStream_t st, uint32_t n, const Arrays3& A);   // ... and back
+
+}  // namespace fsd

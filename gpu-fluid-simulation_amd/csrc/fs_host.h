@@ -1,6 +1,7 @@
-// fs_host.h — what the host files of the C ABI (engine.hip, sim3d.hip) share: the last-error helper, the HIP error
-// macro, and the owners of a handle's device arrays, streams, events and per-pass event ring.  Every owner frees what
-// it holds in its destructor, so a handle is torn down by `delete` alone (members go in reverse order of declaration).
+// fs_host.h — what the host files of the C ABI (engine.hip, engine_slab.hip, engine_3d.hip) share: the last-error
+// helper, the HIP error macro, and the owners of a handle's device arrays, streams, events and per-pass event ring.
+// Every owner frees what it holds in its destructor, so a handle is torn down by `delete` alone (members go in reverse
+// order of declaration).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

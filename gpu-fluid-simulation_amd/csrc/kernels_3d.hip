@@ -1,5 +1,5 @@
-// sim3d.hip — 3D extension of the step (27-cell neighbour path).  NOT in the reference (2D
-// only); build-defined per SURVEY.md Appendix B.3, normative statement oracle/sph_oracle3d.cpp.
+// kernels_3d.hip — kernels of the 3D extension of the step (27-cell neighbour path) and their launchers (fs_3d.h).  NOT in the
+// reference (2D only); build-defined per SURVEY.md Appendix B.3, normative statement oracle/sph_oracle3d.cpp.
 // Same pass chain as 2D: predict+key -> bitonic (key,index) sort -> reorder + dense cell
 // starts -> density -> force+integrate.  SoA with 16-byte lanes: pos4 / vel4 / pred4 (xyz,
 // pred.w carries the density for the force pass), so a neighbour is two 16-B loads.
@@ -8,35 +8,12 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <new>
-#include <string>
-#include <vector>
-
 #include "../../include/fluidsim.h"
-#include "engine.h"
+#include "fs_3d.h"
 
 static_assert(sizeof(fs3_particle) == 48, "fs3_particle is 48 bytes");
 
 namespace fsd {
-
-void set_last_error(const std::string& msg);   // engine.hip
-
-struct Params3 {
-    uint32_t n, gw, gh, gd, ncell;
-    float dt, h, h2;
-    float bx, by, bz;            // bounds * 0.5
-    float mass, poly6, pressure_k, rest_density, damping, visc_coeff, spiky, visc_k;
-    float gx, gy, gz;
-    uint32_t frame;
-    ConstDiv div_2h3, div_h2;    // exact constant divisions, proven at create (fs_device.h div_const)
-    int32_t share_div;           // one reciprocal per denominator + div_by_rcp in the force pass (fs_device.h)
-    int32_t handoff;             // k3_density stores its nine 64-bit pass masks per particle, k3_force walks them (no second scan)
-    uint32_t xcd_chunk_log2;     // xcd_block3(): blocks per chunk dealt to one XCD
-};
 
 // Workgroup -> block of particles for the density / force kernels, XCD-aware as in 2D (fs_device.h xcd_block): the
 // hardware deals consecutive workgroup ids round-robin to the 8 XCDs, and a block's nine sweep rows are the rows of the
@@ -57,29 +34,13 @@ static inline uint32_t xcd_grid3(uint32_t nb, uint32_t c) {
 
 #define B3 256
 
-__device__ __forceinline__ float4 predict3(const Params3& P, float4 p, float4 v) {
-    float4 r;
-    r.x = p.x + v.x * P.dt; r.y = p.y + v.y * P.dt; r.z = p.z + v.z * P.dt; r.w = 0.0f;
-    if (fabsf(r.x) > P.bx) r.x = P.bx * sign_f32(r.x);
-    if (fabsf(r.y) > P.by) r.y = P.by * sign_f32(r.y);
-    if (fabsf(r.z) > P.bz) r.z = P.bz * sign_f32(r.z);
-    return r;
-}
-__device__ __forceinline__ void cell3(const Params3& P, float4 pt, uint32_t* cx, uint32_t* cy, uint32_t* cz) {
-    *cx = f32_to_u32_sat(floorf(__fdiv_rn(pt.x + P.bx, P.h))) + 1u;
-    *cy = f32_to_u32_sat(floorf(__fdiv_rn(pt.y + P.by, P.h))) + 1u;
-    *cz = f32_to_u32_sat(floorf(__fdiv_rn(pt.z + P.bz, P.h))) + 1u;
-}
-
 __global__ __launch_bounds__(B3) void k3_predict_key(Params3 P, const float4* __restrict__ pos,
                                                      const float4* __restrict__ vel, u64* __restrict__ pairs,
                                                      uint32_t* __restrict__ gap_counter) {
     const uint32_t i = blockIdx.x * B3 + threadIdx.x;
     if (i == 0) *gap_counter = 0;
     if (i >= P.n) return;
-    uint32_t cx, cy, cz;
-    cell3(P, predict3(P, pos[i], vel[i]), &cx, &cy, &cz);
-    pairs[i] = ((u64)((cz * P.gh + cy) * P.gw + cx) << 32) | (u64)i;
+    pairs[i] = ((u64)cell_key3(P, predict3(P, pos[i], vel[i])) << 32) | (u64)i;
 }
 
 __global__ __launch_bounds__(B3) void k3_reorder(Params3 P, const u64* __restrict__ pairs,
@@ -114,25 +75,11 @@ __global__ __launch_bounds__(B3) void k3_reorder(Params3 P, const u64* __restric
     if (i == P.n - 1) fill_cells(cs, kc + 1u, P.ncell + 1u, P.n, work, counter, work_cap);
 }
 
-// row j in 0..8 -> (oz, oy) = (j/3 - 1, j%3 - 1); false when the row is outside the grid
-__device__ __forceinline__ bool row3(const Params3& P, const uint32_t* __restrict__ cs, uint32_t cx, uint32_t cy,
-                                     uint32_t cz, int j, uint32_t* lo, uint32_t* hi) {
-    const uint32_t y = cy + (uint32_t)(j % 3 - 1), z = cz + (uint32_t)(j / 3 - 1);
-    if (y >= P.gh || z >= P.gd) return false;
-    const uint32_t xlo = cx - 1u;                         // cx >= 1 always
-    uint32_t xhi = cx + 2u;                               // exclusive; cells past the row end do not exist
-    if (xhi > P.gw) xhi = P.gw;
-    const uint32_t base = (z * P.gh + y) * P.gw;
-    *lo = cs[base + xlo];
-    *hi = cs[base + xhi];
-    return *lo < *hi;
-}
-
-// The same row from the particle's KEY (round 3): cells (cx-1 .. cx+1, cy+oy, cz+oz) are the ids key + (oz gh + oy) gw - 1 .. + 2,
-// so the density and force passes need no cell coordinates (three IEEE divisions per particle in cell3) — only the stored
-// key.  Equivalent to row3 for every reachable key: cell index 0 of every row / plane is padding and always empty
-// (coordinates are floor(..) + 1 >= 1), so a row that wraps into the next row or plane reads an empty range exactly where
-// row3 says "outside the grid", and ids past the table are cut off here.
+// Sweep row j in 0..8, (oz, oy) = (j/3 - 1, j%3 - 1), from the particle's KEY: cells (cx-1 .. cx+1, cy+oy, cz+oz) are the ids
+// key + (oz gh + oy) gw - 1 .. + 2, so the density and force passes need no cell coordinates (three IEEE divisions per
+// particle) — only the stored key.  Cell index 0 of every row / plane is padding and always empty (coordinates are
+// floor(..) + 1 >= 1), so a row that wraps into the next row or plane reads an empty range exactly where the row is outside
+// the grid, and ids past the table are cut off here.  false: no candidates.
 __device__ __forceinline__ bool row3_key(const Params3& P, const uint32_t* __restrict__ cs, uint32_t key, int j,
                                          uint32_t* lo, uint32_t* hi) {
     const int32_t off = ((j / 3 - 1) * (int32_t)P.gh + (j % 3 - 1)) * (int32_t)P.gw - 1;      // scalar
@@ -144,6 +91,16 @@ __device__ __forceinline__ bool row3_key(const Params3& P, const uint32_t* __res
     return *lo < *hi;
 }
 
+// All 18 cell-start look-ups of a particle's nine sweep rows up front: independent loads, one latency.  Empty row: lo = hi = 0.
+__device__ __forceinline__ void rows3_lookup(const Params3& P, const uint32_t* __restrict__ cs, uint32_t key, bool live,
+                                             uint32_t* lo9, uint32_t* hi9) {
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+        lo9[j] = 0; hi9[j] = 0;
+        if (live && !row3_key(P, cs, key, j, &lo9[j], &hi9[j])) { lo9[j] = 0; hi9[j] = 0; }
+    }
+}
+
 __device__ __forceinline__ float dens3(const Params3& P, float4 me, float4 q) {
     const float dx = q.x - me.x, dy = q.y - me.y, dz = q.z - me.z;
     const float r2 = dx * dx + dy * dy + dz * dz;
@@ -152,37 +109,33 @@ __device__ __forceinline__ float dens3(const Params3& P, float4 me, float4 q) {
     return P.mass * kern * 1.0f;
 }
 
-// Workgroup of the density / force kernels: 256 threads.  -DB3F=64 (one wave per workgroup: no barrier couples waves with
-// different neighbour counts, each wave stages its own 10-cell rows) was measured and is SLOWER — density 0.93 -> 1.11 ms,
-// force 1.94 -> 2.14 ms at 8 M (profiles/r03_rejected.md): the kernels' waiting is not barrier skew.
-#ifndef B3F
-#define B3F 256
-#endif
+#define B3F 256              // workgroup of the density / force kernels (one wave per workgroup is slower: profiles/r03_rejected.md)
 #define W3F (B3F / 64)
-#if B3F == 256
-#ifndef TILE3
 #define TILE3 400            // staged candidates per sweep row; one z-plane (3 rows) is staged at a time.  8 M, steps 10-110, strict / tolerance step: 352: 3.30 / 2.70, 384: 3.21 / 2.60, 400: 3.18 / 2.56, 408: 3.18 / 2.56 ms (408 is the most four workgroups per CU have room for)
-#endif
 #define TILE3_ROW TILE3      // rows 0 and 1 over-read into the next row's stage (masked off), only the last row needs the slack
-#else
-#define TILE3 96             // a wave's row at rest: 10 cells x 8 particles; longer rows take the unstaged chunked sweep
-#define TILE3_ROW TILE3      // rows 0 and 1 over-read into the next row's stage, only the last row needs the slack below
-#endif
 #define TILE3_PAD 72u        // the wave-uniform scan reads up to the wave's longest row (<= 64) + 3 past a lane's own range
 #define TILE3_LDS (3 * TILE3_ROW + TILE3_PAD)
 // k3_force stages the neighbours' VELOCITY records {vx, vy, vz, +-1/rho} behind the positions, same row pitch: the walk's
 // second fetch is then an LDS read at a constant offset from the first instead of a 16-byte gather per neighbour (with the
 // masks handed over the kernel was bound by exactly those gathers: waves parked 65 - 79 %, profiles/r03_counters_3d*.md).
 // 19.6 + 18.4 KB per workgroup: four workgroups (16 waves) per CU.
-#ifndef FS3_STAGE_VEL
-#define FS3_STAGE_VEL 1
-#endif
-#ifndef FS3_CHUNK_BATCH
-#define FS3_CHUNK_BATCH 4    // 32-candidate chunks scanned per walk in the chunked sweep (2 .. 4)
-#endif
 #define TILE3_VEL_OFF (TILE3_LDS * 16u)          // bytes from a staged position to the same candidate's velocity
-#define TILE3_FORCE_LDS (TILE3_LDS + (FS3_STAGE_VEL ? 3 * TILE3_ROW : 0))
+#define TILE3_FORCE_LDS (TILE3_LDS + 3 * TILE3_ROW)
 typedef unsigned long long u64m;
+
+// One z-plane of the sweep that fits the tile, staged for the workgroup: the three rows [blo, bhi) into s_flat with coalesced
+// loads — positions, and with VEL the velocity records TILE3_LDS entries behind them — and a barrier.
+template <bool VEL>
+__device__ __forceinline__ void stage3_rows(const uint32_t* blo, const uint32_t* bhi, const float4* pred, const float4* vel_s,
+                                            float4* s_flat) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+        for (uint32_t j = threadIdx.x; j < bhi[r] - blo[r]; j += B3F) {
+            s_flat[r * TILE3_ROW + j] = pred[blo[r] + j];
+            if (VEL) s_flat[TILE3_LDS + r * TILE3_ROW + j] = vel_s[blo[r] + j];
+        }
+    __syncthreads();
+}
 
 // ---- pass masks of one staged z-plane -----------------------------------------------------------------------
 // A 3D row of three cells holds ~24 candidates at rest (8 particles per cell) and passes 32 as soon as the column
@@ -195,90 +148,79 @@ typedef unsigned long long u64m;
 __device__ __forceinline__ void shift_in_not_greater32(uint32_t& mask, float r2, float lim) {
     asm("v_cmp_nlt_f32 vcc, %2, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mask) : "v"(r2), "s"(lim) : "vcc");
 }
+// Where a lane's row r starts in the staged plane, and the bits of a pass mask that are the lane's own `len` candidates
+// (candidate k at bit 63 - k; rows of up to 128: candidates 0 .. 63 in the hi word, 64 .. 127 in the lo word).
+__device__ __forceinline__ uint32_t row_la(const RowRanges& R, const uint32_t* blo, int r) {
+    const uint32_t len = R.hi[r] - R.lo[r];
+    return (uint32_t)r * TILE3_ROW + (len ? R.lo[r] - blo[r] : 0u);
+}
+__device__ __forceinline__ u64m keep64(uint32_t len) { return len ? ~0ull << (64u - len) : 0ull; }            // len <= 64
+__device__ __forceinline__ u64m keep128_hi(uint32_t len) { return len >= 64u ? ~0ull : keep64(len); }
+__device__ __forceinline__ u64m keep128_lo(uint32_t len) { return len > 64u ? ~0ull << (128u - len) : 0ull; }   // len <= 128
+// Candidates t, t + 1, .. of the staged row `base` shifted into the 32-bit register `w`, four at a time, until t reaches
+// `limit` or no lane of the wave has candidates left (t is wave-uniform: scalar branches).  Reads up to 3 entries past the
+// wave's longest row.
+__device__ __forceinline__ void scan3_word(uint32_t& w, uint32_t& t, uint32_t limit, const float4* base, uint32_t len, float4 me,
+                                           float lim) {
+    for (; t < limit && __any(t < len); t += 4u) {
+        const float4 q0 = base[t], q1 = base[t + 1u], q2 = base[t + 2u], q3 = base[t + 3u];
+        const float4 qq[4] = {q0, q1, q2, q3};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float ox = qq[u].x - me.x, oy = qq[u].y - me.y, oz = qq[u].z - me.z;
+            shift_in_not_greater32(w, ox * ox + oy * oy + oz * oz, lim);
+        }
+    }
+}
 __device__ __forceinline__ void scan3_plane(const Params3& P, const RowRanges& R, const uint32_t* blo, float4 me,
                                             const float4* s_flat, u64m m[3], uint32_t la[3]) {
     const float lim = P.h2;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
         const uint32_t len = R.hi[r] - R.lo[r];                           // <= 64 (caller)
-        la[r] = (uint32_t)r * TILE3_ROW + (len ? R.lo[r] - blo[r] : 0u);
+        la[r] = row_la(R, blo, r);
         const float4* base = s_flat + la[r];
         uint32_t mlo = 0, mhi = 0, t = 0;
         // Two 32-bit shift registers, one v_addc_co per candidate (the 64-bit form needs two): candidates 0 .. 31 go
-        // through `mhi`, the rest through `mlo`; t is wave-uniform, so the switch is a scalar branch.
-        for (; t < 32u && __any(t < len); t += 4u) {
-            const float4 q0 = base[t], q1 = base[t + 1u], q2 = base[t + 2u], q3 = base[t + 3u];
-            const float4 qq[4] = {q0, q1, q2, q3};
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float ox = qq[u].x - me.x, oy = qq[u].y - me.y, oz = qq[u].z - me.z;
-                shift_in_not_greater32(mhi, ox * ox + oy * oy + oz * oz, lim);
-            }
-        }
+        // through `mhi`, the rest through `mlo` (len <= 64: the second limit never binds)
+        scan3_word(mhi, t, 32u, base, len, me, lim);
         const uint32_t ta = t;                                            // <= 32: candidates that went through mhi
-        for (; __any(t < len); t += 4u) {
-            const float4 q0 = base[t], q1 = base[t + 1u], q2 = base[t + 2u], q3 = base[t + 3u];
-            const float4 qq[4] = {q0, q1, q2, q3};
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float ox = qq[u].x - me.x, oy = qq[u].y - me.y, oz = qq[u].z - me.z;
-                shift_in_not_greater32(mlo, ox * ox + oy * oy + oz * oz, lim);
-            }
-        }
+        scan3_word(mlo, t, 64u, base, len, me, lim);
         {   // candidate k sits at bit 63 - k: left-align each half, keep the lane's own len candidates
             const uint32_t hi32 = ta ? mhi << (32u - ta) : 0u;
             const uint32_t lo32 = t > ta ? mlo << (32u - (t - ta)) : 0u;
             u64m mask = ((u64m)hi32 << 32) | lo32;
-            mask &= len ? ~0ull << (64u - len) : 0ull;
+            mask &= keep64(len);
             m[r] = mask;
         }
     }
 }
-// Is the mask form available for this wave's plane?  k3_density and k3_force must agree, so both call this with the
-// RowRanges / block bounds they derive from the same cell table.
-__device__ __forceinline__ bool plane_masked(const RowRanges& R, bool fit) {
-    const bool long_row = R.hi[0] - R.lo[0] > 64u || R.hi[1] - R.lo[1] > 64u || R.hi[2] - R.lo[2] > 64u;
-    return fit && !__any(long_row);
-}
-
 // Rows of 65 .. 128 candidates (the compressing column: 5 % of the waves at step 60, 12 - 14 % from step 80 on,
 // tools/rows3d_stats.py): the same hand-off with TWO 64-bit words per row — candidates 0 .. 63 in `hi` (stored in
-// masks[0 .. 9n)), 64 .. 127 in `lo` (masks[9n .. 18n)).  plane_class(): 1 = every row of the wave <= 64 (plane_masked),
-// 2 = every row <= 128, 0 = the chunked sweep.  k3_density and k3_force call it with the same ranges.
-#ifndef FS3_MASK128
-#define FS3_MASK128 1
-#endif
+// masks[0 .. 9n)), 64 .. 127 in `lo` (masks[9n .. 18n)).  plane_class(): 1 = every row of the wave <= 64, 2 = every row <= 128,
+// 0 = the chunked sweep.  k3_density and k3_force must agree, so both call it with the RowRanges / block bounds they derive
+// from the same cell table.
 __device__ __forceinline__ int plane_class(const RowRanges& R, bool fit) {
     const uint32_t l0 = R.hi[0] - R.lo[0], l1 = R.hi[1] - R.lo[1], l2 = R.hi[2] - R.lo[2];
     const uint32_t mx = l0 > l1 ? (l0 > l2 ? l0 : l2) : (l1 > l2 ? l1 : l2);
     if (!fit) return 0;
     if (!__any(mx > 64u)) return 1;
-    return (FS3_MASK128 && !__any(mx > 128u)) ? 2 : 0;
+    return !__any(mx > 128u) ? 2 : 0;
 }
 // One row of up to 128 candidates into four 32-bit shift registers (t is wave-uniform: the switches are scalar branches).
 __device__ __forceinline__ void scan3_row128(const Params3& P, const float4* base, uint32_t len, float4 me, u64m* hi, u64m* lo) {
     const float lim = P.h2;
     uint32_t w0 = 0u, w1 = 0u, w2 = 0u, w3 = 0u, t = 0u;
-#define FS3_SCAN32(W, LIMIT)                                                                                          \
-    for (; t < (LIMIT) && __any(t < len); t += 4u) {                                                                  \
-        const float4 q0 = base[t], q1 = base[t + 1u], q2 = base[t + 2u], q3 = base[t + 3u];                           \
-        const float4 qq[4] = {q0, q1, q2, q3};                                                                        \
-        _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                               \
-            const float ox = qq[u].x - me.x, oy = qq[u].y - me.y, oz = qq[u].z - me.z;                                \
-            shift_in_not_greater32(W, ox * ox + oy * oy + oz * oz, lim);                                              \
-        }                                                                                                             \
-    }
-    FS3_SCAN32(w0, 32u) const uint32_t t0 = t;
-    FS3_SCAN32(w1, 64u) const uint32_t t1 = t;
-    FS3_SCAN32(w2, 96u) const uint32_t t2 = t;
-    FS3_SCAN32(w3, 128u)
-#undef FS3_SCAN32
+    scan3_word(w0, t, 32u, base, len, me, lim); const uint32_t t0 = t;
+    scan3_word(w1, t, 64u, base, len, me, lim); const uint32_t t1 = t;
+    scan3_word(w2, t, 96u, base, len, me, lim); const uint32_t t2 = t;
+    scan3_word(w3, t, 128u, base, len, me, lim);
     // candidate c of the row sits at bit 31 - (c & 31) of word c / 32: left-align each word by the candidates it took
     const uint32_t a0 = t0 ? w0 << (32u - t0) : 0u, a1 = t1 > t0 ? w1 << (32u - (t1 - t0)) : 0u;
     const uint32_t a2 = t2 > t1 ? w2 << (32u - (t2 - t1)) : 0u, a3 = t > t2 ? w3 << (32u - (t - t2)) : 0u;
     u64m h = ((u64m)a0 << 32) | a1, l = ((u64m)a2 << 32) | a3;
-    h &= len >= 64u ? ~0ull : (len ? ~0ull << (64u - len) : 0ull);
-    l &= len > 64u ? ~0ull << (128u - len) : 0ull;      // len <= 128
+    h &= keep128_hi(len);
+    l &= keep128_lo(len);
     *hi = h; *lo = l;
 }
 
@@ -289,24 +231,27 @@ __device__ __forceinline__ float dens3_tol(const Params3& P, float4 me, float4 q
     return __builtin_fmaf(t * t, t, acc);
 }
 
+// The density terms of the set bits of one pass mask, ascending (bit 63 - t = candidate base[t]).
+template <int MODE>
+__device__ __forceinline__ void walk_density(const Params3& P, u64m mask, const float4* base, float4 me, float& rho) {
+    while (mask) {
+        const uint32_t t = (uint32_t)__builtin_clzll(mask);
+        mask ^= 0x8000000000000000ull >> t;
+        if (MODE == 2) rho = dens3_tol(P, me, base[t], rho);
+        else rho += dens3(P, me, base[t]);
+    }
+}
+
 // The 27-cell sweep runs plane by plane (z outer): per plane the workgroup's three row ranges are
 // staged into LDS with coalesced loads (fs_device.h block_tile_bounds).  Waves whose rows fit the 64-bit masks
 // scan the plane into masks and add the terms of the set bits (row 0, 1, 2, ascending: the oracle's order — the
 // candidates outside the radius contribute +0 there, which changes no bit of a non-negative sum); other waves loop
 // over their candidates directly.  MODE 2 (FS_MATH_TOLERANCE): FMA terms, the constant applied once.
-#ifndef FS3_DENSITY_WAVES
-#define FS3_DENSITY_WAVES 0   // > 0: pin the register budget (A/B: tools/ab_variant3d.py)
-#endif
-#if FS3_DENSITY_WAVES > 0
-#define FS3_DENSITY_ATTR __attribute__((amdgpu_waves_per_eu(FS3_DENSITY_WAVES, FS3_DENSITY_WAVES)))
-#else
-#define FS3_DENSITY_ATTR
-#endif
 template <int MODE>
-__global__ __launch_bounds__(B3F) FS3_DENSITY_ATTR void k3_density(Params3 P, float4* __restrict__ pred, const uint32_t* __restrict__ cs,
+__global__ __launch_bounds__(B3F) void k3_density(Params3 P, float4* __restrict__ pred, const uint32_t* __restrict__ cs,
                                                  float4* __restrict__ vel_s, u64m* __restrict__ masks,
                                                  const uint32_t* __restrict__ key_s) {
-    __shared__ float4 s_pred[TILE3_LDS + (FS3_MASK128 ? 64 : 0)];   // a 128-candidate scan reads up to 131 entries from a range start
+    __shared__ float4 s_pred[TILE3_LDS + 64];   // a 128-candidate scan reads up to 131 entries from a range start
     __shared__ uint32_t s_red[24];
     uint32_t blk;
     if (!xcd_block3(P, (P.n + B3F - 1) / B3F, &blk)) return;       // uniform
@@ -315,12 +260,8 @@ __global__ __launch_bounds__(B3F) FS3_DENSITY_ATTR void k3_density(Params3 P, fl
     const float4 me = pred[live ? i : P.n - 1];
     const uint32_t key = key_s[live ? i : P.n - 1];
     float rho = 0.0f;
-    uint32_t lo9[9], hi9[9];        // all 18 cell-start lookups up front: independent loads, one latency
-#pragma unroll
-    for (int j = 0; j < 9; ++j) {
-        lo9[j] = 0; hi9[j] = 0;
-        if (live && !row3_key(P, cs, key, j, &lo9[j], &hi9[j])) { lo9[j] = 0; hi9[j] = 0; }
-    }
+    uint32_t lo9[9], hi9[9];
+    rows3_lookup(P, cs, key, live, lo9, hi9);
 #pragma unroll 1
     for (int plane = 0; plane < 3; ++plane) {
         RowRanges R;
@@ -332,34 +273,21 @@ __global__ __launch_bounds__(B3F) FS3_DENSITY_ATTR void k3_density(Params3 P, fl
         uint32_t blo[3], bhi[3];
         const bool fit = block_tile_bounds<W3F>(R, s_red, blo, bhi, TILE3);
         if (fit) {
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-                for (uint32_t j = threadIdx.x; j < bhi[r] - blo[r]; j += B3F) s_pred[r * TILE3_ROW + j] = pred[blo[r] + j];
-            __syncthreads();
+            stage3_rows<false>(blo, bhi, pred, vel_s, s_pred);
             const int pclass = plane_class(R, fit);
             if (pclass == 2) {
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {
                     const uint32_t len = R.hi[r] - R.lo[r];
-                    const float4* base = s_pred + ((uint32_t)r * TILE3_ROW + (len ? R.lo[r] - blo[r] : 0u));
+                    const float4* base = s_pred + row_la(R, blo, r);
                     u64m mh, ml;
                     scan3_row128(P, base, len, me, &mh, &ml);
                     if (P.handoff && live) {
                         masks[(size_t)(plane * 3 + r) * P.n + i] = mh;
                         masks[(size_t)(9 + plane * 3 + r) * P.n + i] = ml;
                     }
-                    while (mh) {
-                        const uint32_t t = (uint32_t)__builtin_clzll(mh);
-                        mh ^= 0x8000000000000000ull >> t;
-                        if (MODE == 2) rho = dens3_tol(P, me, base[t], rho);
-                        else rho += dens3(P, me, base[t]);
-                    }
-                    while (ml) {
-                        const uint32_t t = (uint32_t)__builtin_clzll(ml);
-                        ml ^= 0x8000000000000000ull >> t;
-                        if (MODE == 2) rho = dens3_tol(P, me, base[64u + t], rho);
-                        else rho += dens3(P, me, base[64u + t]);
-                    }
+                    walk_density<MODE>(P, mh, base, me, rho);
+                    walk_density<MODE>(P, ml, base + 64, me, rho);
                 }
             } else if (pclass == 1) {
                 u64m m[3];
@@ -370,16 +298,7 @@ __global__ __launch_bounds__(B3F) FS3_DENSITY_ATTR void k3_density(Params3 P, fl
                     for (int r = 0; r < 3; ++r) masks[(size_t)(plane * 3 + r) * P.n + i] = m[r];
                 }
 #pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    u64m mm = m[r];
-                    const float4* base = s_pred + la[r];
-                    while (mm) {
-                        const uint32_t t = (uint32_t)__builtin_clzll(mm);
-                        mm ^= 0x8000000000000000ull >> t;
-                        if (MODE == 2) rho = dens3_tol(P, me, base[t], rho);
-                        else rho += dens3(P, me, base[t]);
-                    }
-                }
+                for (int r = 0; r < 3; ++r) walk_density<MODE>(P, m[r], s_pred + la[r], me, rho);
             } else {
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {
@@ -517,12 +436,6 @@ __device__ __forceinline__ Terms3 pair3(const Params3& P, float4 me, float4 mv, 
     return T;
 }
 
-// (the general sweep, sweep3_chunks, follows the mask sweep below: it shares its helpers)
-
-#ifndef FS3_FORCE_WAVES
-#define FS3_FORCE_WAVES (FS3_STAGE_VEL ? 4 : 7)   // with the velocity stage the LDS allows 4 waves per SIMD: take their registers.  Without it: round 2 (own scan): 4: 2.265, 5: 2.232, 6: 2.215 ms.  Round 3 (masks handed over by k3_density), steps 10-50 / 50-110: 5: 1.42 / 2.48, 6: 1.45 / 2.45, 7: 1.38 / 2.38 ms
-#endif
-
 // ---- tolerance mode (fs3_create_ex math_mode = FS_MATH_TOLERANCE): the pressure and viscosity terms of one in-radius
 // neighbour merged algebraically, as kernels_force.hip force_accum_tol does in 2D: one v_rsq_f32, fused multiply-adds,
 // 1/rho_j from the density pass (vel_s.w), ~32 issue slots per pair instead of ~95.  Coincident particles keep the
@@ -574,24 +487,22 @@ __device__ __forceinline__ void pair3_accum(const Params3& P, const Tol3& C, flo
 // 64-bit pass masks, row 0, 1, 2, ascending — the oracle's visiting order.  The masks come from k3_density
 // (Params3::handoff, `masks` != nullptr: three coalesced 8-byte loads) or from a scan of the staged plane.
 // `self_plane`: the lane's own particle sits in row 1 of the middle plane and is skipped (k != i).
-// The walk shared by the 64-bit and the 128-bit mask sweeps: three mask words with the LDS index (and, without the velocity
-// stage, the global index) of their first candidate, consumed in order.
+// The walk shared by the 64-bit and the 128-bit mask sweeps: three mask words with the LDS index of their first candidate,
+// consumed in order.
 template <int MODE>
-__device__ __forceinline__ void walk3(const Params3& P, const Tol3& C, const u64m* m, const uint32_t* la, const uint32_t* gl,
-                                      float4 me, float4 mv, float pressure, const float4* __restrict__ vel_s,
-                                      const float4* s_flat, Acc3& A) {
-    // The three masks are walked as a shift register (round 3): `cur` is the mask being consumed with its LDS / global
-    // bases, (n1, n2) wait behind it.  Empty masks are squeezed out first, so "cur == 0 -> pull n1" is all a refill ever
-    // needs and the per-neighbour bit extraction touches ONE 64-bit mask and ONE pair of bases (the round-2 form selected
-    // among three masks and six bases for every neighbour: ~40 instructions, now ~23).  Row order 0, 1, 2 is kept.
+__device__ __forceinline__ void walk3(const Params3& P, const Tol3& C, const u64m* m, const uint32_t* la, float4 me, float4 mv,
+                                      float pressure, const float4* s_flat, Acc3& A) {
+    // The three masks are walked as a shift register: `cur` is the mask being consumed with its LDS base, (n1, n2) wait
+    // behind it.  Empty masks are squeezed out first, so "cur == 0 -> pull n1" is all a refill ever needs and the
+    // per-neighbour bit extraction touches ONE 64-bit mask and ONE base.  Row order 0, 1, 2 is kept.
     u64m cur = m[0], n1 = m[1], n2 = m[2];
-    uint32_t lac = la[0] << 4, la_1 = la[1] << 4, la_2 = la[2] << 4, loc = gl[0], lo_1 = gl[1], lo_2 = gl[2];   // la* in bytes
-    if (n1 == 0ull) { n1 = n2; la_1 = la_2; lo_1 = lo_2; n2 = 0ull; }
-    if (cur == 0ull) { cur = n1; lac = la_1; loc = lo_1; n1 = n2; la_1 = la_2; lo_1 = lo_2; n2 = 0ull; }
+    uint32_t lac = la[0] << 4, la_1 = la[1] << 4, la_2 = la[2] << 4;   // in bytes
+    if (n1 == 0ull) { n1 = n2; la_1 = la_2; n2 = 0ull; }
+    if (cur == 0ull) { cur = n1; lac = la_1; n1 = n2; la_1 = la_2; n2 = 0ull; }
     // Software-pipelined (as in the 2D kernel): the LDS read and the velocity gather of later neighbours are issued
     // before the terms of neighbour k are evaluated — two neighbours ahead (k+1 and k+2: three slots refilled in turn, the
-    // loop unrolled by three so no value is moved).  With the velocity stage the kernel runs at 4 waves per SIMD and has the
-    // registers for it; the one-deep form it replaced, and the measurements at 7 waves, are in profiles/r03_rejected.md.
+    // loop unrolled by three so no value is moved).  At 4 waves per SIMD the kernel has the registers for it (the one-deep
+    // form: profiles/r03_rejected.md).
 #define FS3_FETCH(have, qn, vn)                                                                                      \
     do {                                                                                                             \
         have = cur != 0ull;                                                                                          \
@@ -599,10 +510,8 @@ __device__ __forceinline__ void walk3(const Params3& P, const Tol3& C, const u64
             const uint32_t t = (uint32_t)__builtin_clzll(cur);                                                       \
             cur ^= 0x8000000000000000ull >> t;                                                                       \
             qn = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_flat) + (lac + (t << 4)));         \
-            /* 32-bit byte offset from the SGPR base (n <= 2^28) instead of 64-bit address arithmetic */             \
-            if (FS3_STAGE_VEL) vn = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_flat) + (lac + (t << 4)) + TILE3_VEL_OFF); \
-            else vn = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(vel_s) + ((loc + t) << 4));     \
-            if (cur == 0ull) { cur = n1; lac = la_1; loc = lo_1; n1 = n2; la_1 = la_2; lo_1 = lo_2; n2 = 0ull; }     \
+            vn = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_flat) + (lac + (t << 4)) + TILE3_VEL_OFF); \
+            if (cur == 0ull) { cur = n1; lac = la_1; n1 = n2; la_1 = la_2; n2 = 0ull; }                              \
         }                                                                                                            \
     } while (0)
     float4 qA = make_float4(0.0f, 0.0f, 0.0f, 0.0f), vA = qA, qB = qA, vB = qA, qC = qA, vC = qA;
@@ -626,8 +535,7 @@ __device__ __forceinline__ void walk3(const Params3& P, const Tol3& C, const u64
 
 template <int MODE>
 __device__ __forceinline__ void sweep3_masks(const Params3& P, const Tol3& C, const RowRanges& R, const uint32_t* blo, bool self_plane,
-                                             uint32_t ii, float4 me, float4 mv, float pressure,
-                                             const float4* __restrict__ vel_s, const float4* s_flat,
+                                             uint32_t ii, float4 me, float4 mv, float pressure, const float4* s_flat,
                                              const u64m* __restrict__ masks, Acc3& A) {
     u64m m[3];
     uint32_t la[3];
@@ -635,33 +543,32 @@ __device__ __forceinline__ void sweep3_masks(const Params3& P, const Tol3& C, co
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             const uint32_t len = R.hi[r] - R.lo[r];
-            la[r] = (uint32_t)r * TILE3_ROW + (len ? R.lo[r] - blo[r] : 0u);
+            la[r] = row_la(R, blo, r);
             m[r] = masks[(size_t)r * P.n + ii];                            // all-zero for lanes past the end (never written: masked below)
-            m[r] &= len ? ~0ull << (64u - len) : 0ull;
+            m[r] &= keep64(len);
         }
     } else {
         scan3_plane(P, R, blo, me, s_flat, m, la);
     }
     if (self_plane && ii - R.lo[1] < R.hi[1] - R.lo[1]) m[1] &= ~(0x8000000000000000ull >> (ii - R.lo[1]));
-    walk3<MODE>(P, C, m, la, R.lo, me, mv, pressure, vel_s, s_flat, A);
+    walk3<MODE>(P, C, m, la, me, mv, pressure, s_flat, A);
 }
 
 // Rows of up to 128 candidates (plane_class() == 2): two words per row, walked as (r0.hi, r0.lo, r1.hi) then (r1.lo, r2.hi,
 // r2.lo) — the same visiting order.  `masks` / `masks_lo`: the plane's words from k3_density, or nullptr (own scan).
 template <int MODE>
 __device__ __forceinline__ void sweep3_masks128(const Params3& P, const Tol3& C, const RowRanges& R, const uint32_t* blo, bool self_plane,
-                                                uint32_t ii, float4 me, float4 mv, float pressure,
-                                                const float4* __restrict__ vel_s, const float4* s_flat,
+                                                uint32_t ii, float4 me, float4 mv, float pressure, const float4* s_flat,
                                                 const u64m* __restrict__ masks, const u64m* __restrict__ masks_lo, Acc3& A) {
     u64m mh[3], ml[3];
     uint32_t la[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
         const uint32_t len = R.hi[r] - R.lo[r];
-        la[r] = (uint32_t)r * TILE3_ROW + (len ? R.lo[r] - blo[r] : 0u);
+        la[r] = row_la(R, blo, r);
         if (masks) {
-            mh[r] = masks[(size_t)r * P.n + ii] & (len >= 64u ? ~0ull : (len ? ~0ull << (64u - len) : 0ull));
-            ml[r] = masks_lo[(size_t)r * P.n + ii] & (len > 64u ? ~0ull << (128u - len) : 0ull);
+            mh[r] = masks[(size_t)r * P.n + ii] & keep128_hi(len);
+            ml[r] = masks_lo[(size_t)r * P.n + ii] & keep128_lo(len);
         } else {
             scan3_row128(P, s_flat + la[r], len, me, &mh[r], &ml[r]);
         }
@@ -673,13 +580,13 @@ __device__ __forceinline__ void sweep3_masks128(const Params3& P, const Tol3& C,
     }
     {
         const u64m m[3] = {mh[0], ml[0], mh[1]};
-        const uint32_t l[3] = {la[0], la[0] + 64u, la[1]}, g[3] = {R.lo[0], R.lo[0] + 64u, R.lo[1]};
-        walk3<MODE>(P, C, m, l, g, me, mv, pressure, vel_s, s_flat, A);
+        const uint32_t l[3] = {la[0], la[0] + 64u, la[1]};
+        walk3<MODE>(P, C, m, l, me, mv, pressure, s_flat, A);
     }
     {
         const u64m m[3] = {ml[1], mh[2], ml[2]};
-        const uint32_t l[3] = {la[1] + 64u, la[2], la[2] + 64u}, g[3] = {R.lo[1] + 64u, R.lo[2], R.lo[2] + 64u};
-        walk3<MODE>(P, C, m, l, g, me, mv, pressure, vel_s, s_flat, A);
+        const uint32_t l[3] = {la[1] + 64u, la[2], la[2] + 64u};
+        walk3<MODE>(P, C, m, l, me, mv, pressure, s_flat, A);
     }
 }
 
@@ -688,6 +595,7 @@ __device__ __forceinline__ void sweep3_masks128(const Params3& P, const Tol3& C,
 // kernels_force.hip force_sweep_chunks) — wave-uniform scan into a 32-bit mask, pipelined walk.  Rows and
 // chunks in order = the oracle's visiting order.  STAGED: candidates from the LDS tile, else from global
 // memory (pred is allocated with FS_PRED_SLACK elements of slack for the read-ahead).
+#define FS3_CHUNK_BATCH 4    // 32-candidate chunks scanned per walk
 template <bool STAGED, int MODE>
 __device__ __forceinline__ void sweep3_chunks(const Params3& P, const Tol3& C, const RowRanges& R, const uint32_t* blo, bool self_plane,
                                               uint32_t ii, float4 me, float4 mv, float pressure,
@@ -734,8 +642,8 @@ __device__ __forceinline__ void sweep3_chunks(const Params3& P, const Tol3& C, c
                 if (r == 1 && self_plane && clen && ii - g < clen) mask &= ~(0x80000000u >> (ii - g));   // k != i
                 mq[q] = mask;
             }
-            uint32_t cur = mq[0], n1 = mq[1 % FS3_CHUNK_BATCH], n2 = FS3_CHUNK_BATCH > 2 ? mq[2 % FS3_CHUNK_BATCH] : 0u,
-                     n3 = FS3_CHUNK_BATCH > 3 ? mq[3 % FS3_CHUNK_BATCH] : 0u;
+            static_assert(FS3_CHUNK_BATCH == 4, "the walk's shift register holds four chunk masks");
+            uint32_t cur = mq[0], n1 = mq[1], n2 = mq[2], n3 = mq[3];
             uint32_t boff = boff0, goff = g0 << 4;
             float4 qn = make_float4(0.0f, 0.0f, 0.0f, 0.0f), vn = qn;
             bool have = false, pending = false;
@@ -748,7 +656,7 @@ __device__ __forceinline__ void sweep3_chunks(const Params3& P, const Tol3& C, c
             const uint32_t tt = (uint32_t)__builtin_clz(cur);                                                        \
             cur ^= 0x80000000u >> tt;                                                                                \
             qn = FS3_CAND(boff, tt);                                                                                 \
-            if (STAGED && FS3_STAGE_VEL) vn = *reinterpret_cast<const float4*>(src + (boff + (tt << 4)) + TILE3_VEL_OFF);  \
+            if (STAGED) vn = *reinterpret_cast<const float4*>(src + (boff + (tt << 4)) + TILE3_VEL_OFF);                 \
             else vn = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(vel_s) + (goff + (tt << 4)));   \
         }                                                                                                            \
     } while (0)
@@ -790,12 +698,8 @@ __device__ __forceinline__ void force3_body(const Params3& P, const float4* __re
     A.px = A.py = A.pz = A.vx = A.vy = A.vz = 0.0f;
     A.seed = ii * 12u + P.frame * 69u;
     const uint32_t key = key_s[ii];
-    uint32_t lo9[9], hi9[9];        // all 18 cell-start lookups up front: independent loads, one latency
-#pragma unroll
-    for (int j = 0; j < 9; ++j) {
-        lo9[j] = 0; hi9[j] = 0;
-        if (live && !row3_key(P, cs, key, j, &lo9[j], &hi9[j])) { lo9[j] = 0; hi9[j] = 0; }
-    }
+    uint32_t lo9[9], hi9[9];
+    rows3_lookup(P, cs, key, live, lo9, hi9);
 #pragma unroll 1
     for (int plane = 0; plane < 3; ++plane) {
         RowRanges R;
@@ -807,19 +711,13 @@ __device__ __forceinline__ void force3_body(const Params3& P, const float4* __re
         uint32_t blo[3], bhi[3];
         const bool fit = block_tile_bounds<W3F>(R, s_red, blo, bhi, TILE3);
         if (fit) {
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-                for (uint32_t j = tid; j < bhi[r] - blo[r]; j += B3F) {
-                    s_buf[r * TILE3_ROW + j] = pred[blo[r] + j];
-                    if (FS3_STAGE_VEL) s_buf[TILE3_LDS + r * TILE3_ROW + j] = vel_s[blo[r] + j];
-                }
-            __syncthreads();
+            stage3_rows<true>(blo, bhi, pred, vel_s, s_buf);
             const int pclass = plane_class(R, fit);      // the same predicate as k3_density: its masks exist exactly for these planes
             if (pclass == 1)
-                sweep3_masks<MODE>(P, C, R, blo, plane == 1, ii, me, mv, pressure, vel_s, s_buf,
+                sweep3_masks<MODE>(P, C, R, blo, plane == 1, ii, me, mv, pressure, s_buf,
                                    masks ? masks + (size_t)plane * 3u * P.n : nullptr, A);
             else if (pclass == 2)
-                sweep3_masks128<MODE>(P, C, R, blo, plane == 1, ii, me, mv, pressure, vel_s, s_buf,
+                sweep3_masks128<MODE>(P, C, R, blo, plane == 1, ii, me, mv, pressure, s_buf,
                                       masks ? masks + (size_t)plane * 3u * P.n : nullptr,
                                       masks ? masks + (size_t)(9 + plane * 3) * P.n : nullptr, A);
             else sweep3_chunks<true, MODE>(P, C, R, blo, plane == 1, ii, me, mv, pressure, pred, vel_s, s_buf, A);
@@ -849,32 +747,15 @@ __device__ __forceinline__ void force3_body(const Params3& P, const float4* __re
     pos_out[i] = p;
     vel_out[i] = v;
 }
-// One kernel per math mode: the register budget that measured best differs (strict: 7 waves per SIMD, tolerance: 6).
-#ifndef FS3_FORCE_WAVES_TOL
-#define FS3_FORCE_WAVES_TOL (FS3_STAGE_VEL ? 4 : 6)
-#endif
-template <int MODE> __global__ void k3_force(Params3 P, const float4* __restrict__ pos_s, const float4* __restrict__ vel_s,
-                                             const float4* __restrict__ pred, const uint32_t* __restrict__ cs,
-                                             float4* __restrict__ pos_out, float4* __restrict__ vel_out,
-                                             const u64m* __restrict__ masks, const uint32_t* __restrict__ key_s,
-                                             const u64* __restrict__ srcs);
-template <>
-__global__ __launch_bounds__(B3F) __attribute__((amdgpu_waves_per_eu(FS3_FORCE_WAVES, FS3_FORCE_WAVES))) void k3_force<0>(
+// 4 waves per SIMD is what the LDS of the staged plane allows: take their registers.
+template <int MODE>
+__global__ __launch_bounds__(B3F) __attribute__((amdgpu_waves_per_eu(4, 4))) void k3_force(
     Params3 P, const float4* __restrict__ pos_s, const float4* __restrict__ vel_s, const float4* __restrict__ pred,
     const uint32_t* __restrict__ cs, float4* __restrict__ pos_out, float4* __restrict__ vel_out, const u64m* __restrict__ masks,
     const uint32_t* __restrict__ key_s, const u64* __restrict__ srcs) {
     __shared__ float4 s_buf[TILE3_FORCE_LDS];     // the staged plane: positions, then velocities
     __shared__ uint32_t s_red[24];
-    force3_body<0>(P, pos_s, vel_s, pred, cs, pos_out, vel_out, masks, key_s, srcs, s_buf, s_red);
-}
-template <>
-__global__ __launch_bounds__(B3F) __attribute__((amdgpu_waves_per_eu(FS3_FORCE_WAVES_TOL, FS3_FORCE_WAVES_TOL))) void k3_force<2>(
-    Params3 P, const float4* __restrict__ pos_s, const float4* __restrict__ vel_s, const float4* __restrict__ pred,
-    const uint32_t* __restrict__ cs, float4* __restrict__ pos_out, float4* __restrict__ vel_out, const u64m* __restrict__ masks,
-    const uint32_t* __restrict__ key_s, const u64* __restrict__ srcs) {
-    __shared__ float4 s_buf[TILE3_FORCE_LDS];
-    __shared__ uint32_t s_red[24];
-    force3_body<2>(P, pos_s, vel_s, pred, cs, pos_out, vel_out, masks, key_s, srcs, s_buf, s_red);
+    force3_body<MODE>(P, pos_s, vel_s, pred, cs, pos_out, vel_out, masks, key_s, srcs, s_buf, s_red);
 }
 
 __global__ __launch_bounds__(B3) void k3_export(uint32_t n, const float4* __restrict__ pos, const float4* __restrict__ pred,
@@ -902,261 +783,38 @@ __global__ __launch_bounds__(B3) void k3_import(uint32_t n, const fs3_particle* 
     key[i] = a.grid;
 }
 
+// ------------------------------------------------------------------------------------ launchers (fs_3d.h)
+uint32_t blocks3(uint32_t n) { return (n + B3F - 1) / B3F; }
+
+void launch3_predict_key(hipStream_t st, const Params3& P, const Arrays3& A) {
+    hipLaunchKernelGGL(k3_predict_key, dim3((P.n + B3 - 1) / B3), dim3(B3), 0, st, P, A.pos, A.vel, A.pairs, A.counter);
+}
+
+void launch3_reorder(hipStream_t st, const Params3& P, const Arrays3& A) {
+    hipLaunchKernelGGL(k3_reorder, dim3((P.n + B3 - 1) / B3), dim3(B3), 0, st, P, A.pairs, A.pos, A.vel, A.pos_out, A.vel_s, A.pred,
+                       A.key, A.cs, (GapEntry*)A.work, A.counter, A.work_cap);
+    launch_fill_gaps(st, A.cs, A.work, A.counter, A.work_cap);
+}
+
+void launch3_density(hipStream_t st, const Params3& P, const Arrays3& A, bool tol) {
+    const dim3 grid(xcd_grid3(blocks3(P.n), P.xcd_chunk_log2)), block(B3F);
+    if (tol) hipLaunchKernelGGL(k3_density<2>, grid, block, 0, st, P, A.pred, A.cs, A.vel_s, A.masks, A.key);
+    else hipLaunchKernelGGL(k3_density<0>, grid, block, 0, st, P, A.pred, A.cs, A.vel_s, A.masks, A.key);
+}
+
+// positions ping-pong: read the previous state (A.pos, source order) through the pairs, write the new one into A.pos_out
+void launch3_force(hipStream_t st, const Params3& P, const Arrays3& A, bool tol, hipEvent_t done) {
+    const dim3 grid(xcd_grid3(blocks3(P.n), P.xcd_chunk_log2)), block(B3F);
+    if (tol) hipExtLaunchKernelGGL(k3_force<2>, grid, block, 0, st, nullptr, done, 0, P, A.pos, A.vel_s, A.pred, A.cs, A.pos_out, A.vel, A.masks, A.key, A.pairs);
+    else hipExtLaunchKernelGGL(k3_force<0>, grid, block, 0, st, nullptr, done, 0, P, A.pos, A.vel_s, A.pred, A.cs, A.pos_out, A.vel, A.masks, A.key, A.pairs);
+}
+
+void launch3_import(hipStream_t st, uint32_t n, const Arrays3& A) {
+    hipLaunchKernelGGL(k3_import, dim3((n + B3 - 1) / B3), dim3(B3), 0, st, n, (const fs3_particle*)A.aos, A.pos, A.pred, A.vel, A.key);
+}
+
+void launch3_export(hipStream_t st, uint32_t n, const Arrays3& A) {
+    hipLaunchKernelGGL(k3_export, dim3((n + B3 - 1) / B3), dim3(B3), 0, st, n, A.pos, A.pred, A.vel, A.key, (fs3_particle*)A.aos);
+}
+
 }  // namespace fsd
-
-// ------------------------------------------------------------------------------------ host
-using fsd::DevArray;
-using fsd::fail;
-namespace {
-void lattice3(const fs3_settings& st, fs_vec3 off, fs3_particle* dst, size_t n) {
-    const uint32_t side = (uint32_t)std::llround(std::cbrt((double)st.particle_count));
-    const float half = (float)side * 0.5f, s = st.particle_spacing;
-    for (uint32_t i = 0; i < st.particle_count && i < n; ++i) {
-        const uint32_t ix = i % side, iy = (i / side) % side, iz = i / (side * side);
-        fs3_particle q;
-        std::memset(&q, 0, sizeof q);
-        q.position.x = ((float)ix - half + 0.5f) * s + off.x;
-        q.position.y = ((float)iy - half + 0.5f) * s + off.y;
-        q.position.z = ((float)iz - half + 0.5f) * s + off.z;
-        q.predicted_position = q.position;
-        dst[i] = q;
-    }
-}
-}  // namespace
-
-// Every resource is held by an owner (fs_host.h) and freed by `delete`; members go in reverse order of declaration: the
-// device arrays first, then the events (profile ring, sort policy, t1 / t0), the stream last.
-struct fs_sim3 {
-    fs3_settings st{};
-    uint32_t n = 0, gw = 0, gh = 0, gd = 0, ncell = 0, tick = 0, work_cap = 0;
-    int device = 0;
-    int math_mode = FS_MATH_IEEE;
-    fsd::Stream stream;
-    fsd::Event t0, t1;
-    fsd::SortPolicy sortp;       // host side of the sort's late-stage plan (sort_policy.h)
-    fsd::PassRing prof;          // per-pass timing
-    DevArray<float4> pos, vel, pos_s, vel_s, pred;
-    DevArray<uint32_t> key, cs, counter, dirty;
-    DevArray<fsd::u64> pairs;
-    DevArray<fsd::u64> masks;        // 9 x n pass masks of the 27-cell sweep, k3_density -> k3_force (Params3::handoff)
-    bool handoff = true;
-    DevArray<unsigned char> work;
-    DevArray<fs3_particle> aos;
-    fsd::ConstDiv div_2h3{}, div_h2{};
-    bool share_div = false;      // all create-time proofs of the shared-denominator path succeeded
-};
-
-static fs_status enqueue3(fs_sim3* s, const fs3_tick_settings* t) {
-    using namespace fsd;
-    s->tick += 1;
-    const float h = s->st.smoothing_radius;
-    const float PI3 = 3.14159265359f;
-    Params3 P;
-    std::memset(&P, 0, sizeof P);
-    P.n = s->n; P.gw = s->gw; P.gh = s->gh; P.gd = s->gd; P.ncell = s->ncell;
-    P.dt = t->delta; P.h = h; P.h2 = h * h;
-    P.bx = s->st.size.x * 0.5f; P.by = s->st.size.y * 0.5f; P.bz = s->st.size.z * 0.5f;
-    P.mass = t->mass;
-    P.poly6 = 315.0f / (64.0f * PI3 * std::pow(h, 9.0f));      // host libm, as in the oracle
-    P.spiky = 15.0f / (PI3 * std::pow(h, 5.0f));
-    P.visc_k = 15.0f / (2.0f * PI3 * (h * h * h));
-    P.pressure_k = t->pressure_constant; P.rest_density = t->rest_density; P.damping = t->damping_factor;
-    P.visc_coeff = t->viscosity_coefficient;
-    P.gx = t->gravity.x; P.gy = t->gravity.y; P.gz = t->gravity.z;
-    P.frame = s->tick;
-    P.div_2h3 = s->div_2h3;
-    P.div_h2 = s->div_h2;
-    // the classification bounds the pressure numerators by (1 + 2^-22) h spiky 2^39 <= 2^60 (fs_device.h)
-    P.share_div = (s->share_div && h * P.spiky <= FS_HSPIKY_HI) ? 1 : 0;
-    P.handoff = s->handoff ? 1 : 0;
-    {   // chunks of ~1/128 of the blocks, at most 2^7 (8 M: 31 250 blocks, a z-plane of the cube is ~310): FS3_XCD_CHUNK_LOG2 overrides
-        static const int forced = getenv("FS3_XCD_CHUNK_LOG2") ? atoi(getenv("FS3_XCD_CHUNK_LOG2")) : -1;
-        const uint32_t nb = (s->n + B3F - 1) / B3F;
-        uint32_t c = 0;
-        while (c < 7u && (128u << (c + 1u)) <= nb) ++c;
-        // 8 M, steps 10-110, strict / tolerance step (ms): c = 0: 3.329 / 2.732, 3: 3.277 / 2.675, 5: 3.260 / 2.645,
-        // 7: 3.255 / 2.636, 8: 3.281 / 2.650, 10: 3.403 / 2.738, 12: 3.425 / 2.761 (large chunks bind an XCD to one depth)
-        P.xcd_chunk_log2 = forced >= 0 ? (uint32_t)(forced > 16 ? 16 : forced) : c;
-    }
-    const bool tol = s->math_mode == FS_MATH_TOLERANCE;
-    hipStream_t st = s->stream;
-    hipEvent_t* ev = nullptr;
-    if (s->prof.on) {
-        const fs_status r = s->prof.begin();
-        if (r != FS_OK) return r;
-        ev = s->prof.current();
-    }
-    const dim3 grid((s->n + B3 - 1) / B3), block(B3);
-    FS_HIP(s->sortp.throttle());                           // at most SortPolicy::FLIGHT steps ahead of the device
-    if (ev) FS_HIP(hipEventRecord(ev[0], st));
-    // predict + key are fused into the first sort kernel (k_bitonic_local<true, 2, *>), as in 2D: no separate launch,
-    // the unsorted pairs never touch HBM.  FS3_SEPARATE_KEYGEN=1 keeps the round-2 kernel (A/B measurements).
-    static const bool separate_keygen = getenv("FS3_SEPARATE_KEYGEN") != nullptr;
-    if (separate_keygen) hipLaunchKernelGGL(k3_predict_key, grid, block, 0, st, P, s->pos.p, s->vel.p, s->pairs.p, s->counter.p);
-    if (ev) FS_HIP(hipEventRecord(ev[1], st));
-    fsd::SortPlan plan;
-    if (!s->sortp.plan(s->n, &plan)) return fail(FS_ERR_DEVICE, "sort: the stand-by kernel's grid barrier timed out");
-    if (separate_keygen) {
-        launch_bitonic_sort(st, s->pairs.p, s->n, s->dirty.p, nullptr, nullptr, nullptr, nullptr, &plan);
-    } else {
-        const fsd::KeyGen3 kg{P.dt, P.h, P.bx, P.by, P.bz, P.gw, P.gh};
-        launch_bitonic_sort(st, s->pairs.p, s->n, s->dirty.p, nullptr, nullptr, nullptr, s->counter.p, &plan, &kg, s->pos.p, s->vel.p);
-    }
-    if (ev) FS_HIP(hipEventRecord(ev[2], st));
-    hipLaunchKernelGGL(k3_reorder, grid, block, 0, st, P, s->pairs.p, s->pos.p, s->vel.p, s->pos_s.p, s->vel_s.p,
-                       s->pred.p, s->key.p, s->cs.p, (GapEntry*)s->work.p, s->counter.p, s->work_cap);
-    launch_fill_gaps(st, s->cs.p, s->work.p, s->counter.p, s->work_cap);
-    if (ev) FS_HIP(hipEventRecord(ev[3], st));
-    const fsd::u64* fm = s->handoff ? s->masks.p : nullptr;
-    const dim3 gridf(xcd_grid3((s->n + B3F - 1) / B3F, P.xcd_chunk_log2)), blockf(B3F);
-    if (tol) hipLaunchKernelGGL(k3_density<2>, gridf, blockf, 0, st, P, s->pred.p, s->cs.p, s->vel_s.p, s->masks.p, s->key.p);
-    else hipLaunchKernelGGL(k3_density<0>, gridf, blockf, 0, st, P, s->pred.p, s->cs.p, s->vel_s.p, s->masks.p, s->key.p);
-    if (ev) FS_HIP(hipEventRecord(ev[4], st));
-    // positions ping-pong: read the previous state (s->pos, source order) through the pairs, write the new one into s->pos_s
-    // the step's completion event (sort_policy.h: the host stays at most four steps ahead) rides on the force kernel as its
-    // completion signal — no marker packet behind it (engine.hip fs_step does the same); a profiled step records markers anyway
-    hipEvent_t done = ev ? nullptr : s->sortp.flight_event();
-    if (tol) hipExtLaunchKernelGGL(k3_force<2>, gridf, blockf, 0, st, nullptr, done, 0, P, s->pos.p, s->vel_s.p, s->pred.p, s->cs.p, s->pos_s.p, s->vel.p, fm, s->key.p, s->pairs.p);
-    else hipExtLaunchKernelGGL(k3_force<0>, gridf, blockf, 0, st, nullptr, done, 0, P, s->pos.p, s->vel_s.p, s->pred.p, s->cs.p, s->pos_s.p, s->vel.p, fm, s->key.p, s->pairs.p);
-    std::swap(s->pos, s->pos_s);
-    if (ev) { FS_HIP(hipEventRecord(ev[5], st)); FS_HIP(hipEventRecord(ev[6], st)); /* FS_PASS_BOUNDARY: slab handles only */ s->prof.pending += 1; }
-    if (ev) FS_HIP(s->sortp.step_enqueued(st));
-    else s->sortp.step_bound();
-    FS_HIP(hipGetLastError());
-    return FS_OK;
-}
-
-extern "C" {
-
-fs_status fs3_reference_lattice(const fs3_settings* st, fs_vec3 off, fs3_particle* dst, size_t n) {
-    if (!st || (!dst && n)) return fail(FS_ERR_INVALID, "null argument");
-    lattice3(*st, off, dst, n);
-    return FS_OK;
-}
-
-fs_status fs3_create(const fs3_settings* st, int device, fs_vec3 off, fs_sim3** out) {
-    return fs3_create_ex(st, device, off, FS_MATH_IEEE, out);
-}
-
-fs_status fs3_create_ex(const fs3_settings* st, int device, fs_vec3 off, int math_mode, fs_sim3** out) {
-    if (!st || !out) return fail(FS_ERR_INVALID, "null argument");
-    *out = nullptr;
-    if (math_mode != FS_MATH_IEEE && math_mode != FS_MATH_TOLERANCE)
-        return fail(FS_ERR_UNSUPPORTED, "3D math_mode must be FS_MATH_IEEE or FS_MATH_TOLERANCE");
-    if (st->particle_count <= 1) return fail(FS_ERR_INVALID, "particle_count <= 1");
-    if (st->particle_count > (1u << 28)) return fail(FS_ERR_INVALID, "particle_count > 2^28 (32-bit byte offsets)");
-    if (!(st->smoothing_radius > 0.0f) || !(st->size.x > 0) || !(st->size.y > 0) || !(st->size.z > 0))
-        return fail(FS_ERR_INVALID, "bad settings");
-    const uint32_t side = (uint32_t)std::llround(std::cbrt((double)st->particle_count));
-    if ((uint64_t)side * side * side != st->particle_count) return fail(FS_ERR_INVALID, "particle_count must be a cube");
-    const double gw = std::ceil((double)st->size.x / st->smoothing_radius) + 2, gh = std::ceil((double)st->size.y / st->smoothing_radius) + 2,
-                 gd = std::ceil((double)st->size.z / st->smoothing_radius) + 2;
-    if (gw * gh * gd >= 4294967295.0) return fail(FS_ERR_INVALID, "grid does not fit u32 cell ids");
-    FS_TRY(fsd::use_device(device));
-    std::unique_ptr<fs_sim3> s(new (std::nothrow) fs_sim3());   // an error exit frees whatever the handle holds by then
-    if (!s) return fail(FS_ERR_OOM, "host allocation failed");
-    s->st = *st; s->n = st->particle_count; s->device = device; s->math_mode = math_mode;
-    s->gw = (uint32_t)((size_t)std::ceil(st->size.x / st->smoothing_radius) + 2);
-    s->gh = (uint32_t)((size_t)std::ceil(st->size.y / st->smoothing_radius) + 2);
-    s->gd = (uint32_t)((size_t)std::ceil(st->size.z / st->smoothing_radius) + 2);
-    s->ncell = s->gw * s->gh * s->gd;
-    s->work_cap = s->ncell / 16u + 1024u;
-    FS_HIP(hipStreamCreateWithFlags(&s->stream.h, hipStreamNonBlocking));
-    const size_t n = s->n;
-    FS_HIP(s->pos.alloc(n)); FS_HIP(s->vel.alloc(n)); FS_HIP(s->pos_s.alloc(n)); FS_HIP(s->vel_s.alloc(n)); FS_HIP(s->pred.alloc(n + FS_PRED_SLACK));
-    FS_HIP(s->key.alloc(n)); FS_HIP(s->pairs.alloc(n)); FS_HIP(s->cs.alloc((size_t)s->ncell + 1)); FS_HIP(s->counter.alloc(4));
-    FS_HIP(s->dirty.alloc(fsd::sort_tile_count((uint32_t)n))); FS_HIP(s->work.alloc((size_t)s->work_cap * fsd::gap_entry_size()));
-    FS_HIP(s->aos.alloc(n));
-    s->handoff = !(getenv("FS3_HANDOFF") && atoi(getenv("FS3_HANDOFF")) == 0);
-    if (s->handoff) FS_HIP(s->masks.alloc((FS3_MASK128 ? 18 : 9) * (size_t)n));   // hi words, then the lo words of rows of 65 .. 128
-    FS_HIP(hipEventCreate(&s->t0.h)); FS_HIP(hipEventCreate(&s->t1.h));
-    FS_HIP(hipMemsetAsync(s->cs.p, 0, s->cs.n * 4, s->stream));
-    FS_HIP(hipMemsetAsync(s->counter.p, 0, 16, s->stream));
-    FS_HIP(hipMemsetAsync(s->dirty.p, 0, s->dirty.n * 4, s->stream));
-    FS_HIP(s->sortp.init(5));         // a z-plane of the cube holds n^(2/3) particles: the moves are long, start at stage S - 5
-    {
-        std::vector<fs3_particle> host(n);
-        lattice3(*st, off, host.data(), n);
-        FS_HIP(hipMemcpyAsync(s->aos.p, host.data(), n * sizeof(fs3_particle), hipMemcpyHostToDevice, s->stream));
-        hipLaunchKernelGGL(fsd::k3_import, dim3((s->n + B3 - 1) / B3), dim3(B3), 0, s->stream, s->n, s->aos.p, s->pos.p,
-                           s->pred.p, s->vel.p, s->key.p);
-        FS_HIP(hipStreamSynchronize(s->stream));
-    }
-    {   // the create-time proofs of the 2D engine (engine.h): the two constant divisions for this h, the lean reciprocal / square root
-        const float hh = st->smoothing_radius;
-        bool rcp_ok, sqrt_ok;
-        FS_TRY(fsd::prove_constdiv(s->stream, s->counter.p + 1, 2.0f * hh * hh * hh, &s->div_2h3));
-        FS_TRY(fsd::prove_constdiv(s->stream, s->counter.p + 1, hh * hh, &s->div_h2));
-        FS_TRY(fsd::prove_rcp_sqrt(s->stream, s->counter.p + 1, &rcp_ok, &sqrt_ok));
-        s->share_div = rcp_ok && sqrt_ok && s->div_2h3.ok && s->div_h2.ok && hh >= 0x1p-19f && hh <= 0x1p19f;
-    }
-    *out = s.release();
-    return FS_OK;
-}
-
-void fs3_destroy(fs_sim3* s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    delete s;
-}
-
-fs_status fs3_step(fs_sim3* s, const fs3_tick_settings* t) {
-    if (!s || !t) return fail(FS_ERR_INVALID, "null argument");
-    FS_HIP(hipSetDevice(s->device));
-    return enqueue3(s, t);
-}
-// a barrier time-out of the sort's stand-by kernel leaves the particle order undefined: reported wherever state is handed over
-static fs_status sort_health3(fs_sim3* s) {
-    FS_HIP(s->sortp.check_timeout(s->dirty.p, s->n));
-    if (s->sortp.dead) return fail(FS_ERR_DEVICE, "sort: the stand-by kernel's grid barrier timed out: the particle order is undefined from that step on; destroy the handle");
-    return FS_OK;
-}
-fs_status fs3_sync(fs_sim3* s) { if (!s) return fail(FS_ERR_INVALID, "null"); FS_HIP(hipStreamSynchronize(s->stream)); return sort_health3(s); }
-uint32_t fs3_tick_count(const fs_sim3* s) { return s ? s->tick : 0; }
-uint32_t fs3_particle_count(const fs_sim3* s) { return s ? s->n : 0; }
-fs_status fs3_grid_dims(const fs_sim3* s, uint32_t* w, uint32_t* h, uint32_t* d) {
-    if (!s || !w || !h || !d) return fail(FS_ERR_INVALID, "null argument");
-    *w = s->gw; *h = s->gh; *d = s->gd;
-    return FS_OK;
-}
-fs_status fs3_download_particles(fs_sim3* s, fs3_particle* dst, size_t n) {
-    if (!s || (!dst && n)) return fail(FS_ERR_INVALID, "null argument");
-    if (n > s->n) n = s->n;
-    FS_HIP(hipSetDevice(s->device));
-    hipLaunchKernelGGL(fsd::k3_export, dim3((s->n + B3 - 1) / B3), dim3(B3), 0, s->stream, s->n, s->pos.p, s->pred.p,
-                       s->vel.p, s->key.p, s->aos.p);
-    if (n) FS_HIP(hipMemcpyAsync(dst, s->aos.p, n * sizeof(fs3_particle), hipMemcpyDeviceToHost, s->stream));
-    FS_HIP(hipStreamSynchronize(s->stream));
-    return sort_health3(s);
-}
-fs_status fs3_upload_particles(fs_sim3* s, const fs3_particle* src, size_t n) {
-    if (!s || (!src && n)) return fail(FS_ERR_INVALID, "null argument");
-    if (n > s->n) n = s->n;
-    FS_HIP(hipSetDevice(s->device));
-    if (n) FS_HIP(hipMemcpyAsync(s->aos.p, src, n * sizeof(fs3_particle), hipMemcpyHostToDevice, s->stream));
-    if (n) hipLaunchKernelGGL(fsd::k3_import, dim3(((uint32_t)n + B3 - 1) / B3), dim3(B3), 0, s->stream, (uint32_t)n,
-                              s->aos.p, s->pos.p, s->pred.p, s->vel.p, s->key.p);
-    FS_HIP(hipStreamSynchronize(s->stream));
-    s->sortp.touched();
-    return FS_OK;
-}
-fs_status fs3_timed_steps(fs_sim3* s, const fs3_tick_settings* t, uint32_t steps, double* ms_total) {
-    if (!s || !t || !ms_total) return fail(FS_ERR_INVALID, "null argument");
-    FS_HIP(hipSetDevice(s->device));
-    FS_HIP(hipEventRecord(s->t0, s->stream));
-    for (uint32_t k = 0; k < steps; ++k) { fs_status r = enqueue3(s, t); if (r != FS_OK) return r; }
-    FS_HIP(hipEventRecord(s->t1, s->stream));
-    FS_HIP(hipEventSynchronize(s->t1));
-    float ms = 0;
-    FS_HIP(hipEventElapsedTime(&ms, s->t0, s->t1));
-    *ms_total = ms;
-    return sort_health3(s);
-}
-fs_status fs3_profile_enable(fs_sim3* s, int enable) { if (!s) return fail(FS_ERR_INVALID, "null"); s->prof.on = enable != 0; return FS_OK; }
-fs_status fs3_profile_read(fs_sim3* s, double ms[FS_PASS_COUNT], uint64_t* steps, int reset) {
-    if (!s || !ms) return fail(FS_ERR_INVALID, "null argument");
-    return s->prof.read(ms, steps, reset);
-}
-
-}  // extern "C"

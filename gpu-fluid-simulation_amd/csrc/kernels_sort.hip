@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "fs_3d.h"
 #include "fs_device.h"
 #include "fs_kernels.h"
 
@@ -219,17 +220,9 @@ __device__ __forceinline__ void lt_tail(const u64* __restrict__ pairs, uint32_t 
 // (compute.wgsl:8-42): it reads pos/vel and builds the (key, index) pairs on the fly instead of
 // reading them — one launch and one write+read of the pair array less per step.
 // KEYGEN: 0 = the pairs exist, 1 = 2D (StepParams, float2 pos / vel), 2 = 3D (KeyGen3 in the first words of the
-// StepParams argument, float4 pos / vel: the expressions of sim3d.hip predict3 / cell3, bit for bit).
+// StepParams argument, float4 pos / vel: fs_3d.h predict3 / cell_key3, as in k3_predict_key).
 __device__ __forceinline__ u64 keygen3(const KeyGen3& K, const float4* __restrict__ pos, const float4* __restrict__ vel, uint32_t i) {
-    const float4 p = pos[i], v = vel[i];
-    float rx = p.x + v.x * K.dt, ry = p.y + v.y * K.dt, rz = p.z + v.z * K.dt;
-    if (fabsf(rx) > K.bx) rx = K.bx * sign_f32(rx);
-    if (fabsf(ry) > K.by) ry = K.by * sign_f32(ry);
-    if (fabsf(rz) > K.bz) rz = K.bz * sign_f32(rz);
-    const uint32_t cx = f32_to_u32_sat(floorf(__fdiv_rn(rx + K.bx, K.h))) + 1u;
-    const uint32_t cy = f32_to_u32_sat(floorf(__fdiv_rn(ry + K.by, K.h))) + 1u;
-    const uint32_t cz = f32_to_u32_sat(floorf(__fdiv_rn(rz + K.bz, K.h))) + 1u;
-    return ((u64)((cz * K.gh + cy) * K.gw + cx) << 32) | (u64)i;
+    return ((u64)cell_key3(K, predict3(K, pos[i], vel[i])) << 32) | (u64)i;
 }
 template <bool INIT, int KEYGEN, int GB>
 __global__ __launch_bounds__(LT<GB>::THREADS) void k_bitonic_local(u64* __restrict__ pairs, uint32_t n,

@@ -111,18 +111,24 @@ def test_first_and_last_has_lane_give_the_block_bounds():
 
 
 def test_model_constants_match_the_kernel_sources():
-    sim3d = paths3d.source_text("sim3d.hip")
+    k3d = paths3d.source_text("kernels_3d.hip")
     kern = paths3d.source_text("fs_kernels.h")
     assert int(paths3d.parse_define(kern, "FS_PRED_SLACK")) == paths3d.FS_PRED_SLACK
-    assert int(paths3d.parse_define(sim3d, "B3F")) == paths3d.B3F
-    m = re.search(r"#if B3F == 256\s*\n#ifndef TILE3\s*\n#define TILE3 (\d+)", sim3d)
-    assert m and int(m.group(1)) == paths3d.TILE3
-    body = sim3d[sim3d.index("int plane_class("):]
+    assert int(paths3d.parse_define(k3d, "B3F")) == paths3d.B3F
+    assert int(paths3d.parse_define(k3d, "TILE3")) == paths3d.TILE3
+    assert "#ifndef B3F" not in k3d and "#ifndef TILE3" not in k3d            # plain constants: no other value is ever built
+    body = k3d[k3d.index("int plane_class("):]
     body = body[:body.index("\n}")]
     assert "mx > 64u" in body and "mx > 128u" in body and "if (!fit) return 0;" in body
     assert paths3d.MASK64 == 64 and paths3d.MASK128 == 128
-    assert "block_tile_bounds<W3F>(R, s_red, blo, bhi, TILE3)" in sim3d
-    assert paths3d.parse_define(sim3d, "FS3_MASK128") == "1"
+    # both passes take their block bounds from the same call with the same tile (k3_density and force3_body).  It is written at
+    # both sites: a shared helper around "rows of plane p -> RowRanges, block_tile_bounds" gets the nine looked-up ranges by
+    # pointer and the compiler then keeps them in scratch (96 B in all four kernels; k3_density 72 -> 54 VGPRs, k3_force
+    # 128 -> 107 / 109), which the split must not do
+    assert k3d.count("block_tile_bounds<W3F>(R, s_red, blo, bhi, TILE3)") == 2
+    # the 128-bit masks are no longer a switch: rows <= 128 are class 2 unconditionally
+    # (the name is spelt in two halves so that a search of the tree for the removed switch finds nothing, this test included)
+    assert "FS3_" + "MASK128" not in k3d and "return !__any(mx > 128u) ? 2 : 0;" in body
     # the unstaged sweep reads at most three candidates past a row's end (chunks are scanned four at a time)
     assert paths3d.FS_PRED_SLACK >= 3
 

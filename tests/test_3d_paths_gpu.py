@@ -110,7 +110,7 @@ GUARD_CASES = ["tiny_offsets", "tiny_velocities", "huge_velocities", "inf_veloci
 
 @pytest.mark.parametrize("case", GUARD_CASES)
 def test_3d_force_quotient_guards(fs, orc, case):
-    """Operands on both sides of every guard of the shared-reciprocal quotients (sim3d.hip: lo_safe / 2^59 in k3_reorder,
+    """Operands on both sides of every guard of the shared-reciprocal quotients (kernels_3d.hip: lo_safe / 2^59 in k3_reorder,
     FS_RCP_HI / FS_PRESSURE_HI in k3_density, FS_SQRT_LO / num_lo_ok3 / the 2^-20 branch in terms3*): whatever the
     classification decides, the step equals the oracle bit for bit, 3 steps."""
     over = {}
