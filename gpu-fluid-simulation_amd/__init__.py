@@ -26,6 +26,7 @@ from ._abi import (  # noqa: F401
     PARTICLE3_DTYPE,
     PARTICLE_DTYPE,
     PASS_NAMES,
+    SAMPLE3_DTYPE,
     SAMPLE_DTYPE,
     ExtensionMissing,
     Options,
@@ -45,7 +46,7 @@ from ._abi import (  # noqa: F401
 
 __all__ = [
     "FluidSimulation", "ResizableBuffer", "SimulationSettings", "default_tick_settings", "dam_break_2d",
-    "FluidSimError", "load_library", "PARTICLE_DTYPE", "SAMPLE_DTYPE",
+    "FluidSimError", "load_library", "PARTICLE_DTYPE", "SAMPLE_DTYPE", "SAMPLE3_DTYPE",
 ]
 
 
@@ -481,6 +482,43 @@ class FluidSimulation3D:
         steps = C.c_uint64()
         _check(self._lib, self._lib.fs3_profile_read(self._h, ms, C.byref(steps), 1 if reset else 0))
         return dict(zip(PASS_NAMES, [float(x) for x in ms])), int(steps.value)
+
+    @property
+    def stream_ptr(self):
+        """hipStream_t of the simulation as an integer (torch.cuda.ExternalStream / RCCL on the same stream)."""
+        return int(self._lib.fs3_stream(self._h) or 0)
+
+    # -- 3D field sampling (build extension; DESIGN.md §14) ------------------
+    def sample(self, points, normalise=False):
+        """Density, Shepard weight, velocity sum, density gradient, neighbour count and cell of the fluid at `points`
+        ((n, 3) float32, any place): a SAMPLE3_DTYPE array.  The velocity is the un-normalised SPH interpolant
+        (include/fluidsim.h); normalise=True divides it by `weight` where that is non-zero.  -gradient is the outward normal
+        of an iso-surface.  Needs a step since create / the last upload.  Points in a coherent order (sorted by cell, a grid,
+        slot order) are sampled several times faster than shuffled ones."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        out = np.zeros(n, dtype=SAMPLE3_DTYPE)
+        _check(self._lib, self._lib.fs3_sample_points(self._h, pts.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p)))
+        if normalise:
+            _normalise_samples(out, None)
+        return out
+
+    def sample_grid(self, width, height, depth=1, world_min=None, world_max=None):
+        """sample() at the voxel centres of a box (default: the whole domain): a [depth, height, width] SAMPLE3_DTYPE array,
+        bit-identical to sample() on those points.  A slice is depth == 1 with world_min[2] == world_max[2]."""
+        sz = self.settings.size
+        wmin = world_min if world_min is not None else (-sz.x / 2, -sz.y / 2, -sz.z / 2)
+        wmax = world_max if world_max is not None else (sz.x / 2, sz.y / 2, sz.z / 2)
+        width, height, depth = int(width), int(height), int(depth)
+        view = _abi.View3(Vec3(*[float(v) for v in wmin]), Vec3(*[float(v) for v in wmax]), width, height, depth)
+        out = np.zeros((depth, height, width), dtype=SAMPLE3_DTYPE)
+        _check(self._lib, self._lib.fs3_sample_grid(self._h, C.byref(view), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def sample_device(self, points_ptr, n, out_ptr):
+        """fs3_sample_points_device: device pointers (n fs_vec3 in, n 40-byte fs3_sample out), enqueued on the simulation's
+        stream after the steps in flight; non-blocking."""
+        _check(self._lib, self._lib.fs3_sample_points_device(self._h, C.c_void_p(points_ptr), int(n), C.c_void_p(out_ptr)))
 
 
 def reference_lattice_3d(settings, offset=(0.0, 0.0, 0.0)):

@@ -130,6 +130,17 @@ class Sample(C.Structure):
                 ("cell", C.c_uint32)]
 
 
+class View3(C.Structure):
+    """fs3_view (include/fluidsim.h): a box and the voxel counts per axis."""
+    _fields_ = [("world_min", Vec3), ("world_max", Vec3), ("width", C.c_uint32), ("height", C.c_uint32), ("depth", C.c_uint32)]
+
+
+class Sample3(C.Structure):
+    """fs3_sample (include/fluidsim.h): 40 bytes."""
+    _fields_ = [("density", C.c_float), ("weight", C.c_float), ("velocity", Vec3), ("gradient", Vec3),
+                ("neighbours", C.c_uint32), ("cell", C.c_uint32)]
+
+
 class SlabConfig(C.Structure):
     _fields_ = [
         ("own_lo", C.c_uint32), ("own_hi", C.c_uint32),
@@ -157,6 +168,10 @@ assert PARTICLE_DTYPE.itemsize == 32
 # fs_sample as a numpy structured dtype (offsets 0/4/8/16/20).
 SAMPLE_DTYPE = np.dtype([("density", "<f4"), ("weight", "<f4"), ("velocity", "<f4", (2,)), ("neighbours", "<u4"), ("cell", "<u4")])
 assert SAMPLE_DTYPE.itemsize == 24 and C.sizeof(Sample) == 24
+# fs3_sample as a numpy structured dtype (offsets 0/4/8/20/32/36).
+SAMPLE3_DTYPE = np.dtype([("density", "<f4"), ("weight", "<f4"), ("velocity", "<f4", (3,)), ("gradient", "<f4", (3,)),
+                          ("neighbours", "<u4"), ("cell", "<u4")])
+assert SAMPLE3_DTYPE.itemsize == 40 and C.sizeof(Sample3) == 40 and C.sizeof(View3) == 36
 assert C.sizeof(Uniform) == 120
 assert C.sizeof(Settings) == 28
 assert C.sizeof(TickSettings) == 60
@@ -277,6 +292,10 @@ PROTOTYPES = {
     "fs3_timed_steps": (C.c_int, [_P, C.POINTER(TickSettings3), C.c_uint32, C.POINTER(C.c_double)]),
     "fs3_profile_enable": (C.c_int, [_P, C.c_int]),
     "fs3_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]),
+    "fs3_stream": (_P, [_P]),
+    "fs3_sample_points": (C.c_int, [_P, _P, C.c_size_t, _P]),
+    "fs3_sample_points_device": (C.c_int, [_P, _P, C.c_size_t, _P]),
+    "fs3_sample_grid": (C.c_int, [_P, C.POINTER(View3), _P]),
     "fs_selftest_constdiv": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_uint32)]),
     "fs_sort_plan_read": (C.c_int, [C.c_void_p, C.POINTER(SortPlanInfo)]),
     "fs_selftest_sort_policy": (C.c_int, [C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t,

@@ -53,6 +53,8 @@ struct fs_sim3 {
     DevArray<fs3_particle> aos;
     fsd::ConstDiv div_2h3{}, div_h2{};
     bool share_div = false;      // all create-time proofs of the shared-denominator path succeeded
+    float mass = 0.0f;           // of the tick of the last step enqueued: what field sampling weighs with
+    bool sample_stale = true;    // no step enqueued since create / the last upload: records and cell table do not belong together
 
     // the arrays as the launchers see them (fs_3d.h): the force pass writes the new positions into the spare buffer
     fsd::Arrays3 arrays() const {
@@ -131,6 +133,7 @@ static fs_status enqueue3(fs_sim3* s, const fs3_tick_settings* t) {
     hipEvent_t done = ev ? nullptr : s->sortp.flight_event();
     launch3_force(st, P, A, tol, done);
     std::swap(s->pos, s->pos_s);
+    s->mass = t->mass; s->sample_stale = false;
     if (ev) { FS_HIP(hipEventRecord(ev[5], st)); FS_HIP(hipEventRecord(ev[6], st)); /* FS_PASS_BOUNDARY: slab handles only */ s->prof.pending += 1; }
     if (ev) FS_HIP(s->sortp.step_enqueued(st));
     else s->sortp.step_bound();
@@ -224,6 +227,7 @@ static fs_status sort_health3(fs_sim3* s) {
     return FS_OK;
 }
 fs_status fs3_sync(fs_sim3* s) { if (!s) return fail(FS_ERR_INVALID, "null"); FS_HIP(hipStreamSynchronize(s->stream)); return sort_health3(s); }
+void* fs3_stream(const fs_sim3* s) { return s ? (void*)s->stream.h : nullptr; }
 uint32_t fs3_tick_count(const fs_sim3* s) { return s ? s->tick : 0; }
 uint32_t fs3_particle_count(const fs_sim3* s) { return s ? s->n : 0; }
 fs_status fs3_grid_dims(const fs_sim3* s, uint32_t* w, uint32_t* h, uint32_t* d) {
@@ -248,6 +252,7 @@ fs_status fs3_upload_particles(fs_sim3* s, const fs3_particle* src, size_t n) {
     if (n) fsd::launch3_import(s->stream, (uint32_t)n, s->arrays());
     FS_HIP(hipStreamSynchronize(s->stream));
     s->sortp.touched();
+    if (n) s->sample_stale = true;
     return FS_OK;
 }
 fs_status fs3_timed_steps(fs_sim3* s, const fs3_tick_settings* t, uint32_t steps, double* ms_total) {
@@ -266,6 +271,101 @@ fs_status fs3_profile_enable(fs_sim3* s, int enable) { if (!s) return fail(FS_ER
 fs_status fs3_profile_read(fs_sim3* s, double ms[FS_PASS_COUNT], uint64_t* steps, int reset) {
     if (!s || !ms) return fail(FS_ERR_INVALID, "null argument");
     return s->prof.read(ms, steps, reset);
+}
+
+// ---- 3D field sampling --------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// Argument and state checks the three calls share, in the order the header lists them.  *go = false: n == 0, nothing to do.
+fs_status sample3_check(fs_sim3* s, const void* points_or_view, size_t n, const void* out, bool* go) {
+    *go = false;
+    if (n == 0) return FS_OK;
+    if (!points_or_view || !out) return fail(FS_ERR_INVALID, "null argument");
+    if (n > ((size_t)1 << 28)) return fail(FS_ERR_INVALID, "sampling: more than 2^28 points");
+    if (s->sample_stale) return fail(FS_ERR_INVALID, "sampling needs a step since create and since the last upload of particles");
+    *go = true;
+    return FS_OK;
+}
+
+// Enqueue the kernel on the simulation's stream.  points_dev == nullptr: the voxel centres of `view`.
+fs_status sample3_enqueue(fs_sim3* s, const fs_vec3* points_dev, const fs3_view* view, size_t n, fs3_sample* out_dev) {
+    static_assert(sizeof(fs3_sample) == 40 && sizeof(fs_vec3) == 12, "fs3_sample is 40 bytes, fs_vec3 three floats");
+    const float h = s->st.smoothing_radius;
+    const float PI3 = 3.14159265359f;
+    fsd::Params3 P;
+    std::memset(&P, 0, sizeof P);
+    P.n = s->n; P.gw = s->gw; P.gh = s->gh; P.gd = s->gd; P.ncell = s->ncell;
+    P.h = h; P.h2 = h * h;
+    P.bx = s->st.size.x * 0.5f; P.by = s->st.size.y * 0.5f; P.bz = s->st.size.z * 0.5f;
+    P.mass = s->mass;
+    P.poly6 = 315.0f / (64.0f * PI3 * std::pow(h, 9.0f));      // enqueue3's, host libm
+    fsd::Sample3Query Q;
+    Q.n = (uint32_t)n;
+    Q.points = (const float*)points_dev;
+    if (view) {
+        Q.wmin = make_float3(view->world_min.x, view->world_min.y, view->world_min.z);
+        Q.wmax = make_float3(view->world_max.x, view->world_max.y, view->world_max.z);
+        Q.width = view->width; Q.height = view->height; Q.depth = view->depth;
+    }
+    Q.out = out_dev;
+    fsd::launch3_sample(s->stream, P, s->arrays(), Q);
+    FS_HIP(hipGetLastError());
+    return FS_OK;
+}
+
+// The blocking forms: device staging for the points (none for a grid) and the records, freed on return.
+fs_status sample3_host(fs_sim3* s, const fs_vec3* points, const fs3_view* view, size_t n, fs3_sample* out) {
+    FS_HIP(hipSetDevice(s->device));
+    DevArray<fs_vec3> dpts;
+    DevArray<fs3_sample> dout;
+    hipError_t e = points ? dpts.alloc(n) : hipSuccess;
+    if (e == hipSuccess) e = dout.alloc(n);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FS_ERR_OOM, "sampling: device staging");
+    }
+    fs_status r = FS_OK;
+    if (points) e = hipMemcpyAsync(dpts.p, points, n * sizeof(fs_vec3), hipMemcpyHostToDevice, s->stream);
+    if (e == hipSuccess) {
+        r = sample3_enqueue(s, dpts.p, points ? nullptr : view, n, dout.p);
+        if (r == FS_OK) e = hipMemcpyAsync(out, dout.p, n * sizeof(fs3_sample), hipMemcpyDeviceToHost, s->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(s->stream);      // before the staging is freed, whatever happened
+    if (e == hipSuccess) e = es;
+    if (r == FS_OK && e != hipSuccess) r = fail(FS_ERR_DEVICE, hipGetErrorString(e));
+    if (r != FS_OK) return r;
+    return sort_health3(s);
+}
+}  // namespace
+extern "C" {
+
+fs_status fs3_sample_points(fs_sim3* s, const fs_vec3* points, size_t n, fs3_sample* out) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    bool go;
+    const fs_status r = sample3_check(s, points, n, out, &go);
+    if (r != FS_OK || !go) return r;
+    return sample3_host(s, points, nullptr, n, out);
+}
+
+fs_status fs3_sample_points_device(fs_sim3* s, const fs_vec3* points_dev, size_t n, fs3_sample* out_dev) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    bool go;
+    const fs_status r = sample3_check(s, points_dev, n, out_dev, &go);
+    if (r != FS_OK || !go) return r;
+    FS_HIP(hipSetDevice(s->device));
+    return sample3_enqueue(s, points_dev, nullptr, n, out_dev);
+}
+
+fs_status fs3_sample_grid(fs_sim3* s, const fs3_view* view, fs3_sample* out) {
+    if (!s || !view) return fail(FS_ERR_INVALID, "null argument");
+    const uint64_t wh = (uint64_t)view->width * view->height;
+    if (wh == 0 || view->depth == 0 || wh > (1ull << 28) || wh * view->depth > (1ull << 28))
+        return fail(FS_ERR_INVALID, "bad grid size");
+    const size_t n = (size_t)(wh * view->depth);
+    bool go;
+    const fs_status r = sample3_check(s, view, n, out, &go);
+    if (r != FS_OK || !go) return r;
+    return sample3_host(s, nullptr, view, n, out);
 }
 
 }  // extern "C"

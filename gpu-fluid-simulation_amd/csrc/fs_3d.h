@@ -37,7 +37,7 @@ struct Arrays3 {
 };
 
 // Predict + cell key of the 3D step, defined once for k3_predict_key, k3_reorder (kernels_3d.hip) and the sort's fused key
-// generation (kernels_sort.hip keygen3).  K: anything with dt, h, bx, by, bz, gw, gh (Params3, KeyGen3).
+// generation (kernels_sort.hip keygen3); the cell coordinates alone also for a query point (kernels_sample3d.hip).  K: anything with dt, h, bx, by, bz, gw, gh (Params3, KeyGen3).
 template <class K>
 __device__ __forceinline__ float4 predict3(const K& P, float4 p, float4 v) {
     float4 r;
@@ -48,10 +48,15 @@ __device__ __forceinline__ float4 predict3(const K& P, float4 p, float4 v) {
     return r;
 }
 template <class K>
+__device__ __forceinline__ void cell_xyz3(const K& P, float4 pt, uint32_t* cx, uint32_t* cy, uint32_t* cz) {
+    *cx = f32_to_u32_sat(floorf(__fdiv_rn(pt.x + P.bx, P.h))) + 1u;
+    *cy = f32_to_u32_sat(floorf(__fdiv_rn(pt.y + P.by, P.h))) + 1u;
+    *cz = f32_to_u32_sat(floorf(__fdiv_rn(pt.z + P.bz, P.h))) + 1u;
+}
+template <class K>
 __device__ __forceinline__ uint32_t cell_key3(const K& P, float4 pt) {
-    const uint32_t cx = f32_to_u32_sat(floorf(__fdiv_rn(pt.x + P.bx, P.h))) + 1u;
-    const uint32_t cy = f32_to_u32_sat(floorf(__fdiv_rn(pt.y + P.by, P.h))) + 1u;
-    const uint32_t cz = f32_to_u32_sat(floorf(__fdiv_rn(pt.z + P.bz, P.h))) + 1u;
+    uint32_t cx, cy, cz;
+    cell_xyz3(P, pt, &cx, &cy, &cz);
     return (cz * P.gh + cy) * P.gw + cx;
 }
 
@@ -63,5 +68,16 @@ void launch3_density(hipStream_t st, const Params3& P, const Arrays3& A, bool to
 void launch3_force(hipStream_t st, const Params3& P, const Arrays3& A, bool tol, hipEvent_t done);
 void launch3_import(hipStream_t st, uint32_t n, const Arrays3& A);   // aos -> pos, pred, vel, key
 void launch3_export(hipStream_t st, uint32_t n, const Arrays3& A);   // ... and back
+
+// 3D field sampling (kernels_sample3d.hip): n queries against pred (.w = density), vel and cs as the last step
+// left them.  P: n, gw, gh, gd, h, h2, bx, by, bz, mass, poly6.  Device pointers; host side only.
+struct Sample3Query {
+    uint32_t n = 0;                    // points, or width * height * depth
+    const float* points = nullptr;     // n fs_vec3, or nullptr: the voxel centres of the view below
+    float3 wmin{}, wmax{};
+    uint32_t width = 0, height = 0, depth = 0;
+    void* out = nullptr;               // n fs3_sample records
+};
+void launch3_sample(hipStream_t st, const Params3& P, const Arrays3& A, const Sample3Query& Q);
 
 }  // namespace fsd

@@ -100,6 +100,13 @@ pub struct Settings3 { pub particle_count: u32, pub particle_spacing: f32, pub s
 pub struct TickSettings3 { pub delta: f32, pub gravity: Vec3, pub mass: f32, pub pressure_constant: f32, pub rest_density: f32, pub damping_factor: f32, pub viscosity_coefficient: f32 }
 #[repr(C)] #[derive(Clone, Copy, Default, Debug)]
 pub struct Particle3 { pub position: Vec3, pub predicted_position: Vec3, pub velocity: Vec3, pub density: f32, pub grid: u32, pub pad: u32 }
+/// fs3_sample: the 3D fluid at one query point (build extension, include/fluidsim.h "3D field sampling"); 40 bytes.
+#[repr(C)] #[derive(Clone, Copy, Default, Debug, PartialEq)]
+pub struct Sample3 { pub density: f32, pub weight: f32, pub velocity: Vec3, pub gradient: Vec3, pub neighbours: u32, pub cell: u32 }
+const _: () = assert!(std::mem::size_of::<Sample3>() == 40);
+/// fs3_view: a box and its voxel counts; a slice is `depth == 1` with `world_min.z == world_max.z`.
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct View3 { pub world_min: Vec3, pub world_max: Vec3, pub width: u32, pub height: u32, pub depth: u32 }
 const _: () = assert!(std::mem::size_of::<Particle3>() == 48);
 
 #[repr(C)] pub struct fs_sim { _p: [u8; 0] }
@@ -210,6 +217,10 @@ extern "C" {
     fn fs3_timed_steps(sim: *mut fs_sim3, tick: *const TickSettings3, steps: u32, ms_total: *mut f64) -> c_int;
     fn fs3_profile_enable(sim: *mut fs_sim3, enable: c_int) -> c_int;
     fn fs3_profile_read(sim: *mut fs_sim3, ms: *mut f64, steps: *mut u64, reset: c_int) -> c_int;
+    fn fs3_stream(sim: *const fs_sim3) -> *mut c_void;
+    fn fs3_sample_points(sim: *mut fs_sim3, points: *const Vec3, n: usize, out: *mut Sample3) -> c_int;
+    fn fs3_sample_points_device(sim: *mut fs_sim3, points_dev: *const Vec3, n: usize, out_dev: *mut Sample3) -> c_int;
+    fn fs3_sample_grid(sim: *mut fs_sim3, view: *const View3, out: *mut Sample3) -> c_int;
     // ResizableBuffer<T> (src/buffer.rs)
     fn fs_buffer_create(device: c_int, elem_size: usize, len: usize, name: *const c_char, out: *mut *mut fs_buffer) -> c_int;
     fn fs_buffer_resize(buf: *mut fs_buffer, new_cap: usize, resized: *mut c_int) -> c_int;
@@ -558,6 +569,26 @@ impl FluidSimulation3D {
         let (mut ms, mut steps) = ([0f64; PASS_COUNT], 0u64);
         check(unsafe { fs3_profile_read(self.raw, ms.as_mut_ptr(), &mut steps, reset as c_int) }); (ms, steps)
     }
+}
+impl FluidSimulation3D {
+    /// Build extension: 3D field sampling (include/fluidsim.h).  Density, Shepard weight, un-normalised velocity sum, density
+    /// gradient (`-gradient` is the outward normal), neighbour count and cell of the fluid at `points`.  Needs a tick since
+    /// `new` / the last upload.  Coherently ordered points are sampled several times faster than shuffled ones.
+    pub fn sample(&mut self, points: &[Vec3]) -> Vec<Sample3> {
+        let mut out = vec![Sample3::default(); points.len()];
+        check(unsafe { fs3_sample_points(self.raw, points.as_ptr(), points.len(), out.as_mut_ptr()) }); out
+    }
+    /// `sample` at the voxel centres of `view`, voxel (i, j, k) at `(k * height + j) * width + i`; bit-identical to `sample` there.
+    pub fn sample_grid(&mut self, view: &View3) -> Vec<Sample3> {
+        let mut out = vec![Sample3::default(); view.width as usize * view.height as usize * view.depth as usize];
+        check(unsafe { fs3_sample_grid(self.raw, view, out.as_mut_ptr()) }); out
+    }
+    /// Device pointers on the simulation's device; enqueued on its stream after the ticks in flight, non-blocking.
+    /// The buffers must stay valid until the stream has passed the call.
+    pub unsafe fn sample_device(&mut self, points_dev: *const Vec3, n: usize, out_dev: *mut Sample3) {
+        check(fs3_sample_points_device(self.raw, points_dev, n, out_dev));
+    }
+    pub fn stream(&self) -> *mut c_void { unsafe { fs3_stream(self.raw) } }
 }
 impl Drop for FluidSimulation3D { fn drop(&mut self) { unsafe { fs3_destroy(self.raw) } } }
 

@@ -534,6 +534,64 @@ fs_status fs3_reference_lattice(const fs3_settings* settings, fs_vec3 offset, fs
 fs_status fs3_timed_steps(fs_sim3* sim, const fs3_tick_settings* tick, uint32_t steps, double* ms_total);
 fs_status fs3_profile_enable(fs_sim3* sim, int enable);
 fs_status fs3_profile_read(fs_sim3* sim, double ms[FS_PASS_COUNT], uint64_t* steps, int reset);
+/* The simulation's HIP stream (hipStream_t): every fs3_* call of this handle is enqueued on it, as fs_stream for a 2D handle. */
+void* fs3_stream(const fs_sim3* sim);
+
+/* ------------------------------------------------ 3D field sampling (build extension, opt-in by being called) */
+/* The 3D counterpart of "field sampling" above, with the density gradient (the surface normal of an iso-surface extractor or
+ * ray-marcher) and with volumes and slices as the grid form.  The result is a pure function of the state an fs_sim3 holds after
+ * its last step: the records p[k] that fs3_download_particles returns (sorted by `grid` after a step), the grid dimensions, the
+ * settings, and the `mass` of the tick passed to the last fs3_step / fs3_timed_steps (the handle keeps it).  It holds in both
+ * math modes.  With n = particle_count, h = smoothing_radius, h2 = h * h, m = mass,
+ * C6 = 315.0f / (64.0f * PI3 * powf(h, 9.0f)) (the oracle's and the step's poly6: host libm, PI3 = 3.14159265359f),
+ * Cg = 6.0f * C6, everything f32 without contraction, for a query point x:
+ *     (cx, cy, cz) = u32_sat(floor((x.a + size.a * 0.5f) / h)) + 1   per axis, TRUE division, wrapping + 1   (oracle cell_xyz)
+ *     cell = (cz * grid_h + cy) * grid_w + cx                                               wrapping u32
+ *     density = weight = +0.0f; velocity = gradient = (+0,+0,+0); neighbours = 0
+ *     for oz in -1,0,1: for oy in -1,0,1: for ox in -1,0,1:
+ *         X = cx+ox, Y = cy+oy, Z = cz+oz (wrapping u32); skipped when X >= grid_w or Y >= grid_h or Z >= grid_d
+ *         id = (Z * grid_h + Y) * grid_w + X
+ *         for the slots k with p[k].grid == id, ascending:
+ *             d = p[k].predicted_position - x;  r2 = d.x*d.x + d.y*d.y + d.z*d.z
+ *             if not (r2 > h2):
+ *                 e = h2 - r2;  W = ((C6 * e) * e) * e
+ *                 density += m * W
+ *                 g = m * ((Cg * e) * e);  gradient.a += g * d.a          (= grad_x of sum m W; the outward normal is -gradient)
+ *                 t = (m / p[k].density) * W                              IEEE division by the stored density
+ *                 weight += t;  velocity.a += t * p[k].velocity.a;  neighbours += 1
+ * A skipped candidate is a branch, not an added zero: velocity and gradient terms can be -0.  Velocity is returned
+ * un-normalised; dividing by `weight` gives the Shepard value.  The known answer that ties the sampler to the step is the
+ * density identity, in FS_MATH_IEEE: at p[i].predicted_position, fmax(fmax(density, 1.19209290e-07f), 0.1f) equals p[i].density
+ * bit for bit — walk order and term are those of oracle/sph_oracle3d.cpp step3, which adds +0 for candidates outside the radius,
+ * and that cannot change a non-negative sum.  Non-finite coordinates give unspecified values and no out-of-bounds access.
+ *
+ * fs3_sample_points: host pointers, blocking.
+ * fs3_sample_points_device: device pointers on the handle's device; enqueued on fs3_stream(sim) after the steps in flight;
+ *   stream-ordered, non-blocking, no allocation, no host read.  The buffers must stay valid until the stream has passed the call.
+ * fs3_sample_grid: host output, blocking.  Voxel (i, j, k) is the point
+ *   world_min + (((float)i + 0.5f) / (float)width) * (world_max - world_min), likewise per axis (fs_sample_grid's expression),
+ *   stored at out[(k * height + j) * width + i]; bit-identical to fs3_sample_points on those points.  A slice is depth == 1 with
+ *   world_min.z == world_max.z: the expression then gives exactly that z.
+ * Query order decides the speed, not the result (see "field sampling").  Nothing is sorted behind the caller's back.
+ * Checks, in this order: NULL handle -> FS_ERR_INVALID; (grid) NULL view, a zero extent, or width * height * depth > 2^28 ->
+ * FS_ERR_INVALID; n == 0 -> FS_OK, nothing touched; NULL points / out -> FS_ERR_INVALID; n > 2^28 -> FS_ERR_INVALID; no step
+ * enqueued since create or since the last fs3_upload_particles with n > 0 (a partial upload counts: records and cell table would
+ * not belong together) -> FS_ERR_INVALID.  See DESIGN.md §14. */
+typedef struct fs3_sample {       /* 40 bytes; offsets 0/4/8/20/32/36 */
+    float density;                /* sum m W */
+    float weight;                 /* sum (m / rho_j) W: the Shepard denominator */
+    fs_vec3 velocity;             /* sum (m / rho_j) W v_j, un-normalised */
+    fs_vec3 gradient;             /* grad_x of sum m W */
+    uint32_t neighbours;          /* candidates with r2 <= h2 */
+    uint32_t cell;                /* cell id of the query point */
+} fs3_sample;
+typedef struct fs3_view {
+    fs_vec3 world_min, world_max;
+    uint32_t width, height, depth;
+} fs3_view;
+fs_status fs3_sample_points(fs_sim3* sim, const fs_vec3* points, size_t n, fs3_sample* out);
+fs_status fs3_sample_points_device(fs_sim3* sim, const fs_vec3* points_dev, size_t n, fs3_sample* out_dev);
+fs_status fs3_sample_grid(fs_sim3* sim, const fs3_view* view, fs3_sample* out);
 
 /* ------------------------------------------------------- ResizableBuffer */
 /* ResizableBuffer<T>::new (src/buffer.rs:27-43). */
