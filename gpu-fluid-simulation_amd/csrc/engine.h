@@ -187,9 +187,9 @@ struct fs_sim : fsd::HandleQueues, fsd::ParticleArrays {
     int trk_channels = -1;          // -1: off
     int trk_alloc_channels = 0;     // channels the attr arrays were allocated for
     int trk_cur = 0;
-    // field sampling (build extension): the records and the cell table belong together — a step has been enqueued
-    // since create and since the last fs_upload_particles / fs_upload_start_indices
-    bool sample_ready = false;
+    // what walks the cell table off the step path (fs_render_density; field sampling): the records and the cell
+    // table belong together — a step has been enqueued since create and since the last fs_upload_particles / fs_upload_start_indices
+    bool walk_ready = false;
 
     fsd::ConstDiv div_2h3{}, div_h2{};   // exact constant divisions of the force pass, proven at create
     fsd::ConstDiv div_h{};               // ... and of the cell coordinates (x / h), over the numerators clamped positions give

@@ -358,7 +358,7 @@ static fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
     L.quad_entries = s->sortp.quad_entries();
     fsd::launch_force(st, P, A, L);
     if (pos_by_src) std::swap(s->pos, s->pos_s);   // the spare buffer now holds the state
-    s->sample_ready = true;
+    s->walk_ready = true;
     if (s->aos_live) s->aos_tick = s->tick;
     if (prof) {
         FS_HIP(hipEventRecord(ev[5], st));
@@ -531,7 +531,7 @@ fs_status fs_upload_particles(fs_sim* s, const fs_particle* src, size_t n) {
     FS_HIP(hipStreamSynchronize(s->stream));
     s->aos_tick = 0xFFFFFFFFu;      // the live view (if any) no longer matches the state: re-materialise on demand
     s->sortp.touched();             // an arbitrary order: the per-stage launches stand by until reports pass again
-    s->sample_ready = false;
+    s->walk_ready = false;
     return FS_OK;
 }
 
@@ -552,7 +552,7 @@ fs_status fs_upload_start_indices(fs_sim* s, const uint32_t* src, size_t n) {
     FS_HIP(hipSetDevice(s->device));
     if (n) FS_HIP(hipMemcpyAsync(s->start_ref.p, src, n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
     FS_HIP(hipStreamSynchronize(s->stream));
-    s->sample_ready = false;
+    s->walk_ready = false;
     return FS_OK;
 }
 
@@ -623,7 +623,8 @@ fs_status fs_render_density(fs_sim* s, const fs_view* view, float* rgba_host) {
     FS_JOIN(s);
     if (view->width == 0 || view->height == 0 || (uint64_t)view->width * view->height > (1ull << 28))
         return fail(FS_ERR_INVALID, "bad image size");
-    if (s->tick == 0) return fail(FS_ERR_INVALID, "render needs at least one fs_step (cell table not built yet)");
+    // an upload writes the records in upload order under the previous sort's cell table: a walk would pair old ranges with new arrays
+    if (!s->walk_ready) return fail(FS_ERR_INVALID, "render needs a step since create and since the last upload of particles or start indices");
     FS_HIP(hipSetDevice(s->device));
     const size_t npix = (size_t)view->width * view->height;
     float4* dimg = nullptr;
@@ -638,7 +639,7 @@ fs_status fs_render_density(fs_sim* s, const fs_view* view, float* rgba_host) {
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     (void)hipFree(dimg);
     if (e != hipSuccess) return fail(FS_ERR_DEVICE, hipGetErrorString(e));
-    return FS_OK;
+    return sort_health(s);        // the image is in `rgba_host` either way; FS_ERR_DEVICE says the order it was walked in is not to be trusted
 }
 
 fs_status fs_set_surface_tension(fs_sim* s, int enable) {
@@ -777,7 +778,7 @@ fs_status sample_check(fs_sim* s, const void* points_or_view, size_t n, const vo
     if (n == 0) return FS_OK;
     if (!points_or_view || !out) return fail(FS_ERR_INVALID, "null argument");
     if (n > ((size_t)1 << 28)) return fail(FS_ERR_INVALID, "sampling: more than 2^28 points");
-    if (!s->sample_ready) return fail(FS_ERR_INVALID, "sampling needs a step since create and since the last upload of particles or start indices");
+    if (!s->walk_ready) return fail(FS_ERR_INVALID, "sampling needs a step since create and since the last upload of particles or start indices");
     *go = true;
     return FS_OK;
 }

@@ -271,17 +271,18 @@ __global__ __launch_bounds__(FS_BLOCK) void k_render_density(StepParams P, float
     pt.y = wmin.y + __fdiv_rn((float)j + 0.5f, (float)height) * (wmax.y - wmin.y);
     const uint32_t lo_fix = quirk_lo_fix(P, pairs, cs, start_ref);
     uint32_t cx, cy;
-    xy_local(P, pt, &cx, &cy);
+    xy_local(P, pt, &cx, &cy);         // P.div_h.ok == 0 (launch_render_density): the true division
     float density = 0.0f, vfac = 0.0f;
     const float denom = P.sqr_radius / 2.0f;                            // fluid_shader.wgsl:66
-    // not row_range (fs_neighbours.h), on purpose: five columns clamped to the grid, reference-layout ids; the stale-start rule is shared
+    // not row_range (fs_neighbours.h), on purpose: five columns clamped to the grid, reference-layout ids; the stale-start rule is shared.
+    // The columns cx - 2 .. cx + 2 that lie in the grid (X = (u32)(cx + ox) < grid_w), in unsigned arithmetic throughout: whatever
+    // (cx, cy) a coordinate gives, xlo < xhi <= grid_w and y < grid_h, so every cs[] index is <= ncell.
+    const uint32_t xlo = cx < 2u ? 0u : cx - 2u;
+    const bool no_column = xlo >= P.grid_w;                             // (so cx < grid_w + 2: cx + 3 below does not wrap)
+    const uint32_t xhi = no_column ? xlo : (cx + 3u < P.grid_w ? cx + 3u : P.grid_w);
     for (int oy = -2; oy < 3; ++oy) {                                   // :39-40 (5x5 cells)
         const uint32_t y = cy + (uint32_t)oy;
-        if (y >= P.grid_h) continue;
-        const int32_t xl = (int32_t)cx - 2, xh = (int32_t)cx + 3;
-        const uint32_t xlo = xl < 0 ? 0u : (uint32_t)xl;
-        const uint32_t xhi = xh > (int32_t)P.grid_w ? P.grid_w : (uint32_t)xh;
-        if (xlo >= xhi) continue;
+        if (y >= P.grid_h || no_column) continue;
         uint32_t a = cs[y * P.grid_w + xlo];
         const uint32_t b = cs[y * P.grid_w + xhi];
         if (a == 0u) a = lo_fix;
@@ -307,9 +308,11 @@ __global__ __launch_bounds__(FS_BLOCK) void k_render_density(StepParams P, float
     out[pix] = make_float4(br + edge, bg + edge, bb + edge, fminf(fmaxf(interior, 0.0f), 1.0f));
 }
 
-void launch_render_density(hipStream_t st, const StepParams& P, float2 wmin, float2 wmax, uint32_t width,
+void launch_render_density(hipStream_t st, const StepParams& P_in, float2 wmin, float2 wmax, uint32_t width,
                            uint32_t height, const float2* pred, const float2* vel, const uint32_t* cs,
                            const uint32_t* start_ref, const u64* pairs, float4* out) {
+    StepParams P = P_in;
+    P.div_h.ok = 0;                    // the 3-instruction quotient is proven for clamped positions only; a view may leave the domain
     const uint32_t npix = width * height;
     hipLaunchKernelGGL(k_render_density, dim3((npix + FS_BLOCK - 1) / FS_BLOCK), dim3(FS_BLOCK), 0, st, P, wmin, wmax,
                        width, height, pred, vel, cs, start_ref, pairs, out);

@@ -370,7 +370,8 @@ impl FluidSimulation {
         let mut h = MemHandle { ipc: [0; 64], bytes: 0, device: 0, dmabuf_fd: -1 };
         check(unsafe { fs_export_handle(self.raw, which, &mut h) }); h
     }
-    /// Headless `fluid_shader.wgsl:27-102`: width*height RGBA f32.
+    /// Headless `fluid_shader.wgsl:27-102`: width*height RGBA f32.  Needs a `tick` since create and since the last upload
+    /// of particles or start indices (include/fluidsim.h).
     pub fn render_density(&mut self, view: &View) -> Vec<f32> {
         let mut v = vec![0f32; 4 * view.width as usize * view.height as usize];
         check(unsafe { fs_render_density(self.raw, view, v.as_mut_ptr()) }); v

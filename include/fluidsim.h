@@ -249,7 +249,18 @@ fs_status fs_generate_force_field(fs_sim* sim, int device, const uint8_t* image,
  * speed, colour ramp.  The reference draws a full-screen quad through an orthographic
  * projection over the whole domain with +y down (src/renderer.rs:558-561); `fs_view` is that
  * mapping made explicit: pixel (i, j) samples world_min + ((i+0.5)/width, (j+0.5)/height) *
- * (world_max - world_min).  Output: width*height RGBA f32 (straight alpha), host memory. */
+ * (world_max - world_min).  Output: width*height RGBA f32 (straight alpha), host memory.
+ *
+ * The pixel's cell is funcs.wgsl:212-214 in f32 with the true division (saturating f32 -> u32, so a point left of or above
+ * the domain falls into column / row 1); window cell (X, Y) = ((u32)(cx + ox), (u32)(cy + oy)) is skipped when X >= grid_w
+ * or Y >= grid_h.  A view may overhang the domain, lie outside it (every pixel 0), be flipped (world_max < world_min) or
+ * degenerate (world_min == world_max).  For coordinates that are not finite or larger than 2^30 * smoothing_radius in
+ * magnitude the pixel values are unspecified; no memory outside the handle's arrays is read for any coordinate.
+ *
+ * Single-domain handles only (FS_ERR_UNSUPPORTED on a slab handle).  FS_ERR_INVALID before the first fs_step and between
+ * fs_upload_particles / fs_upload_start_indices and the next fs_step: an upload leaves the records in upload order under
+ * the previous step's cell table (the precondition of fs_sample_*).  FS_ERR_DEVICE after the sort's stand-by kernel
+ * reported a grid-barrier time-out (the handle is dead, as for fs_step). */
 typedef struct fs_view {
     fs_vec2 world_min, world_max;
     uint32_t width, height;
