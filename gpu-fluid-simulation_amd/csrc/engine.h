@@ -1,6 +1,8 @@
-// engine.h — what the host files of the C ABI share beyond fs_host.h: the 2D simulation handle (engine.hip: the plain handle,
-// the opt-in features, the self-tests; engine_slab.hip: the multi-GPU slab handles), the step parameters, and the create-time
-// device check and proofs (also used by engine_3d.hip).  Internal: include/fluidsim.h is the interface.
+// engine.h — what the host files of the C ABI share beyond fs_host.h: the 2D simulation handle and the state of each of its
+// features, the step parameters, and the device check and create-time proofs (also used by engine_3d.hip).  The handle's files:
+// engine.hip (life cycle, step, transfers, renderer hand-off), engine_features.hip (surface tension, particle tracking),
+// engine_query.hip (density render, field sampling), engine_selftest.hip (self-tests, read-outs), engine_slab.hip (the
+// multi-GPU slab handles).  Internal: include/fluidsim.h is the interface.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -81,6 +83,40 @@ struct PrebuiltMessages {
     void built(const fs_slab_config& c, float d) { valid = true; delta = d; lo = c.own_lo; hi = c.own_hi; }
 };
 
+// Opt-in surface tension (build extension; single-domain handles): fs_set_surface_tension, engine_features.hip.
+struct SurfaceTension {
+    DevArray<float2> stf;           // per sorted slot: the last ST step's force (allocated on first enable)
+    bool on = false;
+    bool valid = false;             // an ST step has been enqueued since create / since ST was last enabled
+    // This step's pass, between the density and the force launches; returns what the force launch adds (ForceLaunch::st_in).
+    const float2* enqueue(hipStream_t st, const StepParams& P, const StepArrays& A, const fs_uniform& u) {
+        if (!on) return nullptr;
+        launch_surface_tension(st, P, A, u.surface_tension_coefficient, u.surface_tension_treshold, u.poly6_kernel_derivative, stf.p);
+        valid = true;
+        return stf.p;
+    }
+};
+
+// Opt-in particle tracking (build extension; single-domain handles): fs_track_enable, engine_features.hip.  Two
+// sets that swap roles every step: [cur] holds the ids / channels in the order of the last enqueued step.
+struct Tracking {
+    DevArray<uint32_t> id[2];
+    DevArray<float> attr[2];        // channel c at c * capacity
+    int channels = -1;              // -1: off
+    int alloc_channels = 0;         // channels the attr arrays were allocated for
+    int cur = 0;
+    bool on() const { return channels >= 0; }
+    // of the last enqueued step
+    uint32_t* ids() const { return id[cur].p; }
+    float* channel(int c, uint32_t capacity) const { return attr[cur].p + (size_t)c * capacity; }
+    // ids / channels follow this step's permutation (`pairs`, after the reorder pass)
+    void carry(hipStream_t st, uint32_t n, const u64* pairs, uint32_t capacity) {
+        if (!on()) return;
+        launch_track_carry(st, n, channels, pairs, id[cur].p, id[cur ^ 1].p, attr[cur].p, attr[cur ^ 1].p, capacity);
+        cur ^= 1;
+    }
+};
+
 // Everything only a slab (multi-GPU) handle has: engine_slab.hip.  Torn down like the handle itself, in reverse order of
 // declaration: the device arrays, then the events, the exchange stream last.
 struct SlabState {
@@ -153,8 +189,9 @@ struct SlabState {
 
 // Every resource is held by an owner (fs_host.h) and freed by `delete`.  Teardown order: members go in reverse order of
 // declaration, then the bases from right to left — so first a slab handle's own state (SlabState: its device arrays, its events,
-// its stream), then the device arrays (the members below, then ParticleArrays), then HandleQueues backwards: the events (profile
-// ring, sort policy, the named ones), and the streams last.  fs_destroy synchronises both streams before any of it.
+// its stream), then the device arrays (tracking's, surface tension's, the other members below, then ParticleArrays), then
+// HandleQueues backwards: the events (profile ring, sort policy, the named ones), and the streams last.  fs_destroy synchronises
+// both streams before any of it.
 struct fs_sim : fsd::HandleQueues, fsd::ParticleArrays {
     fs_settings settings{};
     fs_options opts{};
@@ -176,19 +213,11 @@ struct fs_sim : fsd::HandleQueues, fsd::ParticleArrays {
     fsd::DevArray<fs_particle> aos;      // lazily allocated 32-byte view
     bool aos_live = false;          // a hand-off is registered: the force pass writes the AoS records itself
     uint32_t aos_tick = 0xFFFFFFFFu;   // tick whose state the AoS view holds (only meaningful with aos_live)
-    // surface tension (build extension; single-domain handles): fs_set_surface_tension
-    fsd::DevArray<float2> stf;           // per sorted slot: the last ST step's force (allocated on first enable)
-    bool st_on = false;
-    bool st_valid = false;          // an ST step has been enqueued since create / since ST was last enabled
-    // particle tracking (build extension; single-domain handles): fs_track_enable.  Two sets that swap roles
-    // every step: [trk_cur] holds the ids / channels in the order of the last enqueued step.  Channel c: trk_attr[..] + c * capacity.
-    fsd::DevArray<uint32_t> trk_id[2];
-    fsd::DevArray<float> trk_attr[2];
-    int trk_channels = -1;          // -1: off
-    int trk_alloc_channels = 0;     // channels the attr arrays were allocated for
-    int trk_cur = 0;
-    // what walks the cell table off the step path (fs_render_density; field sampling): the records and the cell
-    // table belong together — a step has been enqueued since create and since the last fs_upload_particles / fs_upload_start_indices
+    fsd::SurfaceTension st;         // the opt-in features' state: one line each in enqueue_step
+    fsd::Tracking trk;
+    // what walks the cell table off the step path (engine_query.hip: fs_render_density; field sampling): the records
+    // and the cell table belong together — a step has been enqueued since create and since the last fs_upload_particles /
+    // fs_upload_start_indices
     bool walk_ready = false;
 
     fsd::ConstDiv div_2h3{}, div_h2{};   // exact constant divisions of the force pass, proven at create
@@ -238,10 +267,12 @@ StepParams make_params(const fs_sim& s, const fs_uniform& u, uint32_t own_lo = 0
 fs_status create_common(fs_sim* s);
 fs_status create_finish(fs_sim* s);
 // After a synchronisation of the stream: a barrier time-out of the sort's stand-by kernel makes the state undefined from
-// that step on — whoever is about to receive state (or a "finished" signal) must hear about it.
+// that step on — whoever is about to receive state (or a "finished" signal) must hear about it (SortPolicy::health).
 fs_status sort_health(fs_sim* s);
-// The create calls' device check: `device` names a HIP device of this process, which becomes the current one.
-fs_status use_device(int device);
+// The device check of every call that takes an ordinal: `device` names a HIP device of this process, which becomes the current
+// one.  No device at all is FS_ERR_DEVICE; an ordinal outside [0, ndev) is FS_ERR_INVALID from the create calls and
+// FS_ERR_DEVICE (`out_of_range`) from the calls that work without a handle.
+fs_status use_device(int device, fs_status out_of_range = FS_ERR_INVALID);
 // Create-time proofs, exhaustive, on the device; blocking.  prove_constdiv: x / c == div_const_fast(x, c, RN(1/c)) for every f32 x
 // with 2^-60 <= |x| <= hi (hi == 0: c, the force kernel's numerators); out->ok stays 0 where the proof does not apply, fails, or is not `enabled`.
 // prove_rcp_sqrt: the lean reciprocal / square root of the shared-denominator path over their whole ranges (both false under

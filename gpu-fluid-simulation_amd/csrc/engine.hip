@@ -1,5 +1,6 @@
-// engine.hip — host side of the C ABI (include/fluidsim.h): simulation handle,
-// SoA device state, pass chain on one HIP stream, AoS import/export.
+// engine.hip — host side of the C ABI (include/fluidsim.h), the core: the simulation handle's life cycle, SoA device state,
+// the pass chain of one step on one HIP stream, the particle / start-index / force-field transfers and the renderer hand-off.
+// What a handle offers beyond that: engine_features.hip, engine_query.hip, engine_selftest.hip; slab handles: engine_slab.hip.
 //
 // Mirrors FluidSimulation::{new,tick,accessors} (src/simulation.rs:139-564).
 // There is no CPU fallback: every entry point that computes requires a HIP device.
@@ -65,7 +66,7 @@ void host_lattice(const fs_settings& s, fs_vec2 off, fs_particle* dst, size_t n)
 
 }  // namespace
 
-// ---- shared with engine_slab.hip and engine_3d.hip (engine.h) --------------------------------------------------------
+// ---- shared with the other engine files (engine.h) -----------------------------------------------------------------------
 // src/simulation.rs:140-141
 void fsd::grid_dims(const fs_settings& s, uint32_t* gw, uint32_t* gh) {
     *gw = (uint32_t)((size_t)std::ceil(s.size.x / s.smoothing_radius) + 2);
@@ -185,11 +186,11 @@ StepParams fsd::make_params(const fs_sim& s, const fs_uniform& u, uint32_t own_l
     return P;
 }
 
-fs_status fsd::use_device(int device) {
+fs_status fsd::use_device(int device, fs_status out_of_range) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(FS_ERR_DEVICE, "no HIP device: the engine has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(FS_ERR_INVALID, "device ordinal out of range");
+    if (device < 0 || device >= ndev) return fail(out_of_range, "device ordinal out of range");
     FS_HIP(hipSetDevice(device));
     return FS_OK;
 }
@@ -287,9 +288,7 @@ fs_status fsd::create_finish(fs_sim* s) {
 
 fs_status fsd::sort_health(fs_sim* s) {
     if (s->slab || s->opts.sort_mode != FS_SORT_BITONIC) return FS_OK;
-    FS_HIP(s->sortp.check_timeout(s->sort_dirty.p, s->n));
-    if (s->sortp.dead) return fail(FS_ERR_DEVICE, "sort: the stand-by kernel's grid barrier timed out: the particle order is undefined from that step on; destroy the handle");
-    return FS_OK;
+    return s->sortp.health(s->sort_dirty.p, s->n);
 }
 
 static fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
@@ -332,12 +331,7 @@ static fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
         fsd::launch_counting_reorder(st, P, A);
     else
         fsd::launch_reorder(st, P, A, s->work_cap);
-    if (s->trk_channels >= 0) {    // particle tracking: ids / channels follow this step's permutation (inside the FS_PASS_REORDER interval)
-        const int in = s->trk_cur, out = in ^ 1;
-        fsd::launch_track_carry(st, s->n, s->trk_channels, s->pairs.p, s->trk_id[in].p, s->trk_id[out].p, s->trk_attr[in].p,
-                                s->trk_attr[out].p, s->capacity);
-        s->trk_cur = out;
-    }
+    s->trk.carry(st, s->n, s->pairs.p, s->capacity);     // particle tracking, if on (inside the FS_PASS_REORDER interval)
     if (prof) FS_HIP(hipEventRecord(ev[3], st));
     // strict / ulp modes: rho2.x IS the density; the separate 4-byte copy is only written in tolerance mode (rho2 = {P, 1/rho})
     s->rho_in_rho2 = P.fast_math != 2;
@@ -345,12 +339,7 @@ static fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
     fsd::launch_density(st, P, A);
     if (prof) FS_HIP(hipEventRecord(ev[4], st));
     fsd::ForceLaunch L = s->force_launch();
-    if (s->st_on) {                    // surface tension: its pass runs inside the FS_PASS_FORCE interval of the profile
-        fsd::launch_surface_tension(st, P, A, s->uniform.surface_tension_coefficient, s->uniform.surface_tension_treshold,
-                                    s->uniform.poly6_kernel_derivative, s->stf.p);
-        L.st_in = s->stf.p;
-        s->st_valid = true;
-    }
+    L.st_in = s->st.enqueue(st, P, A, s->uniform);       // surface tension, if on (inside the FS_PASS_FORCE interval)
     A.rho = s->rho.p;                  // (the force kernels take the array whatever the mode)
     if (pos_by_src) { A.pos_s = s->pos.p; A.pos_out = s->pos_s.p; }    // the role swap described above
     if (s->aos_live) L.aos_out = s->aos.p;
@@ -595,278 +584,26 @@ fs_status fs_generate_force_field(fs_sim* s, int device, const uint8_t* image, u
             return fail(FS_ERR_INVALID, "image dimensions differ from settings.texture_size");
         device = s->device;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return fail(FS_ERR_DEVICE, "no HIP device: the engine has no CPU fallback");
-    FS_HIP(hipSetDevice(device));
+    FS_TRY(use_device(device, FS_ERR_DEVICE));
     const size_t npix = (size_t)w * h;
-    unsigned char* dimg = nullptr; float* ddist = nullptr; uint32_t* dnear = nullptr; float2* dfield = nullptr;
+    DevArray<unsigned char> dimg;
+    DevArray<float> ddist;
+    DevArray<uint32_t> dnear;
+    DevArray<float2> dfield;        // without a handle: the field itself
     hipStream_t st = s ? s->stream : nullptr;
-    hipError_t e = hipMalloc((void**)&dimg, npix);
-    if (e == hipSuccess) e = hipMalloc((void**)&ddist, npix * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&dnear, npix * sizeof(uint32_t));
-    if (e == hipSuccess && !s) e = hipMalloc((void**)&dfield, npix * sizeof(float2));
-    float2* out = s ? s->tex.p : dfield;
+    hipError_t e = dimg.alloc(npix);
+    if (e == hipSuccess) e = ddist.alloc(npix);
+    if (e == hipSuccess) e = dnear.alloc(npix);
+    if (e == hipSuccess && !s) e = dfield.alloc(npix);
+    float2* out = s ? s->tex.p : dfield.p;
     if (s) s->tex_zero = false;     // produced on the device: contents unknown to the host
-    if (e == hipSuccess) e = hipMemcpyAsync(dimg, image, npix, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) { fsd::launch_gradient_field(st, dimg, w, h, ddist, dnear, out); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(dimg.p, image, npix, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) { fsd::launch_gradient_field(st, dimg.p, w, h, ddist.p, dnear.p, out); e = hipGetLastError(); }
     if (e == hipSuccess && field_host) e = hipMemcpyAsync(field_host, out, npix * sizeof(float2), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(dimg); (void)hipFree(ddist); (void)hipFree(dnear); (void)hipFree(dfield);
+    const hipError_t es = hipStreamSynchronize(st);      // before the staging is freed, whatever happened
+    if (e == hipSuccess) e = es;
     if (e != hipSuccess) return fail(FS_ERR_DEVICE, hipGetErrorString(e));
     return FS_OK;
-}
-
-fs_status fs_render_density(fs_sim* s, const fs_view* view, float* rgba_host) {
-    if (!s || !view || !rgba_host) return fail(FS_ERR_INVALID, "null argument");
-    if (s->slab) return fail(FS_ERR_UNSUPPORTED, "render on a slab handle");
-    FS_JOIN(s);
-    if (view->width == 0 || view->height == 0 || (uint64_t)view->width * view->height > (1ull << 28))
-        return fail(FS_ERR_INVALID, "bad image size");
-    // an upload writes the records in upload order under the previous sort's cell table: a walk would pair old ranges with new arrays
-    if (!s->walk_ready) return fail(FS_ERR_INVALID, "render needs a step since create and since the last upload of particles or start indices");
-    FS_HIP(hipSetDevice(s->device));
-    const size_t npix = (size_t)view->width * view->height;
-    float4* dimg = nullptr;
-    FS_HIP(hipMalloc((void**)&dimg, npix * sizeof(float4)));
-    const fsd::StepParams P = make_params(*s, s->uniform);
-    // after a step: `pred` = predicted positions of this step, `vel` = updated velocities (what the
-    // reference's fragment shader sees in in_particles at draw time)
-    fsd::launch_render_density(s->stream, P, make_float2(view->world_min.x, view->world_min.y),
-                               make_float2(view->world_max.x, view->world_max.y), view->width, view->height, s->pred.p,
-                               s->vel.p, s->cs.p, s->start_ref.p, s->pairs.p, dimg);
-    hipError_t e = hipMemcpyAsync(rgba_host, dimg, npix * sizeof(float4), hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    (void)hipFree(dimg);
-    if (e != hipSuccess) return fail(FS_ERR_DEVICE, hipGetErrorString(e));
-    return sort_health(s);        // the image is in `rgba_host` either way; FS_ERR_DEVICE says the order it was walked in is not to be trusted
-}
-
-fs_status fs_set_surface_tension(fs_sim* s, int enable) {
-    if (!s) return fail(FS_ERR_INVALID, "null argument");
-    if (s->slab) return fail(FS_ERR_UNSUPPORTED, "surface tension: single-domain handles only (not built for slab handles)");
-    if (enable && !s->st_on) {
-        if (!s->stf.p) {
-            FS_HIP(hipSetDevice(s->device));
-            FS_HIP(s->stf.alloc(s->capacity));
-        }
-        s->st_valid = false;        // fs_download_surface_tension waits for a step of this enable
-    }
-    s->st_on = enable != 0;
-    return FS_OK;
-}
-
-int fs_surface_tension_enabled(const fs_sim* s) { return (s && s->st_on) ? 1 : 0; }
-
-fs_status fs_download_surface_tension(fs_sim* s, fs_vec2* dst, size_t n) {
-    if (!s || !dst) return fail(FS_ERR_INVALID, "null argument");
-    if (!s->st_valid) return fail(FS_ERR_INVALID, "surface tension: no step with surface tension since the handle was created or ST was last enabled");
-    if (n != s->n) return fail(FS_ERR_INVALID, "surface tension: n must equal the particle count");
-    FS_HIP(hipSetDevice(s->device));
-    static_assert(sizeof(fs_vec2) == sizeof(float2), "fs_vec2 is two f32");
-    if (n) FS_HIP(hipMemcpyAsync(dst, s->stf.p, n * sizeof(fs_vec2), hipMemcpyDeviceToHost, s->stream));
-    FS_HIP(hipStreamSynchronize(s->stream));
-    return sort_health(s);
-}
-
-// ---- particle tracking ----------------------------------------------------------------------------
-fs_status fs_track_enable(fs_sim* s, int channels) {
-    if (!s) return fail(FS_ERR_INVALID, "null argument");
-    if (s->slab) return fail(FS_ERR_UNSUPPORTED, "tracking: single-domain handles only (not built for slab handles)");
-    if (channels < 0 || channels > FS_TRACK_MAX_CHANNELS) return fail(FS_ERR_INVALID, "tracking: channels must be in [0, FS_TRACK_MAX_CHANNELS]");
-    FS_HIP(hipSetDevice(s->device));
-    if (!s->trk_id[0].p) {
-        for (int k = 0; k < 2; ++k)
-            if (s->trk_id[k].alloc(s->capacity) != hipSuccess) {
-                (void)hipGetLastError();
-                s->trk_id[0].release(); s->trk_id[1].release();
-                return fail(FS_ERR_OOM, "tracking: id arrays");
-            }
-    }
-    if (channels > s->trk_alloc_channels) {
-        FS_HIP(hipStreamSynchronize(s->stream));      // steps in flight may still read the arrays about to be replaced
-        s->trk_attr[0].release(); s->trk_attr[1].release();
-        s->trk_alloc_channels = 0;
-        for (int k = 0; k < 2; ++k)
-            if (s->trk_attr[k].alloc((size_t)channels * s->capacity) != hipSuccess) {
-                (void)hipGetLastError();
-                s->trk_attr[0].release(); s->trk_attr[1].release();
-                s->trk_channels = -1;
-                return fail(FS_ERR_OOM, "tracking: channel arrays");
-            }
-        s->trk_alloc_channels = channels;
-    }
-    // on the simulation's stream: ordered after every step already enqueued, before every step enqueued from now on
-    s->trk_cur = 0;
-    fsd::launch_track_iota(s->stream, s->n, s->trk_id[0].p);
-    FS_HIP(hipGetLastError());
-    if (channels && s->n) FS_HIP(hipMemsetAsync(s->trk_attr[0].p, 0, (size_t)channels * s->capacity * sizeof(float), s->stream));
-    s->trk_channels = channels;
-    return FS_OK;
-}
-
-fs_status fs_track_disable(fs_sim* s) {
-    if (!s) return fail(FS_ERR_INVALID, "null argument");
-    s->trk_channels = -1;           // the arrays stay allocated until the handle is destroyed
-    return FS_OK;
-}
-
-int fs_track_channels(const fs_sim* s) { return s ? s->trk_channels : -1; }
-
-namespace {
-// ids (attr = false) or one channel, host <-> the arrays of the last enqueued step.  Blocking.
-fs_status track_copy(fs_sim* s, int channel, bool attr, void* host, size_t n, bool upload) {
-    if (!s || !host) return fail(FS_ERR_INVALID, "null argument");
-    if (s->trk_channels < 0) return fail(FS_ERR_INVALID, "tracking is off (fs_track_enable)");
-    if (attr && (channel < 0 || channel >= s->trk_channels)) return fail(FS_ERR_INVALID, "tracking: no such channel");
-    if (n != s->n) return fail(FS_ERR_INVALID, "tracking: n must equal the particle count");
-    FS_HIP(hipSetDevice(s->device));
-    void* dev = attr ? (void*)(s->trk_attr[s->trk_cur].p + (size_t)channel * s->capacity) : (void*)s->trk_id[s->trk_cur].p;
-    if (n) {
-        if (upload) FS_HIP(hipMemcpyAsync(dev, host, n * 4, hipMemcpyHostToDevice, s->stream));
-        else FS_HIP(hipMemcpyAsync(host, dev, n * 4, hipMemcpyDeviceToHost, s->stream));
-    }
-    FS_HIP(hipStreamSynchronize(s->stream));
-    return upload ? FS_OK : sort_health(s);
-}
-}  // namespace
-
-fs_status fs_track_download_ids(fs_sim* s, uint32_t* dst, size_t n) { return track_copy(s, 0, false, dst, n, false); }
-fs_status fs_track_upload_ids(fs_sim* s, const uint32_t* src, size_t n) { return track_copy(s, 0, false, (void*)src, n, true); }
-fs_status fs_track_download_attr(fs_sim* s, int channel, float* dst, size_t n) { return track_copy(s, channel, true, dst, n, false); }
-fs_status fs_track_upload_attr(fs_sim* s, int channel, const float* src, size_t n) { return track_copy(s, channel, true, (void*)src, n, true); }
-
-fs_status fs_track_ids_device(fs_sim* s, const uint32_t** out) {
-    if (!s || !out) return fail(FS_ERR_INVALID, "null argument");
-    if (s->trk_channels < 0) return fail(FS_ERR_INVALID, "tracking is off (fs_track_enable)");
-    *out = s->trk_id[s->trk_cur].p;
-    return FS_OK;
-}
-
-fs_status fs_track_attr_device(fs_sim* s, int channel, const float** out) {
-    if (!s || !out) return fail(FS_ERR_INVALID, "null argument");
-    if (s->trk_channels < 0) return fail(FS_ERR_INVALID, "tracking is off (fs_track_enable)");
-    if (channel < 0 || channel >= s->trk_channels) return fail(FS_ERR_INVALID, "tracking: no such channel");
-    *out = s->trk_attr[s->trk_cur].p + (size_t)channel * s->capacity;
-    return FS_OK;
-}
-
-/* Off the step path: two downloads and a scatter on the host, so entries of dst that no id names are never written. */
-fs_status fs_download_particles_by_id(fs_sim* s, fs_particle* dst, size_t n) {
-    if (!s || (!dst && n)) return fail(FS_ERR_INVALID, "null argument");
-    if (s->trk_channels < 0) return fail(FS_ERR_INVALID, "tracking is off (fs_track_enable)");
-    std::vector<fs_particle> rec;
-    std::vector<uint32_t> ids;
-    try { rec.resize(s->n); ids.resize(s->n); } catch (const std::bad_alloc&) { return fail(FS_ERR_OOM, "host staging"); }
-    FS_TRY(fs_download_particles(s, rec.data(), rec.size()));
-    if (s->n) {
-        FS_TRY(fs_track_download_ids(s, ids.data(), ids.size()));
-    }
-    for (size_t i = 0; i < ids.size(); ++i)
-        if (ids[i] < n) dst[ids[i]] = rec[i];
-    return FS_OK;
-}
-
-// ---- field sampling ---------------------------------------------------------------------------------
-namespace {
-// Argument and state checks the three calls share, in the order the header lists them.  *go = false: n == 0, nothing to do.
-fs_status sample_check(fs_sim* s, const void* points_or_view, size_t n, const void* out, const float* attr_out, bool* go) {
-    *go = false;
-    if (!s) return fail(FS_ERR_INVALID, "null argument");
-    if (s->slab) return fail(FS_ERR_UNSUPPORTED, "sampling: single-domain handles only (not built for slab handles)");
-    if (attr_out && s->trk_channels <= 0) return fail(FS_ERR_INVALID, "sampling: attr_out needs tracking with at least one channel");
-    if (n == 0) return FS_OK;
-    if (!points_or_view || !out) return fail(FS_ERR_INVALID, "null argument");
-    if (n > ((size_t)1 << 28)) return fail(FS_ERR_INVALID, "sampling: more than 2^28 points");
-    if (!s->walk_ready) return fail(FS_ERR_INVALID, "sampling needs a step since create and since the last upload of particles or start indices");
-    *go = true;
-    return FS_OK;
-}
-
-// Enqueue the kernel on the simulation's stream.  points_dev == nullptr: the pixel centres of `view`.
-fs_status sample_enqueue(fs_sim* s, const fs_vec2* points_dev, const fs_view* view, size_t n, fs_sample* out_dev, float* attr_out_dev) {
-    static_assert(sizeof(fs_sample) == 24, "fs_sample is 24 bytes");
-    fsd::SampleQuery Q;
-    Q.n = (uint32_t)n;
-    Q.points = (const float2*)points_dev;
-    if (view) {
-        Q.wmin = make_float2(view->world_min.x, view->world_min.y);
-        Q.wmax = make_float2(view->world_max.x, view->world_max.y);
-        Q.width = view->width; Q.height = view->height;
-    }
-    Q.out = out_dev; Q.attr_out = attr_out_dev;
-    fsd::SampleState S;
-    // after a step: `pred` = its predicted positions, `vel` = its new velocities (as fs_render_density); keys and densities
-    // from where that step left them
-    S.pred = s->pred.p; S.vel = s->vel.p;
-    S.rho2 = s->rho2.p; S.rho = s->rho_in_rho2 ? nullptr : s->rho.p;
-    S.cs = s->cs.p; S.start_ref = s->start_ref.p; S.pairs = s->pairs.p;
-    if (attr_out_dev) {
-        S.channels = s->trk_channels;
-        S.attr = s->trk_attr[s->trk_cur].p; S.attr_stride = s->capacity;
-    }
-    fsd::launch_sample(s->stream, make_params(*s, s->uniform), Q, S);
-    FS_HIP(hipGetLastError());
-    return FS_OK;
-}
-
-// The blocking forms: device staging for the points (none for a grid), the records and the channel sums.
-fs_status sample_host(fs_sim* s, const fs_vec2* points, const fs_view* view, size_t n, fs_sample* out, float* attr_out) {
-    FS_JOIN(s);
-    FS_HIP(hipSetDevice(s->device));
-    const size_t ch = attr_out ? (size_t)s->trk_channels : 0;
-    fs_vec2* dpts = nullptr; fs_sample* dout = nullptr; float* dattr = nullptr;
-    hipError_t e = hipSuccess;
-    if (points) e = hipMalloc((void**)&dpts, n * sizeof(fs_vec2));
-    if (e == hipSuccess) e = hipMalloc((void**)&dout, n * sizeof(fs_sample));
-    if (e == hipSuccess && ch) e = hipMalloc((void**)&dattr, ch * n * sizeof(float));
-    fs_status r = FS_OK;
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        r = fail(FS_ERR_OOM, "sampling: device staging");
-    } else {
-        if (points) e = hipMemcpyAsync(dpts, points, n * sizeof(fs_vec2), hipMemcpyHostToDevice, s->stream);
-        if (e == hipSuccess) {
-            r = sample_enqueue(s, dpts, points ? nullptr : view, n, dout, dattr);
-            if (r == FS_OK) e = hipMemcpyAsync(out, dout, n * sizeof(fs_sample), hipMemcpyDeviceToHost, s->stream);
-            if (r == FS_OK && e == hipSuccess && ch) e = hipMemcpyAsync(attr_out, dattr, ch * n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
-        }
-        const hipError_t es = hipStreamSynchronize(s->stream);      // before the staging is freed, whatever happened
-        if (e == hipSuccess) e = es;
-        if (r == FS_OK && e != hipSuccess) r = fail(FS_ERR_DEVICE, hipGetErrorString(e));
-    }
-    (void)hipFree(dpts); (void)hipFree(dout); (void)hipFree(dattr);
-    if (r != FS_OK) return r;
-    return sort_health(s);
-}
-}  // namespace
-
-fs_status fs_sample_points(fs_sim* s, const fs_vec2* points, size_t n, fs_sample* out, float* attr_out) {
-    bool go;
-    const fs_status r = sample_check(s, points, n, out, attr_out, &go);
-    if (r != FS_OK || !go) return r;
-    return sample_host(s, points, nullptr, n, out, attr_out);
-}
-
-fs_status fs_sample_points_device(fs_sim* s, const fs_vec2* points_dev, size_t n, fs_sample* out_dev, float* attr_out_dev) {
-    bool go;
-    const fs_status r = sample_check(s, points_dev, n, out_dev, attr_out_dev, &go);
-    if (r != FS_OK || !go) return r;
-    FS_HIP(hipSetDevice(s->device));
-    return sample_enqueue(s, points_dev, nullptr, n, out_dev, attr_out_dev);
-}
-
-fs_status fs_sample_grid(fs_sim* s, const fs_view* view, fs_sample* out, float* attr_out) {
-    if (!s) return fail(FS_ERR_INVALID, "null argument");
-    if (s->slab) return fail(FS_ERR_UNSUPPORTED, "sampling: single-domain handles only (not built for slab handles)");
-    if (!view) return fail(FS_ERR_INVALID, "null argument");
-    if (view->width == 0 || view->height == 0 || (uint64_t)view->width * view->height > (1ull << 28))
-        return fail(FS_ERR_INVALID, "bad grid size");
-    const size_t n = (size_t)view->width * view->height;
-    bool go;
-    const fs_status r = sample_check(s, view, n, out, attr_out, &go);
-    if (r != FS_OK || !go) return r;
-    return sample_host(s, nullptr, view, n, out, attr_out);
 }
 
 fs_status fs_profile_enable(fs_sim* s, int enable) {
@@ -895,94 +632,6 @@ fs_status fs_timed_steps(fs_sim* s, const fs_tick_settings* t, uint32_t steps, d
     FS_HIP(hipEventElapsedTime(&ms, s->t0, s->t1));
     *ms_total = ms;
     return sort_health(s);
-}
-
-/* Exhaustive proof used by the force pass: number of f32 x with lo <= |x| <= hi for which the 3-op
- * constant division (x*y, fma, fma with the given reciprocal y) differs from the IEEE x / c.  Blocking. */
-fs_status fs_selftest_constdiv(int device, float c, float y, float lo, float hi, uint32_t* mismatches) {
-    if (!mismatches || !(lo > 0.0f) || !(hi >= lo) || !std::isfinite(hi)) return fail(FS_ERR_INVALID, "bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(FS_ERR_DEVICE, "no HIP device");
-    FS_HIP(hipSetDevice(device));
-    uint32_t* dm = nullptr;
-    FS_HIP(hipMalloc((void**)&dm, sizeof(uint32_t)));
-    FS_HIP(hipMemset(dm, 0, sizeof(uint32_t)));
-    fsd::launch_verify_constdiv(nullptr, c, y, lo, hi, dm);
-    hipError_t e = hipMemcpy(mismatches, dm, sizeof(uint32_t), hipMemcpyDeviceToHost);
-    (void)hipFree(dm);
-    if (e != hipSuccess) return fail(FS_ERR_DEVICE, hipGetErrorString(e));
-    return FS_OK;
-}
-
-/* The sort on caller-supplied pairs (tests of the late-stage plans on adversarial inputs).  Blocking. */
-fs_status fs_selftest_sort(int device, uint64_t* pairs, uint32_t n, int fuse_stage, uint32_t plan[2]) {
-    if (!pairs || n == 0 || n > (1u << 28)) return fail(FS_ERR_INVALID, "bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(FS_ERR_DEVICE, "no HIP device");
-    FS_HIP(hipSetDevice(device));
-    unsigned long long* dp = nullptr;
-    uint32_t* dd = nullptr;
-    const size_t words = fsd::sort_tile_count(n);
-    FS_HIP(hipMalloc((void**)&dp, (size_t)n * 8));
-    hipError_t e = hipMalloc((void**)&dd, words * 4);
-    if (e == hipSuccess) e = hipMemset(dd, 0, words * 4);
-    if (e == hipSuccess) e = hipMemcpy(dp, pairs, (size_t)n * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        fsd::SortPlan sp;
-        sp.fuse_stage = fuse_stage < 0 ? -1 : (fuse_stage & 0xFF);
-        sp.fallback = fuse_stage >= 0 && (fuse_stage & 0x100) ? 1 : 0;
-        fsd::launch_bitonic_sort(nullptr, dp, n, dd, nullptr, nullptr, nullptr, nullptr, &sp);
-        e = hipMemcpy(pairs, dp, (size_t)n * 8, hipMemcpyDeviceToHost);
-    }
-    if (e == hipSuccess && plan) e = hipMemcpy(plan, dd + fsd::sort_plan_word(n) + 1, 8, hipMemcpyDeviceToHost);
-    uint32_t timeouts = 0;
-    if (e == hipSuccess) e = hipMemcpy(&timeouts, dd + fsd::sort_plan_word(n) + 4, 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && timeouts) { (void)hipFree(dp); (void)hipFree(dd); return fail(FS_ERR_DEVICE, "sort fallback: grid barrier timed out"); }
-    (void)hipFree(dp);
-    (void)hipFree(dd);
-    if (e != hipSuccess) return fail(FS_ERR_DEVICE, hipGetErrorString(e));
-    return FS_OK;
-}
-
-/* The plan policy replayed against a model of the flow (include/fluidsim.h); host only. */
-fs_status fs_selftest_sort_policy(uint32_t S, int start_back, uint32_t lag, const uint32_t* required, size_t steps,
-                                  uint32_t* stage_out, uint32_t* single_out) {
-    if (!required || !stage_out || !single_out || S < 15 || S > 28) return fail(FS_ERR_INVALID, "bad argument");
-    fsd::SortPolicy p;
-    p.start_back = start_back;
-    std::vector<uint32_t> used(steps);
-    for (size_t i = 0; i < steps; ++i) {
-        if (i >= lag && i - lag < steps) {             // the report of step i - lag arrives before step i is planned
-            const size_t j = i - lag;
-            const int st = (int)used[j];
-            const bool passed = st >= (int)required[j];
-            const int cls = passed ? (st - (int)required[j] > 3 ? 3 : st - (int)required[j]) : 0;
-            p.observe((uint32_t)j + 1u, st, passed, cls, S);
-        }
-        used[i] = (uint32_t)(p.stage ? p.stage : p.first_stage(S));
-        p.seq = (uint32_t)i + 1u;                      // what plan() does: this step's sequence number
-        stage_out[i] = used[i];
-        single_out[i] = p.single_standby() ? 1u : 0u;
-    }
-    return FS_OK;
-}
-
-fs_status fs_sort_plan_read(fs_sim* s, fs_sort_plan_info* out) {
-    if (!s || !out) return fail(FS_ERR_INVALID, "null argument");
-    FS_HIP(hipSetDevice(s->device));
-    FS_HIP(hipStreamSynchronize(s->stream));
-    uint32_t w[8] = {};
-    const uint32_t count = s->slab ? s->capacity : s->n;
-    if (count > 1) FS_HIP(hipMemcpy(w, s->sort_dirty.p + fsd::sort_plan_word(count), sizeof w, hipMemcpyDeviceToHost));
-    out->shifted = w[1]; out->per_stage = w[2]; out->standby_runs = w[6]; out->timeouts = w[4]; out->wide_tiles = w[7];
-    out->stage = (uint32_t)s->sortp.stage;
-    out->standby_single = (s->sortp.force_single || (s->sortp.stage && s->sortp.trusted >= 2)) ? 1u : 0u;
-    return FS_OK;
-}
-
-/* Did the create-time proofs succeed for this handle's constants (2h^3, h^2)?  Bits 0 / 1. */
-int fs_constdiv_status(const fs_sim* s) {
-    return s ? (s->div_2h3.ok ? 1 : 0) | (s->div_h2.ok ? 2 : 0) | (s->rcp_ok ? 4 : 0) | (s->sqrt_ok ? 8 : 0) | (s->div_h.ok ? 16 : 0) : 0;
 }
 
 /* ------------------------------------------------- renderer hand-off without a host round trip */
@@ -1028,9 +677,7 @@ fs_status fs_export_handle(fs_sim* s, int which, fs_mem_handle* out) {
 fs_status fs_import_open(const fs_mem_handle* h, int device, void** ptr) {
     if (!h || !ptr) return fail(FS_ERR_INVALID, "null argument");
     *ptr = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(FS_ERR_DEVICE, "no HIP device");
-    FS_HIP(hipSetDevice(device));
+    FS_TRY(use_device(device, FS_ERR_DEVICE));
     hipIpcMemHandle_t ih;
     std::memcpy(&ih, h->ipc, sizeof ih);
     FS_HIP(hipIpcOpenMemHandle(ptr, ih, hipIpcMemLazyEnablePeerAccess));

@@ -1,5 +1,6 @@
 // engine_3d.hip — host side of the 3D extension of the step: the handle and the fs3_* C ABI (kernels and launchers:
-// kernels_3d.hip, fs_3d.h).
+// kernels_3d.hip, fs_3d.h).  From the 2D engine (engine.h): the device check, the create-time proofs, the owners and the
+// sort policy.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -66,18 +67,27 @@ struct fs_sim3 {
     }
 };
 
+static const float PI3 = 3.14159265359f;
+
+// What the step and field sampling both need of Params3: counts, grid, h, the half-bounds and the poly6 constant; the rest zero.
+static fsd::Params3 params3_common(const fs_sim3& s, float mass) {
+    const float h = s.st.smoothing_radius;
+    fsd::Params3 P;
+    std::memset(&P, 0, sizeof P);
+    P.n = s.n; P.gw = s.gw; P.gh = s.gh; P.gd = s.gd; P.ncell = s.ncell;
+    P.h = h; P.h2 = h * h;
+    P.bx = s.st.size.x * 0.5f; P.by = s.st.size.y * 0.5f; P.bz = s.st.size.z * 0.5f;
+    P.mass = mass;
+    P.poly6 = 315.0f / (64.0f * PI3 * std::pow(h, 9.0f));      // host libm, as in the oracle
+    return P;
+}
+
 static fs_status enqueue3(fs_sim3* s, const fs3_tick_settings* t) {
     using namespace fsd;
     s->tick += 1;
     const float h = s->st.smoothing_radius;
-    const float PI3 = 3.14159265359f;
-    Params3 P;
-    std::memset(&P, 0, sizeof P);
-    P.n = s->n; P.gw = s->gw; P.gh = s->gh; P.gd = s->gd; P.ncell = s->ncell;
-    P.dt = t->delta; P.h = h; P.h2 = h * h;
-    P.bx = s->st.size.x * 0.5f; P.by = s->st.size.y * 0.5f; P.bz = s->st.size.z * 0.5f;
-    P.mass = t->mass;
-    P.poly6 = 315.0f / (64.0f * PI3 * std::pow(h, 9.0f));      // host libm, as in the oracle
+    Params3 P = params3_common(*s, t->mass);
+    P.dt = t->delta;
     P.spiky = 15.0f / (PI3 * std::pow(h, 5.0f));
     P.visc_k = 15.0f / (2.0f * PI3 * (h * h * h));
     P.pressure_k = t->pressure_constant; P.rest_density = t->rest_density; P.damping = t->damping_factor;
@@ -129,7 +139,7 @@ static fs_status enqueue3(fs_sim3* s, const fs3_tick_settings* t) {
     if (ev) FS_HIP(hipEventRecord(ev[4], st));
     // positions ping-pong: read the previous state (s->pos, source order) through the pairs, write the new one into s->pos_s
     // the step's completion event (sort_policy.h: the host stays at most four steps ahead) rides on the force kernel as its
-    // completion signal — no marker packet behind it (engine.hip fs_step does the same); a profiled step records markers anyway
+    // completion signal — no marker packet behind it (engine.hip enqueue_step does the same); a profiled step records markers anyway
     hipEvent_t done = ev ? nullptr : s->sortp.flight_event();
     launch3_force(st, P, A, tol, done);
     std::swap(s->pos, s->pos_s);
@@ -164,16 +174,15 @@ fs_status fs3_create_ex(const fs3_settings* st, int device, fs_vec3 off, int mat
         return fail(FS_ERR_INVALID, "bad settings");
     const uint32_t side = (uint32_t)std::llround(std::cbrt((double)st->particle_count));
     if ((uint64_t)side * side * side != st->particle_count) return fail(FS_ERR_INVALID, "particle_count must be a cube");
-    const double gw = std::ceil((double)st->size.x / st->smoothing_radius) + 2, gh = std::ceil((double)st->size.y / st->smoothing_radius) + 2,
-                 gd = std::ceil((double)st->size.z / st->smoothing_radius) + 2;
+    // cells per axis, the f32 quotient as in fsd::grid_dims; kept in doubles until their product is known to fit
+    const auto cells = [st](float size) { return (double)std::ceil(size / st->smoothing_radius) + 2; };
+    const double gw = cells(st->size.x), gh = cells(st->size.y), gd = cells(st->size.z);
     if (gw * gh * gd >= 4294967295.0) return fail(FS_ERR_INVALID, "grid does not fit u32 cell ids");
     FS_TRY(fsd::use_device(device));
     std::unique_ptr<fs_sim3> s(new (std::nothrow) fs_sim3());   // an error exit frees whatever the handle holds by then
     if (!s) return fail(FS_ERR_OOM, "host allocation failed");
     s->st = *st; s->n = st->particle_count; s->device = device; s->math_mode = math_mode;
-    s->gw = (uint32_t)((size_t)std::ceil(st->size.x / st->smoothing_radius) + 2);
-    s->gh = (uint32_t)((size_t)std::ceil(st->size.y / st->smoothing_radius) + 2);
-    s->gd = (uint32_t)((size_t)std::ceil(st->size.z / st->smoothing_radius) + 2);
+    s->gw = (uint32_t)gw; s->gh = (uint32_t)gh; s->gd = (uint32_t)gd;
     s->ncell = s->gw * s->gh * s->gd;
     s->work_cap = s->ncell / 16u + 1024u;
     FS_HIP(hipStreamCreateWithFlags(&s->stream.h, hipStreamNonBlocking));
@@ -221,11 +230,7 @@ fs_status fs3_step(fs_sim3* s, const fs3_tick_settings* t) {
     return enqueue3(s, t);
 }
 // a barrier time-out of the sort's stand-by kernel leaves the particle order undefined: reported wherever state is handed over
-static fs_status sort_health3(fs_sim3* s) {
-    FS_HIP(s->sortp.check_timeout(s->dirty.p, s->n));
-    if (s->sortp.dead) return fail(FS_ERR_DEVICE, "sort: the stand-by kernel's grid barrier timed out: the particle order is undefined from that step on; destroy the handle");
-    return FS_OK;
-}
+static fs_status sort_health3(fs_sim3* s) { return s->sortp.health(s->dirty.p, s->n); }
 fs_status fs3_sync(fs_sim3* s) { if (!s) return fail(FS_ERR_INVALID, "null"); FS_HIP(hipStreamSynchronize(s->stream)); return sort_health3(s); }
 void* fs3_stream(const fs_sim3* s) { return s ? (void*)s->stream.h : nullptr; }
 uint32_t fs3_tick_count(const fs_sim3* s) { return s ? s->tick : 0; }
@@ -290,15 +295,7 @@ fs_status sample3_check(fs_sim3* s, const void* points_or_view, size_t n, const 
 // Enqueue the kernel on the simulation's stream.  points_dev == nullptr: the voxel centres of `view`.
 fs_status sample3_enqueue(fs_sim3* s, const fs_vec3* points_dev, const fs3_view* view, size_t n, fs3_sample* out_dev) {
     static_assert(sizeof(fs3_sample) == 40 && sizeof(fs_vec3) == 12, "fs3_sample is 40 bytes, fs_vec3 three floats");
-    const float h = s->st.smoothing_radius;
-    const float PI3 = 3.14159265359f;
-    fsd::Params3 P;
-    std::memset(&P, 0, sizeof P);
-    P.n = s->n; P.gw = s->gw; P.gh = s->gh; P.gd = s->gd; P.ncell = s->ncell;
-    P.h = h; P.h2 = h * h;
-    P.bx = s->st.size.x * 0.5f; P.by = s->st.size.y * 0.5f; P.bz = s->st.size.z * 0.5f;
-    P.mass = s->mass;
-    P.poly6 = 315.0f / (64.0f * PI3 * std::pow(h, 9.0f));      // enqueue3's, host libm
+    const fsd::Params3 P = params3_common(*s, s->mass);
     fsd::Sample3Query Q;
     Q.n = (uint32_t)n;
     Q.points = (const float*)points_dev;
@@ -313,27 +310,12 @@ fs_status sample3_enqueue(fs_sim3* s, const fs_vec3* points_dev, const fs3_view*
     return FS_OK;
 }
 
-// The blocking forms: device staging for the points (none for a grid) and the records, freed on return.
+// The blocking forms (fs_host.h staged_query): points == nullptr: the grid of `view`.
 fs_status sample3_host(fs_sim3* s, const fs_vec3* points, const fs3_view* view, size_t n, fs3_sample* out) {
     FS_HIP(hipSetDevice(s->device));
-    DevArray<fs_vec3> dpts;
-    DevArray<fs3_sample> dout;
-    hipError_t e = points ? dpts.alloc(n) : hipSuccess;
-    if (e == hipSuccess) e = dout.alloc(n);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(FS_ERR_OOM, "sampling: device staging");
-    }
-    fs_status r = FS_OK;
-    if (points) e = hipMemcpyAsync(dpts.p, points, n * sizeof(fs_vec3), hipMemcpyHostToDevice, s->stream);
-    if (e == hipSuccess) {
-        r = sample3_enqueue(s, dpts.p, points ? nullptr : view, n, dout.p);
-        if (r == FS_OK) e = hipMemcpyAsync(out, dout.p, n * sizeof(fs3_sample), hipMemcpyDeviceToHost, s->stream);
-    }
-    const hipError_t es = hipStreamSynchronize(s->stream);      // before the staging is freed, whatever happened
-    if (e == hipSuccess) e = es;
-    if (r == FS_OK && e != hipSuccess) r = fail(FS_ERR_DEVICE, hipGetErrorString(e));
-    if (r != FS_OK) return r;
+    FS_TRY(fsd::staged_query(s->stream, points, n, out, nullptr, 0, [&](const fs_vec3* dpts, fs3_sample* dout, float*) {
+        return sample3_enqueue(s, dpts, points ? nullptr : view, n, dout);
+    }));
     return sort_health3(s);
 }
 }  // namespace

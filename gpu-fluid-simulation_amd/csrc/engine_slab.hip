@@ -1,7 +1,7 @@
 // engine_slab.hip — host side of the multi-GPU "slab" handles of the C ABI (include/fluidsim.h, fs_slab_*): one rank's window
 // of columns, the pack -> exchange -> step cycle in its three step modes (serial, edge-first, strips), and what
-// re-balancing reads.  The handle itself, the plain step and the opt-in features: engine.hip.  Everything slab-only a handle
-// holds: SlabState (engine.h).
+// re-balancing reads.  The handle itself and the plain step: engine.hip; the opt-in features, none of which a slab handle
+// has: engine_features.hip, engine_query.hip.  Everything slab-only a handle holds: SlabState (engine.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>

@@ -50,7 +50,7 @@ struct StepParams {
     uint32_t own_lo, own_hi;   // owned window [own_lo, own_hi) in GLOBAL columns
     uint32_t grid_w_global;
     const uint32_t* n_live;    // device-side live count (slab mode); nullptr -> n
-    // --- slab mode, overlapped step (engine.hip fs_slab_pack / fs_slab_step): which owned columns THIS launch of the force
+    // --- slab mode, overlapped step (engine_slab.hip fs_slab_pack / fs_slab_step): which owned columns THIS launch of the force
     // pass advances.  adv_outside == 0: the columns [adv_lo, adv_hi) (the interior, computed while the halo messages are in
     // flight; the serial step passes the whole owned window); adv_outside == 1: the owned columns OUTSIDE [adv_lo, adv_hi)
     // (the boundary strips, computed after the unpack).  Global columns, own_lo <= adv_lo <= adv_hi <= own_hi.

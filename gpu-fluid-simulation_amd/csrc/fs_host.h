@@ -1,7 +1,7 @@
-// fs_host.h — what the host files of the C ABI (engine.hip, engine_slab.hip, engine_3d.hip) share: the last-error
-// helper, the HIP error macro, and the owners of a handle's device arrays, streams, events and per-pass event ring.
-// Every owner frees what it holds in its destructor, so a handle is torn down by `delete` alone (members go in reverse
-// order of declaration).
+// fs_host.h — what the host files of the C ABI (engine*.hip) share: the last-error helper, the HIP error macro, and the
+// owners of a handle's device arrays, streams, events and per-pass event ring.  Every owner frees what it holds in its
+// destructor, so a handle is torn down by `delete` alone (members go in reverse order of declaration), and a blocking call
+// stages device memory in DevArray locals: it synchronises the stream (or ends on a blocking copy) before they go out of scope.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -54,6 +54,33 @@ struct DevArray {
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
 };
+
+// The blocking form of a point query (fs_sample_*, fs3_sample_*): device staging for the points (none: the query is a grid), the
+// records and `ch` channel sums per point; `enqueue(points_dev, out_dev, attr_dev)` puts the kernel on `st` and returns a status.
+template <class Pt, class Rec, class Enqueue>
+fs_status staged_query(hipStream_t st, const Pt* points, size_t n, Rec* out, float* attr_out, size_t ch, Enqueue enqueue) {
+    DevArray<Pt> dpts;
+    DevArray<Rec> dout;
+    DevArray<float> dattr;
+    hipError_t e = points ? dpts.alloc(n) : hipSuccess;
+    if (e == hipSuccess) e = dout.alloc(n);
+    if (e == hipSuccess) e = dattr.alloc(ch * n);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FS_ERR_OOM, "sampling: device staging");
+    }
+    fs_status r = FS_OK;
+    if (points) e = hipMemcpyAsync(dpts.p, points, n * sizeof(Pt), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        r = enqueue(dpts.p, dout.p, dattr.p);
+        if (r == FS_OK) e = hipMemcpyAsync(out, dout.p, n * sizeof(Rec), hipMemcpyDeviceToHost, st);
+        if (r == FS_OK && e == hipSuccess && ch) e = hipMemcpyAsync(attr_out, dattr.p, ch * n * sizeof(float), hipMemcpyDeviceToHost, st);
+    }
+    const hipError_t es = hipStreamSynchronize(st);      // before the staging is freed, whatever happened
+    if (e == hipSuccess) e = es;
+    if (r == FS_OK && e != hipSuccess) r = fail(FS_ERR_DEVICE, hipGetErrorString(e));
+    return r;
+}
 
 // A stream or an event of a handle: created into `h` by the HIP call that fits, destroyed with its owner.
 template <class H, hipError_t (*Destroy)(H)>

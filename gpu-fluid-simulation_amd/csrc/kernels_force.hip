@@ -895,7 +895,7 @@ void launch_force(hipStream_t st, const StepParams& P, const StepArrays& A, cons
 #ifndef FS_GENERAL_GRID
 #define FS_GENERAL_GRID 4080u   // 16M, steps 150-250: force 1.175 (1024) -> 1.126 (2048) -> 1.117 ms (4096); steps 10-110 unchanged
 #endif
-    uint32_t gg = general_grid ? general_grid : FS_GENERAL_GRID;      // the host's choice (engine.hip), else the full grid
+    uint32_t gg = general_grid ? general_grid : FS_GENERAL_GRID;      // the host's choice (sort_policy.h), else the full grid
     if (gg > nb) gg = nb;
     if (side) {   // fork: the pre-registered waves on the second stream, beside the lean kernel
         (void)hipEventRecord(ev_fork, st);

@@ -72,7 +72,7 @@ __device__ __forceinline__ void block_message_lists(unsigned char f, uint32_t i,
     }
 }
 
-// overlap != 0 (the overlapped step, engine.hip): ghosts never enter the main array, so the slots past `main_slots` are not the
+// overlap != 0 (the overlapped step, engine_slab.hip): ghosts never enter the main array, so the slots past `main_slots` are not the
 // unpack area of this step but hold the MIGRANTS the boundary strips received and advanced in the last one (owned flag
 // set by k_strip_writeback); they are carried over like the sorted prefix.
 template <bool COUNTING>
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(SL_BLOCK) void k_slab_pack(StepParams P, uint32_t c
     }
 }
 
-// Edge-first step (engine.hip): the messages of step t+1 are built at the END of step t, as soon as the force pass
+// Edge-first step (engine_slab.hip): the messages of step t+1 are built at the END of step t, as soon as the force pass
 // has advanced the owned columns within `boundary_cols` of a neighboured edge (StepParams::adv_outside launch) — the exchange
 // then runs beside the force pass of the interior columns and the next step's k_slab_pack.  Same classification, same lists,
 // same slot order as k_slab_pack would produce at t+1 (a particle's sorted index now IS its slot then), restricted to the
@@ -495,7 +495,7 @@ __global__ __launch_bounds__(SL_BLOCK) void k_slab_maxspeed(const uint32_t* __re
 }
 
 // ------------------------------------------------------------------ overlapped step: the boundary strips
-// (engine.hip fs_slab_pack / fs_slab_step.)  Ghosts stay OUT of the main sorted array.  While the two halo messages are in
+// (engine_slab.hip fs_slab_pack / fs_slab_step.)  Ghosts stay OUT of the main sorted array.  While the two halo messages are in
 // flight the rank sorts its carried-over particles and runs density + force for the INTERIOR columns [adv_lo, adv_hi); what
 // the received records can influence — the owned columns within `Z` of a slab edge — is computed afterwards on a small second
 // array, the STRIP: every particle of the main array whose cell column lies in a strip window (the two ghost columns, the

@@ -664,7 +664,7 @@ static int sort_skip_stage() {
 // [0] verdict, [1] / [2] plan counters, [3] fallback barrier, [4] fallback
 // barrier time-outs, [5] fit class of the last certificate, [6] calls in which the stand-by kernel had work.
 // Fit class: the largest j <= 3 for which (C2), (C3) still hold with windows of H / 2^j — how much room the moves of
-// this step left; the host's choice of the next steps' stage reads it (engine.hip), never the result.
+// this step left; the host's choice of the next steps' stage reads it (sort_policy.h), never the result.
 // feedback (optional, host-visible): [1] stage, [2] verdict, [3] fit class, [4] time-outs, then [0] = seq.
 // Round 4: a grid of small workgroups instead of one of 256 threads.  The kernel's time was never its arithmetic: at 16 M
 // particles it reads 512 x 11 keys 256 KB apart — every one a TLB miss, all of them queued on ONE compute unit's address

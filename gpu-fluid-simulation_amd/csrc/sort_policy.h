@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "fs_host.h"
 #include "fs_kernels.h"
 
 namespace fsd {
@@ -132,15 +133,17 @@ struct SortPolicy {
 
     // After a synchronisation of the simulation's stream: did the stand-by kernel (k_late_fallback) report a grid-barrier
     // time-out in any of the steps enqueued so far?  From that step on the particle order is undefined (include/fluidsim.h), so
-    // every call that hands state to the caller checks this — not only the plan() of a later step.  `dirty`: the sort's tile
+    // every call that hands state to the caller returns this — not only the plan() of a later step.  `dirty`: the sort's tile
     // flags of `n` elements (the plan words behind them hold the count).  Latches.
     bool dead = false;
-    hipError_t check_timeout(const uint32_t* dirty, uint32_t n) {
-        if (dead || !enabled || n < (1u << 15)) return hipSuccess;
-        uint32_t t = 0;
-        const hipError_t r = hipMemcpy(&t, dirty + sort_plan_word(n) + 4, sizeof t, hipMemcpyDeviceToHost);
-        if (r == hipSuccess && t) dead = true;
-        return r;
+    fs_status health(const uint32_t* dirty, uint32_t n) {
+        if (!dead && enabled && n >= (1u << 15)) {
+            uint32_t t = 0;
+            FS_HIP(hipMemcpy(&t, dirty + sort_plan_word(n) + 4, sizeof t, hipMemcpyDeviceToHost));
+            if (t) dead = true;
+        }
+        if (dead) return fail(FS_ERR_DEVICE, "sort: the stand-by kernel's grid barrier timed out: the particle order is undefined from that step on; destroy the handle");
+        return FS_OK;
     }
 
     // The plan of this step's sort of n elements.  Returns false when the stand-by kernel reported a barrier time-out.
