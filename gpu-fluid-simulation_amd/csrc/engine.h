@@ -133,7 +133,7 @@ struct SlabState {
 
     // Overlapped slab step (counting sort only): fs_slab_pack enqueues the pack AND the whole step of the
     // interior columns; the halo exchange runs beside it on `comm`; fs_slab_step finishes the columns within `boundary_cols`
-    // of a slab edge on the strip arrays (kernels_slab.hip "boundary strips").
+    // of a slab edge on the strip arrays (kernels_strip.hip).
     bool transposed = false;               // cell ids column-major (fs_device.h StepParams::transposed): ranks with neighbours, not the strip step
     bool overlap = false;                  // FS_SLAB_STRIPS: ghosts stay out of the main array, boundary strips after the exchange
     bool edge_first = false;               // the default: the next step's messages are built right after the edge columns' force launch

@@ -121,7 +121,7 @@ void launch_verify_unary(hipStream_t st, int which /* 0 rcp_rn_fast, 1 sqrt_rn_f
 size_t gap_entry_size();
 void launch_fill_gaps(hipStream_t st, uint32_t* cs, const void* work, const uint32_t* counter, uint32_t work_cap);
 
-// ---- slab (multi-GPU) mode, kernels_slab.hip -------------------------------------------------
+// ---- slab (multi-GPU) mode, kernels_slab.hip / kernels_strip.hip -------------------------------------------------
 // The arrays of a slab handle its launchers work on: the main array's step arrays (the state is read through pos / vel and
 // written through pos_out / vel_out, the same arrays; key_s: the sorted keys of the last step or import) and the slab's own,
 // filled in one place on the handle (engine.h).  Host side only.
@@ -167,7 +167,7 @@ void launch_slab_prepack(hipStream_t st, const StepParams& P_next, const SlabArr
                          uint32_t edge_grid = 0 /* != 0 (column-major ids): walk only the edge columns' blocks */,
                          bool classify = false /* also do the next launch_slab_pack's work for the slots of the particles it takes:
                                                   key, histogram ticket (counting sort) and out[] entry, the lost counter */);
-// Overlapped slab step — the boundary strips (kernels_slab.hip).  `P` = the main array's StepParams, `A` its arrays;
+// Overlapped slab step — the boundary strips (kernels_strip.hip).  `P` = the main array's StepParams, `A` its arrays;
 // StripArrays::counters: [0] live strip particles (written by the strip's scan), [1] slots filled from the main array, [2] slots in use.
 struct StripArrays {
     uint32_t cap = 0;

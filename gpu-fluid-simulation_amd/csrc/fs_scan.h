@@ -1,6 +1,7 @@
-// fs_scan.h — device helpers shared by the counting sort (kernels_csort.hip) and the slab pack (kernels_slab.hip):
-// wave-level run aggregation for histogram atomics, and the single-pass "decoupled look-back" prefix sum over
-// workgroups (one launch instead of reduce / scan-of-sums / apply; Merrill & Garland's chained scan).
+// fs_scan.h — device helpers shared by the counting sort (kernels_csort.hip), the slab kernels (kernels_slab.hip) and the
+// boundary strips (kernels_strip.hip): the histogram ticket with wave-level run aggregation, the 64-lane inclusive scan,
+// and the single-pass "decoupled look-back" prefix sum over workgroups (one launch instead of reduce / scan-of-sums /
+// apply; Merrill & Garland's chained scan).
 //
 // Look-back protocol.  Workgroups take their logical index from an atomic ticket, so a workgroup only ever waits
 // for workgroups that are already running (no dependence on the hardware's dispatch order).  Each publishes ONE
@@ -35,6 +36,24 @@ __device__ __forceinline__ WaveRun wave_run(uint32_t key, bool active) {
     const uint32_t end = after ? (uint32_t)__ffsll((long long)after) - 1u : 64u;
     r.length = end - r.head_lane;
     return r;
+}
+
+// A particle's arrival ticket inside its cell: the value the histogram atomic returns, stored beside the key
+// (kt[i] = key << 32 | ticket).  Whole wave; an inactive lane adds nothing and its result is meaningless.
+__device__ __forceinline__ uint32_t cell_ticket(uint32_t* __restrict__ hist, uint32_t key, uint32_t ncell, bool active) {
+    const uint32_t k = key < ncell ? key : ncell - 1u;
+    const WaveRun r = wave_run(k, active);
+    uint32_t base = 0;
+    if (r.is_head) base = atomicAdd(&hist[k], r.length);            // one ticket block per run
+    return __shfl(base, r.head_lane) + r.offset;
+}
+
+// Inclusive prefix sum over the 64 lanes of a wave.
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(v, o); if ((int)lane >= o) v += t; }
+    return v;
 }
 
 __device__ __forceinline__ u64 lb_load(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

@@ -10,6 +10,7 @@
 #include "fs_device.h"
 #include "fs_kernels.h"
 #include "fs_scan.h"
+#include "fs_slab.h"
 
 namespace fsd {
 
@@ -43,12 +44,8 @@ __global__ __launch_bounds__(CS_BLOCK) void k_cs_hist(StepParams P, const float2
     const bool active = i < P.n;
     uint32_t key = 0;
     if (active) key = cell_of_point(P, predict_pos(P, pos[i], vel[i]));
-    const uint32_t k = key < P.ncell ? key : P.ncell - 1u;
-    const WaveRun r = wave_run(k, active);
-    uint32_t base = 0;
-    if (r.is_head) base = atomicAdd(&hist[k], r.length);            // one ticket block per run
-    base = __shfl(base, r.head_lane);
-    if (active) kt[i] = ((u64)key << 32) | (u64)(base + r.offset);
+    const uint32_t ticket = cell_ticket(hist, key, P.ncell, active);
+    if (active) kt[i] = ((u64)key << 32) | (u64)ticket;
 }
 
 // Exclusive scan of in[0, count) -> out, one launch.  Tile = SCAN_TILE items per workgroup (1024 threads x 16: the
@@ -89,9 +86,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_lookback(uint32_t* __restri
     for (uint32_t k = 0; k < SCAN_ITEMS; ++k) sum += v[k];
     // inclusive scan of the thread sums: wave scan + the 16 wave totals
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint32_t inc = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(inc, o); if ((int)lane >= o) inc += t; }
+    const uint32_t inc = wave_inclusive_scan(sum);
     if (lane == 63u) s_wave[w] = inc;
     __syncthreads();
     uint32_t wave_off = 0, tile_total = 0;
@@ -138,8 +133,8 @@ __global__ __launch_bounds__(CS_BLOCK) void k_cs_scatter(uint32_t n, uint32_t nc
     if (n_dev) { const uint32_t m = *n_dev; n = m < n ? m : n; }
     if (blockIdx.x * (CS_BLOCK * SC_ITEMS) >= n) return;
     // slab handles: the "safe operand" words of this block's slots start as all-ones, k_cs_fixreorder (next in the stream) clears
-    // the unsafe particles' bits.  (Done here rather than in k_slab_pack: in an edge-first step the pack of tick t + 1 may run
-    // beside the edge columns' density launch of tick t, which still reads the words of tick t.)
+    // the unsafe particles' bits.  (Here and not in k_slab_pack: in an edge-first step the pack of tick t + 1 may run beside the
+    // edge columns' density launch of tick t, which still reads the words of tick t.)
     if (safe_preset && threadIdx.x < CS_BLOCK * SC_ITEMS / 64u) safe_preset[blockIdx.x * (CS_BLOCK * SC_ITEMS / 64u) + threadIdx.x] = ~0ull;
     const uint32_t i0 = blockIdx.x * (CS_BLOCK * SC_ITEMS) + threadIdx.x;
     u64 e[SC_ITEMS];
@@ -266,12 +261,7 @@ __global__ __launch_bounds__(CS_BLOCK) void k_cs_fixreorder(StepParams P, uint32
     pred_s[d] = pd;
     if (key_s) key_s[d] = key;
     if (!kin_safe(pd, v)) atomicAnd(&safe[d >> 6], ~(1ull << (d & 63u)));   // rare; words preset to all-ones
-    if (SLAB) {
-        uint32_t cxl, cy;
-        key_to_local(P, key, &cxl, &cy);
-        const int32_t cxg = (int32_t)cxl + P.col_origin;
-        owned[d] = (cxg >= (int32_t)P.own_lo && cxg < (int32_t)P.own_hi) ? 1 : 0;
-    }
+    if (SLAB) owned[d] = owns_col(P, global_col(P, key)) ? 1 : 0;
     if (rank == 0u && key < P.ncell) {           // first particle of its cell: compute.wgsl:49-55 (index 0 skipped)
         if (d != 0u || !P.ref_quirks) start_ref[key] = d;
     }
@@ -300,7 +290,7 @@ size_t counting_sort_scratch_words(uint32_t n, uint32_t ncell_max) {
 u64* counting_sort_kt(uint32_t* scratch, uint32_t n, uint32_t ncell) { return cs_layout(scratch, n, ncell).kt; }
 uint32_t* counting_sort_hist(uint32_t* scratch) { return scratch; }
 
-// Slab mode: kt / hist were filled by k_slab_pack + k_slab_unpack (kernels_slab.hip).
+// Slab mode: kt / hist were filled by the pack and unpack kernels (kernels_slab.hip; a strip's: kernels_strip.hip).
 void launch_counting_sort_pairs(hipStream_t st, uint32_t cap, uint32_t ncell, uint32_t ncell_alloc, uint32_t* cs, uint32_t* scratch,
                                 uint32_t* n_live_out, uint32_t epoch, const uint32_t* n_dev, unsigned long long* safe_preset) {
     const CsLayout L = cs_layout(scratch, cap, ncell_alloc);

@@ -8,48 +8,38 @@
 //   slots [main, main+R)       records received from the left neighbour this step
 //   slots [main+R, main+2R)    records received from the right neighbour this step
 //
-//   k_slab_pack      ONE launch: predict + global column; old ghosts and leavers become DEAD; the records each neighbour
-//                    needs (migrants and the 2-column ghost halo) are compacted in slot order (deterministic) into the
-//                    fixed-size messages [16-B header | R x {pos, vel}] through a decoupled look-back; the key goes
-//                    straight into the counting sort's histogram (its arrival ticket is stored beside it)
-//   k_slab_unpack    received records -> slots, key from the recomputed predicted position (+ histogram)
+// An outgoing message pair is built by three kernels:
+//   k_slab_pack      predict + global column of every carried-over owned particle; old ghosts and leavers become DEAD.
+//                    Counting sort: the key goes straight into the sort's histogram and the atomic's return value, the
+//                    particle's arrival ticket in its cell, is stored beside it (kt[i] = key << 32 | ticket, fs_scan.h
+//                    cell_ticket), so the sort needs no pass of its own over the slots; bitonic: pairs[i] = key << 32 | i.
+//                    The slots each neighbour needs (migrants + the 2-column halo) are listed per 256-slot block, in slot
+//                    order (stage_l / stage_r, 256 entries per block), with the two counts in blockcnt[block].
+//                    (k_slab_prepack: the same for the next step, from the edge columns alone — the edge-first step.)
+//   k_slab_msg       one wave per MSG_GROUP blocks: exclusive message offsets of its blocks by a wave scan + a decoupled
+//                    look-back over the (few) groups (fs_scan.h); the last group writes the two headers.
+//   k_slab_gather    one workgroup per block: its listed records -> the two fixed-size messages [16-B header | R x {pos, vel}],
+//                    in SLOT ORDER (deterministic).
+// Why three.  A look-back over the 256-slot blocks themselves, one launch, has a prefix frontier that advances ~128 blocks per
+// global-memory round trip: 0.17 ms for the 11 136 blocks of an 8-way rank — the chain must be short, hence the groups.  And
+// a group that gathers the records of its own 64 blocks is fine only while the flagged slots are spread over the array: with
+// column-major cell ids a rank's edge columns are ~80 CONSECUTIVE blocks per side, two workgroups then gather 20 000 records
+// each, 50 - 67 us instead of the 8 us of one workgroup per block.
+//
+//   k_slab_unpack    received records -> slots, key from the recomputed predicted position (+ histogram ticket)
 //   counting sort (default): k_scan_lookback -> k_cs_scatter -> k_cs_fixreorder<true> (kernels_csort.hip; the last one is
 //                    the reorder pass as well: live count, owned flags, start_indices)
 //   bitonic mode:    the network over all slots (DEAD keys end up last) + k_slab_reorder
 //   k_density / k_force run unchanged on the local window (ghosts are not advanced)
+// The strips step's own kernels are in kernels_strip.hip; the device helpers all of these share in fs_slab.h.
 #include "fs_device.h"
 #include "fs_kernels.h"
 #include "fs_scan.h"
+#include "fs_slab.h"
 
 namespace fsd {
 
-#define SL_BLOCK 256
-
-__device__ __forceinline__ uint32_t slab_key(const StepParams& P, float2 pred, uint32_t* cx_global) {
-    uint32_t cx, cy;
-    xy_of_point(P, pred, &cx, &cy);
-    *cx_global = cx;
-    const int32_t lo = (int32_t)P.own_lo - 2, hi = (int32_t)P.own_hi + 2;   // owned + 2 ghost columns per side
-    if ((int32_t)cx < lo || (int32_t)cx >= hi || cy >= P.grid_h) return FS_DEAD_KEY;
-    return key_of_local(P, (uint32_t)((int32_t)cx - P.col_origin), cy);
-}
-
-struct SlabHeader { uint32_t count, overflow, pad0, pad1; };
-
-// The pack in TWO launches (round 2: classify -> single-workgroup scan -> scatter, three launches and a flags array):
-//  k_slab_pack  * predict + global column of every carried-over owned particle; old ghosts and leavers become DEAD;
-//               * COUNTING: the key goes straight into the counting sort's histogram — the atomic's return value is the
-//                 particle's arrival ticket in its cell (kt[i] = key << 32 | ticket, kernels_csort.hip) — so the sort
-//                 needs no pass of its own over the slots; bitonic mode: pairs[i] = key << 32 | i as before;
-//               * the slots each neighbour needs (migrants + the 2-column halo) are listed per 256-slot block, in slot
-//                 order (stage_l / stage_r, 256 entries per block), with the two counts in blockcnt[block];
-//  k_slab_msg   one wave per MSG_GROUP blocks: exclusive message offsets of its blocks by a wave scan + a decoupled
-//               look-back over the (few) groups (fs_scan.h); the last group writes the two headers;
-//  k_slab_gather one workgroup per block: its listed records -> the two fixed-size messages, in SLOT ORDER (deterministic).
-// (A look-back over the 256-slot blocks themselves — one launch — was measured first: its prefix frontier advances ~128
-//  blocks per global-memory round trip, 0.17 ms for the 11 136 blocks of an 8-way rank.  The chain must be short.)
-// The slots of one 256-slot block each message needs (flag bit 0: left, bit 1: right), listed in slot order (stage_l / stage_r,
-// 256 entries per block) with the two counts in blockcnt[block]: the input of k_slab_msg.  Whole workgroup.
+// The per-block lists and counts of the pack (flag bit 0: left message, bit 1: right): the input of k_slab_msg.  Whole workgroup.
 __device__ __forceinline__ void block_message_lists(unsigned char f, uint32_t i, uint32_t blk, uint2* __restrict__ blockcnt,
                                                     uint32_t* __restrict__ stage_l, uint32_t* __restrict__ stage_r) {
     __shared__ uint32_t s_cnt[2 * (SL_BLOCK / 64)];
@@ -72,7 +62,7 @@ __device__ __forceinline__ void block_message_lists(unsigned char f, uint32_t i,
     }
 }
 
-// overlap != 0 (the overlapped step, engine_slab.hip): ghosts never enter the main array, so the slots past `main_slots` are not the
+// overlap != 0 (the strips step, engine_slab.hip): ghosts never enter the main array, so the slots past `main_slots` are not the
 // unpack area of this step but hold the MIGRANTS the boundary strips received and advanced in the last one (owned flag
 // set by k_strip_writeback); they are carried over like the sorted prefix.
 template <bool COUNTING>
@@ -83,7 +73,6 @@ __global__ __launch_bounds__(SL_BLOCK) void k_slab_pack(StepParams P, uint32_t c
                                                         uint32_t* __restrict__ hist, uint2* __restrict__ blockcnt,
                                                         uint32_t* __restrict__ stage_l, uint32_t* __restrict__ stage_r,
                                                         uint32_t* __restrict__ counters, uint32_t* __restrict__ gap_counter,
-                                                        unsigned long long* __restrict__ safe,
                                                         const uint32_t* __restrict__ key_prev, uint32_t prev_adv_lo,
                                                         uint32_t prev_adv_hi, int skip_edge) {
     const uint32_t i = blockIdx.x * SL_BLOCK + threadIdx.x;
@@ -97,10 +86,8 @@ __global__ __launch_bounds__(SL_BLOCK) void k_slab_pack(StepParams P, uint32_t c
     // sort as well (k_slab_prepack: this launch then neither reads nor writes anything of it, and need not wait for that chain)
     bool was_edge = false, skipped = false;
     if (!lists && i < main_slots && i < n_prev && owned[i]) {
-        uint32_t cxl, cy;
-        key_to_local(P, key_prev[i], &cxl, &cy);
-        const int32_t cg = (int32_t)cxl + P.col_origin;
-        was_edge = cg >= (int32_t)P.own_lo && cg < (int32_t)P.own_hi && !(cg >= (int32_t)prev_adv_lo && cg < (int32_t)prev_adv_hi);
+        const int32_t cg = global_col(P, key_prev[i]);
+        was_edge = owns_col(P, cg) && !(cg >= (int32_t)prev_adv_lo && cg < (int32_t)prev_adv_hi);
         skipped = skip_edge && was_edge;
     }
     if (i < main_slots || (overlap && i < cap)) {
@@ -108,27 +95,19 @@ __global__ __launch_bounds__(SL_BLOCK) void k_slab_pack(StepParams P, uint32_t c
             const float2 pr = predict_pos(P, pos[i], vel[i]);
             uint32_t cxg;
             key = slab_key(P, pr, &cxg);
-            if (has_left && cxg < P.own_lo + 2u) f |= 1;
-            if (has_right && cxg + 2u >= P.own_hi) f |= 2;
-            // a leaver must land inside the neighbour's slab and not in ITS far halo: checked by the receiver
-            if (!has_left && cxg < P.own_lo) atomicAdd(&counters[2], 1u);    // left the domain partition
-            if (!has_right && cxg >= P.own_hi) atomicAdd(&counters[2], 1u);
+            f = halo_flags(P, cxg, has_left, has_right);
+            count_leavers(P, cxg, has_left, has_right, counters);
         }
         if (!COUNTING && !skipped) out[i] = ((u64)key << 32) | (u64)i;
     } else if (i < n_prev && i < cap && owned[i]) {
-        // Slot capacity exceeded: the last step left more live records than main slots, and this owned
-        // particle sits where the incoming messages will be unpacked.  It cannot be carried over —
-        // count it (fs_slab_counters.overflow must stay 0; the driver raises on it).
+        // Slot capacity exceeded: the last step left more live records than main slots, and this owned particle sits where the
+        // incoming messages will be unpacked.  It cannot be carried over: counted in overflow (the driver raises on it).
         atomicAdd(&counters[3], 1u);
     }
     if (COUNTING) {
         const bool active = key != FS_DEAD_KEY;
-        const uint32_t k = key < P.ncell ? key : P.ncell - 1u;
-        const WaveRun r = wave_run(k, active);
-        uint32_t base = 0;
-        if (r.is_head) base = atomicAdd(&hist[k], r.length);
-        base = __shfl(base, r.head_lane);
-        if ((i < main_slots || (overlap && i < cap)) && !skipped) out[i] = ((u64)key << 32) | (u64)(active ? base + r.offset : 0u);
+        const uint32_t ticket = cell_ticket(hist, key, P.ncell, active);
+        if ((i < main_slots || (overlap && i < cap)) && !skipped) out[i] = ((u64)key << 32) | (u64)(active ? ticket : 0u);
     }
     if (lists) {
         block_message_lists(f, i, blockIdx.x, blockcnt, stage_l, stage_r);
@@ -145,9 +124,8 @@ __global__ __launch_bounds__(SL_BLOCK) void k_slab_pack(StepParams P, uint32_t c
 // has advanced the owned columns within `boundary_cols` of a neighboured edge (StepParams::adv_outside launch) — the exchange
 // then runs beside the force pass of the interior columns and the next step's k_slab_pack.  Same classification, same lists,
 // same slot order as k_slab_pack would produce at t+1 (a particle's sorted index now IS its slot then), restricted to the
-// particles that launch advanced; `P` carries the window and the tick constants the next pack will use.  k_slab_pack (lists
-// = 0) counts what the full classification flags and k_slab_unpack checks it against the headers: a particle that reached the
-// 2-column band from farther inside than the edge zone shows up in far_halo.
+// particles that launch advanced; `P` carries the window and the tick constants the next pack will use.  The next k_slab_pack
+// (lists = 0) checks the messages' completeness (far_halo).
 __global__ __launch_bounds__(SL_BLOCK) void k_slab_prepack(StepParams P, int has_left, int has_right, int edge_walk,
                                                            const float2* __restrict__ pos, const float2* __restrict__ vel,
                                                            const unsigned char* __restrict__ owned,
@@ -159,9 +137,7 @@ __global__ __launch_bounds__(SL_BLOCK) void k_slab_prepack(StepParams P, int has
     const uint32_t n = *P.n_live;
     // edge_walk (column-major ids): a small grid walks the blocks of the edge columns only (fs_device.h EdgeBlocks; k_slab_msg and
     // k_slab_gather take every other block's counts as zero); otherwise one workgroup per 256-slot block of the whole array
-    EdgeBlocks E;
-    E.eL = 0u; E.eR = 0u; E.nb = gridDim.x;
-    if (edge_walk) E = edge_blocks(P, cs, n, 0u);
+    const EdgeBlocks E = edge_blocks_or_all(P, edge_walk, cs, gridDim.x);
     const uint32_t count = edge_walk ? edge_block_count(E) : gridDim.x;
     for (uint32_t t = blockIdx.x; t < count; t += gridDim.x) {
         const uint32_t blk = edge_walk ? edge_block_at(E, t) : t;
@@ -169,31 +145,18 @@ __global__ __launch_bounds__(SL_BLOCK) void k_slab_prepack(StepParams P, int has
         unsigned char f = 0;
         uint32_t key = FS_DEAD_KEY;
         bool mine = false;                                  // classify: this launch does the next pack's work for the slot
-        if (i < n && owned[i]) {
-            uint32_t cxl, cy;
-            key_to_local(P, key_s[i], &cxl, &cy);
-            const int32_t cg = (int32_t)cxl + P.col_origin;
-            if (slab_advances(P, cg)) {                     // advanced already: pos / vel hold its new state
-                uint32_t cxg;
-                key = slab_key(P, predict_pos(P, pos[i], vel[i]), &cxg);
-                if (has_left && cxg < P.own_lo + 2u) f |= 1;
-                if (has_right && cxg + 2u >= P.own_hi) f |= 2;
-                mine = classify && i < main_slots;
-                if (mine) {                                 // exactly k_slab_pack's bookkeeping for an owned, carried-over slot
-                    if (!has_left && cxg < P.own_lo) atomicAdd(&counters[2], 1u);
-                    if (!has_right && cxg >= P.own_hi) atomicAdd(&counters[2], 1u);
-                }
-            }
+        if (i < n && owned[i] && slab_advances(P, global_col(P, key_s[i]))) {     // advanced already: pos / vel hold its new state
+            uint32_t cxg;
+            key = slab_key(P, predict_pos(P, pos[i], vel[i]), &cxg);
+            f = halo_flags(P, cxg, has_left, has_right);
+            mine = classify && i < main_slots;
+            if (mine) count_leavers(P, cxg, has_left, has_right, counters);   // k_slab_pack will skip this slot
         }
         if (classify) {
             if (counting) {
                 const bool active = mine && key != FS_DEAD_KEY;
-                const uint32_t k = key < P.ncell ? key : P.ncell - 1u;
-                const WaveRun r = wave_run(k, active);
-                uint32_t base = 0;
-                if (r.is_head) base = atomicAdd(&hist[k], r.length);
-                base = __shfl(base, r.head_lane);
-                if (mine) out[i] = ((u64)key << 32) | (u64)(active ? base + r.offset : 0u);
+                const uint32_t ticket = cell_ticket(hist, key, P.ncell, active);
+                if (mine) out[i] = ((u64)key << 32) | (u64)(active ? ticket : 0u);
             } else if (mine) {
                 out[i] = ((u64)key << 32) | (u64)i;
             }
@@ -214,11 +177,8 @@ __device__ __forceinline__ u64 pk_add(u64 a, u64 b) {
 }
 
 #define MSG_GROUP 64u        // pack blocks per k_slab_msg workgroup (one wave scans their counts)
-// Round 4: k_slab_msg only turns the per-block counts into per-block message offsets (blockoff) and writes the headers; the
-// records are gathered by k_slab_gather, one workgroup per pack block.  (One kernel did both, each workgroup gathering the
-// records of its 64 blocks: fine while the flagged slots are spread over the whole array — a few per grid row — but with
-// column-major cell ids a rank's edge columns are ~80 CONSECUTIVE blocks per side, i.e. two workgroups gathered 20 000 records
-// each: 50 - 67 us instead of 8.)
+// Per-block counts -> per-block message offsets (blockoff) + the two headers; k_slab_gather moves the records.  (It once
+// gathered them itself, each workgroup for its 64 blocks: see the file header for what that cost.)
 __global__ __launch_bounds__(64) void k_slab_msg(uint32_t nblocks_pack, uint32_t R, const uint2* __restrict__ blockcnt,
                                                  uint2* __restrict__ blockoff, u64* __restrict__ state,
                                                  uint32_t* __restrict__ ticket, uint32_t epoch, SlabHeader* hdr_left,
@@ -226,9 +186,7 @@ __global__ __launch_bounds__(64) void k_slab_msg(uint32_t nblocks_pack, uint32_t
                                                  const uint32_t* __restrict__ cs_edge) {
     __shared__ uint32_t s_bid;
     // cs_edge != null: only the edge columns' blocks were classified (k_slab_prepack with edge_walk); every other count is zero
-    EdgeBlocks E;
-    E.eL = 0u; E.eR = 0u; E.nb = nblocks_pack;
-    if (cs_edge) E = edge_blocks(P, cs_edge, *P.n_live, 0u);
+    const EdgeBlocks E = edge_blocks_or_all(P, cs_edge, cs_edge, nblocks_pack);
     if (threadIdx.x == 0) s_bid = atomicAdd(ticket, 1u);
     __syncthreads();
     const uint32_t bid = s_bid, ngroups = gridDim.x;
@@ -237,12 +195,7 @@ __global__ __launch_bounds__(64) void k_slab_msg(uint32_t nblocks_pack, uint32_t
     const uint32_t b = bid * MSG_GROUP + lane;
     const u64 tag = (u64)(epoch & 0x3FFFFFu);
     const uint2 c = (b < nblocks_pack && (!cs_edge || edge_block_has(E, b))) ? blockcnt[b] : make_uint2(0u, 0u);
-    uint32_t il = c.x, ir = c.y;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t tx = __shfl_up(il, o), ty = __shfl_up(ir, o);
-        if ((int)lane >= o) { il += tx; ir += ty; }
-    }
+    const uint32_t il = wave_inclusive_scan(c.x), ir = wave_inclusive_scan(c.y);
     const uint32_t tl = __shfl(il, 63), tr = __shfl(ir, 63);            // <= 64 * 256 each
     const u64 mine = ((u64)tl << 20) | (u64)tr;
     u64 ex = 0ull;
@@ -270,9 +223,7 @@ __global__ __launch_bounds__(SL_BLOCK) void k_slab_gather(uint32_t R, const uint
                                                           const float2* __restrict__ pos, const float2* __restrict__ vel,
                                                           float4* __restrict__ rec_left, float4* __restrict__ rec_right,
                                                           StepParams P, const uint32_t* __restrict__ cs_edge) {
-    EdgeBlocks E;
-    E.eL = 0u; E.eR = 0u; E.nb = gridDim.x;
-    if (cs_edge) E = edge_blocks(P, cs_edge, *P.n_live, 0u);
+    const EdgeBlocks E = edge_blocks_or_all(P, cs_edge, cs_edge, gridDim.x);
     const uint32_t count = cs_edge ? edge_block_count(E) : gridDim.x;
     for (uint32_t w = blockIdx.x; w < count; w += gridDim.x) {
         const uint32_t blk = cs_edge ? edge_block_at(E, w) : w;
@@ -303,36 +254,15 @@ __global__ __launch_bounds__(SL_BLOCK) void k_slab_unpack(StepParams P, uint32_t
                                                           u64* __restrict__ out /* kt or pairs */, uint32_t* __restrict__ hist,
                                                           uint32_t* __restrict__ counters) {
     const uint32_t j = blockIdx.x * SL_BLOCK + threadIdx.x;
-    const bool in_range = j < 2u * R;
-    const bool right = j >= R;
-    const uint32_t jj = right ? j - R : j;
-    const SlabHeader* hdr = right ? hdr_right : hdr_left;
-    const float4* rec = right ? rec_right : rec_left;
-    uint32_t cnt = 0;
-    if (in_range && hdr) { cnt = hdr->count < R ? hdr->count : R; if (jj == 0 && hdr->overflow) atomicAdd(&counters[3], 1u); }
+    const ReceivedRecord r(j, R, hdr_left, rec_left, hdr_right, rec_right, counters);
     const uint32_t slot = main_slots + j;
-    uint32_t key = FS_DEAD_KEY;
-    if (in_range && jj < cnt) {
-        const float4 r = rec[jj];
-        const float2 p = make_float2(r.x, r.y), v = make_float2(r.z, r.w);
-        pos[slot] = p;
-        vel[slot] = v;
-        uint32_t cxg;
-        key = slab_key(P, predict_pos(P, p, v), &cxg);
-        if (key == FS_DEAD_KEY) atomicAdd(&counters[2], 1u);           // travelled farther than slab + halo
-        // a migrant that lands in my FAR halo zone would have been needed by my other neighbour too
-        if (!right && cxg + 2u >= P.own_hi && cxg < P.own_hi) atomicAdd(&counters[4], 1u);
-        if (right && cxg < P.own_lo + 2u && cxg >= P.own_lo) atomicAdd(&counters[4], 1u);
-    }
+    uint32_t key = FS_DEAD_KEY, cxg;
+    if (r.has()) key = r.read(P, &pos[slot], &vel[slot], counters, &cxg);
     if (COUNTING) {                                                     // received records join the histogram (after k_slab_pack's)
         const bool active = key != FS_DEAD_KEY;
-        const uint32_t k = key < P.ncell ? key : P.ncell - 1u;
-        const WaveRun r = wave_run(k, active);
-        uint32_t base = 0;
-        if (r.is_head) base = atomicAdd(&hist[k], r.length);
-        base = __shfl(base, r.head_lane);
-        if (in_range) out[slot] = ((u64)key << 32) | (u64)(active ? base + r.offset : 0u);
-    } else if (in_range) {
+        const uint32_t ticket = cell_ticket(hist, key, P.ncell, active);
+        if (r.in_range) out[slot] = ((u64)key << 32) | (u64)(active ? ticket : 0u);
+    } else if (r.in_range) {
         out[slot] = ((u64)key << 32) | (u64)slot;
     }
 }
@@ -380,10 +310,7 @@ __global__ __launch_bounds__(SL_BLOCK) void k_slab_reorder(StepParams P, uint32_
         const unsigned long long sb = __builtin_amdgcn_ballot_w64(kin_safe(pd, v));   // lanes that returned above: 0
         if ((threadIdx.x & 63u) == 0u) safe[i >> 6] = sb;
     }
-    uint32_t cxl, cy;
-    key_to_local(P, key, &cxl, &cy);
-    const int32_t cxg = (int32_t)cxl + P.col_origin;
-    owned[i] = (cxg >= (int32_t)P.own_lo && cxg < (int32_t)P.own_hi) ? 1 : 0;
+    owned[i] = owns_col(P, global_col(P, key)) ? 1 : 0;
 
     const uint32_t kc = key < P.ncell ? key : P.ncell;
     if (i == 0) {
@@ -416,9 +343,9 @@ __global__ __launch_bounds__(SL_BLOCK) void k_slab_export(StepParams P, uint32_t
     if (i >= cap) return;
     AosParticle a;
     a.position = pos[i]; a.predicted = pred[i]; a.velocity = vel[i]; a.density = rho[i];
-    uint32_t cxl, cy;
-    key_to_local(P, key[i], &cxl, &cy);
-    a.grid = cy * P.grid_w_global + (uint32_t)((int32_t)cxl + P.col_origin);      // the reference's id (funcs.wgsl:216-218)
+    uint32_t cy;
+    const int32_t cg = global_col(P, key[i], &cy);
+    a.grid = cy * P.grid_w_global + (uint32_t)cg;                               // the reference's id (funcs.wgsl:216-218)
     out[i] = a;
 }
 
@@ -448,7 +375,7 @@ __global__ __launch_bounds__(SL_BLOCK) void k_slab_colhist(StepParams P, const u
     const uint32_t c = blockIdx.x * SL_BLOCK + threadIdx.x;
     if (c >= P.grid_w) return;
     const int32_t cg = (int32_t)c + P.col_origin;
-    if (cg < (int32_t)P.own_lo || cg >= (int32_t)P.own_hi) return;
+    if (!owns_col(P, cg)) return;
     uint32_t sum = 0;
     if (P.transposed) sum = cs[(c + 1u) * P.grid_h] - cs[c * P.grid_h];       // a column is one contiguous range of cell ids
     else for (uint32_t y = 0; y < P.grid_h; ++y) sum += cs[y * P.grid_w + c + 1] - cs[y * P.grid_w + c];
@@ -465,9 +392,7 @@ __global__ __launch_bounds__(SL_BLOCK) void k_slab_colhist_migrants(StepParams P
     if (j >= count || !owned[first + j]) return;
     const uint32_t k = key[first + j];
     if (k == FS_DEAD_KEY) return;
-    uint32_t cxl, cy;
-    key_to_local(P, k, &cxl, &cy);
-    const int32_t cg = (int32_t)cxl + P.col_origin;
+    const int32_t cg = global_col(P, k);
     if (cg >= 0 && cg < (int32_t)P.grid_w_global) atomicAdd(&hist_global[cg], 1u);
 }
 
@@ -494,194 +419,7 @@ __global__ __launch_bounds__(SL_BLOCK) void k_slab_maxspeed(const uint32_t* __re
     if ((threadIdx.x & 63u) == 0 && m > 0.0f) atomicMax(out_bits, __float_as_uint(m));
 }
 
-// ------------------------------------------------------------------ overlapped step: the boundary strips
-// (engine_slab.hip fs_slab_pack / fs_slab_step.)  Ghosts stay OUT of the main sorted array.  While the two halo messages are in
-// flight the rank sorts its carried-over particles and runs density + force for the INTERIOR columns [adv_lo, adv_hi); what
-// the received records can influence — the owned columns within `Z` of a slab edge — is computed afterwards on a small second
-// array, the STRIP: every particle of the main array whose cell column lies in a strip window (the two ghost columns, the
-// boundary columns, and two columns of interior context), plus the received records.  The strip uses the main array's own
-// window and cell keys, is counting-sorted like it, and goes through the SAME k_density / k_force (StepParams::adv_outside);
-// k_strip_writeback puts the results back: boundary particles to their index in the main arrays, migrants to the slot past
-// the main ones that mirrors their position in the message (k_slab_pack carries them over in the next step).
-//
-//   k_strip_rows      (1 workgroup) per grid row and window: the main array's index range -> exclusive offsets; totals
-//   k_strip_gather    one wave per (row, window): copies {pos, vel} of the range into the strip's slots, histogram + ticket
-//   k_strip_unpack    the received records behind them; classification (ghost / migrant), protocol checks
-//   k_strip_writeback results -> main arrays
-struct StripWin { uint32_t lo0, hi0, lo1, hi1; };      // LOCAL columns [lo0, hi0) and [lo1, hi1); an empty window has lo == hi
-#define STRIP_NONE 0xFFFFFFFFu
-
-#define SR_BLOCK 1024
-__global__ __launch_bounds__(SR_BLOCK) void k_strip_rows(uint32_t grid_w, uint32_t grid_h, StripWin W, uint32_t R2,
-                                                         const uint32_t* __restrict__ cs, uint32_t* __restrict__ rowbase,
-                                                         uint32_t* __restrict__ strip_counters) {
-    __shared__ uint32_t s_wave[SR_BLOCK / 64];
-    __shared__ uint32_t s_carry;
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0u;
-    __syncthreads();
-    const uint32_t entries = 2u * grid_h;
-    for (uint32_t e0 = 0; e0 < entries; e0 += SR_BLOCK) {
-        const uint32_t e = e0 + threadIdx.x;
-        uint32_t c = 0;
-        if (e < entries) {
-            const uint32_t y = e >> 1, lo = (e & 1u) ? W.lo1 : W.lo0, hi = (e & 1u) ? W.hi1 : W.hi0;
-            if (lo < hi) c = cs[y * grid_w + hi] - cs[y * grid_w + lo];
-        }
-        uint32_t inc = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(inc, o); if ((int)lane >= o) inc += t; }
-        if (lane == 63u) s_wave[w] = inc;
-        __syncthreads();
-        uint32_t off = s_carry, tot = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < SR_BLOCK / 64; ++k) { const uint32_t t = s_wave[k]; if (k < w) off += t; tot += t; }
-        if (e < entries) rowbase[e] = off + inc - c;
-        __syncthreads();
-        if (threadIdx.x == 0) s_carry += tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        strip_counters[1] = s_carry;                 // slots filled from the main array
-        strip_counters[2] = s_carry + R2;            // slots in use once the received records sit behind them
-    }
-}
-
-__global__ __launch_bounds__(SL_BLOCK) void k_strip_gather(uint32_t grid_w, uint32_t grid_h, uint32_t ncell, StripWin W,
-                                                           uint32_t strip_cap, const uint32_t* __restrict__ cs,
-                                                           const uint32_t* __restrict__ rowbase, const u64* __restrict__ pairs,
-                                                           const float2* __restrict__ pos_s, const float2* __restrict__ vel_s,
-                                                           float2* __restrict__ sp_pos, float2* __restrict__ sp_vel,
-                                                           u64* __restrict__ kt, uint32_t* __restrict__ hist,
-                                                           uint32_t* __restrict__ back, unsigned long long* __restrict__ safe,
-                                                           uint32_t* __restrict__ counters) {
-    {   // the strip's safe-operand words (k_cs_fixreorder clears the unsafe bits)
-        const uint32_t words = (strip_cap + 63u) / 64u;
-        for (uint32_t t = blockIdx.x * SL_BLOCK + threadIdx.x; t < words; t += gridDim.x * SL_BLOCK) safe[t] = ~0ull;
-    }
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t e = blockIdx.x * (SL_BLOCK / 64) + (threadIdx.x >> 6);       // wave-uniform
-    if (e >= 2u * grid_h) return;
-    const uint32_t y = e >> 1, lo = (e & 1u) ? W.lo1 : W.lo0, hi = (e & 1u) ? W.hi1 : W.hi0;
-    if (lo >= hi) return;
-    const uint32_t a = cs[y * grid_w + lo], c = cs[y * grid_w + hi] - a, base = rowbase[e];
-    for (uint32_t k0 = 0; k0 < c; k0 += 64u) {
-        const uint32_t k = k0 + lane;
-        const bool active = k < c && base + k < strip_cap;
-        if (k < c && !active) atomicAdd(&counters[3], 1u);           // strip capacity exceeded (never: it equals the main array's)
-        uint32_t key = 0;
-        if (active) key = (uint32_t)(pairs[a + k] >> 32);
-        const uint32_t kc = key < ncell ? key : ncell - 1u;
-        const WaveRun r = wave_run(kc, active);
-        uint32_t t = 0;
-        if (r.is_head) t = atomicAdd(&hist[kc], r.length);
-        t = __shfl(t, r.head_lane);
-        if (active) {
-            const uint32_t slot = base + k;
-            kt[slot] = ((u64)key << 32) | (u64)(t + r.offset);
-            sp_pos[slot] = pos_s[a + k];
-            sp_vel[slot] = vel_s[a + k];
-            back[slot] = a + k;                      // the main arrays' sorted index: where the force pass writes
-        }
-    }
-}
-
-// Received records -> strip slots [n_sm + j]; `P` is the MAIN array's StepParams (same window, same keys).
-__global__ __launch_bounds__(SL_BLOCK) void k_strip_unpack(StepParams P, uint32_t main_slots, uint32_t R, uint32_t strip_cap,
-                                                           const SlabHeader* __restrict__ hdr_left,
-                                                           const float4* __restrict__ rec_left,
-                                                           const SlabHeader* __restrict__ hdr_right,
-                                                           const float4* __restrict__ rec_right,
-                                                           float2* __restrict__ sp_pos, float2* __restrict__ sp_vel,
-                                                           u64* __restrict__ kt, uint32_t* __restrict__ hist,
-                                                           uint32_t* __restrict__ back,
-                                                           const uint32_t* __restrict__ strip_counters,
-                                                           uint32_t* __restrict__ counters) {
-    const uint32_t j = blockIdx.x * SL_BLOCK + threadIdx.x;
-    const bool in_range = j < 2u * R;
-    const bool right = j >= R;
-    const uint32_t jj = right ? j - R : j;
-    const SlabHeader* hdr = right ? hdr_right : hdr_left;
-    const float4* rec = right ? rec_right : rec_left;
-    uint32_t cnt = 0;
-    if (in_range && hdr) { cnt = hdr->count < R ? hdr->count : R; if (jj == 0 && hdr->overflow) atomicAdd(&counters[3], 1u); }
-    const uint32_t slot = strip_counters[1] + j;
-    const bool room = slot < strip_cap;
-    uint32_t key = FS_DEAD_KEY, dst = STRIP_NONE;
-    if (in_range && jj < cnt) {
-        if (!room) {
-            atomicAdd(&counters[3], 1u);
-        } else {
-            const float4 r = rec[jj];
-            const float2 p = make_float2(r.x, r.y), v = make_float2(r.z, r.w);
-            sp_pos[slot] = p;
-            sp_vel[slot] = v;
-            uint32_t cxg;
-            key = slab_key(P, predict_pos(P, p, v), &cxg);
-            if (key == FS_DEAD_KEY) atomicAdd(&counters[2], 1u);           // travelled farther than slab + halo
-            // a migrant that lands in my FAR halo zone would have been needed by my other neighbour too
-            if (!right && cxg + 2u >= P.own_hi && cxg < P.own_hi) atomicAdd(&counters[4], 1u);
-            if (right && cxg < P.own_lo + 2u && cxg >= P.own_lo) atomicAdd(&counters[4], 1u);
-            // ... and one that lands within 2 columns of the interior (or in it) was not seen by the interior launch, which
-            // ran while this message was in flight: the boundary zone was too narrow for its speed (fs_slab_set_boundary_cols)
-            if (key != FS_DEAD_KEY && P.adv_lo < P.adv_hi) {
-                if (!right && cxg + 2u >= P.adv_lo) atomicAdd(&counters[4], 1u);
-                if (right && cxg < P.adv_hi + 2u) atomicAdd(&counters[4], 1u);
-            }
-            if (key != FS_DEAD_KEY && cxg >= P.own_lo && cxg < P.own_hi) dst = main_slots + j;   // a migrant: mine from now on
-        }
-    }
-    const bool active = key != FS_DEAD_KEY;
-    const uint32_t k = key < P.ncell ? key : P.ncell - 1u;
-    const WaveRun r = wave_run(k, active);
-    uint32_t base = 0;
-    if (r.is_head) base = atomicAdd(&hist[k], r.length);
-    base = __shfl(base, r.head_lane);
-    if (in_range && room) {
-        kt[slot] = ((u64)key << 32) | (u64)(active ? base + r.offset : 0u);
-        back[slot] = dst;
-    }
-}
-
-// Results of the strip's force pass -> the main arrays.  `P` = the strip's StepParams (adv_outside = 1).
-__global__ __launch_bounds__(SL_BLOCK) void k_strip_writeback(StepParams P, uint32_t main_slots, const u64* __restrict__ sp_pairs,
-                                                              const uint32_t* __restrict__ back,
-                                                              const float2* __restrict__ sp_pos_out,
-                                                              const float2* __restrict__ sp_vel_out,
-                                                              const float2* __restrict__ sp_pred, const float* __restrict__ sp_rho,
-                                                              float2* __restrict__ pos, float2* __restrict__ vel,
-                                                              float2* __restrict__ pred, float* __restrict__ rho,
-                                                              uint32_t* __restrict__ key, unsigned char* __restrict__ owned,
-                                                              uint32_t* __restrict__ counters) {
-    const uint32_t i = blockIdx.x * SL_BLOCK + threadIdx.x;
-    if (i >= *P.n_live) return;
-    const u64 pr = sp_pairs[i];
-    const uint32_t k = (uint32_t)(pr >> 32), dst = back[(uint32_t)pr];
-    if (dst == STRIP_NONE || k == FS_DEAD_KEY) return;     // a ghost record
-    uint32_t cxl, cy;
-    key_to_local(P, k, &cxl, &cy);
-    const int32_t cg = (int32_t)cxl + P.col_origin;
-    if (!slab_advances(P, cg)) {
-        // interior context (advanced by the interior launch) — or a migrant that landed beyond the boundary zone: nobody
-        // advanced it, it is lost (k_strip_unpack has counted it in far_halo already)
-        if (dst >= main_slots) atomicAdd(&counters[2], 1u);
-        return;
-    }
-    pos[dst] = sp_pos_out[i];
-    vel[dst] = sp_vel_out[i];
-    rho[dst] = sp_rho[i];
-    if (dst >= main_slots) {                               // a migrant: the rest of its record, and it is carried over from now on
-        pred[dst] = sp_pred[i];
-        key[dst] = k;
-        owned[dst] = 1;
-    }
-}
-
 // ------------------------------------------------------------------ launchers
-static inline uint32_t nb(uint32_t n) { return (n + SL_BLOCK - 1) / SL_BLOCK; }
-// the records of a message follow its header
-static inline float4* records(const SlabHeader* h) { return h ? (float4*)(h + 1) : nullptr; }
-
 void launch_slab_maxspeed(hipStream_t st, const SlabArrays& A, uint32_t migr_count) {
     hipLaunchKernelGGL(k_slab_maxspeed, dim3(1024), dim3(SL_BLOCK), 0, st, A.counters, A.vel, A.owned, A.counters + 5, A.main_slots, migr_count);
 }
@@ -692,7 +430,7 @@ struct MsgLayout {
     uint32_t *stage_l, *stage_r;
     SlabHeader *hl, *hr;
     MsgLayout(const SlabArrays& A, const SlabMessages& M, uint32_t cap)
-        : blocks(nb(cap)), groups((blocks + MSG_GROUP - 1u) / MSG_GROUP), stage_l(A.stage), stage_r(A.stage + (size_t)blocks * SL_BLOCK),
+        : blocks(sl_blocks(cap)), groups((blocks + MSG_GROUP - 1u) / MSG_GROUP), stage_l(A.stage), stage_r(A.stage + (size_t)blocks * SL_BLOCK),
           hl((SlabHeader*)M.left), hr((SlabHeader*)M.right) {}
 };
 
@@ -713,13 +451,13 @@ void launch_slab_pack(hipStream_t st, const StepParams& P, const SlabArrays& A, 
     const MsgLayout L(A, M, cap);
     hipLaunchKernelGGL(A.counting ? k_slab_pack<true> : k_slab_pack<false>, dim3(L.blocks), dim3(SL_BLOCK), 0, st, P, cap, A.main_slots,
                        A.counting && A.overlap ? 1 : 0, O.lists ? 1 : 0, M.has_left, M.has_right, A.pos, A.vel, A.owned, A.out, A.hist, (uint2*)A.blockcnt,
-                       L.stage_l, L.stage_r, A.counters, A.counter, A.safe, A.key_s, O.prev_adv_lo, O.prev_adv_hi, O.skip_edge ? 1 : 0);
+                       L.stage_l, L.stage_r, A.counters, A.counter, A.key_s, O.prev_adv_lo, O.prev_adv_hi, O.skip_edge ? 1 : 0);
     if ((!L.hl && !L.hr) || !O.lists) return;                           // no neighbour / messages pre-built: nothing to send
     launch_slab_msg(st, P, A, M, L);
 }
 // words of `stage` and of the look-back state launch_slab_pack needs for `cap` slots
-size_t slab_stage_words(uint32_t cap) { return 2 * (size_t)nb(cap) * SL_BLOCK; }
-size_t slab_msg_groups(uint32_t cap) { return (nb(cap) + MSG_GROUP - 1u) / MSG_GROUP; }
+size_t slab_stage_words(uint32_t cap) { return 2 * (size_t)sl_blocks(cap) * SL_BLOCK; }
+size_t slab_msg_groups(uint32_t cap) { return (sl_blocks(cap) + MSG_GROUP - 1u) / MSG_GROUP; }
 
 void launch_slab_prepack(hipStream_t st, const StepParams& P_next, const SlabArrays& A, const SlabMessages& M, uint32_t edge_grid,
                          bool classify) {
@@ -734,53 +472,32 @@ void launch_slab_prepack(hipStream_t st, const StepParams& P_next, const SlabArr
 void launch_slab_unpack(hipStream_t st, const StepParams& P, const SlabArrays& A, const SlabMessages& M) {
     const SlabHeader* hl = (const SlabHeader*)M.left;
     const SlabHeader* hr = (const SlabHeader*)M.right;
-    hipLaunchKernelGGL(A.counting ? k_slab_unpack<true> : k_slab_unpack<false>, dim3(nb(2 * M.R)), dim3(SL_BLOCK), 0, st, P, A.main_slots, M.R,
+    hipLaunchKernelGGL(A.counting ? k_slab_unpack<true> : k_slab_unpack<false>, dim3(sl_blocks(2 * M.R)), dim3(SL_BLOCK), 0, st, P, A.main_slots, M.R,
                        hl, records(hl), hr, records(hr), A.pos_out, A.vel_out, A.out, A.hist, A.counters);
 }
 
 // bitonic slab mode only (the counting sort's k_cs_fixreorder<true> does the reorder itself)
 void launch_slab_reorder(hipStream_t st, const StepParams& P, const SlabArrays& A, uint32_t work_cap) {
-    hipLaunchKernelGGL(k_slab_reorder, dim3(nb(A.cap)), dim3(SL_BLOCK), 0, st, P, A.cap, A.pairs, A.pos, A.vel, A.pos_s,
+    hipLaunchKernelGGL(k_slab_reorder, dim3(sl_blocks(A.cap)), dim3(SL_BLOCK), 0, st, P, A.cap, A.pairs, A.pos, A.vel, A.pos_s,
                        A.vel_s, A.pred, A.key_s, A.owned, A.cs, A.start_ref, (GapEntry*)A.work, A.counter, work_cap, A.counters, A.safe, A.fdefer, A.fcount);
     launch_fill_gaps(st, A.cs, A.work, A.counter, work_cap);
 }
 
 void launch_slab_export(hipStream_t st, const StepParams& P, const SlabArrays& A) {
-    hipLaunchKernelGGL(k_slab_export, dim3(nb(A.cap)), dim3(SL_BLOCK), 0, st, P, A.cap, A.pos, A.pred, A.vel, A.rho, A.key_s, (AosParticle*)A.aos);
+    hipLaunchKernelGGL(k_slab_export, dim3(sl_blocks(A.cap)), dim3(SL_BLOCK), 0, st, P, A.cap, A.pos, A.pred, A.vel, A.rho, A.key_s, (AosParticle*)A.aos);
 }
 
 void launch_slab_import(hipStream_t st, const StepParams& P, const SlabArrays& A, uint32_t n) {
-    hipLaunchKernelGGL(k_slab_import, dim3(nb(A.cap)), dim3(SL_BLOCK), 0, st, P, n, A.cap, (const AosParticle*)A.aos, A.pos_out,
+    hipLaunchKernelGGL(k_slab_import, dim3(sl_blocks(A.cap)), dim3(SL_BLOCK), 0, st, P, n, A.cap, (const AosParticle*)A.aos, A.pos_out,
                        A.pred, A.vel_out, A.rho, A.key_s, A.owned);
 }
 
 void launch_slab_colhist(hipStream_t st, const StepParams& P, const SlabArrays& A, uint32_t* hist_global, uint32_t migr_count) {
-    hipLaunchKernelGGL(k_slab_colhist, dim3(nb(P.grid_w)), dim3(SL_BLOCK), 0, st, P, A.cs, hist_global);
+    hipLaunchKernelGGL(k_slab_colhist, dim3(sl_blocks(P.grid_w)), dim3(SL_BLOCK), 0, st, P, A.cs, hist_global);
     if (migr_count)
-        hipLaunchKernelGGL(k_slab_colhist_migrants, dim3(nb(migr_count)), dim3(SL_BLOCK), 0, st, P, A.main_slots, migr_count, A.owned, A.key_s, hist_global);
+        hipLaunchKernelGGL(k_slab_colhist_migrants, dim3(sl_blocks(migr_count)), dim3(SL_BLOCK), 0, st, P, A.main_slots, migr_count, A.owned, A.key_s, hist_global);
 }
 
 size_t slab_message_bytes(uint32_t R) { return sizeof(SlabHeader) + (size_t)R * sizeof(float4); }
-
-// ---- overlapped step: the boundary strips
-void launch_strip_gather(hipStream_t st, const StepParams& P, const SlabArrays& A, const StripArrays& T, const OverlapPlan& plan, uint32_t R) {
-    const StripWin W{plan.win[0], plan.win[1], plan.win[2], plan.win[3]};
-    hipLaunchKernelGGL(k_strip_rows, dim3(1), dim3(SR_BLOCK), 0, st, P.grid_w, P.grid_h, W, 2u * R, A.cs, T.rowbase, T.counters);
-    const uint32_t waves = 2u * P.grid_h, per_block = SL_BLOCK / 64;
-    hipLaunchKernelGGL(k_strip_gather, dim3((waves + per_block - 1) / per_block), dim3(SL_BLOCK), 0, st, P.grid_w, P.grid_h, P.ncell,
-                       W, T.cap, A.cs, T.rowbase, A.pairs, A.pos_s, A.vel_s, T.pos, T.vel, T.kt, T.hist, T.back, T.safe, A.counters);
-}
-
-void launch_strip_unpack(hipStream_t st, const StepParams& P, const SlabArrays& A, const StripArrays& T, const SlabMessages& M) {
-    const SlabHeader* hl = (const SlabHeader*)M.left;
-    const SlabHeader* hr = (const SlabHeader*)M.right;
-    hipLaunchKernelGGL(k_strip_unpack, dim3(nb(2 * M.R)), dim3(SL_BLOCK), 0, st, P, A.main_slots, M.R, T.cap, hl,
-                       records(hl), hr, records(hr), T.pos, T.vel, T.kt, T.hist, T.back, T.counters, A.counters);
-}
-
-void launch_strip_writeback(hipStream_t st, const StepParams& P_strip, const SlabArrays& A, const StripArrays& T) {
-    hipLaunchKernelGGL(k_strip_writeback, dim3(nb(T.cap)), dim3(SL_BLOCK), 0, st, P_strip, A.main_slots, T.pairs, T.back, T.pos_out,
-                       T.vel_out, T.pred, T.rho, A.pos_out, A.vel_out, A.pred, A.rho, A.key_s, A.owned, A.counters);
-}
 
 }  // namespace fsd

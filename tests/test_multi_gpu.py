@@ -441,6 +441,177 @@ def _read_message(fs, buf, message_bytes):
     return int(hdr[0]), int(hdr[1]), rec
 
 
+def _predicted_columns(fs, st, tick, pos_x, vel_x):
+    """Global column of the predicted x (position + velocity * dt, clamped to the bounds): the column rule, in numpy."""
+    from gpu_fluid_simulation_amd import multi
+    px = (pos_x.astype(np.float32) + vel_x.astype(np.float32) * np.float32(tick.delta)).astype(np.float32)
+    bs = np.float32(st.size.x) * np.float32(0.5)
+    px = np.where(np.abs(px) > bs, bs * np.sign(px), px).astype(np.float32)
+    return multi.global_columns(px, st.size.x, st.smoothing_radius)
+
+
+def _message(fs, st, sim, columns, count=None, overflow=0):
+    """An incoming message written by hand: 16-byte header {count, overflow, 0, 0}, then one {px, py, 0, 0} record at the
+    centre of each of `columns` (distinct heights, spread over 6 of the domain's 8 units).  Returns (device buffer, the records)."""
+    rec = np.zeros((len(columns), 4), dtype=np.float32)
+    h = np.float32(st.smoothing_radius)
+    rec[:, 0] = (np.asarray(columns, dtype=np.float32) - np.float32(0.5)) * h - np.float32(st.size.x) * np.float32(0.5)
+    rec[:, 1] = np.float32(-3.0) + np.float32(6.0) * np.arange(len(columns), dtype=np.float32) / np.float32(max(len(columns), 1))
+    raw = np.zeros(sim.message_bytes, dtype=np.uint8)
+    raw[:16] = np.array([len(columns) if count is None else count, overflow, 0, 0], dtype=np.uint32).view(np.uint8)
+    raw[16:16 + 16 * len(columns)] = rec.view(np.uint8).reshape(-1)
+    buf = fs.ResizableBuffer("in", np.uint8, sim.message_bytes)
+    buf.write(0, raw)
+    return buf, rec
+
+
+SLAB_MODES = {"serial": dict(serial=True), "edge": dict(), "strips": dict(strips=True), "bitonic": dict(serial=True, sort_mode="bitonic")}
+
+
+def _middle_slab(fs, mode, recv):
+    kw = dict(SLAB_MODES[mode])
+    if kw.get("sort_mode") == "bitonic":
+        kw["sort_mode"] = fs.FS_SORT_BITONIC
+    sim, st, tick, own, (lo, hi) = _one_slab(fs, 4096, 0.25, 0.75, recv=recv, **kw)
+    assert hi - lo >= 8 and sim.step_mode == {"serial": 0, "edge": 1, "strips": 2, "bitonic": 0}[mode]
+    if mode == "strips":
+        sim.set_boundary_cols(3)
+    return sim, st, tick, own, lo, hi
+
+
+def _step_with(fs, sim, tick, left, right):
+    out = [fs.ResizableBuffer(k, np.uint8, sim.message_bytes) for k in ("sl", "sr")]
+    sim.pack(tick, C.c_void_p(out[0].device_ptr), C.c_void_p(out[1].device_ptr))
+    sim.wait_packed()
+    sim.step(C.c_void_p(left.device_ptr), C.c_void_p(right.device_ptr))
+    sim.sync()
+    rec, owned = sim.download()
+    return sim.counters(), int(owned.sum())
+
+
+@pytest.mark.parametrize("mode", list(SLAB_MODES))
+def test_unpack_counters_of_hand_built_messages(fs, mode):
+    """k_slab_unpack / k_strip_unpack (+ k_strip_writeback): a middle slab [lo, hi) stepped once with incoming messages written
+    by the test — per side a record in each ghost column, in an owned column well inside, in the two owned columns at the FAR
+    edge (and in the third, which the rule must not reach) and one beyond window + halo.  Expected, from the column rule alone: lost +1 per record beyond the window, far_halo
+    +1 per record in the far two owned columns, one more owned particle per migrant.  The strips step adds its interior rule
+    (a migrant within 2 columns of the interior [lo + z, hi - z), or in it: far_halo) and loses a migrant nobody advanced."""
+    sim, st, tick, own, lo, hi = _middle_slab(fs, mode, recv=1024)     # room for the slab's own outgoing halo: overflow stays 0
+    cols_l = [lo - 2, lo - 1, lo + 6, hi - 3, hi - 2, hi - 1, hi + 2]
+    cols_r = [hi + 1, hi, hi - 7, lo + 2, lo + 1, lo, lo - 3]
+    left, rec_l = _message(fs, st, sim, cols_l)
+    right, rec_r = _message(fs, st, sim, cols_r)
+    z = sim.boundary_cols if mode == "strips" else 0
+    adv_lo, adv_hi = lo + z, hi - z
+    assert mode != "strips" or (z == 3 and adv_lo < adv_hi)
+    lost = far = migrants = 0
+    for is_right, rec in ((False, rec_l), (True, rec_r)):
+        got = _predicted_columns(fs, st, tick, rec[:, 0], rec[:, 2])
+        assert list(got) == (cols_r if is_right else cols_l)
+        for c in got:
+            in_window = lo - 2 <= c < hi + 2
+            mine = lo <= c < hi
+            lost += not in_window
+            far += (mine and c + 2 >= hi) if not is_right else (mine and c < lo + 2)
+            if mode == "strips" and in_window:
+                far += (c + 2 >= adv_lo) if not is_right else (c < adv_hi + 2)
+                lost += mine and adv_lo <= c < adv_hi            # landed in the interior: advanced by nobody
+                mine = mine and not (adv_lo <= c < adv_hi)
+            migrants += mine
+    pc = _predicted_columns(fs, st, tick, own["position"][:, 0], own["velocity"][:, 0])
+    stay = int(((pc >= lo) & (pc < hi)).sum())                  # the slab's own particles that remain owned
+    c, owned = _step_with(fs, sim, tick, left, right)
+    print(mode, c, owned, "expected", dict(lost=int(lost), far_halo=int(far), owned=stay + int(migrants)))
+    assert (c["lost"], c["far_halo"], c["overflow"]) == (lost, far, 0)
+    assert owned == stay + migrants
+    sim.close()
+
+
+@pytest.mark.parametrize("mode", list(SLAB_MODES))
+def test_unpack_takes_no_more_records_than_a_message_holds(fs, mode):
+    """A header that claims count = R + 5 with the overflow flag set: exactly the R records the message holds are taken (all
+    migrants into the first owned column), and the flag reaches fs_slab_counters.overflow."""
+    R = 1024                                  # (the slab's own outgoing halo fits: the only overflow is the header's)
+    sim, st, tick, own, lo, hi = _middle_slab(fs, mode, recv=R)
+    left, _ = _message(fs, st, sim, [lo] * R, count=R + 5, overflow=1)
+    right, _ = _message(fs, st, sim, [])
+    pc = _predicted_columns(fs, st, tick, own["position"][:, 0], own["velocity"][:, 0])
+    stay = int(((pc >= lo) & (pc < hi)).sum())                  # the slab's own particles that remain owned
+    c, owned = _step_with(fs, sim, tick, left, right)
+    print(mode, c, owned, "expected owned", stay + R)
+    assert owned == stay + R
+    assert c["overflow"] != 0 and (c["lost"], c["far_halo"]) == (0, 0)
+    sim.close()
+
+
+def _trimmed_edge_slab(fs, mode):
+    """The leftmost slab of a split whose outer edge was trimmed (own_lo > 0, no left neighbour), with velocities that carry
+    some particles of its first columns across own_lo in one tick."""
+    from gpu_fluid_simulation_amd import multi
+    kw = dict(SLAB_MODES[mode])
+    st, off, tick = fs.dam_break_2d(4096)
+    lat = fs.reference_lattice(st, off)
+    rng = np.random.default_rng(5)
+    lat["velocity"] = rng.uniform(-30.0, 30.0, size=lat["velocity"].shape).astype(np.float32)
+    cols = multi.global_columns(lat["position"][:, 0], st.size.x, st.smoothing_radius)
+    occ = np.nonzero(np.bincount(cols))[0]
+    lo, hi = int(occ[0]) + 4, int(occ[0]) + 20
+    own = lat[(cols >= lo) & (cols < hi)]
+    gw = int(np.ceil(np.float32(st.size.x) / np.float32(st.smoothing_radius))) + 2
+    recv = 1024
+    sim = fs.SlabSimulation(st, lo, hi, False, True, own.shape[0] + 2 * recv + 4096, recv, max_cols=gw, device=0, **kw)
+    sim.upload_owned(own)
+    return sim, st, tick, own, lo, hi
+
+
+def test_pack_counts_particles_that_leave_a_trimmed_outer_edge(fs):
+    """k_slab_pack's leaver rule: no left neighbour and own_lo > 0 — every owned particle predicted left of own_lo is `lost`,
+    exactly as many as the column rule counts.  After three steps the counter is the same for the serial, the strips and the
+    edge-first step (whose edge columns go through k_slab_prepack's use of the rule)."""
+    after = {}
+    for mode in ("serial", "strips", "edge"):
+        sim, st, tick, own, lo, hi = _trimmed_edge_slab(fs, mode)
+        assert lo > 0 and hi - lo >= 8
+        k = int((_predicted_columns(fs, st, tick, own["position"][:, 0], own["velocity"][:, 0]) < lo).sum())
+        assert k > 0
+        sr = fs.ResizableBuffer("sr", np.uint8, sim.message_bytes)
+        empty = fs.ResizableBuffer("e", np.uint8, sim.message_bytes)
+        for step in range(3):
+            sim.pack(tick, None, C.c_void_p(sr.device_ptr))
+            if step == 0:
+                first = sim.counters()["lost"]
+                print(mode, "lost after the first pack", first, "expected", k)
+                assert first == k
+            sim.wait_packed()
+            sim.step(None, C.c_void_p(empty.device_ptr))
+        sim.sync()
+        after[mode] = sim.counters()["lost"]
+        sim.close()
+    print("lost after three steps", after)
+    assert after["serial"] == after["strips"] == after["edge"] >= k
+
+
+def test_bitonic_slabs_with_neighbours_match_single_gpu(fs):
+    """test_slabs_match_single_gpu's (2, 4096, None) case with the reference network as the sort of both sides: k_slab_pack<false>,
+    k_slab_unpack<false> and k_slab_reorder with records actually received.  Same bounds as the counting case."""
+    from tests.slab_oracle import assert_statistics_close, match_and_compare
+    n = 4096
+    st, off, tick = fs.dam_break_2d(n)
+    slabs = InProcessSlabs(fs, st, off, 2, cap=n + 4 * 2048, recv=2048, sort_mode=fs.FS_SORT_BITONIC)
+    single = fs.FluidSimulation(st, device=0, initial_offset=off, ref_quirks=False, sort_mode=fs.FS_SORT_BITONIC)
+    single.upload_particles(slabs.initial)
+    assert slabs.owned().shape[0] == n
+    for s in range(24):
+        slabs.step(tick)
+        single.tick(tick)
+        if s in (0, 1, 4):
+            slabs.assert_clean()
+            match_and_compare(slabs.owned(), single.download_particles(), st.smoothing_radius,
+                              max_key_flips=0.0 if s < 2 else 0.02)
+    slabs.assert_clean()
+    assert_statistics_close(slabs.owned(), single.download_particles(), n)
+
+
 def test_pack_messages_are_in_slot_order_and_deterministic(fs):
     """k_slab_pack + k_slab_msg: the records each neighbour gets are the flagged particles in SLOT order (the look-back
     offsets make the compaction deterministic), identical from run to run, and exactly the particles whose predicted

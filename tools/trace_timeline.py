@@ -1,6 +1,7 @@
 """Timeline of ONE step out of a `rocprofv3 --kernel-trace ... --output-format csv` run: every dispatch between two
 consecutive launches of a delimiter kernel ON ONE QUEUE, with start offset, duration and the queue (= HIP stream) it ran on —
-shows what runs beside what (the halo exchange beside the interior columns' kernels in an overlapped slab step).
+shows what runs beside what (the halo exchange beside the interior columns' kernels in an overlapped slab step).  The default
+delimiter k_slab_pack (kernels_slab.hip) opens every slab step; a strips step's k_strip_* kernels are in kernels_strip.hip.
 
   python tools/trace_timeline.py DIR/p_kernel_trace.csv [delimiter=k_slab_pack] [which=-2] [queue-of-delimiter index=middle]
 """
