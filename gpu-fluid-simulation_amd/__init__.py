@@ -28,11 +28,14 @@ from ._abi import (  # noqa: F401
     PASS_NAMES,
     SAMPLE3_DTYPE,
     SAMPLE_DTYPE,
+    SURFACE_HIT_DTYPE,
+    Camera3,
     ExtensionMissing,
     Options,
     Settings,
     Settings3,
     SlabConfig,
+    SurfaceParams3,
     SlabCounters,
     SortStep,
     TickSettings,
@@ -47,6 +50,7 @@ from ._abi import (  # noqa: F401
 __all__ = [
     "FluidSimulation", "ResizableBuffer", "SimulationSettings", "default_tick_settings", "dam_break_2d",
     "FluidSimError", "load_library", "PARTICLE_DTYPE", "SAMPLE_DTYPE", "SAMPLE3_DTYPE",
+    "SURFACE_HIT_DTYPE", "look_at_camera", "shade_surface",
 ]
 
 
@@ -519,6 +523,54 @@ class FluidSimulation3D:
         """fs3_sample_points_device: device pointers (n fs_vec3 in, n 40-byte fs3_sample out), enqueued on the simulation's
         stream after the steps in flight; non-blocking."""
         _check(self._lib, self._lib.fs3_sample_points_device(self._h, C.c_void_p(points_ptr), int(n), C.c_void_p(out_ptr)))
+
+
+    # -- 3D surface rendering (build extension; DESIGN.md §16) ---------------
+    def render_surface(self, camera, params, out=None):
+        """Ray-march the iso-surface of the density into a G-buffer: a [height, width] SURFACE_HIT_DTYPE array (ray parameter,
+        density, outward normal, Shepard velocity, march index, hit kind) for a Camera3 (look_at_camera) and SurfaceParams3.
+        Blocking; needs a step since create / the last upload.  `out`: a device pointer (int) instead: fs3_render_surface_device,
+        enqueued on the simulation's stream after the steps in flight, non-blocking, returns None."""
+        if out is not None:
+            _check(self._lib, self._lib.fs3_render_surface_device(self._h, C.byref(camera), C.byref(params), C.c_void_p(int(out))))
+            return None
+        hits = np.zeros((int(camera.height), int(camera.width)), dtype=SURFACE_HIT_DTYPE)
+        _check(self._lib, self._lib.fs3_render_surface(self._h, C.byref(camera), C.byref(params), hits.ctypes.data_as(C.c_void_p)))
+        return hits
+
+
+def look_at_camera(eye, target, up, fov_y_or_extent, width, height, orthographic=False):
+    """A Camera3 at `eye` looking at `target`.  Perspective: `fov_y_or_extent` is the vertical field of view in radians;
+    orthographic: the world height of the image.  `right` and `up` of the record span the whole image (width / height gives the
+    aspect), so pixel row 0 is the image's BOTTOM edge along `up`: flip the rows for a top-down image file."""
+    e, t, u = (np.asarray(v, dtype=np.float64) for v in (eye, target, up))
+    fwd = t - e
+    fwd = fwd / np.linalg.norm(fwd)
+    right = np.cross(fwd, u)
+    right = right / np.linalg.norm(right)
+    upv = np.cross(right, fwd)
+    span_y = float(fov_y_or_extent) if orthographic else 2.0 * np.tan(0.5 * float(fov_y_or_extent))
+    span_x = span_y * float(width) / float(height)
+    vec = lambda a: Vec3(*[float(np.float32(x)) for x in a])      # noqa: E731
+    return Camera3(vec(e), vec(fwd), vec(right * span_x), vec(upv * span_y), int(width), int(height), 1 if orthographic else 0, 0)
+
+
+def shade_surface(hits, light=(0.4, -0.8, -0.45), max_speed=None):
+    """Lambert shading of a render_surface G-buffer (numpy only): straight-alpha RGBA float32 of the hits' shape, for write_png.
+    `light` points from the surface towards the light.  Water blue, tinted towards white by speed (relative to `max_speed`,
+    default: the fastest hit); a hit whose first sample was already inside the fluid (hit == 2) is drawn flat and darker."""
+    l = np.asarray(light, dtype=np.float32)
+    l = l / np.linalg.norm(l)
+    lambert = np.clip((hits["normal"] * l).sum(axis=-1), 0.0, 1.0)
+    speed = np.sqrt((hits["velocity"].astype(np.float32) ** 2).sum(axis=-1))
+    top = float(max_speed) if max_speed else float(speed.max())
+    tint = np.clip(speed / top, 0.0, 1.0)[..., None] if top > 0 else np.zeros(hits.shape + (1,), dtype=np.float32)
+    base = np.float32([0.10, 0.35, 0.85]) * (1.0 - tint) + np.float32([0.95, 0.97, 1.0]) * tint
+    shade = np.where(hits["hit"] == 2, 0.35, 0.25 + 0.75 * lambert)[..., None]
+    rgba = np.zeros(hits.shape + (4,), dtype=np.float32)
+    rgba[..., 3] = (hits["hit"] != 0).astype(np.float32)
+    rgba[..., :3] = base * shade * rgba[..., 3:4]
+    return rgba
 
 
 def reference_lattice_3d(settings, offset=(0.0, 0.0, 0.0)):

@@ -141,6 +141,23 @@ class Sample3(C.Structure):
                 ("neighbours", C.c_uint32), ("cell", C.c_uint32)]
 
 
+class Camera3(C.Structure):
+    """fs3_camera (include/fluidsim.h "3D surface rendering"): 64 bytes."""
+    _fields_ = [("eye", Vec3), ("forward", Vec3), ("right", Vec3), ("up", Vec3), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("orthographic", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class SurfaceParams3(C.Structure):
+    """fs3_surface_params (include/fluidsim.h): 20 bytes."""
+    _fields_ = [("iso", C.c_float), ("t_near", C.c_float), ("ds", C.c_float), ("max_steps", C.c_uint32), ("refine", C.c_uint32)]
+
+
+class SurfaceHit3(C.Structure):
+    """fs3_surface_hit (include/fluidsim.h): 40 bytes."""
+    _fields_ = [("t", C.c_float), ("density", C.c_float), ("normal", Vec3), ("velocity", Vec3), ("steps", C.c_uint32),
+                ("hit", C.c_uint32)]
+
+
 class SlabConfig(C.Structure):
     _fields_ = [
         ("own_lo", C.c_uint32), ("own_hi", C.c_uint32),
@@ -172,6 +189,10 @@ assert SAMPLE_DTYPE.itemsize == 24 and C.sizeof(Sample) == 24
 SAMPLE3_DTYPE = np.dtype([("density", "<f4"), ("weight", "<f4"), ("velocity", "<f4", (3,)), ("gradient", "<f4", (3,)),
                           ("neighbours", "<u4"), ("cell", "<u4")])
 assert SAMPLE3_DTYPE.itemsize == 40 and C.sizeof(Sample3) == 40 and C.sizeof(View3) == 36
+# fs3_surface_hit as a numpy structured dtype (offsets 0/4/8/20/32/36).
+SURFACE_HIT_DTYPE = np.dtype([("t", "<f4"), ("density", "<f4"), ("normal", "<f4", (3,)), ("velocity", "<f4", (3,)),
+                              ("steps", "<u4"), ("hit", "<u4")])
+assert SURFACE_HIT_DTYPE.itemsize == 40 and C.sizeof(SurfaceHit3) == 40 and C.sizeof(Camera3) == 64 and C.sizeof(SurfaceParams3) == 20
 assert C.sizeof(Uniform) == 120
 assert C.sizeof(Settings) == 28
 assert C.sizeof(TickSettings) == 60
@@ -296,6 +317,8 @@ PROTOTYPES = {
     "fs3_sample_points": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "fs3_sample_points_device": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "fs3_sample_grid": (C.c_int, [_P, C.POINTER(View3), _P]),
+    "fs3_render_surface": (C.c_int, [_P, C.POINTER(Camera3), C.POINTER(SurfaceParams3), _P]),
+    "fs3_render_surface_device": (C.c_int, [_P, C.POINTER(Camera3), C.POINTER(SurfaceParams3), _P]),
     "fs_selftest_constdiv": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_uint32)]),
     "fs_sort_plan_read": (C.c_int, [C.c_void_p, C.POINTER(SortPlanInfo)]),
     "fs_selftest_sort_policy": (C.c_int, [C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t,

@@ -350,4 +350,57 @@ fs_status fs3_sample_grid(fs_sim3* s, const fs3_view* view, fs3_sample* out) {
     return sample3_host(s, nullptr, view, n, out);
 }
 
+// ---- 3D surface rendering -----------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// The checks of both calls, in the order the header lists them.
+fs_status surface3_check(const fs_sim3* s, const fs3_camera* cam, const fs3_surface_params* sp, const void* out) {
+    static_assert(sizeof(fs3_camera) == 64 && sizeof(fs3_surface_params) == 20 && sizeof(fs3_surface_hit) == 40, "3D surface rendering records");
+    if (!s || !cam || !sp || !out) return fail(FS_ERR_INVALID, "null argument");
+    const uint64_t wh = (uint64_t)cam->width * cam->height;
+    if (wh == 0 || wh > (1ull << 26)) return fail(FS_ERR_INVALID, "bad image size");
+    if (cam->reserved != 0) return fail(FS_ERR_INVALID, "camera: reserved must be 0");
+    if (cam->orthographic != 0 && cam->orthographic != 1) return fail(FS_ERR_INVALID, "camera: orthographic must be 0 or 1");
+    if (!std::isfinite(sp->iso) || !(sp->iso > 0.0f)) return fail(FS_ERR_INVALID, "surface params: iso must be finite and > 0");
+    if (!std::isfinite(sp->t_near) || !(sp->t_near >= 0.0f)) return fail(FS_ERR_INVALID, "surface params: t_near must be finite and >= 0");
+    if (!std::isfinite(sp->ds) || !(sp->ds > 0.0f)) return fail(FS_ERR_INVALID, "surface params: ds must be finite and > 0");
+    if (sp->max_steps < 1u || sp->max_steps > 4096u) return fail(FS_ERR_INVALID, "surface params: max_steps must be 1 .. 4096");
+    if (sp->refine > 24u) return fail(FS_ERR_INVALID, "surface params: refine must be 0 .. 24");
+    if (s->sample_stale) return fail(FS_ERR_INVALID, "rendering needs a step since create and since the last upload of particles");
+    return FS_OK;
+}
+
+fs_status surface3_enqueue(fs_sim3* s, const fs3_camera* cam, const fs3_surface_params* sp, fs3_surface_hit* out_dev) {
+    const fsd::Params3 P = params3_common(*s, s->mass);
+    fsd::Surface3Query Q;
+    Q.eye = make_float3(cam->eye.x, cam->eye.y, cam->eye.z);
+    Q.forward = make_float3(cam->forward.x, cam->forward.y, cam->forward.z);
+    Q.right = make_float3(cam->right.x, cam->right.y, cam->right.z);
+    Q.up = make_float3(cam->up.x, cam->up.y, cam->up.z);
+    Q.width = cam->width; Q.height = cam->height; Q.orthographic = cam->orthographic;
+    Q.iso = sp->iso; Q.t_near = sp->t_near; Q.ds = sp->ds; Q.max_steps = sp->max_steps; Q.refine = sp->refine;
+    Q.out = out_dev;
+    fsd::launch3_render_surface(s->stream, P, s->arrays(), Q);
+    FS_HIP(hipGetLastError());
+    return FS_OK;
+}
+}  // namespace
+extern "C" {
+
+fs_status fs3_render_surface(fs_sim3* s, const fs3_camera* cam, const fs3_surface_params* sp, fs3_surface_hit* out) {
+    FS_TRY(surface3_check(s, cam, sp, out));
+    FS_HIP(hipSetDevice(s->device));
+    const size_t n = (size_t)cam->width * cam->height;
+    FS_TRY(fsd::staged_query(s->stream, (const fs_vec3*)nullptr, n, out, nullptr, 0, [&](const fs_vec3*, fs3_surface_hit* dout, float*) {
+        return surface3_enqueue(s, cam, sp, dout);
+    }));
+    return sort_health3(s);
+}
+
+fs_status fs3_render_surface_device(fs_sim3* s, const fs3_camera* cam, const fs3_surface_params* sp, fs3_surface_hit* out_dev) {
+    FS_TRY(surface3_check(s, cam, sp, out_dev));
+    FS_HIP(hipSetDevice(s->device));
+    return surface3_enqueue(s, cam, sp, out_dev);
+}
+
 }  // extern "C"

@@ -80,4 +80,16 @@ struct Sample3Query {
 };
 void launch3_sample(hipStream_t st, const Params3& P, const Arrays3& A, const Sample3Query& Q);
 
+// 3D surface rendering (kernels_render3d.hip): one ray per pixel of a width x height image, marched against the
+// same state and the same P as a Sample3Query.  Passed to the kernel by value.
+struct Surface3Query {
+    float3 eye{}, forward{}, right{}, up{};
+    uint32_t width = 0, height = 0;
+    int32_t orthographic = 0;
+    float iso = 0.0f, t_near = 0.0f, ds = 0.0f;
+    uint32_t max_steps = 0, refine = 0;
+    void* out = nullptr;               // width * height fs3_surface_hit records, device
+};
+void launch3_render_surface(hipStream_t st, const Params3& P, const Arrays3& A, const Surface3Query& Q);
+
 }  // namespace fsd

@@ -149,6 +149,10 @@ private:
 
 // Build extension, NOT in the reference (2D only): the 3D step (include/fluidsim.h fs3_*) and its field sampling.
 using Sample3 = fs3_sample;
+using Camera3 = fs3_camera;               // build extension: 3D surface rendering
+using SurfaceParams3 = fs3_surface_params;
+using SurfaceHit3 = fs3_surface_hit;
+static_assert(sizeof(Camera3) == 64 && sizeof(SurfaceParams3) == 20 && sizeof(SurfaceHit3) == 40, "3D surface rendering records");
 class FluidSimulation3D {
 public:
     static FluidSimulation3D new_(int device, const fs3_settings& settings, fs_vec3 initial_offset = fs_vec3{0.0f, 0.0f, 0.0f},
@@ -190,6 +194,17 @@ public:
     }
     // ... with device pointers, enqueued on the simulation's stream after the ticks in flight; non-blocking
     void sample_device(const fs_vec3* points_dev, size_t n, Sample3* out_dev) { check(fs3_sample_points_device(h_, points_dev, n, out_dev)); }
+    // 3D surface rendering: ray-marches the density's iso-surface into a G-buffer (distance, density, outward normal, Shepard
+    // velocity, march index, hit kind), pixel (i, j) at j * width + i.  Blocking; needs a tick since creation / the last upload.
+    std::vector<SurfaceHit3> render_surface(const Camera3& camera, const SurfaceParams3& params) {
+        std::vector<SurfaceHit3> out((size_t)camera.width * camera.height);
+        check(fs3_render_surface(h_, &camera, &params, out.data()));
+        return out;
+    }
+    // ... into a device buffer, enqueued on the simulation's stream after the ticks in flight; non-blocking
+    void render_surface_device(const Camera3& camera, const SurfaceParams3& params, SurfaceHit3* out_dev) {
+        check(fs3_render_surface_device(h_, &camera, &params, out_dev));
+    }
     fs_sim3* handle() { return h_; }
 
 private:

@@ -108,6 +108,17 @@ const _: () = assert!(std::mem::size_of::<Sample3>() == 40);
 #[repr(C)] #[derive(Clone, Copy, Debug)]
 pub struct View3 { pub world_min: Vec3, pub world_max: Vec3, pub width: u32, pub height: u32, pub depth: u32 }
 const _: () = assert!(std::mem::size_of::<Particle3>() == 48);
+/// fs3_camera: the rays of a `width` x `height` image (build extension, include/fluidsim.h "3D surface rendering"); 64 bytes.
+/// `right` / `up` span the whole image; `orthographic` 0: rays leave `eye`, 1: parallel rays along `forward`; `reserved` is 0.
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct Camera3 { pub eye: Vec3, pub forward: Vec3, pub right: Vec3, pub up: Vec3, pub width: u32, pub height: u32, pub orthographic: i32, pub reserved: u32 }
+/// fs3_surface_params: iso > 0, t_near >= 0, ds > 0, max_steps 1 ..= 4096, refine 0 ..= 24; 20 bytes.
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct SurfaceParams3 { pub iso: f32, pub t_near: f32, pub ds: f32, pub max_steps: u32, pub refine: u32 }
+/// fs3_surface_hit: one pixel of the G-buffer; 40 bytes, offsets 0/4/8/20/32/36.  `hit` 0: miss, 1: bracketed and refined, 2: the first sample was inside.
+#[repr(C)] #[derive(Clone, Copy, Default, Debug, PartialEq)]
+pub struct SurfaceHit3 { pub t: f32, pub density: f32, pub normal: Vec3, pub velocity: Vec3, pub steps: u32, pub hit: u32 }
+const _: () = assert!(std::mem::size_of::<Camera3>() == 64 && std::mem::size_of::<SurfaceParams3>() == 20 && std::mem::size_of::<SurfaceHit3>() == 40);
 
 #[repr(C)] pub struct fs_sim { _p: [u8; 0] }
 #[repr(C)] pub struct fs_sim3 { _p: [u8; 0] }
@@ -221,6 +232,8 @@ extern "C" {
     fn fs3_sample_points(sim: *mut fs_sim3, points: *const Vec3, n: usize, out: *mut Sample3) -> c_int;
     fn fs3_sample_points_device(sim: *mut fs_sim3, points_dev: *const Vec3, n: usize, out_dev: *mut Sample3) -> c_int;
     fn fs3_sample_grid(sim: *mut fs_sim3, view: *const View3, out: *mut Sample3) -> c_int;
+    fn fs3_render_surface(sim: *mut fs_sim3, camera: *const Camera3, params: *const SurfaceParams3, out_host: *mut SurfaceHit3) -> c_int;
+    fn fs3_render_surface_device(sim: *mut fs_sim3, camera: *const Camera3, params: *const SurfaceParams3, out_dev: *mut SurfaceHit3) -> c_int;
     // ResizableBuffer<T> (src/buffer.rs)
     fn fs_buffer_create(device: c_int, elem_size: usize, len: usize, name: *const c_char, out: *mut *mut fs_buffer) -> c_int;
     fn fs_buffer_resize(buf: *mut fs_buffer, new_cap: usize, resized: *mut c_int) -> c_int;
@@ -588,6 +601,16 @@ impl FluidSimulation3D {
     /// The buffers must stay valid until the stream has passed the call.
     pub unsafe fn sample_device(&mut self, points_dev: *const Vec3, n: usize, out_dev: *mut Sample3) {
         check(fs3_sample_points_device(self.raw, points_dev, n, out_dev));
+    }
+    /// Build extension: 3D surface rendering (include/fluidsim.h).  Ray-marches the density's iso-surface into a G-buffer, pixel
+    /// (i, j) at `j * width + i`.  Blocking; needs a tick since `new` / the last upload.
+    pub fn render_surface(&mut self, camera: &Camera3, params: &SurfaceParams3) -> Vec<SurfaceHit3> {
+        let mut out = vec![SurfaceHit3::default(); camera.width as usize * camera.height as usize];
+        check(unsafe { fs3_render_surface(self.raw, camera, params, out.as_mut_ptr()) }); out
+    }
+    /// ... into a device buffer of `width * height` records; enqueued on the simulation's stream, non-blocking.
+    pub unsafe fn render_surface_device(&mut self, camera: &Camera3, params: &SurfaceParams3, out_dev: *mut SurfaceHit3) {
+        check(fs3_render_surface_device(self.raw, camera, params, out_dev));
     }
     pub fn stream(&self) -> *mut c_void { unsafe { fs3_stream(self.raw) } }
 }

@@ -604,6 +604,67 @@ fs_status fs3_sample_points(fs_sim3* sim, const fs_vec3* points, size_t n, fs3_s
 fs_status fs3_sample_points_device(fs_sim3* sim, const fs_vec3* points_dev, size_t n, fs3_sample* out_dev);
 fs_status fs3_sample_grid(fs_sim3* sim, const fs3_view* view, fs3_sample* out);
 
+/* ------------------------------------------------ 3D surface rendering (build extension, opt-in by being called) */
+/* A headless ray-marcher over the field of "3D field sampling": one ray per pixel is marched through the density until it reaches
+ * `iso`, the crossing is refined by bisection, and one full sample at the hit gives the G-buffer record (distance, density,
+ * outward normal, Shepard velocity).  Shading is the caller's.  All arithmetic is f32 without contraction.  `sqrt` and `/` are
+ * correctly rounded.  `density(x)` is the `density` sum of the "3D field sampling" statement at point `x`, and `sample(x)` is that
+ * statement's full record.  The state is exactly that statement's: the records, the grid, the settings and the mass of the last
+ * step.
+ *
+ * For pixel (i, j), stored at out[j * width + i]:
+ *     u = ((float)i + 0.5f) / (float)width  - 0.5f;   v = ((float)j + 0.5f) / (float)height - 0.5f
+ *     perspective:  o = eye;                                   D.a = (forward.a + u * right.a) + v * up.a
+ *     orthographic: o.a = (eye.a + u * right.a) + v * up.a;    D = forward
+ *     len = sqrt((D.x*D.x + D.y*D.y) + D.z*D.z);   d.a = D.a / len;   x(t).a = o.a + t * d.a
+ *     t_k = t_near + (float)k * ds                 k = 0 .. max_steps-1   (a product, never a running sum)
+ *     K = the smallest k with density(x(t_k)) >= iso
+ *     no such k:  record = {t 0, density 0, normal 0, velocity 0, steps max_steps, hit 0}
+ *     K == 0:     t = t_0, hit = 2
+ *     K  > 0:     lo = t_{K-1}, hi = t_K; `refine` times: mid = 0.5f * (lo + hi); density(x(mid)) >= iso ? hi = mid : lo = mid;   t = hi, hit = 1
+ *     S = sample(x(t));  density = S.density;  gl = sqrt((gx*gx + gy*gy) + gz*gz) of S.gradient
+ *     normal.a = gl > 0 ? (-S.gradient.a) / gl : +0;   velocity.a = S.weight > 0 ? S.velocity.a / S.weight : +0;   steps = K
+ *
+ * Which samples the kernel actually evaluates is its own business.  It may skip any t_k for which it can prove density < iso, for
+ * instance when the point's 27 cells hold no particle, so the sum is exactly +0 and iso > 0.  The record must not change.  `steps`
+ * is defined by K, not by work done, so it stays implementation-independent.
+ *
+ * Pixels with len == 0 or with non-finite camera or ray values get unspecified records.  No out-of-bounds access is allowed in
+ * those cases.
+ *
+ * Checks, in this order:
+ *  1. NULL handle, camera, params or `out` -> FS_ERR_INVALID.
+ *  2. width * height == 0 or > 2^26, reserved != 0, or orthographic not 0 or 1 -> FS_ERR_INVALID.
+ *  3. A params field outside the ranges below, NaN included -> FS_ERR_INVALID.
+ *  4. No step since create or since the last fs3_upload_particles with n > 0 (the rule of "3D field sampling") -> FS_ERR_INVALID.
+ *
+ * fs3_render_surface: host output, blocking.  fs3_render_surface_device: device output on the handle's device; enqueued on
+ * fs3_stream(sim) after the steps in flight; stream-ordered, non-blocking, no allocation, no host read.  If the call is not used,
+ * there is no launch and no allocation.  See DESIGN.md §16. */
+typedef struct fs3_camera {       /* 64 bytes */
+    fs_vec3 eye, forward, right, up;   /* right / up span the whole image (they carry field of view and aspect) */
+    uint32_t width, height;
+    int32_t orthographic;              /* 0: perspective, rays leave `eye`; 1: parallel rays along `forward` */
+    uint32_t reserved;                 /* must be 0 */
+} fs3_camera;
+typedef struct fs3_surface_params { /* 20 bytes */
+    float iso;            /* density threshold, finite, > 0 */
+    float t_near;         /* finite, >= 0 */
+    float ds;             /* march step, finite, > 0 */
+    uint32_t max_steps;   /* 1 .. 4096 */
+    uint32_t refine;      /* bisection iterations, 0 .. 24 */
+} fs3_surface_params;
+typedef struct fs3_surface_hit {  /* 40 bytes; offsets 0/4/8/20/32/36 */
+    float t;              /* ray parameter of the hit (distance from the ray origin: directions are normalised) */
+    float density;        /* sum m W at the hit point */
+    fs_vec3 normal;       /* -gradient / |gradient|, outward */
+    fs_vec3 velocity;     /* Shepard-normalised */
+    uint32_t steps;       /* index k of the first march sample with density >= iso; max_steps on a miss */
+    uint32_t hit;         /* 0 miss, 1 surface bracketed (and refined), 2 the first sample was already inside */
+} fs3_surface_hit;
+fs_status fs3_render_surface(fs_sim3* sim, const fs3_camera* camera, const fs3_surface_params* params, fs3_surface_hit* out_host);
+fs_status fs3_render_surface_device(fs_sim3* sim, const fs3_camera* camera, const fs3_surface_params* params, fs3_surface_hit* out_dev);
+
 /* ------------------------------------------------------- ResizableBuffer */
 /* ResizableBuffer<T>::new (src/buffer.rs:27-43). */
 fs_status fs_buffer_create(int device, size_t elem_size, size_t len, const char* name, fs_buffer** out);
