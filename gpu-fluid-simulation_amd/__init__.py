@@ -23,6 +23,7 @@ from ._abi import (  # noqa: F401
     FS_SORT_COUNTING,
     FS_SLAB_SERIAL,
     FS_SLAB_STRIPS,
+    MESH_VERTEX_DTYPE,
     PARTICLE3_DTYPE,
     PARTICLE_DTYPE,
     PASS_NAMES,
@@ -50,7 +51,7 @@ from ._abi import (  # noqa: F401
 __all__ = [
     "FluidSimulation", "ResizableBuffer", "SimulationSettings", "default_tick_settings", "dam_break_2d",
     "FluidSimError", "load_library", "PARTICLE_DTYPE", "SAMPLE_DTYPE", "SAMPLE3_DTYPE",
-    "SURFACE_HIT_DTYPE", "look_at_camera", "shade_surface",
+    "SURFACE_HIT_DTYPE", "look_at_camera", "shade_surface", "MESH_VERTEX_DTYPE", "write_obj",
 ]
 
 
@@ -537,6 +538,52 @@ class FluidSimulation3D:
         hits = np.zeros((int(camera.height), int(camera.width)), dtype=SURFACE_HIT_DTYPE)
         _check(self._lib, self._lib.fs3_render_surface(self._h, C.byref(camera), C.byref(params), hits.ctypes.data_as(C.c_void_p)))
         return hits
+
+    # -- 3D surface extraction (build extension) --------------
+    def _view3(self, width, height, depth, world_min, world_max):
+        sz = self.settings.size
+        wmin = world_min if world_min is not None else (-sz.x / 2, -sz.y / 2, -sz.z / 2)
+        wmax = world_max if world_max is not None else (sz.x / 2, sz.y / 2, sz.z / 2)
+        return _abi.View3(Vec3(*[float(v) for v in wmin]), Vec3(*[float(v) for v in wmax]), int(width), int(height), int(depth))
+
+    def extract_surface(self, width, height, depth, iso, world_min=None, world_max=None):
+        """The iso-surface of the density as an indexed triangle mesh (surface nets over width x height x depth lattice NODES,
+        the voxel centres of sample_grid on the same box; default: the whole domain): (vertices[V] MESH_VERTEX_DTYPE,
+        triangles[T, 3] uint32), outward winding, open where the surface leaves the box.  Blocking; needs a step since create /
+        the last upload.  Two ABI calls at most: the counts, then the arrays at exact size."""
+        view = self._view3(width, height, depth, world_min, world_max)
+        counts = (C.c_uint32 * 2)()
+        _check(self._lib, self._lib.fs3_extract_surface(self._h, C.byref(view), float(iso), None, 0, None, 0, counts))
+        verts = np.zeros(int(counts[0]), dtype=MESH_VERTEX_DTYPE)
+        tris = np.zeros((int(counts[1]), 3), dtype=np.uint32)
+        if verts.shape[0] or tris.shape[0]:
+            _check(self._lib, self._lib.fs3_extract_surface(
+                self._h, C.byref(view), float(iso), verts.ctypes.data_as(C.c_void_p) if verts.shape[0] else None, verts.shape[0],
+                tris.ctypes.data_as(C.c_void_p) if tris.shape[0] else None, tris.shape[0], counts))
+            assert (int(counts[0]), int(counts[1])) == (verts.shape[0], tris.shape[0])
+        return verts, tris
+
+    def extract_surface_device(self, width, height, depth, iso, verts_ptr, vert_cap, tris_ptr, tri_cap, counts_ptr,
+                               world_min=None, world_max=None):
+        """fs3_extract_surface_device: device pointers (vert_cap 40-byte fs3_mesh_vertex, 3 * tri_cap uint32, 2 uint32 counts),
+        enqueued on the simulation's stream after the steps in flight; no host read.  The counts are always the full ones:
+        compare them with the capacities once the stream has passed the call."""
+        view = self._view3(width, height, depth, world_min, world_max)
+        _check(self._lib, self._lib.fs3_extract_surface_device(
+            self._h, C.byref(view), float(iso), C.c_void_p(int(verts_ptr)) if verts_ptr else None, int(vert_cap),
+            C.c_void_p(int(tris_ptr)) if tris_ptr else None, int(tri_cap), C.c_void_p(int(counts_ptr)) if counts_ptr else None))
+
+
+def write_obj(path, vertices, triangles):
+    """A mesh of extract_surface as a Wavefront OBJ: one `v` and one `vn` line per vertex, one `f a//a b//b c//c` line per
+    triangle, indices 1-based.  Floats are written with nine significant digits (float32 round-trips)."""
+    with open(path, "w") as fh:
+        for p in vertices["position"]:
+            fh.write("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]))
+        for n in vertices["normal"]:
+            fh.write("vn %.9g %.9g %.9g\n" % (n[0], n[1], n[2]))
+        for t in np.asarray(triangles, dtype=np.int64).reshape(-1, 3) + 1:
+            fh.write("f %d//%d %d//%d %d//%d\n" % (t[0], t[0], t[1], t[1], t[2], t[2]))
 
 
 def look_at_camera(eye, target, up, fov_y_or_extent, width, height, orthographic=False):

@@ -158,6 +158,11 @@ class SurfaceHit3(C.Structure):
                 ("hit", C.c_uint32)]
 
 
+class MeshVertex3(C.Structure):
+    """fs3_mesh_vertex (include/fluidsim.h "3D surface extraction"): 40 bytes."""
+    _fields_ = [("position", Vec3), ("normal", Vec3), ("velocity", Vec3), ("density", C.c_float)]
+
+
 class SlabConfig(C.Structure):
     _fields_ = [
         ("own_lo", C.c_uint32), ("own_hi", C.c_uint32),
@@ -193,6 +198,9 @@ assert SAMPLE3_DTYPE.itemsize == 40 and C.sizeof(Sample3) == 40 and C.sizeof(Vie
 SURFACE_HIT_DTYPE = np.dtype([("t", "<f4"), ("density", "<f4"), ("normal", "<f4", (3,)), ("velocity", "<f4", (3,)),
                               ("steps", "<u4"), ("hit", "<u4")])
 assert SURFACE_HIT_DTYPE.itemsize == 40 and C.sizeof(SurfaceHit3) == 40 and C.sizeof(Camera3) == 64 and C.sizeof(SurfaceParams3) == 20
+# fs3_mesh_vertex as a numpy structured dtype (offsets 0/12/24/36).
+MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", (3,)), ("normal", "<f4", (3,)), ("velocity", "<f4", (3,)), ("density", "<f4")])
+assert MESH_VERTEX_DTYPE.itemsize == 40 and C.sizeof(MeshVertex3) == 40
 assert C.sizeof(Uniform) == 120
 assert C.sizeof(Settings) == 28
 assert C.sizeof(TickSettings) == 60
@@ -319,6 +327,8 @@ PROTOTYPES = {
     "fs3_sample_grid": (C.c_int, [_P, C.POINTER(View3), _P]),
     "fs3_render_surface": (C.c_int, [_P, C.POINTER(Camera3), C.POINTER(SurfaceParams3), _P]),
     "fs3_render_surface_device": (C.c_int, [_P, C.POINTER(Camera3), C.POINTER(SurfaceParams3), _P]),
+    "fs3_extract_surface": (C.c_int, [_P, C.POINTER(View3), C.c_float, _P, C.c_uint32, _P, C.c_uint32, _P]),
+    "fs3_extract_surface_device": (C.c_int, [_P, C.POINTER(View3), C.c_float, _P, C.c_uint32, _P, C.c_uint32, _P]),
     "fs_selftest_constdiv": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_uint32)]),
     "fs_sort_plan_read": (C.c_int, [C.c_void_p, C.POINTER(SortPlanInfo)]),
     "fs_selftest_sort_policy": (C.c_int, [C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t,

@@ -56,6 +56,10 @@ struct fs_sim3 {
     bool share_div = false;      // all create-time proofs of the shared-denominator path succeeded
     float mass = 0.0f;           // of the tick of the last step enqueued: what field sampling weighs with
     bool sample_stale = true;    // no step enqueued since create / the last upload: records and cell table do not belong together
+    // scratch of surface extraction, allocated by its first call and grown only by a larger lattice
+    DevArray<float> mesh_field;      // node densities
+    DevArray<uint32_t> mesh_rank;    // per node: the vertex index of its cell
+    DevArray<uint32_t> mesh_sums;    // two words per workgroup of the count pass: sums, then offsets
 
     // the arrays as the launchers see them (fs_3d.h): the force pass writes the new positions into the spare buffer
     fsd::Arrays3 arrays() const {
@@ -401,6 +405,100 @@ fs_status fs3_render_surface_device(fs_sim3* s, const fs3_camera* cam, const fs3
     FS_TRY(surface3_check(s, cam, sp, out_dev));
     FS_HIP(hipSetDevice(s->device));
     return surface3_enqueue(s, cam, sp, out_dev);
+}
+
+// ---- 3D surface extraction ----------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// The checks of both calls, in the order the header lists them.
+fs_status mesh3_check(const fs_sim3* s, const fs3_view* view, float iso, const void* verts, uint32_t vert_cap, const void* tris,
+                      uint32_t tri_cap, const void* counts) {
+    static_assert(sizeof(fs3_mesh_vertex) == 40, "fs3_mesh_vertex is 40 bytes");
+    if (!s || !view || !counts) return fail(FS_ERR_INVALID, "null argument");
+    if (view->width < 2u || view->height < 2u || view->depth < 2u) return fail(FS_ERR_INVALID, "bad lattice size: an extent < 2");
+    const uint64_t wh = (uint64_t)view->width * view->height;
+    if (wh > (1ull << 26) || wh * view->depth > (1ull << 26)) return fail(FS_ERR_INVALID, "bad lattice size: more than 2^26 nodes");
+    if (!std::isfinite(iso) || !(iso > 0.0f)) return fail(FS_ERR_INVALID, "extraction: iso must be finite and > 0");
+    if ((!verts && vert_cap) || (!tris && tri_cap)) return fail(FS_ERR_INVALID, "extraction: null array with a non-zero capacity");
+    if (s->sample_stale) return fail(FS_ERR_INVALID, "extraction needs a step since create and since the last upload of particles");
+    return FS_OK;
+}
+
+// The query of a checked call on the handle's scratch, which grows here and nowhere else.  hipFree of the arrays it replaces
+// waits for the work that still reads them.
+fs_status mesh3_query(fs_sim3* s, const fs3_view* view, float iso, fsd::Mesh3Query* Q) {
+    const size_t nodes = (size_t)view->width * view->height * view->depth;
+    if (nodes > s->mesh_field.n) {
+        const hipError_t e1 = s->mesh_field.alloc(nodes), e2 = s->mesh_rank.alloc(nodes);
+        const hipError_t e3 = s->mesh_sums.alloc(2 * (size_t)fsd::mesh3_workgroups((uint32_t)nodes));
+        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
+            (void)hipGetLastError();
+            s->mesh_field.release(); s->mesh_rank.release(); s->mesh_sums.release();
+            return fail(FS_ERR_OOM, "extraction: device scratch");
+        }
+    }
+    Q->wmin = make_float3(view->world_min.x, view->world_min.y, view->world_min.z);
+    Q->wmax = make_float3(view->world_max.x, view->world_max.y, view->world_max.z);
+    Q->width = view->width; Q->height = view->height; Q->depth = view->depth;
+    Q->iso = iso;
+    Q->field = s->mesh_field.p; Q->rank = s->mesh_rank.p; Q->sums = s->mesh_sums.p;
+    return FS_OK;
+}
+
+// Vertices (which also leaves every active cell's rank for the faces), then faces: whatever part has room.
+fs_status mesh3_emit(fs_sim3* s, const fsd::Mesh3Query& Q) {
+    if (Q.vert_cap == 0u && Q.tri_cap == 0u) return FS_OK;
+    fsd::launch3_mesh_verts(s->stream, params3_common(*s, s->mass), s->arrays(), Q);
+    if (Q.tri_cap != 0u) fsd::launch3_mesh_faces(s->stream, Q);
+    FS_HIP(hipGetLastError());
+    return FS_OK;
+}
+}  // namespace
+extern "C" {
+
+fs_status fs3_extract_surface_device(fs_sim3* s, const fs3_view* view, float iso, fs3_mesh_vertex* verts_dev, uint32_t vert_cap,
+                                     uint32_t* tris_dev, uint32_t tri_cap, uint32_t* counts_dev) {
+    FS_TRY(mesh3_check(s, view, iso, verts_dev, vert_cap, tris_dev, tri_cap, counts_dev));
+    FS_HIP(hipSetDevice(s->device));
+    fsd::Mesh3Query Q;
+    FS_TRY(mesh3_query(s, view, iso, &Q));
+    Q.counts = counts_dev; Q.verts = verts_dev; Q.vert_cap = vert_cap; Q.tris = tris_dev; Q.tri_cap = tri_cap;
+    fsd::launch3_mesh_count(s->stream, params3_common(*s, s->mass), s->arrays(), Q);
+    return mesh3_emit(s, Q);
+}
+
+// Blocking: the counts first (field, count and scan passes), then what fits of either array through the staging helper.
+fs_status fs3_extract_surface(fs_sim3* s, const fs3_view* view, float iso, fs3_mesh_vertex* verts, uint32_t vert_cap, uint32_t* tris,
+                              uint32_t tri_cap, uint32_t counts[2]) {
+    FS_TRY(mesh3_check(s, view, iso, verts, vert_cap, tris, tri_cap, counts));
+    FS_HIP(hipSetDevice(s->device));
+    fsd::Mesh3Query Q;
+    FS_TRY(mesh3_query(s, view, iso, &Q));
+    uint32_t vt[2] = {0u, 0u};
+    FS_TRY(fsd::staged_query(s->stream, (const fs_vec3*)nullptr, 2, vt, nullptr, 0, [&](const fs_vec3*, uint32_t* dcounts, float*) {
+        Q.counts = dcounts;
+        fsd::launch3_mesh_count(s->stream, params3_common(*s, s->mass), s->arrays(), Q);
+        FS_HIP(hipGetLastError());
+        return FS_OK;
+    }));
+    const uint32_t nv = vt[0] < vert_cap ? vt[0] : vert_cap, nt = vt[1] < tri_cap ? vt[1] : tri_cap;
+    Q.vert_cap = nv; Q.tri_cap = 0u;
+    if (nv) {
+        FS_TRY(fsd::staged_query(s->stream, (const fs_vec3*)nullptr, nv, verts, nullptr, 0, [&](const fs_vec3*, fs3_mesh_vertex* dverts, float*) {
+            Q.verts = dverts;
+            return mesh3_emit(s, Q);
+        }));
+    }
+    if (nt) {
+        Q.verts = nullptr; Q.vert_cap = 0u; Q.tri_cap = nt;
+        FS_TRY(fsd::staged_query(s->stream, (const fs_vec3*)nullptr, 3 * (size_t)nt, tris, nullptr, 0, [&](const fs_vec3*, uint32_t* dtris, float*) {
+            Q.tris = dtris;
+            if (nv) { fsd::launch3_mesh_faces(s->stream, Q); FS_HIP(hipGetLastError()); return FS_OK; }   // the ranks are there
+            return mesh3_emit(s, Q);
+        }));
+    }
+    counts[0] = vt[0]; counts[1] = vt[1];
+    return sort_health3(s);
 }
 
 }  // extern "C"

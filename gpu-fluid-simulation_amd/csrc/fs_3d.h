@@ -92,4 +92,25 @@ struct Surface3Query {
 };
 void launch3_render_surface(hipStream_t st, const Params3& P, const Arrays3& A, const Surface3Query& Q);
 
+// 3D surface extraction (kernels_mesh3d.hip): surface nets over the node lattice of a view, against the same state
+// and the same P as a Sample3Query.  Device pointers; host side only.  The scratch belongs to the handle: `field` and `rank` hold
+// width * height * depth entries, `sums` two words per workgroup (mesh3_workgroups).
+struct Mesh3Query {
+    float3 wmin{}, wmax{};
+    uint32_t width = 0, height = 0, depth = 0;   // nodes per axis, each >= 2, product <= 2^26
+    float iso = 0.0f;
+    float* field = nullptr;            // node densities
+    uint32_t* rank = nullptr;          // vertex index of the cell whose low corner the node is (active cells only)
+    uint32_t* sums = nullptr;          // per workgroup {vertices, quads}: counts, then exclusive offsets
+    uint32_t* counts = nullptr;        // {V, T}
+    void* verts = nullptr;             // vert_cap fs3_mesh_vertex records (may be null when vert_cap == 0)
+    uint32_t vert_cap = 0;
+    uint32_t* tris = nullptr;          // 3 * tri_cap indices (may be null when tri_cap == 0)
+    uint32_t tri_cap = 0;
+};
+uint32_t mesh3_workgroups(uint32_t nodes);
+void launch3_mesh_count(hipStream_t st, const Params3& P, const Arrays3& A, const Mesh3Query& Q);   // field, flags, offsets -> counts
+void launch3_mesh_verts(hipStream_t st, const Params3& P, const Arrays3& A, const Mesh3Query& Q);   // after _count: rank, verts[0, vert_cap)
+void launch3_mesh_faces(hipStream_t st, const Mesh3Query& Q);                                       // after _verts: tris[0, tri_cap)
+
 }  // namespace fsd

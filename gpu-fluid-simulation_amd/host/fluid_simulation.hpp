@@ -153,6 +153,12 @@ using Camera3 = fs3_camera;               // build extension: 3D surface renderi
 using SurfaceParams3 = fs3_surface_params;
 using SurfaceHit3 = fs3_surface_hit;
 static_assert(sizeof(Camera3) == 64 && sizeof(SurfaceParams3) == 20 && sizeof(SurfaceHit3) == 40, "3D surface rendering records");
+using MeshVertex3 = fs3_mesh_vertex;      // build extension: 3D surface extraction
+static_assert(sizeof(MeshVertex3) == 40, "fs3_mesh_vertex is 40 bytes");
+struct Mesh3 {
+    std::vector<MeshVertex3> vertices;
+    std::vector<uint32_t> triangles;      // three indices per triangle, outward winding
+};
 class FluidSimulation3D {
 public:
     static FluidSimulation3D new_(int device, const fs3_settings& settings, fs_vec3 initial_offset = fs_vec3{0.0f, 0.0f, 0.0f},
@@ -204,6 +210,25 @@ public:
     // ... into a device buffer, enqueued on the simulation's stream after the ticks in flight; non-blocking
     void render_surface_device(const Camera3& camera, const SurfaceParams3& params, SurfaceHit3* out_dev) {
         check(fs3_render_surface_device(h_, &camera, &params, out_dev));
+    }
+    // 3D surface extraction: surface nets over the width x height x depth lattice nodes of `view` (each >= 2), at exact size in
+    // two calls: the counts, then the arrays.  Blocking; needs a tick since creation / the last upload.
+    Mesh3 extract_surface(const fs3_view& view, float iso) {
+        uint32_t counts[2] = {0, 0};
+        check(fs3_extract_surface(h_, &view, iso, nullptr, 0, nullptr, 0, counts));
+        Mesh3 m;
+        m.vertices.resize(counts[0]);
+        m.triangles.resize(3 * (size_t)counts[1]);
+        if (counts[0] || counts[1])
+            check(fs3_extract_surface(h_, &view, iso, counts[0] ? m.vertices.data() : nullptr, counts[0],
+                                      counts[1] ? m.triangles.data() : nullptr, counts[1], counts));
+        return m;
+    }
+    // ... into device buffers (vert_cap records, 3 * tri_cap indices, two counts), enqueued on the simulation's stream after the
+    // ticks in flight; no host read.  The counts are always the full ones.
+    void extract_surface_device(const fs3_view& view, float iso, MeshVertex3* verts_dev, uint32_t vert_cap, uint32_t* tris_dev,
+                                uint32_t tri_cap, uint32_t* counts_dev) {
+        check(fs3_extract_surface_device(h_, &view, iso, verts_dev, vert_cap, tris_dev, tri_cap, counts_dev));
     }
     fs_sim3* handle() { return h_; }
 

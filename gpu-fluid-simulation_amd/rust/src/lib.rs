@@ -119,6 +119,10 @@ pub struct SurfaceParams3 { pub iso: f32, pub t_near: f32, pub ds: f32, pub max_
 #[repr(C)] #[derive(Clone, Copy, Default, Debug, PartialEq)]
 pub struct SurfaceHit3 { pub t: f32, pub density: f32, pub normal: Vec3, pub velocity: Vec3, pub steps: u32, pub hit: u32 }
 const _: () = assert!(std::mem::size_of::<Camera3>() == 64 && std::mem::size_of::<SurfaceParams3>() == 20 && std::mem::size_of::<SurfaceHit3>() == 40);
+/// fs3_mesh_vertex: one vertex of an extracted iso-surface (build extension, include/fluidsim.h "3D surface extraction"); 40 bytes, offsets 0/12/24/36.
+#[repr(C)] #[derive(Clone, Copy, Default, Debug, PartialEq)]
+pub struct MeshVertex3 { pub position: Vec3, pub normal: Vec3, pub velocity: Vec3, pub density: f32 }
+const _: () = assert!(std::mem::size_of::<MeshVertex3>() == 40);
 
 #[repr(C)] pub struct fs_sim { _p: [u8; 0] }
 #[repr(C)] pub struct fs_sim3 { _p: [u8; 0] }
@@ -234,6 +238,8 @@ extern "C" {
     fn fs3_sample_grid(sim: *mut fs_sim3, view: *const View3, out: *mut Sample3) -> c_int;
     fn fs3_render_surface(sim: *mut fs_sim3, camera: *const Camera3, params: *const SurfaceParams3, out_host: *mut SurfaceHit3) -> c_int;
     fn fs3_render_surface_device(sim: *mut fs_sim3, camera: *const Camera3, params: *const SurfaceParams3, out_dev: *mut SurfaceHit3) -> c_int;
+    fn fs3_extract_surface(sim: *mut fs_sim3, view: *const View3, iso: f32, verts: *mut MeshVertex3, vert_cap: u32, tris: *mut u32, tri_cap: u32, counts: *mut u32) -> c_int;
+    fn fs3_extract_surface_device(sim: *mut fs_sim3, view: *const View3, iso: f32, verts_dev: *mut MeshVertex3, vert_cap: u32, tris_dev: *mut u32, tri_cap: u32, counts_dev: *mut u32) -> c_int;
     // ResizableBuffer<T> (src/buffer.rs)
     fn fs_buffer_create(device: c_int, elem_size: usize, len: usize, name: *const c_char, out: *mut *mut fs_buffer) -> c_int;
     fn fs_buffer_resize(buf: *mut fs_buffer, new_cap: usize, resized: *mut c_int) -> c_int;
@@ -611,6 +617,26 @@ impl FluidSimulation3D {
     /// ... into a device buffer of `width * height` records; enqueued on the simulation's stream, non-blocking.
     pub unsafe fn render_surface_device(&mut self, camera: &Camera3, params: &SurfaceParams3, out_dev: *mut SurfaceHit3) {
         check(fs3_render_surface_device(self.raw, camera, params, out_dev));
+    }
+    /// Build extension: 3D surface extraction (include/fluidsim.h).  Surface nets over the `width` x `height` x `depth` lattice
+    /// nodes of `view` (each >= 2): the vertices and the triangles (three indices each, outward winding) at exact size, in two
+    /// calls: the counts, then the arrays.  Blocking; needs a tick since `new` / the last upload.
+    pub fn extract_surface(&mut self, view: &View3, iso: f32) -> (Vec<MeshVertex3>, Vec<[u32; 3]>) {
+        let mut counts = [0u32; 2];
+        check(unsafe { fs3_extract_surface(self.raw, view, iso, std::ptr::null_mut(), 0, std::ptr::null_mut(), 0, counts.as_mut_ptr()) });
+        let mut verts = vec![MeshVertex3::default(); counts[0] as usize];
+        let mut tris = vec![[0u32; 3]; counts[1] as usize];
+        if counts[0] != 0 || counts[1] != 0 {
+            let vp = if verts.is_empty() { std::ptr::null_mut() } else { verts.as_mut_ptr() };
+            let tp = if tris.is_empty() { std::ptr::null_mut() } else { tris.as_mut_ptr() as *mut u32 };
+            check(unsafe { fs3_extract_surface(self.raw, view, iso, vp, counts[0], tp, counts[1], counts.as_mut_ptr()) });
+        }
+        (verts, tris)
+    }
+    /// ... into device buffers (`vert_cap` records, `3 * tri_cap` indices, two counts); enqueued on the simulation's stream, no
+    /// host read.  The counts are always the full ones: compare them with the capacities once the stream has passed the call.
+    pub unsafe fn extract_surface_device(&mut self, view: &View3, iso: f32, verts_dev: *mut MeshVertex3, vert_cap: u32, tris_dev: *mut u32, tri_cap: u32, counts_dev: *mut u32) {
+        check(fs3_extract_surface_device(self.raw, view, iso, verts_dev, vert_cap, tris_dev, tri_cap, counts_dev));
     }
     pub fn stream(&self) -> *mut c_void { unsafe { fs3_stream(self.raw) } }
 }

@@ -665,6 +665,66 @@ typedef struct fs3_surface_hit {  /* 40 bytes; offsets 0/4/8/20/32/36 */
 fs_status fs3_render_surface(fs_sim3* sim, const fs3_camera* camera, const fs3_surface_params* params, fs3_surface_hit* out_host);
 fs_status fs3_render_surface_device(fs_sim3* sim, const fs3_camera* camera, const fs3_surface_params* params, fs3_surface_hit* out_dev);
 
+/* ------------------------------------------------ 3D surface extraction (build extension, opt-in by being called) */
+/* The iso-surface of the density as an indexed triangle mesh, by surface nets (the dual method): one vertex per lattice cell the
+ * surface crosses, one quad per interior lattice edge it crosses.  No case tables; the output is fully determined by the statement
+ * below.  All arithmetic is f32 without contraction, `/` and `sqrt` are correctly rounded.  `density(x)` and `sample(x)` are those
+ * of "3D field sampling", and the state is that statement's: the records, the grid, the settings and the mass of the last step.
+ *
+ * Lattice.  An fs3_view with width, height, depth >= 2 gives W x H x D NODES.  Node (i, j, k) is fs3_sample_grid's voxel centre:
+ *     N_a(i) = world_min.a + (((float)i + 0.5f) / (float)W) * (world_max.a - world_min.a)     per axis a with its own extent
+ *     F(i,j,k) = density(node), byte-equal to fs3_sample_grid(view).density;   inside(i,j,k) = F >= iso
+ * Cells.  The lattice has (W-1)(H-1)(D-1) cells; cell (i, j, k) has the corner nodes (i+a, j+b, k+c), a, b, c in {0, 1}.  A cell
+ * is ACTIVE when its eight corners are neither all inside nor all outside.
+ * Vertex of an active cell.  Its twelve edges are visited in this order: the four x-edges at (y0, z0) = (0,0), (1,0), (0,1), (1,1);
+ * the four y-edges at (x0, z0) in the same order; the four z-edges at (x0, y0) in the same order.  An edge runs from its low
+ * corner a to its high corner b along its axis.  With sx = sy = sz = +0 and c = 0, an edge with inside(a) != inside(b) adds:
+ *     tt = (iso - Fa) / (Fb - Fa);   c += 1
+ *     x-edge: sx += tt; sy += (float)y0; sz += (float)z0          (y-edge: sy += tt; sx += (float)x0; sz += (float)z0;  z likewise)
+ * Then, per axis a with the cell's index i_a:
+ *     l.a = s_a / (float)c;   position.a = N_a(i_a) + l.a * (N_a(i_a + 1) - N_a(i_a))
+ *     S = sample(position);   density = S.density;   normal and velocity from S exactly as in fs3_surface_hit:
+ *     normal.a = gl > 0 ? (-S.gradient.a) / gl : +0 with gl = sqrt((gx*gx + gy*gy) + gz*gz);  velocity.a = S.weight > 0 ? S.velocity.a / S.weight : +0
+ * Vertex order is ascending cell index (k*(H-1) + j)*(W-1) + i; a vertex's index is its rank among the active cells.
+ * Faces.  Take the lattice edge from node n = (i, j, k) along axis A in {x, y, z}; (u, v) are the next two axes cyclically:
+ * x -> (y, z), y -> (z, x), z -> (x, y).  The edge is INTERIOR when its u- and v-coordinates are both >= 1 and at most the last
+ * node index minus 1 (the four cells around it then exist).  An interior edge whose two end nodes differ in `inside` emits one
+ * quad of those four cells' vertices, the cells at the edge's low A-coordinate and at (u, v) offsets
+ *     A = (u-1, v-1), B = (u, v-1), C = (u, v), D = (u-1, v)
+ * in the order (A, B, C, D) when the low node is inside — counter-clockwise seen from +A, outward — and (A, D, C, B) otherwise.
+ * Quad q becomes the triangles 2q = (v0, v1, v2) and 2q+1 = (v0, v2, v3).  Quad order is ascending 3 * ((k*H + j)*W + i) + A.
+ * Edges on the lattice's boundary emit nothing: a surface that leaves the view is left open there.  Orientation is defined in
+ * index space: a view flipped in an odd number of axes mirrors the winding, which is the caller's business.
+ *
+ * counts[0] = V and counts[1] = T are always the full counts.  Vertices [0, min(V, vert_cap)) and triangles [0, min(T, tri_cap))
+ * are written (3 indices per triangle); a written triangle may name an unwritten vertex; nothing past those ranges is touched.
+ * `verts` may be NULL only when vert_cap == 0, `tris` only when tri_cap == 0; both capacities 0 is a count query.  FS_OK whether or
+ * not the capacities sufficed: the caller compares the counts with its capacities.
+ *
+ * Checks, in this order:
+ *  1. NULL handle, view or counts -> FS_ERR_INVALID.
+ *  2. An extent < 2, or width * height * depth > 2^26 -> FS_ERR_INVALID.
+ *  3. iso not finite or not > 0 -> FS_ERR_INVALID.
+ *  4. A NULL array with a non-zero capacity -> FS_ERR_INVALID.
+ *  5. No step since create or since the last fs3_upload_particles with n > 0 (the rule of "3D field sampling") -> FS_ERR_INVALID.
+ *
+ * fs3_extract_surface: host pointers, blocking.  fs3_extract_surface_device: device pointers on the handle's device (counts_dev
+ * included); enqueued on fs3_stream(sim) after the steps in flight; stream-ordered, no host read.  The scratch (node field,
+ * per-node ranks, workgroup sums) belongs to the handle and grows — allocates — only when a lattice has more nodes than any
+ * earlier one on that handle; otherwise the call only enqueues.  Non-finite view coordinates give unspecified records and no
+ * out-of-bounds access.  Which node densities the kernels actually evaluate is their own business, as in the ray-marcher; the
+ * records must not change.  If the call is not used, there is no launch and no allocation.  See DESIGN.md §17. */
+typedef struct fs3_mesh_vertex {   /* 40 bytes; offsets 0/12/24/36 */
+    fs_vec3 position;             /* in the active cell's box */
+    fs_vec3 normal;               /* -gradient / |gradient|, outward */
+    fs_vec3 velocity;             /* Shepard-normalised */
+    float density;                /* sum m W at `position` */
+} fs3_mesh_vertex;
+fs_status fs3_extract_surface(fs_sim3* sim, const fs3_view* view, float iso, fs3_mesh_vertex* verts, uint32_t vert_cap,
+                              uint32_t* tris /* 3 per triangle */, uint32_t tri_cap, uint32_t counts[2] /* V, T */);
+fs_status fs3_extract_surface_device(fs_sim3* sim, const fs3_view* view, float iso, fs3_mesh_vertex* verts_dev, uint32_t vert_cap,
+                                     uint32_t* tris_dev, uint32_t tri_cap, uint32_t* counts_dev /* [2] */);
+
 /* ------------------------------------------------------- ResizableBuffer */
 /* ResizableBuffer<T>::new (src/buffer.rs:27-43). */
 fs_status fs_buffer_create(int device, size_t elem_size, size_t len, const char* name, fs_buffer** out);
