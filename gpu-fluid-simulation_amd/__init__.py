@@ -51,7 +51,7 @@ from ._abi import (  # noqa: F401
 __all__ = [
     "FluidSimulation", "ResizableBuffer", "SimulationSettings", "default_tick_settings", "dam_break_2d",
     "FluidSimError", "load_library", "PARTICLE_DTYPE", "SAMPLE_DTYPE", "SAMPLE3_DTYPE",
-    "SURFACE_HIT_DTYPE", "look_at_camera", "shade_surface", "MESH_VERTEX_DTYPE", "write_obj",
+    "SURFACE_HIT_DTYPE", "look_at_camera", "shade_surface", "MESH_VERTEX_DTYPE", "write_obj", "box_mask3d",
 ]
 
 
@@ -572,6 +572,58 @@ class FluidSimulation3D:
         _check(self._lib, self._lib.fs3_extract_surface_device(
             self._h, C.byref(view), float(iso), C.c_void_p(int(verts_ptr)) if verts_ptr else None, int(vert_cap),
             C.c_void_p(int(tris_ptr)) if tris_ptr else None, int(tri_cap), C.c_void_p(int(counts_ptr)) if counts_ptr else None))
+
+    # -- 3D colliders (build extension) -----------------------
+    def set_collider(self, field):
+        """Static obstacles: a float32 [D, H, W, 3] voxel field of push vectors in world units over the whole domain, zero = free
+        space (include/fluidsim.h "3D colliders").  Blocking; holds for the steps enqueued afterwards; replaces an earlier one."""
+        f = np.ascontiguousarray(field, dtype=np.float32)
+        if f.ndim != 4 or f.shape[3] != 3:
+            raise ValueError("set_collider expects a [D, H, W, 3] float32 array")
+        d, h, w = f.shape[:3]
+        _check(self._lib, self._lib.fs3_collider_upload(self._h, f.ctypes.data_as(C.c_void_p), int(w), int(h), int(d)))
+
+    def set_collider_mask(self, mask, want_field=False):
+        """The collider of a uint8 [D, H, W] voxel mask (> 128: solid): every solid voxel pushes to its nearest free voxel (exact
+        distance transform in index space, made on the GPU).  want_field=True returns the [D, H, W, 3] field."""
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        if m.ndim != 3:
+            raise ValueError("set_collider_mask expects a [D, H, W] uint8 array")
+        d, h, w = m.shape
+        out = np.zeros((d, h, w, 3), dtype=np.float32) if want_field else None
+        _check(self._lib, self._lib.fs3_collider_from_mask(self._h, m.ctypes.data_as(C.c_void_p), int(w), int(h), int(d),
+                                                          out.ctypes.data_as(C.c_void_p) if want_field else None))
+        return out
+
+    def clear_collider(self):
+        _check(self._lib, self._lib.fs3_collider_clear(self._h))
+
+    @property
+    def collider_dims(self):
+        """(W, H, D) of the collider, (0, 0, 0) when none is set."""
+        w, h, d = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(self._lib, self._lib.fs3_collider_dims(self._h, C.byref(w), C.byref(h), C.byref(d)))
+        return int(w.value), int(h.value), int(d.value)
+
+    def collider(self):
+        """The collider in use as a float32 [D, H, W, 3] array, or None when none is set."""
+        w, h, d = self.collider_dims
+        if w == 0:
+            return None
+        out = np.zeros((d, h, w, 3), dtype=np.float32)
+        _check(self._lib, self._lib.fs3_collider_download(self._h, out.ctypes.data_as(C.c_void_p), w * h * d))
+        return out
+
+
+def box_mask3d(size, shape, world_min, world_max):
+    """A box given in world coordinates rasterised to a collider mask for FluidSimulation3D.set_collider_mask: uint8 [D, H, W] for
+    shape = (W, H, D) over the domain [-size/2, size/2], 255 where the voxel's centre lies inside the box, else 0."""
+    axes = []
+    for a, n in enumerate(shape):
+        c = (np.arange(int(n)) + 0.5) / int(n) * float(size[a]) - float(size[a]) / 2
+        axes.append((c >= float(world_min[a])) & (c <= float(world_max[a])))
+    inside = axes[2][:, None, None] & axes[1][None, :, None] & axes[0][None, None, :]
+    return np.where(inside, 255, 0).astype(np.uint8)
 
 
 def write_obj(path, vertices, triangles):

@@ -329,6 +329,11 @@ PROTOTYPES = {
     "fs3_render_surface_device": (C.c_int, [_P, C.POINTER(Camera3), C.POINTER(SurfaceParams3), _P]),
     "fs3_extract_surface": (C.c_int, [_P, C.POINTER(View3), C.c_float, _P, C.c_uint32, _P, C.c_uint32, _P]),
     "fs3_extract_surface_device": (C.c_int, [_P, C.POINTER(View3), C.c_float, _P, C.c_uint32, _P, C.c_uint32, _P]),
+    "fs3_collider_upload": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "fs3_collider_from_mask": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P]),
+    "fs3_collider_clear": (C.c_int, [_P]),
+    "fs3_collider_dims": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "fs3_collider_download": (C.c_int, [_P, _P, C.c_size_t]),
     "fs_selftest_constdiv": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_uint32)]),
     "fs_sort_plan_read": (C.c_int, [C.c_void_p, C.POINTER(SortPlanInfo)]),
     "fs_selftest_sort_policy": (C.c_int, [C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t,

@@ -60,6 +60,10 @@ struct fs_sim3 {
     DevArray<float> mesh_field;      // node densities
     DevArray<uint32_t> mesh_rank;    // per node: the vertex index of its cell
     DevArray<uint32_t> mesh_sums;    // two words per workgroup of the count pass: sums, then offsets
+    // the opt-in static collider: one float4 push vector per voxel; cw == 0: none, and never set: no allocation.
+    // coll.n is the capacity (it only grows), cw * ch * cd the field in use
+    DevArray<float4> coll;
+    uint32_t cw = 0, ch = 0, cd = 0;
 
     // the arrays as the launchers see them (fs_3d.h): the force pass writes the new positions into the spare buffer
     fsd::Arrays3 arrays() const {
@@ -145,7 +149,10 @@ static fs_status enqueue3(fs_sim3* s, const fs3_tick_settings* t) {
     // the step's completion event (sort_policy.h: the host stays at most four steps ahead) rides on the force kernel as its
     // completion signal — no marker packet behind it (engine.hip enqueue_step does the same); a profiled step records markers anyway
     hipEvent_t done = ev ? nullptr : s->sortp.flight_event();
-    launch3_force(st, P, A, tol, done);
+    // the collider, if one is set, by value: this step keeps the field it was enqueued with (fs3_collider_* order their writes
+    // on the stream behind it)
+    const Collide3 K{s->coll.p, s->cw, s->ch, s->cd, s->st.size.x, s->st.size.y, s->st.size.z};
+    launch3_force(st, P, A, tol, done, s->cw ? &K : nullptr);
     std::swap(s->pos, s->pos_s);
     s->mass = t->mass; s->sample_stale = false;
     if (ev) { FS_HIP(hipEventRecord(ev[5], st)); FS_HIP(hipEventRecord(ev[6], st)); /* FS_PASS_BOUNDARY: slab handles only */ s->prof.pending += 1; }
@@ -280,6 +287,117 @@ fs_status fs3_profile_enable(fs_sim3* s, int enable) { if (!s) return fail(FS_ER
 fs_status fs3_profile_read(fs_sim3* s, double ms[FS_PASS_COUNT], uint64_t* steps, int reset) {
     if (!s || !ms) return fail(FS_ERR_INVALID, "null argument");
     return s->prof.read(ms, steps, reset);
+}
+
+// ---- 3D colliders -------------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+const uint32_t COLLIDER_MAX_EXTENT = 1024u;
+
+// The checks the two setters share, in the order the header lists them (the handle first, by the caller).
+fs_status collider3_check(const void* array, uint32_t w, uint32_t h, uint32_t d) {
+    if (!array) return fail(FS_ERR_INVALID, "null argument");
+    if (w == 0u || h == 0u || d == 0u || w > COLLIDER_MAX_EXTENT || h > COLLIDER_MAX_EXTENT || d > COLLIDER_MAX_EXTENT)
+        return fail(FS_ERR_INVALID, "collider: an extent of 0 or above 1024");
+    return FS_OK;
+}
+
+// Room for `voxels` vectors.  Allocates only when the field grew, and then only after the steps in flight — which read the old
+// array — are done.  On failure the handle has no collider.
+fs_status collider3_reserve(fs_sim3* s, size_t voxels) {
+    if (voxels <= s->coll.n) return FS_OK;
+    FS_HIP(hipStreamSynchronize(s->stream));
+    s->cw = s->ch = s->cd = 0;
+    if (s->coll.alloc(voxels) != hipSuccess) {
+        (void)hipGetLastError();
+        s->coll.release();
+        return fail(FS_ERR_OOM, "collider: device field");
+    }
+    return FS_OK;
+}
+
+// The field in use as w * h * d fs_vec3 on the host.  Blocking.
+fs_status collider3_read(fs_sim3* s, fs_vec3* dst) {
+    const size_t voxels = (size_t)s->cw * s->ch * s->cd;
+    std::unique_ptr<float4[]> host(new (std::nothrow) float4[voxels]);
+    if (!host) return fail(FS_ERR_OOM, "host allocation failed");
+    FS_HIP(hipMemcpyAsync(host.get(), s->coll.p, voxels * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
+    FS_HIP(hipStreamSynchronize(s->stream));
+    for (size_t k = 0; k < voxels; ++k) dst[k] = fs_vec3{host[k].x, host[k].y, host[k].z};
+    return FS_OK;
+}
+}  // namespace
+extern "C" {
+
+fs_status fs3_collider_upload(fs_sim3* s, const fs_vec3* field, uint32_t w, uint32_t h, uint32_t d) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    FS_TRY(collider3_check(field, w, h, d));
+    const size_t voxels = (size_t)w * h * d;
+    std::unique_ptr<float4[]> host(new (std::nothrow) float4[voxels]);
+    if (!host) return fail(FS_ERR_OOM, "host allocation failed");
+    for (size_t k = 0; k < voxels; ++k) {
+        const fs_vec3 f = field[k];
+        if (!std::isfinite(f.x) || !std::isfinite(f.y) || !std::isfinite(f.z)) return fail(FS_ERR_INVALID, "collider: non-finite component");
+        host[k] = make_float4(f.x, f.y, f.z, 0.0f);
+    }
+    FS_HIP(hipSetDevice(s->device));
+    FS_TRY(collider3_reserve(s, voxels));
+    // on the stream: after the steps in flight, before the steps to come
+    FS_HIP(hipMemcpyAsync(s->coll.p, host.get(), voxels * sizeof(float4), hipMemcpyHostToDevice, s->stream));
+    FS_HIP(hipStreamSynchronize(s->stream));
+    s->cw = w; s->ch = h; s->cd = d;
+    return FS_OK;
+}
+
+fs_status fs3_collider_from_mask(fs_sim3* s, const uint8_t* mask, uint32_t w, uint32_t h, uint32_t d, fs_vec3* field_host) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    FS_TRY(collider3_check(mask, w, h, d));
+    const size_t voxels = (size_t)w * h * d;
+    bool any_free = false;
+    for (size_t k = 0; k < voxels && !any_free; ++k) any_free = !(mask[k] > 128);
+    if (!any_free) return fail(FS_ERR_INVALID, "collider: the mask has no free voxel");
+    FS_HIP(hipSetDevice(s->device));
+    DevArray<uint8_t> dmask;
+    DevArray<uint32_t> near_x, near_xy;
+    if (dmask.alloc(voxels) != hipSuccess || near_x.alloc(voxels) != hipSuccess || near_xy.alloc(voxels) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FS_ERR_OOM, "collider: device staging");
+    }
+    FS_TRY(collider3_reserve(s, voxels));
+    fsd::ColliderMask3 Q;
+    Q.mask = dmask.p; Q.w = w; Q.h = h; Q.d = d;
+    Q.vx = s->st.size.x / (float)w; Q.vy = s->st.size.y / (float)h; Q.vz = s->st.size.z / (float)d;
+    Q.near_x = near_x.p; Q.near_xy = near_xy.p; Q.field = s->coll.p;
+    hipError_t e = hipMemcpyAsync(dmask.p, mask, voxels, hipMemcpyHostToDevice, s->stream);
+    if (e == hipSuccess) { fsd::launch3_collider_from_mask(s->stream, Q); e = hipGetLastError(); }
+    const hipError_t es = hipStreamSynchronize(s->stream);      // before the staging is freed, whatever happened
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) { s->cw = s->ch = s->cd = 0; return fail(FS_ERR_DEVICE, hipGetErrorString(e)); }
+    s->cw = w; s->ch = h; s->cd = d;
+    return field_host ? collider3_read(s, field_host) : FS_OK;
+}
+
+fs_status fs3_collider_clear(fs_sim3* s) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    FS_HIP(hipSetDevice(s->device));
+    FS_HIP(hipStreamSynchronize(s->stream));       // the steps in flight read the field
+    s->cw = s->ch = s->cd = 0;
+    s->coll.release();
+    return FS_OK;
+}
+
+fs_status fs3_collider_dims(const fs_sim3* s, uint32_t* w, uint32_t* h, uint32_t* d) {
+    if (!s || !w || !h || !d) return fail(FS_ERR_INVALID, "null argument");
+    *w = s->cw; *h = s->ch; *d = s->cd;
+    return FS_OK;
+}
+
+fs_status fs3_collider_download(fs_sim3* s, fs_vec3* dst, size_t n) {
+    if (!s || !dst) return fail(FS_ERR_INVALID, "null argument");
+    if (s->cw == 0u) return fail(FS_ERR_INVALID, "collider: none is set");
+    if (n != (size_t)s->cw * s->ch * s->cd) return fail(FS_ERR_INVALID, "collider: n must be w * h * d");
+    FS_HIP(hipSetDevice(s->device));
+    return collider3_read(s, dst);
 }
 
 // ---- 3D field sampling --------------------------------------------------------------------------------

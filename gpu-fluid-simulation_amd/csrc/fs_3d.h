@@ -64,8 +64,17 @@ uint32_t blocks3(uint32_t n);          // workgroups of the density / force kern
 void launch3_predict_key(hipStream_t st, const Params3& P, const Arrays3& A);   // FS3_SEPARATE_KEYGEN: else fused into the sort
 void launch3_reorder(hipStream_t st, const Params3& P, const Arrays3& A);       // + launch_fill_gaps
 void launch3_density(hipStream_t st, const Params3& P, const Arrays3& A, bool tol);
-// done (may be null): signalled by the kernel's completion
-void launch3_force(hipStream_t st, const Params3& P, const Arrays3& A, bool tol, hipEvent_t done);
+// The opt-in static collider of a handle (include/fluidsim.h "3D colliders") as the force pass's COLLIDE
+// instantiations take it, by value and apart from Params3: one float4 push vector per voxel {x, y, z, 0}, voxel (i, j, k) at
+// field[(k * h + j) * w + i], over the whole domain.  size: the settings' box, the divisor of the lookup.
+struct Collide3 {
+    const float4* field;
+    uint32_t w, h, d;
+    float sx, sy, sz;
+};
+// done (may be null): signalled by the kernel's completion.  K (may be null: no collider, today's instantiations): the push
+// operator runs in the kernel's tail, after the wall clamp.
+void launch3_force(hipStream_t st, const Params3& P, const Arrays3& A, bool tol, hipEvent_t done, const Collide3* K = nullptr);
 void launch3_import(hipStream_t st, uint32_t n, const Arrays3& A);   // aos -> pos, pred, vel, key
 void launch3_export(hipStream_t st, uint32_t n, const Arrays3& A);   // ... and back
 
@@ -112,5 +121,19 @@ uint32_t mesh3_workgroups(uint32_t nodes);
 void launch3_mesh_count(hipStream_t st, const Params3& P, const Arrays3& A, const Mesh3Query& Q);   // field, flags, offsets -> counts
 void launch3_mesh_verts(hipStream_t st, const Params3& P, const Arrays3& A, const Mesh3Query& Q);   // after _count: rank, verts[0, vert_cap)
 void launch3_mesh_faces(hipStream_t st, const Mesh3Query& Q);                                       // after _verts: tris[0, tri_cap)
+
+
+// 3D collider producer (kernels_collide3d.hip): a w x h x d u8 mask (> 128: solid) to the push field of Collide3 by
+// an exact Euclidean distance transform in index space, three separable u32 passes.  Device pointers; host side only.  `near_x` and
+// `near_xy` hold w * h * d words each (the nearest free voxel after the X pass, packed x | y << 16 after the Y pass).
+struct ColliderMask3 {
+    const uint8_t* mask = nullptr;
+    uint32_t w = 0, h = 0, d = 0;      // each 1 .. 1024
+    float vx = 0.0f, vy = 0.0f, vz = 0.0f;   // voxel edge per axis: size.a / (float)W_a
+    uint32_t* near_x = nullptr;
+    uint32_t* near_xy = nullptr;
+    float4* field = nullptr;           // out
+};
+void launch3_collider_from_mask(hipStream_t st, const ColliderMask3& Q);
 
 }  // namespace fsd

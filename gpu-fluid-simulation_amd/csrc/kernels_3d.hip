@@ -673,16 +673,40 @@ __device__ __forceinline__ void sweep3_chunks(const Params3& P, const Tol3& C, c
     }
 }
 
+// The opt-in static collider (include/fluidsim.h "3D colliders"): the operator C on the position and velocity the
+// step is about to store — the 3D form of move_particle's force-texture push (compute.wgsl:127-140), after the wall clamp and
+// followed by the wall clamp again.  One aligned 16-byte load per particle; every index is clamped, so no p reads out of bounds
+// (NaN -> voxel 0).
+__device__ __forceinline__ uint32_t voxel3(float p, float b, float size, uint32_t w) {
+    const uint32_t i = f32_to_u32_sat(__fdiv_rn(p + b, size) * (float)w);
+    return i < w - 1u ? i : w - 1u;
+}
+__device__ __forceinline__ void collide3(const Params3& P, const Collide3& K, float4& p, float4& v) {
+    const uint32_t ix = voxel3(p.x, P.bx, K.sx, K.w), iy = voxel3(p.y, P.by, K.sy, K.h), iz = voxel3(p.z, P.bz, K.sz, K.d);
+    const float4 f = K.field[(size_t)((iz * K.h + iy) * K.w + ix)];
+    if (!(f.x != 0.0f || f.y != 0.0f || f.z != 0.0f)) return;
+    const float len = sqrt_rn((f.x * f.x + f.y * f.y) + f.z * f.z);
+    if (!(len > 0.0f)) return;                          // a vector whose squares all underflow is free space
+    const float nx = __fdiv_rn(f.x, len), ny = __fdiv_rn(f.y, len), nz = __fdiv_rn(f.z, len);
+    p.x = p.x + f.x; p.y = p.y + f.y; p.z = p.z + f.z;
+    const float vn = (v.x * nx + v.y * ny) + v.z * nz;
+    const float k = (1.0f - P.damping) * vn;
+    v.x = v.x - k * nx; v.y = v.y - k * ny; v.z = v.z - k * nz;
+    if (fabsf(p.x) > P.bx) { p.x = P.bx * sign_f32(p.x); v.x *= -1.0f * P.damping; }
+    if (fabsf(p.y) > P.by) { p.y = P.by * sign_f32(p.y); v.y *= -1.0f * P.damping; }
+    if (fabsf(p.z) > P.bz) { p.z = P.bz * sign_f32(p.z); v.z *= -1.0f * P.damping; }
+}
+
 // The 27-cell sweep runs plane by plane (z outer).  Per plane the workgroup's three row ranges are staged
 // into LDS (as in k3_density) and swept with register pass-masks (sweep3_masks); waves that hold a range
-// longer than 64, and planes whose rows do not fit the tile, take the chunked sweep.
-template <int MODE>
+// longer than 64, and planes whose rows do not fit the tile, take the chunked sweep.  COLLIDE: collide3() before the stores.
+template <int MODE, bool COLLIDE>
 __device__ __forceinline__ void force3_body(const Params3& P, const float4* __restrict__ pos_s,
                                             const float4* __restrict__ vel_s, const float4* __restrict__ pred,
                                             const uint32_t* __restrict__ cs, float4* __restrict__ pos_out,
                                             float4* __restrict__ vel_out, const u64m* __restrict__ masks,
                                             const uint32_t* __restrict__ key_s, const u64* __restrict__ srcs, float4* s_buf,
-                                            uint32_t* s_red) {
+                                            uint32_t* s_red, const Collide3& K) {
     const uint32_t tid = threadIdx.x;
     uint32_t blk;
     if (!xcd_block3(P, (P.n + B3F - 1) / B3F, &blk)) return;       // uniform
@@ -743,6 +767,7 @@ __device__ __forceinline__ void force3_body(const Params3& P, const float4* __re
     if (fabsf(p.x) > P.bx) { p.x = P.bx * sign_f32(p.x); v.x *= -1.0f * P.damping; }
     if (fabsf(p.y) > P.by) { p.y = P.by * sign_f32(p.y); v.y *= -1.0f * P.damping; }
     if (fabsf(p.z) > P.bz) { p.z = P.bz * sign_f32(p.z); v.z *= -1.0f * P.damping; }
+    if (COLLIDE) collide3(P, K, p, v);
     p.w = 0.0f; v.w = 0.0f;
     pos_out[i] = p;
     vel_out[i] = v;
@@ -755,7 +780,18 @@ __global__ __launch_bounds__(B3F) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const uint32_t* __restrict__ key_s, const u64* __restrict__ srcs) {
     __shared__ float4 s_buf[TILE3_FORCE_LDS];     // the staged plane: positions, then velocities
     __shared__ uint32_t s_red[24];
-    force3_body<MODE>(P, pos_s, vel_s, pred, cs, pos_out, vel_out, masks, key_s, srcs, s_buf, s_red);
+    force3_body<MODE, false>(P, pos_s, vel_s, pred, cs, pos_out, vel_out, masks, key_s, srcs, s_buf, s_red, Collide3{});
+}
+// The same kernel with the collider operator in its tail: the only instantiations that take a Collide3.  At the tail the
+// accumulators are dead, so the register budget of four waves per SIMD holds (DESIGN.md §18 has the figures).
+template <int MODE>
+__global__ __launch_bounds__(B3F) __attribute__((amdgpu_waves_per_eu(4, 4))) void k3_force_collide(
+    Params3 P, const float4* __restrict__ pos_s, const float4* __restrict__ vel_s, const float4* __restrict__ pred,
+    const uint32_t* __restrict__ cs, float4* __restrict__ pos_out, float4* __restrict__ vel_out, const u64m* __restrict__ masks,
+    const uint32_t* __restrict__ key_s, const u64* __restrict__ srcs, Collide3 K) {
+    __shared__ float4 s_buf[TILE3_FORCE_LDS];
+    __shared__ uint32_t s_red[24];
+    force3_body<MODE, true>(P, pos_s, vel_s, pred, cs, pos_out, vel_out, masks, key_s, srcs, s_buf, s_red, K);
 }
 
 __global__ __launch_bounds__(B3) void k3_export(uint32_t n, const float4* __restrict__ pos, const float4* __restrict__ pred,
@@ -803,8 +839,13 @@ void launch3_density(hipStream_t st, const Params3& P, const Arrays3& A, bool to
 }
 
 // positions ping-pong: read the previous state (A.pos, source order) through the pairs, write the new one into A.pos_out
-void launch3_force(hipStream_t st, const Params3& P, const Arrays3& A, bool tol, hipEvent_t done) {
+void launch3_force(hipStream_t st, const Params3& P, const Arrays3& A, bool tol, hipEvent_t done, const Collide3* K) {
     const dim3 grid(xcd_grid3(blocks3(P.n), P.xcd_chunk_log2)), block(B3F);
+    if (K) {
+        if (tol) hipExtLaunchKernelGGL(k3_force_collide<2>, grid, block, 0, st, nullptr, done, 0, P, A.pos, A.vel_s, A.pred, A.cs, A.pos_out, A.vel, A.masks, A.key, A.pairs, *K);
+        else hipExtLaunchKernelGGL(k3_force_collide<0>, grid, block, 0, st, nullptr, done, 0, P, A.pos, A.vel_s, A.pred, A.cs, A.pos_out, A.vel, A.masks, A.key, A.pairs, *K);
+        return;
+    }
     if (tol) hipExtLaunchKernelGGL(k3_force<2>, grid, block, 0, st, nullptr, done, 0, P, A.pos, A.vel_s, A.pred, A.cs, A.pos_out, A.vel, A.masks, A.key, A.pairs);
     else hipExtLaunchKernelGGL(k3_force<0>, grid, block, 0, st, nullptr, done, 0, P, A.pos, A.vel_s, A.pred, A.cs, A.pos_out, A.vel, A.masks, A.key, A.pairs);
 }

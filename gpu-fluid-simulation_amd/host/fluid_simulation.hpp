@@ -230,6 +230,24 @@ public:
                                 uint32_t tri_cap, uint32_t* counts_dev) {
         check(fs3_extract_surface_device(h_, &view, iso, verts_dev, vert_cap, tris_dev, tri_cap, counts_dev));
     }
+    // 3D colliders: w * h * d push vectors in world units over the whole domain, voxel (i, j, k) at (k * h + j) * w + i, zero = free
+    // space.  Blocking; holds for the ticks enqueued afterwards.  set_collider_mask: from a voxel mask (> 128: solid).
+    void set_collider(const std::vector<fs_vec3>& field, uint32_t w, uint32_t h, uint32_t d) {
+        if (field.size() != (size_t)w * h * d) throw std::invalid_argument("set_collider: field.size() != w * h * d");
+        check(fs3_collider_upload(h_, field.data(), w, h, d));
+    }
+    void set_collider_mask(const std::vector<uint8_t>& mask, uint32_t w, uint32_t h, uint32_t d) {
+        if (mask.size() != (size_t)w * h * d) throw std::invalid_argument("set_collider_mask: mask.size() != w * h * d");
+        check(fs3_collider_from_mask(h_, mask.data(), w, h, d, nullptr));
+    }
+    void clear_collider() { check(fs3_collider_clear(h_)); }
+    std::vector<fs_vec3> collider() {      // empty when none is set
+        uint32_t w = 0, h = 0, d = 0;
+        check(fs3_collider_dims(h_, &w, &h, &d));
+        std::vector<fs_vec3> v((size_t)w * h * d);
+        if (!v.empty()) check(fs3_collider_download(h_, v.data(), v.size()));
+        return v;
+    }
     fs_sim3* handle() { return h_; }
 
 private:

@@ -240,6 +240,11 @@ extern "C" {
     fn fs3_render_surface_device(sim: *mut fs_sim3, camera: *const Camera3, params: *const SurfaceParams3, out_dev: *mut SurfaceHit3) -> c_int;
     fn fs3_extract_surface(sim: *mut fs_sim3, view: *const View3, iso: f32, verts: *mut MeshVertex3, vert_cap: u32, tris: *mut u32, tri_cap: u32, counts: *mut u32) -> c_int;
     fn fs3_extract_surface_device(sim: *mut fs_sim3, view: *const View3, iso: f32, verts_dev: *mut MeshVertex3, vert_cap: u32, tris_dev: *mut u32, tri_cap: u32, counts_dev: *mut u32) -> c_int;
+    fn fs3_collider_upload(sim: *mut fs_sim3, field_host: *const Vec3, w: u32, h: u32, d: u32) -> c_int;
+    fn fs3_collider_from_mask(sim: *mut fs_sim3, mask_host: *const u8, w: u32, h: u32, d: u32, field_host: *mut Vec3) -> c_int;
+    fn fs3_collider_clear(sim: *mut fs_sim3) -> c_int;
+    fn fs3_collider_dims(sim: *const fs_sim3, w: *mut u32, h: *mut u32, d: *mut u32) -> c_int;
+    fn fs3_collider_download(sim: *mut fs_sim3, dst: *mut Vec3, n: usize) -> c_int;
     // ResizableBuffer<T> (src/buffer.rs)
     fn fs_buffer_create(device: c_int, elem_size: usize, len: usize, name: *const c_char, out: *mut *mut fs_buffer) -> c_int;
     fn fs_buffer_resize(buf: *mut fs_buffer, new_cap: usize, resized: *mut c_int) -> c_int;
@@ -637,6 +642,27 @@ impl FluidSimulation3D {
     /// host read.  The counts are always the full ones: compare them with the capacities once the stream has passed the call.
     pub unsafe fn extract_surface_device(&mut self, view: &View3, iso: f32, verts_dev: *mut MeshVertex3, vert_cap: u32, tris_dev: *mut u32, tri_cap: u32, counts_dev: *mut u32) {
         check(fs3_extract_surface_device(self.raw, view, iso, verts_dev, vert_cap, tris_dev, tri_cap, counts_dev));
+    }
+    /// Build extension: 3D colliders (include/fluidsim.h).  `field`: `w * h * d` push vectors in world units over the whole
+    /// domain, voxel (i, j, k) at `(k * h + j) * w + i`, zero = free space.  Blocking; holds for the ticks enqueued afterwards.
+    pub fn set_collider(&mut self, field: &[Vec3], w: u32, h: u32, d: u32) {
+        assert_eq!(field.len(), w as usize * h as usize * d as usize);
+        check(unsafe { fs3_collider_upload(self.raw, field.as_ptr(), w, h, d) });
+    }
+    /// ... from a voxel mask (> 128: solid): every solid voxel pushes to its nearest free voxel in index space.
+    pub fn set_collider_mask(&mut self, mask: &[u8], w: u32, h: u32, d: u32) {
+        assert_eq!(mask.len(), w as usize * h as usize * d as usize);
+        check(unsafe { fs3_collider_from_mask(self.raw, mask.as_ptr(), w, h, d, std::ptr::null_mut()) });
+    }
+    pub fn clear_collider(&mut self) { check(unsafe { fs3_collider_clear(self.raw) }); }
+    /// (w, h, d) of the collider, (0, 0, 0) when none is set.
+    pub fn collider_dims(&self) -> (u32, u32, u32) { let (mut w, mut h, mut d) = (0, 0, 0); check(unsafe { fs3_collider_dims(self.raw, &mut w, &mut h, &mut d) }); (w, h, d) }
+    /// The field in use; empty when none is set.
+    pub fn collider(&mut self) -> Vec<Vec3> {
+        let (w, h, d) = self.collider_dims();
+        let mut v = vec![Vec3::default(); w as usize * h as usize * d as usize];
+        if !v.is_empty() { check(unsafe { fs3_collider_download(self.raw, v.as_mut_ptr(), v.len()) }); }
+        v
     }
     pub fn stream(&self) -> *mut c_void { unsafe { fs3_stream(self.raw) } }
 }

@@ -499,7 +499,7 @@ fs_status fs_comm_allreduce(fs_sim* sim, fs_comm* comm, void* device_buf, size_t
 /* ------------------------------------------------------------ 3D extension */
 /* NOT in the reference (2D only).  Build-defined per SURVEY.md Appendix B.3: same pass
  * chain and kernel shapes with a third coordinate, 27-cell sweep, clean cell starts, no
- * mouse force / obstacle field.  Normative statement: oracle/sph_oracle3d.cpp. */
+ * mouse force; an obstacle field only on request ("3D colliders" below).  Normative statement: oracle/sph_oracle3d.cpp. */
 typedef struct fs3_settings {
     uint32_t particle_count;      /* must be a cube (side^3) for the built-in lattice */
     float particle_spacing;
@@ -724,6 +724,61 @@ fs_status fs3_extract_surface(fs_sim3* sim, const fs3_view* view, float iso, fs3
                               uint32_t* tris /* 3 per triangle */, uint32_t tri_cap, uint32_t counts[2] /* V, T */);
 fs_status fs3_extract_surface_device(fs_sim3* sim, const fs3_view* view, float iso, fs3_mesh_vertex* verts_dev, uint32_t vert_cap,
                                      uint32_t* tris_dev, uint32_t tri_cap, uint32_t* counts_dev /* [2] */);
+
+/* ------------------------------------------------ 3D colliders (build extension, opt-in by being set) */
+/* Static obstacles for the 3D step: the 3D counterpart of the 2D force texture (read by move_particle, compute.wgsl:127-140;
+ * produced by generate_smooth_gradient_field, src/main.rs:403-515).  A collider is a W x H x D voxel field of push vectors in world
+ * units over the whole domain [-size/2, size/2]; voxel (i, j, k) is field[(k * H + j) * W + i]; a zero vector is free space.  A
+ * handle that never sets one launches exactly the kernels it launched before and computes the same bits.
+ *
+ * With a collider set, a step is the step without one followed, per particle, by the operator C below on the position p and the
+ * velocity v that step stores (after its wall clamp): new state = C(step(state)).  All arithmetic is f32 without contraction, `/`
+ * and `sqrt` are correctly rounded; b.a = size.a * 0.5f are the half-bounds of the step; u32_sat is the conversion of the cell
+ * coordinates (oracle/sph_oracle3d.cpp cell_xyz: NaN and negatives -> 0, >= 2^32 -> 2^32 - 1, else truncation).
+ *     ia = min(u32_sat(((p.a + b.a) / size.a) * (float)W_a), W_a - 1)            per axis a (W_x = W, W_y = H, W_z = D)
+ *     f  = field[(iz * H + iy) * W + ix]
+ *     if f.x != 0 || f.y != 0 || f.z != 0:
+ *         len = sqrt((f.x*f.x + f.y*f.y) + f.z*f.z)
+ *         if len > 0:                                      (a vector whose squares all underflow is treated as zero)
+ *             n.a = f.a / len
+ *             p.a = p.a + f.a
+ *             vn  = (v.x*n.x + v.y*n.y) + v.z*n.z
+ *             k   = (1.0f - damping_factor) * vn           (compute.wgsl:137-138 with a third coordinate)
+ *             v.a = v.a - k * n.a
+ *             per axis, in x, y, z order: if fabsf(p.a) > b.a { p.a = b.a * sign(p.a); v.a *= -1.0f * damping_factor }
+ * predicted_position, density and grid are not touched.  The order is integrate, clamp, push, clamp (the reference's 2D order is
+ * push, then its only clamp): the 3D oracle plus this operator on the CPU is then the whole statement.  The lookup uses the new,
+ * clamped position; every index is clamped as well, so no value of p reads outside the field.
+ *
+ * fs3_collider_upload: a field made by the caller.  fs3_collider_from_mask: the field of a u8 voxel mask (> 128: solid, the 2D
+ * producer's threshold; same layout), made on the GPU by an exact Euclidean distance transform in INDEX space — three separable
+ * passes in u32 arithmetic, so every bit is determined:
+ *     X: a(i,j,k) = the free i' in row (j,k) minimising |i - i'|, ties to the smaller i'; none if the row has no free voxel
+ *     Y: over j' with a(i,j',k) defined, minimise (a(i,j',k) - i)^2 + (j' - j)^2, ties to the smaller j';  b = (a(i,j',k), j')
+ *     Z: over k' with b(i,j,k') defined, minimise (b.x - i)^2 + (b.y - j)^2 + (k' - k)^2, ties to the smaller k';  c = (b.x, b.y, k')
+ *     field(i,j,k).a = (float)((int)c.a - (int)i_a) * s_a,   s_a = size.a / (float)W_a       (a free voxel's nearest is itself: +0)
+ * The squared index distance to c is the minimum over all free voxels; the tie rules only pick among equals.  "Nearest" is in
+ * index space: with voxels that are not cubes it need not be the nearest free voxel in world space.  A solid voxel's vector
+ * reaches the CENTRE-to-centre offset of its nearest free voxel.  `field_host` (may be NULL) receives the field, w * h * d fs_vec3.
+ *
+ * Checks, in this order:
+ *  1. NULL handle -> FS_ERR_INVALID.
+ *  2. NULL array (field, mask, dst, or one of the three extent pointers) -> FS_ERR_INVALID.
+ *  3. An extent of 0 or above 1024 -> FS_ERR_INVALID.
+ *  4. fs3_collider_upload: a non-finite component -> FS_ERR_INVALID.  fs3_collider_from_mask: a mask without a free voxel ->
+ *     FS_ERR_INVALID.  Either way the collider set before stays as it was.
+ * fs3_collider_download: FS_ERR_INVALID when no collider is set or n != w * h * d.  fs3_collider_dims: 0, 0, 0 when none.
+ *
+ * The calls are blocking, like fs3_upload_particles, and ordered on fs3_stream(sim): they take effect for the steps enqueued
+ * afterwards, after the steps already in flight, which never see a half-replaced field.  A second upload replaces the first and
+ * allocates only if the field grew; fs3_collider_clear frees it.  Setting or clearing a collider does NOT make sampling, rendering
+ * or extraction stale (the records and the cell table still belong together).  The time of the operator falls inside
+ * FS_PASS_FORCE.  FS_ABI_VERSION is unchanged.  See DESIGN.md §18. */
+fs_status fs3_collider_upload(fs_sim3* sim, const fs_vec3* field_host, uint32_t w, uint32_t h, uint32_t d);
+fs_status fs3_collider_from_mask(fs_sim3* sim, const uint8_t* mask_host, uint32_t w, uint32_t h, uint32_t d, fs_vec3* field_host /* may be NULL */);
+fs_status fs3_collider_clear(fs_sim3* sim);
+fs_status fs3_collider_dims(const fs_sim3* sim, uint32_t* w, uint32_t* h, uint32_t* d);      /* 0,0,0 when none */
+fs_status fs3_collider_download(fs_sim3* sim, fs_vec3* dst, size_t n);                       /* n == w*h*d; FS_ERR_INVALID when none */
 
 /* ------------------------------------------------------- ResizableBuffer */
 /* ResizableBuffer<T>::new (src/buffer.rs:27-43). */

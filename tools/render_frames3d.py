@@ -1,9 +1,16 @@
 """Render a few frames of the 3D dam break to PNG through the ray-marched G-buffer, headless:
-  python tools/render_frames3d.py [n] [frame,frame,...] [outdir] [width] [height]"""
+  python tools/render_frames3d.py [n] [frame,frame,...] [outdir] [width] [height] [--box x0,y0,z0,x1,y1,z1[,voxels]]
+--box: a static obstacle, a box in world coordinates (+y is the floor) rasterised to a mask of `voxels` (default
+64) voxels along x and as many along y and z as keep them near cubes; the fluid flows around it, the box itself is not drawn."""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.getcwd())
 import gpu_fluid_simulation_amd as g
+box = None
+if "--box" in sys.argv:
+    k = sys.argv.index("--box")
+    box = [float(x) for x in sys.argv[k + 1].split(",")]
+    del sys.argv[k:k + 2]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 64 ** 3
 frames = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [1, 60, 150, 300]
 outdir = sys.argv[3] if len(sys.argv) > 3 else "build/frames3d"
@@ -13,6 +20,11 @@ os.makedirs(outdir, exist_ok=True)
 st, off, tick = g.dam_break_3d(n)
 sim = g.FluidSimulation3D(st, device=0, initial_offset=off)
 sx, sy, sz = st.size.x, st.size.y, st.size.z
+if box is not None:
+    w = int(box[6]) if len(box) > 6 else 64
+    shape = (w, max(1, round(w * sy / sx)), max(1, round(w * sz / sx)))
+    sim.set_collider_mask(g.box_mask3d((sx, sy, sz), shape, box[0:3], box[3:6]))
+    print("collider", sim.collider_dims, flush=True)
 # gravity is +y: "up" is -y.  From in front of the -z wall, above the floor, looking at the middle of the tank.
 eye = (-0.15 * sx, -0.55 * sy, -0.5 * sz - 0.9 * sx)
 cam = g.look_at_camera(eye, (0.0, 0.15 * sy, 0.0), (0.0, -1.0, 0.0), np.radians(42.0), width, height)
