@@ -493,6 +493,35 @@ class FluidSimulation3D:
         """hipStream_t of the simulation as an integer (torch.cuda.ExternalStream / RCCL on the same stream)."""
         return int(self._lib.fs3_stream(self._h) or 0)
 
+    # -- 3D surface tension (build extension; DESIGN.md §19) -----------------
+    def set_surface_tension(self, coefficient, threshold=0.0):
+        """Colour-field surface tension (include/fluidsim.h "3D surface tension") for the steps enqueued after this call:
+        force -coefficient * laplace(c) * n / |n| where the colour gradient |n| exceeds `threshold`."""
+        _check(self._lib, self._lib.fs3_set_surface_tension(self._h, 1, float(coefficient), float(threshold)))
+
+    def clear_surface_tension(self):
+        """Back to the plain step, for the steps enqueued after this call."""
+        _check(self._lib, self._lib.fs3_set_surface_tension(self._h, 0, 0.0, 0.0))
+
+    @property
+    def surface_tension_enabled(self):
+        return bool(self._lib.fs3_surface_tension_enabled(self._h))
+
+    @property
+    def surface_tension_params(self):
+        """(coefficient, threshold) in use, or None when the feature is off."""
+        if not self.surface_tension_enabled:
+            return None
+        c, t = C.c_float(), C.c_float()
+        _check(self._lib, self._lib.fs3_surface_tension_params(self._h, C.byref(c), C.byref(t)))
+        return float(c.value), float(t.value)
+
+    def surface_tension_forces(self):
+        """The last step's surface-tension force per particle, (N, 3) float32 in download_particles() order."""
+        out = np.empty((self.particle_count, 3), dtype=np.float32)
+        _check(self._lib, self._lib.fs3_download_surface_tension(self._h, out.ctypes.data_as(C.c_void_p), out.shape[0]))
+        return out
+
     # -- 3D field sampling (build extension; DESIGN.md §14) ------------------
     def sample(self, points, normalise=False):
         """Density, Shepard weight, velocity sum, density gradient, neighbour count and cell of the fluid at `points`

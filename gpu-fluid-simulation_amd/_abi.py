@@ -334,6 +334,10 @@ PROTOTYPES = {
     "fs3_collider_clear": (C.c_int, [_P]),
     "fs3_collider_dims": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fs3_collider_download": (C.c_int, [_P, _P, C.c_size_t]),
+    "fs3_set_surface_tension": (C.c_int, [_P, C.c_int, C.c_float, C.c_float]),
+    "fs3_surface_tension_enabled": (C.c_int, [_P]),
+    "fs3_surface_tension_params": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "fs3_download_surface_tension": (C.c_int, [_P, _P, C.c_size_t]),
     "fs_selftest_constdiv": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_uint32)]),
     "fs_sort_plan_read": (C.c_int, [C.c_void_p, C.POINTER(SortPlanInfo)]),
     "fs_selftest_sort_policy": (C.c_int, [C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t,

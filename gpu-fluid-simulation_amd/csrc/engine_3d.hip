@@ -64,6 +64,13 @@ struct fs_sim3 {
     // coll.n is the capacity (it only grows), cw * ch * cd the field in use
     DevArray<float4> coll;
     uint32_t cw = 0, ch = 0, cd = 0;
+    // the opt-in surface tension: never enabled: no allocation, no launch
+    struct Tension {
+        DevArray<float4> st;         // the last step's force per sorted slot {x, y, z, 0}; allocated by the first enable
+        float sigma = 0.0f, tau = 0.0f;
+        bool on = false;
+        bool valid = false;          // a step has been enqueued since the feature was last enabled: st belongs to the state
+    } tension;
 
     // the arrays as the launchers see them (fs_3d.h): the force pass writes the new positions into the spare buffer
     fsd::Arrays3 arrays() const {
@@ -152,7 +159,14 @@ static fs_status enqueue3(fs_sim3* s, const fs3_tick_settings* t) {
     // the collider, if one is set, by value: this step keeps the field it was enqueued with (fs3_collider_* order their writes
     // on the stream behind it)
     const Collide3 K{s->coll.p, s->cw, s->ch, s->cd, s->st.size.x, s->st.size.y, s->st.size.z};
-    launch3_force(st, P, A, tol, done, s->cw ? &K : nullptr);
+    // surface tension, if enabled: its pass between the density and the force pass (inside the force interval of the profile),
+    // with the coefficients of this enqueue by value
+    if (s->tension.on) {
+        const Tension3 T{P.h2, 6.0f * P.poly6, 3.0f * P.h2, s->tension.sigma, s->tension.tau};
+        launch3_surface_tension(st, P, A, T, s->tension.st.p);
+        s->tension.valid = true;
+    }
+    launch3_force(st, P, A, tol, done, s->cw ? &K : nullptr, s->tension.on ? s->tension.st.p : nullptr);
     std::swap(s->pos, s->pos_s);
     s->mass = t->mass; s->sample_stale = false;
     if (ev) { FS_HIP(hipEventRecord(ev[5], st)); FS_HIP(hipEventRecord(ev[6], st)); /* FS_PASS_BOUNDARY: slab handles only */ s->prof.pending += 1; }
@@ -398,6 +412,48 @@ fs_status fs3_collider_download(fs_sim3* s, fs_vec3* dst, size_t n) {
     if (n != (size_t)s->cw * s->ch * s->cd) return fail(FS_ERR_INVALID, "collider: n must be w * h * d");
     FS_HIP(hipSetDevice(s->device));
     return collider3_read(s, dst);
+}
+
+// ---- 3D surface tension -------------------------------------------------------------------------------
+fs_status fs3_set_surface_tension(fs_sim3* s, int enable, float coefficient, float threshold) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    if (!enable) { s->tension.on = false; return FS_OK; }          // the two floats are not looked at
+    if (std::isnan(coefficient)) return fail(FS_ERR_INVALID, "surface tension: coefficient is NaN");
+    if (std::isnan(threshold)) return fail(FS_ERR_INVALID, "surface tension: threshold is NaN");
+    if (!s->tension.st.p) {
+        FS_HIP(hipSetDevice(s->device));
+        if (s->tension.st.alloc(s->n) != hipSuccess) {
+            (void)hipGetLastError();
+            s->tension.st.release();
+            return fail(FS_ERR_OOM, "surface tension: device array");
+        }
+    }
+    if (!s->tension.on) s->tension.valid = false;                  // fs3_download_surface_tension waits for a step of this enable
+    s->tension.on = true; s->tension.sigma = coefficient; s->tension.tau = threshold;
+    return FS_OK;
+}
+
+int fs3_surface_tension_enabled(const fs_sim3* s) { return (s && s->tension.on) ? 1 : 0; }
+
+fs_status fs3_surface_tension_params(const fs_sim3* s, float* coefficient, float* threshold) {
+    if (!s || !coefficient || !threshold) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->tension.on) return fail(FS_ERR_INVALID, "surface tension: not enabled");
+    *coefficient = s->tension.sigma; *threshold = s->tension.tau;
+    return FS_OK;
+}
+
+fs_status fs3_download_surface_tension(fs_sim3* s, fs_vec3* dst, size_t n) {
+    if (!s || !dst) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->tension.on) return fail(FS_ERR_INVALID, "surface tension: not enabled");
+    if (!s->tension.valid) return fail(FS_ERR_INVALID, "surface tension: no step since surface tension was last enabled");
+    if (n != s->n) return fail(FS_ERR_INVALID, "surface tension: n must equal the particle count");
+    FS_HIP(hipSetDevice(s->device));
+    std::unique_ptr<float4[]> host(new (std::nothrow) float4[n]);
+    if (!host) return fail(FS_ERR_OOM, "host allocation failed");
+    FS_HIP(hipMemcpyAsync(host.get(), s->tension.st.p, n * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
+    FS_HIP(hipStreamSynchronize(s->stream));
+    for (size_t k = 0; k < n; ++k) dst[k] = fs_vec3{host[k].x, host[k].y, host[k].z};
+    return sort_health3(s);
 }
 
 // ---- 3D field sampling --------------------------------------------------------------------------------

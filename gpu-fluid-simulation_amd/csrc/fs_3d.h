@@ -72,9 +72,19 @@ struct Collide3 {
     uint32_t w, h, d;
     float sx, sy, sz;
 };
+// The opt-in surface tension of a handle (include/fluidsim.h "3D surface tension") as k3_surface_tension takes it,
+// by value and apart from Params3: cg = 6.0f * poly6, h2x3 = 3.0f * h2 (one f32 multiply each, on the host).
+struct Tension3 {
+    float h2, cg, h2x3, sigma, tau;
+};
+// After launch3_density, before launch3_force: st[i] = {sx, sy, sz, 0} per sorted slot, from pred (.w = density), the cell table
+// and — A.masks non-null — the pass masks k3_density handed over.
+void launch3_surface_tension(hipStream_t st, const Params3& P, const Arrays3& A, const Tension3& T, float4* stf);
 // done (may be null): signalled by the kernel's completion.  K (may be null: no collider, today's instantiations): the push
-// operator runs in the kernel's tail, after the wall clamp.
-void launch3_force(hipStream_t st, const Params3& P, const Arrays3& A, bool tol, hipEvent_t done, const Collide3* K = nullptr);
+// operator runs in the kernel's tail, after the wall clamp.  stf (may be null: no surface tension, today's instantiations): the
+// forces of launch3_surface_tension, added to the force sum.
+void launch3_force(hipStream_t st, const Params3& P, const Arrays3& A, bool tol, hipEvent_t done, const Collide3* K = nullptr,
+                   const float4* stf = nullptr);
 void launch3_import(hipStream_t st, uint32_t n, const Arrays3& A);   // aos -> pos, pred, vel, key
 void launch3_export(hipStream_t st, uint32_t n, const Arrays3& A);   // ... and back
 

@@ -341,6 +341,137 @@ __global__ __launch_bounds__(B3F) void k3_density(Params3 P, float4* __restrict_
     *yw = ok ? y : -y;
 }
 
+// ---- opt-in surface tension (include/fluidsim.h "3D surface tension") ---------------------------------
+// The colour-field pass: per sorted slot i, over the neighbours k3_density visits (i itself included, same order),
+//     n += w_j * (((Cg d) d) o),   L += w_j * ((Cg d) (7 r2 - 3 h2)),   o = q_j - q_i, d = h2 - r2, w_j = m / rho_j
+// then st = ((-sigma L) / |n|) n where |n| > tau and |n| > 0, else 0.  k3_density's walk with another term: the same block
+// mapping, row look-up, tile bounds and plane classes, and — handed over — the same pass masks.  A staged candidate is
+// {q.xyz, w}: the division happens once per staged candidate, a neighbour costs one 16-byte LDS read.
+struct TensionAcc { float nx, ny, nz, L; };
+__device__ __forceinline__ void tension_add(const Tension3& T, float4 me, float4 c, TensionAcc& A) {    // c = {q_j.xyz, w_j}, in radius
+    const float ox = c.x - me.x, oy = c.y - me.y, oz = c.z - me.z;
+    const float r2 = ox * ox + oy * oy + oz * oz;
+    const float d = T.h2 - r2;
+    const float k = (T.cg * d) * d;
+    A.nx += c.w * (k * ox); A.ny += c.w * (k * oy); A.nz += c.w * (k * oz);
+    const float lk = (T.cg * d) * ((7.0f * r2) - T.h2x3);
+    A.L += c.w * lk;
+}
+// One candidate of the sweeps without masks: the radius test of dens3 first.
+__device__ __forceinline__ void tension_try(const Tension3& T, float4 me, float4 c, TensionAcc& A) {
+    const float ox = c.x - me.x, oy = c.y - me.y, oz = c.z - me.z;
+    const float r2 = ox * ox + oy * oy + oz * oz;
+    if (!(r2 > T.h2)) tension_add(T, me, c, A);
+}
+// The terms of the set bits of one pass mask, ascending (bit 63 - t = candidate base[t]); the next candidate's read is issued
+// before this one's terms.
+__device__ __forceinline__ void walk_tension(const Tension3& T, u64m mask, const float4* base, float4 me, TensionAcc& A) {
+    float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    bool have = mask != 0ull;
+    if (have) { const uint32_t t = (uint32_t)__builtin_clzll(mask); mask ^= 0x8000000000000000ull >> t; c = base[t]; }
+    while (have) {
+        const float4 c0 = c;
+        have = mask != 0ull;
+        if (have) { const uint32_t t = (uint32_t)__builtin_clzll(mask); mask ^= 0x8000000000000000ull >> t; c = base[t]; }
+        tension_add(T, me, c0, A);
+    }
+}
+
+__global__ __launch_bounds__(B3F) void k3_surface_tension(Params3 P, Tension3 T, const float4* __restrict__ pred,
+                                                         const uint32_t* __restrict__ cs, const u64m* __restrict__ masks,
+                                                         const uint32_t* __restrict__ key_s, float4* __restrict__ st) {
+    __shared__ float4 s_cand[TILE3_LDS + 64];   // a 128-candidate scan reads up to 131 entries from a range start
+    __shared__ uint32_t s_mm[24];
+    uint32_t blk;
+    if (!xcd_block3(P, (P.n + B3F - 1) / B3F, &blk)) return;       // uniform
+    const uint32_t i = blk * B3F + threadIdx.x;
+    const bool live = i < P.n;
+    const uint32_t ii = live ? i : P.n - 1;
+    const float4 me = pred[ii];
+    const uint32_t key = key_s[ii];
+    TensionAcc A;
+    A.nx = A.ny = A.nz = A.L = 0.0f;
+    uint32_t lo9[9], hi9[9];
+    rows3_lookup(P, cs, key, live, lo9, hi9);
+#pragma unroll 1
+    for (int plane = 0; plane < 3; ++plane) {
+        RowRanges R;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            R.lo[r] = plane == 0 ? lo9[r] : plane == 1 ? lo9[3 + r] : lo9[6 + r];
+            R.hi[r] = plane == 0 ? hi9[r] : plane == 1 ? hi9[3 + r] : hi9[6 + r];
+        }
+        uint32_t blo[3], bhi[3];
+        const bool fit = block_tile_bounds<W3F>(R, s_mm, blo, bhi, TILE3);
+        if (fit) {
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+                for (uint32_t j = threadIdx.x; j < bhi[r] - blo[r]; j += B3F) {
+                    float4 c = pred[blo[r] + j];
+                    c.w = __fdiv_rn(P.mass, c.w);                          // w_j, once per staged candidate
+                    s_cand[r * TILE3_ROW + j] = c;
+                }
+            __syncthreads();
+            const int pclass = plane_class(R, fit);      // the same predicate as k3_density: its masks exist exactly for these planes
+            if (pclass == 2) {
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const uint32_t len = R.hi[r] - R.lo[r];
+                    const float4* base = s_cand + row_la(R, blo, r);
+                    u64m mh, ml;
+                    if (masks) {
+                        mh = masks[(size_t)(plane * 3 + r) * P.n + ii] & keep128_hi(len);
+                        ml = masks[(size_t)(9 + plane * 3 + r) * P.n + ii] & keep128_lo(len);
+                    } else {
+                        scan3_row128(P, base, len, me, &mh, &ml);
+                    }
+                    walk_tension(T, mh, base, me, A);
+                    walk_tension(T, ml, base + 64, me, A);
+                }
+            } else if (pclass == 1) {
+                u64m m[3];
+                uint32_t la[3];
+                if (masks) {
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) {
+                        la[r] = row_la(R, blo, r);
+                        m[r] = masks[(size_t)(plane * 3 + r) * P.n + ii] & keep64(R.hi[r] - R.lo[r]);   // lanes past the end: len 0
+                    }
+                } else {
+                    scan3_plane(P, R, blo, me, s_cand, m, la);
+                }
+#pragma unroll
+                for (int r = 0; r < 3; ++r) walk_tension(T, m[r], s_cand + la[r], me, A);
+            } else {
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const bool any = R.lo[r] < R.hi[r];
+                    const uint32_t hi = any ? R.hi[r] - blo[r] : 0u;
+                    const float4* sp = s_cand + r * TILE3_ROW;
+                    for (uint32_t k = any ? R.lo[r] - blo[r] : 0u; k < hi; ++k) tension_try(T, me, sp[k], A);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+                for (uint32_t k = R.lo[r]; k < R.hi[r]; ++k) {
+                    float4 c = pred[k];
+                    c.w = __fdiv_rn(P.mass, c.w);                          // per pair: nothing is staged
+                    tension_try(T, me, c, A);
+                }
+        }
+        __syncthreads();     // the next plane reuses s_cand / s_mm
+    }
+    if (!live) return;
+    const float nl = sqrt_rn((A.nx * A.nx + A.ny * A.ny) + A.nz * A.nz);
+    float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (nl > T.tau && nl > 0.0f) {
+        const float sc = __fdiv_rn(-T.sigma * A.L, nl);
+        f.x = sc * A.nx; f.y = sc * A.ny; f.z = sc * A.nz;
+    }
+    st[i] = f;
+}
+
 struct Acc3 { float px, py, pz, vx, vy, vz; uint32_t seed; };
 struct Terms3 { float px, py, pz, vx, vy, vz; };
 
@@ -700,13 +831,14 @@ __device__ __forceinline__ void collide3(const Params3& P, const Collide3& K, fl
 // The 27-cell sweep runs plane by plane (z outer).  Per plane the workgroup's three row ranges are staged
 // into LDS (as in k3_density) and swept with register pass-masks (sweep3_masks); waves that hold a range
 // longer than 64, and planes whose rows do not fit the tile, take the chunked sweep.  COLLIDE: collide3() before the stores.
-template <int MODE, bool COLLIDE>
+// ST: the surface-tension force of k3_surface_tension joins the force sum (one aligned 16-byte load after the sweep).
+template <int MODE, bool COLLIDE, bool ST>
 __device__ __forceinline__ void force3_body(const Params3& P, const float4* __restrict__ pos_s,
                                             const float4* __restrict__ vel_s, const float4* __restrict__ pred,
                                             const uint32_t* __restrict__ cs, float4* __restrict__ pos_out,
                                             float4* __restrict__ vel_out, const u64m* __restrict__ masks,
                                             const uint32_t* __restrict__ key_s, const u64* __restrict__ srcs, float4* s_buf,
-                                            uint32_t* s_red, const Collide3& K) {
+                                            uint32_t* s_red, const Collide3& K, const float4* __restrict__ st) {
     const uint32_t tid = threadIdx.x;
     uint32_t blk;
     if (!xcd_block3(P, (P.n + B3F - 1) / B3F, &blk)) return;       // uniform
@@ -752,7 +884,8 @@ __device__ __forceinline__ void force3_body(const Params3& P, const float4* __re
     }
     if (!live) return;
     float4 v = mv, p = pos_s[(uint32_t)srcs[i]];        // pos_s: the PREVIOUS state, source order (see k3_reorder)
-    const float ax = A.px + A.vx * P.visc_coeff, ay = A.py + A.vy * P.visc_coeff, az = A.pz + A.vz * P.visc_coeff;
+    float ax = A.px + A.vx * P.visc_coeff, ay = A.py + A.vy * P.visc_coeff, az = A.pz + A.vz * P.visc_coeff;
+    if (ST) { const float4 f = st[i]; ax = ax + f.x; ay = ay + f.y; az = az + f.z; }
     v.x += __fdiv_rn(ax, mrho) * P.dt; v.y += __fdiv_rn(ay, mrho) * P.dt; v.z += __fdiv_rn(az, mrho) * P.dt;
     v.x += P.gx * P.dt; v.y += P.gy * P.dt; v.z += P.gz * P.dt;
     if (!(v.x == v.x && v.y == v.y && v.z == v.z)) { v.x = 0.0f; v.y = 0.0f; v.z = 0.0f; }
@@ -780,7 +913,7 @@ __global__ __launch_bounds__(B3F) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const uint32_t* __restrict__ key_s, const u64* __restrict__ srcs) {
     __shared__ float4 s_buf[TILE3_FORCE_LDS];     // the staged plane: positions, then velocities
     __shared__ uint32_t s_red[24];
-    force3_body<MODE, false>(P, pos_s, vel_s, pred, cs, pos_out, vel_out, masks, key_s, srcs, s_buf, s_red, Collide3{});
+    force3_body<MODE, false, false>(P, pos_s, vel_s, pred, cs, pos_out, vel_out, masks, key_s, srcs, s_buf, s_red, Collide3{}, nullptr);
 }
 // The same kernel with the collider operator in its tail: the only instantiations that take a Collide3.  At the tail the
 // accumulators are dead, so the register budget of four waves per SIMD holds (DESIGN.md §18 has the figures).
@@ -791,7 +924,19 @@ __global__ __launch_bounds__(B3F) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const uint32_t* __restrict__ key_s, const u64* __restrict__ srcs, Collide3 K) {
     __shared__ float4 s_buf[TILE3_FORCE_LDS];
     __shared__ uint32_t s_red[24];
-    force3_body<MODE, true>(P, pos_s, vel_s, pred, cs, pos_out, vel_out, masks, key_s, srcs, s_buf, s_red, K);
+    force3_body<MODE, true, false>(P, pos_s, vel_s, pred, cs, pos_out, vel_out, masks, key_s, srcs, s_buf, s_red, K, nullptr);
+}
+
+// The same kernel with the surface-tension force in the force sum, with and without the collider tail: the only instantiations
+// that take `st`.  Its load comes after the sweep, where the accumulators are about to die (DESIGN.md §19 has the figures).
+template <int MODE, bool COLLIDE>
+__global__ __launch_bounds__(B3F) __attribute__((amdgpu_waves_per_eu(4, 4))) void k3_force_st(
+    Params3 P, const float4* __restrict__ pos_s, const float4* __restrict__ vel_s, const float4* __restrict__ pred,
+    const uint32_t* __restrict__ cs, float4* __restrict__ pos_out, float4* __restrict__ vel_out, const u64m* __restrict__ masks,
+    const uint32_t* __restrict__ key_s, const u64* __restrict__ srcs, Collide3 K, const float4* __restrict__ st) {
+    __shared__ float4 s_buf[TILE3_FORCE_LDS];
+    __shared__ uint32_t s_red[24];
+    force3_body<MODE, COLLIDE, true>(P, pos_s, vel_s, pred, cs, pos_out, vel_out, masks, key_s, srcs, s_buf, s_red, K, st);
 }
 
 __global__ __launch_bounds__(B3) void k3_export(uint32_t n, const float4* __restrict__ pos, const float4* __restrict__ pred,
@@ -838,9 +983,23 @@ void launch3_density(hipStream_t st, const Params3& P, const Arrays3& A, bool to
     else hipLaunchKernelGGL(k3_density<0>, grid, block, 0, st, P, A.pred, A.cs, A.vel_s, A.masks, A.key);
 }
 
-// positions ping-pong: read the previous state (A.pos, source order) through the pairs, write the new one into A.pos_out
-void launch3_force(hipStream_t st, const Params3& P, const Arrays3& A, bool tol, hipEvent_t done, const Collide3* K) {
+// after launch3_density (pred.w, the masks), before launch3_force: writes st and nothing else
+void launch3_surface_tension(hipStream_t stream, const Params3& P, const Arrays3& A, const Tension3& T, float4* st) {
     const dim3 grid(xcd_grid3(blocks3(P.n), P.xcd_chunk_log2)), block(B3F);
+    hipLaunchKernelGGL(k3_surface_tension, grid, block, 0, stream, P, T, A.pred, A.cs, A.masks, A.key, st);
+}
+
+// positions ping-pong: read the previous state (A.pos, source order) through the pairs, write the new one into A.pos_out
+void launch3_force(hipStream_t st, const Params3& P, const Arrays3& A, bool tol, hipEvent_t done, const Collide3* K, const float4* stf) {
+    const dim3 grid(xcd_grid3(blocks3(P.n), P.xcd_chunk_log2)), block(B3F);
+    if (stf) {
+        const Collide3 K0 = K ? *K : Collide3{};
+#define FS3_LAUNCH_ST(MODE, COLLIDE) hipExtLaunchKernelGGL((k3_force_st<MODE, COLLIDE>), grid, block, 0, st, nullptr, done, 0, P, A.pos, A.vel_s, A.pred, A.cs, A.pos_out, A.vel, A.masks, A.key, A.pairs, K0, stf)
+        if (K) { if (tol) FS3_LAUNCH_ST(2, true); else FS3_LAUNCH_ST(0, true); }
+        else { if (tol) FS3_LAUNCH_ST(2, false); else FS3_LAUNCH_ST(0, false); }
+#undef FS3_LAUNCH_ST
+        return;
+    }
     if (K) {
         if (tol) hipExtLaunchKernelGGL(k3_force_collide<2>, grid, block, 0, st, nullptr, done, 0, P, A.pos, A.vel_s, A.pred, A.cs, A.pos_out, A.vel, A.masks, A.key, A.pairs, *K);
         else hipExtLaunchKernelGGL(k3_force_collide<0>, grid, block, 0, st, nullptr, done, 0, P, A.pos, A.vel_s, A.pred, A.cs, A.pos_out, A.vel, A.masks, A.key, A.pairs, *K);

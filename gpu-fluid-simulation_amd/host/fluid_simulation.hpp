@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/fluidsim.h"
@@ -246,6 +247,20 @@ public:
         check(fs3_collider_dims(h_, &w, &h, &d));
         std::vector<fs_vec3> v((size_t)w * h * d);
         if (!v.empty()) check(fs3_collider_download(h_, v.data(), v.size()));
+        return v;
+    }
+    // 3D surface tension: colour-field CSF with coefficient sigma and threshold tau, for the ticks enqueued afterwards.
+    void set_surface_tension(float coefficient, float threshold = 0.0f) { check(fs3_set_surface_tension(h_, 1, coefficient, threshold)); }
+    void clear_surface_tension() { check(fs3_set_surface_tension(h_, 0, 0.0f, 0.0f)); }
+    bool surface_tension_enabled() const { return fs3_surface_tension_enabled(h_) != 0; }
+    std::pair<float, float> surface_tension_params() const {      // (coefficient, threshold); throws when the feature is off
+        float c = 0.0f, t = 0.0f;
+        check(fs3_surface_tension_params(h_, &c, &t));
+        return {c, t};
+    }
+    std::vector<fs_vec3> surface_tension_forces() {               // the last step's force per particle, download order
+        std::vector<fs_vec3> v(particle_count());
+        check(fs3_download_surface_tension(h_, v.data(), v.size()));
         return v;
     }
     fs_sim3* handle() { return h_; }

@@ -245,6 +245,10 @@ extern "C" {
     fn fs3_collider_clear(sim: *mut fs_sim3) -> c_int;
     fn fs3_collider_dims(sim: *const fs_sim3, w: *mut u32, h: *mut u32, d: *mut u32) -> c_int;
     fn fs3_collider_download(sim: *mut fs_sim3, dst: *mut Vec3, n: usize) -> c_int;
+    fn fs3_set_surface_tension(sim: *mut fs_sim3, enable: c_int, coefficient: f32, threshold: f32) -> c_int;
+    fn fs3_surface_tension_enabled(sim: *const fs_sim3) -> c_int;
+    fn fs3_surface_tension_params(sim: *const fs_sim3, coefficient: *mut f32, threshold: *mut f32) -> c_int;
+    fn fs3_download_surface_tension(sim: *mut fs_sim3, dst: *mut Vec3, n: usize) -> c_int;
     // ResizableBuffer<T> (src/buffer.rs)
     fn fs_buffer_create(device: c_int, elem_size: usize, len: usize, name: *const c_char, out: *mut *mut fs_buffer) -> c_int;
     fn fs_buffer_resize(buf: *mut fs_buffer, new_cap: usize, resized: *mut c_int) -> c_int;
@@ -663,6 +667,22 @@ impl FluidSimulation3D {
         let mut v = vec![Vec3::default(); w as usize * h as usize * d as usize];
         if !v.is_empty() { check(unsafe { fs3_collider_download(self.raw, v.as_mut_ptr(), v.len()) }); }
         v
+    }
+    /// Build extension: 3D surface tension (include/fluidsim.h), colour-field CSF with coefficient sigma and threshold tau,
+    /// for the ticks enqueued afterwards.
+    pub fn set_surface_tension(&mut self, coefficient: f32, threshold: f32) { check(unsafe { fs3_set_surface_tension(self.raw, 1, coefficient, threshold) }); }
+    pub fn clear_surface_tension(&mut self) { check(unsafe { fs3_set_surface_tension(self.raw, 0, 0.0, 0.0) }); }
+    pub fn surface_tension_enabled(&self) -> bool { unsafe { fs3_surface_tension_enabled(self.raw) != 0 } }
+    /// (coefficient, threshold) in use, None when the feature is off.
+    pub fn surface_tension_params(&self) -> Option<(f32, f32)> {
+        if !self.surface_tension_enabled() { return None; }
+        let (mut c, mut t) = (0.0f32, 0.0f32);
+        check(unsafe { fs3_surface_tension_params(self.raw, &mut c, &mut t) }); Some((c, t))
+    }
+    /// The last step's surface-tension force per particle, in `download_particles` order.
+    pub fn surface_tension_forces(&mut self) -> Vec<Vec3> {
+        let mut v = vec![Vec3::default(); self.particle_count() as usize];
+        check(unsafe { fs3_download_surface_tension(self.raw, v.as_mut_ptr(), v.len()) }); v
     }
     pub fn stream(&self) -> *mut c_void { unsafe { fs3_stream(self.raw) } }
 }

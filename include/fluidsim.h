@@ -780,6 +780,41 @@ fs_status fs3_collider_clear(fs_sim3* sim);
 fs_status fs3_collider_dims(const fs_sim3* sim, uint32_t* w, uint32_t* h, uint32_t* d);      /* 0,0,0 when none */
 fs_status fs3_collider_download(fs_sim3* sim, fs_vec3* dst, size_t n);                       /* n == w*h*d; FS_ERR_INVALID when none */
 
+/* ------------------------------------------------ 3D surface tension (build extension, opt-in) */
+/* The 3D form of the 2D step's opt-in surface tension above: a colour-field continuum-surface-force pass (Mueller, Charypar &
+ * Gross 2003, §4.4) with the 3D poly6 kernel of the 3D step, W = C (h^2 - r^2)^3, C = 315/(64 pi h^9).  Enabled, every step runs
+ * the pass after its density pass and before its force pass, and the integrate step adds its force:
+ *     acc.a = (fp.a + fv.a * viscosity_coefficient) + st.a
+ * (the division by rho_i, gravity, the NaN reset, the speed clamp, the walls and the collider operator follow unchanged).
+ * fs3_tick_settings has no surface-tension knobs: sigma (coefficient) and tau (threshold) come from fs3_set_surface_tension.
+ *
+ * For sorted slot i with predicted position x, over the neighbours j the density pass visits (27 cells, z outer, then y, x inner,
+ * ascending slots inside a cell, cells outside the grid skipped, i itself included), in f32 without contraction, `/` and sqrt
+ * correctly rounded, all sums starting at +0:
+ *     ox = q_j.x - x.x; oy = q_j.y - x.y; oz = q_j.z - x.z;  r2 = ox*ox + oy*oy + oz*oz;  skipped when r2 > h2
+ *     d = h2 - r2;  w = m / rho_j                      (rho_j: this step's clamped density; m: the tick's mass)
+ *     k = (Cg * d) * d;   n.a += w * (k * o.a)          Cg = 6.0f * poly6 (poly6 = C as the step computes it on the host)
+ *     lk = (Cg * d) * ((7.0f * r2) - h2x3);  L += w * lk   h2x3 = 3.0f * h2
+ *     nl = sqrt((n.x*n.x + n.y*n.y) + n.z*n.z)
+ *     st = (nl > tau && nl > 0) ? s * n with s = (-sigma * L) / nl : 0
+ * Bit-exact in FS_MATH_IEEE.  FS_MATH_TOLERANCE handles run the same IEEE pass on their own densities and keep their per-step
+ * contract.  Off by default: a handle that never enables it launches exactly the kernels it launched before, with the same
+ * arguments.  The pass's time falls inside the FS_PASS_FORCE interval of fs3_profile_read.  FS_ABI_VERSION is unchanged.  See
+ * DESIGN.md §19.
+ *
+ * fs3_set_surface_tension: takes effect for the steps enqueued after the call (no synchronisation: steps already in flight
+ * keep the values they were enqueued with).  The first enable allocates 16 B per particle.  enable == 0 ignores the two floats
+ * and returns the handle to the launches of a handle that never enabled it.  FS_ERR_INVALID for a NULL handle, then for a NaN
+ * coefficient, then for a NaN threshold (infinities and negative values are taken as they are).
+ * fs3_surface_tension_params: the values in use; FS_ERR_INVALID for a NULL argument or when the feature is off.
+ * fs3_download_surface_tension: the last step's st, one fs_vec3 per particle in fs3_download_particles' slot order.  Blocking.
+ * FS_ERR_INVALID, in this order: a NULL argument; the feature is off; no step has been enqueued since it was last enabled;
+ * n != the particle count. */
+fs_status fs3_set_surface_tension(fs_sim3* sim, int enable, float coefficient, float threshold);
+int fs3_surface_tension_enabled(const fs_sim3* sim);
+fs_status fs3_surface_tension_params(const fs_sim3* sim, float* coefficient, float* threshold);
+fs_status fs3_download_surface_tension(fs_sim3* sim, fs_vec3* dst, size_t n);
+
 /* ------------------------------------------------------- ResizableBuffer */
 /* ResizableBuffer<T>::new (src/buffer.rs:27-43). */
 fs_status fs_buffer_create(int device, size_t elem_size, size_t len, const char* name, fs_buffer** out);

@@ -1,5 +1,7 @@
 """Render a few frames of the 3D dam break to PNG through the ray-marched G-buffer, headless:
   python tools/render_frames3d.py [n] [frame,frame,...] [outdir] [width] [height] [--box x0,y0,z0,x1,y1,z1[,voxels]]
+                                  [--surface-tension SIGMA[,TAU]]
+--surface-tension: the opt-in colour-field surface tension with coefficient SIGMA and threshold TAU (default 1.0).
 --box: a static obstacle, a box in world coordinates (+y is the floor) rasterised to a mask of `voxels` (default
 64) voxels along x and as many along y and z as keep them near cubes; the fluid flows around it, the box itself is not drawn."""
 import os, sys
@@ -10,6 +12,11 @@ box = None
 if "--box" in sys.argv:
     k = sys.argv.index("--box")
     box = [float(x) for x in sys.argv[k + 1].split(",")]
+    del sys.argv[k:k + 2]
+tension = None
+if "--surface-tension" in sys.argv:
+    k = sys.argv.index("--surface-tension")
+    tension = [float(x) for x in sys.argv[k + 1].split(",")]
     del sys.argv[k:k + 2]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 64 ** 3
 frames = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [1, 60, 150, 300]
@@ -25,6 +32,9 @@ if box is not None:
     shape = (w, max(1, round(w * sy / sx)), max(1, round(w * sz / sx)))
     sim.set_collider_mask(g.box_mask3d((sx, sy, sz), shape, box[0:3], box[3:6]))
     print("collider", sim.collider_dims, flush=True)
+if tension is not None:
+    sim.set_surface_tension(tension[0], tension[1] if len(tension) > 1 else 1.0)
+    print("surface tension", sim.surface_tension_params, flush=True)
 # gravity is +y: "up" is -y.  From in front of the -z wall, above the floor, looking at the middle of the tank.
 eye = (-0.15 * sx, -0.55 * sy, -0.5 * sz - 0.9 * sx)
 cam = g.look_at_camera(eye, (0.0, 0.15 * sy, 0.0), (0.0, -1.0, 0.0), np.radians(42.0), width, height)
