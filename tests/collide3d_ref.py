@@ -62,6 +62,15 @@ def apply_collider(records, field, size, damping):
     return out, int(hit.sum()), int(clamped.sum())
 
 
+def random_field(shape_whd, seed, fill=0.5, mag=0.15):
+    """[D, H, W, 3] with about `fill` of the voxels non-zero, components up to `mag`"""
+    w, h, d = shape_whd
+    rng = np.random.default_rng(seed)
+    f = rng.uniform(-mag, mag, size=(d, h, w, 3)).astype(f32)
+    f[rng.random((d, h, w)) >= fill] = 0
+    return f
+
+
 # ---- the producer -----------------------------------------------------------------------------------------------------
 def _argmin_first(cost, axis):
     """index of the first minimum along `axis` and the minimum: ties go to the smaller coordinate"""

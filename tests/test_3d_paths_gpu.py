@@ -72,24 +72,10 @@ def test_path_scene_tolerance_mode(fs, orc, name):
 
 
 # ---- 3. operand guards ------------------------------------------------------------------------------------------------
-def make_pair3(fs, orc, side, h=0.2, spacing=0.1, seed=21, vel=1.0, jitter=0.25, room=2.0, **tick_over):
-    """centred lattice (even side: the origin lies inside the fluid) in a roomy box, jittered, with velocities"""
-    n = side ** 3
-    ext = side * spacing
-    st = fs.Settings3(n, float(spacing), float(h), fs.Vec3(*[float(ext * room + 4 * h)] * 3))
-    kw = dict(delta=float(f32(1) / f32(120)), gravity=(0.3, 9.81, -0.2), mass=1.0, pressure_constant=50.0, rest_density=0.0,
-              damping_factor=0.1, viscosity_coefficient=25.0)
-    kw.update(tick_over)
-    tick = fs.TickSettings3(kw["delta"], fs.Vec3(*kw["gravity"]), kw["mass"], kw["pressure_constant"], kw["rest_density"],
-                            kw["damping_factor"], kw["viscosity_coefficient"])
+def make_pair3(fs, orc, side, **kw):
+    """the state of paths3d.pair3_state and an engine handle for it"""
+    ref, st, tick, p = paths3d.pair3_state(fs, orc, side, **kw)
     sim = fs.FluidSimulation3D(st, device=0)
-    ref = orc.OracleSim3D(st)
-    p = ref.particles()
-    if seed is not None:
-        rng = np.random.default_rng(seed)
-        p["position"] += rng.uniform(-jitter, jitter, size=(n, 3)).astype(f32) * f32(spacing)
-        p["velocity"] = rng.uniform(-vel, vel, size=(n, 3)).astype(f32)
-    p["predicted_position"] = p["position"]
     return sim, ref, st, tick, p
 
 
@@ -103,9 +89,7 @@ def run3(sim, ref, tick, p, steps, ctx):
     sim.close(); ref.close()
 
 
-GUARD_CASES = ["tiny_offsets", "tiny_velocities", "huge_velocities", "inf_velocity", "zero_aligned", "huge_pressure",
-               "near_zero_coordinates", "small_operands_on_the_fast_path", "density_across_2p20", "pressure_across_2p39",
-               "distance_across_2m20", "unsafe_next_to_safe"]
+GUARD_CASES = paths3d.GUARD_CASES
 
 
 @pytest.mark.parametrize("case", GUARD_CASES)
@@ -113,63 +97,12 @@ def test_3d_force_quotient_guards(fs, orc, case):
     """Operands on both sides of every guard of the shared-reciprocal quotients (kernels_3d.hip: lo_safe / 2^59 in k3_reorder,
     FS_RCP_HI / FS_PRESSURE_HI in k3_density, FS_SQRT_LO / num_lo_ok3 / the 2^-20 branch in terms3*): whatever the
     classification decides, the step equals the oracle bit for bit, 3 steps."""
-    over = {}
-    if case == "huge_pressure":
-        over = dict(pressure_constant=3.0e33)
-    elif case == "density_across_2p20":            # interior ~1.5e6 > 2^20 > surface and corner densities
-        over = dict(mass=1500.0)
-    elif case == "pressure_across_2p39":           # |k rho| from ~1e11 at the corners to ~1e12 inside: 2^39 = 5.5e11 between
-        over = dict(pressure_constant=1.0e9)
-    sim, ref, st, tick, p = make_pair3(fs, orc, 12, **over)
-    n = p.shape[0]
-    near = np.argsort(np.abs(p["position"]).max(axis=1))[:16]            # the particles around the origin
-    if case == "tiny_offsets":                     # |o| from 2^-149 to ~2^-20 around the origin (r2 below 2^-40 too)
-        p["position"][near[0]] = 0
-        for k, d in enumerate([1e-45, 1e-40, 1e-30, 1e-19, 3e-13, 1e-7]):
-            p["position"][near[1 + k]] = f32(d) * np.array([1, 0 if k % 2 else 1, 0 if k % 3 else -1], f32)
-    elif case == "tiny_velocities":                # differences far below 2^-76 and denormal
-        p["velocity"][:] = 0
-        p["velocity"][::3] = (1e-30, -2e-38, 3e-31)
-        p["velocity"][1::3] = (3e-30, 1e-45, -1e-44)
-    elif case == "huge_velocities":                # differences above 2^60 (clamped only after the force pass)
-        p["velocity"][50] = (3e30, -3e30, 1e29)
-        p["velocity"][51] = (-2e25, 1e19, 7e18)     # 2^59 = 5.8e17 < 7e18
-        p["velocity"][52] = (5e17, -5.7e17, 5.9e17)  # around 2^59 itself
-    elif case == "inf_velocity":
-        p["velocity"][60] = (np.inf, 0.0, 1.0)
-        p["velocity"][61] = (-np.inf, np.nan, 0.0)
-        p["velocity"][62] = (0.0, 1.0, np.inf)
-    elif case == "zero_aligned":                   # exact zeros in every numerator: the lattice, equal velocities
-        p["position"] = orc.OracleSim3D(st).particles()["position"]
-        p["velocity"][:] = (0.25, -0.5, 0.125)
-    elif case == "small_operands_on_the_fast_path":     # numerators between 2^-76 and 2^-60: exact quotients by reciprocal
-        tiny = f32(2.0 ** -53)
-        j = np.arange(n, dtype=f32) % 7
-        p["velocity"][:, 0] = tiny * (f32(1) + j * f32(2.0 ** -22))
-        p["velocity"][:, 1] = tiny * (f32(3) - j * f32(2.0 ** -21))
-        p["velocity"][:, 2] = tiny * (f32(2) + j * f32(2.0 ** -20))
-        col = np.nonzero(np.abs(p["position"][:, 2]) < 0.1)[0][:40]      # a slab moved onto z ~ 2^-53
-        p["position"][col, 2] = tiny * (f32(1) + (np.arange(len(col)) % 5).astype(f32) * f32(2.0 ** -22))
-    elif case == "near_zero_coordinates":
-        rng = np.random.default_rng(5)
-        p["position"][near] = (rng.standard_normal((16, 3)) * 1e-22).astype(f32)
-    elif case == "distance_across_2m20":           # pair distances 2^-21 .. 2^-19, r2 on both sides of 2^-40 and at it
-        e = f32(2.0 ** -20)
-        p["position"][near[0]] = 0
-        for k, d in enumerate([e / 2, np.nextafter(e, f32(0)), e, np.nextafter(e, f32(1)), e * 2]):
-            q = np.zeros(3, f32); q[k % 3] = d if k % 2 else -d
-            p["position"][near[1 + k]] = q
-        p["position"][near[6]] = (e * f32(0.6), e * f32(0.8), 0)         # |o|^2 rounds next to 2^-40 off the axes
-    elif case == "unsafe_next_to_safe":            # the sign of vel_s.w is per particle, the decision per pair
-        p["velocity"][near[0]] = (1e-30, 0.5, -0.5)                      # one unsafe component, safe neighbours all round
-        p["velocity"][near[3]] = (0.5, 2e-17, 0.5)                       # just below 2^-53 = 1.1e-16
-        p["velocity"][near[5]] = (0.5, 0.5, 1.2e-16)                     # just above it: safe
-        p["position"][near[7], 1] = 3e-20                                # an unsafe coordinate
-        p["velocity"][near[9]] = (np.nan, 0.0, 0.0)
+    sim, ref, st, tick, p = make_pair3(fs, orc, 12, **paths3d.guard_overrides(case))
+    p = paths3d.guard_state(orc, st, p, case)
     run3(sim, ref, tick, p, 3, f"guards3d/{case}")
 
 
-@pytest.mark.parametrize("h", [0.05, 0.1, 0.2, 0.33, 0.5, 1.0])
+@pytest.mark.parametrize("h", paths3d.RADII)
 def test_3d_smoothing_radii_with_the_shared_path_on_and_off(fs, orc, h):
     """h * spiky = 15 / (pi h^4) <= 2^19 enables the shared-reciprocal path: on for h >= 0.1, off for h = 0.05 (7.6e5)"""
     hspiky = 15.0 / (3.14159265359 * h ** 4)
@@ -297,50 +230,16 @@ def test_3d_random_configurations_tolerance_mode(fs, orc, case):
 
 
 # ---- 5. walls, grid edges ---------------------------------------------------------------------------------------------
-def _box(fs, n, size, h=0.2):
-    return fs.Settings3(n, 0.1, h, fs.Vec3(*[float(s) for s in size]))
-
-
-def _tick(fs, **over):
-    kw = dict(delta=float(f32(1) / f32(120)), gravity=(0.3, 9.81, -0.2), mass=1.0, pressure_constant=50.0, rest_density=1.0,
-              damping_factor=0.3, viscosity_coefficient=5.0)
-    kw.update(over)
-    return fs.TickSettings3(kw["delta"], fs.Vec3(*kw["gravity"]), kw["mass"], kw["pressure_constant"], kw["rest_density"],
-                            kw["damping_factor"], kw["viscosity_coefficient"])
+_box, _tick = paths3d.box_settings, paths3d.box_tick
 
 
 @pytest.mark.parametrize("exact_multiple", [True, False])
 def test_3d_particles_on_every_face_edge_and_corner(fs, orc, exact_multiple):
     """uploads exactly at +b and -b: 6 faces, 12 edges, 8 corners (26 sign patterns), far outside the box, and the rest of
     the particles near them; with sides that are exact multiples of h cell gw - 1 is reached only by these particles"""
-    size = (2.0, 1.5, 1.25) if exact_multiple else (2.1, 1.55, 1.27)      # h = 0.25: 8 x 6 x 5 cells exactly
-    n = 8 ** 3
-    st = _box(fs, n, size, h=0.25)
-    tick = _tick(fs)
+    st, tick, p = paths3d.faces_state(fs, orc, exact_multiple)
     sim = fs.FluidSimulation3D(st, device=0)
     ref = orc.OracleSim3D(st)
-    b = np.array([f32(s) * f32(0.5) for s in size], dtype=f32)
-    rng = np.random.default_rng(11)
-    p = ref.particles()
-    signs = [(x, y, z) for x in (-1, 0, 1) for y in (-1, 0, 1) for z in (-1, 0, 1) if (x, y, z) != (0, 0, 0)]
-    k = 0
-    for rep in range(4):                           # each pattern: on the wall; twice near it (neighbours); far outside
-        for sg in signs:
-            s = np.array(sg, dtype=f32)
-            inner = rng.uniform(-0.5, 0.5, size=3).astype(f32) * b
-            on = np.where(s != 0, s * b, inner).astype(f32)
-            if rep == 0:
-                p["position"][k] = on
-            elif rep == 3:
-                p["position"][k] = np.where(s != 0, s * b * f32(1e3 if k % 2 else 1.0001), inner)
-            else:
-                p["position"][k] = np.where(s != 0, s * (b - f32(0.07) * rng.uniform(0, 1, 3).astype(f32)), inner)
-            k += 1
-    p["velocity"] = rng.uniform(-1, 1, size=(n, 3)).astype(f32)
-    for j, sg in enumerate(signs):                 # the particles on the walls move outwards: predicted exactly at +-b
-        s = np.array(sg, dtype=f32)
-        p["velocity"][j] = np.where(s != 0, s * np.abs(p["velocity"][j]), p["velocity"][j])
-    p["predicted_position"] = p["position"]
     ref.set_particles(p); sim.upload_particles(p)
     gw, gh, gd = ref.grid_dims
     for s in range(4):
@@ -354,15 +253,12 @@ def test_3d_particles_on_every_face_edge_and_corner(fs, orc, exact_multiple):
     sim.close(); ref.close()
 
 
-@pytest.mark.parametrize("axis,sign", [(a, s) for a in range(3) for s in (-1, 1)])
+@pytest.mark.parametrize("axis,sign", paths3d.WALLS)
 def test_3d_driven_into_each_wall(fs, orc, axis, sign):
     """gravity and initial velocity towards one wall: the block piles up on it (clamp, damped bounce, cell gw - 1 / 1)"""
-    g = [0.0, 0.0, 0.0]; g[axis] = 60.0 * sign
-    sim, ref, st, tick, p = make_pair3(fs, orc, 8, seed=axis * 2 + (sign > 0), room=1.3, gravity=tuple(g), rest_density=1.0,
-                                       damping_factor=0.5)
-    p["velocity"][:, axis] += f32(25.0 * sign)
+    ref, st, tick, p = paths3d.wall_state(fs, orc, axis, sign)
+    sim = fs.FluidSimulation3D(st, device=0)
     b = f32(st.size.x) * f32(0.5)
-    p["predicted_position"] = p["position"]
     ref.set_particles(p); sim.upload_particles(p)
     hit = False
     with np.errstate(all="ignore"):
@@ -375,19 +271,12 @@ def test_3d_driven_into_each_wall(fs, orc, axis, sign):
     sim.close(); ref.close()
 
 
-@pytest.mark.parametrize("size", [(0.15, 0.15, 0.15), (0.15, 2.0, 1.0), (1.0, 0.1, 2.0), (2.0, 1.0, 0.19), (0.2, 0.2, 3.0)])
+@pytest.mark.parametrize("size", paths3d.THIN_SIZES)
 def test_3d_one_cell_and_thin_grids(fs, orc, size):
     """a 3 x 3 x 3 grid (the whole domain one cell) and grids three cells thick along one axis"""
-    n = 6 ** 3
-    st = _box(fs, n, size)
-    tick = _tick(fs, pressure_constant=5.0)
+    st, tick, p = paths3d.thin_state(fs, orc, size)
     sim = fs.FluidSimulation3D(st, device=0)
     ref = orc.OracleSim3D(st)
     want_dims = tuple(int(np.ceil(f32(s) / f32(0.2))) + 2 for s in size)
     assert sim.grid_dims == ref.grid_dims == want_dims
-    rng = np.random.default_rng(int(sum(size) * 100))
-    p = ref.particles()
-    half = np.array(size, dtype=f32) * f32(0.5)
-    p["position"] = (rng.uniform(-1, 1, size=(n, 3)) * half).astype(f32)
-    p["velocity"] = rng.uniform(-0.5, 0.5, size=(n, 3)).astype(f32)
     run3(sim, ref, tick, p, 3, f"thin {size}")

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from tests import collide3d_ref as R
+from tests import features3d as F
 
 f32 = np.float32
 SIZE = (3.2, 2.0, 1.8)
@@ -97,3 +98,56 @@ def test_library_exports_and_binds_the_collider_calls(fs):
     assert lib.fs3_collider_clear(None) == fs._abi.FS_ERR_INVALID
     assert lib.fs3_collider_upload(None, None, 0, 0, 0) == fs._abi.FS_ERR_INVALID
     assert lib.fs_abi_version() == 2
+
+
+# ---- the hard-input cases of test_3d_features_hard_inputs_gpu.py, on the checker alone -------------------------------------
+COLLIDER_IDS = [c for c in F.CASE_IDS if c.endswith("+collide") or c.split("/")[0] in ("random", "edge")]
+
+
+@pytest.mark.parametrize("cid", COLLIDER_IDS)
+def test_hard_input_cases_push_and_reclamp(fs, orc, cid):
+    """what the GPU file relies on, asked of the checker alone: every case with a collider pushes particles, the block driven into
+    a + wall is clamped again after its push, thin and one-cell boxes run with a one-voxel field as well, and the tolerance-mode
+    case leaves out at most 1 % of its particles"""
+    case = F.case_by_id(fs, orc, cid)
+    case.run()
+    print(F.describe(case))
+    fig = case.figures
+    assert case.field is not None and case.field.any() and np.isfinite(case.field).all()
+    assert fig["pushed"] > 0
+    if cid.startswith("edge/wall/") and cid.endswith("+"):
+        assert fig["reclamped"] > 0
+    if cid.endswith("one_voxel"):
+        assert case.field.shape == (1, 1, 1, 3)
+    elif not cid.startswith("tol/"):
+        assert case.field.shape[:3] == F.FIELD_SHAPE[::-1]
+    if cid.startswith("tol/"):
+        assert fig["left_out"] <= 0.01 * fig["n"]
+
+
+def test_thin_boxes_have_both_fields():
+    thin = [c for c in F.EDGE_CASES if c.startswith("thin/")]
+    assert len(thin) == 10 and sum(c.endswith("one_voxel") for c in thin) == 5
+
+
+def test_positions_on_plus_b_reach_the_last_voxel_only_through_the_clamp(fs, orc):
+    """in step 1 some particle stands exactly on +b of every axis before C: its quotient is exactly 1, the unclamped index is the
+    extent itself, and the voxel the clamp selects pushes"""
+    case = F.guard_case(fs, orc, "positions_on_plus_b", "st+collide")
+    chk = case.checker()
+    _, pre, pushed, _, _ = case.checker_step(chk)
+    chk.close()
+    D, H, W = case.field.shape[:3]
+    assert case.field[-1].any(-1).all() and case.field[:, -1].any(-1).all() and case.field[:, :, -1].any(-1).all()
+    hit = 0
+    for a, wa in enumerate((W, H, D)):
+        size = f32(case.size[a])
+        b = size * f32(0.5)
+        on = pre["position"][:, a] == b
+        assert on.any(), f"no particle on +b of axis {a}"
+        x = ((pre["position"][on, a] + b) / size) * f32(wa)
+        assert (R.u32_sat(x) == wa).all(), "the quotient of a particle on +b must be exactly the extent"
+        lo = pre["position"][:, a] == -b
+        assert lo.any() and (R.u32_sat(((pre["position"][lo, a] + b) / size) * f32(wa)) == 0).all()
+        hit += int(on.sum())
+    assert pushed >= hit > 0

@@ -28,13 +28,7 @@ def _size(st):
     return (st.size.x, st.size.y, st.size.z)
 
 
-def _random_field(shape_whd, seed, fill=0.5, mag=0.15):
-    """[D, H, W, 3] with about `fill` of the voxels non-zero, components up to `mag`"""
-    w, h, d = shape_whd
-    rng = np.random.default_rng(seed)
-    f = rng.uniform(-mag, mag, size=(d, h, w, 3)).astype(f32)
-    f[rng.random((d, h, w)) >= fill] = 0
-    return f
+_random_field = R.random_field
 
 
 # ---- 1. against the oracle --------------------------------------------------------------------------------------------

@@ -8,12 +8,13 @@ import numpy as np
 import pytest
 
 import paths3d
+from tests import features3d as F
 from tests import st3d_ref as R
 
 f32 = np.float32
 # the statement's constants as this file's float64 model uses them; test_constants_match_the_sources reads them from the sources
 GRAD_C, LAP_R2, LAP_H2 = 6.0, 7.0, 3.0
-SCENE_ST = (0.02, 0.5)             # (sigma, tau) of the path scenes, shared with test_surface_tension3d_gpu.py
+SCENE_ST = F.SCENE_ST               # (sigma, tau) of the path scenes, shared with test_surface_tension3d_gpu.py
 
 
 def _same_records(a, b, ctx):
@@ -140,6 +141,38 @@ def test_laplacian_is_the_finite_difference_of_the_kernel():
 
 
 # ---- 3. the checker's f32 pass against a float64 sum over all pairs -------------------------------------------------------
+def _pass_against_float64(chk, rec, mass, h):
+    """the checker's n and L on the state its last step left against the float64 sum over all pairs, per particle under the bound
+    of an f32 sum of K terms, (K + 8) 2^-24 sum|term|: (n, L, worst error as a share of the bound).  The f64 sum takes the f32
+    inputs and the f32 constants (Cg, h2, 3 h2) as they are.  The state must be finite."""
+    n = rec.shape[0]
+    assert np.isfinite(rec["predicted_position"]).all() and np.isfinite(rec["density"]).all()
+    poly6 = f32(chk.constants()[0])
+    cg, h2 = f32(GRAD_C) * poly6, f32(h) * f32(h)
+    h2x3 = f32(LAP_H2) * h2
+    nv, Lv, _ = chk.surface_tension_pass(1.0, 0.0)
+    q = rec["predicted_position"].astype(np.float64)
+    w = float(f32(mass)) / rec["density"].astype(np.float64)
+    u = 2.0 ** -24
+    worst = 0.0
+    for i in range(n):
+        o = q - q[i]
+        r2 = (o * o).sum(1)
+        near = r2 <= float(h2)
+        o, r2, wj = o[near], r2[near], w[near]
+        d = float(h2) - r2
+        tn = (wj * (float(cg) * d * d))[:, None] * o
+        tl = wj * (float(cg) * d * (LAP_R2 * r2 - float(h2x3)))
+        K = int(near.sum())
+        assert K >= 1
+        bound_n = (K + 8) * u * np.abs(tn).sum(0)
+        bound_l = (K + 8) * u * np.abs(tl).sum()
+        en, el = np.abs(nv[i].astype(np.float64) - tn.sum(0)), abs(float(Lv[i]) - tl.sum())
+        assert (en <= bound_n).all() and el <= bound_l, (i, K, en, bound_n, el, bound_l)
+        worst = max(worst, float((en / np.maximum(bound_n, 1e-300)).max()), el / max(bound_l, 1e-300))
+    return nv, Lv, worst
+
+
 def test_checker_pass_against_float64_sum_over_all_pairs(fs):
     """13^3 = 2197 random particles in a 1.6^3 box, h = 0.2 (about 18 in radius).  Per component of n and for L:
     |f32 - f64| <= (K + 8) 2^-24 sum|term|, K = the particle's in-radius count: K - 1 roundings of the running sum and at most
@@ -159,29 +192,7 @@ def test_checker_pass_against_float64_sum_over_all_pairs(fs):
     chk.step(tick, None)                                   # sorts, leaves this state's densities (nothing moves: no force, no speed)
     rec = chk.particles()
     assert np.array_equal(np.sort(rec["predicted_position"], axis=0), np.sort(p["position"], axis=0))
-    poly6 = f32(chk.constants()[0])
-    cg, h2 = f32(GRAD_C) * poly6, f32(h) * f32(h)
-    h2x3 = f32(LAP_H2) * h2
-    nv, Lv, _ = chk.surface_tension_pass(1.0, 0.0)
-    q = rec["predicted_position"].astype(np.float64)
-    w = float(tick.mass) / rec["density"].astype(np.float64)
-    u = 2.0 ** -24
-    worst = 0.0
-    for i in range(n):
-        o = q - q[i]
-        r2 = (o * o).sum(1)
-        near = r2 <= float(h2)
-        o, r2, wj = o[near], r2[near], w[near]
-        d = float(h2) - r2
-        tn = (wj * (float(cg) * d * d))[:, None] * o
-        tl = wj * (float(cg) * d * (LAP_R2 * r2 - float(h2x3)))
-        K = int(near.sum())
-        assert K >= 1
-        bound_n = (K + 8) * u * np.abs(tn).sum(0)
-        bound_l = (K + 8) * u * np.abs(tl).sum()
-        en, el = np.abs(nv[i].astype(np.float64) - tn.sum(0)), abs(float(Lv[i]) - tl.sum())
-        assert (en <= bound_n).all() and el <= bound_l, (i, K, en, bound_n, el, bound_l)
-        worst = max(worst, float((en / np.maximum(bound_n, 1e-300)).max()), el / max(bound_l, 1e-300))
+    nv, Lv, worst = _pass_against_float64(chk, rec, tick.mass, h)
     print(f"[st3d] f32 pass against f64: worst error {worst:.3f} of the bound")
     # the threshold: both branches, and st is the statement's closed form of the checker's own n and L
     nl = np.sqrt((nv[:, 0] * nv[:, 0] + nv[:, 1] * nv[:, 1]) + nv[:, 2] * nv[:, 2])
@@ -196,7 +207,71 @@ def test_checker_pass_against_float64_sum_over_all_pairs(fs):
     chk.close()
 
 
-# ---- 4. source pins -------------------------------------------------------------------------------------------------------
+# ---- 4. the hard-input cases of test_3d_features_hard_inputs_gpu.py, on the checker alone ---------------------------------
+NO_FORCE_IN_STEP_1 = ("guard/nan_next_to_everyone/st", "guard/nan_next_to_everyone/st+collide")
+# SCENE_ST's threshold is fixed (0.5, shared with the IEEE scene tests): in this scene the over-full cells leave only two of the 174
+# particles with a colour gradient at or below it.  Both branches are still taken; the 1 % rule cannot be met.
+TOL_UNDER_ONE_PERCENT = ("tol/mixed_wave",)
+
+
+@pytest.mark.parametrize("cid", F.CASE_IDS)
+def test_hard_input_cases_exercise_the_pass(fs, orc, cid):
+    """what the GPU file relies on, asked of the checker alone: no case is empty, the pass produces a force, both branches of the
+    threshold are taken, and where at least 100 particles have a colour gradient the threshold leaves at least 1 % of the
+    particles on each side (tau is chosen for that; the tolerance cases keep SCENE_ST's fixed tau and meet it too, except
+    TOL_UNDER_ONE_PERCENT).  In the tolerance cases the threshold must also sit in a gap of the |n| values (1e-3 relative, a
+    hundred times the mode's density contract), so that no particle changes its branch.  The exception of NO_FORCE_IN_STEP_1:
+    every |n| of its first step is a NaN, which takes the not-above branch (all of step 1), and with tau = 0 every
+    particle of steps 2 and 3 takes the other."""
+    case = F.case_by_id(fs, orc, cid)
+    run = case.run()
+    print(F.describe(case))
+    fig = case.figures
+    assert len(run) == case.steps >= 1 and fig["n"] == case.start.shape[0] >= 8
+    assert np.isfinite(case.sigma) and case.sigma > 0 and np.isfinite(case.tau)
+    forces = [bool(np.any(st != 0)) for _, st in run]
+    if cid in NO_FORCE_IN_STEP_1:       # every |n| is a NaN in step 1 (see features3d._nan_next_to_everyone): admitted, so no force
+        assert not forces[0] and all(forces[1:]) and np.all(run[0][0]["density"] == f32(0.1))
+        return
+    assert forces[0], "the pass produced no force in step 1"
+    assert fig["above"] > 0 and fig["below"] > 0, fig
+    if fig["with_n"] >= 100 and cid not in TOL_UNDER_ONE_PERCENT:
+        assert fig["above"] >= fig["n"] / 100 and fig["below"] >= fig["n"] / 100, fig
+    if cid.startswith("tol/"):
+        assert fig["tau_gap"] > 1e-3 and (fig["sensitivity"] <= 1.0 or fig["st_dv_max"] < 1.0), fig
+        return
+    # sigma puts the pass at the order of the step's own velocity change, wherever that is finite
+    if fig["own_dv"] > 0:
+        assert 0.1 <= fig["st_dv"] / fig["own_dv"] <= 10.0, fig
+
+
+def test_nan_and_infinite_operands_reach_the_pass(fs, orc):
+    """inf_velocity, huge_pressure and unsafe_next_to_safe carry NaN predicted positions into the pass, mass_tiny holds every
+    density at the floor in step 1, density_across_2p20 has densities on both sides of 2^20"""
+    for name in ("inf_velocity", "huge_pressure", "unsafe_next_to_safe"):
+        run = F.guard_case(fs, orc, name, "st+collide").run()
+        assert any(np.isnan(rec["predicted_position"]).any() for rec, _ in run), name
+    rec = F.guard_case(fs, orc, "mass_tiny", "st").run()[0][0]
+    case = F.guard_case(fs, orc, "mass_tiny", "st")
+    assert np.all(rec["density"] == f32(0.1)) and 0 < f32(case.tick.mass) / f32(0.1) < 1e-2
+    rec = F.guard_case(fs, orc, "density_across_2p20", "st").run()[0][0]
+    assert rec["density"].min() < 2 ** 20 < rec["density"].max()
+
+
+@pytest.mark.parametrize("name", ["density_across_2p20", "mass_tiny"])
+def test_checker_pass_against_float64_at_extreme_mass_over_density(fs, orc, name):
+    """the same float64 evaluation at m / rho = 1500 / (5e5 .. 2e6) and at m / 0.1 with m ~ 4e-5: a mistake in the weight that
+    checker and kernel share (1 / rho for m / rho: a factor 1500, or 4e-5) cannot pass"""
+    case = F.guard_case(fs, orc, name, "st")
+    chk = case.checker()
+    chk.step(case.tick, None)
+    rec = chk.particles()
+    _, _, worst = _pass_against_float64(chk, rec, case.tick.mass, case.h)
+    print(f"[st3d] {name}: f32 pass against f64: worst error {worst:.3f} of the bound")
+    chk.close()
+
+
+# ---- 5. source pins -------------------------------------------------------------------------------------------------------
 def _header_text():
     import os
     with open(os.path.join(os.path.dirname(paths3d.__file__), "..", "include", "fluidsim.h")) as fh:
