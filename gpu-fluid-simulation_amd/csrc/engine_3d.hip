@@ -1,5 +1,5 @@
 // engine_3d.hip — host side of the 3D extension of the step: the handle and the fs3_* C ABI (kernels and launchers:
-// kernels_3d.hip, fs_3d.h).  From the 2D engine (engine.h): the device check, the create-time proofs, the owners and the
+// kernels_3d.hip, kernels_density3d.hip, kernels_force3d.hip; fs_3d.h).  From the 2D engine (engine.h): the device check, the create-time proofs, the owners and the
 // sort policy.
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,5 @@
-// fs_3d.h — what the two files of the 3D step share (kernels_3d.hip: the kernels and their launchers, engine_3d.hip: the
-// handle and the fs3_* C ABI): the step parameters, the array set of the launchers, the launchers.  A header of its own:
+// fs_3d.h — what the files of the 3D step share (kernels_3d.hip, kernels_density3d.hip, kernels_force3d.hip: the kernels and
+// their launchers, engine_3d.hip: the handle and the fs3_* C ABI): the step parameters, the array set of the launchers, the launchers.  A header of its own:
 // fs_kernels.h stays the 2D launchers' list, and kernels_sort.hip takes the predict + cell-key expression from here.
 #pragma once
 #include "fs_kernels.h"

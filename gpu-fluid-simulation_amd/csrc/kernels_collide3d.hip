@@ -1,5 +1,5 @@
 // kernels_collide3d.hip — producer of the 3D collider (build extension): a w x h x d u8 voxel mask (> 128: solid,
-// the threshold of the 2D producer, src/main.rs:403-515) to the push field of the force pass's COLLIDE tail (kernels_3d.hip
+// the threshold of the 2D producer, src/main.rs:403-515) to the push field of the force pass's COLLIDE tail (kernels_force3d.hip
 // collide3) by an EXACT Euclidean distance transform in index space.  Three separable passes in u32 arithmetic, stated in
 // include/fluidsim.h "3D colliders"; the result is fully determined, ties included:
 //   k3c_pass_x  per row (j, k):    the free i' minimising |i - i'|

@@ -1,4 +1,4 @@
-"""CPU model of the path choice of the 3D density / force kernels (csrc/kernels_3d.hip), and the scenes built to reach
+"""CPU model of the path choice of the 3D density / force kernels (csrc/fs_sweep3.h, kernels_density3d.hip, kernels_force3d.hip), and the scenes built to reach
 every path.  Pure numpy.  The model restates, from the SORTED KEYS of a state alone:
 
   row3_key           id_lo = key + (oz*gh + oy)*gw - 1 (u32 wrap), no row when id_lo >= ncell, id_hi = min(id_lo + 3, ncell),

@@ -111,21 +111,36 @@ def test_first_and_last_has_lane_give_the_block_bounds():
 
 
 def test_model_constants_match_the_kernel_sources():
-    k3d = paths3d.source_text("kernels_3d.hip")
+    sweep = paths3d.source_text("fs_sweep3.h")          # what the sweep passes share; the passes themselves, and the rest of the step:
+    passes = {name: paths3d.source_text(name) for name in ("kernels_density3d.hip", "kernels_force3d.hip", "kernels_3d.hip")}
+    k3d = sweep + "".join(passes.values())
     kern = paths3d.source_text("fs_kernels.h")
     assert int(paths3d.parse_define(kern, "FS_PRED_SLACK")) == paths3d.FS_PRED_SLACK
-    assert int(paths3d.parse_define(k3d, "B3F")) == paths3d.B3F
-    assert int(paths3d.parse_define(k3d, "TILE3")) == paths3d.TILE3
+    assert int(paths3d.parse_define(sweep, "B3F")) == paths3d.B3F
+    assert int(paths3d.parse_define(sweep, "TILE3")) == paths3d.TILE3
+    assert k3d.count("#define B3F ") == 1 and k3d.count("#define TILE3 ") == 1
     assert "#ifndef B3F" not in k3d and "#ifndef TILE3" not in k3d            # plain constants: no other value is ever built
-    body = k3d[k3d.index("int plane_class("):]
+    body = sweep[sweep.index("int plane_class("):]
     body = body[:body.index("\n}")]
     assert "mx > 64u" in body and "mx > 128u" in body and "if (!fit) return 0;" in body
     assert paths3d.MASK64 == 64 and paths3d.MASK128 == 128
-    # both passes take their block bounds from the same call with the same tile (k3_density and force3_body).  It is written at
-    # both sites: a shared helper around "rows of plane p -> RowRanges, block_tile_bounds" gets the nine looked-up ranges by
-    # pointer and the compiler then keeps them in scratch (96 B in all four kernels; k3_density 72 -> 54 VGPRs, k3_force
-    # 128 -> 107 / 109), which the split must not do
-    assert k3d.count("block_tile_bounds<W3F>(R, s_red, blo, bhi, TILE3)") == 2
+    # every pass takes its block bounds and its plane class from ONE call each, with one tile: the plane driver's (fs_sweep3.h
+    # sweep3_planes), which k3_density, k3_surface_tension and force3_body call with their work as a force-inlined callable.  The
+    # nine looked-up ranges stay locals of the driver, which also indexes them: a helper around "rows of plane p -> RowRanges,
+    # block_tile_bounds" that gets them by pointer makes the compiler keep them in scratch (96 B in every kernel; k3_density
+    # 72 -> 54 VGPRs, k3_force 128 -> 107 / 109), which the driver does not (profiles/3d_sweep_split_resource_usage.txt)
+    assert k3d.count("block_tile_bounds<W3F>(") == 1 and sweep.count("block_tile_bounds<W3F>(R, s_red, blo, bhi, TILE3)") == 1
+    assert k3d.count("int plane_class(") == 1 and k3d.count("plane_class(R, fit)") == 1 and sweep.count("plane_class(R, fit)") == 1
+    driver = sweep[sweep.index("void sweep3_planes("):]
+    driver = driver[:driver.index("\n}")]
+    assert "block_tile_bounds<W3F>(R, s_red, blo, bhi, TILE3)" in driver and "plane_class(R, fit)" in driver
+    assert "xcd_block3(" in sweep[sweep.index("bool sweep3_lane("):sweep.index("void sweep3_planes(")] and "rows3_lookup(" in driver
+    for name, fn in (("kernels_density3d.hip", "void k3_density("), ("kernels_density3d.hip", "void k3_surface_tension("),
+                     ("kernels_force3d.hip", "void force3_body(")):
+        text = passes[name][passes[name].index(fn):]
+        text = text[:text.index("\n}\n")]
+        assert text.count("sweep3_lane(") == 1 and text.count("sweep3_planes(") == 1, fn
+    assert sum(t.count("sweep3_planes(") for t in passes.values()) == 3
     # the 128-bit masks are no longer a switch: rows <= 128 are class 2 unconditionally
     # (the name is spelt in two halves so that a search of the tree for the removed switch finds nothing, this test included)
     assert "FS3_" + "MASK128" not in k3d and "return !__any(mx > 128u) ? 2 : 0;" in body

@@ -94,8 +94,9 @@ GUARD_CASES = paths3d.GUARD_CASES
 
 @pytest.mark.parametrize("case", GUARD_CASES)
 def test_3d_force_quotient_guards(fs, orc, case):
-    """Operands on both sides of every guard of the shared-reciprocal quotients (kernels_3d.hip: lo_safe / 2^59 in k3_reorder,
-    FS_RCP_HI / FS_PRESSURE_HI in k3_density, FS_SQRT_LO / num_lo_ok3 / the 2^-20 branch in terms3*): whatever the
+    """Operands on both sides of every guard of the shared-reciprocal quotients (lo_safe / 2^59 in k3_reorder, kernels_3d.hip;
+    FS_RCP_HI / FS_PRESSURE_HI in k3_density, kernels_density3d.hip; FS_SQRT_LO / num_lo_ok3 / the 2^-20 branch in terms3*,
+    kernels_force3d.hip): whatever the
     classification decides, the step equals the oracle bit for bit, 3 steps."""
     sim, ref, st, tick, p = make_pair3(fs, orc, 12, **paths3d.guard_overrides(case))
     p = paths3d.guard_state(orc, st, p, case)

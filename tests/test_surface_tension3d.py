@@ -279,7 +279,7 @@ def _header_text():
 
 
 def test_constants_match_the_sources():
-    k3d = paths3d.source_text("kernels_3d.hip")
+    k3d = paths3d.source_text("kernels_density3d.hip")
     eng = paths3d.source_text("engine_3d.hip")
     with open(R.SOURCES[0]) as fh:
         chk = fh.read()
@@ -303,6 +303,8 @@ def test_constants_match_the_sources():
     body = k3d[k3d.index("void k3_surface_tension("):]
     body = body[:body.index("\n}\n")]
     assert "__launch_bounds__(B3F) void k3_surface_tension(" in k3d
-    assert "block_tile_bounds<W3F>(R, s_mm, blo, bhi, TILE3)" in body and "plane_class(R, fit)" in body
-    assert "xcd_block3(" in body and "rows3_lookup(" in body
+    # ... by construction: block mapping, row look-up, tile bounds and plane classes are the plane driver's (fs_sweep3.h; pinned
+    # there by test_3d_paths.py), and the plane walk is k3_density's with other terms
+    assert "sweep3_lane(" in body and "sweep3_planes(" in body and "PlaneTerms3<TensionPass>" in body
+    assert "PlaneTerms3<DensityPass<MODE>>" in k3d and "block_tile_bounds" not in k3d and "plane_class(R" not in k3d
     assert "atomic" not in body
