@@ -106,7 +106,7 @@ def selftest_sort(keys, fuse_stage=-1, device=0):
     """The engine's sort (reference network, sort.wgsl:27-51) on bare u32 keys: (sorted_keys, perm, plan).
 
     plan = (calls that took the shifted late-stage merge, calls that took the per-stage plan); see
-    csrc/kernels_sort.hip k_late_cert.  fuse_stage: -1 default plan, 0 per-stage only, k shifted merge from stage k.
+    csrc/kernels_sort_global.inc k_late_cert.  fuse_stage: -1 default plan, 0 per-stage only, k shifted merge from stage k.
     """
     lib = load_library()
     k = np.ascontiguousarray(keys, dtype=np.uint32)

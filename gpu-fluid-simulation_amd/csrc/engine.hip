@@ -320,7 +320,8 @@ static fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
     } else {
         fsd::SortPlan plan;
         if (!s->sortp.plan(s->n, &plan)) return fail(FS_ERR_DEVICE, "sort: the stand-by kernel's grid barrier timed out");
-        fsd::launch_bitonic_sort(st, s->pairs.p, s->n, s->sort_dirty.p, &P, s->pos.p, s->vel.p, s->counter.p, &plan);
+        const fsd::SortKeys keys(P, s->pos.p, s->vel.p, s->counter.p);
+        fsd::launch_bitonic_sort(st, s->pairs.p, s->n, s->sort_dirty.p, &keys, &plan);
     }
     if (prof) FS_HIP(hipEventRecord(ev[2], st));
     fsd::StepArrays A = s->step_arrays();

@@ -142,10 +142,11 @@ static fs_status enqueue3(fs_sim3* s, const fs3_tick_settings* t) {
     fsd::SortPlan plan;
     if (!s->sortp.plan(s->n, &plan)) return fail(FS_ERR_DEVICE, "sort: the stand-by kernel's grid barrier timed out");
     if (separate_keygen) {
-        launch_bitonic_sort(st, s->pairs.p, s->n, s->dirty.p, nullptr, nullptr, nullptr, nullptr, &plan);
+        launch_bitonic_sort(st, s->pairs.p, s->n, s->dirty.p, nullptr, &plan);
     } else {
         const fsd::KeyGen3 kg{P.dt, P.h, P.bx, P.by, P.bz, P.gw, P.gh};
-        launch_bitonic_sort(st, s->pairs.p, s->n, s->dirty.p, nullptr, nullptr, nullptr, s->counter.p, &plan, &kg, s->pos.p, s->vel.p);
+        const fsd::SortKeys keys(kg, s->pos.p, s->vel.p, s->counter.p);
+        launch_bitonic_sort(st, s->pairs.p, s->n, s->dirty.p, &keys, &plan);
     }
     if (ev) FS_HIP(hipEventRecord(ev[2], st));
     launch3_reorder(st, P, A);

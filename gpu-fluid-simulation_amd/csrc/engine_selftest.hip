@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "fs_sort.h"
 
 using namespace fsd;
 
@@ -39,12 +40,13 @@ fs_status fs_selftest_sort(int device, uint64_t* pairs, uint32_t n, int fuse_sta
         fsd::SortPlan sp;
         sp.fuse_stage = fuse_stage < 0 ? -1 : (fuse_stage & 0xFF);
         sp.fallback = fuse_stage >= 0 && (fuse_stage & 0x100) ? 1 : 0;
-        fsd::launch_bitonic_sort(nullptr, dp.p, n, dd.p, nullptr, nullptr, nullptr, nullptr, &sp);
+        fsd::launch_bitonic_sort(nullptr, dp.p, n, dd.p, nullptr, &sp);
         e = hipMemcpy(pairs, dp.p, (size_t)n * 8, hipMemcpyDeviceToHost);
     }
-    if (e == hipSuccess && plan) e = hipMemcpy(plan, dd.p + fsd::sort_plan_word(n) + 1, 8, hipMemcpyDeviceToHost);
+    static_assert(fsd::SORT_PW_PER_STAGE == fsd::SORT_PW_SHIFTED + 1, "plan[2] is read in one copy");
+    if (e == hipSuccess && plan) e = hipMemcpy(plan, dd.p + fsd::sort_plan_word(n) + fsd::SORT_PW_SHIFTED, 8, hipMemcpyDeviceToHost);   // ... and SORT_PW_PER_STAGE
     uint32_t timeouts = 0;
-    if (e == hipSuccess) e = hipMemcpy(&timeouts, dd.p + fsd::sort_plan_word(n) + 4, 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&timeouts, dd.p + fsd::sort_plan_word(n) + fsd::SORT_PW_TIMEOUTS, 4, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(FS_ERR_DEVICE, hipGetErrorString(e));
     if (timeouts) return fail(FS_ERR_DEVICE, "sort fallback: grid barrier timed out");
     return FS_OK;
@@ -77,10 +79,11 @@ fs_status fs_sort_plan_read(fs_sim* s, fs_sort_plan_info* out) {
     if (!s || !out) return fail(FS_ERR_INVALID, "null argument");
     FS_HIP(hipSetDevice(s->device));
     FS_HIP(hipStreamSynchronize(s->stream));
-    uint32_t w[8] = {};
+    uint32_t w[fsd::SORT_PW_COUNT] = {};
     const uint32_t count = s->slab ? s->capacity : s->n;
     if (count > 1) FS_HIP(hipMemcpy(w, s->sort_dirty.p + fsd::sort_plan_word(count), sizeof w, hipMemcpyDeviceToHost));
-    out->shifted = w[1]; out->per_stage = w[2]; out->standby_runs = w[6]; out->timeouts = w[4]; out->wide_tiles = w[7];
+    out->shifted = w[fsd::SORT_PW_SHIFTED]; out->per_stage = w[fsd::SORT_PW_PER_STAGE]; out->standby_runs = w[fsd::SORT_PW_STANDBY_RUNS];
+    out->timeouts = w[fsd::SORT_PW_TIMEOUTS]; out->wide_tiles = w[fsd::SORT_PW_WIDE_TILES];
     out->stage = (uint32_t)s->sortp.stage;
     out->standby_single = (s->sortp.force_single || (s->sortp.stage && s->sortp.trusted >= 2)) ? 1u : 0u;
     return FS_OK;

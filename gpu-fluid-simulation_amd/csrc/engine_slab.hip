@@ -456,7 +456,7 @@ fs_status fs_slab_step(fs_sim* s, const void* recv_left, const void* recv_right)
     } else {
         SortPlan per_stage;                    // ghosts arrive at the end of the array every step: they travel far, no shifted merge
         per_stage.fuse_stage = 0;
-        launch_bitonic_sort(st, s->pairs.p, s->capacity, s->sort_dirty.p, nullptr, nullptr, nullptr, nullptr, &per_stage);
+        launch_bitonic_sort(st, s->pairs.p, s->capacity, s->sort_dirty.p, nullptr, &per_stage);
     }
     if (ev) FS_HIP(hipEventRecord(ev[2], st));
     const bool edge_step = S.edge_first && (S.cfg.has_left || S.cfg.has_right);

@@ -1,6 +1,6 @@
 // fs_3d.h — what the files of the 3D step share (kernels_3d.hip, kernels_density3d.hip, kernels_force3d.hip: the kernels and
 // their launchers, engine_3d.hip: the handle and the fs3_* C ABI): the step parameters, the array set of the launchers, the launchers.  A header of its own:
-// fs_kernels.h stays the 2D launchers' list, and kernels_sort.hip takes the predict + cell-key expression from here.
+// fs_kernels.h stays the 2D launchers' list, and kernels_sort_tile.inc takes the predict + cell-key expression from here.
 #pragma once
 #include "fs_kernels.h"
 
@@ -37,7 +37,7 @@ struct Arrays3 {
 };
 
 // Predict + cell key of the 3D step, defined once for k3_predict_key, k3_reorder (kernels_3d.hip) and the sort's fused key
-// generation (kernels_sort.hip keygen3); the cell coordinates alone also for a query point (kernels_sample3d.hip).  K: anything with dt, h, bx, by, bz, gw, gh (Params3, KeyGen3).
+// generation (kernels_sort_tile.inc keygen3); the cell coordinates alone also for a query point (kernels_sample3d.hip).  K: anything with dt, h, bx, by, bz, gw, gh (Params3, KeyGen3).
 template <class K>
 __device__ __forceinline__ float4 predict3(const K& P, float4 p, float4 v) {
     float4 r;

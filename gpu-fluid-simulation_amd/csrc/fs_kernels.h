@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "fs_device.h"
 
@@ -197,11 +198,8 @@ void launch_slab_colhist(hipStream_t st, const StepParams& P, const SlabArrays& 
 void launch_slab_maxspeed(hipStream_t st, const SlabArrays& A, uint32_t migr_count);
 size_t slab_message_bytes(uint32_t R);
 
-// Bitonic network of sort.wgsl:27-51 / simulation.rs:323-347 on (key<<32 | index) pairs.
-// Returns the number of kernel launches issued.
-// `dirty`: one u32 per 4096-element tile (sort_tile_count(n) entries), scratch owned by the caller.
-// keygen != nullptr: the init pass computes the pairs from pos/vel itself (predict + key fused in).
-// Late-stage plan of one sort call (kernels_sort.hip, k_late_cert).  Whatever the plan, the result is the network's.
+// ---- the bitonic sort (kernels_sort.hip: the schedule; kernels_sort_tile.inc, kernels_sort_global.inc: its kernels) ----
+// Late-stage plan of one sort call (kernels_sort_global.inc, k_late_cert).  Whatever the plan, the result is the network's.
 struct SortPlan {
     int fuse_stage = -1;           // < 0: default stage, 0: per-stage launches only, k: the shifted merge from stage k
     int fallback = 0;              // what stands by for a failing certificate: 0 the per-stage launches (each returns at
@@ -210,17 +208,35 @@ struct SortPlan {
     uint32_t seq = 0;
     int inject_timeout = 0;        // tests (FS_SORT_INJECT_TIMEOUT=1): the stand-by kernel reports a barrier time-out it did not have
 };
-// keygen3d != nullptr (3D engine): the same fusion with float4 pos / vel and the 3D cell key.
+// What the 3D predict + cell key needs (fs_3d.h predict3 / cell_key3).
 struct KeyGen3 { float dt, h, bx, by, bz; uint32_t gw, gh; };
-int launch_bitonic_sort(hipStream_t st, u64* pairs, uint32_t n, uint32_t* dirty, const StepParams* keygen = nullptr,
-                        const float2* pos = nullptr, const float2* vel = nullptr, uint32_t* gap_counter = nullptr,
-                        const SortPlan* plan = nullptr, const KeyGen3* keygen3d = nullptr, const float4* pos4 = nullptr,
-                        const float4* vel4 = nullptr);
-// dirty[sort_plan_word(n) ..]: [0] verdict of the last certificate, [1] / [2] shifted-merge / per-stage plan counters,
-// [3] fallback barrier, [4] fallback barrier time-outs, [5] fit class
-uint32_t sort_plan_word(uint32_t n);
-#define FS_SORT_NO_PLAN 255u
-uint32_t sort_tile_count(uint32_t n);
+// The state a sort call builds its pairs from (no SortKeys: `pairs` holds them): the first kernel computes predict + cell
+// key itself (fused into its tile load, compute.wgsl:8-42) and clears `gap_counter` for the reorder pass that follows in
+// the stream.  Held in the form the kernels' parameter list has — one StepParams and float2 arrays — so the 3D
+// constructor is the one place where the 3D parameters and arrays are dressed up as the 2D ones; k_bitonic_local and
+// k_bitonic_local32 undo it with the matching casts when KEYGEN == 2.
+struct SortKeys {
+    int keygen;                    // the kernels' KEYGEN argument: 1 = 2D, 2 = 3D
+    StepParams P;
+    const float2 *pos, *vel;
+    uint32_t* gap_counter;
+    SortKeys(const StepParams& P2, const float2* pos2, const float2* vel2, uint32_t* gap)
+        : keygen(1), P(P2), pos(pos2), vel(vel2), gap_counter(gap) {}
+    SortKeys(const KeyGen3& K, const float4* pos4, const float4* vel4, uint32_t* gap)
+        : keygen(2), pos(reinterpret_cast<const float2*>(pos4)), vel(reinterpret_cast<const float2*>(vel4)), gap_counter(gap) {
+        static_assert(sizeof(KeyGen3) <= sizeof(StepParams), "KeyGen3 rides in the StepParams argument");
+        memset(&P, 0, sizeof P);
+        memcpy(&P, &K, sizeof K);
+    }
+};
+// Bitonic network of sort.wgsl:27-51 / simulation.rs:323-347 on (key<<32 | index) pairs.
+// Returns the number of kernel launches issued.
+// `dirty`: one u32 per 4096-element tile and, behind them, the plan words (sort_tile_count(n) entries; fs_sort.h
+// SortPlanWord), scratch owned by the caller, zero at create.
+int launch_bitonic_sort(hipStream_t st, u64* pairs, uint32_t n, uint32_t* dirty, const SortKeys* keys = nullptr,
+                        const SortPlan* plan = nullptr);
+uint32_t sort_tile_count(uint32_t n);      // entries of `dirty` for a sort of n elements
+uint32_t sort_plan_word(uint32_t n);       // index of the first plan word in it
 
 // FS_SORT_COUNTING (kernels_csort.hip).  The scratch must be all-zero when the handle is created (histogram, tickets);
 // every step leaves it that way.  `epoch`: a number unique to the launch among the handle's launches.

@@ -2,7 +2,7 @@
 // Device state is SoA (float2 pos / vel / pred, f32 density): coalesced 8-byte
 // per-lane streams instead of the reference's 32-byte AoS records.
 //   (predict_next_position + create_spatial_lookup, compute.wgsl:8-42, are fused into the first
-//    kernel of the sort: kernels_sort.hip k_bitonic_local<INIT, KEYGEN> / kernels_csort.hip k_cs_hist)
+//    kernel of the sort: kernels_sort_tile.inc k_bitonic_local<INIT, KEYGEN> / kernels_csort.hip k_cs_hist)
 //   k_reorder       = payload gather after the (key,index) sort + compute_start_indices
 //                     (compute.wgsl:45-56) + dense cell-start table
 #include "fs_kernels.h"

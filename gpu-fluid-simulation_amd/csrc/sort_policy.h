@@ -1,4 +1,4 @@
-// sort_policy.h — host side of the sort's late-stage plan (kernels_sort.hip, k_late_cert), shared by the 2D and the
+// sort_policy.h — host side of the sort's late-stage plan (kernels_sort_global.inc, k_late_cert), shared by the 2D and the
 // 3D engine.
 //
 // The device-side certificate of every sort reports the stage it ran at, its verdict and how much room the step's
@@ -19,6 +19,7 @@
 
 #include "fs_host.h"
 #include "fs_kernels.h"
+#include "fs_sort.h"
 
 namespace fsd {
 
@@ -139,7 +140,7 @@ struct SortPolicy {
     fs_status health(const uint32_t* dirty, uint32_t n) {
         if (!dead && enabled && n >= (1u << 15)) {
             uint32_t t = 0;
-            FS_HIP(hipMemcpy(&t, dirty + sort_plan_word(n) + 4, sizeof t, hipMemcpyDeviceToHost));
+            FS_HIP(hipMemcpy(&t, dirty + sort_plan_word(n) + SORT_PW_TIMEOUTS, sizeof t, hipMemcpyDeviceToHost));
             if (t) dead = true;
         }
         if (dead) return fail(FS_ERR_DEVICE, "sort: the stand-by kernel's grid barrier timed out: the particle order is undefined from that step on; destroy the handle");

@@ -163,7 +163,7 @@ void fs_destroy(fs_sim* sim);
  * the simulation's stream.  Non-blocking, like the reference (which only
  * records into a CommandEncoder; submit happens at src/main.rs:226).
  * FS_ERR_DEVICE from fs_step / fs_timed_steps is terminal for the handle: besides HIP runtime errors it reports that the
- * sort's stand-by kernel (csrc/kernels_sort.hip k_late_fallback, a persistent launch with a bounded-spin grid barrier)
+ * sort's stand-by kernel (csrc/kernels_sort_global.inc k_late_fallback, a persistent launch with a bounded-spin grid barrier)
  * timed out on a barrier in an EARLIER step — the host learns of it from the device's report a few steps later, and the
  * particle order of every step since is undefined.  Destroy the handle and re-create it (or re-upload a checkpoint into
  * a new one); no further call on the old handle is meaningful.  fs_sort_plan_info.timeouts counts such events
@@ -860,7 +860,7 @@ fs_status fs_selftest_sort(int device, uint64_t* pairs, uint32_t n, int fuse_sta
 fs_status fs_selftest_sort_policy(uint32_t log2_count, int start_back, uint32_t lag, const uint32_t* required, size_t steps,
                                   uint32_t* stage_out, uint32_t* single_out);
 
-/* Diagnostics of the sort's late-stage plan (csrc/kernels_sort.hip): the network's last stages run as one shifted
+/* Diagnostics of the sort's late-stage plan (csrc/kernels_sort.hip, k_late_cert in csrc/kernels_sort_global.inc): the network's last stages run as one shifted
  * merge when a device-side certificate allows it, as per-stage launches otherwise.  Counts since create.  Blocking. */
 typedef struct fs_sort_plan_info {
     uint32_t shifted;        /* sorts that took the shifted merge */

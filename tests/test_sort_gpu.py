@@ -1,4 +1,5 @@
-"""The late-stage plans of the engine's sort (csrc/kernels_sort.hip: shifted merge behind a device-side certificate,
+"""The late-stage plans of the engine's sort (csrc/kernels_sort.hip, its kernels in csrc/kernels_sort_tile.inc and
+csrc/kernels_sort_global.inc: shifted merge behind a device-side certificate,
 per-stage launches otherwise) against the oracle's run of the reference network (sort.wgsl:27-51, schedule
 src/simulation.rs:323-347) on adversarial key sets: the arrangement — ties included — must be the network's whichever
 plan the certificate picks."""
@@ -39,6 +40,20 @@ def test_small_moves_take_the_shifted_merge_and_match(fs, orc, n, fuse):
         assert plan == (1, 0)            # moves of 1500 places fit the +-4096 window of stage 13 and every later one
     else:
         assert plan == (0, 0)
+
+
+@pytest.mark.parametrize("n", [2, 3, 4095, 4096, 4097, 8191, 8192, 8193, 12289])
+@pytest.mark.parametrize("fuse", [-1, 0])
+def test_the_launcher_at_its_smallest_sizes(fs, orc, n, fuse):
+    """The size-dependent branches of the host schedule at the smallest sizes that reach them: fewer than 12 stages in
+    the first kernel (2, 3, 4095), exactly one tile (4096), stage 12 with a mostly-sentinel second tile (4097), with a
+    second tile one short of full and full (8191, 8192), a stage-12 workgroup whose second tile does not exist (8193:
+    three tiles) and the first size with a certificate (12289: 14 stages).  Keys with ~8 ties per value: from n = 5 on
+    the network's arrangement differs from a stable sort's, so a dropped or reordered stage shows on the ties."""
+    keys = np.random.default_rng(n).integers(0, max(2, n // 8), size=n, dtype=np.uint32)
+    plan = _check(fs, orc, keys, fuse)
+    if n <= 8192:
+        assert plan == (0, 0), plan      # at most 13 stages: no certificate is launched
 
 
 @pytest.mark.parametrize("n", [1 << 16, 300_000, 1 << 20])
