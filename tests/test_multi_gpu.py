@@ -16,10 +16,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 class InProcessSlabs:
     def __init__(self, fs, settings, off, world, cap, recv, seed=None, vel=1.0, sort_mode=None, trim_margin=0, serial=False,
-                 boundary_cols=None, strips=False):
+                 boundary_cols=None, strips=False, particles=None):
         from gpu_fluid_simulation_amd import multi
         self.fs, self.multi, self.world, self.trim_margin = fs, multi, world, trim_margin
-        lat = fs.reference_lattice(settings, off)
+        lat = fs.reference_lattice(settings, off) if particles is None else np.array(particles, dtype=fs.PARTICLE_DTYPE)
         if seed is not None:
             rng = np.random.default_rng(seed)
             lat["position"] += rng.uniform(-0.025, 0.025, size=lat["position"].shape).astype(np.float32)

@@ -324,7 +324,8 @@ def test_counting_sort_orders_a_cell_of_5000_particles_like_the_stable_sort(fs, 
     """The counting sort's order inside a cell is the source order — the oracle's std::stable_sort — whatever order the histogram
     atomics were served in, for a cell of ANY size: up to CS_RANK_MAX = 2048 particles by the serial rank loop, beyond by sorting
     the cell's segment in place (kernels_csort.hip cs_sort_segment).  5000 particles in one cell (tools/fuzz_parity.py case 15
-    found that such cells were left in arrival order), bit-exact over two steps."""
+    found that such cells were left in arrival order), bit-exact over two steps.
+    The bound itself, the network's other sizes and the segment's placement: tests/test_csort_gpu.py."""
     n = 16384
     st = fs.SimulationSettings(n, 0.1, 0.2, (40.0, 30.0))
     tick = fs.default_tick_settings(gravity=(0.0, 9.81))
