@@ -51,7 +51,7 @@ from ._abi import (  # noqa: F401
 __all__ = [
     "FluidSimulation", "ResizableBuffer", "SimulationSettings", "default_tick_settings", "dam_break_2d",
     "FluidSimError", "load_library", "PARTICLE_DTYPE", "SAMPLE_DTYPE", "SAMPLE3_DTYPE",
-    "SURFACE_HIT_DTYPE", "look_at_camera", "shade_surface", "MESH_VERTEX_DTYPE", "write_obj", "box_mask3d",
+    "SURFACE_HIT_DTYPE", "look_at_camera", "shade_surface", "surface_hit_points", "MESH_VERTEX_DTYPE", "write_obj", "box_mask3d",
 ]
 
 
@@ -427,12 +427,14 @@ def dam_break_3d(n):
 class FluidSimulation3D:
     """3D extension (include/fluidsim.h fs3_*); not in the reference."""
 
-    def __init__(self, settings, device=0, initial_offset=(0.0, 0.0, 0.0), math_mode=FS_MATH_IEEE):
+    def __init__(self, settings, device=0, initial_offset=(0.0, 0.0, 0.0), math_mode=FS_MATH_IEEE, track=None):
         self._lib = load_library()
         self._h = C.c_void_p()
         self.settings = settings
         off = Vec3(*[float(x) for x in initial_offset])
         _check(self._lib, self._lib.fs3_create_ex(C.byref(settings), int(device), off, int(math_mode), C.byref(self._h)))
+        if track is not None:
+            self.track(track)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -522,38 +524,119 @@ class FluidSimulation3D:
         _check(self._lib, self._lib.fs3_download_surface_tension(self._h, out.ctypes.data_as(C.c_void_p), out.shape[0]))
         return out
 
-    # -- 3D field sampling (build extension) ------------------
-    def sample(self, points, normalise=False):
+    # -- 3D particle tracking (build extension, opt-in) -------
+    def track(self, channels=0):
+        """Give every particle an id (= its current slot) and `channels` float attributes (all 0) that follow it through the
+        sort of every later step.  Calling it again re-initialises."""
+        _check(self._lib, self._lib.fs3_track_enable(self._h, int(channels)))
+
+    def untrack(self):
+        _check(self._lib, self._lib.fs3_track_disable(self._h))
+
+    @property
+    def track_channels(self):
+        """-1 when tracking is off, else the number of attribute channels."""
+        return int(self._lib.fs3_track_channels(self._h))
+
+    def particle_ids(self):
+        """uint32 id of the particle in every slot, in download_particles() order."""
+        out = np.empty(self.particle_count, dtype=np.uint32)
+        _check(self._lib, self._lib.fs3_track_download_ids(self._h, out.ctypes.data_as(C.c_void_p), out.shape[0]))
+        return out
+
+    def set_particle_ids(self, ids):
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        _check(self._lib, self._lib.fs3_track_upload_ids(self._h, ids.ctypes.data_as(C.c_void_p), ids.shape[0]))
+
+    def attribute(self, channel):
+        """float32 attribute `channel` of the particle in every slot, in download_particles() order."""
+        out = np.empty(self.particle_count, dtype=np.float32)
+        _check(self._lib, self._lib.fs3_track_download_attr(self._h, int(channel), out.ctypes.data_as(C.c_void_p), out.shape[0]))
+        return out
+
+    def set_attribute(self, channel, values):
+        """`values` is copied bit for bit when it already is float32 (NaN payloads survive)."""
+        values = np.ascontiguousarray(values, dtype=np.float32)
+        _check(self._lib, self._lib.fs3_track_upload_attr(self._h, int(channel), values.ctypes.data_as(C.c_void_p), values.shape[0]))
+
+    def download_particles_by_id(self):
+        """The records in id order: out[id] is the particle with that id (ids >= particle_count are skipped; entries that no
+        id names stay zero)."""
+        out = np.zeros(self.particle_count, dtype=PARTICLE3_DTYPE)
+        _check(self._lib, self._lib.fs3_download_particles_by_id(self._h, out.ctypes.data_as(C.c_void_p), out.shape[0]))
+        return out
+
+    def particle_ids_device_ptr(self):
+        p = C.c_void_p()
+        _check(self._lib, self._lib.fs3_track_ids_device(self._h, C.byref(p)))
+        return p.value
+
+    def attribute_device_ptr(self, channel):
+        p = C.c_void_p()
+        _check(self._lib, self._lib.fs3_track_attr_device(self._h, int(channel), C.byref(p)))
+        return p.value
+
+    # -- 3D field sampling (build extension; DESIGN.md §14, the channels: §20) ----
+    def _sample_attr(self, n):
+        ch = self.track_channels
+        if ch <= 0:
+            raise FluidSimError(_abi.FS_ERR_INVALID, "sample(attributes=True) needs track(channels >= 1)")
+        return np.zeros((ch, n), dtype=np.float32)
+
+    def sample(self, points, attributes=False, normalise=False):
         """Density, Shepard weight, velocity sum, density gradient, neighbour count and cell of the fluid at `points`
-        ((n, 3) float32, any place): a SAMPLE3_DTYPE array.  The velocity is the un-normalised SPH interpolant
-        (include/fluidsim.h); normalise=True divides it by `weight` where that is non-zero.  -gradient is the outward normal
-        of an iso-surface.  Needs a step since create / the last upload.  Points in a coherent order (sorted by cell, a grid,
-        slot order) are sampled several times faster than shuffled ones."""
+        ((n, 3) float32, any place): a SAMPLE3_DTYPE array, and with attributes=True also the (channels, n) float32 sums of
+        the tracking channels.  Velocity and channels are the un-normalised SPH interpolants (include/fluidsim.h);
+        normalise=True divides them by `weight` where that is non-zero.  -gradient is the outward normal of an iso-surface.
+        Needs a step since create / the last upload.  Points in a coherent order (sorted by cell, a grid, slot order) are
+        sampled several times faster than shuffled ones."""
         pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
         n = pts.shape[0]
         out = np.zeros(n, dtype=SAMPLE3_DTYPE)
+        attr = self._sample_attr(n) if attributes else None
         _check(self._lib, self._lib.fs3_sample_points(self._h, pts.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p)))
+        if attributes:
+            _check(self._lib, self._lib.fs3_sample_attr_points(self._h, pts.ctypes.data_as(C.c_void_p), n, None,
+                                                               attr.ctypes.data_as(C.c_void_p)))
         if normalise:
-            _normalise_samples(out, None)
-        return out
+            _normalise_samples(out, attr)
+        return (out, attr) if attributes else out
 
-    def sample_grid(self, width, height, depth=1, world_min=None, world_max=None):
+    def sample_grid(self, width, height, depth=1, world_min=None, world_max=None, attributes=False):
         """sample() at the voxel centres of a box (default: the whole domain): a [depth, height, width] SAMPLE3_DTYPE array,
-        bit-identical to sample() on those points.  A slice is depth == 1 with world_min[2] == world_max[2]."""
-        sz = self.settings.size
-        wmin = world_min if world_min is not None else (-sz.x / 2, -sz.y / 2, -sz.z / 2)
-        wmax = world_max if world_max is not None else (sz.x / 2, sz.y / 2, sz.z / 2)
+        and with attributes=True also the (channels, depth, height, width) float32 channel sums; bit-identical to sample() on
+        those points.  A slice is depth == 1 with world_min[2] == world_max[2]."""
+        view = self._view3(width, height, depth, world_min, world_max)
         width, height, depth = int(width), int(height), int(depth)
-        view = _abi.View3(Vec3(*[float(v) for v in wmin]), Vec3(*[float(v) for v in wmax]), width, height, depth)
         out = np.zeros((depth, height, width), dtype=SAMPLE3_DTYPE)
+        attr = self._sample_attr(width * height * depth) if attributes else None
         _check(self._lib, self._lib.fs3_sample_grid(self._h, C.byref(view), out.ctypes.data_as(C.c_void_p)))
-        return out
+        if attributes:
+            _check(self._lib, self._lib.fs3_sample_attr_grid(self._h, C.byref(view), None, attr.ctypes.data_as(C.c_void_p)))
+        return (out, attr.reshape(-1, depth, height, width)) if attributes else out
 
     def sample_device(self, points_ptr, n, out_ptr):
         """fs3_sample_points_device: device pointers (n fs_vec3 in, n 40-byte fs3_sample out), enqueued on the simulation's
         stream after the steps in flight; non-blocking."""
         _check(self._lib, self._lib.fs3_sample_points_device(self._h, C.c_void_p(points_ptr), int(n), C.c_void_p(out_ptr)))
 
+    def sample_attr(self, points, weights=False):
+        """The channel sums alone at `points`: (channels, n) float32, with weights=True (weight[n], sums)."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        attr = self._sample_attr(n)
+        w = np.zeros(n, dtype=np.float32) if weights else None
+        _check(self._lib, self._lib.fs3_sample_attr_points(self._h, pts.ctypes.data_as(C.c_void_p), n,
+                                                           w.ctypes.data_as(C.c_void_p) if weights else None,
+                                                           attr.ctypes.data_as(C.c_void_p)))
+        return (w, attr) if weights else attr
+
+    def sample_attr_device(self, points_ptr, n, weight_ptr, attr_ptr):
+        """fs3_sample_attr_points_device: device pointers (n fs_vec3 in, n floats out or 0 / None, channels * n floats out),
+        enqueued on the simulation's stream after the steps in flight; non-blocking."""
+        _check(self._lib, self._lib.fs3_sample_attr_points_device(self._h, C.c_void_p(points_ptr), int(n),
+                                                                  C.c_void_p(weight_ptr) if weight_ptr else None,
+                                                                  C.c_void_p(attr_ptr) if attr_ptr else None))
 
     # -- 3D surface rendering (build extension; DESIGN.md §16) ---------------
     def render_surface(self, camera, params, out=None):
@@ -681,6 +764,22 @@ def look_at_camera(eye, target, up, fov_y_or_extent, width, height, orthographic
     span_x = span_y * float(width) / float(height)
     vec = lambda a: Vec3(*[float(np.float32(x)) for x in a])      # noqa: E731
     return Camera3(vec(e), vec(fwd), vec(right * span_x), vec(upv * span_y), int(width), int(height), 1 if orthographic else 0, 0)
+
+
+def surface_hit_points(camera, hits):
+    """World positions of a render_surface G-buffer's hits, float32 of the hits' shape + (3,), from the camera and the records' `t`
+    (include/fluidsim.h: x(t) = o + t * d; numpy, for shading only).  Pixels without a hit get the ray origin."""
+    v3 = lambda a: np.float32([a.x, a.y, a.z])      # noqa: E731
+    h, w = hits.shape
+    u = ((np.arange(w, dtype=np.float32) + np.float32(0.5)) / np.float32(w) - np.float32(0.5))[None, :, None]
+    v = ((np.arange(h, dtype=np.float32) + np.float32(0.5)) / np.float32(h) - np.float32(0.5))[:, None, None]
+    span = u * v3(camera.right) + v * v3(camera.up)
+    if camera.orthographic:
+        o, d = v3(camera.eye) + span, np.broadcast_to(v3(camera.forward), (h, w, 3))
+    else:
+        o, d = np.broadcast_to(v3(camera.eye), (h, w, 3)), v3(camera.forward) + span
+    d = d / np.sqrt((d * d).sum(axis=-1, keepdims=True))
+    return (o + hits["t"][..., None] * d).astype(np.float32)
 
 
 def shade_surface(hits, light=(0.4, -0.8, -0.45), max_speed=None):

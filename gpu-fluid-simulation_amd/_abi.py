@@ -325,6 +325,19 @@ PROTOTYPES = {
     "fs3_sample_points": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "fs3_sample_points_device": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "fs3_sample_grid": (C.c_int, [_P, C.POINTER(View3), _P]),
+    "fs3_track_enable": (C.c_int, [_P, C.c_int]),
+    "fs3_track_disable": (C.c_int, [_P]),
+    "fs3_track_channels": (C.c_int, [_P]),
+    "fs3_track_download_ids": (C.c_int, [_P, _P, C.c_size_t]),
+    "fs3_track_upload_ids": (C.c_int, [_P, _P, C.c_size_t]),
+    "fs3_track_download_attr": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
+    "fs3_track_upload_attr": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
+    "fs3_track_ids_device": (C.c_int, [_P, C.POINTER(_P)]),
+    "fs3_track_attr_device": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
+    "fs3_download_particles_by_id": (C.c_int, [_P, _P, C.c_size_t]),
+    "fs3_sample_attr_points": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "fs3_sample_attr_points_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "fs3_sample_attr_grid": (C.c_int, [_P, C.POINTER(View3), _P, _P]),
     "fs3_render_surface": (C.c_int, [_P, C.POINTER(Camera3), C.POINTER(SurfaceParams3), _P]),
     "fs3_render_surface_device": (C.c_int, [_P, C.POINTER(Camera3), C.POINTER(SurfaceParams3), _P]),
     "fs3_extract_surface": (C.c_int, [_P, C.POINTER(View3), C.c_float, _P, C.c_uint32, _P, C.c_uint32, _P]),

@@ -13,8 +13,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libfluidsim_hip.so")
-SOURCES = ["engine.hip", "engine_features.hip", "engine_query.hip", "engine_selftest.hip", "engine_slab.hip", "comm.hip", "buffer.hip", "kernels_reorder.hip", "kernels_density.hip", "kernels_force.hip", "kernels_proof.hip", "kernels_sort.hip", "kernels_slab.hip", "kernels_strip.hip", "kernels_csort.hip", "kernels_field.hip", "kernels_track.hip", "kernels_sample.hip", "kernels_3d.hip", "kernels_density3d.hip", "kernels_force3d.hip", "kernels_sample3d.hip", "kernels_render3d.hip", "kernels_mesh3d.hip", "kernels_collide3d.hip", "engine_3d.hip"]
-HEADERS = ["engine.h", "fs_3d.h", "fs_device.h", "fs_field3.h", "fs_host.h", "fs_kernels.h", "fs_neighbours.h", "fs_scan.h", "fs_slab.h", "fs_sort.h", "fs_sort_tile.h", "fs_sweep3.h", "kernels_sort_tile.inc", "kernels_sort_global.inc", "sort_policy.h", os.path.join("..", "..", "include", "fluidsim.h")]
+SOURCES = ["engine.hip", "engine_features.hip", "engine_query.hip", "engine_selftest.hip", "engine_slab.hip", "comm.hip", "buffer.hip", "kernels_reorder.hip", "kernels_density.hip", "kernels_force.hip", "kernels_proof.hip", "kernels_sort.hip", "kernels_slab.hip", "kernels_strip.hip", "kernels_csort.hip", "kernels_field.hip", "kernels_track.hip", "kernels_sample.hip", "kernels_3d.hip", "kernels_density3d.hip", "kernels_force3d.hip", "kernels_sample3d.hip", "kernels_sample_attr3d.hip", "kernels_render3d.hip", "kernels_mesh3d.hip", "kernels_collide3d.hip", "engine_3d.hip"]
+HEADERS = ["engine.h", "fs_3d.h", "fs_device.h", "fs_field3.h", "fs_host.h", "fs_kernels.h", "fs_neighbours.h", "fs_sample3.h", "fs_scan.h", "fs_slab.h", "fs_sort.h", "fs_sort_tile.h", "fs_sweep3.h", "kernels_sort_tile.inc", "kernels_sort_global.inc", "sort_policy.h", os.path.join("..", "..", "include", "fluidsim.h")]
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",
@@ -30,7 +30,7 @@ FLAGS = [
 # kernels_sort_tile.inc and kernels_sort_global.inc are compiled as part of kernels_sort.hip (see its last lines): HEADERS.
 # float-heavy kernels only: the integer sort kernels measured ~1 % faster with the vectoriser on
 # (kernels_reorder.hip and kernels_proof.hip hold no such arithmetic; the flag is the one their kernels were measured with)
-NO_SLP = {"kernels_reorder.hip", "kernels_density.hip", "kernels_force.hip", "kernels_proof.hip", "kernels_3d.hip", "kernels_density3d.hip", "kernels_force3d.hip", "kernels_slab.hip", "kernels_strip.hip", "kernels_sample.hip", "kernels_sample3d.hip", "kernels_render3d.hip", "kernels_mesh3d.hip"}
+NO_SLP = {"kernels_reorder.hip", "kernels_density.hip", "kernels_force.hip", "kernels_proof.hip", "kernels_3d.hip", "kernels_density3d.hip", "kernels_force3d.hip", "kernels_slab.hip", "kernels_strip.hip", "kernels_sample.hip", "kernels_sample3d.hip", "kernels_sample_attr3d.hip", "kernels_render3d.hip", "kernels_mesh3d.hip"}
 
 
 def _flags(src):

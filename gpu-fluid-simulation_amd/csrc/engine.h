@@ -8,6 +8,7 @@
 
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "../../include/fluidsim.h"
 #include "fs_host.h"
@@ -97,8 +98,9 @@ struct SurfaceTension {
     }
 };
 
-// Opt-in particle tracking (build extension; single-domain handles): fs_track_enable, engine_features.hip.  Two
-// sets that swap roles every step: [cur] holds the ids / channels in the order of the last enqueued step.
+// Opt-in particle tracking (build extension, DESIGN.md §12 and, on an fs_sim3, §20; single-domain handles): fs_track_* in
+// engine_features.hip, fs3_track_* in engine_3d.hip.  Two sets that swap roles every step: [cur] holds the ids / channels in the
+// order of the last enqueued step.  `capacity`: the slots of the handle, the stride of the channels (an fs_sim3: its n).
 struct Tracking {
     DevArray<uint32_t> id[2];
     DevArray<float> attr[2];        // channel c at c * capacity
@@ -114,6 +116,67 @@ struct Tracking {
         if (!on()) return;
         launch_track_carry(st, n, channels, pairs, id[cur].p, id[cur ^ 1].p, attr[cur].p, attr[cur ^ 1].p, capacity);
         cur ^= 1;
+    }
+    // fs_track_enable / fs3_track_enable on the current device: allocates on first use, then id[i] = i and every channel +0.0f on
+    // `st` — ordered after every step already enqueued, before every step enqueued from now on.
+    fs_status enable(hipStream_t st, uint32_t n, uint32_t capacity, int ch) {
+        if (ch < 0 || ch > FS_TRACK_MAX_CHANNELS) return fail(FS_ERR_INVALID, "tracking: channels must be in [0, FS_TRACK_MAX_CHANNELS]");
+        if (!id[0].p) {
+            for (int k = 0; k < 2; ++k)
+                if (id[k].alloc(capacity) != hipSuccess) {
+                    (void)hipGetLastError();
+                    id[0].release(); id[1].release();
+                    return fail(FS_ERR_OOM, "tracking: id arrays");
+                }
+        }
+        if (ch > alloc_channels) {
+            FS_HIP(hipStreamSynchronize(st));      // steps in flight may still read the arrays about to be replaced
+            attr[0].release(); attr[1].release();
+            alloc_channels = 0;
+            for (int k = 0; k < 2; ++k)
+                if (attr[k].alloc((size_t)ch * capacity) != hipSuccess) {
+                    (void)hipGetLastError();
+                    attr[0].release(); attr[1].release();
+                    channels = -1;
+                    return fail(FS_ERR_OOM, "tracking: channel arrays");
+                }
+            alloc_channels = ch;
+        }
+        cur = 0;
+        launch_track_iota(st, n, ids());
+        FS_HIP(hipGetLastError());
+        if (ch && n) FS_HIP(hipMemsetAsync(attr[0].p, 0, (size_t)ch * capacity * sizeof(float), st));
+        channels = ch;
+        return FS_OK;
+    }
+    // ids (is_attr = false) or one channel, host <-> the arrays of the last enqueued step, on the current device.  Blocking; the
+    // caller reports the sort's health after a download.
+    fs_status copy(hipStream_t st, uint32_t n, uint32_t capacity, int c, bool is_attr, void* host, size_t count, bool upload) {
+        if (!host) return fail(FS_ERR_INVALID, "null argument");
+        if (!on()) return fail(FS_ERR_INVALID, "tracking is off (enable it first)");
+        if (is_attr && (c < 0 || c >= channels)) return fail(FS_ERR_INVALID, "tracking: no such channel");
+        if (count != n) return fail(FS_ERR_INVALID, "tracking: n must equal the particle count");
+        void* dev = is_attr ? (void*)channel(c, capacity) : (void*)ids();
+        if (count) {
+            if (upload) FS_HIP(hipMemcpyAsync(dev, host, count * 4, hipMemcpyHostToDevice, st));
+            else FS_HIP(hipMemcpyAsync(host, dev, count * 4, hipMemcpyDeviceToHost, st));
+        }
+        FS_HIP(hipStreamSynchronize(st));
+        return FS_OK;
+    }
+    // fs_track_ids_device / fs_track_attr_device (is_attr)
+    fs_status device_ptr(uint32_t capacity, int c, bool is_attr, const void** out) const {
+        if (!out) return fail(FS_ERR_INVALID, "null argument");
+        if (!on()) return fail(FS_ERR_INVALID, "tracking is off (enable it first)");
+        if (is_attr && (c < 0 || c >= channels)) return fail(FS_ERR_INVALID, "tracking: no such channel");
+        *out = is_attr ? (const void*)channel(c, capacity) : (const void*)ids();
+        return FS_OK;
+    }
+    // fs_download_particles_by_id's scatter on the host: dst[ids[i]] = rec[i] where ids[i] < n; other entries are never written
+    template <class Rec>
+    static void scatter_by_id(const std::vector<uint32_t>& ids, const std::vector<Rec>& rec, Rec* dst, size_t n) {
+        for (size_t i = 0; i < ids.size(); ++i)
+            if (ids[i] < n) dst[ids[i]] = rec[i];
     }
 };
 

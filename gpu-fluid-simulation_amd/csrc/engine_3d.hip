@@ -71,6 +71,8 @@ struct fs_sim3 {
         bool on = false;
         bool valid = false;          // a step has been enqueued since the feature was last enabled: st belongs to the state
     } tension;
+    // the opt-in particle tracking: the 2D engine's owner (engine.h), stride n; never enabled: no allocation, no launch
+    fsd::Tracking trk;
 
     // the arrays as the launchers see them (fs_3d.h): the force pass writes the new positions into the spare buffer
     fsd::Arrays3 arrays() const {
@@ -150,6 +152,7 @@ static fs_status enqueue3(fs_sim3* s, const fs3_tick_settings* t) {
     }
     if (ev) FS_HIP(hipEventRecord(ev[2], st));
     launch3_reorder(st, P, A);
+    s->trk.carry(st, s->n, s->pairs.p, s->n);              // particle tracking, if on (inside the FS_PASS_REORDER interval)
     if (ev) FS_HIP(hipEventRecord(ev[3], st));
     launch3_density(st, P, A, tol);
     if (ev) FS_HIP(hipEventRecord(ev[4], st));
@@ -457,6 +460,61 @@ fs_status fs3_download_surface_tension(fs_sim3* s, fs_vec3* dst, size_t n) {
     return sort_health3(s);
 }
 
+// ---- 3D particle tracking -----------------------------------------------------------------------------
+fs_status fs3_track_enable(fs_sim3* s, int channels) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    FS_HIP(hipSetDevice(s->device));
+    return s->trk.enable(s->stream, s->n, s->n, channels);
+}
+
+fs_status fs3_track_disable(fs_sim3* s) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    s->trk.channels = -1;           // the arrays stay allocated until the handle is destroyed
+    return FS_OK;
+}
+
+int fs3_track_channels(const fs_sim3* s) { return s ? s->trk.channels : -1; }
+
+}  // extern "C"
+namespace {
+// ids (attr = false) or one channel, host <-> the arrays of the last enqueued step.  Blocking.
+fs_status track3_copy(fs_sim3* s, int channel, bool attr, void* host, size_t n, bool upload) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    FS_HIP(hipSetDevice(s->device));
+    FS_TRY(s->trk.copy(s->stream, s->n, s->n, channel, attr, host, n, upload));
+    return upload ? FS_OK : sort_health3(s);
+}
+}  // namespace
+extern "C" {
+
+fs_status fs3_track_download_ids(fs_sim3* s, uint32_t* dst, size_t n) { return track3_copy(s, 0, false, dst, n, false); }
+fs_status fs3_track_upload_ids(fs_sim3* s, const uint32_t* src, size_t n) { return track3_copy(s, 0, false, (void*)src, n, true); }
+fs_status fs3_track_download_attr(fs_sim3* s, int channel, float* dst, size_t n) { return track3_copy(s, channel, true, dst, n, false); }
+fs_status fs3_track_upload_attr(fs_sim3* s, int channel, const float* src, size_t n) { return track3_copy(s, channel, true, (void*)src, n, true); }
+
+fs_status fs3_track_ids_device(fs_sim3* s, const uint32_t** out) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    return s->trk.device_ptr(s->n, 0, false, (const void**)out);
+}
+
+fs_status fs3_track_attr_device(fs_sim3* s, int channel, const float** out) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    return s->trk.device_ptr(s->n, channel, true, (const void**)out);
+}
+
+/* Off the step path: two downloads and a scatter on the host, so entries of dst that no id names are never written. */
+fs_status fs3_download_particles_by_id(fs_sim3* s, fs3_particle* dst, size_t n) {
+    if (!s || (!dst && n)) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->trk.on()) return fail(FS_ERR_INVALID, "tracking is off (enable it first)");
+    std::vector<fs3_particle> rec;
+    std::vector<uint32_t> ids;
+    try { rec.resize(s->n); ids.resize(s->n); } catch (const std::bad_alloc&) { return fail(FS_ERR_OOM, "host staging"); }
+    FS_TRY(fs3_download_particles(s, rec.data(), rec.size()));
+    FS_TRY(fs3_track_download_ids(s, ids.data(), ids.size()));
+    fsd::Tracking::scatter_by_id(ids, rec, dst, n);
+    return FS_OK;
+}
+
 // ---- 3D field sampling --------------------------------------------------------------------------------
 }  // extern "C"
 namespace {
@@ -468,6 +526,16 @@ fs_status sample3_check(fs_sim3* s, const void* points_or_view, size_t n, const 
     if (n > ((size_t)1 << 28)) return fail(FS_ERR_INVALID, "sampling: more than 2^28 points");
     if (s->sample_stale) return fail(FS_ERR_INVALID, "sampling needs a step since create and since the last upload of particles");
     *go = true;
+    return FS_OK;
+}
+
+// The view checks of the grid forms: *n = width * height * depth.
+fs_status sample3_grid_size(const fs3_view* view, size_t* n) {
+    if (!view) return fail(FS_ERR_INVALID, "null argument");
+    const uint64_t wh = (uint64_t)view->width * view->height;
+    if (wh == 0 || view->depth == 0 || wh > (1ull << 28) || wh * view->depth > (1ull << 28))
+        return fail(FS_ERR_INVALID, "bad grid size");
+    *n = (size_t)(wh * view->depth);
     return FS_OK;
 }
 
@@ -518,15 +586,79 @@ fs_status fs3_sample_points_device(fs_sim3* s, const fs_vec3* points_dev, size_t
 }
 
 fs_status fs3_sample_grid(fs_sim3* s, const fs3_view* view, fs3_sample* out) {
-    if (!s || !view) return fail(FS_ERR_INVALID, "null argument");
-    const uint64_t wh = (uint64_t)view->width * view->height;
-    if (wh == 0 || view->depth == 0 || wh > (1ull << 28) || wh * view->depth > (1ull << 28))
-        return fail(FS_ERR_INVALID, "bad grid size");
-    const size_t n = (size_t)(wh * view->depth);
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    size_t n;
+    FS_TRY(sample3_grid_size(view, &n));
     bool go;
     const fs_status r = sample3_check(s, view, n, out, &go);
     if (r != FS_OK || !go) return r;
     return sample3_host(s, nullptr, view, n, out);
+}
+
+// ---- the tracking channels in 3D field sampling -------------------------------------------------------
+}  // extern "C"
+namespace {
+// The checks of the three calls after the handle and (grid) the view, in the order the header lists them.  *go = false: n == 0.
+fs_status sample3_attr_check(fs_sim3* s, const void* points_or_view, size_t n, const void* attr_out, bool* go) {
+    *go = false;
+    if (s->trk.channels <= 0) return fail(FS_ERR_INVALID, "sampling: the channels need tracking with at least one channel");
+    return sample3_check(s, points_or_view, n, attr_out, go);
+}
+
+fs_status sample3_attr_enqueue(fs_sim3* s, const fs_vec3* points_dev, const fs3_view* view, size_t n, float* weight_dev, float* attr_dev) {
+    fsd::Sample3AttrQuery Q;
+    Q.n = (uint32_t)n;
+    Q.points = (const float*)points_dev;
+    if (view) {
+        Q.wmin = make_float3(view->world_min.x, view->world_min.y, view->world_min.z);
+        Q.wmax = make_float3(view->world_max.x, view->world_max.y, view->world_max.z);
+        Q.width = view->width; Q.height = view->height; Q.depth = view->depth;
+    }
+    Q.channels = s->trk.channels;
+    Q.attr = s->trk.channel(0, s->n); Q.attr_stride = s->n;
+    Q.weight_out = weight_dev; Q.attr_out = attr_dev;
+    fsd::launch3_sample_attr(s->stream, params3_common(*s, s->mass), s->arrays(), Q);
+    FS_HIP(hipGetLastError());
+    return FS_OK;
+}
+
+// The blocking forms: points == nullptr: the grid of `view`.  weight_out may be null.
+fs_status sample3_attr_host(fs_sim3* s, const fs_vec3* points, const fs3_view* view, size_t n, float* weight_out, float* attr_out) {
+    FS_HIP(hipSetDevice(s->device));
+    FS_TRY(fsd::staged_query(s->stream, points, n, weight_out, attr_out, (size_t)s->trk.channels,
+                             [&](const fs_vec3* dpts, float* dweight, float* dattr) {
+                                 return sample3_attr_enqueue(s, dpts, points ? nullptr : view, n, dweight, dattr);
+                             }));
+    return sort_health3(s);
+}
+}  // namespace
+extern "C" {
+
+fs_status fs3_sample_attr_points(fs_sim3* s, const fs_vec3* points, size_t n, float* weight_out, float* attr_out) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    bool go;
+    const fs_status r = sample3_attr_check(s, points, n, attr_out, &go);
+    if (r != FS_OK || !go) return r;
+    return sample3_attr_host(s, points, nullptr, n, weight_out, attr_out);
+}
+
+fs_status fs3_sample_attr_points_device(fs_sim3* s, const fs_vec3* points_dev, size_t n, float* weight_out_dev, float* attr_out_dev) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    bool go;
+    const fs_status r = sample3_attr_check(s, points_dev, n, attr_out_dev, &go);
+    if (r != FS_OK || !go) return r;
+    FS_HIP(hipSetDevice(s->device));
+    return sample3_attr_enqueue(s, points_dev, nullptr, n, weight_out_dev, attr_out_dev);
+}
+
+fs_status fs3_sample_attr_grid(fs_sim3* s, const fs3_view* view, float* weight_out, float* attr_out) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    size_t n;
+    FS_TRY(sample3_grid_size(view, &n));
+    bool go;
+    const fs_status r = sample3_attr_check(s, view, n, attr_out, &go);
+    if (r != FS_OK || !go) return r;
+    return sample3_attr_host(s, nullptr, view, n, weight_out, attr_out);
 }
 
 // ---- 3D surface rendering -----------------------------------------------------------------------------

@@ -42,37 +42,8 @@ fs_status fs_download_surface_tension(fs_sim* s, fs_vec2* dst, size_t n) {
 fs_status fs_track_enable(fs_sim* s, int channels) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
     if (s->slab) return fail(FS_ERR_UNSUPPORTED, "tracking: single-domain handles only (not built for slab handles)");
-    if (channels < 0 || channels > FS_TRACK_MAX_CHANNELS) return fail(FS_ERR_INVALID, "tracking: channels must be in [0, FS_TRACK_MAX_CHANNELS]");
     FS_HIP(hipSetDevice(s->device));
-    Tracking& T = s->trk;
-    if (!T.id[0].p) {
-        for (int k = 0; k < 2; ++k)
-            if (T.id[k].alloc(s->capacity) != hipSuccess) {
-                (void)hipGetLastError();
-                T.id[0].release(); T.id[1].release();
-                return fail(FS_ERR_OOM, "tracking: id arrays");
-            }
-    }
-    if (channels > T.alloc_channels) {
-        FS_HIP(hipStreamSynchronize(s->stream));      // steps in flight may still read the arrays about to be replaced
-        T.attr[0].release(); T.attr[1].release();
-        T.alloc_channels = 0;
-        for (int k = 0; k < 2; ++k)
-            if (T.attr[k].alloc((size_t)channels * s->capacity) != hipSuccess) {
-                (void)hipGetLastError();
-                T.attr[0].release(); T.attr[1].release();
-                T.channels = -1;
-                return fail(FS_ERR_OOM, "tracking: channel arrays");
-            }
-        T.alloc_channels = channels;
-    }
-    // on the simulation's stream: ordered after every step already enqueued, before every step enqueued from now on
-    T.cur = 0;
-    fsd::launch_track_iota(s->stream, s->n, T.ids());
-    FS_HIP(hipGetLastError());
-    if (channels && s->n) FS_HIP(hipMemsetAsync(T.attr[0].p, 0, (size_t)channels * s->capacity * sizeof(float), s->stream));
-    T.channels = channels;
-    return FS_OK;
+    return s->trk.enable(s->stream, s->n, s->capacity, channels);
 }
 
 fs_status fs_track_disable(fs_sim* s) {
@@ -88,17 +59,9 @@ int fs_track_channels(const fs_sim* s) { return s ? s->trk.channels : -1; }
 namespace {
 // ids (attr = false) or one channel, host <-> the arrays of the last enqueued step.  Blocking.
 fs_status track_copy(fs_sim* s, int channel, bool attr, void* host, size_t n, bool upload) {
-    if (!s || !host) return fail(FS_ERR_INVALID, "null argument");
-    if (!s->trk.on()) return fail(FS_ERR_INVALID, "tracking is off (fs_track_enable)");
-    if (attr && (channel < 0 || channel >= s->trk.channels)) return fail(FS_ERR_INVALID, "tracking: no such channel");
-    if (n != s->n) return fail(FS_ERR_INVALID, "tracking: n must equal the particle count");
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
     FS_HIP(hipSetDevice(s->device));
-    void* dev = attr ? (void*)s->trk.channel(channel, s->capacity) : (void*)s->trk.ids();
-    if (n) {
-        if (upload) FS_HIP(hipMemcpyAsync(dev, host, n * 4, hipMemcpyHostToDevice, s->stream));
-        else FS_HIP(hipMemcpyAsync(host, dev, n * 4, hipMemcpyDeviceToHost, s->stream));
-    }
-    FS_HIP(hipStreamSynchronize(s->stream));
+    FS_TRY(s->trk.copy(s->stream, s->n, s->capacity, channel, attr, host, n, upload));
     return upload ? FS_OK : sort_health(s);
 }
 }  // namespace
@@ -111,18 +74,13 @@ fs_status fs_track_download_attr(fs_sim* s, int channel, float* dst, size_t n) {
 fs_status fs_track_upload_attr(fs_sim* s, int channel, const float* src, size_t n) { return track_copy(s, channel, true, (void*)src, n, true); }
 
 fs_status fs_track_ids_device(fs_sim* s, const uint32_t** out) {
-    if (!s || !out) return fail(FS_ERR_INVALID, "null argument");
-    if (!s->trk.on()) return fail(FS_ERR_INVALID, "tracking is off (fs_track_enable)");
-    *out = s->trk.ids();
-    return FS_OK;
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    return s->trk.device_ptr(s->capacity, 0, false, (const void**)out);
 }
 
 fs_status fs_track_attr_device(fs_sim* s, int channel, const float** out) {
-    if (!s || !out) return fail(FS_ERR_INVALID, "null argument");
-    if (!s->trk.on()) return fail(FS_ERR_INVALID, "tracking is off (fs_track_enable)");
-    if (channel < 0 || channel >= s->trk.channels) return fail(FS_ERR_INVALID, "tracking: no such channel");
-    *out = s->trk.channel(channel, s->capacity);
-    return FS_OK;
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    return s->trk.device_ptr(s->capacity, channel, true, (const void**)out);
 }
 
 /* Off the step path: two downloads and a scatter on the host, so entries of dst that no id names are never written. */
@@ -136,8 +94,7 @@ fs_status fs_download_particles_by_id(fs_sim* s, fs_particle* dst, size_t n) {
     if (s->n) {
         FS_TRY(fs_track_download_ids(s, ids.data(), ids.size()));
     }
-    for (size_t i = 0; i < ids.size(); ++i)
-        if (ids[i] < n) dst[ids[i]] = rec[i];
+    Tracking::scatter_by_id(ids, rec, dst, n);
     return FS_OK;
 }
 

@@ -99,6 +99,21 @@ struct Sample3Query {
 };
 void launch3_sample(hipStream_t st, const Params3& P, const Arrays3& A, const Sample3Query& Q);
 
+// The tracking channels at the same queries (kernels_sample_attr3d.hip): pred and cs of the same state, `channels`
+// (1 .. FS_TRACK_MAX_CHANNELS) arrays of n floats in slot order, channel c at attr + c * attr_stride.
+struct Sample3AttrQuery {
+    uint32_t n = 0;                    // points, or width * height * depth
+    const float* points = nullptr;     // n fs_vec3, or nullptr: the voxel centres of the view below
+    float3 wmin{}, wmax{};
+    uint32_t width = 0, height = 0, depth = 0;
+    int channels = 0;
+    const float* attr = nullptr;
+    uint32_t attr_stride = 0;
+    float* weight_out = nullptr;       // n floats, or nullptr
+    float* attr_out = nullptr;         // channel c at attr_out + c * n
+};
+void launch3_sample_attr(hipStream_t st, const Params3& P, const Arrays3& A, const Sample3AttrQuery& Q);
+
 // 3D surface rendering (kernels_render3d.hip): one ray per pixel of a width x height image, marched against the
 // same state and the same P as a Sample3Query.  Passed to the kernel by value.
 struct Surface3Query {

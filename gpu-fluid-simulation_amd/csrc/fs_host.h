@@ -56,14 +56,15 @@ struct DevArray {
 };
 
 // The blocking form of a point query (fs_sample_*, fs3_sample_*): device staging for the points (none: the query is a grid), the
-// records and `ch` channel sums per point; `enqueue(points_dev, out_dev, attr_dev)` puts the kernel on `st` and returns a status.
+// records (none: `out` is null, fs3_sample_attr_* without weights) and `ch` channel sums per point; `enqueue(points_dev, out_dev,
+// attr_dev)` puts the kernel on `st` and returns a status.
 template <class Pt, class Rec, class Enqueue>
 fs_status staged_query(hipStream_t st, const Pt* points, size_t n, Rec* out, float* attr_out, size_t ch, Enqueue enqueue) {
     DevArray<Pt> dpts;
     DevArray<Rec> dout;
     DevArray<float> dattr;
     hipError_t e = points ? dpts.alloc(n) : hipSuccess;
-    if (e == hipSuccess) e = dout.alloc(n);
+    if (e == hipSuccess) e = dout.alloc(out ? n : 0);
     if (e == hipSuccess) e = dattr.alloc(ch * n);
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -73,7 +74,7 @@ fs_status staged_query(hipStream_t st, const Pt* points, size_t n, Rec* out, flo
     if (points) e = hipMemcpyAsync(dpts.p, points, n * sizeof(Pt), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
         r = enqueue(dpts.p, dout.p, dattr.p);
-        if (r == FS_OK) e = hipMemcpyAsync(out, dout.p, n * sizeof(Rec), hipMemcpyDeviceToHost, st);
+        if (r == FS_OK && out) e = hipMemcpyAsync(out, dout.p, n * sizeof(Rec), hipMemcpyDeviceToHost, st);
         if (r == FS_OK && e == hipSuccess && ch) e = hipMemcpyAsync(attr_out, dattr.p, ch * n * sizeof(float), hipMemcpyDeviceToHost, st);
     }
     const hipError_t es = hipStreamSynchronize(st);      // before the staging is freed, whatever happened

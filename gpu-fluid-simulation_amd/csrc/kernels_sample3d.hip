@@ -12,10 +12,8 @@
 // range [cs[id_lo], cs[id_lo + count]) of the dense cell-start table, walked ascending: exactly the order above.  A skipped
 // candidate adds nothing — a branch, not an added zero: the velocity and gradient terms can be -0.
 //
-// One lane per query keeps that order for free; nothing is staged.  As in 2D the ORDER of the queries decides the speed: lanes
-// of a wave that fall into the same or adjacent cells walk the same cache lines and leave the loops together.  A grid is
-// therefore taken in wave tiles that are compact in every axis that has extent (launch3_sample picks them).
-#include "fs_3d.h"
+// One lane per query keeps that order for free; nothing is staged.  The wave tiles a grid is taken in: fs_sample3.h.
+#include "fs_sample3.h"
 
 namespace fsd {
 
@@ -24,16 +22,6 @@ struct Sample3Rec {                // fs3_sample (include/fluidsim.h), 40 bytes
     uint32_t neighbours, cell;
 };
 static_assert(sizeof(Sample3Rec) == 40, "fs3_sample is 40 bytes");
-
-#define B3S 256                    // workgroup: four waves, one query per lane
-
-// The 256 threads of a workgroup over a GRID tile: the low bits of the lane (then of the wave) number go to x, the next to y,
-// the rest to z.  lane = log2 extents of a wave's tile (they sum to 6), wave = those of the 2 x 2 (x 1) waves of a workgroup.
-struct Sample3Tile {
-    uint32_t lx, ly, wx, wy;       // log2: lane bits in x, in y (z: the rest); wave bits in x, in y (z: the rest)
-    uint32_t tx, ty, tz;           // log2 extents of the workgroup's tile
-    uint32_t nbx, nby;             // workgroup tiles along x, along y
-};
 
 // GRID: the points are the voxel centres of a view (fs_sample_grid's expression per axis) instead of loaded.
 template <bool GRID>
@@ -45,16 +33,7 @@ __global__ __launch_bounds__(B3S) void k3_sample(Params3 P, uint32_t nq, const f
     size_t q;
     float x, y, z;
     if (GRID) {
-        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-        const uint32_t bi = blockIdx.x % T.nbx, bj = (blockIdx.x / T.nbx) % T.nby, bk = blockIdx.x / (T.nbx * T.nby);
-        const uint32_t i = (bi << T.tx) + ((wave & ((1u << T.wx) - 1u)) << T.lx) + (lane & ((1u << T.lx) - 1u));
-        const uint32_t j = (bj << T.ty) + (((wave >> T.wx) & ((1u << T.wy) - 1u)) << T.ly) + ((lane >> T.lx) & ((1u << T.ly) - 1u));
-        const uint32_t k = (bk << T.tz) + ((wave >> (T.wx + T.wy)) << (6u - T.lx - T.ly)) + (lane >> (T.lx + T.ly));
-        if (i >= width || j >= height || k >= depth) return;        // edge tiles are masked
-        q = ((size_t)k * height + j) * width + i;
-        x = wmin.x + __fdiv_rn((float)i + 0.5f, (float)width) * (wmax.x - wmin.x);
-        y = wmin.y + __fdiv_rn((float)j + 0.5f, (float)height) * (wmax.y - wmin.y);
-        z = wmin.z + __fdiv_rn((float)k + 0.5f, (float)depth) * (wmax.z - wmin.z);
+        if (!sample3_tile_voxel(T, wmin, wmax, width, height, depth, &q, &x, &y, &z)) return;
     } else {
         q = (size_t)blockIdx.x * B3S + threadIdx.x;
         if (q >= nq) return;
@@ -107,26 +86,6 @@ __global__ __launch_bounds__(B3S) void k3_sample(Params3 P, uint32_t nq, const f
     out[q] = r;
 }
 
-// The wave tile of a view: six lane bits dealt round-robin (x, y, z) to the axes that have extent — 4 x 4 x 4 voxels for a
-// volume, 8 x 8 for a slice, 64 in a row for a line —, then the two wave bits of the workgroup the same way (8 x 8 x 4,
-// 16 x 16, 256).
-static Sample3Tile sample3_tile(uint32_t width, uint32_t height, uint32_t depth) {
-    const bool has[3] = {width > 1u, height > 1u || (width <= 1u && depth <= 1u), depth > 1u};
-    uint32_t lane[3] = {0, 0, 0}, wave[3] = {0, 0, 0};
-    int a = 0;
-    for (int bit = 0; bit < 8; ++bit) {
-        while (!has[a]) a = (a + 1) % 3;
-        (bit < 6 ? lane : wave)[a] += 1u;
-        a = (a + 1) % 3;
-    }
-    Sample3Tile T;
-    T.lx = lane[0]; T.ly = lane[1]; T.wx = wave[0]; T.wy = wave[1];
-    T.tx = lane[0] + wave[0]; T.ty = lane[1] + wave[1]; T.tz = lane[2] + wave[2];
-    T.nbx = (width + (1u << T.tx) - 1u) >> T.tx;
-    T.nby = (height + (1u << T.ty) - 1u) >> T.ty;
-    return T;
-}
-
 void launch3_sample(hipStream_t st, const Params3& P, const Arrays3& A, const Sample3Query& Q) {
     if (Q.n == 0u) return;
     if (Q.points) {
@@ -134,8 +93,7 @@ void launch3_sample(hipStream_t st, const Params3& P, const Arrays3& A, const Sa
                            Q.wmax, Q.width, Q.height, Q.depth, Sample3Tile{}, A.pred, A.vel, A.cs, (Sample3Rec*)Q.out);
     } else {
         const Sample3Tile T = sample3_tile(Q.width, Q.height, Q.depth);
-        const uint32_t nbz = (Q.depth + (1u << T.tz) - 1u) >> T.tz;
-        hipLaunchKernelGGL(k3_sample<true>, dim3(T.nbx * T.nby * nbz), dim3(B3S), 0, st, P, Q.n, Q.points, Q.wmin, Q.wmax,
+        hipLaunchKernelGGL(k3_sample<true>, dim3(sample3_tile_blocks(T, Q.depth)), dim3(B3S), 0, st, P, Q.n, Q.points, Q.wmin, Q.wmax,
                            Q.width, Q.height, Q.depth, T, A.pred, A.vel, A.cs, (Sample3Rec*)Q.out);
     }
 }

@@ -263,6 +263,47 @@ public:
         check(fs3_download_surface_tension(h_, v.data(), v.size()));
         return v;
     }
+    // 3D particle tracking: every particle gets an id (its current slot) and `channels` float attributes (all 0) that follow it
+    // through the sort of every later tick.
+    void track(int channels = 0) { check(fs3_track_enable(h_, channels)); }
+    void untrack() { check(fs3_track_disable(h_)); }
+    int track_channels() const { return fs3_track_channels(h_); }   // -1: off
+    std::vector<uint32_t> particle_ids() {
+        std::vector<uint32_t> v(particle_count());
+        check(fs3_track_download_ids(h_, v.data(), v.size()));
+        return v;
+    }
+    void set_particle_ids(const std::vector<uint32_t>& v) { check(fs3_track_upload_ids(h_, v.data(), v.size())); }
+    std::vector<float> attribute(int channel) {
+        std::vector<float> v(particle_count());
+        check(fs3_track_download_attr(h_, channel, v.data(), v.size()));
+        return v;
+    }
+    void set_attribute(int channel, const std::vector<float>& v) { check(fs3_track_upload_attr(h_, channel, v.data(), v.size())); }
+    const uint32_t* particle_ids_device() { const uint32_t* p = nullptr; check(fs3_track_ids_device(h_, &p)); return p; }
+    const float* attribute_device(int channel) { const float* p = nullptr; check(fs3_track_attr_device(h_, channel, &p)); return p; }
+    // dst[id] = the record of the particle with that id; entries that no id names are left as they are
+    void download_by_id(std::vector<fs3_particle>& dst) { check(fs3_download_particles_by_id(h_, dst.data(), dst.size())); }
+    // 3D channel sampling: the un-normalised SPH sums of the tracking channels at any points, channel c of query q at c * n + q;
+    // `weight` (may be null) receives the Shepard denominators.  Needs track(channels >= 1) and a tick since the last upload.
+    std::vector<float> sample_attr(const std::vector<fs_vec3>& points, std::vector<float>* weight = nullptr) {
+        std::vector<float> attr((size_t)(track_channels() > 0 ? track_channels() : 0) * points.size(), 0.0f);
+        if (weight) weight->assign(points.size(), 0.0f);
+        check(fs3_sample_attr_points(h_, points.data(), points.size(), weight ? weight->data() : nullptr, attr.data()));
+        return attr;
+    }
+    // ... at the voxel centres of `view` (sample_grid's order); bit-identical to sample_attr() on those points
+    std::vector<float> sample_attr_grid(const fs3_view& view, std::vector<float>* weight = nullptr) {
+        const size_t n = (size_t)view.width * view.height * view.depth;
+        std::vector<float> attr((size_t)(track_channels() > 0 ? track_channels() : 0) * n, 0.0f);
+        if (weight) weight->assign(n, 0.0f);
+        check(fs3_sample_attr_grid(h_, &view, weight ? weight->data() : nullptr, attr.data()));
+        return attr;
+    }
+    // ... with device pointers, enqueued on the simulation's stream after the ticks in flight; non-blocking
+    void sample_attr_device(const fs_vec3* points_dev, size_t n, float* weight_out_dev, float* attr_out_dev) {
+        check(fs3_sample_attr_points_device(h_, points_dev, n, weight_out_dev, attr_out_dev));
+    }
     fs_sim3* handle() { return h_; }
 
 private:

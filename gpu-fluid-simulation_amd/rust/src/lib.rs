@@ -236,6 +236,19 @@ extern "C" {
     fn fs3_sample_points(sim: *mut fs_sim3, points: *const Vec3, n: usize, out: *mut Sample3) -> c_int;
     fn fs3_sample_points_device(sim: *mut fs_sim3, points_dev: *const Vec3, n: usize, out_dev: *mut Sample3) -> c_int;
     fn fs3_sample_grid(sim: *mut fs_sim3, view: *const View3, out: *mut Sample3) -> c_int;
+    fn fs3_track_enable(sim: *mut fs_sim3, channels: c_int) -> c_int;
+    fn fs3_track_disable(sim: *mut fs_sim3) -> c_int;
+    fn fs3_track_channels(sim: *const fs_sim3) -> c_int;
+    fn fs3_track_download_ids(sim: *mut fs_sim3, dst: *mut u32, n: usize) -> c_int;
+    fn fs3_track_upload_ids(sim: *mut fs_sim3, src: *const u32, n: usize) -> c_int;
+    fn fs3_track_download_attr(sim: *mut fs_sim3, channel: c_int, dst: *mut f32, n: usize) -> c_int;
+    fn fs3_track_upload_attr(sim: *mut fs_sim3, channel: c_int, src: *const f32, n: usize) -> c_int;
+    fn fs3_track_ids_device(sim: *mut fs_sim3, out: *mut *const u32) -> c_int;
+    fn fs3_track_attr_device(sim: *mut fs_sim3, channel: c_int, out: *mut *const f32) -> c_int;
+    fn fs3_download_particles_by_id(sim: *mut fs_sim3, dst: *mut Particle3, n: usize) -> c_int;
+    fn fs3_sample_attr_points(sim: *mut fs_sim3, points: *const Vec3, n: usize, weight_out: *mut f32, attr_out: *mut f32) -> c_int;
+    fn fs3_sample_attr_points_device(sim: *mut fs_sim3, points_dev: *const Vec3, n: usize, weight_out_dev: *mut f32, attr_out_dev: *mut f32) -> c_int;
+    fn fs3_sample_attr_grid(sim: *mut fs_sim3, view: *const View3, weight_out: *mut f32, attr_out: *mut f32) -> c_int;
     fn fs3_render_surface(sim: *mut fs_sim3, camera: *const Camera3, params: *const SurfaceParams3, out_host: *mut SurfaceHit3) -> c_int;
     fn fs3_render_surface_device(sim: *mut fs_sim3, camera: *const Camera3, params: *const SurfaceParams3, out_dev: *mut SurfaceHit3) -> c_int;
     fn fs3_extract_surface(sim: *mut fs_sim3, view: *const View3, iso: f32, verts: *mut MeshVertex3, vert_cap: u32, tris: *mut u32, tri_cap: u32, counts: *mut u32) -> c_int;
@@ -683,6 +696,60 @@ impl FluidSimulation3D {
     pub fn surface_tension_forces(&mut self) -> Vec<Vec3> {
         let mut v = vec![Vec3::default(); self.particle_count() as usize];
         check(unsafe { fs3_download_surface_tension(self.raw, v.as_mut_ptr(), v.len()) }); v
+    }
+    /// Build extension: 3D particle tracking (include/fluidsim.h).  Every particle gets an id (its current slot) and `channels`
+    /// f32 attributes (all 0.0) that follow it through the sort of every later step.
+    pub fn track(&mut self, channels: u32) { check(unsafe { fs3_track_enable(self.raw, channels as c_int) }); }
+    pub fn untrack(&mut self) { check(unsafe { fs3_track_disable(self.raw) }); }
+    /// `None` when tracking is off.
+    pub fn track_channels(&self) -> Option<u32> {
+        let c = unsafe { fs3_track_channels(self.raw) };
+        if c < 0 { None } else { Some(c as u32) }
+    }
+    /// The id of the particle in every slot, in `download_particles` order.
+    pub fn particle_ids(&mut self) -> Vec<u32> {
+        let mut v = vec![0u32; self.particle_count() as usize];
+        check(unsafe { fs3_track_download_ids(self.raw, v.as_mut_ptr(), v.len()) }); v
+    }
+    pub fn set_particle_ids(&mut self, ids: &[u32]) { check(unsafe { fs3_track_upload_ids(self.raw, ids.as_ptr(), ids.len()) }); }
+    pub fn attribute(&mut self, channel: u32) -> Vec<f32> {
+        let mut v = vec![0f32; self.particle_count() as usize];
+        check(unsafe { fs3_track_download_attr(self.raw, channel as c_int, v.as_mut_ptr(), v.len()) }); v
+    }
+    pub fn set_attribute(&mut self, channel: u32, values: &[f32]) {
+        check(unsafe { fs3_track_upload_attr(self.raw, channel as c_int, values.as_ptr(), values.len()) });
+    }
+    /// Device pointers to the arrays of the last enqueued step; valid until the next tick / upload / `track`.
+    pub fn particle_ids_device(&mut self) -> *const u32 {
+        let mut p: *const u32 = std::ptr::null();
+        check(unsafe { fs3_track_ids_device(self.raw, &mut p) }); p
+    }
+    pub fn attribute_device(&mut self, channel: u32) -> *const f32 {
+        let mut p: *const f32 = std::ptr::null();
+        check(unsafe { fs3_track_attr_device(self.raw, channel as c_int, &mut p) }); p
+    }
+    /// `dst[id]` = the record of the particle with that id; entries of `dst` that no id names are left as they are.
+    pub fn download_particles_by_id(&mut self, dst: &mut [Particle3]) {
+        check(unsafe { fs3_download_particles_by_id(self.raw, dst.as_mut_ptr(), dst.len()) });
+    }
+    /// Build extension: 3D channel sampling (include/fluidsim.h).  (weights, sums): the Shepard denominators and the
+    /// un-normalised SPH sums of the tracking channels at `points`, channel c of query q at `c * n + q`.  Needs
+    /// `track(channels >= 1)` and a tick since the last upload.
+    pub fn sample_attr(&mut self, points: &[Vec3]) -> (Vec<f32>, Vec<f32>) {
+        let ch = self.track_channels().unwrap_or(0) as usize;
+        let (mut w, mut a) = (vec![0f32; points.len()], vec![0f32; ch * points.len()]);
+        check(unsafe { fs3_sample_attr_points(self.raw, points.as_ptr(), points.len(), w.as_mut_ptr(), a.as_mut_ptr()) }); (w, a)
+    }
+    /// `sample_attr` at the voxel centres of `view` (`sample_grid`'s order); bit-identical to `sample_attr` there.
+    pub fn sample_attr_grid(&mut self, view: &View3) -> (Vec<f32>, Vec<f32>) {
+        let n = view.width as usize * view.height as usize * view.depth as usize;
+        let ch = self.track_channels().unwrap_or(0) as usize;
+        let (mut w, mut a) = (vec![0f32; n], vec![0f32; ch * n]);
+        check(unsafe { fs3_sample_attr_grid(self.raw, view, w.as_mut_ptr(), a.as_mut_ptr()) }); (w, a)
+    }
+    /// Device pointers on the simulation's device (`weight_out_dev` may be null); enqueued on its stream, non-blocking.
+    pub unsafe fn sample_attr_device(&mut self, points_dev: *const Vec3, n: usize, weight_out_dev: *mut f32, attr_out_dev: *mut f32) {
+        check(fs3_sample_attr_points_device(self.raw, points_dev, n, weight_out_dev, attr_out_dev));
     }
     pub fn stream(&self) -> *mut c_void { unsafe { fs3_stream(self.raw) } }
 }

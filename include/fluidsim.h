@@ -604,6 +604,72 @@ fs_status fs3_sample_points(fs_sim3* sim, const fs_vec3* points, size_t n, fs3_s
 fs_status fs3_sample_points_device(fs_sim3* sim, const fs_vec3* points_dev, size_t n, fs3_sample* out_dev);
 fs_status fs3_sample_grid(fs_sim3* sim, const fs3_view* view, fs3_sample* out);
 
+/* ------------------------------------------------ 3D particle tracking (build extension, opt-in) */
+/* The 3D counterpart of "particle tracking" above: every fs3_step cell-sorts the records and they carry no id, so "index i" names
+ * a different particle after every tick.  With tracking on, the handle keeps per particle a uint32_t id and C float channels
+ * (0 <= C <= FS_TRACK_MAX_CHANNELS), stored in slot order (fs3_download_particles' order) and permuted by every step exactly as the
+ * records are.  Let src[i] be the slot, in the order before a step, of the particle which that step places in slot i (the
+ * permutation the step's sort applies: the bitonic network's; the 3D engine has no other sort).  After the step:
+ *     id[i]      = id_before[src[i]]
+ *     attr[c][i] = attr_before[c][src[i]]      for c < C      (bit copies: NaN payloads, -0 and denormals survive)
+ * Nothing else reads or writes them: the simulation state is bit-identical with tracking on or off, in both math modes, with
+ * or without a collider or surface tension.  One gather pass per step, timed inside the FS_PASS_REORDER interval of
+ * fs3_profile_read; with tracking off no launch and no allocation.  See DESIGN.md §20.
+ *
+ * fs3_upload_particles does NOT touch ids or channels: it replaces the records of slots, and identity stays with the slot, so
+ * download -> edit -> upload keeps every id.
+ *
+ * fs3_track_enable: allocates on first use (8 B + 8 B per channel, per particle) and (re)initialises id[i] = i (the slot held
+ *   at the moment of the call, i.e. fs3_download_particles' current order) and every channel to +0.0f.  Calling it again
+ *   re-initialises, also with another channel count.  channels < 0 or > FS_TRACK_MAX_CHANNELS: FS_ERR_INVALID.  Takes effect
+ *   for steps enqueued after the call and is ordered after the steps already in flight.
+ * fs3_track_disable: later steps do not carry; the read calls below then return FS_ERR_INVALID.  Off is the default.
+ * fs3_track_channels: -1 when off, else C.
+ * fs3_track_download_* / fs3_track_upload_*: blocking host copies in slot order.  n must equal the particle count and channel
+ *   must be < C, else FS_ERR_INVALID.  Uploaded ids are the caller's business (any uint32_t, duplicates allowed).
+ * fs3_track_ids_device / fs3_track_attr_device: device pointers to the arrays of the last enqueued step (stream-ordered on
+ *   fs3_stream), for a renderer on the same device.  Valid until the next fs3_step / fs3_timed_steps / upload / enable: the
+ *   arrays ping-pong.
+ * fs3_download_particles_by_id: dst[id[i]] = particle[i] for every slot with id[i] < n; entries of dst that no id names are
+ *   left exactly as the caller passed them; with duplicate ids it is unspecified which record wins.  n is the length of dst
+ *   and need not equal the particle count.  Blocking; off the step path. */
+fs_status fs3_track_enable(fs_sim3* sim, int channels);
+fs_status fs3_track_disable(fs_sim3* sim);
+int fs3_track_channels(const fs_sim3* sim);
+fs_status fs3_track_download_ids(fs_sim3* sim, uint32_t* dst, size_t n);
+fs_status fs3_track_upload_ids(fs_sim3* sim, const uint32_t* src, size_t n);
+fs_status fs3_track_download_attr(fs_sim3* sim, int channel, float* dst, size_t n);
+fs_status fs3_track_upload_attr(fs_sim3* sim, int channel, const float* src, size_t n);
+fs_status fs3_track_ids_device(fs_sim3* sim, const uint32_t** out);
+fs_status fs3_track_attr_device(fs_sim3* sim, int channel, const float** out);
+fs_status fs3_download_particles_by_id(fs_sim3* sim, fs3_particle* dst, size_t n);
+
+/* ------------------------------------------------ 3D channel sampling (build extension, opt-in by being called) */
+/* The SPH interpolant of the tracking channels at arbitrary points: what shows a carried dye, age or temperature on a slice, on a
+ * ray-marched surface (sample at the hit points) or on a mesh (sample at the vertices).  The statement is that of "3D field
+ * sampling" with the same cells, order, skip rules and `r2 > h2` branch, the same W and the same
+ *     t = (m / p[k].density) * W                                  IEEE division by the stored density, f32 without contraction
+ * and, with attr[c] what fs3_track_download_attr returns and C = fs3_track_channels(sim), for an in-radius candidate k:
+ *     weight += t;  a_c += t * attr[c][k]      for c < C
+ * The sums start at +0.0f; a skipped candidate is a branch, not an added zero.  The results are un-normalised: a_c / weight is the
+ * Shepard value.  Two identities follow, bit for bit, on the same points: `weight` is fs3_sample.weight; a channel that holds
+ * 1.0f in every slot sums to `weight`, and channels that hold the stored velocity.x / .y / .z of every slot sum to
+ * fs3_sample.velocity.  A pure function of the stored state, in both math modes.
+ *
+ * Outputs: attr_out[c * n + q] = a_c of query q (n = width * height * depth for a grid, voxel order and voxel centres those of
+ * fs3_sample_grid); weight_out may be NULL, else weight_out[q] = weight.
+ * fs3_sample_attr_points / fs3_sample_attr_grid: host pointers, blocking; the grid form is bit-identical to the point form on
+ *   fs3_sample_grid's voxel centres.
+ * fs3_sample_attr_points_device: device pointers on the handle's device; enqueued on fs3_stream(sim) after the steps in flight;
+ *   stream-ordered, non-blocking, no allocation, no host read.  The buffers must stay valid until the stream has passed the call.
+ * Checks, in this order: NULL handle -> FS_ERR_INVALID; (grid) NULL view, a zero extent, or width * height * depth > 2^28 ->
+ * FS_ERR_INVALID; tracking off or C == 0 -> FS_ERR_INVALID; n == 0 -> FS_OK, nothing touched; NULL points / attr_out ->
+ * FS_ERR_INVALID; n > 2^28 -> FS_ERR_INVALID; no step enqueued since create or since the last fs3_upload_particles with n > 0 ->
+ * FS_ERR_INVALID.  See DESIGN.md §20. */
+fs_status fs3_sample_attr_points(fs_sim3* sim, const fs_vec3* points, size_t n, float* weight_out, float* attr_out);
+fs_status fs3_sample_attr_points_device(fs_sim3* sim, const fs_vec3* points_dev, size_t n, float* weight_out_dev, float* attr_out_dev);
+fs_status fs3_sample_attr_grid(fs_sim3* sim, const fs3_view* view, float* weight_out, float* attr_out);
+
 /* ------------------------------------------------ 3D surface rendering (build extension, opt-in by being called) */
 /* A headless ray-marcher over the field of "3D field sampling": one ray per pixel is marched through the density until it reaches
  * `iso`, the crossing is refined by bisection, and one full sample at the hit gives the G-buffer record (distance, density,

@@ -1,6 +1,8 @@
 """Render a few frames of the 3D dam break to PNG through the ray-marched G-buffer, headless:
   python tools/render_frames3d.py [n] [frame,frame,...] [outdir] [width] [height] [--box x0,y0,z0,x1,y1,z1[,voxels]]
-                                  [--surface-tension SIGMA[,TAU]]
+                                  [--surface-tension SIGMA[,TAU]] [--dye]
+--dye: particle tracking with one channel: the particles of the -x half of the initial block carry 1.0, the others
+0.0; the shaded surface is tinted red by the Shepard value of the channel at the hit points (sampled there with sample_attr).
 --surface-tension: the opt-in colour-field surface tension with coefficient SIGMA and threshold TAU (default 1.0).
 --box: a static obstacle, a box in world coordinates (+y is the floor) rasterised to a mask of `voxels` (default
 64) voxels along x and as many along y and z as keep them near cubes; the fluid flows around it, the box itself is not drawn."""
@@ -18,6 +20,9 @@ if "--surface-tension" in sys.argv:
     k = sys.argv.index("--surface-tension")
     tension = [float(x) for x in sys.argv[k + 1].split(",")]
     del sys.argv[k:k + 2]
+dye = "--dye" in sys.argv
+if dye:
+    sys.argv.remove("--dye")
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 64 ** 3
 frames = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [1, 60, 150, 300]
 outdir = sys.argv[3] if len(sys.argv) > 3 else "build/frames3d"
@@ -35,6 +40,10 @@ if box is not None:
 if tension is not None:
     sim.set_surface_tension(tension[0], tension[1] if len(tension) > 1 else 1.0)
     print("surface tension", sim.surface_tension_params, flush=True)
+if dye:
+    x0 = sim.download_particles()["position"][:, 0]
+    sim.track(1)                                    # ids = the slots of this download
+    sim.set_attribute(0, (x0 < np.median(x0)).astype(np.float32))
 # gravity is +y: "up" is -y.  From in front of the -z wall, above the floor, looking at the middle of the tank.
 eye = (-0.15 * sx, -0.55 * sy, -0.5 * sz - 0.9 * sx)
 cam = g.look_at_camera(eye, (0.0, 0.15 * sy, 0.0), (0.0, -1.0, 0.0), np.radians(42.0), width, height)
@@ -47,6 +56,15 @@ for f in frames:
     reach = 1.2 * (abs(eye[2]) + 0.5 * sz) + sx
     hits = sim.render_surface(cam, g.SurfaceParams3(iso, 0.0, 0.5 * h, min(4096, int(reach / (0.5 * h)) + 1), 8))
     rgba = g.shade_surface(hits, max_speed=6.0)[::-1]                 # row 0 of the G-buffer is the image's bottom edge
+    if dye:                                         # visual only: the channel's Shepard value where the rays hit
+        lit = hits["hit"] != 0
+        wgt, sums = sim.sample_attr(g.surface_hit_points(cam, hits)[lit], weights=True)
+        c = np.zeros(hits.shape, dtype=np.float32)
+        c[lit] = np.where(wgt > 0, sums[0] / np.where(wgt > 0, wgt, 1), 0)
+        c = c[::-1, :, None]
+        shade = rgba[..., :3].max(axis=-1, keepdims=True)
+        rgba[..., :3] = rgba[..., :3] * (1 - c) + np.float32([0.9, 0.15, 0.1]) * shade * c
+        print("frame", f, "dyed share of the hits", round(float(c[rgba[..., 3] > 0].mean()), 4), flush=True)
     g.write_png(os.path.join(outdir, f"dam3d_{n}_{f:05d}.png"), rgba, background=(0.04, 0.04, 0.06))
     print("frame", f, "coverage", round(float((hits["hit"] != 0).mean()), 4), "mean march index of hits",
           round(float(hits["steps"][hits["hit"] != 0].mean()), 1), flush=True)
