@@ -5,6 +5,9 @@
 -fno-slp-vectorize (float kernels, see NO_SLP): at -O3 the SLP vectoriser packs adjacent scalar f32 mul/add into v_pk_* ops;
 on gfx950 those issue at half rate and cost extra v_mov to line the operands up (measured at 16M:
 force 0.93 -> 0.85 ms, density 0.30 -> 0.29 ms without it; same bits either way).
+
+SOURCES are the translation units; HEADERS is everything else a unit reads — the headers and the .inc fragments that are
+compiled as part of kernels_sort.hip and kernels_force.hip — so that touching any of them makes the library stale.
 """
 import os
 import subprocess
@@ -14,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libfluidsim_hip.so")
 SOURCES = ["engine.hip", "engine_features.hip", "engine_query.hip", "engine_selftest.hip", "engine_slab.hip", "comm.hip", "buffer.hip", "kernels_reorder.hip", "kernels_density.hip", "kernels_force.hip", "kernels_proof.hip", "kernels_sort.hip", "kernels_slab.hip", "kernels_strip.hip", "kernels_csort.hip", "kernels_field.hip", "kernels_track.hip", "kernels_sample.hip", "kernels_3d.hip", "kernels_density3d.hip", "kernels_force3d.hip", "kernels_sample3d.hip", "kernels_sample_attr3d.hip", "kernels_render3d.hip", "kernels_mesh3d.hip", "kernels_collide3d.hip", "engine_3d.hip"]
-HEADERS = ["engine.h", "fs_3d.h", "fs_device.h", "fs_field3.h", "fs_host.h", "fs_kernels.h", "fs_neighbours.h", "fs_sample3.h", "fs_scan.h", "fs_slab.h", "fs_sort.h", "fs_sort_tile.h", "fs_sweep3.h", "kernels_sort_tile.inc", "kernels_sort_global.inc", "sort_policy.h", os.path.join("..", "..", "include", "fluidsim.h")]
+HEADERS = ["engine.h", "fs_3d.h", "fs_device.h", "fs_field3.h", "fs_force_lists.h", "fs_force_pair.h", "fs_force_sweep.h", "fs_host.h", "fs_kernels.h", "fs_neighbours.h", "fs_sample3.h", "fs_scan.h", "fs_slab.h", "fs_sort.h", "fs_sort_tile.h", "fs_sweep3.h", "kernels_force_quad.inc", "kernels_sort_tile.inc", "kernels_sort_global.inc", "sort_policy.h", os.path.join("..", "..", "include", "fluidsim.h")]
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",
@@ -28,6 +31,7 @@ FLAGS = [
 
 
 # kernels_sort_tile.inc and kernels_sort_global.inc are compiled as part of kernels_sort.hip (see its last lines): HEADERS.
+# kernels_force_quad.inc likewise, as part of kernels_force.hip (it uses that file's integrator and parameter list).
 # float-heavy kernels only: the integer sort kernels measured ~1 % faster with the vectoriser on
 # (kernels_reorder.hip and kernels_proof.hip hold no such arithmetic; the flag is the one their kernels were measured with)
 NO_SLP = {"kernels_reorder.hip", "kernels_density.hip", "kernels_force.hip", "kernels_proof.hip", "kernels_3d.hip", "kernels_density3d.hip", "kernels_force3d.hip", "kernels_slab.hip", "kernels_strip.hip", "kernels_sample.hip", "kernels_sample3d.hip", "kernels_sample_attr3d.hip", "kernels_render3d.hip", "kernels_mesh3d.hip"}

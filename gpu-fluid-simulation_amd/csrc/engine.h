@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/fluidsim.h"
+#include "fs_force_lists.h"
 #include "fs_host.h"
 #include "fs_kernels.h"
 #include "sort_policy.h"
@@ -25,7 +26,7 @@ struct ParticleArrays {
     DevArray<float2> pos, vel, pos_s, vel_s, pred;
     DevArray<float> rho;
     DevArray<float2> rho2;          // {density, RN(1/density)}: what the force pass gathers per neighbour
-    DevArray<uint32_t> fdefer, fwork;   // force pass: per-block deferred-wave bits and the worklist (counter[3] = its length)
+    DevArray<uint32_t> fdefer, fwork;   // force pass: per-block deferred-wave bits and the worklist (fs_force_lists.h; its counters: counter[4..5])
     DevArray<uint32_t> bbounds;         // 8 words per 256-particle block: the density pass's block-wide sweep ranges, read by the force pass
     DevArray<unsigned long long> safe;   // one bit per sorted particle: coordinates / velocity inside the exact-quotient ranges (fs_device.h)
     DevArray<u64> pairs;
@@ -41,7 +42,7 @@ struct ParticleArrays {
         auto ok = [&e](hipError_t r) { e = r; return r == hipSuccess; };
         (void)(ok(pos.alloc(cap)) && ok(vel.alloc(cap)) && ok(pos_s.alloc(cap)) && ok(vel_s.alloc(cap)) &&
                ok(pred.alloc(cap + FS_PRED_SLACK)) && ok(rho.alloc(cap)) && ok(rho2.alloc(cap)) && ok(safe.alloc((cap + 63) / 64 + 1)) &&
-               ok(fdefer.alloc(2 * ((cap + 255) / 256 + 8))) && ok(fwork.alloc(2 * (cap / 256 + 8) + 16)) &&
+               ok(fdefer.alloc(force_defer_words(cap))) && ok(fwork.alloc(force_worklist_words(cap))) &&
                ok(bbounds.alloc(8 * ((cap + 255) / 256 + 8))) && ok(pairs.alloc(cap)) && ok(counter.alloc(8)));
         return e;
     }

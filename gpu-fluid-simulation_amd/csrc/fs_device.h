@@ -298,6 +298,13 @@ __device__ __forceinline__ bool edge_block_has(const EdgeBlocks& E, uint32_t b) 
 // ranges and says whether they fit an LDS tile of `tile` entries each.
 struct RowRanges { uint32_t lo[3], hi[3]; };
 
+// One candidate of a pass-mask scan (the 2D sweeps of fs_force_sweep.h, the 3D ones of fs_sweep3.h and kernels_force3d.hip):
+// mask = mask << 1 | !(r2 > lim), as a compare into vcc and an add-with-carry of the mask to itself.
+__device__ __forceinline__ void shift_in_not_greater(uint32_t& mask, float r2, float lim) {
+    // !(lim < r2) == !(r2 > lim), NaN included; this operand order lets `lim` stay in an SGPR
+    asm("v_cmp_nlt_f32 vcc, %2, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mask) : "v"(r2), "s"(lim) : "vcc");
+}
+
 // Block-wide [min lo, max hi) per sweep row; returns true when all three fit the tile.
 // WAVES: waves per workgroup (4 for the 256-thread kernels; 1 for the 3D density / force kernels, whose workgroup is one
 // wave so that no barrier couples waves with different neighbour counts).

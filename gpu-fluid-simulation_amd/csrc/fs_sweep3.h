@@ -81,14 +81,11 @@ __device__ __forceinline__ void stage3_rows(const uint32_t* blo, const uint32_t*
 // ---- pass masks of one staged z-plane -----------------------------------------------------------------------
 // A 3D row of three cells holds ~24 candidates at rest (8 particles per cell) and passes 32 as soon as the column
 // compresses, so the pass masks are 64 bits, filled as two 32-bit shift registers: v_cmp + one v_addc_co per candidate shift
-// `!(r2 > h^2)` in (see kernels_force.hip force_sweep_masks for the 2D form).  Candidate t of a row ends up at bit 63 - t.
+// `!(r2 > h^2)` in (fs_device.h shift_in_not_greater; fs_force_sweep.h force_sweep_masks is the 2D form).  Candidate t of a row ends up at bit 63 - t.
 // Valid for waves whose three rows hold <= 64 candidates each; the rows are read from the LDS stage `s_flat`
 // (TILE3_ROW entries per row).  Both the density and the force pass need exactly these masks: k3_density computes
 // them, walks them for its own sum and (Params3::handoff) stores them — 72 B per particle — so that k3_force does not
 // scan the 216 candidates a second time (~2 600 of its ~9 900 VALU instructions per wave).
-__device__ __forceinline__ void shift_in_not_greater32(uint32_t& mask, float r2, float lim) {
-    asm("v_cmp_nlt_f32 vcc, %2, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mask) : "v"(r2), "s"(lim) : "vcc");
-}
 // Where a lane's row r starts in the staged plane, and the bits of a pass mask that are the lane's own `len` candidates
 // (candidate k at bit 63 - k; rows of up to 128: candidates 0 .. 63 in the hi word, 64 .. 127 in the lo word).
 __device__ __forceinline__ uint32_t row_la(const RowRanges& R, const uint32_t* blo, int r) {
@@ -109,7 +106,7 @@ __device__ __forceinline__ void scan3_word(uint32_t& w, uint32_t& t, uint32_t li
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const float ox = qq[u].x - me.x, oy = qq[u].y - me.y, oz = qq[u].z - me.z;
-            shift_in_not_greater32(w, ox * ox + oy * oy + oz * oz, lim);
+            shift_in_not_greater(w, ox * ox + oy * oy + oz * oz, lim);
         }
     }
 }

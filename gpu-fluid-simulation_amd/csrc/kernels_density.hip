@@ -4,10 +4,13 @@
 //   k_render_density  = the density-splat image (fluid_shader.wgsl:27-102)
 #include <stdlib.h>
 
+#include "fs_force_lists.h"
 #include "fs_kernels.h"
 #include "fs_neighbours.h"
 
 namespace fsd {
+
+static_assert(FS_BLOCK == 256, "fs_force_lists.h lays the lists out for blocks of 256 particles");
 
 // -------------------------------------------------------------------- density
 __device__ __forceinline__ float density_cube_tol(float h2, float2 me, float2 q, float acc) {
@@ -58,8 +61,7 @@ __device__ __forceinline__ void density_block(const StepParams& P, uint32_t blk,
         const bool unfit = bhi[0] - blo[0] > NBF_TILE || bhi[1] - blo[1] > NBF_TILE || bhi[2] - blo[2] > NBF_TILE;
         const bool long_row = R.hi[0] - R.lo[0] > 32u || R.hi[1] - R.lo[1] > 32u || R.hi[2] - R.lo[2] > 32u;
         if ((unfit || __any(long_row)) && __builtin_amdgcn_ballot_w64(live) != 0 && (threadIdx.x & 63u) == 0u) {
-            const uint32_t old = atomicOr(&force_defer[2u * blk], 1u << (threadIdx.x >> 6));
-            if (old == 0u) force_work[atomicAdd(&force_count[0], 1u)] = blk;
+            force_list_push(force_defer, force_work, force_count, P.n, blk, threadIdx.x >> 6, FS_LIST_PRE);
         }
     }
     float rho = 0.0f;

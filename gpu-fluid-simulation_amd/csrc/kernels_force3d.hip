@@ -104,7 +104,7 @@ __device__ __forceinline__ Terms3 pair3(const Params3& P, float4 me, float4 mv, 
 }
 
 // ---- tolerance mode (fs3_create_ex math_mode = FS_MATH_TOLERANCE): the pressure and viscosity terms of one in-radius
-// neighbour merged algebraically, as kernels_force.hip force_accum_tol does in 2D: one v_rsq_f32, fused multiply-adds,
+// neighbour merged algebraically, as fs_force_pair.h force_accum_tol does in 2D: one v_rsq_f32, fused multiply-adds,
 // 1/rho_j from the density pass (vel_s.w), ~32 issue slots per pair instead of ~95.  Coincident particles keep the
 // oracle's xorshift direction.
 struct Tol3 { float cP, c3, c2, hh, kp0; };
@@ -196,7 +196,7 @@ __device__ __forceinline__ void walk3(const Params3& P, const Tol3& C, const u64
 #undef FS3_FETCH
 }
 
-// Mask sweep of one staged z-plane (see kernels_force.hip force_sweep_masks): every lane walks the set bits of its three
+// Mask sweep of one staged z-plane (see fs_force_sweep.h force_sweep_masks): every lane walks the set bits of its three
 // 64-bit pass masks, row 0, 1, 2, ascending — the oracle's visiting order.  The masks come from k3_density (Params3::handoff,
 // `masks` != nullptr) or from a scan of the staged plane (fs_sweep3.h masks3_plane).  In the middle plane the lane's own
 // particle sits in row 1 and is skipped (k != i).
@@ -243,7 +243,7 @@ __device__ __forceinline__ void sweep3_masks128(const Params3& P, const Tol3& C,
 
 // General sweep of three rows (one z-plane) for waves that hold a row longer than 64 candidates, or whose
 // plane does not fit the LDS tile: the same machinery one 32-candidate chunk of one row at a time (see
-// kernels_force.hip force_sweep_chunks) — wave-uniform scan into a 32-bit mask, pipelined walk.  Rows and
+// fs_force_sweep.h force_sweep_chunks) — wave-uniform scan into a 32-bit mask, pipelined walk.  Rows and
 // chunks in order = the oracle's visiting order.  STAGED: candidates from the LDS tile, else from global
 // memory (pred is allocated with FS_PRED_SLACK elements of slack for the read-ahead).
 #define FS3_CHUNK_BATCH 4    // 32-candidate chunks scanned per walk
@@ -263,7 +263,7 @@ __device__ __forceinline__ void sweep3_chunks(const Params3& P, const Tol3& C, c
         const uint32_t b0 = r == 0 ? b00 : r == 1 ? b01 : b02;
         const uint32_t len = hi - lo;
         // FS3_CHUNK_BATCH chunks of 32 candidates are scanned before the walk starts and their masks are walked as one shift
-        // register (kernels_force.hip force_sweep_chunks: a lane then waits for the wave's slowest lane once per 128
+        // register (fs_force_sweep.h force_sweep_chunks: a lane then waits for the wave's slowest lane once per 128
         // candidates instead of once per 32); the chunks of a batch are consecutive in the row, a refill advances the bases
 #pragma unroll 1
         for (uint32_t c0 = 0; __any(c0 < len); c0 += 32u * FS3_CHUNK_BATCH) {   // c0 is wave-uniform
@@ -284,7 +284,7 @@ __device__ __forceinline__ void sweep3_chunks(const Params3& P, const Tol3& C, c
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const float ox = qq[u].x - me.x, oy = qq[u].y - me.y, oz = qq[u].z - me.z;
-                        shift_in_not_greater32(mask, ox * ox + oy * oy + oz * oz, lim);
+                        shift_in_not_greater(mask, ox * ox + oy * oy + oz * oz, lim);
                     }
                 }
                 mask = t ? mask << (32u - t) : 0u;

@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from tests.dense_scene import dense_scene
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 FLOAT_FIELDS = ("position", "predicted_position", "velocity", "density")
@@ -457,19 +459,6 @@ def test_dense_cluster_exercises_overflow_paths(fs, orc, sort_mode):
     assert cnt.max() > 150          # the scene really has hot cells
 
 
-def _dense_scene(fs, n=8192, seed=17):
-    st = fs.SimulationSettings(n, 0.1, 0.2, (40.0, 30.0))
-    tick = fs.default_tick_settings(gravity=(0.0, 9.81))
-    rng = np.random.default_rng(seed)
-    p = fs.reference_lattice(st, (0.0, 0.0))
-    idx = rng.choice(n, 3000, replace=False)
-    p["position"][idx] = rng.uniform(-0.3, 0.3, size=(3000, 2)).astype(np.float32) + np.float32([5.0, -4.0])
-    p["position"][idx[:64]] = p["position"][idx[64:128]]          # coincident pairs: the serial random direction (compute.wgsl:211)
-    p["predicted_position"] = p["position"]
-    p["velocity"] = rng.uniform(-0.5, 0.5, size=(n, 2)).astype(np.float32)
-    return st, tick, p
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("math", ["ieee", "ulp"])
 def test_force_quad_kernel_changes_no_bit(fs, orc, monkeypatch, math):
@@ -477,7 +466,7 @@ def test_force_quad_kernel_changes_no_bit(fs, orc, monkeypatch, math):
     broadcasts) must leave every bit where the lane-per-particle general kernel leaves it — dense clusters, rows of hundreds of
     candidates, coincident pairs (which it hands to the general kernel), both math modes that use it; strict math also against
     the oracle.  FS_FORCE_QUAD_ALWAYS=1 puts it into every step (otherwise the host picks it from the list length a few steps ago)."""
-    st, tick, p = _dense_scene(fs)
+    st, tick, p = dense_scene(fs)
     mm = fs.FS_MATH_IEEE if math == "ieee" else fs.FS_MATH_WGSL_ULP
     monkeypatch.setenv("FS_FORCE_QUAD_ALWAYS", "1")
     quad = fs.FluidSimulation(st, device=0, math_mode=mm)

@@ -6,6 +6,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.dense_scene import dense_scene
+
 pytestmark = pytest.mark.gpu
 FLOAT_FIELDS = ("position", "predicted_position", "velocity", "density")
 
@@ -139,25 +141,12 @@ def test_bitexact_large(fs, n):
     sim.close(); chk.close()
 
 
-def _dense_scene(fs, n=8192, seed=17):
-    st = fs.SimulationSettings(n, 0.1, 0.2, (40.0, 30.0))
-    tick = fs.default_tick_settings(gravity=(0.0, 9.81))
-    rng = np.random.default_rng(seed)
-    p = fs.reference_lattice(st, (0.0, 0.0))
-    idx = rng.choice(n, 3000, replace=False)
-    p["position"][idx] = rng.uniform(-0.3, 0.3, size=(3000, 2)).astype(np.float32) + np.float32([5.0, -4.0])
-    p["position"][idx[:64]] = p["position"][idx[64:128]]          # coincident pairs
-    p["predicted_position"] = p["position"]
-    p["velocity"] = rng.uniform(-0.5, 0.5, size=(n, 2)).astype(np.float32)
-    return st, tick, p
-
-
 @pytest.mark.parametrize("path", ["general", "quad", "aos"])
 def test_every_force_path_bitexact(fs, monkeypatch, path):
     """A dense cluster (rows longer than the tiles: k_force_general and the unstaged ST sweep), FS_FORCE_QUAD_ALWAYS
     (k_force_quad) and a registered export handle (the AOS instantiations: the force pass writes the records itself)."""
     from tests.st_ref import STChecker
-    st, tick, p = _dense_scene(fs)
+    st, tick, p = dense_scene(fs)
     if path == "quad":
         monkeypatch.setenv("FS_FORCE_QUAD_ALWAYS", "1")
     sim = fs.FluidSimulation(st, device=0, surface_tension=True)
