@@ -28,8 +28,9 @@ __device__ __forceinline__ uint32_t quirk_lo_fix(const StepParams& P, const u64*
     return v < cnt ? v : cnt;
 }
 
+// (row_range and lane_row_ranges are __host__ too: tests/row_ranges_checker.hip sweeps them against each other on the CPU.)
 // (cx, y) are the cell's (u, v) of the handle's id layout (fs_device.h StepParams::transposed; the reference layout: u = x, v = y).
-__device__ __forceinline__ bool row_range(const StepParams& P, const uint32_t* __restrict__ cs, uint32_t cx,
+__host__ __device__ __forceinline__ bool row_range(const StepParams& P, const uint32_t* __restrict__ cs, uint32_t cx,
                                           uint32_t y, uint32_t lo_fix, uint32_t* lo, uint32_t* hi) {
     if (y >= P.grid_v) return false;             // id >= ncell: OOB start_indices read -> nothing
     const uint32_t id_lo = y * P.grid_u + cx - 1u;
@@ -45,15 +46,32 @@ __device__ __forceinline__ bool row_range(const StepParams& P, const uint32_t* _
 }
 
 // The lane's three row ranges: rows cy - 1, cy, cy + 1 of the sweep around its cell (cx, cy).  A dead lane, a row outside the grid
-// and an empty row all come back as lo == hi.
-__device__ __forceinline__ RowRanges lane_row_ranges(const StepParams& P, const uint32_t* cs, uint32_t lo_fix, uint32_t cx,
+// and an empty row all come back as lo == hi.  Same integers as three row_range() calls, without their branches: a row that
+// row_range() refuses (dead lane, y >= grid_v, id_lo >= ncell — the wrapped cy - 1 and cx - 1 included) reads entry 0 instead, which
+// is always there (cs has ncell + 1 entries), so the six loads depend on nothing but the cell and are all in flight together —
+// one round trip to the cell table per lane instead of three.  The selects come after the loads.
+__host__ __device__ __forceinline__ RowRanges lane_row_ranges(const StepParams& P, const uint32_t* cs, uint32_t lo_fix, uint32_t cx,
                                                      uint32_t cy, bool live) {
     RowRanges R;
+    bool ok[3];
+    uint32_t a[3], b[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-        R.lo[r] = 0; R.hi[r] = 0;
-        if (live) (void)row_range(P, cs, cx, cy + (uint32_t)(r - 1), lo_fix, &R.lo[r], &R.hi[r]);
-        if (R.hi[r] < R.lo[r]) R.hi[r] = R.lo[r];
+        const uint32_t y = cy + (uint32_t)(r - 1);
+        const uint32_t id_lo = y * P.grid_u + cx - 1u;
+        ok[r] = live && y < P.grid_v && id_lo < P.ncell;
+        uint32_t id_hi = id_lo + 3u;
+        if (id_hi > P.ncell) id_hi = P.ncell;
+        a[r] = cs[ok[r] ? id_lo : 0u];
+        b[r] = cs[ok[r] ? id_hi : 0u];
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        uint32_t lo = a[r] == 0u ? lo_fix : a[r];
+        uint32_t hi = b[r];
+        if (!ok[r]) { lo = 0u; hi = 0u; }
+        R.lo[r] = lo;
+        R.hi[r] = hi < lo ? lo : hi;
     }
     return R;
 }
@@ -72,6 +90,37 @@ __device__ __forceinline__ RowRanges lane_row_ranges(const StepParams& P, const 
                              // lean kernel in every step (force 0.603 -> 0.595 ms at 16 M; more at 1 M and per slab rank)
 #endif
 
+// Staging the three block-wide ranges, in two halves: every global load of the three rows goes to registers first
+// (stage_rows_load), the LDS writes follow (stage_rows_store), so a thread's loads are all in flight at once instead of one
+// load - wait - write round trip per 256 candidates of a row.  A tile is at most FS_STAGE_TRIPS x 256 entries, so the trips are
+// unrolled: 3 rows x 3 trips of T in registers between the halves, most of them predicated off (a row holds 260 - 300
+// candidates in the fluid's bulk).  `fetch(k)` reads what is staged of candidate k, `put(r, j, v)` writes it to slot j of row r.
+#define FS_STAGE_TRIPS 3
+static_assert(NB_TILE <= FS_STAGE_TRIPS * FS_BLOCK && NBF_TILE <= FS_STAGE_TRIPS * FS_BLOCK,
+              "stage_rows_load / stage_rows_store cover a tile in FS_STAGE_TRIPS trips of the workgroup");
+template <typename T> struct StagedRows { T v[3][FS_STAGE_TRIPS]; };
+
+template <typename T, typename Fetch>
+__device__ __forceinline__ void stage_rows_load(StagedRows<T>& S, const uint32_t* blo, const uint32_t* bhi, Fetch fetch) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int t = 0; t < FS_STAGE_TRIPS; ++t) {
+            const uint32_t j = threadIdx.x + (uint32_t)t * FS_BLOCK;
+            if (j < bhi[r] - blo[r]) S.v[r][t] = fetch(blo[r] + j);
+        }
+}
+template <typename T, typename Put>
+__device__ __forceinline__ void stage_rows_store(const StagedRows<T>& S, const uint32_t* blo, const uint32_t* bhi, Put put) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int t = 0; t < FS_STAGE_TRIPS; ++t) {
+            const uint32_t j = threadIdx.x + (uint32_t)t * FS_BLOCK;
+            if (j < bhi[r] - blo[r]) put(r, j, S.v[r][t]);
+        }
+}
+
 // The density -> force hand-off (fs_device.h StepParams::block_bounds): the 8-word record of block `blk` holds the block-wide
 // ranges as [lo0, lo1, lo2, hi0, hi1, hi2].
 __device__ __forceinline__ void store_block_bounds(const StepParams& P, uint32_t blk, const uint32_t* blo, const uint32_t* bhi) {
@@ -81,6 +130,12 @@ __device__ __forceinline__ void store_block_bounds(const StepParams& P, uint32_t
 __device__ __forceinline__ void load_block_bounds(const StepParams& P, uint32_t blk, uint32_t* blo, uint32_t* bhi) {
     const uint32_t* bb = P.block_bounds + 8u * blk;
     blo[0] = bb[0]; blo[1] = bb[1]; blo[2] = bb[2]; bhi[0] = bb[3]; bhi[1] = bb[4]; bhi[2] = bb[5];
+}
+
+// The record's ranges, and whether all three fit a tile of `tile` entries (what block_tile_bounds() says of the same ranges).
+__device__ __forceinline__ bool recorded_tile_bounds(const StepParams& P, uint32_t blk, uint32_t* blo, uint32_t* bhi, uint32_t tile) {
+    load_block_bounds(P, blk, blo, bhi);
+    return bhi[0] - blo[0] <= tile && bhi[1] - blo[1] <= tile && bhi[2] - blo[2] <= tile;
 }
 
 struct AosParticle { float2 position, predicted, velocity; float density; uint32_t grid; };   // ParticleInstance, 32 B

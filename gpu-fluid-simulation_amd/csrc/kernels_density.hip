@@ -44,8 +44,8 @@ __device__ __forceinline__ void density_block(const StepParams& P, uint32_t blk,
                                               uint32_t* __restrict__ force_count, float2 (*s_pred)[NB_TILE], uint32_t* s_red) {
     const uint32_t i = blk * FS_BLOCK + threadIdx.x;
     const bool live = i < n;
+    const float2 me = pred[live ? i : n - 1];      // issued first: the quirk's two dependent scalar loads run beside it
     const uint32_t lo_fix = quirk_lo_fix(P, pairs, cs, start_ref);
-    const float2 me = pred[live ? i : n - 1];
     uint32_t cx, cy;                // (u, v) of the cell-id layout: (x, y) unless the handle is a transposed slab rank
     int32_t cg;
     uv_local(P, me, &cx, &cy, &cg);
@@ -66,9 +66,9 @@ __device__ __forceinline__ void density_block(const StepParams& P, uint32_t blk,
     }
     float rho = 0.0f;
     if (fit) {
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            for (uint32_t j = threadIdx.x; j < bhi[r] - blo[r]; j += FS_BLOCK) s_pred[r][j] = pred[blo[r] + j];
+        StagedRows<float2> S;       // all loads of the three rows, then the LDS writes (fs_neighbours.h)
+        stage_rows_load(S, blo, bhi, [&](uint32_t k) { return pred[k]; });
+        stage_rows_store(S, blo, bhi, [&](int r, uint32_t j, float2 q) { s_pred[r][j] = q; });
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
@@ -181,12 +181,24 @@ __device__ __forceinline__ void st_term(const StConsts& C, float2 me, float2 q, 
     L += in ? w * lk : 0.0f;
 }
 
+// The weight in two halves, so that the staging can load every candidate's operand before it forms the first weight:
+// st_weight_operand is the one word read per candidate, st_weight_of the weight from it.
+template <bool MASS1>
+__device__ __forceinline__ float st_weight_operand(const float2* __restrict__ rho2, const float* __restrict__ rho_arr, uint32_t j) {
+    if (MASS1) return rho2[j].y;                    // +-RN(1/rho_j): the sign is the density pass's safe bit
+    return rho_arr ? rho_arr[j] : rho2[j].x;        // rho_j.  rho_arr: tolerance mode (rho2 = {pressure, 1/rho})
+}
+template <bool MASS1>
+__device__ __forceinline__ float st_weight_of(const StepParams& P, float d) {
+    if (MASS1) return fabsf(d);                     // RN(1/rho_j) == RN(1.0f / rho_j)
+    return __fdiv_rn(P.mass, d);
+}
 template <bool MASS1>
 __device__ __forceinline__ float st_weight(const StepParams& P, const float2* __restrict__ rho2, const float* __restrict__ rho_arr,
                                            uint32_t j) {
-    if (MASS1) return fabsf(rho2[j].y);             // RN(1/rho_j) == RN(1.0f / rho_j): the sign is the density pass's safe bit
-    return __fdiv_rn(P.mass, rho_arr ? rho_arr[j] : rho2[j].x);   // rho_arr: tolerance mode (rho2 = {pressure, 1/rho})
+    return st_weight_of<MASS1>(P, st_weight_operand<MASS1>(rho2, rho_arr, j));
 }
+struct StCandidate { float2 q; float d; };          // what k_surface_tension stages of a candidate: position, weight operand
 
 template <bool MASS1>
 __global__ __launch_bounds__(FS_BLOCK) void k_surface_tension(StepParams P, StConsts C, const float2* __restrict__ pred,
@@ -210,19 +222,18 @@ __global__ __launch_bounds__(FS_BLOCK) void k_surface_tension(StepParams P, StCo
     uint32_t blo[3], bhi[3];
     bool fit;
     if (P.block_bounds) {       // this step's density pass reduced the same ranges over the same 256 particles
-        load_block_bounds(P, blk, blo, bhi);
-        fit = bhi[0] - blo[0] <= NB_TILE && bhi[1] - blo[1] <= NB_TILE && bhi[2] - blo[2] <= NB_TILE;
+        fit = recorded_tile_bounds(P, blk, blo, bhi, NB_TILE);
     } else {
         fit = block_tile_bounds(R, s_red, blo, bhi, NB_TILE);
     }
     float nx = 0.0f, ny = 0.0f, L = 0.0f;
     if (fit) {
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            for (uint32_t j = threadIdx.x; j < bhi[r] - blo[r]; j += FS_BLOCK) {
-                s_q[r][j] = pred[blo[r] + j];
-                s_w[r][j] = st_weight<MASS1>(P, rho2, rho_arr, blo[r] + j);
-            }
+        StagedRows<StCandidate> S;  // all loads of the three rows, then the weights and the LDS writes (fs_neighbours.h)
+        stage_rows_load(S, blo, bhi, [&](uint32_t k) { return StCandidate{pred[k], st_weight_operand<MASS1>(rho2, rho_arr, k)}; });
+        stage_rows_store(S, blo, bhi, [&](int r, uint32_t j, const StCandidate& c) {
+            s_q[r][j] = c.q;
+            s_w[r][j] = st_weight_of<MASS1>(P, c.d);
+        });
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < 3; ++r) {

@@ -6,6 +6,8 @@
 // in kernels_force_quad.inc (compiled as part of this unit, see there).
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 #include "fs_force_lists.h"
 #include "fs_force_sweep.h"
 #include "fs_kernels.h"
@@ -116,6 +118,12 @@ __device__ __forceinline__ void integrate_store(const StepParams& P, uint32_t i,
 #ifndef FS_FORCE_WAVES
 #define FS_FORCE_WAVES 8
 #endif
+// The load half of k_force's stage (fs_neighbours.h); the kernels that keep the staging loop hold no rows in flight.
+struct NoStagedRows {};
+__device__ __forceinline__ void force_stage_load(StagedRows<float2>& S, const uint32_t* blo, const uint32_t* bhi,
+                                                 const float2* __restrict__ pred) {
+    stage_rows_load(S, blo, bhi, [&](uint32_t k) { return pred[k]; });
+}
 // One workgroup's 256 particles.  GENERAL = false is the lean main path: mask sweep with the shared-reciprocal terms
 // only.  A wave it cannot finish that way — its tile does not fit the LDS stage, one of its sweep rows is longer than
 // 32 candidates (dense clusters), or an operand fell outside the proven quotient ranges — is handed to the general
@@ -123,11 +131,11 @@ __device__ __forceinline__ void integrate_store(const StepParams& P, uint32_t i,
 // GENERAL = true is the complete body (chunked sweeps, true-division fallback) for the waves named in `wave_bits`.
 // The split keeps the rare paths out of the common kernel's register allocation.  When it was made (round 2) a
 // timing-only build without them needed 39 VGPRs instead of 64 + 35 spilled, force 0.72 -> 0.665 ms at 16M
-// (profiles/r02_d_rejected.md).  Today: k_force 45 - 59 VGPRs by mode and AOS, no spills
-// (profiles/force_split_resource_usage.txt).
+// (profiles/r02_d_rejected.md).  Today: k_force 56 - 58 VGPRs by mode and AOS with its staged rows in flight, no spills
+// (profiles/prologue_resource_usage.txt).
 // The two lists — waves named by k_density before the launch ("pre"), waves the lean path gives up on itself ("late") —
 // are laid out in fs_force_lists.h.
-template <int MODE, bool AOS, bool GENERAL, bool ST>
+template <int MODE, bool AOS, bool GENERAL, bool ST, bool EARLY>
 __device__ __forceinline__ void force_block(const StepParams& P, uint32_t blk, uint32_t n, uint32_t wave_bits,
                                             const float2* __restrict__ pos_s, const float2* __restrict__ vel_s,
                                             const float2* __restrict__ pred, const float2* __restrict__ rho2,
@@ -146,12 +154,27 @@ __device__ __forceinline__ void force_block(const StepParams& P, uint32_t blk, u
     const bool pre = !GENERAL && ((wave_bits >> (tid >> 6)) & 1u);
     if (pre) live = false;
     const uint32_t ii = i < n ? i : n - 1;           // dead lanes shadow the last particle, store nothing
-    const uint32_t lo_fix = quirk_lo_fix(P, pairs, cs, start_ref);
+    // EARLY (k_force): the prologue's global loads in three round trips.  With the density pass's record of the block-wide ranges
+    // (every single-domain step) nothing the lane computes decides what is staged: the staging loads go out first, the lane's own
+    // record right behind them, then the source position and the six cell-table entries; the LDS writes come last.
+    // k_force_edge and k_force_general have no registers for the rows in flight (profiles/prologue_resource_usage.txt): they
+    // stage where they did, with the loop.
+    uint32_t blo[3], bhi[3];
+    bool staged = false;
+    std::conditional_t<EARLY, StagedRows<float2>, NoStagedRows> S;     // the rows in flight: k_force only
+    const bool ahead = EARLY && P.block_bounds != nullptr;     // uniform
+    if constexpr (EARLY) {
+        if (ahead) {
+            staged = recorded_tile_bounds(P, blk, blo, bhi, NBF_TILE);
+            if (staged) force_stage_load(S, blo, bhi, pred);
+        }
+    }
     const float2 me = pred[ii];
     const float2 mv = vel_s[ii];
     const float2 mrec = rho2[ii];                   // {rho, +-1/rho}; MODE 2: {pressure, 1/rho}
     // own position at the start of the step: the sorted copy, or (pos_by_src) the previous state through the pair's source index
     const float2 p_own = pos_s[P.pos_by_src ? (uint32_t)pairs[ii] : ii];
+    const uint32_t lo_fix = quirk_lo_fix(P, pairs, cs, start_ref);
     const float mrho = MODE == 2 ? 0.0f : mrec.x;
     const bool me_ok = mrec.y > 0.0f;               // this particle's "safe operand" classification (fs_device.h)
     const float pressure = MODE == 2 ? mrec.x : P.pressure_k * (mrho - P.rest_density);      // funcs.wgsl:152-154
@@ -166,23 +189,24 @@ __device__ __forceinline__ void force_block(const StepParams& P, uint32_t blk, u
         if (!slab_advances(P, cg)) live = false;
     }
     const RowRanges R = lane_row_ranges(P, cs, lo_fix, cx, cy, live);
-    uint32_t blo[3], bhi[3];
-    bool staged;
-    if (P.block_bounds) {
+    if (!ahead) {
         // the density pass of this step reduced the same ranges over the same 256 particles (a slab launch that advances only
         // some columns zeroes the other lanes' ranges: the stored bounds are then a superset — more is staged, nothing is missed)
-        load_block_bounds(P, blk, blo, bhi);
-        staged = bhi[0] - blo[0] <= NBF_TILE && bhi[1] - blo[1] <= NBF_TILE && bhi[2] - blo[2] <= NBF_TILE;
-    } else {
-        staged = block_tile_bounds(R, s_red, blo, bhi, NBF_TILE);
+        if (P.block_bounds) staged = recorded_tile_bounds(P, blk, blo, bhi, NBF_TILE);
+        else staged = block_tile_bounds(R, s_red, blo, bhi, NBF_TILE);
+        if constexpr (EARLY) {
+            if (staged) force_stage_load(S, blo, bhi, pred);
+        }
     }
     bool defer = !staged;                            // lean path only; wave-uniform from here on
     if (staged) {
+        if constexpr (EARLY) {
+            stage_rows_store(S, blo, bhi, [&](int r, uint32_t j, float2 q) { s_pred[r][j] = q; });
+        } else {
 #pragma unroll
-        for (int r = 0; r < 3; ++r)
-            for (uint32_t j = tid; j < bhi[r] - blo[r]; j += FS_BLOCK) {
-                s_pred[r][j] = pred[blo[r] + j];
-            }
+            for (int r = 0; r < 3; ++r)
+                for (uint32_t j = tid; j < bhi[r] - blo[r]; j += FS_BLOCK) s_pred[r][j] = pred[blo[r] + j];
+        }
         __syncthreads();
         const bool long_row = R.hi[0] - R.lo[0] > 32u || R.hi[1] - R.lo[1] > 32u || R.hi[2] - R.lo[2] > 32u;
         if (!__any(long_row))
@@ -239,7 +263,7 @@ __global__ __launch_bounds__(FS_BLOCK) __attribute__((amdgpu_waves_per_eu(FS_FOR
     uint32_t blk;
     if (!xcd_block(P, (n + FS_BLOCK - 1) / FS_BLOCK, &blk)) return;   // uniform: no live particle in this block
     if (!block_may_advance(P, pairs, blk, n)) return;                 // uniform: none of its columns belongs to this launch
-    force_block<MODE, AOS, false, ST>(P, blk, n, defer_bits[force_defer_word(blk, FS_LIST_PRE)], pos_s, vel_s, pred, rho2, cs, start_ref, pairs, tex,
+    force_block<MODE, AOS, false, ST, true>(P, blk, n, defer_bits[force_defer_word(blk, FS_LIST_PRE)], pos_s, vel_s, pred, rho2, cs, start_ref, pairs, tex,
                                       pos_out, vel_out, aos_out, rho_arr, defer_bits, worklist, work_count, st_in, s_pred, s_red);
 }
 
@@ -255,7 +279,7 @@ __global__ __launch_bounds__(FS_BLOCK) __attribute__((amdgpu_waves_per_eu(FS_FOR
     for (uint32_t t = blockIdx.x; t < edge_block_count(E); t += gridDim.x) {
         const uint32_t blk = edge_block_at(E, t);
         if (block_may_advance(P, pairs, blk, n))         // uniform (the ghost columns' blocks at the very ends)
-            force_block<MODE, AOS, false, false>(P, blk, n, defer_bits[force_defer_word(blk, FS_LIST_PRE)], pos_s, vel_s, pred, rho2, cs, start_ref, pairs, tex,
+            force_block<MODE, AOS, false, false, false>(P, blk, n, defer_bits[force_defer_word(blk, FS_LIST_PRE)], pos_s, vel_s, pred, rho2, cs, start_ref, pairs, tex,
                                                  pos_out, vel_out, aos_out, rho_arr, defer_bits, worklist, work_count, st_in, s_pred, s_red);
         __syncthreads();                                 // the LDS stage is reused
     }
@@ -293,7 +317,7 @@ __global__ __launch_bounds__(FS_BLOCK) __attribute__((amdgpu_waves_per_eu(FS_GEN
             const uint32_t blk = list[e];
             if (!block_may_advance(P, pairs, blk, n)) continue;          // uniform
             const uint32_t bits = defer_bits[force_defer_word(blk, w)];
-            force_block<MODE, AOS, true, ST>(P, blk, n, bits, pos_s, vel_s, pred, rho2, cs, start_ref, pairs,
+            force_block<MODE, AOS, true, ST, false>(P, blk, n, bits, pos_s, vel_s, pred, rho2, cs, start_ref, pairs,
                                              tex, pos_out, vel_out, aos_out, rho_arr, defer_bits, worklist, work_count, st_in, s_pred,
                                              s_red);
             __syncthreads();                         // the LDS stage is reused by the next entry
