@@ -21,6 +21,7 @@ from ._abi import (  # noqa: F401
     FS_MATH_WGSL_ULP,
     FS_SORT_BITONIC,
     FS_SORT_COUNTING,
+    FS_SLAB_ROWMAJOR,
     FS_SLAB_SERIAL,
     FS_SLAB_STRIPS,
     MESH_VERTEX_DTYPE,
@@ -816,11 +817,12 @@ class SlabSimulation:
     """
 
     def __init__(self, settings, own_lo, own_hi, has_left, has_right, capacity, recv_capacity, max_cols, device=0,
-                 sort_mode=None, serial=False, strips=False):
+                 sort_mode=None, serial=False, strips=False, rowmajor=False):
         self._lib = load_library()
         self._h = C.c_void_p()
         self.settings = settings
         mode = (0 if sort_mode is None else 1 + int(sort_mode)) | (FS_SLAB_SERIAL if serial else 0) | (FS_SLAB_STRIPS if strips else 0)
+        mode |= FS_SLAB_ROWMAJOR if rowmajor else 0        # row-major cell ids even where a slab edge has a neighbour
         self.cfg = SlabConfig(int(own_lo), int(own_hi), int(bool(has_left)), int(bool(has_right)), int(capacity),
                               int(recv_capacity), int(max_cols), mode)
         _check(self._lib, self._lib.fs_slab_create(C.byref(settings), int(device), C.byref(self.cfg), C.byref(self._h)))
@@ -868,6 +870,12 @@ class SlabSimulation:
     def upload_owned(self, arr):
         arr = np.ascontiguousarray(arr, dtype=PARTICLE_DTYPE)
         _check(self._lib, self._lib.fs_slab_upload_owned(self._h, arr.ctypes.data_as(C.c_void_p), arr.shape[0]))
+
+    def upload_force_field(self, field):
+        """As FluidSimulation.upload_force_field: f32 [texture_size.y, texture_size.x, 2]."""
+        field = np.ascontiguousarray(field, dtype=np.float32)
+        h, w = field.shape[0], field.shape[1]
+        _check(self._lib, self._lib.fs_upload_force_field(self._h, field.ctypes.data_as(C.c_void_p), w, h))
 
     def set_window(self, own_lo, own_hi):
         _check(self._lib, self._lib.fs_slab_set_window(self._h, int(own_lo), int(own_hi)))

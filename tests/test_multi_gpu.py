@@ -16,7 +16,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 class InProcessSlabs:
     def __init__(self, fs, settings, off, world, cap, recv, seed=None, vel=1.0, sort_mode=None, trim_margin=0, serial=False,
-                 boundary_cols=None, strips=False, particles=None):
+                 boundary_cols=None, strips=False, particles=None, bounds=None, rowmajor=False, field=None):
+        """bounds: explicit column boundaries (world + 1 of them) instead of the equal-count partition; rowmajor: FS_SLAB_ROWMAJOR
+        on every rank; field: a force field [texture_size.y, texture_size.x, 2], uploaded to every rank."""
         from gpu_fluid_simulation_amd import multi
         self.fs, self.multi, self.world, self.trim_margin = fs, multi, world, trim_margin
         lat = fs.reference_lattice(settings, off) if particles is None else np.array(particles, dtype=fs.PARTICLE_DTYPE)
@@ -26,17 +28,21 @@ class InProcessSlabs:
             lat["predicted_position"] = lat["position"]
             lat["velocity"] = rng.uniform(-vel, vel, size=lat["velocity"].shape).astype(np.float32)
         self.initial = lat
-        cols = multi.global_columns(lat["position"][:, 0], settings.size.x, settings.smoothing_radius)
+        half = np.float32(settings.size.x) * np.float32(0.5)      # a particle beyond a wall belongs to the rank that owns the wall's column
+        cols = multi.global_columns(np.clip(lat["position"][:, 0], -half, half), settings.size.x, settings.smoothing_radius)
         self.gw = int(np.ceil(np.float32(settings.size.x) / np.float32(settings.smoothing_radius))) + 2
         hist = np.bincount(cols, minlength=self.gw)[: self.gw]
-        self.bounds = multi.trim_outer_edges(multi.partition_columns(hist, world), hist, trim_margin)
+        self.bounds = multi.trim_outer_edges(multi.partition_columns(hist, world), hist, trim_margin) if bounds is None else list(bounds)
+        assert len(self.bounds) == world + 1
         self.sims, self.bufs = [], []
         for r in range(world):
             s = fs.SlabSimulation(settings, self.bounds[r], self.bounds[r + 1], r > 0, r < world - 1, cap, recv,
-                                  max_cols=self.gw, device=0, sort_mode=sort_mode, serial=serial, strips=strips)
+                                  max_cols=self.gw, device=0, sort_mode=sort_mode, serial=serial, strips=strips, rowmajor=rowmajor)
             assert s.step_mode == (0 if serial or sort_mode == fs.FS_SORT_BITONIC else 2 if strips else 1)
             if boundary_cols is not None and s.overlapped:
                 s.set_boundary_cols(boundary_cols)
+            if field is not None:
+                s.upload_force_field(field)
             s.upload_owned(lat[(cols >= self.bounds[r]) & (cols < self.bounds[r + 1])])
             self.sims.append(s)
             self.bufs.append({k: fs.ResizableBuffer(k, np.uint8, s.message_bytes) for k in ("sl", "sr", "rl", "rr")})
