@@ -10,6 +10,7 @@ import numpy as np
 import paths3d
 from tests import collide3d_ref as CR
 from tests import st3d_ref as R
+from tests.st_choice import choose_surface_tension as _choose
 from tests.track_ref import jitter_velocities
 
 f32 = np.float32
@@ -76,52 +77,26 @@ class Case:
 
 
 # ---- the feature settings, from the checker alone -----------------------------------------------------------------------
-def _median_pos(x):
-    x = np.asarray(x, dtype=np.float64)
-    x = x[np.isfinite(x) & (x > 0)]
-    return float(np.median(x)) if x.size else 0.0
-
-
-def gap_threshold(nl):
-    """a threshold near the median of the finite, non-zero |n| values, in the widest relative gap of their middle half (as
-    test_tolerance_mode_within_tolerance places it); 0 when fewer than two such values exist"""
-    nl = np.sort(np.asarray(nl, dtype=np.float64))
-    nl = nl[np.isfinite(nl) & (nl > 0)]
-    if nl.size < 2:
-        return 0.0
-    mid = nl[nl.size // 4: max(3 * nl.size // 4, nl.size // 4 + 2)]
-    k = int(np.argmax(mid[1:] / mid[:-1]))
-    return float(f32(np.sqrt(mid[k] * mid[k + 1])))
-
-
 def choose_surface_tension(case):
-    """sigma: the ratio of the medians of the step's own velocity change |acc / rho + g| dt (the checker's acc, plain step) and of
-    |st| dt / rho at sigma = 1, so that the pass changes velocities by as much as the step does; kept inside [1e-30, 1e30] and 1
-    where the pass gives no finite force.  tau: gap_threshold of the |n| of one step with (sigma, 0)."""
-    with np.errstate(all="ignore"):
+    """st_choice.choose_surface_tension on the 3D checker: the step's own acceleration is |acc / rho + g| (the checker's acc, plain
+    step); the force and the |n| are those of one step with (sigma, 0)."""
+    def own():
         chk = case.checker()
         acc = chk.step(case.tick, None, want_acc=True).astype(np.float64)
         rho = chk.particles()["density"].astype(np.float64)
         g = np.array([case.tick.gravity.x, case.tick.gravity.y, case.tick.gravity.z], dtype=np.float64)
-        own = np.linalg.norm(acc / rho[:, None] + g, axis=1)
         chk.close()
-        chk = case.checker()
-        chk.step(case.tick, (1.0, 0.0))
-        unit = np.linalg.norm(chk.st.astype(np.float64), axis=1) / chk.particles()["density"].astype(np.float64)
-        chk.close()
-        a, b = _median_pos(own), _median_pos(unit)
-        sigma = float(f32(min(max(a / b, 1e-30), 1e30))) if a > 0 and b > 0 else 1.0
+        return np.linalg.norm(acc / rho[:, None] + g, axis=1)
+
+    def tension(sigma):
         chk = case.checker()
         chk.step(case.tick, (sigma, 0.0))
         nl = norm3(chk.surface_tension_pass(sigma, 0.0)[0])
-        tau = gap_threshold(nl)
-        dv = np.linalg.norm(chk.st.astype(np.float64), axis=1) * float(case.tick.delta) / chk.particles()["density"]
+        unit = np.linalg.norm(chk.st.astype(np.float64), axis=1) / chk.particles()["density"].astype(np.float64)
         chk.close()
-    pos = np.isfinite(nl) & (nl > 0)
-    case.sigma, case.tau = sigma, tau
-    case.figures.update(sigma=sigma, tau=tau, n=int(nl.shape[0]), with_n=int(pos.sum()), above=int((pos & (nl > f32(tau))).sum()),
-                        below=int((pos & ~(nl > f32(tau))).sum()), own_dv=a * float(case.tick.delta), st_dv=_median_pos(dv))
-    return case
+        return unit, nl
+
+    return _choose(case, own, tension, case.tick.delta)
 
 
 def choose_collider(case, shape=FIELD_SHAPE, seed=None):

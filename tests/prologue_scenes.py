@@ -133,13 +133,13 @@ def ragged(n):
 
 # ---- staging depth ----------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
-def one_cell(seed=6):
+def one_cell(seed=6, cell=(100, CS.BIG_ROW)):
     """256 particles in one cell: one workgroup, its own row 256 candidates long (one staging trip), the other rows empty."""
     n = BLOCK
     st, tick = g.SimulationSettings(n, 0.1, H, CS.BOX), tick_settings()
     rng = np.random.default_rng(seed)
     p = _particles(n)
-    CS.fill(p, np.arange(n), st, [(100, CS.BIG_ROW)] * n, rng)
+    CS.fill(p, np.arange(n), st, [tuple(cell)] * n, rng)
     return st, tick, CS.finish(st, p, rng, vel=0.0)
 
 

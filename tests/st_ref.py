@@ -51,6 +51,8 @@ def lib():
         L.stc_move.restype = None
         L.stc_step.argtypes = [P, P, C.c_int, P]
         L.stc_step.restype = None
+        L.orc_sort_stable.argtypes = [P]
+        L.orc_sort_stable.restype = None
         L.orc_set_threads(1)
         _lib = L
     return _lib
@@ -80,6 +82,10 @@ class STChecker(O.OracleSim):
             self.st = st
         else:
             self.L.stc_step(self.h, C.addressof(tick), 1 if stable_sort else 0, None)
+
+    def sort_stable(self):
+        """the stable sort of step(stable_sort=True), as a pass of its own (beside OracleSim.sort)"""
+        self.L.orc_sort_stable(self.h)
 
     def surface_tension_pass(self):
         """The ST pass on the current state (after density()): (st (N, 2) f32, {n.x, n.y, L} (N, 3) f32)."""

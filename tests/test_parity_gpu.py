@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from tests import parity_states as PS
 from tests.dense_scene import dense_scene
 
 pytestmark = pytest.mark.gpu
@@ -28,25 +29,11 @@ def assert_particles_equal(got, want, ctx=""):
 
 
 def make_pair(fs, orc, n, size=None, off=None, seed=None, vel=1.0, jitter=0.025, quirks=True, **tick_over):
-    if size is None:
-        st, off_, tick = fs.dam_break_2d(n)
-        off = off_ if off is None else off
-    else:
-        st = fs.SimulationSettings(n, 0.1, 0.2, size)
-        tick = fs.default_tick_settings(gravity=(0.0, 9.81))
-        off = off or (0.0, 0.0)
-    for k, v in tick_over.items():
-        if k in ("gravity", "mouse_pos"):
-            v = fs.Vec2(*v)
-        setattr(tick, k, v)
+    st, off, tick = PS.pair_settings(fs, n, size, off, **tick_over)
     sim = fs.FluidSimulation(st, device=0, initial_offset=off, ref_quirks=quirks)
     ref = orc.OracleSim(st, off, ref_quirks=quirks)
     if seed is not None:
-        rng = np.random.default_rng(seed)
-        p = ref.particles()
-        p["position"] += rng.uniform(-jitter, jitter, size=(n, 2)).astype(np.float32)
-        p["predicted_position"] = p["position"]
-        p["velocity"] = rng.uniform(-vel, vel, size=(n, 2)).astype(np.float32)
+        p = PS.jitter(ref.particles(), seed, vel, jitter)
         ref.set_particles(p)
         sim.upload_particles(p)
     return sim, ref, st, tick
@@ -102,9 +89,9 @@ def test_golden_jitter_mouse_field(fs):
         assert np.array_equal(sim.download_start_indices(), z[f"start_indices_{s}"])
 
 
-@pytest.mark.parametrize("n", [2, 3, 5, 257, 5000, 4097])
+@pytest.mark.parametrize("n", PS.RAGGED_DAM_N)
 def test_ragged_counts(fs, orc, n):
-    sim, ref, st, tick = make_pair(fs, orc, n, size=(9.0, 7.0), seed=n)
+    sim, ref, st, tick = make_pair(fs, orc, n, size=PS.RAGGED_BOX, seed=n)
     run_and_compare(sim, ref, tick, 4, f"ragged{n}")
 
 
@@ -161,31 +148,23 @@ def test_poisoned_stale_start(fs, orc):
 
 
 def test_mouse_and_force_field(fs, orc):
-    sim, ref, st, tick = make_pair(fs, orc, 4096, seed=3, mouse_state=-1, mouse_pos=(-3.0, 2.5))
-    field = np.zeros((1024, 1024, 2), dtype=np.float32)
-    field[500:900, 0:600] = (0.25, -0.75)
+    sim, ref, st, tick = make_pair(fs, orc, 4096, **PS.MOUSE_FIELD)
+    field = PS.mouse_field()
     sim.upload_force_field(field)
     ref.texture_view()[:] = field
     run_and_compare(sim, ref, tick, 5, "mouse+field")
 
 
 def test_coincident_particles_prng_path(fs, orc):
-    sim, ref, st, tick = make_pair(fs, orc, 4096, seed=4)
-    p = ref.particles()
-    p["position"][1:6] = p["position"][0]
-    p["predicted_position"][1:6] = p["position"][0]
-    p["velocity"][:6] = 0
+    sim, ref, st, tick = make_pair(fs, orc, 4096, **PS.COINCIDENT)
+    p = PS.coincident_state(ref.particles())
     ref.set_particles(p); sim.upload_particles(p)
     run_and_compare(sim, ref, tick, 3, "coincident")
 
 
 def test_nan_reset_speed_clamp_and_walls(fs, orc):
-    sim, ref, st, tick = make_pair(fs, orc, 4096, seed=6, vel=40.0)
-    p = ref.particles()
-    p["velocity"][7] = (np.nan, 1.0)
-    p["velocity"][11] = (9000.0, -9000.0)
-    p["position"][13] = (1e6, -1e6)        # outside the box: clamps in predict and at the walls
-    p["predicted_position"][13] = p["position"][13]
+    sim, ref, st, tick = make_pair(fs, orc, 4096, **PS.NAN_CLAMP)
+    p = PS.nan_clamp_state(ref.particles())
     ref.set_particles(p); sim.upload_particles(p)
     run_and_compare(sim, ref, tick, 4, "nan/clamp")
 
@@ -533,36 +512,17 @@ def test_64m_properties(fs):
     assert np.median(p["density"]) == pytest.approx(101.46, rel=1e-3)
 
 
-@pytest.mark.parametrize("case", range(16))
+@pytest.mark.parametrize("case", range(PS.RANDOM_CASES))
 def test_random_configurations(fs, orc, case):
     """Seeded random settings (smoothing radius, spacing, domain aspect, dt, mass, stiffness, rest density,
     damping, viscosity, gravity sign, texture size, mouse) and particle counts: bit-exact in both sort modes."""
-    rng = np.random.default_rng(1000 + case)
-    n = int(rng.integers(2, 6000))
-    h = float(rng.choice([0.05, 0.1, 0.2, 0.33, 0.5, 1.0]))
-    spacing = float(h * rng.uniform(0.3, 0.9))
-    side = np.sqrt(n) * spacing
-    size = (float(side * rng.uniform(1.2, 3.0) + 4 * h), float(side * rng.uniform(1.2, 3.0) + 4 * h))
-    tex = (int(rng.choice([64, 256, 1024])), int(rng.choice([64, 128, 1024])))
-    st = fs.SimulationSettings(n, spacing, h, size, tex)
-    tick = fs.default_tick_settings(
-        delta=float(rng.choice([1 / 240, 1 / 120, 1 / 60])), gravity=(float(rng.uniform(-5, 5)), float(rng.uniform(-10, 10))),
-        mass=float(rng.uniform(0.5, 2.0)), pressure_constant=float(rng.uniform(5, 100)),
-        rest_density=float(rng.choice([0.0, 1.0, 20.0])), damping_factor=float(rng.uniform(0.0, 0.9)),
-        viscosity_coefficient=float(rng.choice([0.0, 5.0, 25.0])), mouse_state=int(rng.choice([0, 0, 1, -1])),
-        mouse_pos=(float(rng.uniform(-1, 1)), float(rng.uniform(-1, 1))), mouse_force_radius=float(rng.uniform(0.5, 5)))
-    off = (float(rng.uniform(-0.2, 0.2) * size[0]), float(rng.uniform(-0.2, 0.2) * size[1]))
-    for mode, stable in ((fs.FS_SORT_BITONIC, False), (fs.FS_SORT_COUNTING, True)):
+    st, off, tick, runs = PS.random_configuration(fs, orc, case)
+    for sort, p, field in runs:
+        mode, stable = (fs.FS_SORT_BITONIC, False) if sort == "bitonic" else (fs.FS_SORT_COUNTING, True)
         sim = fs.FluidSimulation(st, device=0, initial_offset=off, sort_mode=mode)
         ref = orc.OracleSim(st, off)
-        p = ref.particles()
-        p["position"] += rng.uniform(-0.3, 0.3, size=(n, 2)).astype(np.float32) * np.float32(spacing)
-        p["predicted_position"] = p["position"]
-        p["velocity"] = (rng.standard_normal((n, 2)) * 2.0).astype(np.float32)
         ref.set_particles(p); sim.upload_particles(p)
-        if case % 3 == 0:
-            field = np.zeros((tex[1], tex[0], 2), dtype=np.float32)
-            field[tex[1] // 3: tex[1] // 2, tex[0] // 4: tex[0] // 2] = (float(rng.uniform(-1, 1)), float(rng.uniform(-1, 1)))
+        if field is not None:
             sim.upload_force_field(field); ref.texture_view()[:] = field
         for s in range(4):
             sim.tick(tick); ref.step(tick, stable_sort=stable)
@@ -574,48 +534,11 @@ def test_random_configurations(fs, orc, case):
 # ---- operands at and beyond the guards of the shared-denominator quotients ----------
 # The force pass forms a/b from one reciprocal only inside proven ranges; everything else must take the
 # true-division body.  These scenes put numerators and denominators on both sides of every guard.
-@pytest.mark.parametrize("case", ["tiny_offsets", "tiny_velocities", "huge_velocities", "inf_velocity",
-                                  "zero_aligned", "huge_pressure", "near_zero_coordinates", "small_operands_on_the_fast_path"])
+@pytest.mark.parametrize("case", PS.GUARD_CASES)
 def test_force_quotient_guards(fs, orc, case):
-    over = {}
-    if case == "huge_pressure":
-        over = dict(pressure_constant=3.0e33)              # dx*kern*shared beyond 2^60, some overflow to inf
-    sim, ref, st, tick = make_pair(fs, orc, 4096, seed=21, **over)
-    p = ref.particles()
+    sim, ref, st, tick = make_pair(fs, orc, 4096, seed=PS.GUARD_SEED, **PS.guard_overrides(case))
+    p = PS.guard_state(orc, st, ref.particles(), case)
     n = p.shape[0]
-    base = p["position"][100].copy()
-    if case == "tiny_offsets":                             # |ox|, |oy| from 2^-149 up to ~2^-20 (r2 below 2^-40 too)
-        for k, d in enumerate([1e-45, 1e-40, 1e-30, 1e-19, 3e-13, 1e-7]):
-            p["position"][101 + k] = base + np.float32(d) * np.array([1, 0 if k % 2 else 1], np.float32)
-        p["position"][100:108] -= base                     # around the origin, where such offsets are representable
-    elif case == "tiny_velocities":                        # velocity differences far below 2^-60 and denormal
-        p["velocity"][:] = 0
-        p["velocity"][::3] = (1e-30, -2e-38)
-        p["velocity"][1::3] = (3e-30, 1e-45)
-    elif case == "huge_velocities":                        # differences above 2^60 (clamped only after the force pass)
-        p["velocity"][50] = (3e30, -3e30)
-        p["velocity"][51] = (-2e25, 1e19)
-    elif case == "inf_velocity":
-        p["velocity"][60] = (np.inf, 0.0)
-        p["velocity"][61] = (-np.inf, np.nan)
-    elif case == "zero_aligned":                           # exact zeros in every numerator: lattice, equal velocities
-        q = orc.OracleSim(st, (0.0, 0.0)).particles()
-        p["position"] = q["position"]
-        p["velocity"][:] = (0.25, -0.5)
-    elif case == "small_operands_on_the_fast_path":        # numerators between 2^-76 and 2^-60: exact quotients by reciprocal
-        f = np.float32
-        tiny = f(2.0 ** -53)
-        j = np.arange(n, dtype=np.float32) % 7
-        p["velocity"][:, 0] = tiny * (f(1) + j * f(2.0 ** -22))      # differences are multiples of 2^-75
-        p["velocity"][:, 1] = tiny * (f(3) - j * f(2.0 ** -21))
-        col = np.isclose(p["position"][:, 0], p["position"][np.argmin(np.abs(p["position"][:, 0])), 0])
-        k = np.nonzero(col)[0][:40]                        # one lattice column moved onto x ~ 2^-53: offsets of 2^-75 .. 2^-73
-        p["position"][k, 0] = tiny * (f(1) + (np.arange(len(k)) % 5).astype(np.float32) * f(2.0 ** -22))
-    elif case == "near_zero_coordinates":                  # positions within 1e-20 of the origin: tiny but nonzero offsets
-        rng = np.random.default_rng(5)
-        idx = np.arange(200, 232)
-        p["position"][idx] = (rng.standard_normal((32, 2)) * 1e-22).astype(np.float32)
-    p["predicted_position"] = p["position"]
     ref.set_particles(p); sim.upload_particles(p)
     with np.errstate(all="ignore"):
         run_and_compare(sim, ref, tick, 3, f"guards/{case}")

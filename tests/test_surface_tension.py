@@ -2,7 +2,9 @@
 
 The formulas: the 2D poly6 kernel the density pass uses, W = 4/(pi h^8)(h^2 - r^2)^3, its gradient Cg d^2 (q - x) and its
 2D Laplacian Cl d (3 r^2 - h^2) with d = h^2 - r^2, Cg = 24/(pi h^8), Cl = 48/(pi h^8) — checked in float64 against
-quadrature and finite differences.  Then the checker against an O(N^2) float64 sum, and its move pass against the oracle's."""
+quadrature and finite differences.  Then the checker against an O(N^2) float64 sum, and its move pass against the oracle's.
+Last, the hard-input cases of tests/features2d.py on the checker alone: every case that tests/test_surface_tension_hard_inputs_gpu.py
+runs on the engine tests what it says (both threshold branches, exact-zero and NaN |n|, tau on a particle's |n|, the floor)."""
 import numpy as np
 import pytest
 
@@ -178,3 +180,168 @@ def test_checker_move_with_st_uses_the_forces(fs):
     moved = np.any(a.particles()["velocity"] != b.particles()["velocity"], axis=1)
     pushed = np.any(a.st != 0.0, axis=1)
     assert moved.sum() > 100 and not np.any(moved & ~pushed)
+
+
+# ------------------------------------------- the hard-input cases of tests/test_surface_tension_hard_inputs_gpu.py, on the checker alone
+from tests import features2d as F                                  # noqa: E402
+from tests import parity_states as PS                              # noqa: E402
+
+f32 = np.float32
+ALL_BELOW = ("guard/tau_nan",)                                     # nl > NaN is false: the point of the case
+NO_FORCE_IN_STEP_1 = ("guard/nan_next_to_everyone",)               # every |n| of step 1 is a NaN: the point of the case
+SET_BY_HAND = ("guard/isolated/tau0", "guard/isolated/tau-1", "guard/tau_exact", "guard/sigma-35", "guard/sigma_inf", "guard/tau_nan")
+NAN_REACHES_THE_PASS = ("inf_velocity", "nan_clamp", "nan_next_to_everyone", "sigma_inf")
+UNSAFE_FLAG = ("tiny_velocities", "huge_velocities", "inf_velocity", "huge_pressure")
+
+
+def _same(a, b):
+    """equal values, a NaN met by a NaN"""
+    return np.array_equal(a, b, equal_nan=True)
+
+
+@pytest.mark.parametrize("cid", F.CASE_IDS)
+def test_hard_input_cases_exercise_the_pass(fs, orc, cid):
+    """What the GPU file relies on, asked of the checker alone.  The registry's step (the calls of stc_step one by one, to keep n
+    and L) gives STChecker.step's bytes; every force is the statement's closed form of that step's n and L, zero on the
+    not-above branch; over the case's steps both branches of `nl > tau && nl > 0` are taken (ALL_BELOW and step 1 of
+    NO_FORCE_IN_STEP_1 assert that one is empty instead); where sigma and tau were chosen and at least 100 particles have a
+    colour gradient, step 1 leaves at least 1 % of the particles on each side and the pass changes velocities by 0.1 to 10 times
+    what the step itself does."""
+    case = F.case_by_id(fs, orc, cid)
+    run = case.run()
+    print(F.describe(case))
+    fig = case.figures
+    n = case.start.shape[0]
+    assert len(run) == case.steps >= 1 and fig["n"] == n >= 2 and np.isfinite(fig["own_dv"])
+    chk = case.checker()
+    sigma, tau = f32(case.sigma), f32(case.tau)
+    for k, s in enumerate(run):
+        with np.errstate(all="ignore"):
+            chk.step(case.tick, stable_sort=case.stable)
+            assert chk.particles().tobytes() == s.rec.tobytes() and chk.st.tobytes() == s.st.tobytes(), f"step {k}"
+            assert np.array_equal(chk.start_indices(), s.start)
+            up = s.above(tau)
+            sc = (-sigma * s.nl3[:, 2]) / s.nl
+            want = np.where(up[:, None], sc[:, None] * s.nl3[:, :2], f32(0)).astype(f32)
+        assert _same(want, s.st), f"step {k}: st is not the closed form of n and L"
+        assert fig["above"][k] == int(up.sum()) and fig["below"][k] == n - int(up.sum())
+    chk.close()
+    forces = [bool(np.any(s.st != 0)) for s in run]
+    if cid in ALL_BELOW:
+        assert sum(fig["above"]) == 0 and not any(forces)
+        return
+    if cid in NO_FORCE_IN_STEP_1:
+        assert fig["nan_n"][0] == n and fig["above"][0] == 0 and not forces[0] and np.all(run[0].rec["density"] == f32(0.1))
+        assert all(forces[1:]) and fig["above"][1:] == [n] * (case.steps - 1)
+        return
+    assert any(forces) and (forces[0] or n < 100), "the pass produced no force"
+    assert sum(fig["above"]) > 0 and sum(fig["below"]) > 0, fig
+    if cid not in SET_BY_HAND:
+        if fig["with_n"] >= 100:
+            assert fig["above"][0] >= n / 100 and fig["below"][0] >= n / 100, fig
+        if fig["own_dv"] > 0:
+            assert 0.1 <= fig["st_dv"] / fig["own_dv"] <= 10.0, fig
+
+
+@pytest.mark.parametrize("name", ["isolated/tau0", "isolated/tau-1"])
+def test_isolated_particles_have_no_gradient_and_no_force(fs, orc, name):
+    """n == (0, 0) exactly for the four particles farther than h from everyone (the self term adds 0); with tau <= 0 only
+    `nl > 0` keeps their force at zero — and L is not zero, so a kernel without the second comparison divides -sigma L by 0 —
+    while every other particle gets a force"""
+    case = F.guard_case(fs, orc, name)
+    assert case.tau <= 0
+    for s in case.run():
+        alone = (s.nl3[:, 0] == 0) & (s.nl3[:, 1] == 0)
+        assert alone.sum() == len(F.ISOLATED) and np.all(s.rec["predicted_position"][alone, 0] >= 2.5)
+        assert np.all(s.nl3[alone, 2] < 0)
+        assert not s.st[alone].any() and np.all(np.any(s.st[~alone] != 0, axis=1))
+
+
+def test_tau_exact_sits_on_one_particles_gradient(fs, orc):
+    case = F.guard_case(fs, orc, "tau_exact")
+    s = case.run()[0]
+    k, nxt = case.figures["exact"], case.figures["next"]
+    tau = f32(case.tau)
+    assert s.nl[k:k + 1].view(np.uint32)[0] == np.array([tau]).view(np.uint32)[0] and (s.nl == tau).sum() == 1
+    assert not s.st[k].any()                                        # nl > tau is false at equality
+    assert s.nl[nxt] > tau and not np.any((s.nl > tau) & (s.nl < s.nl[nxt])) and s.st[nxt].any()
+    assert s.nl[nxt] <= tau * f32(1.01)                             # ... and `>=` would be the only difference nearby
+
+
+def test_mass_tiny_holds_every_density_at_the_floor(fs, orc):
+    case = F.guard_case(fs, orc, "mass_tiny")
+    for s in case.run():
+        assert np.all(s.rec["density"] == f32(0.1))
+    assert 0 < f32(case.tick.mass) / f32(0.1) < 1e-2 and np.isfinite(case.sigma) and any(s.st.any() for s in case.run())
+
+
+def test_guard_cases_still_carry_their_operands(fs, orc):
+    """A NaN reaches the pass (|n| is a NaN for some particle of some step) in NAN_REACHES_THE_PASS, an infinite force in sigma_inf;
+    UNSAFE_FLAG, the guard scenes of the plain step that do, still set the density pass's unsafe flag for some particle of step 1
+    (tiny_offsets, zero_aligned, near_zero_coordinates and small_operands_on_the_fast_path leave every particle safe) — evaluated from
+    the checker's predicted positions, velocities and densities with the rules of csrc/fs_device.h (kin_safe; rho <= 2^20;
+    |k (rho - rho0)| <= 2^39)."""
+    for name in NAN_REACHES_THE_PASS:
+        assert sum(F.guard_case(fs, orc, name).run() and F.guard_case(fs, orc, name).figures["nan_n"]) > 0, name
+    assert any(np.isinf(s.st).any() for s in F.guard_case(fs, orc, "sigma_inf").run())
+    for name in UNSAFE_FLAG:
+        case = F.guard_case(fs, orc, name)
+        chk = case.checker()
+        F.density_state(chk, case.tick, case.stable)
+        p = chk.particles()
+        chk.close()
+        with np.errstate(all="ignore"):
+            c = np.concatenate([p["predicted_position"], p["velocity"]], axis=1)
+            lo_safe = (c == 0) | (np.abs(c) >= f32(2.0 ** -53))
+            kin = lo_safe.all(axis=1) & (np.abs(p["velocity"]) <= f32(2.0 ** 59)).all(axis=1)
+            press = f32(case.tick.pressure_constant) * (p["density"] - f32(case.tick.rest_density))
+            safe = kin & (p["density"] <= f32(2.0 ** 20)) & (np.abs(press) <= f32(2.0 ** 39))
+        assert (~safe).sum() > 0, name
+
+
+def test_settings_guards(fs, orc):
+    """tau = NaN: no force, and the records are the plain oracle's; sigma = -35: the force of +35 with the other sign"""
+    case = F.guard_case(fs, orc, "tau_nan")
+    ref = orc.OracleSim(case.st, case.off)
+    ref.set_particles(case.start)
+    for s in case.run():
+        ref.step(case.tick)
+        assert ref.particles().tobytes() == s.rec.tobytes() and np.array_equal(ref.start_indices(), s.start)
+    ref.close()
+    neg = F.guard_case(fs, orc, "sigma-35")
+    pos = F.Case("sigma+35", neg.st, neg.off, neg.tick, neg.start, 1).set_st(sigma=35.0, tau=neg.tau)
+    assert np.array_equal(neg.run()[0].st, -pos.run()[0].st) and neg.run()[0].st.any()
+
+
+@pytest.mark.parametrize("name", F.TOL_CASES)
+def test_tolerance_cases_keep_their_branches(fs, orc, name):
+    """tau keeps 1e-3 (a hundred times the density contract of FS_MATH_TOLERANCE) from every |n|, and no particle's |n| can reach
+    tau under that contract (features2d.choose_tolerance_threshold); both branches are taken"""
+    case = F.tolerance_case(fs, orc, name)
+    case.run()
+    print(F.describe(case))
+    fig = case.figures
+    assert fig["tau_gap"] > F.TOL_GAP and fig["tau_margin"] > 1.0 and fig["above"][0] > 0 and fig["below"][0] > 0, fig
+
+
+def test_host_and_switch_cases_take_both_branches(fs, orc):
+    for case in (F.host_case(fs, orc), F.host_case(fs, orc, "counting", False)) + F.switch_cases(fs, orc):
+        case.run()
+        print(F.describe(case))
+        assert min(case.figures["above"]) > 0 and min(case.figures["below"]) > 0
+
+
+def test_tiny_offsets_reach_the_passes(fs, orc):
+    """tiny_offsets_at_rest keeps its offsets through the predict step: the first step's predicted positions hold the origin and
+    six distinct points between 2^-149 and 1e-7 from it.  (tiny_offsets of the plain suite does not: its seven particles coincide.)"""
+    want = sorted(float(f32(d)) for d in (1e-45, 1e-40, 1e-30, 1e-19, 3e-13, 1e-7))
+    for name, kept in (("tiny_offsets_at_rest", True), ("tiny_offsets", False)):
+        case = F.guard_case(fs, orc, name)
+        chk = case.checker()
+        F.density_state(chk, case.tick, case.stable)
+        q = chk.particles()["predicted_position"]
+        chk.close()
+        x = q[(np.abs(q) <= f32(1e-7)).all(axis=1)]
+        assert (sorted(float(v) for v in x[:, 0] if v != 0) == want) == kept, name
+        if kept:
+            assert x.shape[0] == 7 and np.unique(x, axis=0).shape[0] == 7

@@ -1,6 +1,8 @@
 """GPU tests of the opt-in surface tension: k_surface_tension + the ST instantiations of the force kernels
 against the CPU checker (tests/st_checker.cpp: the oracle plus the statement), bit for bit in FS_MATH_IEEE — every field of
-every particle, start_indices and the st buffer — and within the per-step contract in the other math modes."""
+every particle, start_indices and the st buffer — and within the per-step contract in the other math modes.
+The pass at the plain step's hard inputs (operand guards, radii, random configurations, grid edges, mouse and field, the force in
+the other math modes, host paths, A/B switches): tests/test_surface_tension_hard_inputs_gpu.py."""
 import ctypes as C
 
 import numpy as np
@@ -174,13 +176,9 @@ def test_other_math_modes_within_contract(fs, mode):
     """One step from the same (disordered) state: keys, start_indices and predicted positions exact; density rtol 1e-5,
     velocity rtol 1e-5 / atol 2e-5, position atol 1e-4 h — the modes' per-step contract against the IEEE statement."""
     from tests.st_ref import STChecker
-    st, off, tick = fs.dam_break_2d(16384)
+    from tests.parity_states import disordered_dam_break
+    st, off, tick, p = disordered_dam_break(fs)
     chk = STChecker(st, off)
-    rng = np.random.default_rng(11)
-    p = chk.particles()
-    p["position"] += rng.uniform(-0.02, 0.02, size=p["position"].shape).astype(np.float32)
-    p["predicted_position"] = p["position"]
-    p["velocity"] = rng.uniform(-1, 1, size=p["velocity"].shape).astype(np.float32)
     chk.set_particles(p)
     for _ in range(3):
         chk.step(tick)
