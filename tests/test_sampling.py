@@ -247,3 +247,160 @@ def test_null_handle_is_invalid_without_a_device(fs):
     assert lib.fs_sample_points(None, pts, 0, out, None) == inv
     assert lib.fs_sample_points_device(None, pts, 4, out, None) == inv
     assert lib.fs_sample_grid(None, C.byref(view), out, None) == inv
+
+
+# ---- the statement itself, restated in plain numpy, against the checker at wrapped and saturated cells --------------------------
+from tests import hard_states2d as H  # noqa: E402
+from tests import prologue_scenes as S  # noqa: E402
+
+U32 = 0xFFFFFFFF
+
+
+def _u32_sat(x):
+    """NaN and negatives -> 0, >= 2^32 -> 2^32 - 1, else truncation (include/fluidsim.h)"""
+    if not (x > 0.0):
+        return 0
+    if x >= 4294967296.0:
+        return U32
+    return int(x)
+
+
+def _powf(x, y):
+    """powf of the C library: numpy's float32 power is another implementation and differs from it in the last bit (at h = 0.2,
+    0.1, 0.05, 0.33), which would be a difference in Cv and not in the sampler"""
+    import ctypes.util
+    libm = C.CDLL(ctypes.util.find_library("m"))
+    libm.powf.restype, libm.powf.argtypes = C.c_float, [C.c_float, C.c_float]
+    return libm.powf(float(x), float(y))
+
+
+def restated_sample(p, start, u, pts, attr):
+    """The statement of include/fluidsim.h "field sampling", line for line: f32 scalars (numpy float32 arithmetic rounds every
+    operation to f32 and contracts nothing), one operation per line, the cells of the 3 x 3 block in the statement's order, each
+    walked ascending from its stored start index, u32 cell arithmetic wrapping by `& U32`.  Written from the header, not from
+    tests/sample_checker.cpp.  -> (SAMPLE_DTYPE[len(pts)], f32 (C, len(pts)))"""
+    from tests.sample_ref import SAMPLE_DTYPE
+    f = np.float32
+    n, gw, gh = int(u.particle_count), int(u.grid_w), int(u.grid_h)
+    h, m = f(u.smoothing_radius), f(u.particle_mass)
+    h2 = h * h
+    h8 = f(_powf(h, 8.0))                                      # powf(h, 8.0f): the C library's, as the header says
+    pi_h8 = f(3.14159265) * h8
+    cv = f(4.0) / pi_h8
+    half_x = f(u.bounds.x) * f(0.5)
+    half_y = f(u.bounds.y) * f(0.5)
+    grid, q, vel, rho = p["grid"], p["predicted_position"], p["velocity"], p["density"]
+    C_ = attr.shape[0]
+    out = np.zeros(len(pts), dtype=SAMPLE_DTYPE)
+    aout = np.zeros((C_, len(pts)), dtype=f)
+    for i, (x, y) in enumerate(pts):
+        x, y = f(x), f(y)
+        sx = x + half_x
+        sy = y + half_y
+        qx = sx / h
+        qy = sy / h
+        cx = (_u32_sat(np.floor(qx)) + 1) & U32
+        cy = (_u32_sat(np.floor(qy)) + 1) & U32
+        density, weight, vx, vy = f(0.0), f(0.0), f(0.0), f(0.0)
+        a = [f(0.0)] * C_
+        neighbours = 0
+        for oy in (-1, 0, 1):
+            for ox in (-1, 0, 1):
+                X = (cx + ox) & U32
+                Y = (cy + oy) & U32
+                if X >= gw or Y >= gh:
+                    continue
+                cid = (Y * gw + X) & U32
+                k = int(start[cid])
+                while k < n and int(grid[k]) == cid:
+                    dx = q[k, 0] - x
+                    dy = q[k, 1] - y
+                    xx = dx * dx
+                    yy = dy * dy
+                    r2 = xx + yy
+                    if not (r2 > h2):
+                        e = h2 - r2
+                        w1 = cv * e
+                        w2 = w1 * e
+                        W = w2 * e
+                        mw = m * W
+                        density = density + mw
+                        mr = m / rho[k]
+                        t = mr * W
+                        weight = weight + t
+                        tx = t * vel[k, 0]
+                        ty = t * vel[k, 1]
+                        vx = vx + tx
+                        vy = vy + ty
+                        for c in range(C_):
+                            ta = t * attr[c, k]
+                            a[c] = a[c] + ta
+                        neighbours += 1
+                    k += 1
+        out[i] = (density, weight, (vx, vy), neighbours, (cy * gw + cx) & U32)
+        aout[:, i] = a
+    return out, aout
+
+
+SPECIAL_STATES = {"corners": lambda: S.corners(), "one_cell": lambda: S.one_cell(), "trips2": lambda: S.strip(*S.STRIP["trips2"])}
+
+
+def _special_state(fs, name):
+    """the scene after one oracle step, on the sample checker; two channels with -0.0, denormals and large values"""
+    from tests.sample_ref import SampleChecker, set_threads
+    set_threads(min(8, os.cpu_count() or 1))
+    st, tick, p0 = SPECIAL_STATES[name]()
+    chk = SampleChecker(st)
+    chk.set_particles(p0)
+    chk.step(tick)
+    p = chk.particles()
+    return chk, st, p, H.sample_channel_values(p.shape[0], 2)
+
+
+@pytest.mark.parametrize("name", sorted(SPECIAL_STATES))
+def test_checker_is_the_statement_at_wrapped_and_saturated_cells(fs, orc, name):
+    """The GPU tests of tests/test_sampling_hard_inputs_gpu.py compare the engine with the checker at queries whose cell
+    coordinates saturate, wrap to 0 or lie past the grid, at +-inf and NaN.  Here the checker is compared with the plain numpy
+    restatement of the header's statement at those queries, on states whose occupied cells include the grid's corners (corners),
+    one cell of 256 particles (one_cell) and rows of one particle per cell (trips2): every byte of every sample and channel sum."""
+    chk, st, p, attr = _special_state(fs, name)
+    pts = H.special_queries(st, p)
+    assert 200 <= pts.shape[0] <= 3000
+    u = fs.Uniform.from_buffer_copy(chk.uniform_bytes())
+    with np.errstate(all="ignore"):
+        want, wa = restated_sample(p, chk.start_indices(), u, pts, attr)
+    got, ga = chk.sample(pts, attr)
+    if got.tobytes() != want.tobytes():
+        k = int(np.flatnonzero((got.view(np.uint8).reshape(-1, 24) != want.view(np.uint8).reshape(-1, 24)).any(axis=1))[0])
+        raise AssertionError(f"{name}: checker and restatement differ at query {k} {pts[k]}: checker {got[k]}, restatement {want[k]}")
+    assert ga.tobytes() == wa.tobytes(), f"{name}: channel sums differ"
+    assert got["neighbours"].any() and not got["neighbours"].all()
+    chk.close()
+
+
+def test_special_query_set_reaches_what_it_names(fs, orc):
+    """On the checker and the corners scene: a query with neighbours in each of the four corner cells a particle can be in; a
+    query whose column wrapped to 0, and one whose row did; a query without a valid column (cx > grid_w), and one without a
+    valid row; queries with exactly one valid column (cx == grid_w); NaN, +-inf and -0.0 among the coordinates.  The cell
+    coordinates come from tests/pyref.py's xy_of_point, not from the sampler."""
+    chk, st, p, attr = _special_state(fs, "corners")
+    pts = H.special_queries(st, p)
+    out, _ = chk.sample(pts)
+    gw, gh = chk.grid_dims
+    assert (gw, gh) == S.CORNER_GRID
+    cell = H.query_cells(st, pts)
+    cx, cy = cell[:, 0], cell[:, 1]
+    assert np.array_equal(out["cell"], ((cy * gw + cx) & U32).astype(np.uint32))
+    for (x, y) in S.CORNER_CELLS:
+        here = (cx == x) & (cy == y)
+        assert (out["neighbours"][here] > 0).any(), f"no query with neighbours in corner cell ({x}, {y})"
+    big = np.nan_to_num(pts.astype(np.float64), nan=0.0, posinf=1e300, neginf=-1e300)
+    assert ((cx == 0) & (big[:, 0] > 1e9) & (cy >= 1) & (cy < gh)).any(), "no query whose column wrapped to 0 in a valid row"
+    assert ((cy == 0) & (big[:, 1] > 1e9) & (cx >= 1) & (cx < gw)).any(), "no query whose row wrapped to 0 in a valid column"
+    assert ((cx > gw) & (cx < 1000)).any() and ((cy > gh) & (cy < 1000)).any(), "no query just past the last valid column / row"
+    assert (cx == gw).any() and (cy == gh).any() and (cx == gw - 1).any() and (cy == gh - 1).any()
+    assert not out["neighbours"][(cx > gw) & (cx < 1000)].any()
+    assert np.isnan(pts).any() and np.isposinf(pts).any() and np.isneginf(pts).any()
+    assert (np.signbit(pts) & (pts == 0)).any()
+    assert (np.abs(pts) == np.float32(3e38)).any() and (np.abs(pts) == np.float32(1e10)).any()
+    chk.close()

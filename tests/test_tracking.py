@@ -1,6 +1,8 @@
 """CPU-side checks of the opt-in particle tracking: the checker of tests/track_ref.py is sound (its permutation
 is the one the oracle's sort applies, for both sorts), ids stay a permutation, every host binding names every new call, and the
-calls refuse a NULL handle without touching a device.  No GPU."""
+calls refuse a NULL handle without touching a device.  Last, the registry of the plain step's hard inputs
+(tests/hard_states2d.py) on the checker alone: every case moves most slots, the tie cases have ties the two sorts arrange
+differently.  No GPU."""
 import ctypes as C
 import os
 import re
@@ -114,3 +116,46 @@ def test_null_handle_is_invalid_without_a_device(fs):
     assert lib.fs_track_attr_device(None, 0, C.byref(out)) == inv
     assert lib.fs_download_particles_by_id(None, buf, 4) == inv
     assert b"null" in lib.fs_last_error()
+
+
+# ---- the registry of hard inputs (tests/hard_states2d.py): its cases test what they say ---------------------------------------
+from tests import hard_states2d as H  # noqa: E402
+
+
+@pytest.mark.parametrize("cid", H.CASE_IDS)
+def test_hard_input_cases_are_not_vacuous(fs, orc, cid):
+    """Every case of the registry on TrackChecker(verify=True) — the derived permutation IS the one the oracle's sort applied, at
+    every step, also where records are NaN or infinite and where hundreds of keys tie — and the figures the GPU tests rest on: a
+    case of at least 64 particles has a step in which more than half of the slots change occupant; a tie case run with the
+    reference network has a step with slots where the network's arrangement differs from the stable one (so an id that followed
+    the stable order would show); the ids stay a permutation.  tests/test_tracking_hard_inputs_gpu.py runs the same cases on
+    the engine."""
+    case = H.case_by_id(fs, orc, cid)
+    run = case.run()                                   # verify=True inside
+    print(case.describe())
+    assert len(run) == case.steps >= H.MIN_STEPS
+    moved, ties, finite = case.moved(), case.tie_slots(), case.finite_after()
+    assert len(moved) == len(ties) == len(finite) == case.steps
+    if case.n >= H.MOVED_MIN_N:
+        assert max(moved) > 0.5, moved
+    if case.tie_case and not case.stable:
+        assert max(ties) > 0, ties
+    for s, ids in enumerate(case.ids()):
+        assert np.array_equal(np.sort(ids), np.arange(case.n, dtype=np.uint32)), f"step {s}"
+    for s, step in enumerate(run):                     # the keys kept per step are the sorted records' keys, un-permuted
+        assert np.array_equal(step.keys[step.perm], step.rec["grid"]) and np.all(step.rec["grid"][:-1] <= step.rec["grid"][1:])
+
+
+def test_hard_input_registry_names_its_tie_cases_and_sorts(fs, orc):
+    """coincident, one_cell, corners, dense_scene and the four strips are tie cases and run with the reference network (the
+    strips, one_cell, corners and dense_scene with the counting sort as well); both sort modes and both quirk settings occur;
+    the cases that do not stay finite are the two the sampler's file names."""
+    tie = set(H.TIE_CASE_IDS)
+    for want in ("coincident", "one_cell/bitonic", "corners/quirks/bitonic", "corners/noquirks/bitonic", "dense_scene/bitonic",
+                 "strip/trips2/bitonic", "strip/trips3/bitonic", "strip/force_unstaged/bitonic", "strip/both_unstaged/bitonic"):
+        assert want in tie, want
+    assert len(H.CASE_IDS) == len(set(H.CASE_IDS))
+    cases = [H.case_by_id(fs, orc, cid) for cid in H.CASE_IDS]
+    assert {c.sort for c in cases} == set(H.SORTS) and {c.quirks for c in cases} == {True, False}
+    assert {c.n for c in cases} >= {2, 3, 5, 257, 4097, 5000}
+    assert sorted(c.name for c in cases if not c.stays_finite) == ["guard/inf_velocity", "nan_clamp"]
