@@ -1,5 +1,6 @@
 // engine.h — what the host files of the C ABI share beyond fs_host.h: the 2D simulation handle and the state of each of its
-// features, the step parameters, and the device check and create-time proofs (also used by engine_3d.hip).  The handle's files:
+// features, the step parameters, and the device check and create-time proofs (also used by the 3D handle's files through
+// engine_3d.h).  The handle's files:
 // engine.hip (life cycle, step, transfers, renderer hand-off), engine_features.hip (surface tension, particle tracking),
 // engine_query.hip (density render, field sampling), engine_selftest.hip (self-tests, read-outs), engine_slab.hip (the
 // multi-GPU slab handles).  Internal: include/fluidsim.h is the interface.
@@ -100,8 +101,8 @@ struct SurfaceTension {
 };
 
 // Opt-in particle tracking (build extension, DESIGN.md §12 and, on an fs_sim3, §20; single-domain handles): fs_track_* in
-// engine_features.hip, fs3_track_* in engine_3d.hip.  Two sets that swap roles every step: [cur] holds the ids / channels in the
-// order of the last enqueued step.  `capacity`: the slots of the handle, the stride of the channels (an fs_sim3: its n).
+// engine_features.hip, fs3_track_* in engine_3d_features.hip.  Two sets that swap roles every step: [cur] holds the ids /
+// channels in the order of the last enqueued step.  `capacity`: the slots of the handle, the stride of the channels (an fs_sim3: its n).
 struct Tracking {
     DevArray<uint32_t> id[2];
     DevArray<float> attr[2];        // channel c at c * capacity

@@ -1,0 +1,151 @@
+// engine_3d.h — what the host files of the fs3_* C ABI share: the 3D simulation handle with the state of each of its features, the
+// Params3 both the step and the queries start from, and the few helpers more than one of them needs.  The handle's files:
+// engine_3d.hip (lattice, life cycle, step, getters, transfers, timing), engine_3d_features.hip (what the step enqueues for:
+// colliders, surface tension, tracking), engine_3d_query.hip (everything behind sample_stale: sampling, rendering, extraction).
+// From the 2D engine (engine.h): the device check, the create-time proofs, the owners, the sort policy and Tracking.
+#pragma once
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <new>
+
+#include "engine.h"
+#include "fs_3d.h"
+
+// Every resource is held by an owner (fs_host.h) and freed by `delete`; members go in reverse order of declaration: the
+// device arrays first, then the events (profile ring, sort policy, t1 / t0), the stream last.
+struct fs_sim3 {
+    fs3_settings st{};
+    uint32_t n = 0, gw = 0, gh = 0, gd = 0, ncell = 0, tick = 0, work_cap = 0;
+    int device = 0;
+    int math_mode = FS_MATH_IEEE;
+    fsd::Stream stream;
+    fsd::Event t0, t1;
+    fsd::SortPolicy sortp;       // host side of the sort's late-stage plan (sort_policy.h)
+    fsd::PassRing prof;          // per-pass timing
+    fsd::DevArray<float4> pos, vel, pos_s, vel_s, pred;
+    fsd::DevArray<uint32_t> key, cs, counter, dirty;
+    fsd::DevArray<fsd::u64> pairs;
+    fsd::DevArray<fsd::u64> masks;   // 9 x n pass masks of the 27-cell sweep, k3_density -> k3_force (Params3::handoff)
+    bool handoff = true;
+    fsd::DevArray<unsigned char> work;
+    fsd::DevArray<fs3_particle> aos;
+    fsd::ConstDiv div_2h3{}, div_h2{};
+    bool share_div = false;      // all create-time proofs of the shared-denominator path succeeded
+    float mass = 0.0f;           // of the tick of the last step enqueued: what field sampling weighs with
+    bool sample_stale = true;    // no step enqueued since create / the last upload: records and cell table do not belong together
+
+    // The opt-in features' state, one struct and one line in enqueue3 each.
+    // Scratch of surface extraction, allocated by its first call and grown only by a larger lattice.
+    struct MeshScratch {
+        fsd::DevArray<float> field;      // node densities
+        fsd::DevArray<uint32_t> rank;    // per node: the vertex index of its cell
+        fsd::DevArray<uint32_t> sums;    // two words per workgroup of the count pass: sums, then offsets
+        // Room for a lattice of `nodes`: all three or none.  hipFree of the arrays it replaces waits for the work that still reads them.
+        fs_status reserve(size_t nodes) {
+            if (nodes <= field.n) return FS_OK;
+            const hipError_t e1 = field.alloc(nodes), e2 = rank.alloc(nodes);
+            const hipError_t e3 = sums.alloc(2 * (size_t)fsd::mesh3_workgroups((uint32_t)nodes));
+            if (e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess) return FS_OK;
+            (void)hipGetLastError();
+            field.release(); rank.release(); sums.release();
+            return fsd::fail(FS_ERR_OOM, "extraction: device scratch");
+        }
+    } mesh;
+    // The opt-in static collider: one float4 push vector per voxel; w == 0: none, and never set: no allocation.
+    // field.n is the capacity (it only grows), w * h * d the field in use.
+    struct Collider {
+        fsd::DevArray<float4> field;
+        uint32_t w = 0, h = 0, d = 0;
+        size_t voxels() const { return (size_t)w * h * d; }
+        void set(uint32_t w_, uint32_t h_, uint32_t d_) { w = w_; h = h_; d = d_; }
+        void clear() { w = h = d = 0; }
+        // Room for `count` vectors.  Allocates only when the field grew, and then only after the steps in flight on `st` — which
+        // read the old array — are done.  On failure the handle has no collider.
+        fs_status reserve(hipStream_t st, size_t count) {
+            if (count <= field.n) return FS_OK;
+            FS_HIP(hipStreamSynchronize(st));
+            clear();
+            if (field.alloc(count) != hipSuccess) {
+                (void)hipGetLastError();
+                field.release();
+                return fsd::fail(FS_ERR_OOM, "collider: device field");
+            }
+            return FS_OK;
+        }
+        // What a step takes, by value into *K: it keeps the field it was enqueued with (fs3_collider_* order their writes on the
+        // stream behind it).  Null: none is set.  size: the settings' box.
+        const fsd::Collide3* for_step(fs_vec3 size, fsd::Collide3* K) const {
+            *K = fsd::Collide3{field.p, w, h, d, size.x, size.y, size.z};
+            return w ? K : nullptr;
+        }
+    } collider;
+    // The opt-in surface tension: never enabled: no allocation, no launch.
+    struct Tension {
+        fsd::DevArray<float4> st;    // the last step's force per sorted slot {x, y, z, 0}; allocated by the first enable
+        float sigma = 0.0f, tau = 0.0f;
+        bool on = false;
+        bool valid = false;          // a step has been enqueued since the feature was last enabled: st belongs to the state
+        // This step's pass, between the density and the force pass (inside the force interval of the profile), with the coefficients
+        // of this enqueue by value; returns what launch3_force adds, or null.
+        const float4* enqueue(hipStream_t stream, const fsd::Params3& P, const fsd::Arrays3& A) {
+            using fsd::Tension3;
+            if (!on) return nullptr;
+            const Tension3 T{P.h2, 6.0f * P.poly6, 3.0f * P.h2, sigma, tau};
+            fsd::launch3_surface_tension(stream, P, A, T, st.p);
+            valid = true;
+            return st.p;
+        }
+    } tension;
+    // The opt-in particle tracking: the 2D engine's owner (engine.h), stride n; never enabled: no allocation, no launch.
+    fsd::Tracking trk;
+
+    // the arrays as the launchers see them (fs_3d.h): the force pass writes the new positions into the spare buffer
+    fsd::Arrays3 arrays() const {
+        fsd::Arrays3 A;
+        A.pos = pos.p; A.vel = vel.p; A.pos_out = pos_s.p; A.vel_s = vel_s.p; A.pred = pred.p; A.key = key.p;
+        A.pairs = pairs.p; A.cs = cs.p; A.masks = handoff ? masks.p : nullptr;
+        A.work = work.p; A.counter = counter.p; A.work_cap = work_cap; A.aos = aos.p;
+        return A;
+    }
+};
+
+namespace fsd {
+
+static const float PI3 = 3.14159265359f;
+
+// What the step and field sampling both need of Params3: counts, grid, h, the half-bounds and the poly6 constant; the rest zero.
+inline Params3 params3_common(const fs_sim3& s, float mass) {
+    const float h = s.st.smoothing_radius;
+    Params3 P;
+    std::memset(&P, 0, sizeof P);
+    P.n = s.n; P.gw = s.gw; P.gh = s.gh; P.gd = s.gd; P.ncell = s.ncell;
+    P.h = h; P.h2 = h * h;
+    P.bx = s.st.size.x * 0.5f; P.by = s.st.size.y * 0.5f; P.bz = s.st.size.z * 0.5f;
+    P.mass = mass;
+    P.poly6 = 315.0f / (64.0f * PI3 * std::pow(h, 9.0f));      // host libm, as in the oracle
+    return P;
+}
+
+// a barrier time-out of the sort's stand-by kernel leaves the particle order undefined: reported wherever state is handed over
+inline fs_status sort_health3(fs_sim3* s) { return s->sortp.health(s->dirty.p, s->n); }
+
+// The box and lattice of an fs3_view into any query that carries them (Sample3Query, Sample3AttrQuery, Mesh3Query).
+template <class Query>
+void set_view3(Query* Q, const fs3_view& view) {
+    Q->wmin = make_float3(view.world_min.x, view.world_min.y, view.world_min.z);
+    Q->wmax = make_float3(view.world_max.x, view.world_max.y, view.world_max.z);
+    Q->width = view.width; Q->height = view.height; Q->depth = view.depth;
+}
+
+// n float4 {x, y, z, -} of a device array as fs_vec3 on the host.  Blocking on `st`.
+inline fs_status download_vec3(hipStream_t st, const float4* dev, size_t n, fs_vec3* dst) {
+    std::unique_ptr<float4[]> host(new (std::nothrow) float4[n]);
+    if (!host) return fail(FS_ERR_OOM, "host allocation failed");
+    FS_HIP(hipMemcpyAsync(host.get(), dev, n * sizeof(float4), hipMemcpyDeviceToHost, st));
+    FS_HIP(hipStreamSynchronize(st));
+    for (size_t k = 0; k < n; ++k) dst[k] = fs_vec3{host[k].x, host[k].y, host[k].z};
+    return FS_OK;
+}
+
+}  // namespace fsd

@@ -1,0 +1,188 @@
+// engine_3d_features.hip — the opt-in features the 3D step enqueues for (their state: engine_3d.h, one struct each): colliders
+// (DESIGN.md §18), surface tension (§19), particle tracking (§20) and, on top of tracking, fs3_download_particles_by_id.
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "engine_3d.h"
+
+using fsd::DevArray;
+using fsd::fail;
+using fsd::sort_health3;
+namespace {
+// The checks the two collider setters share, in the order the header lists them (the handle first, by the caller).
+fs_status collider3_check(const void* array, uint32_t w, uint32_t h, uint32_t d) {
+    const uint32_t top = fsd::COLLIDER3_MAX_EXTENT;
+    if (!array) return fail(FS_ERR_INVALID, "null argument");
+    if (w == 0u || h == 0u || d == 0u || w > top || h > top || d > top) return fail(FS_ERR_INVALID, "collider: an extent of 0 or above 1024");
+    return FS_OK;
+}
+
+// The field in use as w * h * d fs_vec3 on the host.  Blocking.
+fs_status collider3_read(fs_sim3* s, fs_vec3* dst) { return fsd::download_vec3(s->stream, s->collider.field.p, s->collider.voxels(), dst); }
+
+// ids (attr = false) or one channel, host <-> the arrays of the last enqueued step.  Blocking.
+fs_status track3_copy(fs_sim3* s, int channel, bool attr, void* host, size_t n, bool upload) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    FS_HIP(hipSetDevice(s->device));
+    FS_TRY(s->trk.copy(s->stream, s->n, s->n, channel, attr, host, n, upload));
+    return upload ? FS_OK : sort_health3(s);
+}
+}  // namespace
+
+extern "C" {
+
+// ---- 3D colliders -------------------------------------------------------------------------------------
+fs_status fs3_collider_upload(fs_sim3* s, const fs_vec3* field, uint32_t w, uint32_t h, uint32_t d) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    FS_TRY(collider3_check(field, w, h, d));
+    const size_t voxels = (size_t)w * h * d;
+    std::unique_ptr<float4[]> host(new (std::nothrow) float4[voxels]);
+    if (!host) return fail(FS_ERR_OOM, "host allocation failed");
+    for (size_t k = 0; k < voxels; ++k) {
+        const fs_vec3 f = field[k];
+        if (!std::isfinite(f.x) || !std::isfinite(f.y) || !std::isfinite(f.z)) return fail(FS_ERR_INVALID, "collider: non-finite component");
+        host[k] = make_float4(f.x, f.y, f.z, 0.0f);
+    }
+    FS_HIP(hipSetDevice(s->device));
+    FS_TRY(s->collider.reserve(s->stream, voxels));
+    // on the stream: after the steps in flight, before the steps to come
+    FS_HIP(hipMemcpyAsync(s->collider.field.p, host.get(), voxels * sizeof(float4), hipMemcpyHostToDevice, s->stream));
+    FS_HIP(hipStreamSynchronize(s->stream));
+    s->collider.set(w, h, d);
+    return FS_OK;
+}
+
+fs_status fs3_collider_from_mask(fs_sim3* s, const uint8_t* mask, uint32_t w, uint32_t h, uint32_t d, fs_vec3* field_host) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    FS_TRY(collider3_check(mask, w, h, d));
+    const size_t voxels = (size_t)w * h * d;
+    bool any_free = false;
+    for (size_t k = 0; k < voxels && !any_free; ++k) any_free = !(mask[k] > 128);
+    if (!any_free) return fail(FS_ERR_INVALID, "collider: the mask has no free voxel");
+    FS_HIP(hipSetDevice(s->device));
+    DevArray<uint8_t> dmask;
+    DevArray<uint32_t> near_x, near_xy;
+    if (dmask.alloc(voxels) != hipSuccess || near_x.alloc(voxels) != hipSuccess || near_xy.alloc(voxels) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FS_ERR_OOM, "collider: device staging");
+    }
+    FS_TRY(s->collider.reserve(s->stream, voxels));
+    fsd::ColliderMask3 Q;
+    Q.mask = dmask.p; Q.w = w; Q.h = h; Q.d = d;
+    Q.vx = s->st.size.x / (float)w; Q.vy = s->st.size.y / (float)h; Q.vz = s->st.size.z / (float)d;
+    Q.near_x = near_x.p; Q.near_xy = near_xy.p; Q.field = s->collider.field.p;
+    hipError_t e = hipMemcpyAsync(dmask.p, mask, voxels, hipMemcpyHostToDevice, s->stream);
+    if (e == hipSuccess) { fsd::launch3_collider_from_mask(s->stream, Q); e = hipGetLastError(); }
+    const hipError_t es = hipStreamSynchronize(s->stream);      // before the staging is freed, whatever happened
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) { s->collider.clear(); return fail(FS_ERR_DEVICE, hipGetErrorString(e)); }
+    s->collider.set(w, h, d);
+    return field_host ? collider3_read(s, field_host) : FS_OK;
+}
+
+fs_status fs3_collider_clear(fs_sim3* s) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    FS_HIP(hipSetDevice(s->device));
+    FS_HIP(hipStreamSynchronize(s->stream));       // the steps in flight read the field
+    s->collider.clear();
+    s->collider.field.release();
+    return FS_OK;
+}
+
+fs_status fs3_collider_dims(const fs_sim3* s, uint32_t* w, uint32_t* h, uint32_t* d) {
+    if (!s || !w || !h || !d) return fail(FS_ERR_INVALID, "null argument");
+    *w = s->collider.w; *h = s->collider.h; *d = s->collider.d;
+    return FS_OK;
+}
+
+fs_status fs3_collider_download(fs_sim3* s, fs_vec3* dst, size_t n) {
+    if (!s || !dst) return fail(FS_ERR_INVALID, "null argument");
+    if (s->collider.w == 0u) return fail(FS_ERR_INVALID, "collider: none is set");
+    if (n != s->collider.voxels()) return fail(FS_ERR_INVALID, "collider: n must be w * h * d");
+    FS_HIP(hipSetDevice(s->device));
+    return collider3_read(s, dst);
+}
+
+// ---- 3D surface tension -------------------------------------------------------------------------------
+fs_status fs3_set_surface_tension(fs_sim3* s, int enable, float coefficient, float threshold) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    if (!enable) { s->tension.on = false; return FS_OK; }          // the two floats are not looked at
+    if (std::isnan(coefficient)) return fail(FS_ERR_INVALID, "surface tension: coefficient is NaN");
+    if (std::isnan(threshold)) return fail(FS_ERR_INVALID, "surface tension: threshold is NaN");
+    if (!s->tension.st.p) {
+        FS_HIP(hipSetDevice(s->device));
+        if (s->tension.st.alloc(s->n) != hipSuccess) {
+            (void)hipGetLastError();
+            s->tension.st.release();
+            return fail(FS_ERR_OOM, "surface tension: device array");
+        }
+    }
+    if (!s->tension.on) s->tension.valid = false;                  // fs3_download_surface_tension waits for a step of this enable
+    s->tension.on = true; s->tension.sigma = coefficient; s->tension.tau = threshold;
+    return FS_OK;
+}
+
+int fs3_surface_tension_enabled(const fs_sim3* s) { return (s && s->tension.on) ? 1 : 0; }
+
+fs_status fs3_surface_tension_params(const fs_sim3* s, float* coefficient, float* threshold) {
+    if (!s || !coefficient || !threshold) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->tension.on) return fail(FS_ERR_INVALID, "surface tension: not enabled");
+    *coefficient = s->tension.sigma; *threshold = s->tension.tau;
+    return FS_OK;
+}
+
+fs_status fs3_download_surface_tension(fs_sim3* s, fs_vec3* dst, size_t n) {
+    if (!s || !dst) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->tension.on) return fail(FS_ERR_INVALID, "surface tension: not enabled");
+    if (!s->tension.valid) return fail(FS_ERR_INVALID, "surface tension: no step since surface tension was last enabled");
+    if (n != s->n) return fail(FS_ERR_INVALID, "surface tension: n must equal the particle count");
+    FS_HIP(hipSetDevice(s->device));
+    FS_TRY(fsd::download_vec3(s->stream, s->tension.st.p, n, dst));
+    return sort_health3(s);
+}
+
+// ---- 3D particle tracking -----------------------------------------------------------------------------
+fs_status fs3_track_enable(fs_sim3* s, int channels) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    FS_HIP(hipSetDevice(s->device));
+    return s->trk.enable(s->stream, s->n, s->n, channels);
+}
+
+fs_status fs3_track_disable(fs_sim3* s) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    s->trk.channels = -1;           // the arrays stay allocated until the handle is destroyed
+    return FS_OK;
+}
+
+int fs3_track_channels(const fs_sim3* s) { return s ? s->trk.channels : -1; }
+
+fs_status fs3_track_download_ids(fs_sim3* s, uint32_t* dst, size_t n) { return track3_copy(s, 0, false, dst, n, false); }
+fs_status fs3_track_upload_ids(fs_sim3* s, const uint32_t* src, size_t n) { return track3_copy(s, 0, false, (void*)src, n, true); }
+fs_status fs3_track_download_attr(fs_sim3* s, int channel, float* dst, size_t n) { return track3_copy(s, channel, true, dst, n, false); }
+fs_status fs3_track_upload_attr(fs_sim3* s, int channel, const float* src, size_t n) { return track3_copy(s, channel, true, (void*)src, n, true); }
+
+fs_status fs3_track_ids_device(fs_sim3* s, const uint32_t** out) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    return s->trk.device_ptr(s->n, 0, false, (const void**)out);
+}
+
+fs_status fs3_track_attr_device(fs_sim3* s, int channel, const float** out) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    return s->trk.device_ptr(s->n, channel, true, (const void**)out);
+}
+
+/* Off the step path: two downloads and a scatter on the host, so entries of dst that no id names are never written. */
+fs_status fs3_download_particles_by_id(fs_sim3* s, fs3_particle* dst, size_t n) {
+    if (!s || (!dst && n)) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->trk.on()) return fail(FS_ERR_INVALID, "tracking is off (enable it first)");
+    std::vector<fs3_particle> rec;
+    std::vector<uint32_t> ids;
+    try { rec.resize(s->n); ids.resize(s->n); } catch (const std::bad_alloc&) { return fail(FS_ERR_OOM, "host staging"); }
+    FS_TRY(fs3_download_particles(s, rec.data(), rec.size()));
+    FS_TRY(fs3_track_download_ids(s, ids.data(), ids.size()));
+    fsd::Tracking::scatter_by_id(ids, rec, dst, n);
+    return FS_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
 // fs_3d.h — what the files of the 3D step share (kernels_3d.hip, kernels_density3d.hip, kernels_force3d.hip: the kernels and
-// their launchers, engine_3d.hip: the handle and the fs3_* C ABI): the step parameters, the array set of the launchers, the launchers.  A header of its own:
+// their launchers, engine_3d*.hip over engine_3d.h: the handle and the fs3_* C ABI): the step parameters, the array set of the
+// launchers, the launchers.  A header of its own:
 // fs_kernels.h stays the 2D launchers' list, and kernels_sort_tile.inc takes the predict + cell-key expression from here.
 #pragma once
 #include "fs_kernels.h"
@@ -151,9 +152,10 @@ void launch3_mesh_faces(hipStream_t st, const Mesh3Query& Q);                   
 // 3D collider producer (kernels_collide3d.hip): a w x h x d u8 mask (> 128: solid) to the push field of Collide3 by
 // an exact Euclidean distance transform in index space, three separable u32 passes.  Device pointers; host side only.  `near_x` and
 // `near_xy` hold w * h * d words each (the nearest free voxel after the X pass, packed x | y << 16 after the Y pass).
+constexpr uint32_t COLLIDER3_MAX_EXTENT = 1024u;   // the largest extent: the host's check and the LDS line of the three passes
 struct ColliderMask3 {
     const uint8_t* mask = nullptr;
-    uint32_t w = 0, h = 0, d = 0;      // each 1 .. 1024
+    uint32_t w = 0, h = 0, d = 0;      // each 1 .. COLLIDER3_MAX_EXTENT
     float vx = 0.0f, vy = 0.0f, vz = 0.0f;   // voxel edge per axis: size.a / (float)W_a
     uint32_t* near_x = nullptr;
     uint32_t* near_xy = nullptr;

@@ -83,6 +83,24 @@ fs_status staged_query(hipStream_t st, const Pt* points, size_t n, Rec* out, flo
     return r;
 }
 
+// The blocking form of a call that only reads back what a kernel wrote (a G-buffer, counts, a mesh): device staging for `n`
+// records, `enqueue(out_dev)` puts the kernel on `st` and returns a status, the records land in `out`.  As staged_query: no
+// staging is FS_ERR_OOM, and the stream is synchronised before the staging is freed, whatever happened.
+template <class Rec, class Enqueue>
+fs_status download_records(hipStream_t st, size_t n, Rec* out, Enqueue enqueue) {
+    DevArray<Rec> dout;
+    if (dout.alloc(n) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FS_ERR_OOM, "sampling: device staging");
+    }
+    fs_status r = enqueue(dout.p);
+    hipError_t e = r == FS_OK ? hipMemcpyAsync(out, dout.p, n * sizeof(Rec), hipMemcpyDeviceToHost, st) : hipSuccess;
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    if (r == FS_OK && e != hipSuccess) r = fail(FS_ERR_DEVICE, hipGetErrorString(e));
+    return r;
+}
+
 // A stream or an event of a handle: created into `h` by the HIP call that fits, destroyed with its owner.
 template <class H, hipError_t (*Destroy)(H)>
 struct Owned {

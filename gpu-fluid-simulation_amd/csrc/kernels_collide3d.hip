@@ -5,7 +5,8 @@
 //   k3c_pass_x  per row (j, k):    the free i' minimising |i - i'|
 //   k3c_pass_y  per column (i, k): over the rows' answers, minimising (x - i)^2 + (j' - j)^2
 //   k3c_pass_z  per pillar (i, j): over the columns' answers, minimising (x - i)^2 + (y - j)^2 + (k' - k)^2 -> the push vector
-// One line per workgroup, staged in LDS (an extent is at most 1024), targets beyond the workgroup looped, brute force over the line
+// One line per workgroup, staged in LDS (an extent is at most COLLIDER3_MAX_EXTENT of fs_3d.h),
+// targets beyond the workgroup looped, brute force over the line
 // in ascending order with a strict `<`: ties go to the smaller coordinate.  No atomics, no waiting between workgroups; off the step
 // path.  Squared index distances are at most 3 * 1023^2 < 2^22.
 #include <hip/hip_runtime.h>
@@ -15,13 +16,12 @@
 namespace fsd {
 
 #define B3C 256
-#define C3_MAX 1024u             // largest extent (engine_3d.hip checks it)
 #define C3_NONE 0xFFFFFFFFu      // no free voxel in the line(s) so far
 
 __device__ __forceinline__ uint32_t sq_diff(uint32_t a, uint32_t b) { const uint32_t d = a > b ? a - b : b - a; return d * d; }
 
 __global__ __launch_bounds__(B3C) void k3c_pass_x(const uint8_t* __restrict__ mask, uint32_t w, uint32_t* __restrict__ near_x) {
-    __shared__ uint32_t s_free[C3_MAX];
+    __shared__ uint32_t s_free[COLLIDER3_MAX_EXTENT];
     const size_t base = (size_t)blockIdx.x * w;                          // row (j, k) = blockIdx.x: contiguous
     for (uint32_t t = threadIdx.x; t < w; t += B3C) s_free[t] = mask[base + t] > 128 ? 0u : 1u;
     __syncthreads();
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(B3C) void k3c_pass_x(const uint8_t* __restrict__ ma
 
 __global__ __launch_bounds__(B3C) void k3c_pass_y(const uint32_t* __restrict__ near_x, uint32_t w, uint32_t h,
                                                   uint32_t* __restrict__ near_xy) {
-    __shared__ uint32_t s_x[C3_MAX];
+    __shared__ uint32_t s_x[COLLIDER3_MAX_EXTENT];
     const uint32_t i = blockIdx.x % w, k = blockIdx.x / w;               // column (i, k): stride w
     const size_t base = (size_t)k * h * w + i;
     for (uint32_t t = threadIdx.x; t < h; t += B3C) s_x[t] = near_x[base + (size_t)t * w];
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(B3C) void k3c_pass_y(const uint32_t* __restrict__ n
 
 __global__ __launch_bounds__(B3C) void k3c_pass_z(const uint32_t* __restrict__ near_xy, uint32_t w, uint32_t h, uint32_t d,
                                                   float vx, float vy, float vz, float4* __restrict__ field) {
-    __shared__ uint32_t s_xy[C3_MAX];
+    __shared__ uint32_t s_xy[COLLIDER3_MAX_EXTENT];
     const uint32_t i = blockIdx.x % w, j = blockIdx.x / w;               // pillar (i, j): stride w * h
     const size_t base = (size_t)j * w + i, plane = (size_t)w * h;
     for (uint32_t t = threadIdx.x; t < d; t += B3C) s_xy[t] = near_xy[base + t * plane];

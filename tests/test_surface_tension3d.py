@@ -280,7 +280,7 @@ def _header_text():
 
 def test_constants_match_the_sources():
     k3d = paths3d.source_text("kernels_density3d.hip")
-    eng = paths3d.source_text("engine_3d.hip")
+    eng = paths3d.source_text("engine_3d.h")
     with open(R.SOURCES[0]) as fh:
         chk = fh.read()
     num = r"([0-9]+\.[0-9]+)f"
