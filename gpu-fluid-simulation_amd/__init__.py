@@ -33,6 +33,7 @@ from ._abi import (  # noqa: F401
     SURFACE_HIT_DTYPE,
     Camera3,
     ExtensionMissing,
+    Nozzle3,
     Options,
     Settings,
     Settings3,
@@ -576,6 +577,47 @@ class FluidSimulation3D:
         p = C.c_void_p()
         _check(self._lib, self._lib.fs3_track_attr_device(self._h, int(channel), C.byref(p)))
         return p.value
+
+    # -- 3D particle count (build extension) ------------------
+    @property
+    def capacity(self):
+        """Slots of the handle: particle_count can grow to this (reserve() raises it)."""
+        return int(self._lib.fs3_capacity(self._h))
+
+    def reserve(self, capacity):
+        """Room for `capacity` particles (grow-only, blocking); the state and everything observable are preserved."""
+        _check(self._lib, self._lib.fs3_reserve(self._h, int(capacity)))
+
+    def emit(self, records):
+        """Append PARTICLE3_DTYPE records behind the live particles, all fields as given; particle_count + len <= capacity."""
+        arr = np.ascontiguousarray(records, dtype=PARTICLE3_DTYPE)
+        _check(self._lib, self._lib.fs3_emit_particles(self._h, arr.ctypes.data_as(C.c_void_p), arr.shape[0]))
+
+    def emit_nozzle(self, origin, u, v, velocity, nu, nv):
+        """Append a layer of nu x nv particles generated on the device: centred on `origin`, spaced by the vectors u and v,
+        all with `velocity` (include/fluidsim.h "3D particle count")."""
+        vec = lambda a: Vec3(float(a[0]), float(a[1]), float(a[2]))
+        z = Nozzle3(vec(origin), vec(u), vec(v), vec(velocity), int(nu), int(nv))
+        _check(self._lib, self._lib.fs3_emit_nozzle(self._h, C.byref(z)))
+
+    def remove_box(self, lo, hi):
+        """Remove every particle with lo <= position <= hi on every axis (blocking, stable); returns how many went."""
+        a, b, n = Vec3(*[float(x) for x in lo]), Vec3(*[float(x) for x in hi]), C.c_uint32()
+        _check(self._lib, self._lib.fs3_remove_in_box(self._h, C.byref(a), C.byref(b), C.byref(n)))
+        return int(n.value)
+
+    def remove(self, flags):
+        """Remove the particles whose entry of `flags` (one per particle, download_particles() order) is non-zero (blocking,
+        stable); returns how many went."""
+        f = np.ascontiguousarray(np.asarray(flags) != 0, dtype=np.uint8)
+        n = C.c_uint32()
+        _check(self._lib, self._lib.fs3_remove_flagged(self._h, f.ctypes.data_as(C.c_void_p), f.shape[0], C.byref(n)))
+        return int(n.value)
+
+    @property
+    def next_id(self):
+        """The id the next emitted particle gets while tracking is on (0 when it is off)."""
+        return int(self._lib.fs3_track_next_id(self._h))
 
     # -- 3D field sampling (build extension; DESIGN.md §14, the channels: §20) ----
     def _sample_attr(self, n):

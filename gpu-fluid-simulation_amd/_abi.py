@@ -152,6 +152,11 @@ class SurfaceParams3(C.Structure):
     _fields_ = [("iso", C.c_float), ("t_near", C.c_float), ("ds", C.c_float), ("max_steps", C.c_uint32), ("refine", C.c_uint32)]
 
 
+class Nozzle3(C.Structure):
+    """fs3_nozzle (include/fluidsim.h "3D particle count"): 56 bytes."""
+    _fields_ = [("origin", Vec3), ("u", Vec3), ("v", Vec3), ("velocity", Vec3), ("nu", C.c_uint32), ("nv", C.c_uint32)]
+
+
 class SurfaceHit3(C.Structure):
     """fs3_surface_hit (include/fluidsim.h): 40 bytes."""
     _fields_ = [("t", C.c_float), ("density", C.c_float), ("normal", Vec3), ("velocity", Vec3), ("steps", C.c_uint32),
@@ -352,6 +357,13 @@ PROTOTYPES = {
     "fs3_surface_tension_enabled": (C.c_int, [_P]),
     "fs3_surface_tension_params": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "fs3_download_surface_tension": (C.c_int, [_P, _P, C.c_size_t]),
+    "fs3_reserve": (C.c_int, [_P, C.c_uint32]),
+    "fs3_capacity": (C.c_uint32, [_P]),
+    "fs3_emit_particles": (C.c_int, [_P, _P, C.c_size_t]),
+    "fs3_emit_nozzle": (C.c_int, [_P, C.POINTER(Nozzle3)]),
+    "fs3_remove_in_box": (C.c_int, [_P, C.POINTER(Vec3), C.POINTER(Vec3), C.POINTER(C.c_uint32)]),
+    "fs3_remove_flagged": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "fs3_track_next_id": (C.c_uint32, [_P]),
     "fs_selftest_constdiv": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_uint32)]),
     "fs_sort_plan_read": (C.c_int, [C.c_void_p, C.POINTER(SortPlanInfo)]),
     "fs_selftest_sort_policy": (C.c_int, [C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t,

@@ -102,7 +102,7 @@ struct SurfaceTension {
 
 // Opt-in particle tracking (build extension, DESIGN.md §12 and, on an fs_sim3, §20; single-domain handles): fs_track_* in
 // engine_features.hip, fs3_track_* in engine_3d_features.hip.  Two sets that swap roles every step: [cur] holds the ids /
-// channels in the order of the last enqueued step.  `capacity`: the slots of the handle, the stride of the channels (an fs_sim3: its n).
+// channels in the order of the last enqueued step.  `capacity`: the slots of the handle, the stride of the channels (an fs_sim3: its cap).
 struct Tracking {
     DevArray<uint32_t> id[2];
     DevArray<float> attr[2];        // channel c at c * capacity

@@ -1,7 +1,8 @@
 // engine_3d.h — what the host files of the fs3_* C ABI share: the 3D simulation handle with the state of each of its features, the
 // Params3 both the step and the queries start from, and the few helpers more than one of them needs.  The handle's files:
 // engine_3d.hip (lattice, life cycle, step, getters, transfers, timing), engine_3d_features.hip (what the step enqueues for:
-// colliders, surface tension, tracking), engine_3d_query.hip (everything behind sample_stale: sampling, rendering, extraction).
+// colliders, surface tension, tracking), engine_3d_query.hip (everything behind sample_stale: sampling, rendering, extraction),
+// engine_3d_count.hip (a particle count that changes at run time: reserve, emit, remove).
 // From the 2D engine (engine.h): the device check, the create-time proofs, the owners, the sort policy and Tracking.
 #pragma once
 #include <cmath>
@@ -16,7 +17,9 @@
 // device arrays first, then the events (profile ring, sort policy, t1 / t0), the stream last.
 struct fs_sim3 {
     fs3_settings st{};
-    uint32_t n = 0, gw = 0, gh = 0, gd = 0, ncell = 0, tick = 0, work_cap = 0;
+    uint32_t n = 0;              // the live count: what every step and query works on
+    uint32_t cap = 0;            // slots of every per-slot array (>= n; == n until fs3_reserve), the stride of masks and channels
+    uint32_t gw = 0, gh = 0, gd = 0, ncell = 0, tick = 0, work_cap = 0;
     int device = 0;
     int math_mode = FS_MATH_IEEE;
     fsd::Stream stream;
@@ -26,7 +29,7 @@ struct fs_sim3 {
     fsd::DevArray<float4> pos, vel, pos_s, vel_s, pred;
     fsd::DevArray<uint32_t> key, cs, counter, dirty;
     fsd::DevArray<fsd::u64> pairs;
-    fsd::DevArray<fsd::u64> masks;   // 9 x n pass masks of the 27-cell sweep, k3_density -> k3_force (Params3::handoff)
+    fsd::DevArray<fsd::u64> masks;   // 18 x cap pass masks of the 27-cell sweep, k3_density -> k3_force (Params3::handoff)
     bool handoff = true;
     fsd::DevArray<unsigned char> work;
     fsd::DevArray<fs3_particle> aos;
@@ -97,8 +100,22 @@ struct fs_sim3 {
             return st.p;
         }
     } tension;
-    // The opt-in particle tracking: the 2D engine's owner (engine.h), stride n; never enabled: no allocation, no launch.
+    // The opt-in particle tracking: the 2D engine's owner (engine.h), stride cap; never enabled: no allocation, no launch.
     fsd::Tracking trk;
+    uint32_t next_id = 0;        // the id of the next particle emitted while tracking is on: the live count at fs3_track_enable
+    // Scratch of a removal, allocated by the first one for `cap` slots and released by fs3_reserve.
+    struct RemoveScratch {
+        fsd::DevArray<uint8_t> flags;    // per slot: removed
+        fsd::DevArray<uint32_t> sums;    // per workgroup of the flags pass: survivors, then offsets; the total behind them
+        fs_status reserve(uint32_t cap) {
+            if (flags.p) return FS_OK;
+            if (flags.alloc(cap) == hipSuccess && sums.alloc((size_t)fsd::remove3_workgroups(cap) + 1) == hipSuccess) return FS_OK;
+            (void)hipGetLastError();
+            release();
+            return fsd::fail(FS_ERR_OOM, "removal: device scratch");
+        }
+        void release() { flags.release(); sums.release(); }
+    } removal;
 
     // the arrays as the launchers see them (fs_3d.h): the force pass writes the new positions into the spare buffer
     fsd::Arrays3 arrays() const {

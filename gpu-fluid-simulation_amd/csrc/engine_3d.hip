@@ -1,6 +1,6 @@
 // engine_3d.hip — host side of the 3D extension of the step (kernels and launchers: kernels_3d.hip, kernels_density3d.hip,
 // kernels_force3d.hip; fs_3d.h): the lattice, the handle's life cycle, the step, the getters, the particle transfers and the
-// timed steps.  The handle and what its three files share: engine_3d.h.
+// timed steps.  The handle and what its files share: engine_3d.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -79,7 +79,7 @@ fs_status enqueue3(fs_sim3* s, const fs3_tick_settings* t) {
     }
     if (ev) FS_HIP(hipEventRecord(ev[2], st));
     launch3_reorder(st, P, A);
-    s->trk.carry(st, s->n, s->pairs.p, s->n);              // particle tracking, if on (inside the FS_PASS_REORDER interval)
+    s->trk.carry(st, s->n, s->pairs.p, s->cap);             // particle tracking, if on (inside the FS_PASS_REORDER interval)
     if (ev) FS_HIP(hipEventRecord(ev[3], st));
     launch3_density(st, P, A, tol);
     if (ev) FS_HIP(hipEventRecord(ev[4], st));
@@ -131,7 +131,7 @@ fs_status fs3_create_ex(const fs3_settings* st, int device, fs_vec3 off, int mat
     FS_TRY(fsd::use_device(device));
     std::unique_ptr<fs_sim3> s(new (std::nothrow) fs_sim3());   // an error exit frees whatever the handle holds by then
     if (!s) return fail(FS_ERR_OOM, "host allocation failed");
-    s->st = *st; s->n = st->particle_count; s->device = device; s->math_mode = math_mode;
+    s->st = *st; s->n = s->cap = st->particle_count; s->device = device; s->math_mode = math_mode;
     s->gw = (uint32_t)gw; s->gh = (uint32_t)gh; s->gd = (uint32_t)gd;
     s->ncell = s->gw * s->gh * s->gd;
     s->work_cap = s->ncell / 16u + 1024u;

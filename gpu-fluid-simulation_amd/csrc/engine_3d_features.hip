@@ -25,7 +25,7 @@ fs_status collider3_read(fs_sim3* s, fs_vec3* dst) { return fsd::download_vec3(s
 fs_status track3_copy(fs_sim3* s, int channel, bool attr, void* host, size_t n, bool upload) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
     FS_HIP(hipSetDevice(s->device));
-    FS_TRY(s->trk.copy(s->stream, s->n, s->n, channel, attr, host, n, upload));
+    FS_TRY(s->trk.copy(s->stream, s->n, s->cap, channel, attr, host, n, upload));
     return upload ? FS_OK : sort_health3(s);
 }
 }  // namespace
@@ -112,7 +112,7 @@ fs_status fs3_set_surface_tension(fs_sim3* s, int enable, float coefficient, flo
     if (std::isnan(threshold)) return fail(FS_ERR_INVALID, "surface tension: threshold is NaN");
     if (!s->tension.st.p) {
         FS_HIP(hipSetDevice(s->device));
-        if (s->tension.st.alloc(s->n) != hipSuccess) {
+        if (s->tension.st.alloc(s->cap) != hipSuccess) {
             (void)hipGetLastError();
             s->tension.st.release();
             return fail(FS_ERR_OOM, "surface tension: device array");
@@ -146,7 +146,9 @@ fs_status fs3_download_surface_tension(fs_sim3* s, fs_vec3* dst, size_t n) {
 fs_status fs3_track_enable(fs_sim3* s, int channels) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
     FS_HIP(hipSetDevice(s->device));
-    return s->trk.enable(s->stream, s->n, s->n, channels);
+    FS_TRY(s->trk.enable(s->stream, s->n, s->cap, channels));
+    s->next_id = s->n;              // the ids in use are 0 .. n - 1: emission goes on from there
+    return FS_OK;
 }
 
 fs_status fs3_track_disable(fs_sim3* s) {
@@ -164,12 +166,12 @@ fs_status fs3_track_upload_attr(fs_sim3* s, int channel, const float* src, size_
 
 fs_status fs3_track_ids_device(fs_sim3* s, const uint32_t** out) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
-    return s->trk.device_ptr(s->n, 0, false, (const void**)out);
+    return s->trk.device_ptr(s->cap, 0, false, (const void**)out);
 }
 
 fs_status fs3_track_attr_device(fs_sim3* s, int channel, const float** out) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
-    return s->trk.device_ptr(s->n, channel, true, (const void**)out);
+    return s->trk.device_ptr(s->cap, channel, true, (const void**)out);
 }
 
 /* Off the step path: two downloads and a scatter on the host, so entries of dst that no id names are never written. */

@@ -29,7 +29,7 @@ fs_status sample3_attr_enqueue(fs_sim3* s, const fs_vec3* points_dev, const fs3_
     Q.points = (const float*)points_dev;
     if (view) fsd::set_view3(&Q, *view);
     Q.channels = s->trk.channels;
-    Q.attr = s->trk.channel(0, s->n); Q.attr_stride = s->n;
+    Q.attr = s->trk.channel(0, s->cap); Q.attr_stride = s->cap;
     Q.weight_out = weight_dev; Q.attr_out = attr_dev;
     fsd::launch3_sample_attr(s->stream, params3_common(*s, s->mass), s->arrays(), Q);
     FS_HIP(hipGetLastError());

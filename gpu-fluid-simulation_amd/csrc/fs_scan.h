@@ -56,6 +56,30 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
     return v;
 }
 
+// Exclusive prefix of v over the workgroup's threads in thread order, and the workgroup's total.  Every thread calls it
+// (surface extraction, kernels_mesh3d.hip; the compaction of a removal, kernels_count3d.hip).
+template <int WAVES>
+__device__ __forceinline__ uint32_t block_scan3(uint32_t v, uint32_t* s_wave /*[WAVES]*/, uint32_t* total) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (uint32_t d = 1u; d < 64u; d <<= 1) {
+        const uint32_t t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    if (lane == 63u) s_wave[wave] = inc;
+    __syncthreads();
+    uint32_t base = 0u, tot = 0u;
+#pragma unroll
+    for (uint32_t w = 0u; w < (uint32_t)WAVES; ++w) {
+        const uint32_t t = s_wave[w];
+        if (w < wave) base += t;
+        tot += t;
+    }
+    *total = tot;
+    return base + inc - v;
+}
+
 __device__ __forceinline__ u64 lb_load(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void lb_store(u64* p, u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 

@@ -21,6 +21,7 @@
 //   k3_mesh_faces  the flags again, a workgroup scan -> the quad's rank; the four cells' ranks give six indices
 // Every output position is a prefix sum of flags in the statement's order: no atomics anywhere.
 #include "fs_field3.h"
+#include "fs_scan.h"      // block_scan3
 
 namespace fsd {
 
@@ -85,29 +86,6 @@ __device__ __forceinline__ uint32_t node_flags3(const Lattice3& L, const float* 
 
 // vertices in the low half, quads in the high half: a workgroup holds at most 256 and 768
 __device__ __forceinline__ uint32_t packed_counts3(uint32_t flags) { return (flags & 1u) | ((uint32_t)__popc((flags >> 1) & 7u) << 16); }
-
-// Exclusive prefix of v over the workgroup's threads in thread order, and the workgroup's total.  Every thread calls it.
-template <int WAVES>
-__device__ __forceinline__ uint32_t block_scan3(uint32_t v, uint32_t* s_wave /*[WAVES]*/, uint32_t* total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (uint32_t d = 1u; d < 64u; d <<= 1) {
-        const uint32_t t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63u) s_wave[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0u, tot = 0u;
-#pragma unroll
-    for (uint32_t w = 0u; w < (uint32_t)WAVES; ++w) {
-        const uint32_t t = s_wave[w];
-        if (w < wave) base += t;
-        tot += t;
-    }
-    *total = tot;
-    return base + inc - v;
-}
 
 __global__ __launch_bounds__(B3M) void k3_mesh_count(Lattice3 L, const float* __restrict__ field, uint2* __restrict__ sums) {
     __shared__ uint32_t s_wave[B3M / 64];

@@ -65,6 +65,19 @@ struct SortPolicy {
     }
     // the state was replaced from outside: an arbitrary order
     void touched() { trusted = 0; skip_seq = seq + 1; }
+    // The element count moved to another padded size (a 3D handle's emission or removal), the stream is idle and
+    // the caller has zeroed the plan words at their new place: an upload, and what the reports said about the stages of the old
+    // network says nothing about this one's.  The last report is consumed unlearnt — but for a barrier time-out, which latches
+    // as in plan() — and the next step starts at first_stage() of its own S again.
+    void resized() {
+        touched();
+        if (fb) {
+            const volatile uint32_t* f = fb;
+            if (f[4]) dead = true;
+            seen = f[0];
+        }
+        stage = 0; roomy = 0;
+    }
 
     // Wait until the step enqueued FLIGHT steps ago has finished (call before enqueueing a step) ...
     hipError_t throttle() {

@@ -263,6 +263,17 @@ public:
         check(fs3_download_surface_tension(h_, v.data(), v.size()));
         return v;
     }
+    // 3D particle count: `capacity` slots of which particle_count() are live.  reserve: grow-only, blocking, everything observable
+    // is preserved.  emit / emit_nozzle append behind the live particles (count + n <= capacity), the nozzle's layer of nu x nv
+    // records generated on the device.  remove_box (lo <= position <= hi on every axis) and remove (flags[i] != 0, one per
+    // particle in download order) are blocking and stable, and return how many particles went.
+    uint32_t capacity() const { return fs3_capacity(h_); }
+    void reserve(uint32_t capacity) { check(fs3_reserve(h_, capacity)); }
+    void emit(const std::vector<fs3_particle>& v) { check(fs3_emit_particles(h_, v.data(), v.size())); }
+    void emit_nozzle(const fs3_nozzle& nozzle) { check(fs3_emit_nozzle(h_, &nozzle)); }
+    uint32_t remove_box(fs_vec3 lo, fs_vec3 hi) { uint32_t n = 0; check(fs3_remove_in_box(h_, &lo, &hi, &n)); return n; }
+    uint32_t remove(const std::vector<uint8_t>& flags) { uint32_t n = 0; check(fs3_remove_flagged(h_, flags.data(), flags.size(), &n)); return n; }
+    uint32_t next_id() const { return fs3_track_next_id(h_); }      // of the next emitted particle while tracking is on; 0: off
     // 3D particle tracking: every particle gets an id (its current slot) and `channels` float attributes (all 0) that follow it
     // through the sort of every later tick.
     void track(int channels = 0) { check(fs3_track_enable(h_, channels)); }

@@ -115,6 +115,10 @@ pub struct Camera3 { pub eye: Vec3, pub forward: Vec3, pub right: Vec3, pub up: 
 /// fs3_surface_params: iso > 0, t_near >= 0, ds > 0, max_steps 1 ..= 4096, refine 0 ..= 24; 20 bytes.
 #[repr(C)] #[derive(Clone, Copy, Debug)]
 pub struct SurfaceParams3 { pub iso: f32, pub t_near: f32, pub ds: f32, pub max_steps: u32, pub refine: u32 }
+/// fs3_nozzle: a layer of `nu` x `nv` particles centred on `origin`, spaced by `u` and `v` (include/fluidsim.h "3D particle count"); 56 bytes.
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct Nozzle3 { pub origin: Vec3, pub u: Vec3, pub v: Vec3, pub velocity: Vec3, pub nu: u32, pub nv: u32 }
+const _: () = assert!(std::mem::size_of::<Nozzle3>() == 56);
 /// fs3_surface_hit: one pixel of the G-buffer; 40 bytes, offsets 0/4/8/20/32/36.  `hit` 0: miss, 1: bracketed and refined, 2: the first sample was inside.
 #[repr(C)] #[derive(Clone, Copy, Default, Debug, PartialEq)]
 pub struct SurfaceHit3 { pub t: f32, pub density: f32, pub normal: Vec3, pub velocity: Vec3, pub steps: u32, pub hit: u32 }
@@ -262,6 +266,13 @@ extern "C" {
     fn fs3_surface_tension_enabled(sim: *const fs_sim3) -> c_int;
     fn fs3_surface_tension_params(sim: *const fs_sim3, coefficient: *mut f32, threshold: *mut f32) -> c_int;
     fn fs3_download_surface_tension(sim: *mut fs_sim3, dst: *mut Vec3, n: usize) -> c_int;
+    fn fs3_reserve(sim: *mut fs_sim3, capacity: u32) -> c_int;
+    fn fs3_capacity(sim: *const fs_sim3) -> u32;
+    fn fs3_emit_particles(sim: *mut fs_sim3, src: *const Particle3, n: usize) -> c_int;
+    fn fs3_emit_nozzle(sim: *mut fs_sim3, nozzle: *const Nozzle3) -> c_int;
+    fn fs3_remove_in_box(sim: *mut fs_sim3, lo: *const Vec3, hi: *const Vec3, removed: *mut u32) -> c_int;
+    fn fs3_remove_flagged(sim: *mut fs_sim3, flags_host: *const u8, n: usize, removed: *mut u32) -> c_int;
+    fn fs3_track_next_id(sim: *const fs_sim3) -> u32;
     // ResizableBuffer<T> (src/buffer.rs)
     fn fs_buffer_create(device: c_int, elem_size: usize, len: usize, name: *const c_char, out: *mut *mut fs_buffer) -> c_int;
     fn fs_buffer_resize(buf: *mut fs_buffer, new_cap: usize, resized: *mut c_int) -> c_int;
@@ -697,6 +708,20 @@ impl FluidSimulation3D {
         let mut v = vec![Vec3::default(); self.particle_count() as usize];
         check(unsafe { fs3_download_surface_tension(self.raw, v.as_mut_ptr(), v.len()) }); v
     }
+    /// Build extension: 3D particle count (include/fluidsim.h).  `capacity` slots, of which `particle_count` are live.
+    pub fn capacity(&self) -> u32 { unsafe { fs3_capacity(self.raw) } }
+    /// Room for `capacity` particles: grow-only, blocking, everything observable is preserved.
+    pub fn reserve(&mut self, capacity: u32) { check(unsafe { fs3_reserve(self.raw, capacity) }); }
+    /// Appends `src` behind the live particles, all fields as given; `particle_count + src.len() <= capacity`.
+    pub fn emit(&mut self, src: &[Particle3]) { check(unsafe { fs3_emit_particles(self.raw, src.as_ptr(), src.len()) }); }
+    /// Appends a layer of `nu * nv` particles generated on the device.
+    pub fn emit_nozzle(&mut self, nozzle: &Nozzle3) { check(unsafe { fs3_emit_nozzle(self.raw, nozzle) }); }
+    /// Removes every particle with `lo <= position <= hi` on every axis (blocking, stable); returns how many went.
+    pub fn remove_box(&mut self, lo: Vec3, hi: Vec3) -> u32 { let mut n = 0u32; check(unsafe { fs3_remove_in_box(self.raw, &lo, &hi, &mut n) }); n }
+    /// Removes the particles whose flag (one per particle, `download_particles` order) is non-zero; returns how many went.
+    pub fn remove(&mut self, flags: &[u8]) -> u32 { let mut n = 0u32; check(unsafe { fs3_remove_flagged(self.raw, flags.as_ptr(), flags.len(), &mut n) }); n }
+    /// The id the next emitted particle gets while tracking is on (0 when it is off).
+    pub fn next_id(&self) -> u32 { unsafe { fs3_track_next_id(self.raw) } }
     /// Build extension: 3D particle tracking (include/fluidsim.h).  Every particle gets an id (its current slot) and `channels`
     /// f32 attributes (all 0.0) that follow it through the sort of every later step.
     pub fn track(&mut self, channels: u32) { check(unsafe { fs3_track_enable(self.raw, channels as c_int) }); }

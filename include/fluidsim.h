@@ -881,6 +881,59 @@ int fs3_surface_tension_enabled(const fs_sim3* sim);
 fs_status fs3_surface_tension_params(const fs_sim3* sim, float* coefficient, float* threshold);
 fs_status fs3_download_surface_tension(fs_sim3* sim, fs_vec3* dst, size_t n);
 
+/* ------------------------------------------------ 3D particle count (build extension, opt-in by being called) */
+/* A particle count that changes at run time: a tap, an outflow, a count that is no cube.  A handle has `capacity` slots and a
+ * live count <= capacity; after fs3_create both are settings.particle_count.  fs3_particle_count returns the live count, and
+ * every step, transfer and query works on exactly that many particles.  The live count is always known to the host: emission
+ * has a size the caller gives, removal is a blocking call that returns how many particles went.  The step's passes are
+ * unchanged, and a handle that never calls these functions launches exactly the kernels it launched before, with the same
+ * arguments.  FS_ABI_VERSION is unchanged.  See DESIGN.md §21.
+ *
+ * fs3_reserve: grow-only and blocking.  capacity <= fs3_capacity is FS_OK and does nothing; capacity > 2^28 is FS_ERR_INVALID.
+ * Every per-slot array gets `capacity` slots; the records, the tick, ids and channels, the last step's surface-tension forces,
+ * the collider and the validity of the queries are preserved bit for bit.  Everything new is allocated before anything old is
+ * released: on FS_ERR_OOM the handle is exactly what it was.  Device pointers handed out by fs3_track_*_device die.
+ *
+ * fs3_emit_particles: appends n host records at slots [count, count + n), stored as fs3_upload_particles stores them, all
+ * fields as given; ordered on fs3_stream after the steps in flight, and back only when `src` has been read.  In this order: a NULL
+ * handle is FS_ERR_INVALID; n == 0 is FS_OK and touches nothing; a NULL src is FS_ERR_INVALID; count + n > capacity is
+ * FS_ERR_INVALID and changes nothing.
+ *
+ * fs3_emit_nozzle: the same append of M = nu * nv records generated on the device, no host array and no transfer.  For q in
+ * [0, M), in f32 without contraction:
+ *     a = q % nu;  b = q / nu;  sa = ((float)a + 0.5f) - 0.5f * (float)nu;  sb = ((float)b + 0.5f) - 0.5f * (float)nv
+ *     position.c = (origin.c + sa * u.c) + sb * v.c;  predicted_position = position;  velocity = nozzle.velocity
+ *     density = +0;  grid = 0;  stored at slot count + q
+ * Positions outside the box are legal: the step's clamps deal with them as with an upload.  FS_ERR_INVALID, in this order: a
+ * NULL handle or nozzle; nu == 0, nv == 0 or nu * nv > 2^28; any of the 12 floats not finite; count + M > capacity (nothing
+ * changes).  Enqueued on fs3_stream; it waits for the steps in flight only when the count crosses a power of two.
+ *
+ * fs3_remove_in_box / fs3_remove_flagged: blocking.  Slot i goes when lo.a <= position.a && position.a <= hi.a on every axis
+ * (inclusive edges; a NaN coordinate is never removed; the test runs on the device), or when flags_host[i] != 0, where n must
+ * equal the count (else FS_ERR_INVALID).  The survivors keep their relative order; position, predicted position and density,
+ * velocity, key and, with tracking on, ids and every channel move as bit copies.  *removed receives the number removed.  Fewer
+ * than 2 survivors: FS_ERR_INVALID, *removed = 0, nothing changes.  Nothing matches: FS_OK, *removed = 0, nothing changes at
+ * all (the queries stay valid).  NULL arguments are FS_ERR_INVALID.
+ *
+ * After any call that changed the count: the queries (fs3_sample_*, fs3_sample_attr_*, fs3_render_surface*,
+ * fs3_extract_surface*) return FS_ERR_INVALID until the next step, fs3_download_surface_tension until the next step with the
+ * pass on, and pointers from fs3_track_*_device are dead.  fs3_upload_particles still clamps to the live count and never grows it.
+ *
+ * Tracking: fs3_track_enable sets next_id to the live count at the call; every particle emitted while tracking is on gets
+ * id = next_id++ in emission order (wrapping u32) and +0.0f in every channel; fs3_track_upload_ids does not touch next_id;
+ * removal compacts ids and channels with the records.  fs3_track_next_id: next_id, or 0 when tracking is off. */
+fs_status fs3_reserve(fs_sim3* sim, uint32_t capacity);
+uint32_t fs3_capacity(const fs_sim3* sim);
+fs_status fs3_emit_particles(fs_sim3* sim, const fs3_particle* src, size_t n);
+typedef struct fs3_nozzle {       /* 56 bytes */
+    fs_vec3 origin, u, v, velocity;
+    uint32_t nu, nv;
+} fs3_nozzle;
+fs_status fs3_emit_nozzle(fs_sim3* sim, const fs3_nozzle* nozzle);
+fs_status fs3_remove_in_box(fs_sim3* sim, const fs_vec3* lo, const fs_vec3* hi, uint32_t* removed);
+fs_status fs3_remove_flagged(fs_sim3* sim, const uint8_t* flags_host, size_t n, uint32_t* removed);
+uint32_t fs3_track_next_id(const fs_sim3* sim);
+
 /* ------------------------------------------------------- ResizableBuffer */
 /* ResizableBuffer<T>::new (src/buffer.rs:27-43). */
 fs_status fs_buffer_create(int device, size_t elem_size, size_t len, const char* name, fs_buffer** out);

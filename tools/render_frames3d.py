@@ -1,6 +1,9 @@
 """Render a few frames of the 3D dam break to PNG through the ray-marched G-buffer, headless:
   python tools/render_frames3d.py [n] [frame,frame,...] [outdir] [width] [height] [--box x0,y0,z0,x1,y1,z1[,voxels]]
-                                  [--surface-tension SIGMA[,TAU]] [--dye]
+                                  [--surface-tension SIGMA[,TAU]] [--dye] [--faucet K[,NU,NV]]
+--faucet: a particle count that grows: the handle reserves room for twice its particles and a nozzle under the
+ceiling, above the dry half of the tank, emits a layer of NU x NV particles (default 16 x 16, one spacing apart, falling at 3 m/s)
+every K steps until the capacity is reached.  With --box the jet fills a tank that has an obstacle in it.
 --dye: particle tracking with one channel: the particles of the -x half of the initial block carry 1.0, the others
 0.0; the shaded surface is tinted red by the Shepard value of the channel at the hit points (sampled there with sample_attr).
 --surface-tension: the opt-in colour-field surface tension with coefficient SIGMA and threshold TAU (default 1.0).
@@ -19,6 +22,12 @@ tension = None
 if "--surface-tension" in sys.argv:
     k = sys.argv.index("--surface-tension")
     tension = [float(x) for x in sys.argv[k + 1].split(",")]
+    del sys.argv[k:k + 2]
+faucet = None
+if "--faucet" in sys.argv:
+    k = sys.argv.index("--faucet")
+    faucet = [int(x) for x in sys.argv[k + 1].split(",")]
+    faucet = (faucet + [16, 16])[:3] if len(faucet) == 1 else faucet
     del sys.argv[k:k + 2]
 dye = "--dye" in sys.argv
 if dye:
@@ -48,10 +57,19 @@ if dye:
 eye = (-0.15 * sx, -0.55 * sy, -0.5 * sz - 0.9 * sx)
 cam = g.look_at_camera(eye, (0.0, 0.15 * sy, 0.0), (0.0, -1.0, 0.0), np.radians(42.0), width, height)
 h = st.smoothing_radius
+if faucet is not None:
+    sim.reserve(2 * n)
+    sp = st.particle_spacing
+    nozzle = dict(origin=(0.25 * sx, -0.5 * sy + 2 * h, 0.0), u=(sp, 0.0, 0.0), v=(0.0, 0.0, sp), velocity=(0.0, 3.0, 0.0),
+                  nu=faucet[1], nv=faucet[2])
 done = 0
 for f in frames:
     while done < f:
+        if faucet is not None and done % faucet[0] == 0 and sim.particle_count + faucet[1] * faucet[2] <= sim.capacity:
+            sim.emit_nozzle(**nozzle)
         sim.tick(tick); done += 1
+    if faucet is not None:
+        print("frame", f, "particles", sim.particle_count, "of", sim.capacity, flush=True)
     iso = 0.5 * float(np.median(sim.download_particles()["density"]))
     reach = 1.2 * (abs(eye[2]) + 0.5 * sz) + sx
     hits = sim.render_surface(cam, g.SurfaceParams3(iso, 0.0, 0.5 * h, min(4096, int(reach / (0.5 * h)) + 1), 8))
