@@ -1,0 +1,207 @@
+"""What the handles of the C ABI share: the status check, the marshalling helpers, the life cycle of a handle, the calls that
+exist under both the `fs_` and the `fs3_` prefix, and the two features (tracking, surface-tension read-outs) that are the same
+for 2D and 3D once the prefix, the record dtype and the vector width come from the class."""
+import ctypes as C
+
+import numpy as np
+
+from . import _abi
+from ._abi import PASS_NAMES, Vec2, Vec3, load_library
+
+
+class FluidSimError(RuntimeError):
+    def __init__(self, status, message):
+        super().__init__(f"fluidsim status {status}: {message}")
+        self.status = status
+
+
+def _check(lib, status):
+    if status != _abi.FS_OK:
+        raise FluidSimError(status, lib.fs_last_error().decode("utf-8", "replace"))
+
+
+def _ptr(arr):
+    """The data of a numpy array as a c_void_p."""
+    return arr.ctypes.data_as(C.c_void_p)
+
+
+def _vec2(a):
+    return Vec2(float(a[0]), float(a[1]))
+
+
+def _vec3(a):
+    return Vec3(*[float(x) for x in a])
+
+
+def _normalise_samples(out, attr):
+    """Shepard normalisation in place: velocity and channel sums divided by the weight, where that is non-zero."""
+    w = out["weight"]
+    ok = w != 0
+    out["velocity"][ok] /= w[ok, None]
+    if attr is not None:
+        attr[:, ok] /= w[ok]
+
+
+class _Handle:
+    """Owner of one handle of the library.  `_prefix` selects the family of calls; `_destroy` is the full name of the call
+    that frees the handle, written out per class because it does not follow from the prefix (a slab is made by
+    fs_slab_create and freed by fs_destroy)."""
+    _prefix = "fs_"
+    _destroy = None
+
+    def __init__(self):
+        self._lib = load_library()
+        self._h = C.c_void_p()
+
+    def _fn(self, stem):
+        return getattr(self._lib, self._prefix + stem)
+
+    def _call(self, stem, *args):
+        """`prefix + stem` on this handle; its status is checked."""
+        _check(self._lib, self._fn(stem)(self._h, *args))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class _Engine(_Handle):
+    """A handle that steps on a stream of its own: both simulations and the slab."""
+
+    def sync(self):
+        self._call("sync")
+
+    @property
+    def tick_count(self):
+        return int(self._fn("tick_count")(self._h))
+
+    @property
+    def stream_ptr(self):
+        """The HIP stream the steps (and the *_device calls) are enqueued on, as an integer (torch.cuda.ExternalStream)."""
+        return self._fn("stream")(self._h)
+
+    def profile(self, enable=True):
+        self._call("profile_enable", 1 if enable else 0)
+
+    def profile_read(self, reset=True):
+        ms = (C.c_double * len(PASS_NAMES))()
+        steps = C.c_uint64()
+        self._call("profile_read", ms, C.byref(steps), 1 if reset else 0)
+        return dict(zip(PASS_NAMES, [float(x) for x in ms])), int(steps.value)
+
+
+class _Simulation(_Engine):
+    """A whole simulation on one device: its records are `_record`, its vectors have `_dim` components."""
+    _record = None
+    _dim = None
+
+    def tick(self, tick_settings):
+        self._call("step", C.byref(tick_settings))
+
+    def timed_steps(self, tick_settings, steps):
+        ms = C.c_double()
+        self._call("timed_steps", C.byref(tick_settings), int(steps), C.byref(ms))
+        return float(ms.value)
+
+    @property
+    def particle_count(self):
+        return int(self._fn("particle_count")(self._h))
+
+    def download_particles(self):
+        out = np.empty(self.particle_count, dtype=self._record)
+        self._call("download_particles", _ptr(out), out.shape[0])
+        return out
+
+    def upload_particles(self, arr):
+        arr = np.ascontiguousarray(arr, dtype=self._record)
+        self._call("upload_particles", _ptr(arr), arr.shape[0])
+
+
+class _SurfaceTension:
+    """The read-outs of the opt-in surface tension; set_surface_tension differs and stays per class."""
+
+    @property
+    def surface_tension_enabled(self):
+        return bool(self._fn("surface_tension_enabled")(self._h))
+
+    def surface_tension_forces(self):
+        """The last step's surface-tension force per particle, (N, 2) float32 for the 2D simulation and (N, 3) for the 3D one,
+        in download_particles() order."""
+        out = np.empty((self.particle_count, self._dim), dtype=np.float32)
+        self._call("download_surface_tension", _ptr(out), out.shape[0])
+        return out
+
+
+class _Tracking:
+    """Opt-in particle tracking (build extension; DESIGN.md §12, 3D: §20)."""
+
+    def track(self, channels=0):
+        """Give every particle an id (= its current slot) and `channels` float attributes (all 0) that follow it through the
+        sort of every later step.  Calling it again re-initialises."""
+        self._call("track_enable", int(channels))
+
+    def untrack(self):
+        self._call("track_disable")
+
+    @property
+    def track_channels(self):
+        """-1 when tracking is off, else the number of attribute channels."""
+        return int(self._fn("track_channels")(self._h))
+
+    def particle_ids(self):
+        """uint32 id of the particle in every slot, in download_particles() order."""
+        out = np.empty(self.particle_count, dtype=np.uint32)
+        self._call("track_download_ids", _ptr(out), out.shape[0])
+        return out
+
+    def set_particle_ids(self, ids):
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        self._call("track_upload_ids", _ptr(ids), ids.shape[0])
+
+    def attribute(self, channel):
+        """float32 attribute `channel` of the particle in every slot, in download_particles() order."""
+        out = np.empty(self.particle_count, dtype=np.float32)
+        self._call("track_download_attr", int(channel), _ptr(out), out.shape[0])
+        return out
+
+    def set_attribute(self, channel, values):
+        """`values` is copied bit for bit when it already is float32 (NaN payloads survive)."""
+        values = np.ascontiguousarray(values, dtype=np.float32)
+        self._call("track_upload_attr", int(channel), _ptr(values), values.shape[0])
+
+    def download_particles_by_id(self):
+        """The records in id order: out[id] is the particle with that id (ids >= particle_count are skipped; entries that no
+        id names stay zero)."""
+        out = np.zeros(self.particle_count, dtype=self._record)
+        self._call("download_particles_by_id", _ptr(out), out.shape[0])
+        return out
+
+    def particle_ids_device_ptr(self):
+        p = C.c_void_p()
+        self._call("track_ids_device", C.byref(p))
+        return p.value
+
+    def attribute_device_ptr(self, channel):
+        p = C.c_void_p()
+        self._call("track_attr_device", int(channel), C.byref(p))
+        return p.value
+
+    def _sample_attr(self, n):
+        """The zeroed (channels, n) array that a sampling call fills with the channel sums."""
+        ch = self.track_channels
+        if ch <= 0:
+            raise FluidSimError(_abi.FS_ERR_INVALID, "sample(attributes=True) needs track(channels >= 1)")
+        return np.zeros((ch, n), dtype=np.float32)

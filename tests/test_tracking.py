@@ -4,13 +4,11 @@ calls refuse a NULL handle without touching a device.  Last, the registry of the
 (tests/hard_states2d.py) on the checker alone: every case moves most slots, the tie cases have ties the two sorts arrange
 differently.  No GPU."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TRACK_CALLS = ("fs_track_enable", "fs_track_disable", "fs_track_channels", "fs_track_download_ids", "fs_track_upload_ids",
                "fs_track_download_attr", "fs_track_upload_attr", "fs_track_ids_device", "fs_track_attr_device",
                "fs_download_particles_by_id")
@@ -71,33 +69,12 @@ def test_reset_restarts_the_ids_at_the_current_slots(fs, orc):
     assert np.array_equal(chk.ids, perm)
 
 
-def _strip_c_comments(s):
-    s = re.sub(r"/\*.*?\*/", " ", s, flags=re.S)
-    return re.sub(r"//[^\n]*", " ", s)
-
-
 def test_every_layer_names_every_tracking_call(fs):
-    header = _strip_c_comments(open(os.path.join(ROOT, "include", "fluidsim.h")).read())
-    pkg = os.path.join(ROOT, "gpu-fluid-simulation_amd")
-    rust = _strip_c_comments(open(os.path.join(pkg, "rust", "src", "lib.rs")).read())
-    rust_extern = re.search(r'extern\s+"C"\s*\{(.*?)\n\}', rust, flags=re.S).group(1)
-    rust_rest = rust.replace(rust_extern, "")
-    cpp = _strip_c_comments(open(os.path.join(pkg, "host", "fluid_simulation.hpp")).read())
-    py = open(os.path.join(pkg, "__init__.py")).read()
-    lib = fs.load_library()
-    for name in TRACK_CALLS:
-        assert re.search(rf"\b{name}\s*\(", header), f"{name} not declared in include/fluidsim.h"
-        assert name in fs._abi.PROTOTYPES, f"{name} has no ctypes prototype"
-        assert hasattr(lib, name), f"{name} not exported by the library"
-        assert re.search(rf"\bfn\s+{name}\s*\(", rust_extern), f"{name} not in the Rust extern block"
-        assert re.search(rf"\b{name}\s*\(", rust_rest), f"{name} bound but never called by the Rust wrapper"
-        assert re.search(rf"\b{name}\s*\(", cpp), f"{name} not used by the C++ mirror"
-        assert re.search(rf"\.{name}\s*\(", py), f"{name} not used by the Python wrapper"
-    assert re.search(r"#define\s+FS_TRACK_MAX_CHANNELS\s+4\b", header)
-    for method in ("track", "untrack", "track_channels", "particle_ids", "set_particle_ids", "attribute", "set_attribute",
-                   "download_particles_by_id", "particle_ids_device_ptr", "attribute_device_ptr"):
-        assert hasattr(fs.FluidSimulation, method), f"FluidSimulation.{method} missing"
-    assert lib.fs_abi_version() == 2
+    from tests.layers import assert_every_layer_names, header_text
+    assert_every_layer_names(fs, TRACK_CALLS, fs.FluidSimulation, (
+        "track", "untrack", "track_channels", "particle_ids", "set_particle_ids", "attribute", "set_attribute",
+        "download_particles_by_id", "particle_ids_device_ptr", "attribute_device_ptr"))
+    assert re.search(r"#define\s+FS_TRACK_MAX_CHANNELS\s+4\b", header_text())
 
 
 def test_null_handle_is_invalid_without_a_device(fs):

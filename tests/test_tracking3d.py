@@ -3,13 +3,10 @@ tests/track3d_ref.py is sound (the permutation it derives is the one the 3D orac
 tests/sample_attr3d_ref.py is tied to the pinned 3D sampler by the two identities of the header, every host binding names every
 new call, and the calls refuse a NULL handle without touching a device.  No GPU."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TRACK3_CALLS = ("fs3_track_enable", "fs3_track_disable", "fs3_track_channels", "fs3_track_download_ids", "fs3_track_upload_ids",
                 "fs3_track_download_attr", "fs3_track_upload_attr", "fs3_track_ids_device", "fs3_track_attr_device",
                 "fs3_download_particles_by_id", "fs3_sample_attr_points", "fs3_sample_attr_points_device", "fs3_sample_attr_grid")
@@ -127,32 +124,11 @@ def test_restatement_against_a_float64_sum(fs, orc):
 
 
 # ---- layers and NULL handles ----------------------------------------------------------------------------------------------
-def _strip_c_comments(s):
-    s = re.sub(r"/\*.*?\*/", " ", s, flags=re.S)
-    return re.sub(r"//[^\n]*", " ", s)
-
-
 def test_every_layer_names_every_3d_tracking_call(fs):
-    header = _strip_c_comments(open(os.path.join(ROOT, "include", "fluidsim.h")).read())
-    pkg = os.path.join(ROOT, "gpu-fluid-simulation_amd")
-    rust = _strip_c_comments(open(os.path.join(pkg, "rust", "src", "lib.rs")).read())
-    rust_extern = re.search(r'extern\s+"C"\s*\{(.*?)\n\}', rust, flags=re.S).group(1)
-    rust_rest = rust.replace(rust_extern, "")
-    cpp = _strip_c_comments(open(os.path.join(pkg, "host", "fluid_simulation.hpp")).read())
-    py = open(os.path.join(pkg, "__init__.py")).read()
-    lib = fs.load_library()
-    for name in TRACK3_CALLS:
-        assert re.search(rf"\b{name}\s*\(", header), f"{name} not declared in include/fluidsim.h"
-        assert name in fs._abi.PROTOTYPES, f"{name} has no ctypes prototype"
-        assert hasattr(lib, name), f"{name} not exported by the library"
-        assert re.search(rf"\bfn\s+{name}\s*\(", rust_extern), f"{name} not in the Rust extern block"
-        assert re.search(rf"\b{name}\s*\(", rust_rest), f"{name} bound but never called by the Rust wrapper"
-        assert re.search(rf"\b{name}\s*\(", cpp), f"{name} not used by the C++ mirror"
-        assert re.search(rf"\.{name}\s*\(", py), f"{name} not used by the Python wrapper"
-    for method in ("track", "untrack", "track_channels", "particle_ids", "set_particle_ids", "attribute", "set_attribute",
-                   "download_particles_by_id", "particle_ids_device_ptr", "attribute_device_ptr", "sample_attr_device"):
-        assert hasattr(fs.FluidSimulation3D, method), f"FluidSimulation3D.{method} missing"
-    assert lib.fs_abi_version() == 2
+    from tests.layers import assert_every_layer_names
+    assert_every_layer_names(fs, TRACK3_CALLS, fs.FluidSimulation3D, (
+        "track", "untrack", "track_channels", "particle_ids", "set_particle_ids", "attribute", "set_attribute",
+        "download_particles_by_id", "particle_ids_device_ptr", "attribute_device_ptr", "sample_attr_device"))
 
 
 def test_null_handle_is_invalid_without_a_device(fs):
