@@ -32,6 +32,7 @@ from ._abi import (  # noqa: F401
     SURFACE_HIT_DTYPE,
     Camera3,
     ExtensionMissing,
+    Nozzle,
     Nozzle3,
     Options,
     Settings,

@@ -152,6 +152,11 @@ class SurfaceParams3(C.Structure):
     _fields_ = [("iso", C.c_float), ("t_near", C.c_float), ("ds", C.c_float), ("max_steps", C.c_uint32), ("refine", C.c_uint32)]
 
 
+class Nozzle(C.Structure):
+    """fs_nozzle (include/fluidsim.h "2D particle count"): 40 bytes."""
+    _fields_ = [("origin", Vec2), ("u", Vec2), ("v", Vec2), ("velocity", Vec2), ("nu", C.c_uint32), ("nv", C.c_uint32)]
+
+
 class Nozzle3(C.Structure):
     """fs3_nozzle (include/fluidsim.h "3D particle count"): 56 bytes."""
     _fields_ = [("origin", Vec3), ("u", Vec3), ("v", Vec3), ("velocity", Vec3), ("nu", C.c_uint32), ("nv", C.c_uint32)]
@@ -286,6 +291,13 @@ PROTOTYPES = {
     "fs_sample_points": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
     "fs_sample_points_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
     "fs_sample_grid": (C.c_int, [_P, C.POINTER(View), _P, _P]),
+    "fs_reserve": (C.c_int, [_P, C.c_uint32]),
+    "fs_capacity": (C.c_uint32, [_P]),
+    "fs_emit_particles": (C.c_int, [_P, _P, C.c_size_t]),
+    "fs_emit_nozzle": (C.c_int, [_P, C.POINTER(Nozzle)]),
+    "fs_remove_in_box": (C.c_int, [_P, C.POINTER(Vec2), C.POINTER(Vec2), C.POINTER(C.c_uint32)]),
+    "fs_remove_flagged": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "fs_track_next_id": (C.c_uint32, [_P]),
     "fs_export_handle": (C.c_int, [_P, C.c_int, _P]),
     "fs_import_open": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "fs_import_read": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t]),

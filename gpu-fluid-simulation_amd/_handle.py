@@ -1,6 +1,6 @@
 """What the handles of the C ABI share: the status check, the marshalling helpers, the life cycle of a handle, the calls that
-exist under both the `fs_` and the `fs3_` prefix, and the two features (tracking, surface-tension read-outs) that are the same
-for 2D and 3D once the prefix, the record dtype and the vector width come from the class."""
+exist under both the `fs_` and the `fs3_` prefix, and the features (tracking, surface-tension read-outs, a particle count that
+changes at run time) that are the same for 2D and 3D once the prefix, the record dtype and the vector width come from the class."""
 import ctypes as C
 
 import numpy as np
@@ -143,6 +143,55 @@ class _SurfaceTension:
         out = np.empty((self.particle_count, self._dim), dtype=np.float32)
         self._call("download_surface_tension", _ptr(out), out.shape[0])
         return out
+
+
+class _Count:
+    """A particle count that changes at run time (build extension; DESIGN.md §22, 3D: §21).  `_nozzle` is the class's nozzle
+    structure (fs_nozzle / fs3_nozzle); vectors have `_dim` components."""
+    _nozzle = None
+
+    def _vec(self, a):
+        return _vec2(a) if self._dim == 2 else _vec3(a)
+
+    @property
+    def capacity(self):
+        """Slots of the handle: particle_count can grow to this (reserve() raises it)."""
+        return int(self._fn("capacity")(self._h))
+
+    def reserve(self, capacity):
+        """Room for `capacity` particles (grow-only, blocking); the state and everything observable are preserved."""
+        self._call("reserve", int(capacity))
+
+    def emit(self, records):
+        """Append records (the class's particle dtype) behind the live particles, all fields as given;
+        particle_count + len <= capacity."""
+        arr = np.ascontiguousarray(records, dtype=self._record)
+        self._call("emit_particles", _ptr(arr), arr.shape[0])
+
+    def emit_nozzle(self, origin, u, v, velocity, nu, nv=1):
+        """Append nu x nv particles generated on the device: centred on `origin`, spaced by the vectors u and v, all with
+        `velocity` (include/fluidsim.h "2D particle count" / "3D particle count").  nv == 1 is a line."""
+        z = self._nozzle(self._vec(origin), self._vec(u), self._vec(v), self._vec(velocity), int(nu), int(nv))
+        self._call("emit_nozzle", C.byref(z))
+
+    def remove_box(self, lo, hi):
+        """Remove every particle with lo <= position <= hi on every axis (blocking, stable); returns how many went."""
+        a, b, n = self._vec(lo), self._vec(hi), C.c_uint32()
+        self._call("remove_in_box", C.byref(a), C.byref(b), C.byref(n))
+        return int(n.value)
+
+    def remove(self, flags):
+        """Remove the particles whose entry of `flags` (one per particle, download_particles() order) is non-zero (blocking,
+        stable); returns how many went."""
+        f = np.ascontiguousarray(np.asarray(flags) != 0, dtype=np.uint8)
+        n = C.c_uint32()
+        self._call("remove_flagged", _ptr(f), f.shape[0], C.byref(n))
+        return int(n.value)
+
+    @property
+    def next_id(self):
+        """The id the next emitted particle gets while tracking is on (0 when it is off)."""
+        return int(self._fn("track_next_id")(self._h))
 
 
 class _Tracking:

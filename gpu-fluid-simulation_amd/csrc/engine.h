@@ -2,8 +2,8 @@
 // features, the step parameters, and the device check and create-time proofs (also used by the 3D handle's files through
 // engine_3d.h).  The handle's files:
 // engine.hip (life cycle, step, transfers, renderer hand-off), engine_features.hip (surface tension, particle tracking),
-// engine_query.hip (density render, field sampling), engine_selftest.hip (self-tests, read-outs), engine_slab.hip (the
-// multi-GPU slab handles).  Internal: include/fluidsim.h is the interface.
+// engine_query.hip (density render, field sampling), engine_count.hip (a particle count that changes at run time),
+// engine_selftest.hip (self-tests, read-outs), engine_slab.hip (the multi-GPU slab handles).  Internal: include/fluidsim.h is the interface.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -182,7 +182,24 @@ struct Tracking {
     }
 };
 
-// Everything only a slab (multi-GPU) handle has: engine_slab.hip.  Torn down like the handle itself, in reverse order of
+// A particle count that changes at run time (build extension; single-domain handles): fs_reserve, fs_emit_*,
+// fs_remove_* in engine_count.hip.  What the handle keeps for it: the id of the next emitted particle and the scratch of a
+// removal, allocated by the first one for `capacity` slots and released by fs_reserve.  Never called: no allocation, no launch.
+struct CountChange {
+    uint32_t next_id = 0;           // while tracking is on: the live count at fs_track_enable, then + 1 per emitted particle (wrapping)
+    DevArray<uint8_t> flags;        // per slot: removed
+    DevArray<uint32_t> sums;        // per workgroup of the flags pass: survivors, then offsets; the total behind them
+    fs_status reserve(uint32_t capacity) {
+        if (flags.p) return FS_OK;
+        if (flags.alloc(capacity) == hipSuccess && sums.alloc((size_t)remove_workgroups(capacity) + 1) == hipSuccess) return FS_OK;
+        (void)hipGetLastError();
+        release();
+        return fail(FS_ERR_OOM, "removal: device scratch");
+    }
+    void release() { flags.release(); sums.release(); }
+};
+
+// Everything only a slab (multi-GPU) handle has: engine_slab.hip. Torn down like the handle itself, in reverse order of
 // declaration: the device arrays, then the events, the exchange stream last.
 struct SlabState {
     Stream comm;                    // the exchange's stream (fs_slab_exchange, or the caller's transport between comm_begin / comm_end)
@@ -280,6 +297,7 @@ struct fs_sim : fsd::HandleQueues, fsd::ParticleArrays {
     uint32_t aos_tick = 0xFFFFFFFFu;   // tick whose state the AoS view holds (only meaningful with aos_live)
     fsd::SurfaceTension st;         // the opt-in features' state: one line each in enqueue_step
     fsd::Tracking trk;
+    fsd::CountChange count;         // (not a per-step feature: emission and removal happen between steps)
     // what walks the cell table off the step path (engine_query.hip: fs_render_density; field sampling): the records
     // and the cell table belong together — a step has been enqueued since create and since the last fs_upload_particles /
     // fs_upload_start_indices

@@ -316,7 +316,7 @@ static fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
     const bool counting = s->opts.sort_mode == FS_SORT_COUNTING;
     if (prof) FS_HIP(hipEventRecord(ev[1], st));
     if (counting) {
-        fsd::launch_counting_sort(st, P, s->pos.p, s->vel.p, s->cs.p, s->csort.p, s->counter.p, s->safe.p, s->tick);
+        fsd::launch_counting_sort(st, P, s->capacity, s->pos.p, s->vel.p, s->cs.p, s->csort.p, s->counter.p, s->safe.p, s->tick);
     } else {
         fsd::SortPlan plan;
         if (!s->sortp.plan(s->n, &plan)) return fail(FS_ERR_DEVICE, "sort: the stand-by kernel's grid barrier timed out");
@@ -329,7 +329,7 @@ static fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
     A.key_s = nullptr;
     if (pos_by_src) A.pos_s = nullptr;     // ... and so does the sorted copy of the positions
     if (counting)      // rank fix-up of the counting sort fused with the reorder pass (kernels_csort.hip)
-        fsd::launch_counting_reorder(st, P, A);
+        fsd::launch_counting_reorder(st, P, s->capacity, A);
     else
         fsd::launch_reorder(st, P, A, s->work_cap);
     s->trk.carry(st, s->n, s->pairs.p, s->capacity);     // particle tracking, if on (inside the FS_PASS_REORDER interval)

@@ -107,8 +107,27 @@ __global__ __launch_bounds__(B3C) void k3_remove_scatter(uint32_t n, const uint8
     }
 }
 
-// ------------------------------------------------------------------------------------ launchers (fs_3d.h)
-uint32_t remove3_workgroups(uint32_t n) { return (n + B3C - 1u) / B3C; }
+// ------------------------------------------------------------------------------------ launchers
+// The passes without a dimension in them serve the 2D handle as well (fs_kernels.h; its own passes: kernels_count.hip).
+uint32_t remove_workgroups(uint32_t n) { return (n + B3C - 1u) / B3C; }
+
+void launch_remove_offsets(hipStream_t st, uint32_t nwg, uint32_t* sums) {
+    hipLaunchKernelGGL(k3_remove_offsets, dim3(1), dim3(B3C_SCAN), 0, st, nwg, (nwg + B3C_SCAN - 1u) / B3C_SCAN, sums);
+}
+
+void launch_remove_count_flags(hipStream_t st, uint32_t n, const uint8_t* flags, uint32_t* sums) {
+    const uint32_t nwg = remove_workgroups(n);
+    hipLaunchKernelGGL(k3_remove_flags<false>, dim3(nwg), dim3(B3C), 0, st, n, (const float4*)nullptr, float3{}, float3{},
+                       const_cast<uint8_t*>(flags), sums);          // (BOX == false only reads them)
+    launch_remove_offsets(st, nwg, sums);
+}
+
+void launch_emit_track(hipStream_t st, uint32_t m, uint32_t first_id, uint32_t* ids, int channels, float* attr, uint32_t stride) {
+    hipLaunchKernelGGL(k3_emit_track, dim3((m + B3C - 1u) / B3C), dim3(B3C), 0, st, m, first_id, ids, channels, attr, stride);
+}
+
+// ---- the 3D handle's (fs_3d.h)
+uint32_t remove3_workgroups(uint32_t n) { return remove_workgroups(n); }
 
 void launch3_emit_nozzle(hipStream_t st, const Nozzle3& Z, uint32_t first_slot, const Arrays3& A) {
     const uint32_t m = Z.nu * Z.nv;                                 // <= 2^28: the host's check
@@ -117,19 +136,19 @@ void launch3_emit_nozzle(hipStream_t st, const Nozzle3& Z, uint32_t first_slot, 
 }
 
 void launch3_emit_track(hipStream_t st, uint32_t m, uint32_t first_id, uint32_t* ids, int channels, float* attr, uint32_t stride) {
-    hipLaunchKernelGGL(k3_emit_track, dim3((m + B3C - 1u) / B3C), dim3(B3C), 0, st, m, first_id, ids, channels, attr, stride);
+    launch_emit_track(st, m, first_id, ids, channels, attr, stride);
 }
 
 void launch3_remove_count(hipStream_t st, uint32_t n, const float4* pos, const float3* lo, const float3* hi, uint8_t* flags,
                           uint32_t* sums) {
-    const uint32_t nwg = remove3_workgroups(n);
-    if (lo) hipLaunchKernelGGL(k3_remove_flags<true>, dim3(nwg), dim3(B3C), 0, st, n, pos, *lo, *hi, flags, sums);
-    else hipLaunchKernelGGL(k3_remove_flags<false>, dim3(nwg), dim3(B3C), 0, st, n, pos, float3{}, float3{}, flags, sums);
-    hipLaunchKernelGGL(k3_remove_offsets, dim3(1), dim3(B3C_SCAN), 0, st, nwg, (nwg + B3C_SCAN - 1u) / B3C_SCAN, sums);
+    if (!lo) return launch_remove_count_flags(st, n, flags, sums);
+    const uint32_t nwg = remove_workgroups(n);
+    hipLaunchKernelGGL(k3_remove_flags<true>, dim3(nwg), dim3(B3C), 0, st, n, pos, *lo, *hi, flags, sums);
+    launch_remove_offsets(st, nwg, sums);
 }
 
 void launch3_remove_scatter(hipStream_t st, uint32_t n, const uint8_t* flags, const uint32_t* sums, const Compact3& C) {
-    hipLaunchKernelGGL(k3_remove_scatter, dim3(remove3_workgroups(n)), dim3(B3C), 0, st, n, flags, sums, C);
+    hipLaunchKernelGGL(k3_remove_scatter, dim3(remove_workgroups(n)), dim3(B3C), 0, st, n, flags, sums, C);
 }
 
 }  // namespace fsd

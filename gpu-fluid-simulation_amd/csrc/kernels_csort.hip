@@ -7,6 +7,7 @@
 // The pairs then feed the same density / force chain as the bitonic mode.
 #include <hip/hip_ext.h>
 
+#include "fs_csort_layout.h"
 #include "fs_device.h"
 #include "fs_kernels.h"
 #include "fs_scan.h"
@@ -267,25 +268,10 @@ __global__ __launch_bounds__(CS_BLOCK) void k_cs_fixreorder(StepParams P, uint32
     }
 }
 
-static inline size_t even(size_t w) { return (w + 1u) & ~(size_t)1u; }
-struct CsLayout { uint32_t *hist, *slot_src, *ticket; u64 *kt, *state; uint32_t scan_blocks; };
-static CsLayout cs_layout(uint32_t* scratch, uint32_t n, uint32_t ncell) {
-    // hist (ncell + 1) | kt (n x u64) | slot_src (n) | scan state (u64 per tile) | tickets
-    CsLayout L;
-    size_t o = 0;
-    L.hist = scratch; o = even((size_t)ncell + 1u);
-    L.kt = (u64*)(scratch + o); o += 2 * (size_t)n;
-    L.slot_src = scratch + o; o = even(o + n);
-    L.scan_blocks = (uint32_t)(((size_t)ncell + 1u + SCAN_TILE - 1) / SCAN_TILE);
-    L.state = (u64*)(scratch + o); o += 2 * (size_t)L.scan_blocks;
-    L.ticket = scratch + o;
-    return L;
-}
+// where everything lives in the scratch: fs_csort_layout.h (host arithmetic, also checked on the CPU)
+static_assert(SCAN_TILE == CS_SCAN_TILE, "fs_csort_layout.h counts the scan tiles of k_scan_lookback");
 // `ncell_max`: the largest table the handle will ever scan (slab handles move their window).
-size_t counting_sort_scratch_words(uint32_t n, uint32_t ncell_max) {
-    const size_t tiles = ((size_t)ncell_max + 1u + SCAN_TILE - 1) / SCAN_TILE;
-    return even((size_t)ncell_max + 1u) + 2 * (size_t)n + even(n) + 2 * tiles + 16;
-}
+size_t counting_sort_scratch_words(uint32_t n, uint32_t ncell_max) { return cs_scratch_words(n, ncell_max); }
 // which words of the scratch must be zero when a handle is created: the histogram and the ticket counters (all of it is simplest)
 u64* counting_sort_kt(uint32_t* scratch, uint32_t n, uint32_t ncell) { return cs_layout(scratch, n, ncell).kt; }
 uint32_t* counting_sort_hist(uint32_t* scratch) { return scratch; }
@@ -314,18 +300,20 @@ void launch_counting_reorder_slab(hipStream_t st, const StepParams& P, const Ste
                        A.n_dev);
 }
 
-void launch_counting_sort(hipStream_t st, const StepParams& P, const float2* pos, const float2* vel, uint32_t* cs,
+// `cap`: the slots the scratch was sized for (counting_sort_scratch_words).  The layout follows it, not the live count P.n: the
+// look-back words and the tickets keep their addresses across an emission or a removal.
+void launch_counting_sort(hipStream_t st, const StepParams& P, uint32_t cap, const float2* pos, const float2* vel, uint32_t* cs,
                           uint32_t* scratch, uint32_t* gap_counter, unsigned long long* safe, uint32_t epoch) {
     const uint32_t n = P.n, ncell = P.ncell, count = ncell + 1u;
-    const CsLayout L = cs_layout(scratch, n, ncell);
+    const CsLayout L = cs_layout(scratch, cap, ncell);
     const dim3 grid((n + CS_BLOCK - 1) / CS_BLOCK), block(CS_BLOCK);
     hipLaunchKernelGGL(k_cs_hist, grid, block, 0, st, P, pos, vel, L.kt, L.hist, gap_counter, safe);
     hipLaunchKernelGGL(k_scan_lookback, dim3((count + SCAN_TILE - 1) / SCAN_TILE), dim3(SCAN_BLOCK), 0, st, L.hist, count, cs, L.state, L.ticket,
                        epoch, (uint32_t*)nullptr);
     hipLaunchKernelGGL(k_cs_scatter, dim3((n + CS_BLOCK * SC_ITEMS - 1) / (CS_BLOCK * SC_ITEMS)), block, 0, st, n, ncell, L.kt, cs, L.slot_src, (const uint32_t*)nullptr, (unsigned long long*)nullptr);
 }
-void launch_counting_reorder(hipStream_t st, const StepParams& P, const StepArrays& A) {
-    const CsLayout L = cs_layout(A.csort, P.n, P.ncell);
+void launch_counting_reorder(hipStream_t st, const StepParams& P, uint32_t cap, const StepArrays& A) {
+    const CsLayout L = cs_layout(A.csort, cap, P.ncell);
     hipLaunchKernelGGL(k_cs_fixreorder<false>, dim3((P.n + CS_BLOCK - 1) / CS_BLOCK), dim3(CS_BLOCK), 0, st, P, P.n, L.kt, A.cs,
                        L.slot_src, A.pairs, A.pos, A.vel, A.pos_s, A.vel_s, A.pred, A.key_s, (unsigned char*)nullptr, A.start_ref, A.safe,
                        A.fdefer, A.fcount, (const uint32_t*)nullptr);

@@ -118,6 +118,18 @@ public:
     const float* attribute_device(int channel) { const float* p = nullptr; check(fs_track_attr_device(h_, channel, &p)); return p; }
     // dst[id] = the record of the particle with that id; entries that no id names are left as they are
     void download_by_id(std::vector<ParticleInstance>& dst) { check(fs_download_particles_by_id(h_, dst.data(), dst.size())); }
+    // 2D particle count: `capacity` slots of which particle_count() are live.  reserve: grow-only, blocking, everything observable
+    // is preserved; refused once a renderer hand-off is registered (size that handle with fs_options.capacity).  emit /
+    // emit_nozzle append behind the live particles (count + n <= capacity), the nozzle's nu x nv records generated on the
+    // device (nv == 1: a line).  remove_box (lo <= position <= hi on both axes) and remove (flags[i] != 0, one per particle)
+    // are blocking stable compactions and return how many particles went.
+    uint32_t capacity() const { return fs_capacity(h_); }
+    void reserve(uint32_t capacity) { check(fs_reserve(h_, capacity)); }
+    void emit(const std::vector<ParticleInstance>& v) { check(fs_emit_particles(h_, v.data(), v.size())); }
+    void emit_nozzle(const fs_nozzle& nozzle) { check(fs_emit_nozzle(h_, &nozzle)); }
+    uint32_t remove_box(fs_vec2 lo, fs_vec2 hi) { uint32_t n = 0; check(fs_remove_in_box(h_, &lo, &hi, &n)); return n; }
+    uint32_t remove(const std::vector<uint8_t>& flags) { uint32_t n = 0; check(fs_remove_flagged(h_, flags.data(), flags.size(), &n)); return n; }
+    uint32_t next_id() const { return fs_track_next_id(h_); }       // of the next emitted particle while tracking is on; 0: off
     // Build extension, NOT in the reference: field sampling (include/fluidsim.h), single-domain handles.  Density, Shepard weight,
     // un-normalised velocity sum, neighbour count and cell of the fluid at any points; `attr` (may be null) receives the channel
     // sums, channel c of query k at c * n + k.  Needs a tick since creation / the last upload.  Coherently ordered points are

@@ -115,6 +115,10 @@ pub struct Camera3 { pub eye: Vec3, pub forward: Vec3, pub right: Vec3, pub up: 
 /// fs3_surface_params: iso > 0, t_near >= 0, ds > 0, max_steps 1 ..= 4096, refine 0 ..= 24; 20 bytes.
 #[repr(C)] #[derive(Clone, Copy, Debug)]
 pub struct SurfaceParams3 { pub iso: f32, pub t_near: f32, pub ds: f32, pub max_steps: u32, pub refine: u32 }
+/// fs_nozzle: `nu` x `nv` particles centred on `origin`, spaced by `u` and `v` (include/fluidsim.h "2D particle count"); 40 bytes.
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct Nozzle { pub origin: Vec2, pub u: Vec2, pub v: Vec2, pub velocity: Vec2, pub nu: u32, pub nv: u32 }
+const _: () = assert!(std::mem::size_of::<Nozzle>() == 40);
 /// fs3_nozzle: a layer of `nu` x `nv` particles centred on `origin`, spaced by `u` and `v` (include/fluidsim.h "3D particle count"); 56 bytes.
 #[repr(C)] #[derive(Clone, Copy, Debug)]
 pub struct Nozzle3 { pub origin: Vec3, pub u: Vec3, pub v: Vec3, pub velocity: Vec3, pub nu: u32, pub nv: u32 }
@@ -175,6 +179,14 @@ extern "C" {
     fn fs_sample_points(sim: *mut fs_sim, points: *const Vec2, n: usize, out: *mut Sample, attr_out: *mut f32) -> c_int;
     fn fs_sample_points_device(sim: *mut fs_sim, points_dev: *const Vec2, n: usize, out_dev: *mut Sample, attr_out_dev: *mut f32) -> c_int;
     fn fs_sample_grid(sim: *mut fs_sim, view: *const View, out: *mut Sample, attr_out: *mut f32) -> c_int;
+    // 2D particle count
+    fn fs_reserve(sim: *mut fs_sim, capacity: u32) -> c_int;
+    fn fs_capacity(sim: *const fs_sim) -> u32;
+    fn fs_emit_particles(sim: *mut fs_sim, src: *const ParticleInstance, n: usize) -> c_int;
+    fn fs_emit_nozzle(sim: *mut fs_sim, nozzle: *const Nozzle) -> c_int;
+    fn fs_remove_in_box(sim: *mut fs_sim, lo: *const Vec2, hi: *const Vec2, removed: *mut u32) -> c_int;
+    fn fs_remove_flagged(sim: *mut fs_sim, flags_host: *const u8, n: usize, removed: *mut u32) -> c_int;
+    fn fs_track_next_id(sim: *const fs_sim) -> u32;
     // profiling
     fn fs_profile_enable(sim: *mut fs_sim, enable: c_int) -> c_int;
     fn fs_profile_read(sim: *mut fs_sim, ms: *mut f64, steps: *mut u64, reset: c_int) -> c_int;
@@ -408,6 +420,21 @@ impl FluidSimulation {
     pub fn download_particles_by_id(&mut self, dst: &mut [ParticleInstance]) {
         check(unsafe { fs_download_particles_by_id(self.raw, dst.as_mut_ptr(), dst.len()) });
     }
+    /// Build extension: 2D particle count (include/fluidsim.h).  `capacity` slots, of which `particle_count` are live.
+    pub fn capacity(&self) -> u32 { unsafe { fs_capacity(self.raw) } }
+    /// Room for `capacity` particles: grow-only, blocking, everything observable is preserved.  Refused on a handle with a
+    /// renderer hand-off registered: size that one with `Options::capacity` at create.
+    pub fn reserve(&mut self, capacity: u32) { check(unsafe { fs_reserve(self.raw, capacity) }); }
+    /// Appends `src` behind the live particles, all fields as given; `particle_count + src.len() <= capacity`.
+    pub fn emit(&mut self, src: &[ParticleInstance]) { check(unsafe { fs_emit_particles(self.raw, src.as_ptr(), src.len()) }); }
+    /// Appends `nu * nv` particles generated on the device (`nv == 1`: a line, the usual 2D tap).
+    pub fn emit_nozzle(&mut self, nozzle: &Nozzle) { check(unsafe { fs_emit_nozzle(self.raw, nozzle) }); }
+    /// Removes every particle with `lo <= position <= hi` on both axes (blocking, stable); returns how many went.
+    pub fn remove_box(&mut self, lo: Vec2, hi: Vec2) -> u32 { let mut n = 0u32; check(unsafe { fs_remove_in_box(self.raw, &lo, &hi, &mut n) }); n }
+    /// Removes the particles whose flag (one per particle, download order) is non-zero (blocking, stable); returns how many went.
+    pub fn remove(&mut self, flags: &[u8]) -> u32 { let mut n = 0u32; check(unsafe { fs_remove_flagged(self.raw, flags.as_ptr(), flags.len(), &mut n) }); n }
+    /// The id the next emitted particle gets while tracking is on (0 when it is off).
+    pub fn next_id(&self) -> u32 { unsafe { fs_track_next_id(self.raw) } }
     /// `start_indices` to the host (the renderer's second storage binding; u32[grid_w * grid_h]).
     pub fn download_start_indices(&mut self) -> Vec<u32> {
         let (w, h) = self.grid_dims();

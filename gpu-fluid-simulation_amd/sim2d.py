@@ -4,9 +4,9 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (FS_MATH_IEEE, FS_SORT_BITONIC, PARTICLE_DTYPE, SAMPLE_DTYPE, Options, Settings, SortStep, TickSettings,
+from ._abi import (FS_MATH_IEEE, FS_SORT_BITONIC, PARTICLE_DTYPE, SAMPLE_DTYPE, Nozzle, Options, Settings, SortStep, TickSettings,
                    Uniform, UVec2, Vec2, load_library)
-from ._handle import _check, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec2
+from ._handle import _check, _Count, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec2
 
 
 def SimulationSettings(particle_count=100_000, particle_spacing=0.1, smoothing_radius=0.2, size=(53.0, 53.0),
@@ -45,12 +45,13 @@ def dam_break_2d(n):
     return settings, (float(off[0]), float(off[1])), tick
 
 
-class FluidSimulation(_Tracking, _SurfaceTension, _Simulation):
+class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Simulation):
     """FluidSimulation (src/simulation.rs:10-37) on one MI355X, driven through the C ABI."""
     _prefix = "fs_"
     _destroy = "fs_destroy"
     _record = PARTICLE_DTYPE
     _dim = 2
+    _nozzle = Nozzle         # the particle count that changes at run time (DESIGN.md §22): _Count
 
     def __init__(self, settings, device=0, sort_mode=FS_SORT_BITONIC, ref_quirks=True, initial_offset=(0.0, 0.0),
                  capacity=0, math_mode=FS_MATH_IEEE, surface_tension=False, track=None):

@@ -7,7 +7,7 @@ import numpy as np
 from . import _abi
 from ._abi import (FS_MATH_IEEE, MESH_VERTEX_DTYPE, PARTICLE3_DTYPE, SAMPLE3_DTYPE, SURFACE_HIT_DTYPE, Camera3, Nozzle3,
                    Settings3, TickSettings3, Vec3, load_library)
-from ._handle import _check, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec3
+from ._handle import _check, _Count, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec3
 
 
 def dam_break_3d(n):
@@ -27,12 +27,13 @@ def dam_break_3d(n):
     return st, (float(off[0]), float(off[1]), float(off[2])), tick
 
 
-class FluidSimulation3D(_Tracking, _SurfaceTension, _Simulation):
+class FluidSimulation3D(_Count, _Tracking, _SurfaceTension, _Simulation):
     """3D extension (include/fluidsim.h fs3_*); not in the reference."""
     _prefix = "fs3_"
     _destroy = "fs3_destroy"
     _record = PARTICLE3_DTYPE
     _dim = 3
+    _nozzle = Nozzle3        # the particle count that changes at run time (DESIGN.md §21): _Count
 
     def __init__(self, settings, device=0, initial_offset=(0.0, 0.0, 0.0), math_mode=FS_MATH_IEEE, track=None):
         super().__init__()
@@ -71,46 +72,6 @@ class FluidSimulation3D(_Tracking, _SurfaceTension, _Simulation):
         c, t = C.c_float(), C.c_float()
         self._call("surface_tension_params", C.byref(c), C.byref(t))
         return float(c.value), float(t.value)
-
-    # -- 3D particle count (build extension) ------------------
-    @property
-    def capacity(self):
-        """Slots of the handle: particle_count can grow to this (reserve() raises it)."""
-        return int(self._fn("capacity")(self._h))
-
-    def reserve(self, capacity):
-        """Room for `capacity` particles (grow-only, blocking); the state and everything observable are preserved."""
-        self._call("reserve", int(capacity))
-
-    def emit(self, records):
-        """Append PARTICLE3_DTYPE records behind the live particles, all fields as given; particle_count + len <= capacity."""
-        arr = np.ascontiguousarray(records, dtype=PARTICLE3_DTYPE)
-        self._call("emit_particles", _ptr(arr), arr.shape[0])
-
-    def emit_nozzle(self, origin, u, v, velocity, nu, nv):
-        """Append a layer of nu x nv particles generated on the device: centred on `origin`, spaced by the vectors u and v,
-        all with `velocity` (include/fluidsim.h "3D particle count")."""
-        z = Nozzle3(_vec3(origin), _vec3(u), _vec3(v), _vec3(velocity), int(nu), int(nv))
-        self._call("emit_nozzle", C.byref(z))
-
-    def remove_box(self, lo, hi):
-        """Remove every particle with lo <= position <= hi on every axis (blocking, stable); returns how many went."""
-        a, b, n = _vec3(lo), _vec3(hi), C.c_uint32()
-        self._call("remove_in_box", C.byref(a), C.byref(b), C.byref(n))
-        return int(n.value)
-
-    def remove(self, flags):
-        """Remove the particles whose entry of `flags` (one per particle, download_particles() order) is non-zero (blocking,
-        stable); returns how many went."""
-        f = np.ascontiguousarray(np.asarray(flags) != 0, dtype=np.uint8)
-        n = C.c_uint32()
-        self._call("remove_flagged", _ptr(f), f.shape[0], C.byref(n))
-        return int(n.value)
-
-    @property
-    def next_id(self):
-        """The id the next emitted particle gets while tracking is on (0 when it is off)."""
-        return int(self._fn("track_next_id")(self._h))
 
     # -- 3D field sampling (build extension; DESIGN.md §14, the channels: §20) ----
     def sample(self, points, attributes=False, normalise=False):

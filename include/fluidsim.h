@@ -394,6 +394,74 @@ fs_status fs_sample_points(fs_sim* sim, const fs_vec2* points, size_t n, fs_samp
 fs_status fs_sample_points_device(fs_sim* sim, const fs_vec2* points_dev, size_t n, fs_sample* out_dev, float* attr_out_dev);
 fs_status fs_sample_grid(fs_sim* sim, const fs_view* view, fs_sample* out, float* attr_out);
 
+/* ------------------------------------------------ 2D particle count (build extension, opt-in by being called) */
+/* A particle count that changes at run time: a tap that fills a tank, an outflow, a scene assembled from blocks of fluid.  The
+ * 2D counterpart of "3D particle count" below, clause for clause.  A handle has `capacity` slots (fs_options.capacity at create,
+ * at least settings.particle_count) and a live count <= capacity; after fs_create both are settings.particle_count.
+ * fs_particle_count returns the live count, and every step, transfer and query works on exactly that many particles;
+ * fs_uniform.particle_count follows it.  The live count is always known to the host: emission has a size the caller gives,
+ * removal is a blocking call that returns how many particles went.  The step's passes are unchanged, in both sort modes, and a
+ * handle that never calls these functions launches exactly the kernels it launched before, with the same arguments.
+ * FS_ABI_VERSION is unchanged.  Single-domain handles only: on a slab handle every call below is FS_ERR_INVALID right after
+ * the NULL check (a slab's count belongs to the exchange; fs_capacity and fs_track_next_id only read).  See DESIGN.md §22.
+ *
+ * fs_reserve: grow-only and blocking.  capacity > 2^28 is FS_ERR_INVALID; capacity <= fs_capacity is FS_OK and does nothing.
+ * Every per-slot array gets `capacity` slots; the records, the tick, start_indices, the force field, ids and channels, the last
+ * step's surface-tension forces and the validity of the queries are preserved bit for bit.  Everything new is allocated before
+ * anything old is released: on FS_ERR_OOM the handle is exactly what it was.  Device pointers handed out by fs_track_*_device
+ * die.  On a handle with a renderer hand-off registered (fs_export_handle(FS_EXPORT_PARTICLES)) fs_reserve is FS_ERR_INVALID,
+ * whatever the capacity: the exported allocation cannot move.  Such a caller sizes the handle with fs_options.capacity at create.
+ *
+ * fs_emit_particles: appends n host records at slots [count, count + n), stored as fs_upload_particles stores them, all five
+ * fields as given; ordered on fs_stream after the steps in flight, and back only when `src` has been read.  In this order: a NULL
+ * handle is FS_ERR_INVALID; n == 0 is FS_OK and touches nothing; a NULL src is FS_ERR_INVALID; count + n > capacity is
+ * FS_ERR_INVALID and changes nothing.
+ *
+ * fs_emit_nozzle: the same append of M = nu * nv records generated on the device, no host array and no transfer.  For q in
+ * [0, M), in f32 without contraction:
+ *     a = q % nu;  b = q / nu;  sa = ((float)a + 0.5f) - 0.5f * (float)nu;  sb = ((float)b + 0.5f) - 0.5f * (float)nv
+ *     position.c = (origin.c + sa * u.c) + sb * v.c;  predicted_position = position;  velocity = nozzle.velocity
+ *     density = +0;  grid = 0;  stored at slot count + q
+ * nv == 1 is a line of particles, the usual 2D tap; nv > 1 a block of fluid.  Positions outside the box are legal: the step's
+ * clamps deal with them as with an upload.  FS_ERR_INVALID, in this order: a NULL handle or nozzle; nu == 0, nv == 0 or
+ * nu * nv > 2^28; any of the 8 floats not finite; count + M > capacity (nothing changes).  Enqueued on fs_stream; with
+ * FS_SORT_BITONIC it waits for the steps in flight only when the count crosses a power of two, with FS_SORT_COUNTING never.
+ *
+ * fs_remove_in_box / fs_remove_flagged: blocking.  Slot i goes when lo.a <= position.a && position.a <= hi.a on both axes
+ * (inclusive edges; a NaN coordinate is never removed; the test runs on the device), or when flags_host[i] != 0, where n must
+ * equal the count (else FS_ERR_INVALID).  The survivors keep their relative order; position, predicted position, velocity,
+ * density, grid and, with tracking on, ids and every channel move as bit copies.  *removed receives the number removed.  Fewer
+ * than 2 survivors: FS_ERR_INVALID, *removed = 0, nothing changes.  Nothing matches: FS_OK, *removed = 0, nothing changes at
+ * all (the queries stay valid).  NULL arguments are FS_ERR_INVALID.
+ *
+ * After any call that changed the count: fs_render_density, fs_sample_* and fs_sample_grid return FS_ERR_INVALID until the next
+ * step, fs_download_surface_tension until the next step with the pass on, and pointers from fs_track_*_device are dead.
+ * fs_upload_particles still clamps to the live count and never grows it.  start_indices is sized by the grid and persistent: no
+ * call here touches it, so after a removal it may name slots >= count (the stale-start quirk of ref_quirks = 1 then clamps to
+ * the cell's count, as it always did).  Slots behind the live count keep whatever they held; no result depends on them.
+ *
+ * Renderer hand-off: emission and removal are allowed on a handle with a hand-off registered.  The exported view then holds the
+ * new state, for the new count, after the next step (or after the next fs_particles_device, which re-materialises it); between
+ * the change and that, its contents are unspecified.  The exported allocation has `capacity` records and never moves: the IPC
+ * handle names all of it, so an importer reads the new count's records at the address it already has.  fs_mem_handle.bytes and
+ * the dma-buf descriptor cover the live count at the time of the export only: a consumer of the descriptor calls
+ * fs_export_handle again after the count has grown past that.
+ *
+ * Tracking: fs_track_enable sets next_id to the live count at the call; every particle emitted while tracking is on gets
+ * id = next_id++ in emission order (wrapping u32) and +0.0f in every channel; fs_track_upload_ids does not touch next_id;
+ * removal compacts ids and channels with the records.  fs_track_next_id: next_id, or 0 when tracking is off. */
+fs_status fs_reserve(fs_sim* sim, uint32_t capacity);
+uint32_t fs_capacity(const fs_sim* sim);
+fs_status fs_emit_particles(fs_sim* sim, const fs_particle* src, size_t n);
+typedef struct fs_nozzle {        /* 40 bytes */
+    fs_vec2 origin, u, v, velocity;
+    uint32_t nu, nv;
+} fs_nozzle;
+fs_status fs_emit_nozzle(fs_sim* sim, const fs_nozzle* nozzle);
+fs_status fs_remove_in_box(fs_sim* sim, const fs_vec2* lo, const fs_vec2* hi, uint32_t* removed);
+fs_status fs_remove_flagged(fs_sim* sim, const uint8_t* flags_host, size_t n, uint32_t* removed);
+uint32_t fs_track_next_id(const fs_sim* sim);
+
 /* ------------------------------------------------ multi-GPU slab mode (build extension) */
 /* NOT in the reference (single wgpu device, src/renderer.rs:108-133).  SURVEY.md §8e: a rank
  * owns the global cell columns [own_lo, own_hi) of the grid (src/simulation.rs:140-141) and
