@@ -5,6 +5,9 @@ Every operation is one numpy f32 operation (one rounding, no contraction).  The 
 sums grow in the statement's order: the 27 cells oz, oy, ox in -1..1, and within a cell the slots ascending — step j of a cell
 adds, for every query whose cell still has a j-th slot and whose candidate is in radius, that candidate's term and nothing else
 (a skipped candidate is not an added zero)."""
+import ctypes
+import ctypes.util
+
 import numpy as np
 
 from tests.track3d_ref import cell_xyz
@@ -13,9 +16,22 @@ f = np.float32
 PI3 = f(3.14159265359)
 
 
+_libm = None
+
+
+def powf(x, y):
+    """powf of the host libm, which the header's C6 names.  numpy's float32 power is another implementation: at h = 0.33 it is
+    one ulp off, and so was every weight (tests/test_hard_states3d.py compares the two)."""
+    global _libm
+    if _libm is None:
+        _libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+        _libm.powf.restype, _libm.powf.argtypes = ctypes.c_float, [ctypes.c_float, ctypes.c_float]
+    return f(_libm.powf(float(f(x)), float(f(y))))
+
+
 def poly6(h):
     """C6 = 315.0f / (64.0f * PI3 * powf(h, 9.0f))."""
-    return f(315.0) / (f(64.0) * PI3 * np.power(f(h), f(9.0)))
+    return f(315.0) / (f(64.0) * PI3 * powf(h, 9.0))
 
 
 def sample_attr(settings, grid_dims, mass, p, attr, points, dtype=np.float32):

@@ -483,6 +483,57 @@ def test_queries_wait_for_a_step_after_a_change(fs):
     smp.close(); sim.close(); chk.close()
 
 
+def test_rendering_and_extraction_with_a_live_count_below_the_capacity(fs):
+    """reserve, emit 150, step, remove a quarter, step: after each of the two steps the G-buffer at 37 x 23 and the meshes on
+    (17, 9, 6) and (33, 33, 33) equal their checkers, both loaded from the download at the live count"""
+    from tests.emit3d_ref import random_records
+    from tests.mesh3d_ref import Mesh3Checker, scene_views
+    from tests.render3d_ref import Render3Checker, iso_of, params, scene_cameras
+    sim, chk, tick, st = make(fs, 12 ** 3)
+    sim.reserve(1900)
+
+    def check(ctx):
+        n = sim.particle_count
+        assert n < sim.capacity == 1900
+        p = sim.download_particles()
+        assert p.shape[0] == n and all(np.isfinite(p[fld]).all() for fld in FIELDS)
+        live, iso = chk.settings(n), iso_of(p)
+        rnd = Render3Checker(live, chk.offset).load(p, tick.mass)
+        kinds = set()
+        for name, (cam, t_near) in scene_cameras(live, p, 37, 23).items():
+            for refine in (0, 8):
+                sp = params(iso, t_near, 0.5 * st.smoothing_radius, 64, refine)
+                want = rnd.render(cam, sp)
+                got = sim.render_surface(fs.Camera3.from_buffer_copy(bytes(cam)), fs.SurfaceParams3.from_buffer_copy(bytes(sp)))
+                assert got.tobytes() == want.tobytes(), f"{ctx}: render {name} refine {refine}"
+                kinds.update(np.unique(want["hit"]).tolist())
+        assert kinds == {0, 1, 2}, f"{ctx}: hit kinds {kinds}"
+        rnd.close()
+        msh = Mesh3Checker(live, chk.offset).load(p, tick.mass)
+        most = 0
+        for name, (wmin, wmax) in scene_views(live, p).items():
+            for dims in ((17, 9, 6), (33, 33, 33)):
+                want_v, want_t, want_c = msh.extract(dims, wmin, wmax, iso)
+                got_v, got_t = sim.extract_surface(*dims, iso, wmin, wmax)
+                assert (got_v.shape[0], got_t.shape[0]) == want_c, f"{ctx}: mesh {name} {dims}: counts"
+                assert got_v.tobytes() == want_v.tobytes() and got_t.tobytes() == want_t.tobytes(), f"{ctx}: mesh {name} {dims}"
+                most = max(most, want_c[0])
+        assert most > 500, f"{ctx}: the largest mesh has {most} vertices"
+        msh.close()
+
+    rec = random_records(st, 150, 81)
+    sim.emit(rec); chk.emit(rec)
+    steps(sim, chk, tick, 1, "after emit")
+    assert sim.particle_count == 1878
+    check("1878 of 1900")
+    kill = np.random.default_rng(7).random(chk.n) < 0.25
+    assert sim.remove(kill) == chk.remove(kill)
+    steps(sim, chk, tick, 1, "after remove")
+    assert 1300 < sim.particle_count < 1500
+    check(f"{sim.particle_count} of 1900")
+    sim.close(); chk.close()
+
+
 # ---- 11. stream order ----------------------------------------------------------------------------------------------------
 def test_nozzle_between_steps_without_a_sync(fs):
     sim, chk, tick, st = make(fs, 12 ** 3)
