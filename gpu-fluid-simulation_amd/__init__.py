@@ -30,6 +30,7 @@ from ._abi import (  # noqa: F401
     SAMPLE3_DTYPE,
     SAMPLE_DTYPE,
     SURFACE_HIT_DTYPE,
+    BodyMotion3,
     Camera3,
     ExtensionMissing,
     Nozzle,
@@ -63,7 +64,7 @@ from .sim2d import (  # noqa: F401
     reference_lattice,
     sort_schedule,
 )
-from .sim3d import FluidSimulation3D, box_mask3d, dam_break_3d, look_at_camera, reference_lattice_3d  # noqa: F401
+from .sim3d import FluidSimulation3D, box_mask3d, dam_break_3d, look_at_camera, reference_lattice_3d, rigid_motion  # noqa: F401
 from .slab import SlabSimulation  # noqa: F401
 
 __all__ = [

@@ -162,6 +162,14 @@ class Nozzle3(C.Structure):
     _fields_ = [("origin", Vec3), ("u", Vec3), ("v", Vec3), ("velocity", Vec3), ("nu", C.c_uint32), ("nv", C.c_uint32)]
 
 
+FS3_MAX_BODIES = 8
+
+
+class BodyMotion3(C.Structure):
+    """fs3_body_motion (include/fluidsim.h "3D moving bodies"): 72 bytes.  rot: row-major R, world = R * local."""
+    _fields_ = [("centre", Vec3), ("rot", C.c_float * 9), ("velocity", Vec3), ("angular_velocity", Vec3)]
+
+
 class SurfaceHit3(C.Structure):
     """fs3_surface_hit (include/fluidsim.h): 40 bytes."""
     _fields_ = [("t", C.c_float), ("density", C.c_float), ("normal", Vec3), ("velocity", Vec3), ("steps", C.c_uint32),
@@ -365,6 +373,14 @@ PROTOTYPES = {
     "fs3_collider_clear": (C.c_int, [_P]),
     "fs3_collider_dims": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fs3_collider_download": (C.c_int, [_P, _P, C.c_size_t]),
+    "fs3_body_create": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, Vec3, C.POINTER(C.c_uint32)]),
+    "fs3_body_create_from_mask": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, Vec3, _P, C.POINTER(C.c_uint32)]),
+    "fs3_body_set_motion": (C.c_int, [_P, C.c_uint32, C.POINTER(BodyMotion3)]),
+    "fs3_body_get_motion": (C.c_int, [_P, C.c_uint32, C.POINTER(BodyMotion3)]),
+    "fs3_body_dims": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(Vec3)]),
+    "fs3_body_download": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t]),
+    "fs3_body_destroy": (C.c_int, [_P, C.c_uint32]),
+    "fs3_body_count": (C.c_uint32, [_P]),
     "fs3_set_surface_tension": (C.c_int, [_P, C.c_int, C.c_float, C.c_float]),
     "fs3_surface_tension_enabled": (C.c_int, [_P]),
     "fs3_surface_tension_params": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),

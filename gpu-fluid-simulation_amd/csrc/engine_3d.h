@@ -1,7 +1,7 @@
 // engine_3d.h — what the host files of the fs3_* C ABI share: the 3D simulation handle with the state of each of its features, the
 // Params3 both the step and the queries start from, and the few helpers more than one of them needs.  The handle's files:
 // engine_3d.hip (lattice, life cycle, step, getters, transfers, timing), engine_3d_features.hip (what the step enqueues for:
-// colliders, surface tension, tracking), engine_3d_query.hip (everything behind sample_stale: sampling, rendering, extraction),
+// colliders, moving bodies, surface tension, tracking), engine_3d_query.hip (everything behind sample_stale: sampling, rendering, extraction),
 // engine_3d_count.hip (a particle count that changes at run time: reserve, emit, remove).
 // From the 2D engine (engine.h): the device check, the create-time proofs, the owners, the sort policy and Tracking.
 #pragma once
@@ -83,6 +83,40 @@ struct fs_sim3 {
             return w ? K : nullptr;
         }
     } collider;
+    // The opt-in moving bodies: per slot a voxel field over the body's own box and the motion the host last set;
+    // w == 0: the slot is free, and never created: no allocation, no launch.
+    struct Bodies {
+        struct Slot {
+            fsd::DevArray<float4> field;
+            uint32_t w = 0, h = 0, d = 0;
+            fs_vec3 extent{};
+            fs3_body_motion motion{};
+            size_t voxels() const { return (size_t)w * h * d; }
+        } slot[FS3_MAX_BODIES];
+        bool has(uint32_t k) const { return k < FS3_MAX_BODIES && slot[k].w != 0u; }
+        uint32_t count() const { uint32_t c = 0; for (const Slot& b : slot) c += b.w ? 1u : 0u; return c; }
+        // the lowest free slot, FS3_MAX_BODIES when every slot is in use
+        uint32_t free_slot() const { uint32_t k = 0; while (k < FS3_MAX_BODIES && slot[k].w) ++k; return k; }
+        // What a step takes, by value into *B: the fields and the motions as they are when it is enqueued, the slots in use in
+        // ascending order (fs3_body_* order their writes and frees on the stream behind it).  Null: no slot is in use.
+        const fsd::Bodies3* for_step(fsd::Bodies3* B) const {
+            uint32_t c = 0;
+            for (const Slot& b : slot) {
+                if (!b.w) continue;
+                const fs3_body_motion& m = b.motion;
+                fsd::Body3& K = B->body[c++];
+                K.field = b.field.p; K.w = b.w; K.h = b.h; K.d = b.d;
+                K.ex = b.extent.x; K.ey = b.extent.y; K.ez = b.extent.z;
+                K.hx = b.extent.x * 0.5f; K.hy = b.extent.y * 0.5f; K.hz = b.extent.z * 0.5f;
+                K.cx = m.centre.x; K.cy = m.centre.y; K.cz = m.centre.z;
+                for (int e = 0; e < 9; ++e) K.r[e] = m.rot[e];
+                K.ux = m.velocity.x; K.uy = m.velocity.y; K.uz = m.velocity.z;
+                K.wx = m.angular_velocity.x; K.wy = m.angular_velocity.y; K.wz = m.angular_velocity.z;
+            }
+            B->count = c;
+            return c ? B : nullptr;
+        }
+    } bodies;
     // The opt-in surface tension: never enabled: no allocation, no launch.
     struct Tension {
         fsd::DevArray<float4> st;    // the last step's force per sorted slot {x, y, z, 0}; allocated by the first enable

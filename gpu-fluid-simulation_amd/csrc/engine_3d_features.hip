@@ -1,5 +1,6 @@
 // engine_3d_features.hip — the opt-in features the 3D step enqueues for (their state: engine_3d.h, one struct each): colliders
-// (DESIGN.md §18), surface tension (§19), particle tracking (§20) and, on top of tracking, fs3_download_particles_by_id.
+// (DESIGN.md §18), moving bodies (§23), surface tension (§19), particle tracking (§20) and, on top of tracking,
+// fs3_download_particles_by_id.
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -16,6 +17,44 @@ fs_status collider3_check(const void* array, uint32_t w, uint32_t h, uint32_t d)
     if (!array) return fail(FS_ERR_INVALID, "null argument");
     if (w == 0u || h == 0u || d == 0u || w > top || h > top || d > top) return fail(FS_ERR_INVALID, "collider: an extent of 0 or above 1024");
     return FS_OK;
+}
+
+// The producer of §18 on a host mask, blocking: the push field of a w x h x d mask over a box of `size` into `field` (device,
+// w * h * d vectors).  Its staging and scratch live for the call.  The stream is synchronised before they are freed, whatever
+// happened.
+fs_status mask_to_field3(hipStream_t st, const uint8_t* mask, uint32_t w, uint32_t h, uint32_t d, fs_vec3 size, float4* field,
+                         const DevArray<uint8_t>& dmask, const DevArray<uint32_t>& near_x, const DevArray<uint32_t>& near_xy) {
+    fsd::ColliderMask3 Q;
+    Q.mask = dmask.p; Q.w = w; Q.h = h; Q.d = d;
+    Q.vx = size.x / (float)w; Q.vy = size.y / (float)h; Q.vz = size.z / (float)d;
+    Q.near_x = near_x.p; Q.near_xy = near_xy.p; Q.field = field;
+    hipError_t e = hipMemcpyAsync(dmask.p, mask, (size_t)w * h * d, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) { fsd::launch3_collider_from_mask(st, Q); e = hipGetLastError(); }
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    return e == hipSuccess ? FS_OK : fail(FS_ERR_DEVICE, hipGetErrorString(e));
+}
+
+bool mask_has_free_voxel(const uint8_t* mask, size_t voxels) {
+    for (size_t k = 0; k < voxels; ++k) if (!(mask[k] > 128)) return true;
+    return false;
+}
+
+// Checks 3 and 4 of the two body constructors (the handle and the pointers first, by the caller).
+fs_status body3_check(uint32_t w, uint32_t h, uint32_t d, fs_vec3 extent) {
+    FS_TRY(collider3_check(&extent, w, h, d));
+    const auto good = [](float a) { return std::isfinite(a) && a > 0.0f; };
+    if (!good(extent.x) || !good(extent.y) || !good(extent.z)) return fail(FS_ERR_INVALID, "body: a box extent that is not finite and > 0");
+    return FS_OK;
+}
+
+// A produced or uploaded field becomes the body of `slot`: identity pose at the origin, at rest.
+void body3_install(fs_sim3* s, uint32_t slot, DevArray<float4>&& field, uint32_t w, uint32_t h, uint32_t d, fs_vec3 extent) {
+    fs_sim3::Bodies::Slot& b = s->bodies.slot[slot];
+    b.field = std::move(field);
+    b.w = w; b.h = h; b.d = d; b.extent = extent;
+    b.motion = fs3_body_motion{};
+    b.motion.rot[0] = b.motion.rot[4] = b.motion.rot[8] = 1.0f;
 }
 
 // The field in use as w * h * d fs_vec3 on the host.  Blocking.
@@ -57,9 +96,7 @@ fs_status fs3_collider_from_mask(fs_sim3* s, const uint8_t* mask, uint32_t w, ui
     if (!s) return fail(FS_ERR_INVALID, "null argument");
     FS_TRY(collider3_check(mask, w, h, d));
     const size_t voxels = (size_t)w * h * d;
-    bool any_free = false;
-    for (size_t k = 0; k < voxels && !any_free; ++k) any_free = !(mask[k] > 128);
-    if (!any_free) return fail(FS_ERR_INVALID, "collider: the mask has no free voxel");
+    if (!mask_has_free_voxel(mask, voxels)) return fail(FS_ERR_INVALID, "collider: the mask has no free voxel");
     FS_HIP(hipSetDevice(s->device));
     DevArray<uint8_t> dmask;
     DevArray<uint32_t> near_x, near_xy;
@@ -68,15 +105,8 @@ fs_status fs3_collider_from_mask(fs_sim3* s, const uint8_t* mask, uint32_t w, ui
         return fail(FS_ERR_OOM, "collider: device staging");
     }
     FS_TRY(s->collider.reserve(s->stream, voxels));
-    fsd::ColliderMask3 Q;
-    Q.mask = dmask.p; Q.w = w; Q.h = h; Q.d = d;
-    Q.vx = s->st.size.x / (float)w; Q.vy = s->st.size.y / (float)h; Q.vz = s->st.size.z / (float)d;
-    Q.near_x = near_x.p; Q.near_xy = near_xy.p; Q.field = s->collider.field.p;
-    hipError_t e = hipMemcpyAsync(dmask.p, mask, voxels, hipMemcpyHostToDevice, s->stream);
-    if (e == hipSuccess) { fsd::launch3_collider_from_mask(s->stream, Q); e = hipGetLastError(); }
-    const hipError_t es = hipStreamSynchronize(s->stream);      // before the staging is freed, whatever happened
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) { s->collider.clear(); return fail(FS_ERR_DEVICE, hipGetErrorString(e)); }
+    const fs_status r = mask_to_field3(s->stream, mask, w, h, d, s->st.size, s->collider.field.p, dmask, near_x, near_xy);
+    if (r != FS_OK) { s->collider.clear(); return r; }
     s->collider.set(w, h, d);
     return field_host ? collider3_read(s, field_host) : FS_OK;
 }
@@ -103,6 +133,104 @@ fs_status fs3_collider_download(fs_sim3* s, fs_vec3* dst, size_t n) {
     FS_HIP(hipSetDevice(s->device));
     return collider3_read(s, dst);
 }
+
+// ---- 3D moving bodies -----------------------------------------------------------------------------------
+fs_status fs3_body_create(fs_sim3* s, const fs_vec3* field, uint32_t w, uint32_t h, uint32_t d, fs_vec3 extent, uint32_t* body_out) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    if (!field || !body_out) return fail(FS_ERR_INVALID, "null argument");
+    FS_TRY(body3_check(w, h, d, extent));
+    const size_t voxels = (size_t)w * h * d;
+    std::unique_ptr<float4[]> host(new (std::nothrow) float4[voxels]);
+    if (!host) return fail(FS_ERR_OOM, "host allocation failed");
+    for (size_t k = 0; k < voxels; ++k) {
+        const fs_vec3 f = field[k];
+        if (!std::isfinite(f.x) || !std::isfinite(f.y) || !std::isfinite(f.z)) return fail(FS_ERR_INVALID, "body: non-finite component");
+        host[k] = make_float4(f.x, f.y, f.z, 0.0f);
+    }
+    const uint32_t slot = s->bodies.free_slot();
+    if (slot == FS3_MAX_BODIES) return fail(FS_ERR_INVALID, "body: no free slot");
+    FS_HIP(hipSetDevice(s->device));
+    DevArray<float4> dev;
+    if (dev.alloc(voxels) != hipSuccess) { (void)hipGetLastError(); return fail(FS_ERR_OOM, "body: device field"); }
+    FS_HIP(hipMemcpyAsync(dev.p, host.get(), voxels * sizeof(float4), hipMemcpyHostToDevice, s->stream));
+    FS_HIP(hipStreamSynchronize(s->stream));
+    body3_install(s, slot, std::move(dev), w, h, d, extent);
+    *body_out = slot;
+    return FS_OK;
+}
+
+fs_status fs3_body_create_from_mask(fs_sim3* s, const uint8_t* mask, uint32_t w, uint32_t h, uint32_t d, fs_vec3 extent,
+                                    fs_vec3* field_host, uint32_t* body_out) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    if (!mask || !body_out) return fail(FS_ERR_INVALID, "null argument");
+    FS_TRY(body3_check(w, h, d, extent));
+    const size_t voxels = (size_t)w * h * d;
+    if (!mask_has_free_voxel(mask, voxels)) return fail(FS_ERR_INVALID, "body: the mask has no free voxel");
+    const uint32_t slot = s->bodies.free_slot();
+    if (slot == FS3_MAX_BODIES) return fail(FS_ERR_INVALID, "body: no free slot");
+    FS_HIP(hipSetDevice(s->device));
+    DevArray<uint8_t> dmask;
+    DevArray<uint32_t> near_x, near_xy;
+    DevArray<float4> dev;
+    if (dmask.alloc(voxels) != hipSuccess || near_x.alloc(voxels) != hipSuccess || near_xy.alloc(voxels) != hipSuccess ||
+        dev.alloc(voxels) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FS_ERR_OOM, "body: device staging");
+    }
+    FS_TRY(mask_to_field3(s->stream, mask, w, h, d, extent, dev.p, dmask, near_x, near_xy));
+    if (field_host) FS_TRY(fsd::download_vec3(s->stream, dev.p, voxels, field_host));
+    body3_install(s, slot, std::move(dev), w, h, d, extent);
+    *body_out = slot;
+    return FS_OK;
+}
+
+fs_status fs3_body_set_motion(fs_sim3* s, uint32_t body, const fs3_body_motion* m) {
+    if (!s || !m) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->bodies.has(body)) return fail(FS_ERR_INVALID, "body: the slot holds no body");
+    const float* f = &m->centre.x;              // 18 floats, nothing between them (static_assert below)
+    for (int k = 0; k < 18; ++k) if (!std::isfinite(f[k])) return fail(FS_ERR_INVALID, "body: non-finite motion");
+    s->bodies.slot[body].motion = *m;           // host memory only: the next enqueue takes it by value
+    return FS_OK;
+}
+static_assert(sizeof(fs3_body_motion) == 18 * sizeof(float), "fs3_body_motion is 18 packed floats");
+static_assert(fsd::BODIES3_MAX == FS3_MAX_BODIES, "Bodies3 holds every slot of the ABI");
+
+fs_status fs3_body_get_motion(const fs_sim3* s, uint32_t body, fs3_body_motion* out) {
+    if (!s || !out) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->bodies.has(body)) return fail(FS_ERR_INVALID, "body: the slot holds no body");
+    *out = s->bodies.slot[body].motion;
+    return FS_OK;
+}
+
+fs_status fs3_body_dims(const fs_sim3* s, uint32_t body, uint32_t* w, uint32_t* h, uint32_t* d, fs_vec3* extent) {
+    if (!s || !w || !h || !d || !extent) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->bodies.has(body)) return fail(FS_ERR_INVALID, "body: the slot holds no body");
+    const fs_sim3::Bodies::Slot& b = s->bodies.slot[body];
+    *w = b.w; *h = b.h; *d = b.d; *extent = b.extent;
+    return FS_OK;
+}
+
+fs_status fs3_body_download(fs_sim3* s, uint32_t body, fs_vec3* dst, size_t n) {
+    if (!s || !dst) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->bodies.has(body)) return fail(FS_ERR_INVALID, "body: the slot holds no body");
+    const fs_sim3::Bodies::Slot& b = s->bodies.slot[body];
+    if (n != b.voxels()) return fail(FS_ERR_INVALID, "body: n must be w * h * d");
+    FS_HIP(hipSetDevice(s->device));
+    return fsd::download_vec3(s->stream, b.field.p, n, dst);
+}
+
+fs_status fs3_body_destroy(fs_sim3* s, uint32_t body) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->bodies.has(body)) return fail(FS_ERR_INVALID, "body: the slot holds no body");
+    FS_HIP(hipSetDevice(s->device));
+    FS_HIP(hipStreamSynchronize(s->stream));       // the steps in flight read the field
+    fs_sim3::Bodies::Slot& b = s->bodies.slot[body];
+    b.w = b.h = b.d = 0;
+    b.field.release();
+    return FS_OK;
+}
+
+uint32_t fs3_body_count(const fs_sim3* s) { return s ? s->bodies.count() : 0u; }
 
 // ---- 3D surface tension -------------------------------------------------------------------------------
 fs_status fs3_set_surface_tension(fs_sim3* s, int enable, float coefficient, float threshold) {

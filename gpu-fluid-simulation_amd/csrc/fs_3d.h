@@ -1,4 +1,4 @@
-// fs_3d.h — what the files of the 3D step share (kernels_3d.hip, kernels_density3d.hip, kernels_force3d.hip: the kernels and
+// fs_3d.h — what the files of the 3D step share (kernels_3d.hip, kernels_density3d.hip, kernels_force3d.hip, kernels_bodies3d.hip: the kernels and
 // their launchers, engine_3d*.hip over engine_3d.h: the handle and the fs3_* C ABI): the step parameters, the array set of the
 // launchers, the launchers.  A header of its own:
 // fs_kernels.h stays the 2D launchers' list, and kernels_sort_tile.inc takes the predict + cell-key expression from here.
@@ -86,6 +86,27 @@ void launch3_surface_tension(hipStream_t st, const Params3& P, const Arrays3& A,
 // forces of launch3_surface_tension, added to the force sum.
 void launch3_force(hipStream_t st, const Params3& P, const Arrays3& A, bool tol, hipEvent_t done, const Collide3* K = nullptr,
                    const float4* stf = nullptr);
+// The opt-in moving bodies of a handle (include/fluidsim.h "3D moving bodies") as k3_bodies takes them, by value
+// and apart from Params3 (kernels_bodies3d.hip).  Per body: the voxel field of Collide3 over the body's own box, and the motion
+// of this enqueue.  r[3 * i + j]: row-major R, world = R * local.  body[0 .. count) are the slots in use, ascending.
+constexpr uint32_t BODIES3_MAX = 8u;   // FS3_MAX_BODIES
+struct Body3 {
+    const float4* field;
+    uint32_t w, h, d;
+    float ex, ey, ez;            // the box's extent: the divisor of the lookup
+    float hx, hy, hz;            // extent * 0.5f
+    float cx, cy, cz;
+    float r[9];
+    float ux, uy, uz;
+    float wx, wy, wz;
+};
+struct Bodies3 {
+    uint32_t count;
+    Body3 body[BODIES3_MAX];
+};
+// After launch3_force, on the positions (A.pos_out) and velocities (A.vel) it stored: the operators B of every body in order.
+// P: n, bx, by, bz, damping.  done (may be null): signalled by the kernel's completion, as launch3_force's is.
+void launch3_bodies(hipStream_t st, const Params3& P, const Arrays3& A, const Bodies3& B, hipEvent_t done);
 void launch3_import(hipStream_t st, uint32_t n, const Arrays3& A);   // aos -> pos, pred, vel, key
 void launch3_export(hipStream_t st, uint32_t n, const Arrays3& A);   // ... and back
 

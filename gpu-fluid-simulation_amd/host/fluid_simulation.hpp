@@ -261,6 +261,34 @@ public:
         if (!v.empty()) check(fs3_collider_download(h_, v.data(), v.size()));
         return v;
     }
+    // 3D moving bodies: w * h * d push vectors over the body's own box [-extent/2, extent/2] in the body frame, the layout of
+    // set_collider.  add_body* return the slot (the lowest free one of 0 .. FS3_MAX_BODIES - 1) and block; the body starts at the
+    // origin with the identity pose, at rest.  set_body_motion: host memory only, for the ticks enqueued afterwards; the engine
+    // does not advance the pose.
+    uint32_t add_body(const std::vector<fs_vec3>& field, uint32_t w, uint32_t h, uint32_t d, fs_vec3 extent) {
+        if (field.size() != (size_t)w * h * d) throw std::invalid_argument("add_body: field.size() != w * h * d");
+        uint32_t slot = 0;
+        check(fs3_body_create(h_, field.data(), w, h, d, extent, &slot));
+        return slot;
+    }
+    uint32_t add_body_mask(const std::vector<uint8_t>& mask, uint32_t w, uint32_t h, uint32_t d, fs_vec3 extent) {
+        if (mask.size() != (size_t)w * h * d) throw std::invalid_argument("add_body_mask: mask.size() != w * h * d");
+        uint32_t slot = 0;
+        check(fs3_body_create_from_mask(h_, mask.data(), w, h, d, extent, nullptr, &slot));
+        return slot;
+    }
+    void set_body_motion(uint32_t body, const fs3_body_motion& motion) { check(fs3_body_set_motion(h_, body, &motion)); }
+    fs3_body_motion body_motion(uint32_t body) const { fs3_body_motion m{}; check(fs3_body_get_motion(h_, body, &m)); return m; }
+    std::vector<fs_vec3> body_field(uint32_t body) {
+        uint32_t w = 0, h = 0, d = 0;
+        fs_vec3 extent{};
+        check(fs3_body_dims(h_, body, &w, &h, &d, &extent));
+        std::vector<fs_vec3> v((size_t)w * h * d);
+        check(fs3_body_download(h_, body, v.data(), v.size()));
+        return v;
+    }
+    void remove_body(uint32_t body) { check(fs3_body_destroy(h_, body)); }
+    uint32_t body_count() const { return fs3_body_count(h_); }
     // 3D surface tension: colour-field CSF with coefficient sigma and threshold tau, for the ticks enqueued afterwards.
     void set_surface_tension(float coefficient, float threshold = 0.0f) { check(fs3_set_surface_tension(h_, 1, coefficient, threshold)); }
     void clear_surface_tension() { check(fs3_set_surface_tension(h_, 0, 0.0f, 0.0f)); }

@@ -123,6 +123,19 @@ const _: () = assert!(std::mem::size_of::<Nozzle>() == 40);
 #[repr(C)] #[derive(Clone, Copy, Debug)]
 pub struct Nozzle3 { pub origin: Vec3, pub u: Vec3, pub v: Vec3, pub velocity: Vec3, pub nu: u32, pub nv: u32 }
 const _: () = assert!(std::mem::size_of::<Nozzle3>() == 56);
+/// fs3_body_motion: pose and velocity of a moving body (build extension, include/fluidsim.h "3D moving bodies"); 72 bytes.
+/// `rot`: row-major R, world = R * local; the engine checks only that it is finite.
+#[repr(C)] #[derive(Clone, Copy, Debug, PartialEq)]
+pub struct BodyMotion3 { pub centre: Vec3, pub rot: [f32; 9], pub velocity: Vec3, pub angular_velocity: Vec3 }
+const _: () = assert!(std::mem::size_of::<BodyMotion3>() == 72);
+impl Default for BodyMotion3 {
+    /// The motion of a new body: the identity pose at the origin, at rest.
+    fn default() -> Self {
+        BodyMotion3 { centre: Vec3::default(), rot: [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0], velocity: Vec3::default(), angular_velocity: Vec3::default() }
+    }
+}
+/// FS3_MAX_BODIES: the body slots of a 3D handle.
+pub const MAX_BODIES3: u32 = 8;
 /// fs3_surface_hit: one pixel of the G-buffer; 40 bytes, offsets 0/4/8/20/32/36.  `hit` 0: miss, 1: bracketed and refined, 2: the first sample was inside.
 #[repr(C)] #[derive(Clone, Copy, Default, Debug, PartialEq)]
 pub struct SurfaceHit3 { pub t: f32, pub density: f32, pub normal: Vec3, pub velocity: Vec3, pub steps: u32, pub hit: u32 }
@@ -274,6 +287,14 @@ extern "C" {
     fn fs3_collider_clear(sim: *mut fs_sim3) -> c_int;
     fn fs3_collider_dims(sim: *const fs_sim3, w: *mut u32, h: *mut u32, d: *mut u32) -> c_int;
     fn fs3_collider_download(sim: *mut fs_sim3, dst: *mut Vec3, n: usize) -> c_int;
+    fn fs3_body_create(sim: *mut fs_sim3, field_host: *const Vec3, w: u32, h: u32, d: u32, extent: Vec3, body_out: *mut u32) -> c_int;
+    fn fs3_body_create_from_mask(sim: *mut fs_sim3, mask_host: *const u8, w: u32, h: u32, d: u32, extent: Vec3, field_host: *mut Vec3, body_out: *mut u32) -> c_int;
+    fn fs3_body_set_motion(sim: *mut fs_sim3, body: u32, motion: *const BodyMotion3) -> c_int;
+    fn fs3_body_get_motion(sim: *const fs_sim3, body: u32, out: *mut BodyMotion3) -> c_int;
+    fn fs3_body_dims(sim: *const fs_sim3, body: u32, w: *mut u32, h: *mut u32, d: *mut u32, extent: *mut Vec3) -> c_int;
+    fn fs3_body_download(sim: *mut fs_sim3, body: u32, dst: *mut Vec3, n: usize) -> c_int;
+    fn fs3_body_destroy(sim: *mut fs_sim3, body: u32) -> c_int;
+    fn fs3_body_count(sim: *const fs_sim3) -> u32;
     fn fs3_set_surface_tension(sim: *mut fs_sim3, enable: c_int, coefficient: f32, threshold: f32) -> c_int;
     fn fs3_surface_tension_enabled(sim: *const fs_sim3) -> c_int;
     fn fs3_surface_tension_params(sim: *const fs_sim3, coefficient: *mut f32, threshold: *mut f32) -> c_int;
@@ -719,6 +740,41 @@ impl FluidSimulation3D {
         if !v.is_empty() { check(unsafe { fs3_collider_download(self.raw, v.as_mut_ptr(), v.len()) }); }
         v
     }
+    /// Build extension: 3D moving bodies (include/fluidsim.h).  `field`: `w * h * d` push vectors over the body's own box
+    /// `[-extent/2, extent/2]` in the body frame, the layout of `set_collider`.  Returns the slot, the lowest free one of
+    /// `0 .. MAX_BODIES3`.  Blocking.  The body starts at the origin with the identity pose, at rest.
+    pub fn add_body(&mut self, field: &[Vec3], w: u32, h: u32, d: u32, extent: Vec3) -> u32 {
+        assert_eq!(field.len(), w as usize * h as usize * d as usize);
+        let mut slot = 0u32;
+        check(unsafe { fs3_body_create(self.raw, field.as_ptr(), w, h, d, extent, &mut slot) });
+        slot
+    }
+    /// ... from a voxel mask (> 128: solid) over the body's box: `set_collider_mask`'s producer.
+    pub fn add_body_mask(&mut self, mask: &[u8], w: u32, h: u32, d: u32, extent: Vec3) -> u32 {
+        assert_eq!(mask.len(), w as usize * h as usize * d as usize);
+        let mut slot = 0u32;
+        check(unsafe { fs3_body_create_from_mask(self.raw, mask.as_ptr(), w, h, d, extent, std::ptr::null_mut(), &mut slot) });
+        slot
+    }
+    /// Pose and velocity of a body for the ticks enqueued afterwards; host memory only.  The engine does not advance the pose.
+    pub fn set_body_motion(&mut self, body: u32, motion: &BodyMotion3) { check(unsafe { fs3_body_set_motion(self.raw, body, motion) }); }
+    pub fn body_motion(&self, body: u32) -> BodyMotion3 { let mut m = BodyMotion3::default(); check(unsafe { fs3_body_get_motion(self.raw, body, &mut m) }); m }
+    /// ((w, h, d), extent) of a body.
+    pub fn body_dims(&self, body: u32) -> ((u32, u32, u32), Vec3) {
+        let (mut w, mut h, mut d, mut e) = (0, 0, 0, Vec3::default());
+        check(unsafe { fs3_body_dims(self.raw, body, &mut w, &mut h, &mut d, &mut e) });
+        ((w, h, d), e)
+    }
+    /// A body's field.  Blocking.
+    pub fn body_field(&mut self, body: u32) -> Vec<Vec3> {
+        let ((w, h, d), _) = self.body_dims(body);
+        let mut v = vec![Vec3::default(); w as usize * h as usize * d as usize];
+        check(unsafe { fs3_body_download(self.raw, body, v.as_mut_ptr(), v.len()) });
+        v
+    }
+    /// Destroys a body and frees its slot; the other bodies keep theirs.  Blocking.
+    pub fn remove_body(&mut self, body: u32) { check(unsafe { fs3_body_destroy(self.raw, body) }); }
+    pub fn body_count(&self) -> u32 { unsafe { fs3_body_count(self.raw) } }
     /// Build extension: 3D surface tension (include/fluidsim.h), colour-field CSF with coefficient sigma and threshold tau,
     /// for the ticks enqueued afterwards.
     pub fn set_surface_tension(&mut self, coefficient: f32, threshold: f32) { check(unsafe { fs3_set_surface_tension(self.raw, 1, coefficient, threshold) }); }

@@ -914,6 +914,77 @@ fs_status fs3_collider_clear(fs_sim3* sim);
 fs_status fs3_collider_dims(const fs_sim3* sim, uint32_t* w, uint32_t* h, uint32_t* d);      /* 0,0,0 when none */
 fs_status fs3_collider_download(fs_sim3* sim, fs_vec3* dst, size_t n);                       /* n == w*h*d; FS_ERR_INVALID when none */
 
+/* ------------------------------------------------ 3D moving bodies (build extension, opt-in by being created) */
+/* Kinematic rigid bodies for the 3D step: up to FS3_MAX_BODIES per handle, each a small W x H x D voxel field of push vectors
+ * (the layout of "3D colliders": field[(k * H + j) * W + i], a zero vector is free space) over the body's own box
+ * [-extent/2, extent/2] in the BODY frame, with a pose and a velocity the host sets per step.  The fluid feels the body (one-way
+ * coupling): the engine neither integrates the pose nor computes forces on the body.  A handle without a body launches exactly
+ * the kernels it launched before and computes the same bits.
+ *
+ * With bodies present, a step is B_7(...B_0(C(step(state)))): the static collider C first if one is set, then the operator of
+ * each existing body in ascending slot order, on the position p and the velocity v the step is about to store.  All arithmetic is
+ * f32 without contraction, `/` and `sqrt` are correctly rounded, u32_sat as in "3D colliders"; b.a are the half-bounds of the
+ * step and damping the tick's damping_factor.  Per body: c = centre, rij = rot[3*i + j] (world = R * local), u = velocity,
+ * w = angular_velocity, hb.a = extent.a * 0.5f (on the host, once), W_x = W, W_y = H, W_z = D.
+ *     d.a  = p.a - c.a
+ *     q.x  = (r00*d.x + r10*d.y) + r20*d.z                                   (q = R^T d: the body frame)
+ *     q.y  = (r01*d.x + r11*d.y) + r21*d.z
+ *     q.z  = (r02*d.x + r12*d.y) + r22*d.z
+ *     if !(fabsf(q.x) <= hb.x && fabsf(q.y) <= hb.y && fabsf(q.z) <= hb.z): unchanged      (NaN: unchanged; on a face: inside)
+ *     ia = min(u32_sat(((q.a + hb.a) / extent.a) * (float)W_a), W_a - 1)
+ *     g  = field[(iz * H + iy) * W + ix];   if g.x == 0 && g.y == 0 && g.z == 0: unchanged
+ *     len = sqrt((g.x*g.x + g.y*g.y) + g.z*g.z);   if !(len > 0): unchanged
+ *     f.x = (r00*g.x + r01*g.y) + r02*g.z;  f.y = (r10*g.x + r11*g.y) + r12*g.z;  f.z = (r20*g.x + r21*g.y) + r22*g.z
+ *     n.a = f.a / len
+ *     p.a = p.a + f.a
+ *     s.a = p.a - c.a                                                        (the pushed position)
+ *     us.x = u.x + (w.y*s.z - w.z*s.y);  us.y = u.y + (w.z*s.x - w.x*s.z);  us.z = u.z + (w.x*s.y - w.y*s.x)
+ *     r.a = v.a - us.a
+ *     rn  = (r.x*n.x + r.y*n.y) + r.z*n.z
+ *     k   = (1.0f - damping) * rn
+ *     v.a = us.a + (r.a - k*n.a)
+ *     per axis, in x, y, z order: if fabsf(p.a) > b.a { p.a = b.a * sign(p.a); v.a *= -1.0f * damping }
+ * predicted_position, density and grid are not touched.  FS_MATH_TOLERANCE handles run the same IEEE operator, as they do C.
+ * The engine does not check that rot is a rotation, only that it is finite.
+ *
+ * fs3_body_create: a field made by the caller.  fs3_body_create_from_mask: the producer of "3D colliders" on the body's box —
+ * the same three passes, the same tie rules, s_a = extent.a / (float)W_a; `field_host` (may be NULL) receives the field.
+ * *body_out is the lowest free slot in 0 .. FS3_MAX_BODIES - 1; slots are stable (destroying body 1 leaves body 2 as body 2).  A
+ * new body has the identity pose at the origin and zero velocities.
+ *
+ * Checks, in this order, all FS_ERR_INVALID; a refused call changes nothing:
+ *  1. NULL handle.
+ *  2. NULL array or out pointer (field, mask, body_out, motion, dst, or one of the four of fs3_body_dims).
+ *  3. An extent (w, h, d) of 0 or above 1024.
+ *  4. A component of the box `extent` that is not finite and > 0.
+ *  5. A non-finite field component, or a mask without a free voxel.
+ *  6. No free slot.
+ *  7. The per-body calls: a slot that holds no body (fs3_body_download then: n != w * h * d).
+ *  8. fs3_body_set_motion: any non-finite float.
+ *
+ * create*, download and destroy are blocking and ordered on fs3_stream(sim), exactly as the fs3_collider_* calls are; destroy
+ * synchronises before freeing, because steps in flight read the field.  fs3_body_set_motion touches host memory only: a step takes
+ * every body's motion by value when it is enqueued, so setting a different pose before each of several un-synchronised steps is
+ * the intended use.  The pose holds until it is set again.  Nothing here makes sampling, rendering or extraction stale; particles
+ * emitted inside a body are pushed by the next step.  The time of the operators falls inside FS_PASS_FORCE.  FS_ABI_VERSION is
+ * unchanged.  See DESIGN.md §23. */
+#define FS3_MAX_BODIES 8
+typedef struct fs3_body_motion {
+    fs_vec3 centre;            /* world position of the body box's centre */
+    float   rot[9];            /* row-major R, world = R * local; the caller supplies a rotation, the engine checks only finiteness */
+    fs_vec3 velocity;          /* of the centre, world units per second */
+    fs_vec3 angular_velocity;  /* world frame, rad/s */
+} fs3_body_motion;
+fs_status fs3_body_create(fs_sim3* sim, const fs_vec3* field_host, uint32_t w, uint32_t h, uint32_t d, fs_vec3 extent, uint32_t* body_out);
+fs_status fs3_body_create_from_mask(fs_sim3* sim, const uint8_t* mask_host, uint32_t w, uint32_t h, uint32_t d, fs_vec3 extent,
+                                    fs_vec3* field_host /* may be NULL */, uint32_t* body_out);
+fs_status fs3_body_set_motion(fs_sim3* sim, uint32_t body, const fs3_body_motion* motion);
+fs_status fs3_body_get_motion(const fs_sim3* sim, uint32_t body, fs3_body_motion* out);
+fs_status fs3_body_dims(const fs_sim3* sim, uint32_t body, uint32_t* w, uint32_t* h, uint32_t* d, fs_vec3* extent);
+fs_status fs3_body_download(fs_sim3* sim, uint32_t body, fs_vec3* dst, size_t n);            /* n == w*h*d */
+fs_status fs3_body_destroy(fs_sim3* sim, uint32_t body);
+uint32_t  fs3_body_count(const fs_sim3* sim);                                                /* 0 for a NULL handle */
+
 /* ------------------------------------------------ 3D surface tension (build extension, opt-in) */
 /* The 3D form of the 2D step's opt-in surface tension above: a colour-field continuum-surface-force pass (Mueller, Charypar &
  * Gross 2003, §4.4) with the 3D poly6 kernel of the 3D step, W = C (h^2 - r^2)^3, C = 315/(64 pi h^9).  Enabled, every step runs

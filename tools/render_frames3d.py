@@ -1,6 +1,9 @@
 """Render a few frames of the 3D dam break to PNG through the ray-marched G-buffer, headless:
   python tools/render_frames3d.py [n] [frame,frame,...] [outdir] [width] [height] [--box x0,y0,z0,x1,y1,z1[,voxels]]
-                                  [--surface-tension SIGMA[,TAU]] [--dye] [--faucet K[,NU,NV]]
+                                  [--surface-tension SIGMA[,TAU]] [--dye] [--faucet K[,NU,NV]] [--paddle [AMPLITUDE,PERIOD]]
+--paddle: a moving rigid body: a plate across the tank, as high and deep as the box and 3 h thick, that swings along
+x about the middle of the tank, x(t) = AMPLITUDE * sin(2 pi t / PERIOD) (default a twentieth of the box's width, 2 s); its pose and
+velocity are set before every step.  The dam breaks against it and it keeps making waves; the plate itself is not drawn.
 --faucet: a particle count that grows: the handle reserves room for twice its particles and a nozzle under the
 ceiling, above the dry half of the tank, emits a layer of NU x NV particles (default 16 x 16, one spacing apart, falling at 3 m/s)
 every K steps until the capacity is reached.  With --box the jet fills a tank that has an obstacle in it.
@@ -29,6 +32,12 @@ if "--faucet" in sys.argv:
     faucet = [int(x) for x in sys.argv[k + 1].split(",")]
     faucet = (faucet + [16, 16])[:3] if len(faucet) == 1 else faucet
     del sys.argv[k:k + 2]
+paddle = None
+if "--paddle" in sys.argv:
+    k = sys.argv.index("--paddle")
+    given = k + 1 < len(sys.argv) and "," in sys.argv[k + 1]
+    paddle = [float(x) for x in sys.argv[k + 1].split(",")] if given else []
+    del sys.argv[k:k + (2 if given else 1)]
 dye = "--dye" in sys.argv
 if dye:
     sys.argv.remove("--dye")
@@ -46,6 +55,12 @@ if box is not None:
     shape = (w, max(1, round(w * sy / sx)), max(1, round(w * sz / sx)))
     sim.set_collider_mask(g.box_mask3d((sx, sy, sz), shape, box[0:3], box[3:6]))
     print("collider", sim.collider_dims, flush=True)
+if paddle is not None:
+    amp, period = paddle if paddle else (0.05 * sx, 2.0)
+    mask = np.full((1, 1, 5), 255, dtype=np.uint8)      # five slices along x, solid but the two end slices
+    mask[:, :, [0, -1]] = 0
+    plate = sim.add_body_mask(mask, (5 * st.smoothing_radius, sy, sz))
+    print("paddle: body", plate, sim.body_dims(plate), "amplitude", amp, "period", period, flush=True)
 if tension is not None:
     sim.set_surface_tension(tension[0], tension[1] if len(tension) > 1 else 1.0)
     print("surface tension", sim.surface_tension_params, flush=True)
@@ -67,6 +82,10 @@ for f in frames:
     while done < f:
         if faucet is not None and done % faucet[0] == 0 and sim.particle_count + faucet[1] * faucet[2] <= sim.capacity:
             sim.emit_nozzle(**nozzle)
+        if paddle is not None:
+            om = 2.0 * np.pi / period
+            t = (done + 1) * tick.delta                 # the pose at the end of the step that is about to run
+            sim.set_body_motion(plate, (amp * np.sin(om * t), 0.0, 0.0), velocity=(amp * om * np.cos(om * t), 0.0, 0.0))
         sim.tick(tick); done += 1
     if faucet is not None:
         print("frame", f, "particles", sim.particle_count, "of", sim.capacity, flush=True)
