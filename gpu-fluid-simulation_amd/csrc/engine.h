@@ -2,7 +2,8 @@
 // features, the step parameters, and the device check and create-time proofs (also used by the 3D handle's files through
 // engine_3d.h).  The handle's files:
 // engine.hip (life cycle, step, transfers, renderer hand-off), engine_features.hip (surface tension, particle tracking),
-// engine_query.hip (density render, field sampling), engine_count.hip (a particle count that changes at run time),
+// engine_query.hip (density render, field sampling), engine_count.hip (a particle count that changes at run time; what it
+// shares with the 3D handle's engine_3d_count.hip: engine_count.h, and Tracking and RemoveScratch below),
 // engine_selftest.hip (self-tests, read-outs), engine_slab.hip (the multi-GPU slab handles).  Internal: include/fluidsim.h is the interface.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -109,6 +110,7 @@ struct Tracking {
     int channels = -1;              // -1: off
     int alloc_channels = 0;         // channels the attr arrays were allocated for
     int cur = 0;
+    uint32_t next_id = 0;           // while on: the live count at enable, then + 1 per emitted particle, wrapping
     bool on() const { return channels >= 0; }
     // of the last enqueued step
     uint32_t* ids() const { return id[cur].p; }
@@ -118,6 +120,12 @@ struct Tracking {
         if (!on()) return;
         launch_track_carry(st, n, channels, pairs, id[cur].p, id[cur ^ 1].p, attr[cur].p, attr[cur ^ 1].p, capacity);
         cur ^= 1;
+    }
+    // Tracking's share of an emission of m records at slot `first`: the next m ids, +0.0f in every channel.
+    void emitted(hipStream_t st, uint32_t first, uint32_t m, uint32_t capacity) {
+        if (!on()) return;
+        launch_emit_track(st, m, next_id, ids() + first, channels, channel(0, capacity) + first, capacity);
+        next_id += m;               // wraps
     }
     // fs_track_enable / fs3_track_enable on the current device: allocates on first use, then id[i] = i and every channel +0.0f on
     // `st` — ordered after every step already enqueued, before every step enqueued from now on.
@@ -149,6 +157,7 @@ struct Tracking {
         FS_HIP(hipGetLastError());
         if (ch && n) FS_HIP(hipMemsetAsync(attr[0].p, 0, (size_t)ch * capacity * sizeof(float), st));
         channels = ch;
+        next_id = n;                // the ids in use are 0 .. n - 1: emission goes on from there
         return FS_OK;
     }
     // ids (is_attr = false) or one channel, host <-> the arrays of the last enqueued step, on the current device.  Blocking; the
@@ -182,11 +191,9 @@ struct Tracking {
     }
 };
 
-// A particle count that changes at run time (build extension; single-domain handles): fs_reserve, fs_emit_*,
-// fs_remove_* in engine_count.hip.  What the handle keeps for it: the id of the next emitted particle and the scratch of a
-// removal, allocated by the first one for `capacity` slots and released by fs_reserve.  Never called: no allocation, no launch.
-struct CountChange {
-    uint32_t next_id = 0;           // while tracking is on: the live count at fs_track_enable, then + 1 per emitted particle (wrapping)
+// Scratch of a removal (fs_remove_* in engine_count.hip, fs3_remove_* in engine_3d_count.hip), allocated by
+// the first one for `capacity` slots and released by fs_reserve / fs3_reserve.  Never called: no allocation, no launch.
+struct RemoveScratch {
     DevArray<uint8_t> flags;        // per slot: removed
     DevArray<uint32_t> sums;        // per workgroup of the flags pass: survivors, then offsets; the total behind them
     fs_status reserve(uint32_t capacity) {
@@ -297,7 +304,7 @@ struct fs_sim : fsd::HandleQueues, fsd::ParticleArrays {
     uint32_t aos_tick = 0xFFFFFFFFu;   // tick whose state the AoS view holds (only meaningful with aos_live)
     fsd::SurfaceTension st;         // the opt-in features' state: one line each in enqueue_step
     fsd::Tracking trk;
-    fsd::CountChange count;         // (not a per-step feature: emission and removal happen between steps)
+    fsd::RemoveScratch removal;     // (not a per-step feature: emission and removal happen between steps)
     // what walks the cell table off the step path (engine_query.hip: fs_render_density; field sampling): the records
     // and the cell table belong together — a step has been enqueued since create and since the last fs_upload_particles /
     // fs_upload_start_indices

@@ -2,8 +2,9 @@
 // Params3 both the step and the queries start from, and the few helpers more than one of them needs.  The handle's files:
 // engine_3d.hip (lattice, life cycle, step, getters, transfers, timing), engine_3d_features.hip (what the step enqueues for:
 // colliders, moving bodies, surface tension, tracking), engine_3d_query.hip (everything behind sample_stale: sampling, rendering, extraction),
-// engine_3d_count.hip (a particle count that changes at run time: reserve, emit, remove).
-// From the 2D engine (engine.h): the device check, the create-time proofs, the owners, the sort policy and Tracking.
+// engine_3d_count.hip (a particle count that changes at run time: reserve, emit, remove; what it shares with the 2D handle's
+// engine_count.hip: engine_count.h).
+// From the 2D engine (engine.h): the device check, the create-time proofs, the owners, the sort policy, Tracking and RemoveScratch.
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -136,20 +137,7 @@ struct fs_sim3 {
     } tension;
     // The opt-in particle tracking: the 2D engine's owner (engine.h), stride cap; never enabled: no allocation, no launch.
     fsd::Tracking trk;
-    uint32_t next_id = 0;        // the id of the next particle emitted while tracking is on: the live count at fs3_track_enable
-    // Scratch of a removal, allocated by the first one for `cap` slots and released by fs3_reserve.
-    struct RemoveScratch {
-        fsd::DevArray<uint8_t> flags;    // per slot: removed
-        fsd::DevArray<uint32_t> sums;    // per workgroup of the flags pass: survivors, then offsets; the total behind them
-        fs_status reserve(uint32_t cap) {
-            if (flags.p) return FS_OK;
-            if (flags.alloc(cap) == hipSuccess && sums.alloc((size_t)fsd::remove3_workgroups(cap) + 1) == hipSuccess) return FS_OK;
-            (void)hipGetLastError();
-            release();
-            return fsd::fail(FS_ERR_OOM, "removal: device scratch");
-        }
-        void release() { flags.release(); sums.release(); }
-    } removal;
+    fsd::RemoveScratch removal;  // scratch of a removal: the 2D engine's owner too
 
     // the arrays as the launchers see them (fs_3d.h): the force pass writes the new positions into the spare buffer
     fsd::Arrays3 arrays() const {

@@ -1,78 +1,39 @@
 // engine_3d_count.hip — a particle count that changes at run time (include/fluidsim.h "3D particle count"; the
-// handle: engine_3d.h, the device passes: kernels_count3d.hip): fs3_reserve grows every per-slot array, fs3_emit_* append at
+// handle: engine_3d.h, the device passes: kernels_count.hip): fs3_reserve grows every per-slot array, fs3_emit_* append at
 // [n, n + m), fs3_remove_* compact.  The live count is always known to the host: the step's pass chain and its kernels are
-// untouched, each step simply takes the n of its enqueue.
+// untouched, each step simply takes the n of its enqueue.  The 2D handle's counterpart: engine_count.hip; what the two share:
+// engine_count.h.
 #include <hip/hip_runtime.h>
 
 #include "engine_3d.h"
+#include "engine_count.h"
 
-using fsd::DevArray;
-using fsd::fail;
-using fsd::sort_health3;
+using namespace fsd;
 namespace {
-const uint32_t MAX_SLOTS = 1u << 28;       // as fs3_create: 32-bit byte offsets
-
-uint32_t padded(uint32_t n) { uint32_t p2 = 1; while (p2 < n) p2 <<= 1; return p2; }
-
 // The count becomes new_n (2 <= new_n <= cap, != n), the state arrays already hold it (or will, in stream order).  What every
 // change shares: the queries and surface tension's forces no longer belong to the state, and the sort's bookkeeping follows
-// (DESIGN.md §21).  Inside one padded size the plan words stay where they are and the change is an upload to the policy.
-// Across one — and on every shrink, which blocks anyway — the plan words move: the stream is drained, the time-out word is
-// read at its old place (the latch survives), all of `dirty` goes back to its state at create, and the policy starts over.
+// (sort_count_changed).
 fs_status count_changed(fs_sim3* s, uint32_t new_n) {
-    const bool moved = padded(new_n) != padded(s->n) || new_n < s->n;
-    fs_status health = FS_OK;
-    if (moved) {
-        FS_HIP(hipStreamSynchronize(s->stream));
-        health = sort_health3(s);                         // with the old count; latches SortPolicy::dead
-        FS_HIP(hipMemsetAsync(s->dirty.p, 0, s->dirty.n * 4, s->stream));
-        s->sortp.resized();
-    } else {
-        s->sortp.touched();
-    }
+    const fs_status health = sort_count_changed(s->stream, s->sortp, s->dirty, s->n, new_n);
     s->n = new_n;
     s->sample_stale = true;
     s->tension.valid = false;
     return health;
 }
 
-// Tracking's share of an emission of m records at slot n: the next m ids, +0.0f in every channel.
-void track_emitted(fs_sim3* s, uint32_t m) {
-    if (!s->trk.on()) return;
-    fsd::launch3_emit_track(s->stream, m, s->next_id, s->trk.ids() + s->n, s->trk.channels, s->trk.channel(0, s->cap) + s->n, s->cap);
-    s->next_id += m;                                      // wraps
-}
-
-// device -> device on the handle's stream, `count` elements
-template <class T>
-hipError_t carry(hipStream_t st, DevArray<T>& to, const DevArray<T>& from, size_t count) {
-    return count && from.p ? hipMemcpyAsync(to.p, from.p, count * sizeof(T), hipMemcpyDeviceToDevice, st) : hipSuccess;
-}
-
-// The removal both forms end in: `flags` (device, n bytes; box: written by the flags pass) decide.  Blocking.
-fs_status remove3(fs_sim3* s, const float3* lo, const float3* hi, uint32_t* removed) {
-    using namespace fsd;
-    const uint32_t n = s->n, nwg = remove3_workgroups(n);
-    launch3_remove_count(s->stream, n, s->pos.p, lo, hi, s->removal.flags.p, s->removal.sums.p);
-    FS_HIP(hipGetLastError());
+// The removal both forms end in: removal.flags (device, n bytes) and removal.sums are filled.  Blocking.
+fs_status remove3(fs_sim3* s, uint32_t* removed) {
+    const uint32_t n = s->n;
     uint32_t keep = 0;
-    FS_HIP(hipMemcpyAsync(&keep, s->removal.sums.p + nwg, 4, hipMemcpyDeviceToHost, s->stream));
-    FS_HIP(hipStreamSynchronize(s->stream));
-    FS_TRY(sort_health3(s));
+    FS_TRY(removal_survivors(s->stream, s->removal, n, &s->sortp, s->dirty.p, &keep));
     if (keep == n) return FS_OK;                          // nothing matched: nothing changes, queries stay valid
-    if (keep < 2u) return fail(FS_ERR_INVALID, "removal: fewer than 2 particles would survive");
     // out of place: positions and velocities into the spare arrays, pred (+ density) and keys into the AoS staging buffer
     // (48 B per slot: cap float4, then cap words) and back; ids and channels into tracking's other set
     Compact3 C{};
     C.pos = s->pos.p; C.vel = s->vel.p; C.pred = s->pred.p; C.key = s->key.p;
     C.pos_out = s->pos_s.p; C.vel_out = s->vel_s.p;
     C.pred_out = (float4*)s->aos.p; C.key_out = (uint32_t*)((float4*)s->aos.p + s->cap);
-    Tracking& T = s->trk;
-    if (T.on()) {
-        C.ids = T.id[T.cur].p; C.ids_out = T.id[T.cur ^ 1].p;
-        C.attr = T.attr[T.cur].p; C.attr_out = T.attr[T.cur ^ 1].p;
-        C.channels = T.channels; C.stride = s->cap;
-    }
+    compact_tracking(&C, s->trk, s->cap);
     launch3_remove_scatter(s->stream, n, s->removal.flags.p, s->removal.sums.p, C);
     FS_HIP(hipGetLastError());
     FS_HIP(hipMemcpyAsync(s->pred.p, C.pred_out, (size_t)keep * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
@@ -80,7 +41,7 @@ fs_status remove3(fs_sim3* s, const float3* lo, const float3* hi, uint32_t* remo
     FS_HIP(hipStreamSynchronize(s->stream));
     std::swap(s->pos, s->pos_s);
     std::swap(s->vel, s->vel_s);
-    if (T.on()) T.cur ^= 1;
+    if (s->trk.on()) s->trk.cur ^= 1;
     const fs_status r = count_changed(s, keep);
     FS_HIP(hipStreamSynchronize(s->stream));
     *removed = n - keep;
@@ -91,7 +52,7 @@ fs_status remove3(fs_sim3* s, const float3* lo, const float3* hi, uint32_t* remo
 extern "C" {
 
 uint32_t fs3_capacity(const fs_sim3* s) { return s ? s->cap : 0; }
-uint32_t fs3_track_next_id(const fs_sim3* s) { return (s && s->trk.on()) ? s->next_id : 0; }
+uint32_t fs3_track_next_id(const fs_sim3* s) { return (s && s->trk.on()) ? s->trk.next_id : 0; }
 
 fs_status fs3_reserve(fs_sim3* s, uint32_t capacity) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
@@ -99,21 +60,18 @@ fs_status fs3_reserve(fs_sim3* s, uint32_t capacity) {
     if (capacity <= s->cap) return FS_OK;
     FS_HIP(hipSetDevice(s->device));
     const size_t cap = capacity, n = s->n;
-    const uint32_t old_cap = s->cap;
-    fsd::Tracking& T = s->trk;
     // everything new first: on failure the locals go and the handle is what it was
     DevArray<float4> pos, vel, pos_s, vel_s, pred, st;
-    DevArray<uint32_t> key, dirty, id[2];
-    DevArray<fsd::u64> pairs, masks;
+    DevArray<uint32_t> key, dirty;
+    DevArray<u64> pairs, masks;
     DevArray<fs3_particle> aos;
-    DevArray<float> attr[2];
+    TrackingGrowth G;
     hipError_t e = hipSuccess;
     auto ok = [&e](hipError_t r) { e = r; return r == hipSuccess; };
     (void)(ok(pos.alloc(cap)) && ok(vel.alloc(cap)) && ok(pos_s.alloc(cap)) && ok(vel_s.alloc(cap)) && ok(pred.alloc(cap + FS_PRED_SLACK)) &&
-           ok(key.alloc(cap)) && ok(pairs.alloc(cap)) && ok(dirty.alloc(fsd::sort_tile_count(capacity))) && ok(aos.alloc(cap)) &&
+           ok(key.alloc(cap)) && ok(pairs.alloc(cap)) && ok(dirty.alloc(sort_tile_count(capacity))) && ok(aos.alloc(cap)) &&
            ok(masks.alloc(s->masks.p ? 18 * cap : 0)) && ok(st.alloc(s->tension.st.p ? cap : 0)) &&
-           ok(id[0].alloc(T.id[0].p ? cap : 0)) && ok(id[1].alloc(T.id[0].p ? cap : 0)) &&
-           ok(attr[0].alloc((size_t)T.alloc_channels * cap)) && ok(attr[1].alloc((size_t)T.alloc_channels * cap)));
+           ok(G.alloc(s->trk, cap)));
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(FS_ERR_OOM, "reserve: device arrays");
@@ -129,11 +87,7 @@ fs_status fs3_reserve(fs_sim3* s, uint32_t capacity) {
     if (e == hipSuccess) e = carry(q, pred, s->pred, n);
     if (e == hipSuccess) e = carry(q, key, s->key, n);
     if (e == hipSuccess) e = carry(q, st, s->tension.st, n);
-    if (T.on()) {                                                          // the set in use; channel c moves from c * old_cap to c * cap
-        if (e == hipSuccess) e = carry(q, id[T.cur], T.id[T.cur], n);
-        for (int c = 0; c < T.channels && e == hipSuccess && n; ++c)
-            e = hipMemcpyAsync(attr[T.cur].p + (size_t)c * cap, T.attr[T.cur].p + (size_t)c * old_cap, n * sizeof(float), hipMemcpyDeviceToDevice, q);
-    }
+    if (e == hipSuccess) e = G.carry_from(q, s->trk, n, s->cap, cap);
     const hipError_t es = hipStreamSynchronize(q);                         // before anything is freed, whatever happened
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return fail(FS_ERR_DEVICE, hipGetErrorString(e));
@@ -141,8 +95,7 @@ fs_status fs3_reserve(fs_sim3* s, uint32_t capacity) {
     s->key = std::move(key); s->pairs = std::move(pairs); s->dirty = std::move(dirty); s->aos = std::move(aos);
     if (masks.p) s->masks = std::move(masks);
     if (st.p) s->tension.st = std::move(st);
-    if (id[0].p) { T.id[0] = std::move(id[0]); T.id[1] = std::move(id[1]); }
-    if (attr[0].p) { T.attr[0] = std::move(attr[0]); T.attr[1] = std::move(attr[1]); }
+    G.commit(s->trk);
     s->removal.release();                                                  // sized by the capacity: the next removal allocates it again
     s->cap = capacity;
     return sort_health3(s);
@@ -155,12 +108,12 @@ fs_status fs3_emit_particles(fs_sim3* s, const fs3_particle* src, size_t n) {
     if (n > (size_t)(s->cap - s->n)) return fail(FS_ERR_INVALID, "emit: count + n exceeds the capacity (fs3_reserve first)");
     FS_HIP(hipSetDevice(s->device));
     // as fs3_upload_particles stores them, at slot `count`: through the staging buffer, which has cap >= n slots
-    fsd::Arrays3 A = s->arrays();
+    Arrays3 A = s->arrays();
     A.pos += s->n; A.pred += s->n; A.vel += s->n; A.key += s->n;
     FS_HIP(hipMemcpyAsync(s->aos.p, src, n * sizeof(fs3_particle), hipMemcpyHostToDevice, s->stream));
-    fsd::launch3_import(s->stream, (uint32_t)n, A);
+    launch3_import(s->stream, (uint32_t)n, A);
     FS_HIP(hipGetLastError());
-    track_emitted(s, (uint32_t)n);
+    s->trk.emitted(s->stream, s->n, (uint32_t)n, s->cap);
     FS_HIP(hipStreamSynchronize(s->stream));               // `src` belongs to the caller again
     return count_changed(s, s->n + (uint32_t)n);
 }
@@ -175,13 +128,13 @@ fs_status fs3_emit_nozzle(fs_sim3* s, const fs3_nozzle* z) {
         if (!std::isfinite(a.x) || !std::isfinite(a.y) || !std::isfinite(a.z)) return fail(FS_ERR_INVALID, "nozzle: non-finite component");
     if (m > (uint64_t)(s->cap - s->n)) return fail(FS_ERR_INVALID, "emit: count + nu * nv exceeds the capacity (fs3_reserve first)");
     FS_HIP(hipSetDevice(s->device));
-    fsd::Nozzle3 Z;
+    Nozzle3 Z;
     Z.origin = make_float3(z->origin.x, z->origin.y, z->origin.z); Z.u = make_float3(z->u.x, z->u.y, z->u.z);
     Z.v = make_float3(z->v.x, z->v.y, z->v.z); Z.velocity = make_float3(z->velocity.x, z->velocity.y, z->velocity.z);
     Z.nu = z->nu; Z.nv = z->nv;
-    fsd::launch3_emit_nozzle(s->stream, Z, s->n, s->arrays());
+    launch3_emit_nozzle(s->stream, Z, s->n, s->arrays());
     FS_HIP(hipGetLastError());
-    track_emitted(s, (uint32_t)m);
+    s->trk.emitted(s->stream, s->n, (uint32_t)m, s->cap);
     return count_changed(s, s->n + (uint32_t)m);
 }
 
@@ -190,8 +143,9 @@ fs_status fs3_remove_in_box(fs_sim3* s, const fs_vec3* lo, const fs_vec3* hi, ui
     if (!s || !lo || !hi || !removed) return fail(FS_ERR_INVALID, "null argument");
     FS_HIP(hipSetDevice(s->device));
     FS_TRY(s->removal.reserve(s->cap));
-    const float3 l = make_float3(lo->x, lo->y, lo->z), h = make_float3(hi->x, hi->y, hi->z);
-    return remove3(s, &l, &h, removed);
+    launch3_remove_box(s->stream, s->n, s->pos.p, make_float3(lo->x, lo->y, lo->z), make_float3(hi->x, hi->y, hi->z), s->removal.flags.p,
+                            s->removal.sums.p);
+    return remove3(s, removed);
 }
 
 fs_status fs3_remove_flagged(fs_sim3* s, const uint8_t* flags, size_t n, uint32_t* removed) {
@@ -201,7 +155,8 @@ fs_status fs3_remove_flagged(fs_sim3* s, const uint8_t* flags, size_t n, uint32_
     FS_HIP(hipSetDevice(s->device));
     FS_TRY(s->removal.reserve(s->cap));
     FS_HIP(hipMemcpyAsync(s->removal.flags.p, flags, n, hipMemcpyHostToDevice, s->stream));
-    return remove3(s, nullptr, nullptr, removed);
+    launch_remove_count_flags(s->stream, s->n, s->removal.flags.p, s->removal.sums.p);
+    return remove3(s, removed);
 }
 
 }  // extern "C"

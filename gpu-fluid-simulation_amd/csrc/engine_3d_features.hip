@@ -275,7 +275,6 @@ fs_status fs3_track_enable(fs_sim3* s, int channels) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
     FS_HIP(hipSetDevice(s->device));
     FS_TRY(s->trk.enable(s->stream, s->n, s->cap, channels));
-    s->next_id = s->n;              // the ids in use are 0 .. n - 1: emission goes on from there
     return FS_OK;
 }
 

@@ -1,22 +1,19 @@
 // engine_count.hip — a particle count that changes at run time on the 2D handle (include/fluidsim.h "2D particle count",
-// DESIGN.md §22; the handle: engine.h, the device passes: kernels_count.hip and, where no dimension is in them,
-// kernels_count3d.hip): fs_reserve grows every per-slot array, fs_emit_* append at [n, n + m), fs_remove_* compact.  The live
-// count is always known to the host: the step's pass chain and its kernels are untouched, each step simply takes the n of its
-// enqueue.  The 3D handle's counterpart: engine_3d_count.hip.
+// DESIGN.md §22; the handle: engine.h, the device passes: kernels_count.hip): fs_reserve grows every per-slot array, fs_emit_*
+// append at [n, n + m), fs_remove_* compact.  The live count is always known to the host: the step's pass chain and its kernels
+// are untouched, each step simply takes the n of its enqueue.  The 3D handle's counterpart: engine_3d_count.hip; what the two
+// share: engine_count.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <utility>
 
-#include "engine.h"
+#include "engine_count.h"
 
 using namespace fsd;
 namespace {
-const uint32_t MAX_SLOTS = 1u << 28;       // as fs_create_ex: 32-bit byte offsets
-
-uint32_t padded(uint32_t n) { uint32_t p2 = 1; while (p2 < n) p2 <<= 1; return p2; }
-
 const char* const SLAB = "slab handle: its particle count belongs to the exchange";
+
+bool bitonic(const fs_sim* s) { return s->opts.sort_mode == FS_SORT_BITONIC; }
 
 // State that is not at home: after a step the keys are the high words of `pairs` and, in strict / ulp mode,
 // the densities are rho2.x.  Before a record is appended (its grid and density would be lost at the next read-out) or the
@@ -30,22 +27,12 @@ void bring_home(fs_sim* s) {
 
 // The count becomes new_n (2 <= new_n <= capacity, != n), the state arrays already hold it (or will, in stream order).  What
 // every change shares: the queries and surface tension's forces no longer belong to the state, a registered hand-off's view is
-// re-materialised on demand, and the bitonic sort's bookkeeping follows (unchanged).  Inside one padded size the
-// plan words stay where they are and the change is an upload to the policy.  Across one — and on every shrink, which blocks
-// anyway — the plan words move: the stream is drained, the time-out word is read at its old place (the latch survives), all of
-// `sort_dirty` goes back to its state at create, and the policy starts over.  The counting sort keeps no word whose place
-// depends on the count (its scratch is laid out by the capacity): it never waits.
+// re-materialised on demand, and the bitonic sort's bookkeeping follows (sort_count_changed).  The counting sort keeps no word
+// whose place depends on the count (its scratch is laid out by the capacity): it never waits.
 fs_status count_changed(fs_sim* s, uint32_t new_n) {
     fs_status health = FS_OK;
-    const bool bitonic = s->opts.sort_mode == FS_SORT_BITONIC;
-    if (bitonic && (padded(new_n) != padded(s->n) || new_n < s->n)) {
-        FS_HIP(hipStreamSynchronize(s->stream));
-        health = sort_health(s);                          // with the old count; latches SortPolicy::dead
-        FS_HIP(hipMemsetAsync(s->sort_dirty.p, 0, s->sort_dirty.n * 4, s->stream));
-        s->sortp.resized();
-    } else {
-        s->sortp.touched();
-    }
+    if (bitonic(s)) health = sort_count_changed(s->stream, s->sortp, s->sort_dirty, s->n, new_n);
+    else s->sortp.touched();
     s->n = new_n;
     s->walk_ready = false;
     s->st.valid = false;
@@ -53,30 +40,12 @@ fs_status count_changed(fs_sim* s, uint32_t new_n) {
     return health;
 }
 
-// Tracking's share of an emission of m records at slot n: the next m ids, +0.0f in every channel.
-void track_emitted(fs_sim* s, uint32_t m) {
-    if (!s->trk.on()) return;
-    launch_emit_track(s->stream, m, s->count.next_id, s->trk.ids() + s->n, s->trk.channels, s->trk.channel(0, s->capacity) + s->n,
-                      s->capacity);
-    s->count.next_id += m;                                // wraps
-}
-
-// device -> device on the handle's stream, `count` elements
-template <class T>
-hipError_t carry(hipStream_t st, DevArray<T>& to, const DevArray<T>& from, size_t count) {
-    return count && from.p ? hipMemcpyAsync(to.p, from.p, count * sizeof(T), hipMemcpyDeviceToDevice, st) : hipSuccess;
-}
-
-// The removal both forms end in: count.flags (device, n bytes) and count.sums are filled.  Blocking.
+// The removal both forms end in: removal.flags (device, n bytes) and removal.sums are filled.  Blocking.
 fs_status remove2(fs_sim* s, uint32_t* removed) {
-    const uint32_t n = s->n, cap = s->capacity, nwg = remove_workgroups(n);
-    FS_HIP(hipGetLastError());
+    const uint32_t n = s->n, cap = s->capacity;
     uint32_t keep = 0;
-    FS_HIP(hipMemcpyAsync(&keep, s->count.sums.p + nwg, 4, hipMemcpyDeviceToHost, s->stream));
-    FS_HIP(hipStreamSynchronize(s->stream));
-    FS_TRY(sort_health(s));
+    FS_TRY(removal_survivors(s->stream, s->removal, n, bitonic(s) ? &s->sortp : nullptr, s->sort_dirty.p, &keep));
     if (keep == n) return FS_OK;                          // nothing matched: nothing changes, queries stay valid
-    if (keep < 2u) return fail(FS_ERR_INVALID, "removal: fewer than 2 particles would survive");
     bring_home(s);
     if (!s->aos.p) FS_HIP(s->aos.alloc(cap));
     // out of place: positions and velocities into the spare arrays (in bitonic mode the step swaps those two sets itself), pred,
@@ -86,13 +55,8 @@ fs_status remove2(fs_sim* s, uint32_t* removed) {
     C.pos = s->pos.p; C.vel = s->vel.p; C.pred = s->pred.p; C.rho = (const uint32_t*)s->rho.p; C.key = s->key.p;
     C.pos_out = s->pos_s.p; C.vel_out = s->vel_s.p;
     C.pred_out = (float2*)s->aos.p; C.rho_out = (uint32_t*)(C.pred_out + cap); C.key_out = C.rho_out + cap;
-    Tracking& T = s->trk;
-    if (T.on()) {
-        C.ids = T.id[T.cur].p; C.ids_out = T.id[T.cur ^ 1].p;
-        C.attr = T.attr[T.cur].p; C.attr_out = T.attr[T.cur ^ 1].p;
-        C.channels = T.channels; C.stride = cap;
-    }
-    launch_remove_scatter(s->stream, n, s->count.flags.p, s->count.sums.p, C);
+    compact_tracking(&C, s->trk, cap);
+    launch_remove_scatter(s->stream, n, s->removal.flags.p, s->removal.sums.p, C);
     FS_HIP(hipGetLastError());
     FS_HIP(hipMemcpyAsync(s->pred.p, C.pred_out, (size_t)keep * sizeof(float2), hipMemcpyDeviceToDevice, s->stream));
     FS_HIP(hipMemcpyAsync(s->rho.p, C.rho_out, (size_t)keep * 4, hipMemcpyDeviceToDevice, s->stream));
@@ -100,7 +64,7 @@ fs_status remove2(fs_sim* s, uint32_t* removed) {
     FS_HIP(hipStreamSynchronize(s->stream));
     std::swap(s->pos, s->pos_s);
     std::swap(s->vel, s->vel_s);
-    if (T.on()) T.cur ^= 1;
+    if (s->trk.on()) s->trk.cur ^= 1;
     const fs_status r = count_changed(s, keep);
     FS_HIP(hipStreamSynchronize(s->stream));
     *removed = n - keep;
@@ -111,7 +75,7 @@ fs_status remove2(fs_sim* s, uint32_t* removed) {
 extern "C" {
 
 uint32_t fs_capacity(const fs_sim* s) { return s ? s->capacity : 0; }
-uint32_t fs_track_next_id(const fs_sim* s) { return (s && s->trk.on()) ? s->count.next_id : 0; }
+uint32_t fs_track_next_id(const fs_sim* s) { return (s && s->trk.on()) ? s->trk.next_id : 0; }
 
 fs_status fs_reserve(fs_sim* s, uint32_t capacity) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
@@ -121,21 +85,18 @@ fs_status fs_reserve(fs_sim* s, uint32_t capacity) {
     if (capacity <= s->capacity) return FS_OK;
     FS_HIP(hipSetDevice(s->device));
     const size_t cap = capacity, n = s->n;
-    const uint32_t old_cap = s->capacity;
     const bool counting = s->opts.sort_mode == FS_SORT_COUNTING;
-    Tracking& T = s->trk;
     // everything new first: on failure the locals go and the handle is what it was
     ParticleArrays A;                                       // pos .. pairs (and an 8-word counter that is dropped again)
-    DevArray<uint32_t> key, dirty, csort, id[2];
+    DevArray<uint32_t> key, dirty, csort;
     DevArray<fs_particle> aos;
     DevArray<float2> stf;
-    DevArray<float> attr[2];
+    TrackingGrowth G;
     hipError_t e = hipSuccess;
     auto ok = [&e](hipError_t r) { e = r; return r == hipSuccess; };
     (void)(ok(A.alloc_common(cap)) && ok(key.alloc(cap)) && ok(dirty.alloc(sort_tile_count(capacity))) && ok(aos.alloc(cap)) &&
            ok(csort.alloc(counting ? counting_sort_scratch_words(capacity, s->ncell) : 0)) && ok(stf.alloc(s->st.stf.p ? cap : 0)) &&
-           ok(id[0].alloc(T.id[0].p ? cap : 0)) && ok(id[1].alloc(T.id[0].p ? cap : 0)) &&
-           ok(attr[0].alloc((size_t)T.alloc_channels * cap)) && ok(attr[1].alloc((size_t)T.alloc_channels * cap)));
+           ok(G.alloc(s->trk, cap)));
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(FS_ERR_OOM, "reserve: device arrays");
@@ -157,11 +118,7 @@ fs_status fs_reserve(fs_sim* s, uint32_t capacity) {
     if (e == hipSuccess) e = carry(q, A.pairs, s->pairs, n);
     if (e == hipSuccess) e = carry(q, key, s->key, n);
     if (e == hipSuccess) e = carry(q, stf, s->st.stf, n);
-    if (T.on()) {                                                          // the set in use; channel c moves from c * old_cap to c * cap
-        if (e == hipSuccess) e = carry(q, id[T.cur], T.id[T.cur], n);
-        for (int c = 0; c < T.channels && e == hipSuccess && n; ++c)
-            e = hipMemcpyAsync(attr[T.cur].p + (size_t)c * cap, T.attr[T.cur].p + (size_t)c * old_cap, n * sizeof(float), hipMemcpyDeviceToDevice, q);
-    }
+    if (e == hipSuccess) e = G.carry_from(q, s->trk, n, s->capacity, cap);
     const hipError_t es = hipStreamSynchronize(q);                         // before anything is freed, whatever happened
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return fail(FS_ERR_DEVICE, hipGetErrorString(e));
@@ -171,9 +128,8 @@ fs_status fs_reserve(fs_sim* s, uint32_t capacity) {
     s->key = std::move(key); s->sort_dirty = std::move(dirty); s->aos = std::move(aos);
     if (csort.p) s->csort = std::move(csort);
     if (stf.p) s->st.stf = std::move(stf);
-    if (id[0].p) { T.id[0] = std::move(id[0]); T.id[1] = std::move(id[1]); }
-    if (attr[0].p) { T.attr[0] = std::move(attr[0]); T.attr[1] = std::move(attr[1]); }
-    s->count.release();                                                    // sized by the capacity: the next removal allocates it again
+    G.commit(s->trk);
+    s->removal.release();                                                   // sized by the capacity: the next removal allocates it again
     s->capacity = capacity;
     return sort_health(s);
 }
@@ -193,7 +149,7 @@ fs_status fs_emit_particles(fs_sim* s, const fs_particle* src, size_t n) {
     FS_HIP(hipMemcpyAsync(stage, src, n * sizeof(fs_particle), hipMemcpyHostToDevice, s->stream));
     launch_import_aos(s->stream, (uint32_t)n, stage, s->pos.p + s->n, s->pred.p + s->n, s->vel.p + s->n, s->rho.p + s->n, s->key.p + s->n);
     FS_HIP(hipGetLastError());
-    track_emitted(s, (uint32_t)n);
+    s->trk.emitted(s->stream, s->n, (uint32_t)n, s->capacity);
     FS_HIP(hipStreamSynchronize(s->stream));               // `src` belongs to the caller again
     return count_changed(s, s->n + (uint32_t)n);
 }
@@ -216,7 +172,7 @@ fs_status fs_emit_nozzle(fs_sim* s, const fs_nozzle* z) {
     Z.nu = z->nu; Z.nv = z->nv;
     launch_emit_nozzle(s->stream, Z, s->pos.p + s->n, s->pred.p + s->n, s->vel.p + s->n, s->rho.p + s->n, s->key.p + s->n);
     FS_HIP(hipGetLastError());
-    track_emitted(s, (uint32_t)m);
+    s->trk.emitted(s->stream, s->n, (uint32_t)m, s->capacity);
     return count_changed(s, s->n + (uint32_t)m);
 }
 
@@ -225,8 +181,8 @@ fs_status fs_remove_in_box(fs_sim* s, const fs_vec2* lo, const fs_vec2* hi, uint
     if (!s || !lo || !hi || !removed) return fail(FS_ERR_INVALID, "null argument");
     if (s->slab) return fail(FS_ERR_INVALID, SLAB);
     FS_HIP(hipSetDevice(s->device));
-    FS_TRY(s->count.reserve(s->capacity));
-    launch_remove_box(s->stream, s->n, s->pos.p, make_float2(lo->x, lo->y), make_float2(hi->x, hi->y), s->count.flags.p, s->count.sums.p);
+    FS_TRY(s->removal.reserve(s->capacity));
+    launch_remove_box(s->stream, s->n, s->pos.p, make_float2(lo->x, lo->y), make_float2(hi->x, hi->y), s->removal.flags.p, s->removal.sums.p);
     return remove2(s, removed);
 }
 
@@ -236,9 +192,9 @@ fs_status fs_remove_flagged(fs_sim* s, const uint8_t* flags, size_t n, uint32_t*
     if (s->slab) return fail(FS_ERR_INVALID, SLAB);
     if (n != s->n) return fail(FS_ERR_INVALID, "removal: n must equal the particle count");
     FS_HIP(hipSetDevice(s->device));
-    FS_TRY(s->count.reserve(s->capacity));
-    FS_HIP(hipMemcpyAsync(s->count.flags.p, flags, n, hipMemcpyHostToDevice, s->stream));
-    launch_remove_count_flags(s->stream, s->n, s->count.flags.p, s->count.sums.p);
+    FS_TRY(s->removal.reserve(s->capacity));
+    FS_HIP(hipMemcpyAsync(s->removal.flags.p, flags, n, hipMemcpyHostToDevice, s->stream));
+    launch_remove_count_flags(s->stream, s->n, s->removal.flags.p, s->removal.sums.p);
     return remove2(s, removed);
 }
 

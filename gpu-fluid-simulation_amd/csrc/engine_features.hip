@@ -44,7 +44,6 @@ fs_status fs_track_enable(fs_sim* s, int channels) {
     if (s->slab) return fail(FS_ERR_UNSUPPORTED, "tracking: single-domain handles only (not built for slab handles)");
     FS_HIP(hipSetDevice(s->device));
     FS_TRY(s->trk.enable(s->stream, s->n, s->capacity, channels));
-    s->count.next_id = s->n;        // what the next emitted particle gets
     return FS_OK;
 }
 

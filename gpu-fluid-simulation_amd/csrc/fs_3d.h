@@ -3,6 +3,7 @@
 // launchers, the launchers.  A header of its own:
 // fs_kernels.h stays the 2D launchers' list, and kernels_sort_tile.inc takes the predict + cell-key expression from here.
 #pragma once
+#include "fs_count.h"
 #include "fs_kernels.h"
 
 namespace fsd {
@@ -184,34 +185,6 @@ struct ColliderMask3 {
 };
 void launch3_collider_from_mask(hipStream_t st, const ColliderMask3& Q);
 
-// A particle count that changes at run time (kernels_count3d.hip).  Device pointers; host side only.
-// The nozzle of fs3_emit_nozzle, by value: record q of nu * nv goes to slot first_slot + q of pos, pred, vel and key.
-struct Nozzle3 {
-    float3 origin, u, v, velocity;
-    uint32_t nu, nv;
-};
-void launch3_emit_nozzle(hipStream_t st, const Nozzle3& Z, uint32_t first_slot, const Arrays3& A);
-// Tracking's share of an emission of m records: ids[q] = first_id + q, +0.0f in each channel (c at attr + c * stride); ids and
-// attr point at the first emitted slot.
-void launch3_emit_track(hipStream_t st, uint32_t m, uint32_t first_id, uint32_t* ids, int channels, float* attr, uint32_t stride);
-// The removal's compaction: what the scatter reads and the arrays, none of them among those, it writes.  ids null: no tracking.
-struct Compact3 {
-    const float4 *pos, *vel, *pred;
-    const uint32_t* key;
-    float4 *pos_out, *vel_out, *pred_out;
-    uint32_t* key_out;
-    const uint32_t* ids;
-    uint32_t* ids_out;
-    const float* attr;
-    float* attr_out;
-    int channels;
-    uint32_t stride;
-};
-uint32_t remove3_workgroups(uint32_t n);   // `sums` holds one word per workgroup and one more, the survivors' total
-// flags (n bytes) and offsets passes.  lo / hi non-null: the kill flags are the inclusive box test of pos, written to `flags`;
-// null: `flags` holds the caller's.  Leaves sums[w]: survivors below workgroup w's slots, sums[remove3_workgroups(n)]: all.
-void launch3_remove_count(hipStream_t st, uint32_t n, const float4* pos, const float3* lo, const float3* hi, uint8_t* flags,
-                          uint32_t* sums);
-void launch3_remove_scatter(hipStream_t st, uint32_t n, const uint8_t* flags, const uint32_t* sums, const Compact3& C);
+// A particle count that changes at run time: fs_count.h, for both handles.
 
 }  // namespace fsd

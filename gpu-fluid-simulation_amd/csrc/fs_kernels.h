@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "fs_count.h"
 #include "fs_device.h"
 
 namespace fsd {
@@ -85,40 +86,7 @@ void launch_export_aos(hipStream_t st, uint32_t n, const float2* pos, const floa
 void launch_keys_from_pairs(hipStream_t st, uint32_t n, const u64* pairs, uint32_t* key, const float2* rho2, float* rho);
 void launch_import_aos(hipStream_t st, uint32_t n, const void* in, float2* pos, float2* pred, float2* vel, float* rho,
                        uint32_t* key);
-// A particle count that changes at run time (§21).  Device pointers; host side only.
-// The passes without a dimension in them, one copy for both handles (kernels_count3d.hip):
-uint32_t remove_workgroups(uint32_t n);    // `sums` holds one word per workgroup of a flags pass and one more, the survivors' total
-// sums[w] = survivors (flags[i] == 0) among workgroup w's 256 slots of the caller's `flags`, then launch_remove_offsets
-void launch_remove_count_flags(hipStream_t st, uint32_t n, const uint8_t* flags, uint32_t* sums);
-// one workgroup: sums[w] -> survivors below workgroup w's slots, sums[nwg] = all
-void launch_remove_offsets(hipStream_t st, uint32_t nwg, uint32_t* sums);
-// Tracking's share of an emission of m records: ids[q] = first_id + q (wrapping), +0.0f in each channel (c at attr + c * stride);
-// ids and attr point at the first emitted slot.
-void launch_emit_track(hipStream_t st, uint32_t m, uint32_t first_id, uint32_t* ids, int channels, float* attr, uint32_t stride);
-// The 2D passes (kernels_count.hip).  The nozzle of fs_emit_nozzle, by value: record q of nu * nv goes to element q of the five
-// arrays, which the caller passes offset by the live count.
-struct Nozzle2 {
-    float2 origin, u, v, velocity;
-    uint32_t nu, nv;
-};
-void launch_emit_nozzle(hipStream_t st, const Nozzle2& Z, float2* pos, float2* pred, float2* vel, float* rho, uint32_t* key);
-// The removal's compaction: what the scatter reads and the arrays, none of them among those, it writes.  The densities move as
-// words.  ids null: no tracking.
-struct Compact2 {
-    const float2 *pos, *vel, *pred;
-    const uint32_t *rho, *key;
-    float2 *pos_out, *vel_out, *pred_out;
-    uint32_t *rho_out, *key_out;
-    const uint32_t* ids;
-    uint32_t* ids_out;
-    const float* attr;
-    float* attr_out;
-    int channels;
-    uint32_t stride;
-};
-// flags[i] = the inclusive box test of pos[i] (n bytes), the per-workgroup survivor sums, then launch_remove_offsets
-void launch_remove_box(hipStream_t st, uint32_t n, const float2* pos, float2 lo, float2 hi, uint8_t* flags, uint32_t* sums);
-void launch_remove_scatter(hipStream_t st, uint32_t n, const uint8_t* flags, const uint32_t* sums, const Compact2& C);
+// A particle count that changes at run time: fs_count.h.
 
 void launch_render_density(hipStream_t st, const StepParams& P, float2 wmin, float2 wmax, uint32_t width,
                            uint32_t height, const float2* pred, const float2* vel, const uint32_t* cs,

@@ -57,7 +57,7 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
 }
 
 // Exclusive prefix of v over the workgroup's threads in thread order, and the workgroup's total.  Every thread calls it
-// (surface extraction, kernels_mesh3d.hip; the compaction of a removal, kernels_count3d.hip).
+// (surface extraction, kernels_mesh3d.hip; the compaction of a removal, kernels_count.hip).
 template <int WAVES>
 __device__ __forceinline__ uint32_t block_scan3(uint32_t v, uint32_t* s_wave /*[WAVES]*/, uint32_t* total) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
