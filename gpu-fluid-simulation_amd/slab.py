@@ -1,4 +1,4 @@
-"""One rank of the multi-GPU slab decomposition (include/fluidsim.h fs_slab_*); multi.py is its driver."""
+"""One rank of the multi-GPU slab decomposition (include/fluidsim.h fs_slab_*); multi/ is its driver."""
 import ctypes as C
 
 import numpy as np
@@ -11,7 +11,7 @@ class SlabSimulation(_Engine):
     """One rank of the multi-GPU slab decomposition (include/fluidsim.h fs_slab_*).
 
     Owns the global cell columns [own_lo, own_hi).  A step is pack() -> exchange the two
-    messages with the slab neighbours -> step(); see multi.py for the driver.
+    messages with the slab neighbours -> step(); see multi/ for the driver.
     """
     _prefix = "fs_"
     _destroy = "fs_destroy"        # a slab is a simulation handle: made by fs_slab_create, freed by fs_destroy

@@ -6,7 +6,7 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "gpu-fluid-simulation_amd")
-NOT_THE_WRAPPER = ("_abi.py", "build.py", "multi.py")      # the prototypes, the build and the multi-GPU driver
+NOT_THE_WRAPPER = ("_abi.py", "build.py")      # the prototypes and the build (the glob below does not reach into multi/)
 
 
 def strip_c_comments(s):

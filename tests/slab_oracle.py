@@ -1,6 +1,6 @@
 """Oracle-backed slab engine for the multi-rank tests (TEST INFRASTRUCTURE): speaks exactly
 the message format of the HIP slab engine (16-byte header + 16-byte {pos, vel} records) but
-advances its local set with the CPU oracle.  Lets the N>1 protocol of multi.py run on CPU
+advances its local set with the CPU oracle.  Lets the N>1 protocol of multi/ run on CPU
 ranks (gloo) without a GPU."""
 import numpy as np
 
@@ -35,7 +35,7 @@ def read_message(buf_u8):
     return buf_u8[16:16 + 16 * k].view(f32).reshape(k, 4).copy()
 
 
-class OracleSlabEngine:
+class OracleSlabEngine(multi.SlabEngine):
     def __init__(self, orc, settings, bounds, rank, world, transport):
         self.orc, self.settings, self.t = orc, settings, transport
         self.rank, self.world = rank, world

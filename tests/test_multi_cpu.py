@@ -137,7 +137,7 @@ rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
 dist.init_process_group("gloo", rank=rank, world_size=world)
 n, steps, speed, floor, mode = int(sys.argv[2]), int(sys.argv[3]), float(sys.argv[4]), int(sys.argv[5]), sys.argv[6]
 if mode == "undersized":
-    multi.travel_margin = lambda *a, **k: 0          # the round-1 behaviour: a fixed margin, blind to the fluid's speed
+    multi.partition.travel_margin = lambda *a, **k: 0          # where plan_rebalance looks it up; the round-1 behaviour: a fixed margin, blind to the fluid's speed
 st, off, tick = g.dam_break_2d(n)
 tick.gravity = g.Vec2(0.0, 0.0)
 hist, gw = multi.lattice_histogram(g, st, off)
@@ -200,6 +200,58 @@ def test_travel_margin_bounds():
     assert f(127.0, 9.81, 1 / 120, 0.2, 64) >= int(np.ceil(64 * 127.0 / 120 / 0.2))   # covers the plain advection distance
     assert f(1e9, 0.0, 1 / 120, 0.2, 64) == int(np.ceil(64 * 500.0 / 120 / 0.2)) + 2  # never beyond the speed clamp
     assert f(30.0, 0.0, 1 / 120, 0.2, 4) < f(30.0, 0.0, 1 / 120, 0.2, 64)
+
+
+# the boundary policy of a re-balancing step on hist[40:120] = 10 of 200 columns, dt = 1/120, h = 0.2; the expected values come
+# from SlabDriver.rebalance as it stood before the policy became a function:
+# bounds, vmax, accel, every, max_shift, trim, capacity_main, max_cols -> bounds, interval, margin, boundary_cols
+PLAN_CASES = [
+    ([0, 80, 200], 1, 10, 64, 2, 8, None, None, [26, 80, 134], 64, 14, 4),         # balanced: the full interval
+    ([0, 100, 200], 1, 10, 64, 2, 8, None, None, [32, 98, 128], 8, 8, 4),          # > 15 % over the mean: an eighth
+    ([0, 85, 200], 1, 10, 64, 2, 8, None, None, [32, 83, 128], 32, 8, 4),          # > 10 % over the mean: half
+    ([0, 86, 200], 1, 10, 64, 2, 8, 500, None, [32, 84, 128], 8, 8, 4),            # past 90 % of the main slots: an eighth
+    ([0, 85, 200], 1, 10, 64, 2, 8, 500, None, [32, 83, 128], 32, 8, 4),           # just inside them: the mean decides
+    ([0, 80, 200], 30, 0, 4, 1, 2, None, None, [30, 80, 130], 4, 10, 5),           # the margin follows the speed
+    ([30, 80, 130], 30, 0, 4, 1, 0, None, None, [0, 80, 200], 4, 0, 5),            # margin 0: back to the walls
+    ([0, 80, 200], 1, 10, 64, 2, 8, None, 30, [50, 80, 110], 64, 14, 4),           # never wider than the engine's tables
+    ([0, 50, 60, 200], 600, 10, 16, 3, 4, None, None, [0, 53, 63, 164], 2, 44, 24),  # three ranks, speed past the clamp
+]
+
+
+@pytest.mark.parametrize("case", PLAN_CASES, ids=[str(k) for k in range(len(PLAN_CASES))])
+def test_plan_rebalance_is_the_drivers_policy(case):
+    from gpu_fluid_simulation_amd import multi
+    bounds, vmax, accel, every, max_shift, trim, cap_main, max_cols, want_bounds, want_interval, want_margin, want_boundary = case
+    hist = np.zeros(200, dtype=np.int64)
+    hist[40:120] = 10
+    got = multi.plan_rebalance(list(bounds), hist, vmax, accel, 1 / 120, 0.2, every, max_shift, trim, capacity_main=cap_main,
+                               max_cols=max_cols)
+    assert got == (want_bounds, want_interval, want_margin, want_boundary)
+    # before the first step there is no tick to take dt from: the floor margin, no boundary zone, the same interval
+    new, interval, margin, boundary = multi.plan_rebalance(list(bounds), hist, vmax, accel, None, 0.2, every, max_shift, trim,
+                                                           capacity_main=cap_main, max_cols=max_cols)
+    assert (interval, margin, boundary) == (want_interval, trim, None) and new[1:-1] == want_bounds[1:-1]
+
+
+def test_transports_and_engines_provide_their_interface():
+    from gpu_fluid_simulation_amd import multi
+    from tests.slab_oracle import OracleSlabEngine
+    for cls in (multi.HostTransport, multi.DeviceTransport, multi.NativeTransport):
+        assert issubclass(cls, multi.SlabTransport)
+        for name in multi.SlabTransport.INTERFACE:
+            assert callable(getattr(cls, name)), f"{cls.__name__}.{name} missing"
+        # the base class only names these: every transport brings its own
+        for name in ("exchange", "reduce_rebalance"):
+            assert getattr(cls, name) is not getattr(multi.SlabTransport, name), f"{cls.__name__}.{name} not implemented"
+    assert multi.NativeTransport.close
+    for cls in (multi.HipSlabEngine, OracleSlabEngine):
+        assert issubclass(cls, multi.SlabEngine)
+        for name in multi.SlabEngine.INTERFACE:
+            assert hasattr(cls, name), f"{cls.__name__}.{name} missing"
+        for name in ("pack", "finish", "set_window", "owned_particles", "counters", "max_speed", "column_histogram", "sync"):
+            assert getattr(cls, name) is not getattr(multi.SlabEngine, name), f"{cls.__name__}.{name} not implemented"
+    assert multi.HipSlabEngine.rebalance_inputs is not multi.SlabEngine.rebalance_inputs      # the device path
+    assert OracleSlabEngine.rebalance_inputs is multi.SlabEngine.rebalance_inputs             # the host path
 
 
 # ---- properties of the pure partition logic (hypothesis) --------------------------------------------------------

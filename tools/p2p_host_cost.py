@@ -1,4 +1,4 @@
-"""Host-side cost of one torch.distributed P2P exchange as multi.Transport issues it (4 ops, fixed tensors),
+"""Host-side cost of one torch.distributed P2P exchange as multi/transport.py issues it (multi.Transport: 4 ops, fixed tensors),
 measured with a single-rank RCCL group sending to itself: the GPU work is two local copies, so what is left
 is what the host pays per step.  python tools/p2p_host_cost.py [bytes]"""
 import os, sys, time
