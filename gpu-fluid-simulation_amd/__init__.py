@@ -30,6 +30,7 @@ from ._abi import (  # noqa: F401
     SAMPLE3_DTYPE,
     SAMPLE_DTYPE,
     SURFACE_HIT_DTYPE,
+    BodyMotion,
     BodyMotion3,
     Camera3,
     ExtensionMissing,
@@ -62,6 +63,7 @@ from .sim2d import (  # noqa: F401
     default_tick_settings,
     generate_force_field,
     reference_lattice,
+    rigid_motion2d,
     sort_schedule,
 )
 from .sim3d import FluidSimulation3D, box_mask3d, dam_break_3d, look_at_camera, reference_lattice_3d, rigid_motion  # noqa: F401

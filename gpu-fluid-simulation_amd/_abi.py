@@ -157,6 +157,14 @@ class Nozzle(C.Structure):
     _fields_ = [("origin", Vec2), ("u", Vec2), ("v", Vec2), ("velocity", Vec2), ("nu", C.c_uint32), ("nv", C.c_uint32)]
 
 
+FS_MAX_BODIES = 8
+
+
+class BodyMotion(C.Structure):
+    """fs_body_motion (include/fluidsim.h "2D moving bodies"): 36 bytes.  rot: row-major R, world = R * local."""
+    _fields_ = [("centre", Vec2), ("rot", C.c_float * 4), ("velocity", Vec2), ("angular_velocity", C.c_float)]
+
+
 class Nozzle3(C.Structure):
     """fs3_nozzle (include/fluidsim.h "3D particle count"): 56 bytes."""
     _fields_ = [("origin", Vec3), ("u", Vec3), ("v", Vec3), ("velocity", Vec3), ("nu", C.c_uint32), ("nv", C.c_uint32)]
@@ -306,6 +314,14 @@ PROTOTYPES = {
     "fs_remove_in_box": (C.c_int, [_P, C.POINTER(Vec2), C.POINTER(Vec2), C.POINTER(C.c_uint32)]),
     "fs_remove_flagged": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_uint32)]),
     "fs_track_next_id": (C.c_uint32, [_P]),
+    "fs_body_create": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, Vec2, C.POINTER(C.c_uint32)]),
+    "fs_body_create_from_mask": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, Vec2, _P, C.POINTER(C.c_uint32)]),
+    "fs_body_set_motion": (C.c_int, [_P, C.c_uint32, C.POINTER(BodyMotion)]),
+    "fs_body_get_motion": (C.c_int, [_P, C.c_uint32, C.POINTER(BodyMotion)]),
+    "fs_body_dims": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(Vec2)]),
+    "fs_body_download": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t]),
+    "fs_body_destroy": (C.c_int, [_P, C.c_uint32]),
+    "fs_body_count": (C.c_uint32, [_P]),
     "fs_export_handle": (C.c_int, [_P, C.c_int, _P]),
     "fs_import_open": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "fs_import_read": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t]),

@@ -1,7 +1,7 @@
 // engine.h — what the host files of the C ABI share beyond fs_host.h: the 2D simulation handle and the state of each of its
 // features, the step parameters, and the device check and create-time proofs (also used by the 3D handle's files through
 // engine_3d.h).  The handle's files:
-// engine.hip (life cycle, step, transfers, renderer hand-off), engine_features.hip (surface tension, particle tracking),
+// engine.hip (life cycle, step, transfers, renderer hand-off), engine_features.hip (surface tension, particle tracking, moving bodies),
 // engine_query.hip (density render, field sampling), engine_count.hip (a particle count that changes at run time; what it
 // shares with the 3D handle's engine_3d_count.hip: engine_count.h, and Tracking and RemoveScratch below),
 // engine_selftest.hip (self-tests, read-outs), engine_slab.hip (the multi-GPU slab handles).  Internal: include/fluidsim.h is the interface.
@@ -191,6 +191,47 @@ struct Tracking {
     }
 };
 
+// Opt-in moving bodies (build extension; single-domain handles): fs_body_* in engine_features.hip.  Per slot a
+// field of push vectors over the body's own box and the motion the host last set; w == 0: the slot is free, and never created:
+// no allocation, no launch.
+struct Bodies {
+    struct Slot {
+        DevArray<float2> field;
+        uint32_t w = 0, h = 0;
+        fs_vec2 extent{};
+        fs_body_motion motion{};
+        size_t pixels() const { return (size_t)w * h; }
+    } slot[FS_MAX_BODIES];
+    bool has(uint32_t k) const { return k < FS_MAX_BODIES && slot[k].w != 0u; }
+    uint32_t count() const { uint32_t c = 0; for (const Slot& b : slot) c += b.w ? 1u : 0u; return c; }
+    // the lowest free slot, FS_MAX_BODIES when every slot is in use
+    uint32_t free_slot() const { uint32_t k = 0; while (k < FS_MAX_BODIES && slot[k].w) ++k; return k; }
+    // This step's pass, behind the force launches, on the state they stored (A.pos_out / A.vel_out; aos: the live 32-B records,
+    // or null): the fields and the motions as they are now, by value, the slots in use in ascending order (fs_body_* order their
+    // writes and frees on the stream behind it).  `done`: the step's completion event, which this launch carries in the force
+    // pass's place.  No slot in use: nothing is launched.
+    void enqueue(hipStream_t st, const StepParams& P, const StepArrays& A, void* aos, hipEvent_t done) const {
+        Bodies2 B;
+        uint32_t c = 0;
+        for (const Slot& b : slot) {
+            if (!b.w) continue;
+            const fs_body_motion& m = b.motion;
+            Body2& K = B.body[c++];
+            K.field = b.field.p; K.w = b.w; K.h = b.h;
+            K.ex = b.extent.x; K.ey = b.extent.y;
+            K.hx = b.extent.x * 0.5f; K.hy = b.extent.y * 0.5f;
+            K.cx = m.centre.x; K.cy = m.centre.y;
+            K.r00 = m.rot[0]; K.r01 = m.rot[1]; K.r10 = m.rot[2]; K.r11 = m.rot[3];
+            K.ux = m.velocity.x; K.uy = m.velocity.y;
+            K.wz = m.angular_velocity;
+        }
+        if (!c) return;
+        for (uint32_t k = c; k < BODIES2_MAX; ++k) B.body[k] = Body2{};
+        B.count = c;
+        launch_bodies(st, P, A, B, aos, done);
+    }
+};
+
 // Scratch of a removal (fs_remove_* in engine_count.hip, fs3_remove_* in engine_3d_count.hip), allocated by
 // the first one for `capacity` slots and released by fs_reserve / fs3_reserve.  Never called: no allocation, no launch.
 struct RemoveScratch {
@@ -304,6 +345,7 @@ struct fs_sim : fsd::HandleQueues, fsd::ParticleArrays {
     uint32_t aos_tick = 0xFFFFFFFFu;   // tick whose state the AoS view holds (only meaningful with aos_live)
     fsd::SurfaceTension st;         // the opt-in features' state: one line each in enqueue_step
     fsd::Tracking trk;
+    fsd::Bodies bodies;
     fsd::RemoveScratch removal;     // (not a per-step feature: emission and removal happen between steps)
     // what walks the cell table off the step path (engine_query.hip: fs_render_density; field sampling): the records
     // and the cell table belong together — a step has been enqueued since create and since the last fs_upload_particles /

@@ -344,9 +344,13 @@ static fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
     A.rho = s->rho.p;                  // (the force kernels take the array whatever the mode)
     if (pos_by_src) { A.pos_s = s->pos.p; A.pos_out = s->pos_s.p; }    // the role swap described above
     if (s->aos_live) L.aos_out = s->aos.p;
-    if (!prof) L.done = s->sortp.flight_event();
+    // with moving bodies their pass follows the force launches and carries the completion event in their place
+    const bool bodies = s->bodies.count() != 0u;
+    hipEvent_t done = prof ? nullptr : s->sortp.flight_event();
+    if (!bodies) L.done = done;
     L.quad_entries = s->sortp.quad_entries();
     fsd::launch_force(st, P, A, L);
+    if (bodies) s->bodies.enqueue(st, P, A, L.aos_out, done);   // on the buffers that hold the new state, before the role swap below
     if (pos_by_src) std::swap(s->pos, s->pos_s);   // the spare buffer now holds the state
     s->walk_ready = true;
     if (s->aos_live) s->aos_tick = s->tick;
@@ -356,7 +360,7 @@ static fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
         s->prof.pending += 1;
     }
     if (prof) FS_HIP(s->sortp.step_enqueued(st));      // (the profile's own events are markers anyway)
-    else s->sortp.step_bound();                        // the general force launch carried the step's completion event
+    else s->sortp.step_bound();                        // the general force launch (with bodies: theirs) carried the step's completion event
     FS_HIP(hipGetLastError());
     return FS_OK;
 }

@@ -1,11 +1,16 @@
-// engine_features.hip — the opt-in per-step features of a single-domain handle: surface tension and particle
-// tracking (§12).  Their state and what the step enqueues for them: SurfaceTension / Tracking (engine.h).
+// engine_features.hip — the opt-in per-step features of a single-domain handle: surface tension, particle
+// tracking (§12) and moving bodies (§24).  Their state and what the step enqueues for them: SurfaceTension / Tracking / Bodies
+// (engine.h).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+#include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
 #include "engine.h"
+#include "fs_3d.h"
 
 using namespace fsd;
 
@@ -98,5 +103,157 @@ fs_status fs_download_particles_by_id(fs_sim* s, fs_particle* dst, size_t n) {
     Tracking::scatter_by_id(ids, rec, dst, n);
     return FS_OK;
 }
+
+}  // extern "C"
+
+// ---- 2D moving bodies -----------------------------------------------------------------------------------
+namespace {
+const char* const BODY_SLAB = "body: single-domain handles only (not built for slab handles)";
+
+// Checks 4 and 5 of the two body constructors (the handle and the pointers first, by the caller).
+fs_status body_check(uint32_t w, uint32_t h, fs_vec2 extent) {
+    if (w == 0u || h == 0u || w > 1024u || h > 1024u) return fail(FS_ERR_INVALID, "body: w or h of 0 or above 1024");
+    const auto good = [](float a) { return std::isfinite(a) && a > 0.0f; };
+    if (!good(extent.x) || !good(extent.y)) return fail(FS_ERR_INVALID, "body: a box extent that is not finite and > 0");
+    return FS_OK;
+}
+
+// A produced or uploaded field becomes the body of `slot`: identity pose at the origin, at rest.
+void body_install(fs_sim* s, uint32_t slot, DevArray<float2>&& field, uint32_t w, uint32_t h, fs_vec2 extent) {
+    Bodies::Slot& b = s->bodies.slot[slot];
+    b.field = std::move(field);
+    b.w = w; b.h = h; b.extent = extent;
+    b.motion = fs_body_motion{};
+    b.motion.rot[0] = b.motion.rot[3] = 1.0f;
+}
+
+// host -> a fresh device field, blocking on the handle's stream
+fs_status body_upload(fs_sim* s, const fs_vec2* host, size_t pixels, DevArray<float2>* dev) {
+    static_assert(sizeof(fs_vec2) == sizeof(float2), "fs_vec2 is two f32");
+    if (dev->alloc(pixels) != hipSuccess) { (void)hipGetLastError(); return fail(FS_ERR_OOM, "body: device field"); }
+    FS_HIP(hipMemcpyAsync(dev->p, host, pixels * sizeof(float2), hipMemcpyHostToDevice, s->stream));
+    FS_HIP(hipStreamSynchronize(s->stream));
+    return FS_OK;
+}
+
+// The per-body calls' checks 1, 2 and 8 (the pointers between them, by the caller through `null`).
+fs_status body_slot(const fs_sim* s, bool null, uint32_t body) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    if (s->slab) return fail(FS_ERR_UNSUPPORTED, BODY_SLAB);
+    if (null) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->bodies.has(body)) return fail(FS_ERR_INVALID, "body: the slot holds no body");
+    return FS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+fs_status fs_body_create(fs_sim* s, const fs_vec2* field, uint32_t w, uint32_t h, fs_vec2 extent, uint32_t* body_out) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    if (s->slab) return fail(FS_ERR_UNSUPPORTED, BODY_SLAB);
+    if (!field || !body_out) return fail(FS_ERR_INVALID, "null argument");
+    FS_TRY(body_check(w, h, extent));
+    const size_t pixels = (size_t)w * h;
+    for (size_t k = 0; k < pixels; ++k)
+        if (!std::isfinite(field[k].x) || !std::isfinite(field[k].y)) return fail(FS_ERR_INVALID, "body: non-finite component");
+    const uint32_t slot = s->bodies.free_slot();
+    if (slot == FS_MAX_BODIES) return fail(FS_ERR_INVALID, "body: no free slot");
+    FS_HIP(hipSetDevice(s->device));
+    DevArray<float2> dev;
+    FS_TRY(body_upload(s, field, pixels, &dev));
+    body_install(s, slot, std::move(dev), w, h, extent);
+    *body_out = slot;
+    return FS_OK;
+}
+
+// The producer of "3D colliders" (launch3_collider_from_mask: one library, one transform) on the w x h x 1 mask over a box of
+// (extent.x, extent.y, 1); its z component is +0 everywhere and is dropped on the host, between the two blocking copies.
+fs_status fs_body_create_from_mask(fs_sim* s, const uint8_t* mask, uint32_t w, uint32_t h, fs_vec2 extent, fs_vec2* field_host,
+                                   uint32_t* body_out) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    if (s->slab) return fail(FS_ERR_UNSUPPORTED, BODY_SLAB);
+    if (!mask || !body_out) return fail(FS_ERR_INVALID, "null argument");
+    FS_TRY(body_check(w, h, extent));
+    const size_t pixels = (size_t)w * h;
+    bool any_free = false;
+    for (size_t k = 0; k < pixels && !any_free; ++k) any_free = !(mask[k] > 128);
+    if (!any_free) return fail(FS_ERR_INVALID, "body: the mask has no free pixel");
+    const uint32_t slot = s->bodies.free_slot();
+    if (slot == FS_MAX_BODIES) return fail(FS_ERR_INVALID, "body: no free slot");
+    FS_HIP(hipSetDevice(s->device));
+    std::unique_ptr<float4[]> host4(new (std::nothrow) float4[pixels]);
+    std::unique_ptr<fs_vec2[]> host2(new (std::nothrow) fs_vec2[pixels]);
+    if (!host4 || !host2) return fail(FS_ERR_OOM, "host allocation failed");
+    DevArray<uint8_t> dmask;
+    DevArray<uint32_t> near_x, near_xy;
+    DevArray<float4> field4;
+    if (dmask.alloc(pixels) != hipSuccess || near_x.alloc(pixels) != hipSuccess || near_xy.alloc(pixels) != hipSuccess ||
+        field4.alloc(pixels) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FS_ERR_OOM, "body: device staging");
+    }
+    ColliderMask3 Q;
+    Q.mask = dmask.p; Q.w = w; Q.h = h; Q.d = 1u;
+    Q.vx = extent.x / (float)w; Q.vy = extent.y / (float)h; Q.vz = 1.0f;
+    Q.near_x = near_x.p; Q.near_xy = near_xy.p; Q.field = field4.p;
+    hipError_t e = hipMemcpyAsync(dmask.p, mask, pixels, hipMemcpyHostToDevice, s->stream);
+    if (e == hipSuccess) { launch3_collider_from_mask(s->stream, Q); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(host4.get(), field4.p, pixels * sizeof(float4), hipMemcpyDeviceToHost, s->stream);
+    const hipError_t es = hipStreamSynchronize(s->stream);      // before the staging is freed, whatever happened
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(FS_ERR_DEVICE, hipGetErrorString(e));
+    for (size_t k = 0; k < pixels; ++k) host2[k] = fs_vec2{host4[k].x, host4[k].y};
+    DevArray<float2> dev;
+    FS_TRY(body_upload(s, host2.get(), pixels, &dev));
+    if (field_host) std::memcpy(field_host, host2.get(), pixels * sizeof(fs_vec2));
+    body_install(s, slot, std::move(dev), w, h, extent);
+    *body_out = slot;
+    return FS_OK;
+}
+
+fs_status fs_body_set_motion(fs_sim* s, uint32_t body, const fs_body_motion* m) {
+    FS_TRY(body_slot(s, !m, body));
+    const float* f = &m->centre.x;              // 9 floats, nothing between them (static_assert below)
+    for (int k = 0; k < 9; ++k) if (!std::isfinite(f[k])) return fail(FS_ERR_INVALID, "body: non-finite motion");
+    s->bodies.slot[body].motion = *m;           // host memory only: the next enqueue takes it by value
+    return FS_OK;
+}
+static_assert(sizeof(fs_body_motion) == 9 * sizeof(float), "fs_body_motion is 9 packed floats");
+static_assert(fsd::BODIES2_MAX == FS_MAX_BODIES, "Bodies2 holds every slot of the ABI");
+
+fs_status fs_body_get_motion(const fs_sim* s, uint32_t body, fs_body_motion* out) {
+    FS_TRY(body_slot(s, !out, body));
+    *out = s->bodies.slot[body].motion;
+    return FS_OK;
+}
+
+fs_status fs_body_dims(const fs_sim* s, uint32_t body, uint32_t* w, uint32_t* h, fs_vec2* extent) {
+    FS_TRY(body_slot(s, !w || !h || !extent, body));
+    const Bodies::Slot& b = s->bodies.slot[body];
+    *w = b.w; *h = b.h; *extent = b.extent;
+    return FS_OK;
+}
+
+fs_status fs_body_download(fs_sim* s, uint32_t body, fs_vec2* dst, size_t n) {
+    FS_TRY(body_slot(s, !dst, body));
+    const Bodies::Slot& b = s->bodies.slot[body];
+    if (n != b.pixels()) return fail(FS_ERR_INVALID, "body: n must be w * h");
+    FS_HIP(hipSetDevice(s->device));
+    FS_HIP(hipMemcpyAsync(dst, b.field.p, n * sizeof(fs_vec2), hipMemcpyDeviceToHost, s->stream));
+    FS_HIP(hipStreamSynchronize(s->stream));
+    return FS_OK;
+}
+
+fs_status fs_body_destroy(fs_sim* s, uint32_t body) {
+    FS_TRY(body_slot(s, false, body));
+    FS_HIP(hipSetDevice(s->device));
+    FS_HIP(hipStreamSynchronize(s->stream));       // the steps in flight read the field
+    Bodies::Slot& b = s->bodies.slot[body];
+    b.w = b.h = 0;
+    b.field.release();
+    return FS_OK;
+}
+
+uint32_t fs_body_count(const fs_sim* s) { return s ? s->bodies.count() : 0u; }
 
 }  // extern "C"

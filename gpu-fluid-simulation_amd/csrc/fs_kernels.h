@@ -72,6 +72,29 @@ void launch_force(hipStream_t st, const StepParams& P, const StepArrays& A, cons
 // densities (rho2; A.rho != nullptr: tolerance mode, densities in rho) over the density pass's neighbour walk.  Single-domain handles.
 // cg = poly6_kernel_derivative (24/(pi h^8)); sigma = surface_tension_coefficient, tau = surface_tension_treshold.
 void launch_surface_tension(hipStream_t st, const StepParams& P, const StepArrays& A, float sigma, float tau, float cg, float2* st_out);
+// The opt-in moving bodies of a single-domain handle (include/fluidsim.h "2D moving bodies") as k_bodies takes
+// them, by value and apart from StepParams (kernels_bodies.hip).  Per body: the field of push vectors over the body's own box,
+// and the motion of this enqueue.  rij: row-major R, world = R * local.  body[0 .. count) are the slots in use, ascending.
+constexpr uint32_t BODIES2_MAX = 8u;   // FS_MAX_BODIES
+struct Body2 {
+    const float2* field;
+    uint32_t w, h;
+    float ex, ey;                      // the box's extent: the divisor of the lookup
+    float hx, hy;                      // extent * 0.5f
+    float cx, cy;
+    float r00, r01, r10, r11;
+    float ux, uy;
+    float wz;
+};
+struct Bodies2 {
+    uint32_t count;
+    Body2 body[BODIES2_MAX];
+};
+// After launch_force, on the positions (A.pos_out) and velocities (A.vel_out) it stored: the operators B of every body in order.
+// P: n, bs_x, bs_y, damping.  aos (may be null): the 32-B records the force pass wrote as well (ForceLaunch::aos_out); a particle
+// a body hits gets its new position and velocity there too.  done (may be null): signalled by the kernel's completion, as
+// ForceLaunch::done is.
+void launch_bodies(hipStream_t st, const StepParams& P, const StepArrays& A, const Bodies2& B, void* aos, hipEvent_t done);
 // Particle tracking (build extension): after the reorder pass of a step, id_out[i] = id_in[src] and, for c < channels,
 // attr_out[c * stride + i] = attr_in[c * stride + src], src = the low word of pairs[i] (the slot before the step).  channels in [0, 4].
 void launch_track_carry(hipStream_t st, uint32_t n, int channels, const u64* pairs, const uint32_t* id_in, uint32_t* id_out,

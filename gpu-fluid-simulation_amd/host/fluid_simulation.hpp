@@ -130,6 +130,34 @@ public:
     uint32_t remove_box(fs_vec2 lo, fs_vec2 hi) { uint32_t n = 0; check(fs_remove_in_box(h_, &lo, &hi, &n)); return n; }
     uint32_t remove(const std::vector<uint8_t>& flags) { uint32_t n = 0; check(fs_remove_flagged(h_, flags.data(), flags.size(), &n)); return n; }
     uint32_t next_id() const { return fs_track_next_id(h_); }       // of the next emitted particle while tracking is on; 0: off
+    // Build extension, NOT in the reference: 2D moving bodies (include/fluidsim.h), single-domain handles.  w * h push vectors in
+    // world units over the body's own box [-extent/2, extent/2] in the body frame.  add_body* return the slot (the lowest free one
+    // of 0 .. FS_MAX_BODIES - 1) and block; the body starts at the origin with the identity pose, at rest.  set_body_motion: host
+    // memory only, for the ticks enqueued afterwards; the engine does not advance the pose.
+    uint32_t add_body(const std::vector<fs_vec2>& field, uint32_t w, uint32_t h, fs_vec2 extent) {
+        if (field.size() != (size_t)w * h) throw std::invalid_argument("add_body: field.size() != w * h");
+        uint32_t slot = 0;
+        check(fs_body_create(h_, field.data(), w, h, extent, &slot));
+        return slot;
+    }
+    uint32_t add_body_mask(const std::vector<uint8_t>& mask, uint32_t w, uint32_t h, fs_vec2 extent) {
+        if (mask.size() != (size_t)w * h) throw std::invalid_argument("add_body_mask: mask.size() != w * h");
+        uint32_t slot = 0;
+        check(fs_body_create_from_mask(h_, mask.data(), w, h, extent, nullptr, &slot));
+        return slot;
+    }
+    void set_body_motion(uint32_t body, const fs_body_motion& motion) { check(fs_body_set_motion(h_, body, &motion)); }
+    fs_body_motion body_motion(uint32_t body) const { fs_body_motion m{}; check(fs_body_get_motion(h_, body, &m)); return m; }
+    std::vector<fs_vec2> body_field(uint32_t body) {
+        uint32_t w = 0, h = 0;
+        fs_vec2 extent{};
+        check(fs_body_dims(h_, body, &w, &h, &extent));
+        std::vector<fs_vec2> v((size_t)w * h);
+        check(fs_body_download(h_, body, v.data(), v.size()));
+        return v;
+    }
+    void remove_body(uint32_t body) { check(fs_body_destroy(h_, body)); }
+    uint32_t body_count() const { return fs_body_count(h_); }
     // Build extension, NOT in the reference: field sampling (include/fluidsim.h), single-domain handles.  Density, Shepard weight,
     // un-normalised velocity sum, neighbour count and cell of the fluid at any points; `attr` (may be null) receives the channel
     // sums, channel c of query k at c * n + k.  Needs a tick since creation / the last upload.  Coherently ordered points are

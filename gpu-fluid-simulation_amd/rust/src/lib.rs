@@ -134,6 +134,19 @@ impl Default for BodyMotion3 {
         BodyMotion3 { centre: Vec3::default(), rot: [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0], velocity: Vec3::default(), angular_velocity: Vec3::default() }
     }
 }
+/// fs_body_motion: pose and velocity of a 2D moving body (build extension, include/fluidsim.h "2D moving bodies"); 36 bytes.
+/// `rot`: row-major R, world = R * local; the engine checks only that it is finite.  `angular_velocity`: rad/s, counter-clockwise.
+#[repr(C)] #[derive(Clone, Copy, Debug, PartialEq)]
+pub struct BodyMotion { pub centre: Vec2, pub rot: [f32; 4], pub velocity: Vec2, pub angular_velocity: f32 }
+const _: () = assert!(std::mem::size_of::<BodyMotion>() == 36);
+impl Default for BodyMotion {
+    /// The motion of a new body: the identity pose at the origin, at rest.
+    fn default() -> Self {
+        BodyMotion { centre: Vec2::default(), rot: [1.0, 0.0, 0.0, 1.0], velocity: Vec2::default(), angular_velocity: 0.0 }
+    }
+}
+/// FS_MAX_BODIES: the body slots of a 2D handle.
+pub const MAX_BODIES: u32 = 8;
 /// FS3_MAX_BODIES: the body slots of a 3D handle.
 pub const MAX_BODIES3: u32 = 8;
 /// fs3_surface_hit: one pixel of the G-buffer; 40 bytes, offsets 0/4/8/20/32/36.  `hit` 0: miss, 1: bracketed and refined, 2: the first sample was inside.
@@ -200,6 +213,14 @@ extern "C" {
     fn fs_remove_in_box(sim: *mut fs_sim, lo: *const Vec2, hi: *const Vec2, removed: *mut u32) -> c_int;
     fn fs_remove_flagged(sim: *mut fs_sim, flags_host: *const u8, n: usize, removed: *mut u32) -> c_int;
     fn fs_track_next_id(sim: *const fs_sim) -> u32;
+    fn fs_body_create(sim: *mut fs_sim, field_host: *const Vec2, w: u32, h: u32, extent: Vec2, body_out: *mut u32) -> c_int;
+    fn fs_body_create_from_mask(sim: *mut fs_sim, mask_host: *const u8, w: u32, h: u32, extent: Vec2, field_host: *mut Vec2, body_out: *mut u32) -> c_int;
+    fn fs_body_set_motion(sim: *mut fs_sim, body: u32, motion: *const BodyMotion) -> c_int;
+    fn fs_body_get_motion(sim: *const fs_sim, body: u32, out: *mut BodyMotion) -> c_int;
+    fn fs_body_dims(sim: *const fs_sim, body: u32, w: *mut u32, h: *mut u32, extent: *mut Vec2) -> c_int;
+    fn fs_body_download(sim: *mut fs_sim, body: u32, dst: *mut Vec2, n: usize) -> c_int;
+    fn fs_body_destroy(sim: *mut fs_sim, body: u32) -> c_int;
+    fn fs_body_count(sim: *const fs_sim) -> u32;
     // profiling
     fn fs_profile_enable(sim: *mut fs_sim, enable: c_int) -> c_int;
     fn fs_profile_read(sim: *mut fs_sim, ms: *mut f64, steps: *mut u64, reset: c_int) -> c_int;
@@ -456,6 +477,41 @@ impl FluidSimulation {
     pub fn remove(&mut self, flags: &[u8]) -> u32 { let mut n = 0u32; check(unsafe { fs_remove_flagged(self.raw, flags.as_ptr(), flags.len(), &mut n) }); n }
     /// The id the next emitted particle gets while tracking is on (0 when it is off).
     pub fn next_id(&self) -> u32 { unsafe { fs_track_next_id(self.raw) } }
+    /// Build extension: 2D moving bodies (include/fluidsim.h).  `field`: `w * h` push vectors in world units over the body's own
+    /// box `[-extent/2, extent/2]` in the body frame.  Returns the slot (the lowest free one of `0 .. MAX_BODIES`); blocking.  The
+    /// body starts at the origin with the identity pose, at rest.
+    pub fn add_body(&mut self, field: &[Vec2], w: u32, h: u32, extent: Vec2) -> u32 {
+        assert_eq!(field.len(), (w as usize) * (h as usize));
+        let mut slot = 0u32;
+        check(unsafe { fs_body_create(self.raw, field.as_ptr(), w, h, extent, &mut slot) });
+        slot
+    }
+    /// The body of a `w * h` mask (`> 128`: solid) over the box `extent`, by the exact distance transform of the 3D colliders.
+    pub fn add_body_mask(&mut self, mask: &[u8], w: u32, h: u32, extent: Vec2) -> u32 {
+        assert_eq!(mask.len(), (w as usize) * (h as usize));
+        let mut slot = 0u32;
+        check(unsafe { fs_body_create_from_mask(self.raw, mask.as_ptr(), w, h, extent, std::ptr::null_mut(), &mut slot) });
+        slot
+    }
+    /// Pose and velocity for the ticks enqueued afterwards; host memory only.  The engine does not advance the pose.
+    pub fn set_body_motion(&mut self, body: u32, motion: &BodyMotion) { check(unsafe { fs_body_set_motion(self.raw, body, motion) }); }
+    pub fn body_motion(&self, body: u32) -> BodyMotion { let mut m = BodyMotion::default(); check(unsafe { fs_body_get_motion(self.raw, body, &mut m) }); m }
+    /// `((w, h), extent)` of a body.
+    pub fn body_dims(&self, body: u32) -> ((u32, u32), Vec2) {
+        let (mut w, mut h, mut e) = (0u32, 0u32, Vec2::default());
+        check(unsafe { fs_body_dims(self.raw, body, &mut w, &mut h, &mut e) });
+        ((w, h), e)
+    }
+    /// A body's field, `w * h` vectors.  Blocking.
+    pub fn body_field(&mut self, body: u32) -> Vec<Vec2> {
+        let ((w, h), _) = self.body_dims(body);
+        let mut v = vec![Vec2::default(); (w as usize) * (h as usize)];
+        check(unsafe { fs_body_download(self.raw, body, v.as_mut_ptr(), v.len()) });
+        v
+    }
+    /// Destroys a body and frees its slot; the other bodies keep theirs.  Blocking.
+    pub fn remove_body(&mut self, body: u32) { check(unsafe { fs_body_destroy(self.raw, body) }); }
+    pub fn body_count(&self) -> u32 { unsafe { fs_body_count(self.raw) } }
     /// `start_indices` to the host (the renderer's second storage binding; u32[grid_w * grid_h]).
     pub fn download_start_indices(&mut self) -> Vec<u32> {
         let (w, h) = self.grid_dims();

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (FS_MATH_IEEE, FS_SORT_BITONIC, PARTICLE_DTYPE, SAMPLE_DTYPE, Nozzle, Options, Settings, SortStep, TickSettings,
+from ._abi import (FS_MATH_IEEE, FS_SORT_BITONIC, PARTICLE_DTYPE, SAMPLE_DTYPE, BodyMotion, Nozzle, Options, Settings, SortStep, TickSettings,
                    Uniform, UVec2, Vec2, load_library)
 from ._handle import _check, _Count, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec2
 
@@ -169,6 +169,67 @@ class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Simulation):
         self._call("sample_points_device", C.c_void_p(points_ptr), int(n), C.c_void_p(out_ptr),
                    C.c_void_p(attr_ptr) if attr_ptr else None)
 
+    # -- 2D moving bodies (build extension) --------------------
+    def add_body(self, field, extent):
+        """A kinematic rigid body: a float32 [H, W, 2] field of push vectors in world units (zero = free space) over the body's
+        own box [-extent/2, extent/2] in the body frame (include/fluidsim.h "2D moving bodies").  Returns its slot, the lowest
+        free one of 0 .. 7.  Blocking.  The body starts at the origin with the identity pose, at rest: set_body_motion places it."""
+        f = np.ascontiguousarray(field, dtype=np.float32)
+        if f.ndim != 3 or f.shape[2] != 2:
+            raise ValueError("add_body expects a [H, W, 2] float32 array")
+        h, w = f.shape[:2]
+        slot = C.c_uint32()
+        self._call("body_create", _ptr(f), int(w), int(h), _vec2(extent), C.byref(slot))
+        return int(slot.value)
+
+    def add_body_mask(self, mask, extent, want_field=False):
+        """The body of a uint8 [H, W] mask (> 128: solid) over the box `extent`: the exact distance transform of the 3D colliders
+        on the body's box (not set_obstacle_image's chamfer).  Returns the slot, with want_field=True (slot, the [H, W, 2] field)."""
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        if m.ndim != 2:
+            raise ValueError("add_body_mask expects a [H, W] uint8 array")
+        h, w = m.shape
+        out = np.zeros((h, w, 2), dtype=np.float32) if want_field else None
+        slot = C.c_uint32()
+        self._call("body_create_from_mask", _ptr(m), int(w), int(h), _vec2(extent), _ptr(out) if want_field else None, C.byref(slot))
+        return (int(slot.value), out) if want_field else int(slot.value)
+
+    def set_body_motion(self, body, centre, rot=None, velocity=(0.0, 0.0), angular_velocity=0.0):
+        """Pose and velocity of a body for the steps enqueued after this call; host memory only, no copy, no sync.  `rot`: four
+        floats, row-major R with world = R * local (None: the identity).  The engine does not advance the pose: set it before
+        every step of a moving body (rigid_motion2d computes one)."""
+        r = np.eye(2, dtype=np.float32) if rot is None else np.asarray(rot, dtype=np.float32)
+        m = BodyMotion(_vec2(centre), (C.c_float * 4)(*[float(x) for x in r.reshape(4)]), _vec2(velocity), float(angular_velocity))
+        self._call("body_set_motion", int(body), C.byref(m))
+
+    def body_motion(self, body):
+        """(centre[2], rot[2, 2], velocity[2], angular_velocity) of a body: float32 arrays and a float32 scalar."""
+        m = BodyMotion()
+        self._call("body_get_motion", int(body), C.byref(m))
+        v = lambda a: np.array([a.x, a.y], dtype=np.float32)      # noqa: E731
+        return v(m.centre), np.array(list(m.rot), dtype=np.float32).reshape(2, 2), v(m.velocity), np.float32(m.angular_velocity)
+
+    def body_dims(self, body):
+        """((W, H), (ex, ey)) of a body: its field's extents and its box."""
+        w, h, e = C.c_uint32(), C.c_uint32(), Vec2()
+        self._call("body_dims", int(body), C.byref(w), C.byref(h), C.byref(e))
+        return (int(w.value), int(h.value)), (float(e.x), float(e.y))
+
+    def body_field(self, body):
+        """A body's field as a float32 [H, W, 2] array.  Blocking."""
+        (w, h), _ = self.body_dims(body)
+        out = np.zeros((h, w, 2), dtype=np.float32)
+        self._call("body_download", int(body), _ptr(out), w * h)
+        return out
+
+    def remove_body(self, body):
+        """Destroys a body and frees its slot; the other bodies keep theirs.  Blocking."""
+        self._call("body_destroy", int(body))
+
+    @property
+    def body_count(self):
+        return int(self._fn("body_count")(self._h))
+
     def export_handle(self, which=_abi.FS_EXPORT_PARTICLES):
         """fs_export_handle: interprocess handle of the AoS particle view (switches on the live view) or of start_indices."""
         h = _abi.MemHandle()
@@ -184,6 +245,16 @@ class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Simulation):
         p, n = C.c_void_p(), C.c_size_t()
         self._call("start_indices_device", C.byref(p), C.byref(n))
         return p.value, int(n.value)
+
+
+def rigid_motion2d(centre0, velocity, rate, t):
+    """The pose of a body that started at `centre0` with the identity rotation, moves with `velocity` and turns counter-clockwise
+    at `rate` rad/s, at time t: (centre[2], rot[4]) — in float64, cast to float32 once; the four floats are what
+    FluidSimulation.set_body_motion takes as `rot`.  The matching angular velocity is `rate`."""
+    c = np.asarray(centre0, dtype=np.float64) + np.asarray(velocity, dtype=np.float64) * float(t)
+    th = float(rate) * float(t)
+    rot = np.array([np.cos(th), -np.sin(th), np.sin(th), np.cos(th)], dtype=np.float64)
+    return c.astype(np.float32), rot.astype(np.float32)
 
 
 def generate_force_field(image, device=0):

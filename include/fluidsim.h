@@ -462,6 +462,83 @@ fs_status fs_remove_in_box(fs_sim* sim, const fs_vec2* lo, const fs_vec2* hi, ui
 fs_status fs_remove_flagged(fs_sim* sim, const uint8_t* flags_host, size_t n, uint32_t* removed);
 uint32_t fs_track_next_id(const fs_sim* sim);
 
+/* ------------------------------------------------ 2D moving bodies (build extension, opt-in by being created) */
+/* Kinematic rigid bodies for the 2D step: a wave-maker paddle, a stirrer, a piston, a gate.  The 2D counterpart of "3D moving
+ * bodies" below.  Up to FS_MAX_BODIES per handle, each a small W x H field of push vectors, field[j * W + i], a zero vector is
+ * free space, over the body's own box [-extent/2, extent/2] in the BODY frame, with a pose and a velocity the host sets per step.
+ * The vectors are in world units of the body frame — not the pixel units of the force texture (fs_upload_force_field), which
+ * stays what it was: one domain-wide static field, pushed out inside move_particle.  The fluid feels the body (one-way
+ * coupling): the engine neither integrates the pose nor computes forces on the body.  A handle without a body launches exactly
+ * the kernels it launched before and computes the same bits.
+ *
+ * With bodies present, a step is B_7(...B_0(step(state))): the whole reference step first, its texture push-out and its wall
+ * clamp included, then the operator of each existing body in ascending slot order, on the position p and the velocity v the step
+ * is about to leave.  All arithmetic is f32 without contraction, `/` and `sqrt` are correctly rounded, u32_sat as in "3D
+ * colliders"; b.a = bounds.a * 0.5f are the half-bounds of the step (its own bs_x, bs_y) and damping the tick's damping_factor.
+ * Per body: c = centre, rij = rot[2*i + j] (world = R * local), u = velocity, w = angular_velocity, hb.a = extent.a * 0.5f (on
+ * the host, once), W_x = W, W_y = H.
+ *     d.a  = p.a - c.a
+ *     q.x  = r00*d.x + r10*d.y;   q.y = r01*d.x + r11*d.y                    (q = R^T d: the body frame)
+ *     if !(fabsf(q.x) <= hb.x && fabsf(q.y) <= hb.y): unchanged              (NaN: unchanged; on an edge: inside)
+ *     ia = min(u32_sat(((q.a + hb.a) / extent.a) * (float)W_a), W_a - 1)
+ *     g  = field[iy * W + ix];   if g.x == 0 && g.y == 0: unchanged
+ *     len = sqrt(g.x*g.x + g.y*g.y);   if !(len > 0): unchanged              (a vector whose squares underflow is free space)
+ *     f.x = r00*g.x + r01*g.y;   f.y = r10*g.x + r11*g.y                     (R g: back to the world)
+ *     n.a = f.a / len
+ *     p.a = p.a + f.a
+ *     s.a = p.a - c.a                                                        (the pushed position)
+ *     us.x = u.x - w*s.y;   us.y = u.y + w*s.x                               (the body surface's velocity there)
+ *     r.a = v.a - us.a
+ *     rn  = r.x*n.x + r.y*n.y
+ *     k   = (1.0f - damping) * rn
+ *     v.a = us.a + (r.a - k*n.a)
+ *     per axis, x then y: if fabsf(p.a) > b.a { p.a = b.a * sign(p.a); v.a *= -1.0f * damping }
+ * predicted_position, density and grid are not touched, and neither is start_indices.  All three math modes (FS_MATH_IEEE,
+ * FS_MATH_WGSL_ULP, FS_MATH_TOLERANCE) run this same IEEE operator.  The engine does not check that rot is a rotation, only that
+ * it is finite.  A pushed particle keeps the body surface's velocity along the normal, so a moving wall hands momentum over.
+ *
+ * fs_body_create: a field made by the caller.  fs_body_create_from_mask: the exact distance transform of "3D colliders" on a
+ * w x h x 1 mask over the body's box, the z component dropped — the same passes, the same tie rules, s_a = extent.a / (float)W_a,
+ * a mask value > 128 is solid; `field_host` (may be NULL) receives the field, w * h fs_vec2.  It is not the chamfer of
+ * fs_generate_force_field, which works in pixel units and is not exact.  *body_out is the lowest free slot in
+ * 0 .. FS_MAX_BODIES - 1; slots are stable (destroying body 1 leaves body 2 as body 2).  A new body has the identity pose at the
+ * origin and zero velocities.
+ *
+ * Checks, in this order, FS_ERR_INVALID unless stated; a refused call changes nothing:
+ *  1. NULL handle.
+ *  2. A slab handle -> FS_ERR_UNSUPPORTED (single-domain handles only).
+ *  3. NULL array or out pointer (field, mask, body_out, motion, dst, or one of the three of fs_body_dims).
+ *  4. w or h of 0 or above 1024.
+ *  5. A component of the box `extent` that is not finite and > 0.
+ *  6. A non-finite field component, or a mask without a free pixel.
+ *  7. No free slot.
+ *  8. The per-body calls: a slot that holds no body (fs_body_download then: n != w * h).
+ *  9. fs_body_set_motion: any non-finite float.
+ *
+ * create*, download and destroy are blocking and ordered on fs_stream(sim); destroy synchronises before freeing, because steps
+ * in flight read the field.  fs_body_set_motion touches host memory only: a step (fs_step, and every step of fs_timed_steps)
+ * takes every body's motion by value when it is enqueued, so setting a different pose before each of several un-synchronised
+ * steps is the intended use.  The pose holds until it is set again.  Nothing here makes rendering or sampling stale; particles
+ * emitted inside a body (fs_emit_*) are pushed by the next step.  With a renderer hand-off registered
+ * (fs_export_handle(FS_EXPORT_PARTICLES)) the exported records hold the pushed positions and velocities.  The time of the
+ * operators falls inside FS_PASS_FORCE.  FS_ABI_VERSION is unchanged.  See DESIGN.md §24. */
+#define FS_MAX_BODIES 8
+typedef struct fs_body_motion {
+    fs_vec2 centre;            /* world position of the body box's centre */
+    float   rot[4];            /* row-major R, world = R * local; the caller supplies a rotation, the engine checks only finiteness */
+    fs_vec2 velocity;          /* of the centre, world units per second */
+    float   angular_velocity;  /* rad/s, counter-clockwise in (x, y) */
+} fs_body_motion;
+fs_status fs_body_create(fs_sim* sim, const fs_vec2* field_host, uint32_t w, uint32_t h, fs_vec2 extent, uint32_t* body_out);
+fs_status fs_body_create_from_mask(fs_sim* sim, const uint8_t* mask_host, uint32_t w, uint32_t h, fs_vec2 extent,
+                                   fs_vec2* field_host /* may be NULL */, uint32_t* body_out);
+fs_status fs_body_set_motion(fs_sim* sim, uint32_t body, const fs_body_motion* motion);
+fs_status fs_body_get_motion(const fs_sim* sim, uint32_t body, fs_body_motion* out);
+fs_status fs_body_dims(const fs_sim* sim, uint32_t body, uint32_t* w, uint32_t* h, fs_vec2* extent);
+fs_status fs_body_download(fs_sim* sim, uint32_t body, fs_vec2* dst, size_t n);              /* n == w*h */
+fs_status fs_body_destroy(fs_sim* sim, uint32_t body);
+uint32_t  fs_body_count(const fs_sim* sim);                                                  /* 0 for a NULL handle */
+
 /* ------------------------------------------------ multi-GPU slab mode (build extension) */
 /* NOT in the reference (single wgpu device, src/renderer.rs:108-133).  SURVEY.md §8e: a rank
  * owns the global cell columns [own_lo, own_hi) of the grid (src/simulation.rs:140-141) and

@@ -1,13 +1,18 @@
 """Render a few frames of the dam break to PNG (visual validation on a headless GPU box).
-  python tools/render_frames.py [n] [frames] [outdir] [--faucet[=k]]
+  python tools/render_frames.py [n] [frames] [outdir] [--faucet[=k]] [--paddle]
 --faucet: a tap and an outflow on top of the dam break — every k steps (default 4) a line nozzle of 64 particles
 under the ceiling pours downwards, and every k steps the particles in a box at the floor's right-hand end are removed; the handle
-is created with room for the tap's particles (capacity = 2 n)."""
+is created with room for the tap's particles (capacity = 2 n).
+--paddle: a moving body on top of the dam break — a plate from ceiling to floor, 1.2 thick, that starts just right
+of the block and pushes it against the -x wall at 3 m/s until a quarter of the block's width is left, then stands; its pose is
+set before every step."""
 import os, sys
+import numpy as np
 sys.path.insert(0, os.getcwd())
 import gpu_fluid_simulation_amd as g
 faucet = next((a for a in sys.argv[1:] if a.startswith("--faucet")), None)
-sys.argv = [a for a in sys.argv if not a.startswith("--faucet")]
+paddle = "--paddle" in sys.argv
+sys.argv = [a for a in sys.argv if not a.startswith("--faucet") and a != "--paddle"]
 every = int(faucet.split("=")[1]) if faucet and "=" in faucet else 4
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 16
 frames = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [1, 150, 400, 800]
@@ -16,14 +21,25 @@ os.makedirs(outdir, exist_ok=True)
 st, off, tick = g.dam_break_2d(n)
 sim = g.FluidSimulation(st, device=0, initial_offset=off, capacity=2 * n if faucet else 0)
 sp, (sx, sy) = st.particle_spacing, (st.size.x, st.size.y)
+if paddle:
+    L = round(n ** 0.5) * sp
+    plate = np.full((4, 8), 255, dtype=np.uint8)         # [H, W]: solid but the two end columns in x
+    plate[:, [0, -1]] = 0
+    body = sim.add_body_mask(plate, (1.2, sy))
+    px, stop, u = np.float32(-sx / 2 + L + 0.7), np.float32(-sx / 2 + 0.25 * L), np.float32(-3.0)
 done = 0
 for f in frames:
     while done < f:
+        if paddle:
+            moving = px > stop
+            sim.set_body_motion(body, (px, 0.0), velocity=(float(u) if moving else 0.0, 0.0))
+            if moving:
+                px = px + u * np.float32(tick.delta)
         if faucet and done % every == 0:
             if sim.particle_count + 64 <= sim.capacity:       # +y is down: the tap sits under the ceiling, right of the block
                 sim.emit_nozzle((0.25 * sx, -0.45 * sy), (sp, 0.0), (0.0, sp), (0.0, 4.0), 64, 1)
             sim.remove_box((0.45 * sx, 0.4 * sy), (0.5 * sx, 0.5 * sy))
         sim.tick(tick); done += 1
     img = sim.render_density(640, 400)
-    g.write_png(os.path.join(outdir, f"{'faucet' if faucet else 'dam'}_{n}_{f:05d}.png"), img)
+    g.write_png(os.path.join(outdir, f"{'faucet' if faucet else 'paddle' if paddle else 'dam'}_{n}_{f:05d}.png"), img)
     print("frame", f, "particles", sim.particle_count, "alpha coverage", float((img[..., 3] > 0.5).mean()), flush=True)
