@@ -11,7 +11,7 @@ Mirrors, by name and argument meaning:
   ResizableBuffer                             src/buffer.rs:17-88
 
 One module per handle (sim2d, sim3d, slab, buffers) over what they share (_handle);
-imaging and selftest hold the free functions.  This file only re-exports.
+imaging and selftest hold the free functions, body_dynamics the host-side integrator of a dynamic 2D body.  This file only re-exports.
 """
 from . import _abi
 from ._abi import (  # noqa: F401
@@ -30,6 +30,7 @@ from ._abi import (  # noqa: F401
     SAMPLE3_DTYPE,
     SAMPLE_DTYPE,
     SURFACE_HIT_DTYPE,
+    BodyLoad,
     BodyMotion,
     BodyMotion3,
     Camera3,
@@ -52,10 +53,12 @@ from ._abi import (  # noqa: F401
     load_library,
 )
 from ._handle import FluidSimError, _check  # noqa: F401
+from .body_dynamics import BodyDynamics2D  # noqa: F401
 from .buffers import ImportedBuffer, ResizableBuffer  # noqa: F401
 from .imaging import shade_surface, surface_hit_points, write_obj, write_png  # noqa: F401
 from .selftest import selftest_sort, selftest_sort_policy  # noqa: F401
 from .sim2d import (  # noqa: F401
+    BodyLoads,
     FluidSimulation,
     SimulationSettings,
     build_uniform,

@@ -165,6 +165,15 @@ class BodyMotion(C.Structure):
     _fields_ = [("centre", Vec2), ("rot", C.c_float * 4), ("velocity", Vec2), ("angular_velocity", C.c_float)]
 
 
+FS_BODY_LOAD_SHIFT = 20
+
+
+class BodyLoad(C.Structure):
+    """fs_body_load (include/fluidsim.h "2D body loads"): 48 bytes."""
+    _fields_ = [("impulse_q", C.c_int64 * 2), ("angular_q", C.c_int64), ("hits", C.c_uint64), ("dropped", C.c_uint64),
+                ("steps", C.c_uint64)]
+
+
 class Nozzle3(C.Structure):
     """fs3_nozzle (include/fluidsim.h "3D particle count"): 56 bytes."""
     _fields_ = [("origin", Vec3), ("u", Vec3), ("v", Vec3), ("velocity", Vec3), ("nu", C.c_uint32), ("nv", C.c_uint32)]
@@ -322,6 +331,10 @@ PROTOTYPES = {
     "fs_body_download": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t]),
     "fs_body_destroy": (C.c_int, [_P, C.c_uint32]),
     "fs_body_count": (C.c_uint32, [_P]),
+    "fs_body_loads_enable": (C.c_int, [_P, C.c_int]),
+    "fs_body_loads_enabled": (C.c_int, [_P]),
+    "fs_body_loads": (C.c_int, [_P, C.c_uint32, C.POINTER(BodyLoad), C.c_int]),
+    "fs_body_loads_device": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
     "fs_export_handle": (C.c_int, [_P, C.c_int, _P]),
     "fs_import_open": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "fs_import_read": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t]),

@@ -202,6 +202,14 @@ struct Bodies {
         fs_body_motion motion{};
         size_t pixels() const { return (size_t)w * h; }
     } slot[FS_MAX_BODIES];
+    // Opt-in loads (fs_body_loads_* in engine_features.hip).  words: FS_MAX_BODIES x 5 64-bit words by slot, what
+    // fs_body_loads_device hands out; shards: the pass's scratch, zero between steps; both allocated by the first enable.
+    // steps[k]: steps enqueued with loads on since slot k's words were last zeroed.
+    struct Loads {
+        bool on = false;
+        DevArray<unsigned long long> words, shards;
+        uint64_t steps[FS_MAX_BODIES] = {};
+    } loads;
     bool has(uint32_t k) const { return k < FS_MAX_BODIES && slot[k].w != 0u; }
     uint32_t count() const { uint32_t c = 0; for (const Slot& b : slot) c += b.w ? 1u : 0u; return c; }
     // the lowest free slot, FS_MAX_BODIES when every slot is in use
@@ -209,13 +217,16 @@ struct Bodies {
     // This step's pass, behind the force launches, on the state they stored (A.pos_out / A.vel_out; aos: the live 32-B records,
     // or null): the fields and the motions as they are now, by value, the slots in use in ascending order (fs_body_* order their
     // writes and frees on the stream behind it).  `done`: the step's completion event, which this launch carries in the force
-    // pass's place.  No slot in use: nothing is launched.
-    void enqueue(hipStream_t st, const StepParams& P, const StepArrays& A, void* aos, hipEvent_t done) const {
+    // pass's place.  No slot in use: nothing is launched.  Loads on: the pass's second form and its fold, which carries `done`.
+    void enqueue(hipStream_t st, const StepParams& P, const StepArrays& A, void* aos, hipEvent_t done) {
         Bodies2 B;
+        BodyLoadMap M{};
         uint32_t c = 0;
-        for (const Slot& b : slot) {
+        for (uint32_t k = 0; k < FS_MAX_BODIES; ++k) {
+            const Slot& b = slot[k];
             if (!b.w) continue;
             const fs_body_motion& m = b.motion;
+            M.slot[c] = k;
             Body2& K = B.body[c++];
             K.field = b.field.p; K.w = b.w; K.h = b.h;
             K.ex = b.extent.x; K.ey = b.extent.y;
@@ -227,8 +238,10 @@ struct Bodies {
         }
         if (!c) return;
         for (uint32_t k = c; k < BODIES2_MAX; ++k) B.body[k] = Body2{};
-        B.count = c;
-        launch_bodies(st, P, A, B, aos, done);
+        B.count = M.count = c;
+        if (!loads.on) { launch_bodies(st, P, A, B, aos, done); return; }
+        launch_bodies_loads(st, P, A, B, aos, M, loads.shards.p, loads.words.p, done);
+        for (uint32_t k = 0; k < c; ++k) loads.steps[M.slot[k]] += 1u;
     }
 };
 

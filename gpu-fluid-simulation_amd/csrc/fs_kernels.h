@@ -95,6 +95,20 @@ struct Bodies2 {
 // a body hits gets its new position and velocity there too.  done (may be null): signalled by the kernel's completion, as
 // ForceLaunch::done is.
 void launch_bodies(hipStream_t st, const StepParams& P, const StepArrays& A, const Bodies2& B, void* aos, hipEvent_t done);
+// The same pass while the handle's loads are on (include/fluidsim.h "2D body loads"): k_bodies_loads, which also
+// adds each body's five 64-bit words of this step (sum Q(j.x), sum Q(j.y), sum Q(tz), hits, dropped; by kernel index) into a
+// row of `shards` (BODY_LOAD_SHARDS rows of BODY_LOAD_ROW words, all zero on entry), then k_body_loads_fold, which adds the rows
+// into `words` (FS_MAX_BODIES x 5, by slot: M.slot[kernel index]) and leaves `shards` zero again; the fold carries `done`.
+constexpr uint32_t BODY_LOAD_SHIFT = 20u;      // FS_BODY_LOAD_SHIFT
+constexpr uint32_t BODY_LOAD_WORDS = 5u;
+constexpr uint32_t BODY_LOAD_ROW = BODIES2_MAX * BODY_LOAD_WORDS;
+constexpr uint32_t BODY_LOAD_SHARDS = 64u;
+struct BodyLoadMap {
+    uint32_t count;                    // Bodies2::count
+    uint32_t slot[BODIES2_MAX];
+};
+void launch_bodies_loads(hipStream_t st, const StepParams& P, const StepArrays& A, const Bodies2& B, void* aos, const BodyLoadMap& M,
+                         unsigned long long* shards, unsigned long long* words, hipEvent_t done);
 // Particle tracking (build extension): after the reorder pass of a step, id_out[i] = id_in[src] and, for c < channels,
 // attr_out[c * stride + i] = attr_in[c * stride + src], src = the low word of pairs[i] (the slot before the step).  channels in [0, 4].
 void launch_track_carry(hipStream_t st, uint32_t n, int channels, const u64* pairs, const uint32_t* id_in, uint32_t* id_out,

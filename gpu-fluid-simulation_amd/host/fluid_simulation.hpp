@@ -158,6 +158,16 @@ public:
     }
     void remove_body(uint32_t body) { check(fs_body_destroy(h_, body)); }
     uint32_t body_count() const { return fs_body_count(h_); }
+    // Build extension: 2D body loads (include/fluidsim.h).  The impulse and angular impulse the fluid hands each body, as 64-bit
+    // fixed-point sums (2^-FS_BODY_LOAD_SHIFT per unit particle mass); enabling zeroes them, the particles stay the same bytes.
+    void enable_body_loads(bool on = true) { check(fs_body_loads_enable(h_, on ? 1 : 0)); }
+    bool body_loads_enabled() const { return fs_body_loads_enabled(h_) != 0; }
+    fs_body_load body_loads(uint32_t body, bool reset = false) {          // blocking
+        fs_body_load l{};
+        check(fs_body_loads(h_, body, &l, reset ? 1 : 0));
+        return l;
+    }
+    const void* body_loads_device() { const void* p = nullptr; check(fs_body_loads_device(h_, &p)); return p; }
     // Build extension, NOT in the reference: field sampling (include/fluidsim.h), single-domain handles.  Density, Shepard weight,
     // un-normalised velocity sum, neighbour count and cell of the fluid at any points; `attr` (may be null) receives the channel
     // sums, channel c of query k at c * n + k.  Needs a tick since creation / the last upload.  Coherently ordered points are

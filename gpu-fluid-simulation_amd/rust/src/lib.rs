@@ -145,6 +145,22 @@ impl Default for BodyMotion {
         BodyMotion { centre: Vec2::default(), rot: [1.0, 0.0, 0.0, 1.0], velocity: Vec2::default(), angular_velocity: 0.0 }
     }
 }
+/// fs_body_load: what the fluid handed one 2D body (build extension, include/fluidsim.h "2D body loads"); 48 bytes.  The three
+/// sums are in units of 2^-BODY_LOAD_SHIFT per unit particle mass, modulo 2^64.
+#[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct BodyLoad { pub impulse_q: [i64; 2], pub angular_q: i64, pub hits: u64, pub dropped: u64, pub steps: u64 }
+const _: () = assert!(std::mem::size_of::<BodyLoad>() == 48);
+/// FS_BODY_LOAD_SHIFT
+pub const BODY_LOAD_SHIFT: u32 = 20;
+impl BodyLoad {
+    /// Momentum handed to the body: `impulse_q * 2^-20 * mass`, `mass` the mass of one particle.
+    pub fn impulse(&self, mass: f64) -> [f64; 2] {
+        let k = mass / (1u64 << BODY_LOAD_SHIFT) as f64;
+        [self.impulse_q[0] as f64 * k, self.impulse_q[1] as f64 * k]
+    }
+    /// Angular momentum about the body's centre handed to the body, counter-clockwise positive.
+    pub fn angular_impulse(&self, mass: f64) -> f64 { self.angular_q as f64 * mass / (1u64 << BODY_LOAD_SHIFT) as f64 }
+}
 /// FS_MAX_BODIES: the body slots of a 2D handle.
 pub const MAX_BODIES: u32 = 8;
 /// FS3_MAX_BODIES: the body slots of a 3D handle.
@@ -221,6 +237,10 @@ extern "C" {
     fn fs_body_download(sim: *mut fs_sim, body: u32, dst: *mut Vec2, n: usize) -> c_int;
     fn fs_body_destroy(sim: *mut fs_sim, body: u32) -> c_int;
     fn fs_body_count(sim: *const fs_sim) -> u32;
+    fn fs_body_loads_enable(sim: *mut fs_sim, on: c_int) -> c_int;
+    fn fs_body_loads_enabled(sim: *const fs_sim) -> c_int;
+    fn fs_body_loads(sim: *mut fs_sim, body: u32, out: *mut BodyLoad, reset: c_int) -> c_int;
+    fn fs_body_loads_device(sim: *mut fs_sim, words: *mut *const c_void) -> c_int;
     // profiling
     fn fs_profile_enable(sim: *mut fs_sim, enable: c_int) -> c_int;
     fn fs_profile_read(sim: *mut fs_sim, ms: *mut f64, steps: *mut u64, reset: c_int) -> c_int;
@@ -512,6 +532,22 @@ impl FluidSimulation {
     /// Destroys a body and frees its slot; the other bodies keep theirs.  Blocking.
     pub fn remove_body(&mut self, body: u32) { check(unsafe { fs_body_destroy(self.raw, body) }); }
     pub fn body_count(&self) -> u32 { unsafe { fs_body_count(self.raw) } }
+    /// Build extension: 2D body loads (include/fluidsim.h).  Turns the per-body sums of what the fluid hands each body on or off;
+    /// enabling zeroes them.  The particles are the same bytes either way.
+    pub fn enable_body_loads(&mut self, on: bool) { check(unsafe { fs_body_loads_enable(self.raw, on as c_int) }); }
+    pub fn body_loads_enabled(&self) -> bool { unsafe { fs_body_loads_enabled(self.raw) != 0 } }
+    /// A body's load words since they were last zeroed (blocking); `reset` zeroes them behind the read.
+    pub fn body_loads(&mut self, body: u32, reset: bool) -> BodyLoad {
+        let mut l = BodyLoad::default();
+        check(unsafe { fs_body_loads(self.raw, body, &mut l, reset as c_int) });
+        l
+    }
+    /// Device address of the `MAX_BODIES x 5` 64-bit words, by slot, for a consumer on the handle's stream.
+    pub fn body_loads_device(&mut self) -> *const c_void {
+        let mut p: *const c_void = std::ptr::null();
+        check(unsafe { fs_body_loads_device(self.raw, &mut p) });
+        p
+    }
     /// `start_indices` to the host (the renderer's second storage binding; u32[grid_w * grid_h]).
     pub fn download_start_indices(&mut self) -> Vec<u32> {
         let (w, h) = self.grid_dims();

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (FS_MATH_IEEE, FS_SORT_BITONIC, PARTICLE_DTYPE, SAMPLE_DTYPE, BodyMotion, Nozzle, Options, Settings, SortStep, TickSettings,
+from ._abi import (FS_MATH_IEEE, FS_SORT_BITONIC, PARTICLE_DTYPE, SAMPLE_DTYPE, BodyLoad, BodyMotion, Nozzle, Options, Settings, SortStep, TickSettings,
                    Uniform, UVec2, Vec2, load_library)
 from ._handle import _check, _Count, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec2
 
@@ -230,6 +230,30 @@ class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Simulation):
     def body_count(self):
         return int(self._fn("body_count")(self._h))
 
+    # -- 2D body loads (build extension) -----------------------
+    def enable_body_loads(self, on=True):
+        """Turns the per-body load sums on or off (include/fluidsim.h "2D body loads").  Enabling zeroes every body's words.  While
+        off a step launches what it launched without them; while on the particles are still byte for byte the same."""
+        self._call("body_loads_enable", 1 if on else 0)
+
+    @property
+    def body_loads_enabled(self):
+        return bool(self._fn("body_loads_enabled")(self._h))
+
+    def body_loads(self, body, reset=False):
+        """What the fluid handed body `body` since its words were last zeroed: a BodyLoads record.  Blocking (one sync);
+        reset=True zeroes the slot's words behind the read."""
+        out = BodyLoad()
+        self._call("body_loads", int(body), C.byref(out), 1 if reset else 0)
+        return BodyLoads((int(out.impulse_q[0]), int(out.impulse_q[1])), int(out.angular_q), int(out.hits), int(out.dropped),
+                         int(out.steps))
+
+    def body_loads_device_ptr(self):
+        """fs_body_loads_device: the device address of the 8 x 5 64-bit words, by slot, for a consumer on the handle's stream."""
+        p = C.c_void_p()
+        self._call("body_loads_device", C.byref(p))
+        return p.value
+
     def export_handle(self, which=_abi.FS_EXPORT_PARTICLES):
         """fs_export_handle: interprocess handle of the AoS particle view (switches on the live view) or of start_indices."""
         h = _abi.MemHandle()
@@ -245,6 +269,40 @@ class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Simulation):
         p, n = C.c_void_p(), C.c_size_t()
         self._call("start_indices_device", C.byref(p), C.byref(n))
         return p.value, int(n.value)
+
+
+class BodyLoads:
+    """One body's load words (include/fluidsim.h "2D body loads"): the raw integers impulse_q (x, y) and angular_q in units of
+    2^-20 velocity (and velocity * length) per unit particle mass, `hits`, `dropped`, and `steps`, the steps they were summed
+    over.  The float64 views multiply by 2^-20 and the mass of one particle."""
+    SCALE = 2.0 ** -_abi.FS_BODY_LOAD_SHIFT
+
+    def __init__(self, impulse_q, angular_q, hits, dropped, steps):
+        self.impulse_q, self.angular_q, self.hits, self.dropped, self.steps = tuple(impulse_q), angular_q, hits, dropped, steps
+
+    def words(self):
+        """the five device words as Python ints modulo 2^64, in the device's order"""
+        m = (1 << 64) - 1
+        return [self.impulse_q[0] & m, self.impulse_q[1] & m, self.angular_q & m, self.hits, self.dropped]
+
+    def impulse(self, mass):
+        """momentum handed to the body, float64 [2]"""
+        return np.array([q * self.SCALE * float(mass) for q in self.impulse_q], dtype=np.float64)
+
+    def angular_impulse(self, mass):
+        """angular momentum about the body's centre handed to the body, counter-clockwise positive"""
+        return self.angular_q * self.SCALE * float(mass)
+
+    def mean_force(self, mass, dt):
+        """the impulse divided by steps * dt (zero steps: zero)"""
+        return self.impulse(mass) / (self.steps * float(dt)) if self.steps else np.zeros(2)
+
+    def mean_torque(self, mass, dt):
+        return self.angular_impulse(mass) / (self.steps * float(dt)) if self.steps else 0.0
+
+    def __repr__(self):
+        return (f"BodyLoads(impulse_q={self.impulse_q}, angular_q={self.angular_q}, hits={self.hits}, dropped={self.dropped}, "
+                f"steps={self.steps})")
 
 
 def rigid_motion2d(centre0, velocity, rate, t):

@@ -468,8 +468,9 @@ uint32_t fs_track_next_id(const fs_sim* sim);
  * free space, over the body's own box [-extent/2, extent/2] in the BODY frame, with a pose and a velocity the host sets per step.
  * The vectors are in world units of the body frame — not the pixel units of the force texture (fs_upload_force_field), which
  * stays what it was: one domain-wide static field, pushed out inside move_particle.  The fluid feels the body (one-way
- * coupling): the engine neither integrates the pose nor computes forces on the body.  A handle without a body launches exactly
- * the kernels it launched before and computes the same bits.
+ * coupling): the engine neither integrates the pose nor computes forces on the body — it can REPORT what the fluid hands each
+ * body, see "2D body loads" below, and a host that integrates the pose from that closes the loop.  A handle without a body
+ * launches exactly the kernels it launched before and computes the same bits.
  *
  * With bodies present, a step is B_7(...B_0(step(state))): the whole reference step first, its texture push-out and its wall
  * clamp included, then the operator of each existing body in ascending slot order, on the position p and the velocity v the step
@@ -538,6 +539,58 @@ fs_status fs_body_dims(const fs_sim* sim, uint32_t body, uint32_t* w, uint32_t* 
 fs_status fs_body_download(fs_sim* sim, uint32_t body, fs_vec2* dst, size_t n);              /* n == w*h */
 fs_status fs_body_destroy(fs_sim* sim, uint32_t body);
 uint32_t  fs_body_count(const fs_sim* sim);                                                  /* 0 for a NULL handle */
+
+/* ------------------------------------------------ 2D body loads (build extension, opt-in per handle) */
+/* The impulse and the angular impulse the fluid gives each body of "2D moving bodies", summed on the GPU inside the bodies' own
+ * pass.  fs_body_loads_enable(sim, on) turns them on or off.  While off, a step launches exactly the kernels it launches without
+ * this section and leaves the same bytes.  While on, the particle state is still byte for byte that of "2D moving bodies": loads
+ * only observe.
+ *
+ * A HIT of body b is a particle that reaches the line `p.a = p.a + f.a` of the operator B_b above.  With that section's names:
+ *   v0   the velocity on entry to B_b: after the step and after the operators of the lower slots (their wall re-clamp included);
+ *   v1.a = us.a + (r.a - k*n.a): the velocity B_b computes, BEFORE its wall re-clamp — what the wall does is not the body's load;
+ *   s.a  = p.a - c.a: the pushed position relative to the centre, before the re-clamp.
+ * f32 without contraction, one operation per line:
+ *     j.x = v0.x - v1.x;   j.y = v0.y - v1.y     (impulse on the body per unit particle mass: minus the particle's velocity change)
+ *     t0 = s.x * j.y;   t1 = s.y * j.x;   tz = t0 - t1     (angular impulse about the body's centre, counter-clockwise positive)
+ * The positional push p += f carries no momentum and is not counted.
+ *
+ * Fixed point: Q(x) is the signed 64-bit integer nearest to x * 2^FS_BODY_LOAD_SHIFT, ties to even (the product is exact in f32,
+ * so every correctly rounded route gives the same integer).  If any of j.x, j.y, tz is NaN or fails fabsf(x) < 16384.0f (2^14),
+ * the hit adds nothing to the three sums and is counted in `dropped`; its particle is moved exactly as without loads.  Per body
+ * the engine keeps five 64-bit words: sum Q(j.x), sum Q(j.y), sum Q(tz), hits (every hit, dropped ones included) and dropped,
+ * each sum modulo 2^64 over all hits of all steps since the words were last zeroed.  |Q| < 2^34 and a step has at most 2^28
+ * particles, so one step cannot wrap; at |j| < 2^7 and 16 M hits per step wrapping is thousands of steps away.  The engine does
+ * not guard it: read with reset != 0 often enough.  Integer sums are associative, so the words are ONE defined value whatever the
+ * order of lanes, waves and workgroups: identical from run to run and equal to a host sum of Q over the hits.
+ * Momentum handed to body b = impulse_q * 2^-FS_BODY_LOAD_SHIFT * (the mass of one particle), in world units.
+ *
+ * Enabling (also when already on) zeroes every slot's words and `steps`.  A body created while loads are on starts at zero; a
+ * destroyed slot's words are zeroed before the slot can be reused.  Steps taken while loads are off count nothing, and disabling
+ * keeps the words (they cannot be read until the next enable, which zeroes them).  fs_body_loads is blocking and ordered on
+ * fs_stream(sim): it returns the words behind every step enqueued so far; reset != 0 zeroes that slot's words and `steps` behind
+ * the read, on the stream.  fs_body_loads_device hands out the device address of FS_MAX_BODIES x 5 64-bit words, by slot, in the
+ * order above, for a consumer on the stream: it holds the finished values once any step has completed (the step's last launch
+ * folds the pass's partial sums into it; the address is stable until the handle is destroyed).
+ *
+ * Checks, in this order, FS_ERR_INVALID unless stated; a refused call changes nothing:
+ *  1. NULL handle (fs_body_loads_enabled: 0).
+ *  2. A slab handle -> FS_ERR_UNSUPPORTED.
+ *  3. NULL out pointer (`out`, `words`).
+ *  4. fs_body_loads: a slot that holds no body.
+ *  5. fs_body_loads, fs_body_loads_device: loads are not enabled ("not enabled").
+ * FS_ABI_VERSION is unchanged.  See DESIGN.md §25. */
+#define FS_BODY_LOAD_SHIFT 20
+typedef struct fs_body_load {
+    int64_t  impulse_q[2];   /* sum Q(j.x), sum Q(j.y): times 2^-20 times the particle mass = momentum handed to the body */
+    int64_t  angular_q;      /* sum Q(tz) */
+    uint64_t hits, dropped;
+    uint64_t steps;          /* steps enqueued with loads on since the words were zeroed (host-side count) */
+} fs_body_load;
+fs_status fs_body_loads_enable(fs_sim* sim, int on);
+int       fs_body_loads_enabled(const fs_sim* sim);                                         /* 0 for a NULL handle */
+fs_status fs_body_loads(fs_sim* sim, uint32_t body, fs_body_load* out, int reset);           /* blocking */
+fs_status fs_body_loads_device(fs_sim* sim, const void** words);
 
 /* ------------------------------------------------ multi-GPU slab mode (build extension) */
 /* NOT in the reference (single wgpu device, src/renderer.rs:108-133).  SURVEY.md §8e: a rank

@@ -1,18 +1,24 @@
 """Render a few frames of the dam break to PNG (visual validation on a headless GPU box).
-  python tools/render_frames.py [n] [frames] [outdir] [--faucet[=k]] [--paddle]
+  python tools/render_frames.py [n] [frames] [outdir] [--faucet[=k]] [--paddle] [--float]
 --faucet: a tap and an outflow on top of the dam break — every k steps (default 4) a line nozzle of 64 particles
 under the ceiling pours downwards, and every k steps the particles in a box at the floor's right-hand end are removed; the handle
 is created with room for the tap's particles (capacity = 2 n).
 --paddle: a moving body on top of the dam break — a plate from ceiling to floor, 1.2 thick, that starts just right
 of the block and pushes it against the -x wall at 3 m/s until a quarter of the block's width is left, then stands; its pose is
-set before every step."""
+set before every step.
+--float: a dynamic body — a square box of half the fluid's density released above the block falls into the dam
+break; the handle's body loads are on and BodyDynamics2D integrates them on the host between the steps (one sync per step): the
+fluid's impulses slow and turn it (the bodies' contact model hands over momentum where particles are pushed out of the box, it is
+no pressure integral, so the box sinks, slower than it would fall), and the host stops it at the floor.  Prints the box's pose
+with every frame."""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.getcwd())
 import gpu_fluid_simulation_amd as g
 faucet = next((a for a in sys.argv[1:] if a.startswith("--faucet")), None)
 paddle = "--paddle" in sys.argv
-sys.argv = [a for a in sys.argv if not a.startswith("--faucet") and a != "--paddle"]
+floating = "--float" in sys.argv
+sys.argv = [a for a in sys.argv if not a.startswith("--faucet") and a not in ("--paddle", "--float")]
 every = int(faucet.split("=")[1]) if faucet and "=" in faucet else 4
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 16
 frames = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [1, 150, 400, 800]
@@ -27,6 +33,19 @@ if paddle:
     plate[:, [0, -1]] = 0
     body = sim.add_body_mask(plate, (1.2, sy))
     px, stop, u = np.float32(-sx / 2 + L + 0.7), np.float32(-sx / 2 + 0.25 * L), np.float32(-3.0)
+if floating:
+    L = round(n ** 0.5) * sp
+    side = 0.125 * L
+    box = np.full((8, 8), 255, dtype=np.uint8)           # solid but its rim: the field pushes out of every side
+    box[[0, -1], :] = 0
+    box[:, [0, -1]] = 0
+    floater = sim.add_body_mask(box, (side, side))
+    # half as dense as the fluid it displaces (one particle of mass tick.mass per sp^2)
+    mass = 0.5 * tick.mass * (side / sp) ** 2
+    dyn = g.BodyDynamics2D(mass, mass * side * side / 6.0, (-sx / 2 + 0.5 * L, sy / 2 - L - side), gravity=(tick.gravity.x, tick.gravity.y),
+                           particle_mass=tick.mass)
+    sim.enable_body_loads()
+    sim.set_body_motion(floater, *dyn.motion())
 done = 0
 for f in frames:
     while done < f:
@@ -40,6 +59,13 @@ for f in frames:
                 sim.emit_nozzle((0.25 * sx, -0.45 * sy), (sp, 0.0), (0.0, sp), (0.0, 4.0), 64, 1)
             sim.remove_box((0.45 * sx, 0.4 * sy), (0.5 * sx, 0.5 * sy))
         sim.tick(tick); done += 1
+        if floating:
+            dyn.advance(sim, floater, tick)
+            if dyn.centre[1] > 0.5 * (sy - side):             # +y is down: the floor
+                dyn.centre[1], dyn.velocity[1] = 0.5 * (sy - side), 0.0
+                sim.set_body_motion(floater, *dyn.motion())
     img = sim.render_density(640, 400)
-    g.write_png(os.path.join(outdir, f"{'faucet' if faucet else 'paddle' if paddle else 'dam'}_{n}_{f:05d}.png"), img)
+    g.write_png(os.path.join(outdir, f"{'faucet' if faucet else 'paddle' if paddle else 'float' if floating else 'dam'}_{n}_{f:05d}.png"), img)
     print("frame", f, "particles", sim.particle_count, "alpha coverage", float((img[..., 3] > 0.5).mean()), flush=True)
+    if floating:
+        print("  box centre", dyn.centre.tolist(), "angle", dyn.angle, "velocity", dyn.velocity.tolist(), flush=True)
