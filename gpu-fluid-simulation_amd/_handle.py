@@ -1,6 +1,6 @@
 """What the handles of the C ABI share: the status check, the marshalling helpers, the life cycle of a handle, the calls that
 exist under both the `fs_` and the `fs3_` prefix, and the features (tracking, surface-tension read-outs, a particle count that
-changes at run time) that are the same for 2D and 3D once the prefix, the record dtype and the vector width come from the class."""
+changes at run time, moving bodies) that are the same for 2D and 3D once the prefix, the record dtype and the vector width come from the class."""
 import ctypes as C
 
 import numpy as np
@@ -108,6 +108,9 @@ class _Simulation(_Engine):
     _record = None
     _dim = None
 
+    def _vec(self, a):
+        return _vec2(a) if self._dim == 2 else _vec3(a)
+
     def tick(self, tick_settings):
         self._call("step", C.byref(tick_settings))
 
@@ -150,9 +153,6 @@ class _Count:
     structure (fs_nozzle / fs3_nozzle); vectors have `_dim` components."""
     _nozzle = None
 
-    def _vec(self, a):
-        return _vec2(a) if self._dim == 2 else _vec3(a)
-
     @property
     def capacity(self):
         """Slots of the handle: particle_count can grow to this (reserve() raises it)."""
@@ -192,6 +192,61 @@ class _Count:
     def next_id(self):
         """The id the next emitted particle gets while tracking is on (0 when it is off)."""
         return int(self._fn("track_next_id")(self._h))
+
+
+class _Bodies:
+    """Opt-in moving rigid bodies (build extension; DESIGN.md §24, 3D: §23).  A field is a float32 [H, W, 2] or [D, H, W, 3]
+    array, a mask a uint8 [H, W] or [D, H, W] one: `_dim` axes, slowest first (the C calls take the extents fastest first), and
+    `_dim` components.  set_body_motion and body_motion stay per class: their defaults and the angular velocity (a scalar in 2D, a
+    vector in 3D) differ."""
+
+    def _axes(self):
+        return "H, W" if self._dim == 2 else "D, H, W"
+
+    def add_body(self, field, extent):
+        """A kinematic rigid body: a field of push vectors in world units (zero = free space) over the body's own box
+        [-extent/2, extent/2] in the body frame (include/fluidsim.h "2D moving bodies" / "3D moving bodies").  Returns its slot, the
+        lowest free one of 0 .. 7.  Blocking.  The body starts at the origin with the identity pose, at rest: set_body_motion
+        places it."""
+        f = np.ascontiguousarray(field, dtype=np.float32)
+        if f.ndim != self._dim + 1 or f.shape[-1] != self._dim:
+            raise ValueError(f"add_body expects a [{self._axes()}, {self._dim}] float32 array")
+        slot = C.c_uint32()
+        self._call("body_create", _ptr(f), *[int(n) for n in f.shape[-2::-1]], self._vec(extent), C.byref(slot))
+        return int(slot.value)
+
+    def add_body_mask(self, mask, extent, want_field=False):
+        """The body of a mask (> 128: solid) over the box `extent`: the exact distance transform of set_collider_mask's producer
+        on the body's box (in 2D: not set_obstacle_image's chamfer).  Returns the slot, with want_field=True (slot, the field)."""
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        if m.ndim != self._dim:
+            raise ValueError(f"add_body_mask expects a [{self._axes()}] uint8 array")
+        out = np.zeros(m.shape + (self._dim,), dtype=np.float32) if want_field else None
+        slot = C.c_uint32()
+        self._call("body_create_from_mask", _ptr(m), *[int(n) for n in m.shape[::-1]], self._vec(extent),
+                   _ptr(out) if want_field else None, C.byref(slot))
+        return (int(slot.value), out) if want_field else int(slot.value)
+
+    def body_dims(self, body):
+        """((W, H), (ex, ey)) or ((W, H, D), (ex, ey, ez)) of a body: its field's extents and its box."""
+        n, e = [C.c_uint32() for _ in range(self._dim)], self._vec((0.0,) * self._dim)
+        self._call("body_dims", int(body), *[C.byref(k) for k in n], C.byref(e))
+        return tuple(int(k.value) for k in n), tuple(float(getattr(e, a)) for a in "xyz"[:self._dim])
+
+    def body_field(self, body):
+        """A body's field as a float32 [H, W, 2] or [D, H, W, 3] array.  Blocking."""
+        shape = self.body_dims(body)[0][::-1]
+        out = np.zeros(shape + (self._dim,), dtype=np.float32)
+        self._call("body_download", int(body), _ptr(out), int(np.prod(shape)))
+        return out
+
+    def remove_body(self, body):
+        """Destroys a body and frees its slot; the other bodies keep theirs.  Blocking."""
+        self._call("body_destroy", int(body))
+
+    @property
+    def body_count(self):
+        return int(self._fn("body_count")(self._h))
 
 
 class _Tracking:

@@ -1,7 +1,8 @@
 // engine.h — what the host files of the C ABI share beyond fs_host.h: the 2D simulation handle and the state of each of its
 // features, the step parameters, and the device check and create-time proofs (also used by the 3D handle's files through
 // engine_3d.h).  The handle's files:
-// engine.hip (life cycle, step, transfers, renderer hand-off), engine_features.hip (surface tension, particle tracking, moving bodies),
+// engine.hip (life cycle, step, transfers, renderer hand-off), engine_features.hip (surface tension, particle tracking, moving bodies;
+// what the bodies share with the 3D handle's engine_3d_features.hip: engine_bodies.h, and BodySlots below),
 // engine_query.hip (density render, field sampling), engine_count.hip (a particle count that changes at run time; what it
 // shares with the 3D handle's engine_3d_count.hip: engine_count.h, and Tracking and RemoveScratch below),
 // engine_selftest.hip (self-tests, read-outs), engine_slab.hip (the multi-GPU slab handles).  Internal: include/fluidsim.h is the interface.
@@ -191,17 +192,29 @@ struct Tracking {
     }
 };
 
+// The slot table of the moving bodies of either handle (Bodies below, fs_sim3::Bodies in engine_3d.h): MAX slots of a type whose
+// w == 0 says that the slot is free.
+template <class Slot, uint32_t MAX>
+struct BodySlots {
+    Slot slot[MAX];
+    bool has(uint32_t k) const { return k < MAX && slot[k].w != 0u; }
+    uint32_t count() const { uint32_t c = 0; for (const Slot& b : slot) c += b.w ? 1u : 0u; return c; }
+    // the lowest free slot, MAX when every slot is in use
+    uint32_t free_slot() const { uint32_t k = 0; while (k < MAX && slot[k].w) ++k; return k; }
+};
+
 // Opt-in moving bodies (build extension; single-domain handles): fs_body_* in engine_features.hip.  Per slot a
 // field of push vectors over the body's own box and the motion the host last set; w == 0: the slot is free, and never created:
 // no allocation, no launch.
-struct Bodies {
-    struct Slot {
-        DevArray<float2> field;
-        uint32_t w = 0, h = 0;
-        fs_vec2 extent{};
-        fs_body_motion motion{};
-        size_t pixels() const { return (size_t)w * h; }
-    } slot[FS_MAX_BODIES];
+struct BodySlot2 {
+    DevArray<float2> field;
+    uint32_t w = 0, h = 0;
+    fs_vec2 extent{};
+    fs_body_motion motion{};
+    size_t pixels() const { return (size_t)w * h; }
+};
+struct Bodies : BodySlots<BodySlot2, FS_MAX_BODIES> {
+    using Slot = BodySlot2;
     // Opt-in loads (fs_body_loads_* in engine_features.hip).  words: FS_MAX_BODIES x 5 64-bit words by slot, what
     // fs_body_loads_device hands out; shards: the pass's scratch, zero between steps; both allocated by the first enable.
     // steps[k]: steps enqueued with loads on since slot k's words were last zeroed.
@@ -210,10 +223,6 @@ struct Bodies {
         DevArray<unsigned long long> words, shards;
         uint64_t steps[FS_MAX_BODIES] = {};
     } loads;
-    bool has(uint32_t k) const { return k < FS_MAX_BODIES && slot[k].w != 0u; }
-    uint32_t count() const { uint32_t c = 0; for (const Slot& b : slot) c += b.w ? 1u : 0u; return c; }
-    // the lowest free slot, FS_MAX_BODIES when every slot is in use
-    uint32_t free_slot() const { uint32_t k = 0; while (k < FS_MAX_BODIES && slot[k].w) ++k; return k; }
     // This step's pass, behind the force launches, on the state they stored (A.pos_out / A.vel_out; aos: the live 32-B records,
     // or null): the fields and the motions as they are now, by value, the slots in use in ascending order (fs_body_* order their
     // writes and frees on the stream behind it).  `done`: the step's completion event, which this launch carries in the force

@@ -3,8 +3,10 @@
 // engine_3d.hip (lattice, life cycle, step, getters, transfers, timing), engine_3d_features.hip (what the step enqueues for:
 // colliders, moving bodies, surface tension, tracking), engine_3d_query.hip (everything behind sample_stale: sampling, rendering, extraction),
 // engine_3d_count.hip (a particle count that changes at run time: reserve, emit, remove; what it shares with the 2D handle's
-// engine_count.hip: engine_count.h).
-// From the 2D engine (engine.h): the device check, the create-time proofs, the owners, the sort policy, Tracking and RemoveScratch.
+// engine_count.hip: engine_count.h).  What the bodies and the collider's mask producer share with the 2D handle's
+// engine_features.hip: engine_bodies.h.
+// From the 2D engine (engine.h): the device check, the create-time proofs, the owners, the sort policy, Tracking, RemoveScratch
+// and BodySlots.
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -86,18 +88,15 @@ struct fs_sim3 {
     } collider;
     // The opt-in moving bodies: per slot a voxel field over the body's own box and the motion the host last set;
     // w == 0: the slot is free, and never created: no allocation, no launch.
-    struct Bodies {
-        struct Slot {
-            fsd::DevArray<float4> field;
-            uint32_t w = 0, h = 0, d = 0;
-            fs_vec3 extent{};
-            fs3_body_motion motion{};
-            size_t voxels() const { return (size_t)w * h * d; }
-        } slot[FS3_MAX_BODIES];
-        bool has(uint32_t k) const { return k < FS3_MAX_BODIES && slot[k].w != 0u; }
-        uint32_t count() const { uint32_t c = 0; for (const Slot& b : slot) c += b.w ? 1u : 0u; return c; }
-        // the lowest free slot, FS3_MAX_BODIES when every slot is in use
-        uint32_t free_slot() const { uint32_t k = 0; while (k < FS3_MAX_BODIES && slot[k].w) ++k; return k; }
+    struct BodySlot {
+        fsd::DevArray<float4> field;
+        uint32_t w = 0, h = 0, d = 0;
+        fs_vec3 extent{};
+        fs3_body_motion motion{};
+        size_t voxels() const { return (size_t)w * h * d; }
+    };
+    struct Bodies : fsd::BodySlots<BodySlot, FS3_MAX_BODIES> {      // has, count, free_slot: engine.h
+        using Slot = BodySlot;
         // What a step takes, by value into *B: the fields and the motions as they are when it is enqueued, the slots in use in
         // ascending order (fs3_body_* order their writes and frees on the stream behind it).  Null: no slot is in use.
         const fsd::Bodies3* for_step(fsd::Bodies3* B) const {

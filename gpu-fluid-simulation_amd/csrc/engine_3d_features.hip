@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "engine_3d.h"
+#include "engine_bodies.h"
 
 using fsd::DevArray;
 using fsd::fail;
@@ -19,32 +20,17 @@ fs_status collider3_check(const void* array, uint32_t w, uint32_t h, uint32_t d)
     return FS_OK;
 }
 
-// The producer of §18 on a host mask, blocking: the push field of a w x h x d mask over a box of `size` into `field` (device,
-// w * h * d vectors).  Its staging and scratch live for the call.  The stream is synchronised before they are freed, whatever
-// happened.
-fs_status mask_to_field3(hipStream_t st, const uint8_t* mask, uint32_t w, uint32_t h, uint32_t d, fs_vec3 size, float4* field,
-                         const DevArray<uint8_t>& dmask, const DevArray<uint32_t>& near_x, const DevArray<uint32_t>& near_xy) {
-    fsd::ColliderMask3 Q;
-    Q.mask = dmask.p; Q.w = w; Q.h = h; Q.d = d;
-    Q.vx = size.x / (float)w; Q.vy = size.y / (float)h; Q.vz = size.z / (float)d;
-    Q.near_x = near_x.p; Q.near_xy = near_xy.p; Q.field = field;
-    hipError_t e = hipMemcpyAsync(dmask.p, mask, (size_t)w * h * d, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) { fsd::launch3_collider_from_mask(st, Q); e = hipGetLastError(); }
-    const hipError_t es = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = es;
-    return e == hipSuccess ? FS_OK : fail(FS_ERR_DEVICE, hipGetErrorString(e));
-}
-
-bool mask_has_free_voxel(const uint8_t* mask, size_t voxels) {
-    for (size_t k = 0; k < voxels; ++k) if (!(mask[k] > 128)) return true;
-    return false;
-}
-
 // Checks 3 and 4 of the two body constructors (the handle and the pointers first, by the caller).
 fs_status body3_check(uint32_t w, uint32_t h, uint32_t d, fs_vec3 extent) {
     FS_TRY(collider3_check(&extent, w, h, d));
-    const auto good = [](float a) { return std::isfinite(a) && a > 0.0f; };
-    if (!good(extent.x) || !good(extent.y) || !good(extent.z)) return fail(FS_ERR_INVALID, "body: a box extent that is not finite and > 0");
+    if (!fsd::all_positive(&extent.x, 3)) return fail(FS_ERR_INVALID, "body: a box extent that is not finite and > 0");
+    return FS_OK;
+}
+
+// The per-body calls' checks: the handle and the pointers (`null`), then the slot.
+fs_status body3_slot(const fs_sim3* s, bool null, uint32_t body) {
+    if (!s || null) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->bodies.has(body)) return fail(FS_ERR_INVALID, "body: the slot holds no body");
     return FS_OK;
 }
 
@@ -96,16 +82,15 @@ fs_status fs3_collider_from_mask(fs_sim3* s, const uint8_t* mask, uint32_t w, ui
     if (!s) return fail(FS_ERR_INVALID, "null argument");
     FS_TRY(collider3_check(mask, w, h, d));
     const size_t voxels = (size_t)w * h * d;
-    if (!mask_has_free_voxel(mask, voxels)) return fail(FS_ERR_INVALID, "collider: the mask has no free voxel");
+    if (!fsd::mask_has_free(mask, voxels)) return fail(FS_ERR_INVALID, "collider: the mask has no free voxel");
     FS_HIP(hipSetDevice(s->device));
-    DevArray<uint8_t> dmask;
-    DevArray<uint32_t> near_x, near_xy;
-    if (dmask.alloc(voxels) != hipSuccess || near_x.alloc(voxels) != hipSuccess || near_xy.alloc(voxels) != hipSuccess) {
+    fsd::MaskStaging stage;
+    if (stage.alloc(voxels) != hipSuccess) {
         (void)hipGetLastError();
         return fail(FS_ERR_OOM, "collider: device staging");
     }
     FS_TRY(s->collider.reserve(s->stream, voxels));
-    const fs_status r = mask_to_field3(s->stream, mask, w, h, d, s->st.size, s->collider.field.p, dmask, near_x, near_xy);
+    const fs_status r = mask_to_field3(s->stream, mask, w, h, d, s->st.size, s->collider.field.p, stage);
     if (r != FS_OK) { s->collider.clear(); return r; }
     s->collider.set(w, h, d);
     return field_host ? collider3_read(s, field_host) : FS_OK;
@@ -165,19 +150,17 @@ fs_status fs3_body_create_from_mask(fs_sim3* s, const uint8_t* mask, uint32_t w,
     if (!mask || !body_out) return fail(FS_ERR_INVALID, "null argument");
     FS_TRY(body3_check(w, h, d, extent));
     const size_t voxels = (size_t)w * h * d;
-    if (!mask_has_free_voxel(mask, voxels)) return fail(FS_ERR_INVALID, "body: the mask has no free voxel");
+    if (!fsd::mask_has_free(mask, voxels)) return fail(FS_ERR_INVALID, "body: the mask has no free voxel");
     const uint32_t slot = s->bodies.free_slot();
     if (slot == FS3_MAX_BODIES) return fail(FS_ERR_INVALID, "body: no free slot");
     FS_HIP(hipSetDevice(s->device));
-    DevArray<uint8_t> dmask;
-    DevArray<uint32_t> near_x, near_xy;
+    fsd::MaskStaging stage;
     DevArray<float4> dev;
-    if (dmask.alloc(voxels) != hipSuccess || near_x.alloc(voxels) != hipSuccess || near_xy.alloc(voxels) != hipSuccess ||
-        dev.alloc(voxels) != hipSuccess) {
+    if (stage.alloc(voxels) != hipSuccess || dev.alloc(voxels) != hipSuccess) {
         (void)hipGetLastError();
         return fail(FS_ERR_OOM, "body: device staging");
     }
-    FS_TRY(mask_to_field3(s->stream, mask, w, h, d, extent, dev.p, dmask, near_x, near_xy));
+    FS_TRY(mask_to_field3(s->stream, mask, w, h, d, extent, dev.p, stage));
     if (field_host) FS_TRY(fsd::download_vec3(s->stream, dev.p, voxels, field_host));
     body3_install(s, slot, std::move(dev), w, h, d, extent);
     *body_out = slot;
@@ -185,10 +168,9 @@ fs_status fs3_body_create_from_mask(fs_sim3* s, const uint8_t* mask, uint32_t w,
 }
 
 fs_status fs3_body_set_motion(fs_sim3* s, uint32_t body, const fs3_body_motion* m) {
-    if (!s || !m) return fail(FS_ERR_INVALID, "null argument");
-    if (!s->bodies.has(body)) return fail(FS_ERR_INVALID, "body: the slot holds no body");
-    const float* f = &m->centre.x;              // 18 floats, nothing between them (static_assert below)
-    for (int k = 0; k < 18; ++k) if (!std::isfinite(f[k])) return fail(FS_ERR_INVALID, "body: non-finite motion");
+    FS_TRY(body3_slot(s, !m, body));
+    // 18 floats, nothing between them (static_assert below)
+    if (!fsd::all_finite(&m->centre.x, 18)) return fail(FS_ERR_INVALID, "body: non-finite motion");
     s->bodies.slot[body].motion = *m;           // host memory only: the next enqueue takes it by value
     return FS_OK;
 }
@@ -196,23 +178,20 @@ static_assert(sizeof(fs3_body_motion) == 18 * sizeof(float), "fs3_body_motion is
 static_assert(fsd::BODIES3_MAX == FS3_MAX_BODIES, "Bodies3 holds every slot of the ABI");
 
 fs_status fs3_body_get_motion(const fs_sim3* s, uint32_t body, fs3_body_motion* out) {
-    if (!s || !out) return fail(FS_ERR_INVALID, "null argument");
-    if (!s->bodies.has(body)) return fail(FS_ERR_INVALID, "body: the slot holds no body");
+    FS_TRY(body3_slot(s, !out, body));
     *out = s->bodies.slot[body].motion;
     return FS_OK;
 }
 
 fs_status fs3_body_dims(const fs_sim3* s, uint32_t body, uint32_t* w, uint32_t* h, uint32_t* d, fs_vec3* extent) {
-    if (!s || !w || !h || !d || !extent) return fail(FS_ERR_INVALID, "null argument");
-    if (!s->bodies.has(body)) return fail(FS_ERR_INVALID, "body: the slot holds no body");
+    FS_TRY(body3_slot(s, !w || !h || !d || !extent, body));
     const fs_sim3::Bodies::Slot& b = s->bodies.slot[body];
     *w = b.w; *h = b.h; *d = b.d; *extent = b.extent;
     return FS_OK;
 }
 
 fs_status fs3_body_download(fs_sim3* s, uint32_t body, fs_vec3* dst, size_t n) {
-    if (!s || !dst) return fail(FS_ERR_INVALID, "null argument");
-    if (!s->bodies.has(body)) return fail(FS_ERR_INVALID, "body: the slot holds no body");
+    FS_TRY(body3_slot(s, !dst, body));
     const fs_sim3::Bodies::Slot& b = s->bodies.slot[body];
     if (n != b.voxels()) return fail(FS_ERR_INVALID, "body: n must be w * h * d");
     FS_HIP(hipSetDevice(s->device));
@@ -220,8 +199,7 @@ fs_status fs3_body_download(fs_sim3* s, uint32_t body, fs_vec3* dst, size_t n) {
 }
 
 fs_status fs3_body_destroy(fs_sim3* s, uint32_t body) {
-    if (!s) return fail(FS_ERR_INVALID, "null argument");
-    if (!s->bodies.has(body)) return fail(FS_ERR_INVALID, "body: the slot holds no body");
+    FS_TRY(body3_slot(s, false, body));
     FS_HIP(hipSetDevice(s->device));
     FS_HIP(hipStreamSynchronize(s->stream));       // the steps in flight read the field
     fs_sim3::Bodies::Slot& b = s->bodies.slot[body];

@@ -9,8 +9,7 @@
 #include <new>
 #include <vector>
 
-#include "engine.h"
-#include "fs_3d.h"
+#include "engine_bodies.h"
 
 using namespace fsd;
 
@@ -113,8 +112,7 @@ const char* const BODY_SLAB = "body: single-domain handles only (not built for s
 // Checks 4 and 5 of the two body constructors (the handle and the pointers first, by the caller).
 fs_status body_check(uint32_t w, uint32_t h, fs_vec2 extent) {
     if (w == 0u || h == 0u || w > 1024u || h > 1024u) return fail(FS_ERR_INVALID, "body: w or h of 0 or above 1024");
-    const auto good = [](float a) { return std::isfinite(a) && a > 0.0f; };
-    if (!good(extent.x) || !good(extent.y)) return fail(FS_ERR_INVALID, "body: a box extent that is not finite and > 0");
+    if (!all_positive(&extent.x, 2)) return fail(FS_ERR_INVALID, "body: a box extent that is not finite and > 0");
     return FS_OK;
 }
 
@@ -176,8 +174,8 @@ fs_status fs_body_create(fs_sim* s, const fs_vec2* field, uint32_t w, uint32_t h
 }
 static_assert(FS_BODY_LOAD_SHIFT == BODY_LOAD_SHIFT && sizeof(fs_body_load) == 6 * 8, "fs_body_load: the kernel's five words and steps");
 
-// The producer of "3D colliders" (launch3_collider_from_mask: one library, one transform) on the w x h x 1 mask over a box of
-// (extent.x, extent.y, 1); its z component is +0 everywhere and is dropped on the host, between the two blocking copies.
+// The producer of "3D colliders" (mask_to_field3, engine_bodies.h: one library, one transform) on the w x h x 1 mask over a box
+// of (extent.x, extent.y, 1); its z component is +0 everywhere and is dropped on the host, between the two blocking copies.
 fs_status fs_body_create_from_mask(fs_sim* s, const uint8_t* mask, uint32_t w, uint32_t h, fs_vec2 extent, fs_vec2* field_host,
                                    uint32_t* body_out) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
@@ -185,32 +183,22 @@ fs_status fs_body_create_from_mask(fs_sim* s, const uint8_t* mask, uint32_t w, u
     if (!mask || !body_out) return fail(FS_ERR_INVALID, "null argument");
     FS_TRY(body_check(w, h, extent));
     const size_t pixels = (size_t)w * h;
-    bool any_free = false;
-    for (size_t k = 0; k < pixels && !any_free; ++k) any_free = !(mask[k] > 128);
-    if (!any_free) return fail(FS_ERR_INVALID, "body: the mask has no free pixel");
+    if (!mask_has_free(mask, pixels)) return fail(FS_ERR_INVALID, "body: the mask has no free pixel");
     const uint32_t slot = s->bodies.free_slot();
     if (slot == FS_MAX_BODIES) return fail(FS_ERR_INVALID, "body: no free slot");
     FS_HIP(hipSetDevice(s->device));
     std::unique_ptr<float4[]> host4(new (std::nothrow) float4[pixels]);
     std::unique_ptr<fs_vec2[]> host2(new (std::nothrow) fs_vec2[pixels]);
     if (!host4 || !host2) return fail(FS_ERR_OOM, "host allocation failed");
-    DevArray<uint8_t> dmask;
-    DevArray<uint32_t> near_x, near_xy;
+    MaskStaging stage;
     DevArray<float4> field4;
-    if (dmask.alloc(pixels) != hipSuccess || near_x.alloc(pixels) != hipSuccess || near_xy.alloc(pixels) != hipSuccess ||
-        field4.alloc(pixels) != hipSuccess) {
+    if (stage.alloc(pixels) != hipSuccess || field4.alloc(pixels) != hipSuccess) {
         (void)hipGetLastError();
         return fail(FS_ERR_OOM, "body: device staging");
     }
-    ColliderMask3 Q;
-    Q.mask = dmask.p; Q.w = w; Q.h = h; Q.d = 1u;
-    Q.vx = extent.x / (float)w; Q.vy = extent.y / (float)h; Q.vz = 1.0f;
-    Q.near_x = near_x.p; Q.near_xy = near_xy.p; Q.field = field4.p;
-    hipError_t e = hipMemcpyAsync(dmask.p, mask, pixels, hipMemcpyHostToDevice, s->stream);
-    if (e == hipSuccess) { launch3_collider_from_mask(s->stream, Q); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(host4.get(), field4.p, pixels * sizeof(float4), hipMemcpyDeviceToHost, s->stream);
-    const hipError_t es = hipStreamSynchronize(s->stream);      // before the staging is freed, whatever happened
-    if (e == hipSuccess) e = es;
+    FS_TRY(mask_to_field3(s->stream, mask, w, h, 1u, fs_vec3{extent.x, extent.y, 1.0f}, field4.p, stage));
+    hipError_t e = hipMemcpyAsync(host4.get(), field4.p, pixels * sizeof(float4), hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     if (e != hipSuccess) return fail(FS_ERR_DEVICE, hipGetErrorString(e));
     for (size_t k = 0; k < pixels; ++k) host2[k] = fs_vec2{host4[k].x, host4[k].y};
     DevArray<float2> dev;
@@ -223,8 +211,8 @@ fs_status fs_body_create_from_mask(fs_sim* s, const uint8_t* mask, uint32_t w, u
 
 fs_status fs_body_set_motion(fs_sim* s, uint32_t body, const fs_body_motion* m) {
     FS_TRY(body_slot(s, !m, body));
-    const float* f = &m->centre.x;              // 9 floats, nothing between them (static_assert below)
-    for (int k = 0; k < 9; ++k) if (!std::isfinite(f[k])) return fail(FS_ERR_INVALID, "body: non-finite motion");
+    // 9 floats, nothing between them (static_assert below)
+    if (!all_finite(&m->centre.x, 9)) return fail(FS_ERR_INVALID, "body: non-finite motion");
     s->bodies.slot[body].motion = *m;           // host memory only: the next enqueue takes it by value
     return FS_OK;
 }

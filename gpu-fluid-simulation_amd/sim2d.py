@@ -6,7 +6,7 @@ import numpy as np
 from . import _abi
 from ._abi import (FS_MATH_IEEE, FS_SORT_BITONIC, PARTICLE_DTYPE, SAMPLE_DTYPE, BodyLoad, BodyMotion, Nozzle, Options, Settings, SortStep, TickSettings,
                    Uniform, UVec2, Vec2, load_library)
-from ._handle import _check, _Count, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec2
+from ._handle import _Bodies, _check, _Count, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec2
 
 
 def SimulationSettings(particle_count=100_000, particle_spacing=0.1, smoothing_radius=0.2, size=(53.0, 53.0),
@@ -45,7 +45,7 @@ def dam_break_2d(n):
     return settings, (float(off[0]), float(off[1])), tick
 
 
-class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Simulation):
+class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Bodies, _Simulation):
     """FluidSimulation (src/simulation.rs:10-37) on one MI355X, driven through the C ABI."""
     _prefix = "fs_"
     _destroy = "fs_destroy"
@@ -169,31 +169,7 @@ class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Simulation):
         self._call("sample_points_device", C.c_void_p(points_ptr), int(n), C.c_void_p(out_ptr),
                    C.c_void_p(attr_ptr) if attr_ptr else None)
 
-    # -- 2D moving bodies (build extension) --------------------
-    def add_body(self, field, extent):
-        """A kinematic rigid body: a float32 [H, W, 2] field of push vectors in world units (zero = free space) over the body's
-        own box [-extent/2, extent/2] in the body frame (include/fluidsim.h "2D moving bodies").  Returns its slot, the lowest
-        free one of 0 .. 7.  Blocking.  The body starts at the origin with the identity pose, at rest: set_body_motion places it."""
-        f = np.ascontiguousarray(field, dtype=np.float32)
-        if f.ndim != 3 or f.shape[2] != 2:
-            raise ValueError("add_body expects a [H, W, 2] float32 array")
-        h, w = f.shape[:2]
-        slot = C.c_uint32()
-        self._call("body_create", _ptr(f), int(w), int(h), _vec2(extent), C.byref(slot))
-        return int(slot.value)
-
-    def add_body_mask(self, mask, extent, want_field=False):
-        """The body of a uint8 [H, W] mask (> 128: solid) over the box `extent`: the exact distance transform of the 3D colliders
-        on the body's box (not set_obstacle_image's chamfer).  Returns the slot, with want_field=True (slot, the [H, W, 2] field)."""
-        m = np.ascontiguousarray(mask, dtype=np.uint8)
-        if m.ndim != 2:
-            raise ValueError("add_body_mask expects a [H, W] uint8 array")
-        h, w = m.shape
-        out = np.zeros((h, w, 2), dtype=np.float32) if want_field else None
-        slot = C.c_uint32()
-        self._call("body_create_from_mask", _ptr(m), int(w), int(h), _vec2(extent), _ptr(out) if want_field else None, C.byref(slot))
-        return (int(slot.value), out) if want_field else int(slot.value)
-
+    # -- 2D moving bodies (build extension): _Bodies, and the motion ---
     def set_body_motion(self, body, centre, rot=None, velocity=(0.0, 0.0), angular_velocity=0.0):
         """Pose and velocity of a body for the steps enqueued after this call; host memory only, no copy, no sync.  `rot`: four
         floats, row-major R with world = R * local (None: the identity).  The engine does not advance the pose: set it before
@@ -208,27 +184,6 @@ class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Simulation):
         self._call("body_get_motion", int(body), C.byref(m))
         v = lambda a: np.array([a.x, a.y], dtype=np.float32)      # noqa: E731
         return v(m.centre), np.array(list(m.rot), dtype=np.float32).reshape(2, 2), v(m.velocity), np.float32(m.angular_velocity)
-
-    def body_dims(self, body):
-        """((W, H), (ex, ey)) of a body: its field's extents and its box."""
-        w, h, e = C.c_uint32(), C.c_uint32(), Vec2()
-        self._call("body_dims", int(body), C.byref(w), C.byref(h), C.byref(e))
-        return (int(w.value), int(h.value)), (float(e.x), float(e.y))
-
-    def body_field(self, body):
-        """A body's field as a float32 [H, W, 2] array.  Blocking."""
-        (w, h), _ = self.body_dims(body)
-        out = np.zeros((h, w, 2), dtype=np.float32)
-        self._call("body_download", int(body), _ptr(out), w * h)
-        return out
-
-    def remove_body(self, body):
-        """Destroys a body and frees its slot; the other bodies keep theirs.  Blocking."""
-        self._call("body_destroy", int(body))
-
-    @property
-    def body_count(self):
-        return int(self._fn("body_count")(self._h))
 
     # -- 2D body loads (build extension; DESIGN.md §25) -----------------------
     def enable_body_loads(self, on=True):

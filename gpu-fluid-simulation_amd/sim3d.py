@@ -7,7 +7,7 @@ import numpy as np
 from . import _abi
 from ._abi import (FS_MATH_IEEE, MESH_VERTEX_DTYPE, PARTICLE3_DTYPE, SAMPLE3_DTYPE, SURFACE_HIT_DTYPE, BodyMotion3, Camera3,
                    Nozzle3, Settings3, TickSettings3, Vec3, load_library)
-from ._handle import _check, _Count, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec3
+from ._handle import _Bodies, _check, _Count, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec3
 
 
 def dam_break_3d(n):
@@ -27,7 +27,7 @@ def dam_break_3d(n):
     return st, (float(off[0]), float(off[1]), float(off[2])), tick
 
 
-class FluidSimulation3D(_Count, _Tracking, _SurfaceTension, _Simulation):
+class FluidSimulation3D(_Count, _Tracking, _SurfaceTension, _Bodies, _Simulation):
     """3D extension (include/fluidsim.h fs3_*); not in the reference."""
     _prefix = "fs3_"
     _destroy = "fs3_destroy"
@@ -211,32 +211,7 @@ class FluidSimulation3D(_Count, _Tracking, _SurfaceTension, _Simulation):
         self._call("collider_download", _ptr(out), w * h * d)
         return out
 
-    # -- 3D moving bodies (build extension) --------------------
-    def add_body(self, field, extent):
-        """A kinematic rigid body: a float32 [D, H, W, 3] voxel field of push vectors (zero = free space) over the body's own box
-        [-extent/2, extent/2] in the body frame (include/fluidsim.h "3D moving bodies").  Returns its slot, the lowest free one of
-        0 .. 7.  Blocking.  The body starts at the origin with the identity pose, at rest: set_body_motion places it."""
-        f = np.ascontiguousarray(field, dtype=np.float32)
-        if f.ndim != 4 or f.shape[3] != 3:
-            raise ValueError("add_body expects a [D, H, W, 3] float32 array")
-        d, h, w = f.shape[:3]
-        slot = C.c_uint32()
-        self._call("body_create", _ptr(f), int(w), int(h), int(d), _vec3(extent), C.byref(slot))
-        return int(slot.value)
-
-    def add_body_mask(self, mask, extent, want_field=False):
-        """The body of a uint8 [D, H, W] voxel mask (> 128: solid) over the box `extent`: set_collider_mask's producer on the body's
-        box.  Returns the slot, with want_field=True (slot, the [D, H, W, 3] field)."""
-        m = np.ascontiguousarray(mask, dtype=np.uint8)
-        if m.ndim != 3:
-            raise ValueError("add_body_mask expects a [D, H, W] uint8 array")
-        d, h, w = m.shape
-        out = np.zeros((d, h, w, 3), dtype=np.float32) if want_field else None
-        slot = C.c_uint32()
-        self._call("body_create_from_mask", _ptr(m), int(w), int(h), int(d), _vec3(extent), _ptr(out) if want_field else None,
-                   C.byref(slot))
-        return (int(slot.value), out) if want_field else int(slot.value)
-
+    # -- 3D moving bodies (build extension): _Bodies, and the motion ---
     def set_body_motion(self, body, centre, rot=None, velocity=(0.0, 0.0, 0.0), angular_velocity=(0.0, 0.0, 0.0)):
         """Pose and velocity of a body for the steps enqueued after this call; host memory only, no copy, no sync.  `rot`: nine
         floats, row-major R with world = R * local (None: the identity).  The engine does not advance the pose: set it before
@@ -251,27 +226,6 @@ class FluidSimulation3D(_Count, _Tracking, _SurfaceTension, _Simulation):
         self._call("body_get_motion", int(body), C.byref(m))
         v = lambda a: np.array([a.x, a.y, a.z], dtype=np.float32)      # noqa: E731
         return v(m.centre), np.array(list(m.rot), dtype=np.float32).reshape(3, 3), v(m.velocity), v(m.angular_velocity)
-
-    def body_dims(self, body):
-        """((W, H, D), (ex, ey, ez)) of a body: its field's extents and its box."""
-        w, h, d, e = C.c_uint32(), C.c_uint32(), C.c_uint32(), Vec3()
-        self._call("body_dims", int(body), C.byref(w), C.byref(h), C.byref(d), C.byref(e))
-        return (int(w.value), int(h.value), int(d.value)), (float(e.x), float(e.y), float(e.z))
-
-    def body_field(self, body):
-        """A body's field as a float32 [D, H, W, 3] array.  Blocking."""
-        (w, h, d), _ = self.body_dims(body)
-        out = np.zeros((d, h, w, 3), dtype=np.float32)
-        self._call("body_download", int(body), _ptr(out), w * h * d)
-        return out
-
-    def remove_body(self, body):
-        """Destroys a body and frees its slot; the other bodies keep theirs.  Blocking."""
-        self._call("body_destroy", int(body))
-
-    @property
-    def body_count(self):
-        return int(self._fn("body_count")(self._h))
 
 
 def rigid_motion(centre0, velocity, axis, rate, t):

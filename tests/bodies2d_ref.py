@@ -32,9 +32,10 @@ class Body:
         return self.centre, self.rot, self.velocity, self.angular_velocity
 
 
-def apply_body(records, body, size, damping):
-    """B(records): (new records, particles hit, particles re-clamped after their push).  `size`: the settings' box, `damping`: the
-    tick's damping_factor."""
+def apply_body_record(records, body, size, damping):
+    """B(records) with what the loads need of every hit (tests/body_loads2d_ref.py): (new records, rec) — rec["hit"]: bool per
+    particle; per HIT, in particle order: rec["v0"], rec["v1"], rec["s"] float32 [hits, 2] and rec["clamped"] bool [hits].
+    `size`: the settings' box, `damping`: the tick's damping_factor."""
     field = body.field
     H, W = field.shape[:2]
     out = records.copy()
@@ -68,6 +69,7 @@ def apply_body(records, body, size, damping):
         ln = np.sqrt(t0 + t1)
         hit = inside & nz & (ln > f32(0))
         g, ln, ph, vh = g[hit], ln[hit], p[hit], v[hit]
+        v0 = vh.copy()                                  # the velocity on entry to this operator
         t0 = r00 * g[:, 0]
         t1 = r01 * g[:, 1]
         fx = t0 + t1
@@ -98,6 +100,8 @@ def apply_body(records, body, size, damping):
         vy = usy + t0
         ph = np.stack([px, py], axis=1).astype(f32).reshape(-1, 2)
         vh = np.stack([vx, vy], axis=1).astype(f32).reshape(-1, 2)
+        v1 = vh.copy()                                  # before the wall re-clamp
+        s = np.stack([sx, sy], axis=1).astype(f32).reshape(-1, 2)
         clamped = np.zeros(ph.shape[0], dtype=bool)
         for a in range(2):
             over = np.abs(ph[:, a]) > b[a]
@@ -108,7 +112,13 @@ def apply_body(records, body, size, damping):
     v[hit] = vh
     out["position"] = p
     out["velocity"] = v
-    return out, int(hit.sum()), int(clamped.sum())
+    return out, {"hit": hit, "v0": v0, "v1": v1, "s": s, "clamped": clamped}
+
+
+def apply_body(records, body, size, damping):
+    """B(records): (new records, particles hit, particles re-clamped after their push)"""
+    out, rec = apply_body_record(records, body, size, damping)
+    return out, int(rec["hit"].sum()), int(rec["clamped"].sum())
 
 
 def apply_bodies(records, bodies, size, damping):

@@ -1,99 +1,17 @@
 """CPU statement of the 2D body loads (include/fluidsim.h "2D body loads"), written from the header's text and
-from nothing in the kernel: the operator B of "2D moving bodies" restated in numpy float32, one f32 operation per line, with what
-the loads need of every hit (v0, v1, s, the hit mask, the re-clamp mask), the fixed-point Q, the five checker words as exact
+from nothing in the kernel: on the operator B of "2D moving bodies" (tests/bodies2d_ref.apply_body_record: its one statement,
+with v0, v1, s, the hit mask and the re-clamp mask of every hit) the header's three lines per hit, the fixed-point Q, the five checker words as exact
 Python-int sums modulo 2^64, and the run of the shared scene (tests/bodies2d_ref.Scene) with its words per step.
 TEST INFRASTRUCTURE ONLY."""
 import numpy as np
 
 from tests import bodies2d_ref as B
-from tests import collide3d_ref as CR
+from tests.bodies2d_ref import apply_body_record as apply_body      # (new records, rec)
 
 f32 = np.float32
 SHIFT = 20
 MOD = 1 << 64
 LIMIT = f32(16384.0)
-
-
-def apply_body(records, body, size, damping):
-    """B(records) with the load outputs: (new records, rec) — rec["hit"]: bool per particle; per HIT, in particle order:
-    rec["v0"], rec["v1"], rec["s"] float32 [hits, 2] and rec["clamped"] bool [hits]."""
-    field = body.field
-    H, W = field.shape[:2]
-    out = records.copy()
-    p = out["position"].astype(f32)
-    v = out["velocity"].astype(f32)
-    b = np.array([f32(s) for s in size], dtype=f32) * f32(0.5)
-    damping = f32(damping)
-    c, r, u, w, ext = body.centre, body.rot, body.velocity, body.angular_velocity, body.extent
-    r00, r01, r10, r11 = (f32(x) for x in r)
-    with np.errstate(all="ignore"):
-        hb = ext * f32(0.5)
-        dx = p[:, 0] - c[0]
-        dy = p[:, 1] - c[1]
-        t0 = r00 * dx
-        t1 = r10 * dy
-        qx = t0 + t1
-        t0 = r01 * dx
-        t1 = r11 * dy
-        qy = t0 + t1
-        inside = (np.abs(qx) <= hb[0]) & (np.abs(qy) <= hb[1])
-        idx = []
-        for a, (q, wa) in enumerate(((qx, W), (qy, H))):
-            x = q + hb[a]
-            x = x / ext[a]
-            x = x * f32(wa)
-            idx.append(np.minimum(CR.u32_sat(x), np.uint64(wa - 1)).astype(np.int64))
-        g = field[idx[1], idx[0]]
-        nz = (g[:, 0] != 0) | (g[:, 1] != 0)
-        t0 = g[:, 0] * g[:, 0]
-        t1 = g[:, 1] * g[:, 1]
-        ln = np.sqrt(t0 + t1)
-        hit = inside & nz & (ln > f32(0))
-        g, ln, ph, vh = g[hit], ln[hit], p[hit], v[hit]
-        v0 = vh.copy()                                  # the velocity on entry to this operator
-        t0 = r00 * g[:, 0]
-        t1 = r01 * g[:, 1]
-        fx = t0 + t1
-        t0 = r10 * g[:, 0]
-        t1 = r11 * g[:, 1]
-        fy = t0 + t1
-        nx = fx / ln
-        ny = fy / ln
-        px = ph[:, 0] + fx
-        py = ph[:, 1] + fy
-        sx = px - c[0]
-        sy = py - c[1]
-        t0 = w * sy
-        usx = u[0] - t0
-        t0 = w * sx
-        usy = u[1] + t0
-        rx = vh[:, 0] - usx
-        ry = vh[:, 1] - usy
-        t0 = rx * nx
-        t1 = ry * ny
-        rn = t0 + t1
-        k = (f32(1.0) - damping) * rn
-        t0 = k * nx
-        t0 = rx - t0
-        vx = usx + t0
-        t0 = k * ny
-        t0 = ry - t0
-        vy = usy + t0
-        ph = np.stack([px, py], axis=1).astype(f32).reshape(-1, 2)
-        vh = np.stack([vx, vy], axis=1).astype(f32).reshape(-1, 2)
-        v1 = vh.copy()                                  # before the wall re-clamp
-        s = np.stack([sx, sy], axis=1).astype(f32).reshape(-1, 2)
-        clamped = np.zeros(ph.shape[0], dtype=bool)
-        for a in range(2):
-            over = np.abs(ph[:, a]) > b[a]
-            ph[over, a] = b[a] * np.sign(ph[over, a])
-            vh[over, a] = vh[over, a] * (f32(-1.0) * damping)
-            clamped |= over
-    p[hit] = ph
-    v[hit] = vh
-    out["position"] = p
-    out["velocity"] = v
-    return out, {"hit": hit, "v0": v0, "v1": v1, "s": s, "clamped": clamped}
 
 
 def contributions(rec):

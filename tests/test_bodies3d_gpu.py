@@ -8,36 +8,12 @@ import pytest
 
 from tests import bodies3d_ref as B
 from tests import collide3d_ref as CR
+from tests.handle_helpers import _add, _same, _size
 from tests.track_ref import jitter_velocities
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 SIDE = 16
-
-
-def _same(got, want, ctx):
-    """every field of every particle, byte for byte"""
-    assert got.shape == want.shape, f"{ctx}: {got.shape[0]} particles, expected {want.shape[0]}"
-    for name in want.dtype.names:
-        if name == "pad":
-            continue
-        a, b = np.ascontiguousarray(got[name]), np.ascontiguousarray(want[name])
-        bad = a.view(np.uint32).reshape(a.shape[0], -1) != b.view(np.uint32).reshape(b.shape[0], -1)
-        assert not bad.any(), f"{ctx}: {name} differs in {int(bad.any(axis=1).sum())} particles, first {int(np.argmax(bad.any(axis=1)))}"
-
-
-def _size(st):
-    return (st.size.x, st.size.y, st.size.z)
-
-
-def _add(sim, bodies):
-    """the reference bodies into a handle, in order; returns the slots"""
-    slots = []
-    for b in bodies:
-        k = sim.add_body(b.field, b.extent)
-        sim.set_body_motion(k, *b.motion())
-        slots.append(k)
-    return slots
 
 
 # ---- 1. against the oracle --------------------------------------------------------------------------------------------

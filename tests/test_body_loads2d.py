@@ -1,5 +1,5 @@
-"""2D body loads without a GPU (include/fluidsim.h "2D body loads"): the restated operator of
-tests/body_loads2d_ref.py is the operator of tests/bodies2d_ref.py, Q rounds as the header says, the fixed-point sums are the
+"""2D body loads without a GPU (include/fluidsim.h "2D body loads"): the hit record that tests/body_loads2d_ref.py
+takes from the operator of tests/bodies2d_ref.py agrees with that operator's records and counts, Q rounds as the header says, the fixed-point sums are the
 momentum the particles lost, the shared scene meets the conditions the GPU comparison relies on, BodyDynamics2D integrates a
 scripted sequence of loads as computed by hand, and every layer names the four calls."""
 import ctypes as C
@@ -19,7 +19,8 @@ METHODS = ["enable_body_loads", "body_loads_enabled", "body_loads", "body_loads_
 
 def test_restated_operator_is_the_operator(fs, orc):
     """side 64, steps 1 .. 8, each of the three bodies on the state the one before left: the same bytes, the same number of hits
-    and of re-clamped particles as bodies2d_ref.apply_body; and the run's snapshots are bodies2d_ref.oracle_run's"""
+    and of re-clamped particles as bodies2d_ref.apply_body, whose counts are derived from the record's masks (one statement of the
+    operator: bodies2d_ref.apply_body_record); and the run's snapshots are bodies2d_ref.oracle_run's"""
     run = L.scene_run(fs, orc, 64)
     sc = run["scene"]
     bodies = sc.bodies()

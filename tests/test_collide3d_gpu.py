@@ -7,25 +7,12 @@ import numpy as np
 import pytest
 
 from tests import collide3d_ref as R
+from tests.handle_helpers import _same, _size
 from tests.track_ref import jitter_velocities
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 SIDE = 16
-
-
-def _same(got, want, ctx):
-    """every field of every particle, byte for byte"""
-    for name in want.dtype.names:
-        if name == "pad":
-            continue
-        a, b = np.ascontiguousarray(got[name]), np.ascontiguousarray(want[name])
-        bad = a.view(np.uint32).reshape(a.shape[0], -1) != b.view(np.uint32).reshape(b.shape[0], -1)
-        assert not bad.any(), f"{ctx}: {name} differs in {int(bad.any(axis=1).sum())} particles, first {int(np.argmax(bad.any(axis=1)))}"
-
-
-def _size(st):
-    return (st.size.x, st.size.y, st.size.z)
 
 
 _random_field = R.random_field

@@ -8,6 +8,7 @@ import pytest
 
 import paths3d
 from tests import collide3d_ref as CR
+from tests.handle_helpers import _same
 from tests import st3d_ref as R
 from tests.test_surface_tension3d import SCENE_ST
 from tests.track_ref import jitter_velocities
@@ -16,14 +17,6 @@ pytestmark = pytest.mark.gpu
 f32 = np.float32
 SIGMA = 100.0          # dam_break_3d: |st| is then about a tenth of the pressure + viscosity sum, |st| dt / rho up to ~1.5 m/s
 TOL_SIGMA = 10.0       # the tolerance-mode step: |st| dt / rho up to ~0.15 m/s, well below the scene's speeds (jitter: 3 m/s)
-
-
-def _same(got, want, ctx):
-    """every field of every particle, byte for byte"""
-    for name in ("grid", "predicted_position", "density", "velocity", "position"):
-        a, b = np.ascontiguousarray(got[name]), np.ascontiguousarray(want[name])
-        bad = a.view(np.uint32).reshape(a.shape[0], -1) != b.view(np.uint32).reshape(b.shape[0], -1)
-        assert not bad.any(), f"{ctx}: {name} differs in {int(bad.any(axis=1).sum())} particles, first {int(np.argmax(bad.any(axis=1)))}"
 
 
 def _same_st(got, want, ctx):
