@@ -30,6 +30,7 @@ from ._abi import (  # noqa: F401
     SAMPLE3_DTYPE,
     SAMPLE_DTYPE,
     SURFACE_HIT_DTYPE,
+    Body3Load,
     BodyLoad,
     BodyMotion,
     BodyMotion3,
@@ -53,7 +54,7 @@ from ._abi import (  # noqa: F401
     load_library,
 )
 from ._handle import FluidSimError, _check  # noqa: F401
-from .body_dynamics import BodyDynamics2D  # noqa: F401
+from .body_dynamics import BodyDynamics2D, BodyDynamics3D  # noqa: F401
 from .buffers import ImportedBuffer, ResizableBuffer  # noqa: F401
 from .imaging import shade_surface, surface_hit_points, write_obj, write_png  # noqa: F401
 from .selftest import selftest_sort, selftest_sort_policy  # noqa: F401
@@ -69,7 +70,7 @@ from .sim2d import (  # noqa: F401
     rigid_motion2d,
     sort_schedule,
 )
-from .sim3d import FluidSimulation3D, box_mask3d, dam_break_3d, look_at_camera, reference_lattice_3d, rigid_motion  # noqa: F401
+from .sim3d import BodyLoads3D, FluidSimulation3D, box_mask3d, dam_break_3d, look_at_camera, reference_lattice_3d, rigid_motion  # noqa: F401
 from .slab import SlabSimulation  # noqa: F401
 
 __all__ = [

@@ -187,6 +187,12 @@ class BodyMotion3(C.Structure):
     _fields_ = [("centre", Vec3), ("rot", C.c_float * 9), ("velocity", Vec3), ("angular_velocity", Vec3)]
 
 
+class Body3Load(C.Structure):
+    """fs3_body_load (include/fluidsim.h "3D body loads"): 72 bytes."""
+    _fields_ = [("impulse_q", C.c_int64 * 3), ("angular_q", C.c_int64 * 3), ("hits", C.c_uint64), ("dropped", C.c_uint64),
+                ("steps", C.c_uint64)]
+
+
 class SurfaceHit3(C.Structure):
     """fs3_surface_hit (include/fluidsim.h): 40 bytes."""
     _fields_ = [("t", C.c_float), ("density", C.c_float), ("normal", Vec3), ("velocity", Vec3), ("steps", C.c_uint32),
@@ -410,6 +416,10 @@ PROTOTYPES = {
     "fs3_body_download": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t]),
     "fs3_body_destroy": (C.c_int, [_P, C.c_uint32]),
     "fs3_body_count": (C.c_uint32, [_P]),
+    "fs3_body_loads_enable": (C.c_int, [_P, C.c_int]),
+    "fs3_body_loads_enabled": (C.c_int, [_P]),
+    "fs3_body_loads": (C.c_int, [_P, C.c_uint32, C.POINTER(Body3Load), C.c_int]),
+    "fs3_body_loads_device": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
     "fs3_set_surface_tension": (C.c_int, [_P, C.c_int, C.c_float, C.c_float]),
     "fs3_surface_tension_enabled": (C.c_int, [_P]),
     "fs3_surface_tension_params": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -248,6 +248,24 @@ class _Bodies:
     def body_count(self):
         return int(self._fn("body_count")(self._h))
 
+    # -- body loads (build extension; DESIGN.md §25, 3D: §26); body_loads stays per class: the records differ
+    def enable_body_loads(self, on=True):
+        """Turns the per-body load sums on or off (include/fluidsim.h "2D body loads" / "3D body loads").  Enabling zeroes every
+        body's words.  While off a step launches what it launched without them; while on the particles are still byte for byte
+        the same."""
+        self._call("body_loads_enable", 1 if on else 0)
+
+    @property
+    def body_loads_enabled(self):
+        return bool(self._fn("body_loads_enabled")(self._h))
+
+    def body_loads_device_ptr(self):
+        """fs_body_loads_device / fs3_body_loads_device: the device address of the 8 x 5 (3D: 8 x 8) 64-bit words, by slot, for a
+        consumer on the handle's stream."""
+        p = C.c_void_p()
+        self._call("body_loads_device", C.byref(p))
+        return p.value
+
 
 class _Tracking:
     """Opt-in particle tracking (build extension; DESIGN.md §12, 3D: §20)."""

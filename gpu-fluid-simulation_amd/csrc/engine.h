@@ -2,7 +2,7 @@
 // features, the step parameters, and the device check and create-time proofs (also used by the 3D handle's files through
 // engine_3d.h).  The handle's files:
 // engine.hip (life cycle, step, transfers, renderer hand-off), engine_features.hip (surface tension, particle tracking, moving bodies;
-// what the bodies share with the 3D handle's engine_3d_features.hip: engine_bodies.h, and BodySlots below),
+// what the bodies share with the 3D handle's engine_3d_features.hip: engine_bodies.h, and BodySlots and BodyLoads below),
 // engine_query.hip (density render, field sampling), engine_count.hip (a particle count that changes at run time; what it
 // shares with the 3D handle's engine_3d_count.hip: engine_count.h, and Tracking and RemoveScratch below),
 // engine_selftest.hip (self-tests, read-outs), engine_slab.hip (the multi-GPU slab handles).  Internal: include/fluidsim.h is the interface.
@@ -203,6 +203,52 @@ struct BodySlots {
     uint32_t free_slot() const { uint32_t k = 0; while (k < MAX && slot[k].w) ++k; return k; }
 };
 
+// The opt-in loads of either handle's bodies (fs_body_loads_* in engine_features.hip; fs3_body_loads_* in
+// engine_3d_features.hip, §26) over MAX slots of WORDS 64-bit words.  words: MAX x WORDS by slot, what *_body_loads_device hands
+// out; shards: the pass's scratch (BODY_LOAD_SHARDS rows of MAX x WORDS), zero between steps; both allocated by the first enable
+// and kept for the life of the handle.  steps[k]: steps enqueued with loads on since slot k's words were last zeroed.  Each
+// handle's file keeps its entry points, the order of its checks and its messages.
+template <uint32_t MAX, uint32_t WORDS>
+struct BodyLoads {
+    bool on = false;
+    DevArray<unsigned long long> words, shards;
+    uint64_t steps[MAX] = {};
+    static constexpr size_t SLOT_BYTES = WORDS * sizeof(unsigned long long);
+    // Zeroes the words of `slot` on the stream, behind what is enqueued, and its step count (loads never enabled: no words).
+    hipError_t zero(hipStream_t st, uint32_t slot) {
+        steps[slot] = 0;
+        return words.p ? hipMemsetAsync(words.p + slot * WORDS, 0, SLOT_BYTES, st) : hipSuccess;
+    }
+    // fs_body_loads_enable / fs3_body_loads_enable behind their checks (the device is set): on zeroes every slot, also when already on.
+    fs_status enable(hipStream_t st, bool on_) {
+        if (on_) {
+            if (!words.p) {
+                DevArray<unsigned long long> w, sh;
+                if (w.alloc(MAX * WORDS) != hipSuccess || sh.alloc(BODY_LOAD_SHARDS * MAX * WORDS) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return fail(FS_ERR_OOM, "body loads: device words");
+                }
+                FS_HIP(hipMemsetAsync(sh.p, 0, sh.n * sizeof(unsigned long long), st));   // the fold keeps them zero
+                words = std::move(w);
+                shards = std::move(sh);
+            }
+            FS_HIP(hipMemsetAsync(words.p, 0, words.n * sizeof(unsigned long long), st));
+            for (uint64_t& c : steps) c = 0;
+        }
+        on = on_;
+        return FS_OK;
+    }
+    // The words of `slot` behind every step enqueued so far, and its step count; reset: zeroed behind the read, on the stream.  Blocking.
+    fs_status read(hipStream_t st, uint32_t slot, bool reset, unsigned long long (&w)[WORDS], uint64_t* steps_out) {
+        *steps_out = steps[slot];
+        hipError_t e = hipMemcpyAsync(w, words.p + slot * WORDS, SLOT_BYTES, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && reset) e = zero(st, slot);
+        const hipError_t es = hipStreamSynchronize(st);             // before `w` leaves the caller's scope, whatever happened
+        if (e == hipSuccess) e = es;
+        return e == hipSuccess ? FS_OK : fail(FS_ERR_DEVICE, hipGetErrorString(e));
+    }
+};
+
 // Opt-in moving bodies (build extension; single-domain handles): fs_body_* in engine_features.hip.  Per slot a
 // field of push vectors over the body's own box and the motion the host last set; w == 0: the slot is free, and never created:
 // no allocation, no launch.
@@ -215,14 +261,8 @@ struct BodySlot2 {
 };
 struct Bodies : BodySlots<BodySlot2, FS_MAX_BODIES> {
     using Slot = BodySlot2;
-    // Opt-in loads (fs_body_loads_* in engine_features.hip).  words: FS_MAX_BODIES x 5 64-bit words by slot, what
-    // fs_body_loads_device hands out; shards: the pass's scratch, zero between steps; both allocated by the first enable.
-    // steps[k]: steps enqueued with loads on since slot k's words were last zeroed.
-    struct Loads {
-        bool on = false;
-        DevArray<unsigned long long> words, shards;
-        uint64_t steps[FS_MAX_BODIES] = {};
-    } loads;
+    using Loads = BodyLoads<FS_MAX_BODIES, BODY_LOAD_WORDS>;       // five words per body
+    Loads loads;
     // This step's pass, behind the force launches, on the state they stored (A.pos_out / A.vel_out; aos: the live 32-B records,
     // or null): the fields and the motions as they are now, by value, the slots in use in ascending order (fs_body_* order their
     // writes and frees on the stream behind it).  `done`: the step's completion event, which this launch carries in the force

@@ -97,13 +97,19 @@ struct fs_sim3 {
     };
     struct Bodies : fsd::BodySlots<BodySlot, FS3_MAX_BODIES> {      // has, count, free_slot: engine.h
         using Slot = BodySlot;
+        // Opt-in loads (fs3_body_loads_* in engine_3d_features.hip): eight words per body, the 2D handle's type.
+        using Loads = fsd::BodyLoads<FS3_MAX_BODIES, fsd::BODY3_LOAD_WORDS>;
+        Loads loads;
         // What a step takes, by value into *B: the fields and the motions as they are when it is enqueued, the slots in use in
-        // ascending order (fs3_body_* order their writes and frees on the stream behind it).  Null: no slot is in use.
-        const fsd::Bodies3* for_step(fsd::Bodies3* B) const {
+        // ascending order (fs3_body_* order their writes and frees on the stream behind it); *M: the slot of each.  Null: no slot
+        // is in use.
+        const fsd::Bodies3* for_step(fsd::Bodies3* B, fsd::BodyLoadMap* M) const {
             uint32_t c = 0;
-            for (const Slot& b : slot) {
+            for (uint32_t k = 0; k < FS3_MAX_BODIES; ++k) {
+                const Slot& b = slot[k];
                 if (!b.w) continue;
                 const fs3_body_motion& m = b.motion;
+                M->slot[c] = k;
                 fsd::Body3& K = B->body[c++];
                 K.field = b.field.p; K.w = b.w; K.h = b.h; K.d = b.d;
                 K.ex = b.extent.x; K.ey = b.extent.y; K.ez = b.extent.z;
@@ -113,8 +119,16 @@ struct fs_sim3 {
                 K.ux = m.velocity.x; K.uy = m.velocity.y; K.uz = m.velocity.z;
                 K.wx = m.angular_velocity.x; K.wy = m.angular_velocity.y; K.wz = m.angular_velocity.z;
             }
-            B->count = c;
+            B->count = M->count = c;
             return c ? B : nullptr;
+        }
+        // This step's pass behind the force kernel; it carries `done` in that kernel's place.  Loads on: the pass's second form and
+        // its fold, which carries `done`, and a step more for every slot in use.
+        void enqueue(hipStream_t st, const fsd::Params3& P, const fsd::Arrays3& A, const fsd::Bodies3& B, const fsd::BodyLoadMap& M,
+                     hipEvent_t done) {
+            if (!loads.on) { fsd::launch3_bodies(st, P, A, B, done); return; }
+            fsd::launch3_bodies_loads(st, P, A, B, M, loads.shards.p, loads.words.p, done);
+            for (uint32_t k = 0; k < M.count; ++k) loads.steps[M.slot[k]] += 1u;
         }
     } bodies;
     // The opt-in surface tension: never enabled: no allocation, no launch.

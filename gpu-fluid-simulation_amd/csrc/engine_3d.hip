@@ -90,11 +90,13 @@ fs_status enqueue3(fs_sim3* s, const fs3_tick_settings* t) {
     // the opt-in features' operands (engine_3d.h): the collider by value, and surface tension's pass ahead of the force pass
     Collide3 K;
     const float4* stf = s->tension.enqueue(st, P, A);
-    // with moving bodies their pass follows the force kernel and carries the completion event in its place
+    // with moving bodies their pass follows the force kernel and carries the completion event in its place; with
+    // their loads on (§26) that is the pass's loads form and its fold
     Bodies3 BD;
-    const Bodies3* bodies = s->bodies.for_step(&BD);
+    fsd::BodyLoadMap BM{};
+    const Bodies3* bodies = s->bodies.for_step(&BD, &BM);
     launch3_force(st, P, A, tol, bodies ? nullptr : done, s->collider.for_step(s->st.size, &K), stf);
-    if (bodies) launch3_bodies(st, P, A, *bodies, done);
+    if (bodies) s->bodies.enqueue(st, P, A, *bodies, BM, done);
     std::swap(s->pos, s->pos_s);
     s->mass = t->mass; s->sample_stale = false;
     if (ev) { FS_HIP(hipEventRecord(ev[5], st)); FS_HIP(hipEventRecord(ev[6], st)); /* FS_PASS_BOUNDARY: slab handles only */ s->prof.pending += 1; }

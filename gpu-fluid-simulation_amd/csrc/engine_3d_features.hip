@@ -1,5 +1,5 @@
 // engine_3d_features.hip — the opt-in features the 3D step enqueues for (their state: engine_3d.h, one struct each): colliders
-// (DESIGN.md §18), moving bodies (§23), surface tension (§19), particle tracking (§20) and, on top of tracking,
+// (DESIGN.md §18), moving bodies (§23) and their loads (§26), surface tension (§19), particle tracking (§20) and, on top of tracking,
 // fs3_download_particles_by_id.
 #include <hip/hip_runtime.h>
 
@@ -205,10 +205,44 @@ fs_status fs3_body_destroy(fs_sim3* s, uint32_t body) {
     fs_sim3::Bodies::Slot& b = s->bodies.slot[body];
     b.w = b.h = b.d = 0;
     b.field.release();
+    FS_HIP(s->bodies.loads.zero(s->stream, body));                // before the slot can be reused (a new body starts at zero)
     return FS_OK;
 }
 
 uint32_t fs3_body_count(const fs_sim3* s) { return s ? s->bodies.count() : 0u; }
+
+// ---- 3D body loads ------------------------------------------------------------------------------------
+static_assert(sizeof(fs3_body_load) == 9 * 8, "fs3_body_load: the kernel's eight words and steps");
+const char* const LOADS3_OFF = "body loads: not enabled (fs3_body_loads_enable)";
+
+fs_status fs3_body_loads_enable(fs_sim3* s, int on) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    if (on) FS_HIP(hipSetDevice(s->device));
+    return s->bodies.loads.enable(s->stream, on != 0);
+}
+
+int fs3_body_loads_enabled(const fs_sim3* s) { return s && s->bodies.loads.on ? 1 : 0; }
+
+fs_status fs3_body_loads(fs_sim3* s, uint32_t body, fs3_body_load* out, int reset) {
+    FS_TRY(body3_slot(s, !out, body));
+    fs_sim3::Bodies::Loads& L = s->bodies.loads;
+    if (!L.on) return fail(FS_ERR_INVALID, LOADS3_OFF);
+    FS_HIP(hipSetDevice(s->device));
+    unsigned long long w[fsd::BODY3_LOAD_WORDS];
+    uint64_t steps;
+    FS_TRY(L.read(s->stream, body, reset != 0, w, &steps));
+    for (int a = 0; a < 3; ++a) { out->impulse_q[a] = (int64_t)w[a]; out->angular_q[a] = (int64_t)w[3 + a]; }
+    out->hits = w[6]; out->dropped = w[7];
+    out->steps = steps;
+    return FS_OK;
+}
+
+fs_status fs3_body_loads_device(fs_sim3* s, const void** words) {
+    if (!s || !words) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->bodies.loads.on) return fail(FS_ERR_INVALID, LOADS3_OFF);
+    *words = s->bodies.loads.words.p;
+    return FS_OK;
+}
 
 // ---- 3D surface tension -------------------------------------------------------------------------------
 fs_status fs3_set_surface_tension(fs_sim3* s, int enable, float coefficient, float threshold) {

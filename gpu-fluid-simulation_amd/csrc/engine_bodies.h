@@ -1,5 +1,5 @@
 // engine_bodies.h — what engine_features.hip (the 2D handle) and engine_3d_features.hip (the 3D handle) share of the moving
-// bodies and of the mask producer behind them and the 3D colliders (§18), beyond BodySlots in engine.h:
+// bodies and of the mask producer behind them and the 3D colliders (§18), beyond BodySlots and BodyLoads in engine.h:
 // plain functions over the pieces of a handle they work on.  Each handle's file keeps its entry points, the order of its checks
 // and its messages.
 #pragma once

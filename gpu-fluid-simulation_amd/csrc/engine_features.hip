@@ -125,15 +125,6 @@ void body_install(fs_sim* s, uint32_t slot, DevArray<float2>&& field, uint32_t w
     b.motion.rot[0] = b.motion.rot[3] = 1.0f;
 }
 
-constexpr size_t LOAD_SLOT_BYTES = BODY_LOAD_WORDS * sizeof(unsigned long long);
-
-// Zeroes the load words of `slot` on the stream, behind what is enqueued, and its step count (loads never enabled: no words).
-hipError_t loads_zero(fs_sim* s, uint32_t slot) {
-    Bodies::Loads& L = s->bodies.loads;
-    L.steps[slot] = 0;
-    return L.words.p ? hipMemsetAsync(L.words.p + slot * BODY_LOAD_WORDS, 0, LOAD_SLOT_BYTES, s->stream) : hipSuccess;
-}
-
 // host -> a fresh device field, blocking on the handle's stream
 fs_status body_upload(fs_sim* s, const fs_vec2* host, size_t pixels, DevArray<float2>* dev) {
     static_assert(sizeof(fs_vec2) == sizeof(float2), "fs_vec2 is two f32");
@@ -249,7 +240,7 @@ fs_status fs_body_destroy(fs_sim* s, uint32_t body) {
     Bodies::Slot& b = s->bodies.slot[body];
     b.w = b.h = 0;
     b.field.release();
-    FS_HIP(loads_zero(s, body));                    // before the slot can be reused (a new body starts at zero)
+    FS_HIP(s->bodies.loads.zero(s->stream, body));                // before the slot can be reused (a new body starts at zero)
     return FS_OK;
 }
 
@@ -259,24 +250,8 @@ uint32_t fs_body_count(const fs_sim* s) { return s ? s->bodies.count() : 0u; }
 fs_status fs_body_loads_enable(fs_sim* s, int on) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
     if (s->slab) return fail(FS_ERR_UNSUPPORTED, BODY_SLAB);
-    Bodies::Loads& L = s->bodies.loads;
-    if (on) {
-        FS_HIP(hipSetDevice(s->device));
-        if (!L.words.p) {
-            DevArray<unsigned long long> words, shards;
-            if (words.alloc(FS_MAX_BODIES * BODY_LOAD_WORDS) != hipSuccess || shards.alloc(BODY_LOAD_SHARDS * BODY_LOAD_ROW) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(FS_ERR_OOM, "body loads: device words");
-            }
-            FS_HIP(hipMemsetAsync(shards.p, 0, shards.n * sizeof(unsigned long long), s->stream));   // the fold keeps them zero
-            L.words = std::move(words);
-            L.shards = std::move(shards);
-        }
-        FS_HIP(hipMemsetAsync(L.words.p, 0, L.words.n * sizeof(unsigned long long), s->stream));
-        for (uint64_t& c : L.steps) c = 0;
-    }
-    L.on = on != 0;
-    return FS_OK;
+    if (on) FS_HIP(hipSetDevice(s->device));
+    return s->bodies.loads.enable(s->stream, on != 0);
 }
 
 int fs_body_loads_enabled(const fs_sim* s) { return s && s->bodies.loads.on ? 1 : 0; }
@@ -287,12 +262,8 @@ fs_status fs_body_loads(fs_sim* s, uint32_t body, fs_body_load* out, int reset) 
     if (!L.on) return fail(FS_ERR_INVALID, "body loads: not enabled (fs_body_loads_enable)");
     FS_HIP(hipSetDevice(s->device));
     unsigned long long w[BODY_LOAD_WORDS];
-    const uint64_t steps = L.steps[body];
-    hipError_t e = hipMemcpyAsync(w, L.words.p + body * BODY_LOAD_WORDS, LOAD_SLOT_BYTES, hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess && reset) e = loads_zero(s, body);      // behind the read, on the stream
-    const hipError_t es = hipStreamSynchronize(s->stream);      // before `w` leaves scope, whatever happened
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(FS_ERR_DEVICE, hipGetErrorString(e));
+    uint64_t steps;
+    FS_TRY(L.read(s->stream, body, reset != 0, w, &steps));
     out->impulse_q[0] = (int64_t)w[0]; out->impulse_q[1] = (int64_t)w[1];
     out->angular_q = (int64_t)w[2];
     out->hits = w[3]; out->dropped = w[4];

@@ -108,6 +108,15 @@ struct Bodies3 {
 // After launch3_force, on the positions (A.pos_out) and velocities (A.vel) it stored: the operators B of every body in order.
 // P: n, bx, by, bz, damping.  done (may be null): signalled by the kernel's completion, as launch3_force's is.
 void launch3_bodies(hipStream_t st, const Params3& P, const Arrays3& A, const Bodies3& B, hipEvent_t done);
+// The same pass while the handle's loads are on (include/fluidsim.h "3D body loads"): k3_bodies_loads, which also
+// adds each body's eight 64-bit words of this step (sum Q(j.xyz), sum Q(t.xyz), hits, dropped; by kernel index) into a row of
+// `shards` (BODY_LOAD_SHARDS rows of BODY3_LOAD_ROW words, all zero on entry), then k3_body_loads_fold, which adds the rows into
+// `words` (FS3_MAX_BODIES x 8, by slot: M.slot[kernel index]) and leaves `shards` zero again; the fold carries `done`.
+constexpr uint32_t BODY3_LOAD_WORDS = 8u;
+constexpr uint32_t BODY3_LOAD_ROW = BODIES3_MAX * BODY3_LOAD_WORDS;
+static_assert(BODIES3_MAX == BODIES2_MAX, "BodyLoadMap (fs_kernels.h) holds a slot per body of either handle");
+void launch3_bodies_loads(hipStream_t st, const Params3& P, const Arrays3& A, const Bodies3& B, const BodyLoadMap& M,
+                          unsigned long long* shards, unsigned long long* words, hipEvent_t done);
 void launch3_import(hipStream_t st, uint32_t n, const Arrays3& A);   // aos -> pos, pred, vel, key
 void launch3_export(hipStream_t st, uint32_t n, const Arrays3& A);   // ... and back
 

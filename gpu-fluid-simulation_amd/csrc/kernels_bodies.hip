@@ -23,6 +23,7 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
+#include "fs_body_loads.h"
 #include "fs_device.h"
 #include "fs_kernels.h"
 
@@ -131,9 +132,6 @@ __device__ __forceinline__ bool body_apply(const Body2& K, uint32_t i, float2& p
     return true;
 }
 
-// Q(x): the integer nearest to x * 2^20, ties to even; the product is exact for |x| < 2^14 and the result below 2^34.
-__device__ __forceinline__ long long load_q(float x) { return (long long)rintf(x * (float)(1u << BODY_LOAD_SHIFT)); }
-
 // One hit's j and tz into the lane's three sums; false: out of range or NaN, the hit is dropped and adds nothing.
 __device__ __forceinline__ bool load_add(const BodyHit& h, long long& ax, long long& ay, long long& at) {
     const float jx = h.v0x - h.v1x, jy = h.v0y - h.v1y;
@@ -143,26 +141,6 @@ __device__ __forceinline__ bool load_add(const BodyHit& h, long long& ax, long l
     if (!(fabsf(jx) < 16384.0f && fabsf(jy) < 16384.0f && fabsf(tz) < 16384.0f)) return false;      // NaN: dropped
     ax += load_q(jx); ay += load_q(jy); at += load_q(tz);
     return true;
-}
-
-// v + (v of the lane SHR places below in the lane's row of 16, 0 where that leaves the row): one DPP move per half
-template <int SHR>
-__device__ __forceinline__ long long row_shr_add(long long v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u64)v, 0x110 + SHR, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)((u64)v >> 32), 0x110 + SHR, 0xf, 0xf, true);
-    return v + (long long)(((u64)(uint32_t)hi << 32) | (u64)(uint32_t)lo);
-}
-
-// The sum over the wave's 64 lanes, wave-uniform (all lanes active): four DPP steps leave each row's sum in its lane 15, the
-// four row sums are read into scalar registers and added there.  No LDS traffic, unlike a __shfl_xor butterfly (measured first:
-// 4 us slower with the paddle in the fluid, profiles/body_loads2d_cost.md).
-__device__ __forceinline__ long long wave_sum(long long v) {
-    v = row_shr_add<1>(v); v = row_shr_add<2>(v); v = row_shr_add<4>(v); v = row_shr_add<8>(v);
-    const int lo = (int)(uint32_t)(u64)v, hi = (int)(uint32_t)((u64)v >> 32);
-    u64 s = 0ull;
-    for (int r = 15; r < 64; r += 16)
-        s += ((u64)(uint32_t)__builtin_amdgcn_readlane(hi, r) << 32) | (u64)(uint32_t)__builtin_amdgcn_readlane(lo, r);
-    return (long long)s;
 }
 
 template <bool AOS>
@@ -221,15 +199,10 @@ __global__ __launch_bounds__(B2B) void k_bodies_loads(Bodies2 B, uint32_t n, flo
     }
 }
 
-// Block k (one wave) owns word k = 5 * kernel index + word: lane r takes row r of the shard table and zeroes it for the next step.
+// Block k (one wave) owns word k = 5 * kernel index + word: lane r takes row r of the shard table and zeroes it for the next step
+// (fs_body_loads.h, shared with the 3D pass).
 __global__ __launch_bounds__(BODY_LOAD_SHARDS) void k_body_loads_fold(BodyLoadMap M, u64* __restrict__ shards, u64* __restrict__ words) {
-    static_assert(BODY_LOAD_SHARDS == 64u, "one wave holds a word's rows");
-    const uint32_t k = blockIdx.x;                                        // < 5 * M.count: the grid
-    u64* const cell = shards + threadIdx.x * BODY_LOAD_ROW + k;
-    const u64 part = *cell;
-    if (part != 0ull) *cell = 0ull;
-    const u64 sum = (u64)wave_sum((long long)part);
-    if (threadIdx.x == 0u && sum != 0ull) words[M.slot[k / BODY_LOAD_WORDS] * BODY_LOAD_WORDS + k % BODY_LOAD_WORDS] += sum;
+    body_loads_fold<BODY_LOAD_WORDS, BODY_LOAD_ROW>(M, shards, words);
 }
 
 void launch_bodies_loads(hipStream_t st, const StepParams& P, const StepArrays& A, const Bodies2& B, void* aos, const BodyLoadMap& M,

@@ -327,6 +327,15 @@ public:
     }
     void remove_body(uint32_t body) { check(fs3_body_destroy(h_, body)); }
     uint32_t body_count() const { return fs3_body_count(h_); }
+    // 3D body loads (include/fluidsim.h "3D body loads"): what the fluid hands each body, summed on the GPU in fixed point.
+    void enable_body_loads(bool on = true) { check(fs3_body_loads_enable(h_, on ? 1 : 0)); }
+    bool body_loads_enabled() const { return fs3_body_loads_enabled(h_) != 0; }
+    fs3_body_load body_loads(uint32_t body, bool reset = false) {         // blocking
+        fs3_body_load l{};
+        check(fs3_body_loads(h_, body, &l, reset ? 1 : 0));
+        return l;
+    }
+    const void* body_loads_device() { const void* p = nullptr; check(fs3_body_loads_device(h_, &p)); return p; }
     // 3D surface tension: colour-field CSF with coefficient sigma and threshold tau, for the ticks enqueued afterwards.
     void set_surface_tension(float coefficient, float threshold = 0.0f) { check(fs3_set_surface_tension(h_, 1, coefficient, threshold)); }
     void clear_surface_tension() { check(fs3_set_surface_tension(h_, 0, 0.0f, 0.0f)); }

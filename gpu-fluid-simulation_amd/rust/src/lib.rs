@@ -161,6 +161,23 @@ impl BodyLoad {
     /// Angular momentum about the body's centre handed to the body, counter-clockwise positive.
     pub fn angular_impulse(&self, mass: f64) -> f64 { self.angular_q as f64 * mass / (1u64 << BODY_LOAD_SHIFT) as f64 }
 }
+/// fs3_body_load: what the fluid handed one 3D body (build extension, include/fluidsim.h "3D body loads"); 72 bytes.  The six
+/// sums are in units of 2^-BODY_LOAD_SHIFT per unit particle mass, modulo 2^64; `angular_q` is about the body's centre, world frame.
+#[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct Body3Load { pub impulse_q: [i64; 3], pub angular_q: [i64; 3], pub hits: u64, pub dropped: u64, pub steps: u64 }
+const _: () = assert!(std::mem::size_of::<Body3Load>() == 72);
+impl Body3Load {
+    /// Momentum handed to the body: `impulse_q * 2^-20 * mass`, `mass` the mass of one particle.
+    pub fn impulse(&self, mass: f64) -> [f64; 3] {
+        let k = mass / (1u64 << BODY_LOAD_SHIFT) as f64;
+        [self.impulse_q[0] as f64 * k, self.impulse_q[1] as f64 * k, self.impulse_q[2] as f64 * k]
+    }
+    /// Angular momentum about the body's centre handed to the body, world frame.
+    pub fn angular_impulse(&self, mass: f64) -> [f64; 3] {
+        let k = mass / (1u64 << BODY_LOAD_SHIFT) as f64;
+        [self.angular_q[0] as f64 * k, self.angular_q[1] as f64 * k, self.angular_q[2] as f64 * k]
+    }
+}
 /// FS_MAX_BODIES: the body slots of a 2D handle.
 pub const MAX_BODIES: u32 = 8;
 /// FS3_MAX_BODIES: the body slots of a 3D handle.
@@ -336,6 +353,10 @@ extern "C" {
     fn fs3_body_download(sim: *mut fs_sim3, body: u32, dst: *mut Vec3, n: usize) -> c_int;
     fn fs3_body_destroy(sim: *mut fs_sim3, body: u32) -> c_int;
     fn fs3_body_count(sim: *const fs_sim3) -> u32;
+    fn fs3_body_loads_enable(sim: *mut fs_sim3, on: c_int) -> c_int;
+    fn fs3_body_loads_enabled(sim: *const fs_sim3) -> c_int;
+    fn fs3_body_loads(sim: *mut fs_sim3, body: u32, out: *mut Body3Load, reset: c_int) -> c_int;
+    fn fs3_body_loads_device(sim: *mut fs_sim3, words: *mut *const c_void) -> c_int;
     fn fs3_set_surface_tension(sim: *mut fs_sim3, enable: c_int, coefficient: f32, threshold: f32) -> c_int;
     fn fs3_surface_tension_enabled(sim: *const fs_sim3) -> c_int;
     fn fs3_surface_tension_params(sim: *const fs_sim3, coefficient: *mut f32, threshold: *mut f32) -> c_int;
@@ -867,6 +888,21 @@ impl FluidSimulation3D {
     /// Destroys a body and frees its slot; the other bodies keep theirs.  Blocking.
     pub fn remove_body(&mut self, body: u32) { check(unsafe { fs3_body_destroy(self.raw, body) }); }
     pub fn body_count(&self) -> u32 { unsafe { fs3_body_count(self.raw) } }
+    /// Build extension: 3D body loads (include/fluidsim.h).  Enabling zeroes every body's words; loads only observe.
+    pub fn enable_body_loads(&mut self, on: bool) { check(unsafe { fs3_body_loads_enable(self.raw, on as c_int) }); }
+    pub fn body_loads_enabled(&self) -> bool { unsafe { fs3_body_loads_enabled(self.raw) != 0 } }
+    /// What the fluid handed `body` since its words were last zeroed.  Blocking; `reset` zeroes the slot behind the read.
+    pub fn body_loads(&mut self, body: u32, reset: bool) -> Body3Load {
+        let mut l = Body3Load::default();
+        check(unsafe { fs3_body_loads(self.raw, body, &mut l, reset as c_int) });
+        l
+    }
+    /// The device address of the 8 x 8 64-bit words, by slot, for a consumer on the handle's stream.
+    pub fn body_loads_device(&mut self) -> *const c_void {
+        let mut p: *const c_void = std::ptr::null();
+        check(unsafe { fs3_body_loads_device(self.raw, &mut p) });
+        p
+    }
     /// Build extension: 3D surface tension (include/fluidsim.h), colour-field CSF with coefficient sigma and threshold tau,
     /// for the ticks enqueued afterwards.
     pub fn set_surface_tension(&mut self, coefficient: f32, threshold: f32) { check(unsafe { fs3_set_surface_tension(self.raw, 1, coefficient, threshold) }); }

@@ -185,16 +185,7 @@ class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Bodies, _Simulation):
         v = lambda a: np.array([a.x, a.y], dtype=np.float32)      # noqa: E731
         return v(m.centre), np.array(list(m.rot), dtype=np.float32).reshape(2, 2), v(m.velocity), np.float32(m.angular_velocity)
 
-    # -- 2D body loads (build extension) -----------------------
-    def enable_body_loads(self, on=True):
-        """Turns the per-body load sums on or off (include/fluidsim.h "2D body loads").  Enabling zeroes every body's words.  While
-        off a step launches what it launched without them; while on the particles are still byte for byte the same."""
-        self._call("body_loads_enable", 1 if on else 0)
-
-    @property
-    def body_loads_enabled(self):
-        return bool(self._fn("body_loads_enabled")(self._h))
-
+    # -- 2D body loads (build extension): enable, enabled and the device pointer are _Bodies' ---
     def body_loads(self, body, reset=False):
         """What the fluid handed body `body` since its words were last zeroed: a BodyLoads record.  Blocking (one sync);
         reset=True zeroes the slot's words behind the read."""
@@ -202,12 +193,6 @@ class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Bodies, _Simulation):
         self._call("body_loads", int(body), C.byref(out), 1 if reset else 0)
         return BodyLoads((int(out.impulse_q[0]), int(out.impulse_q[1])), int(out.angular_q), int(out.hits), int(out.dropped),
                          int(out.steps))
-
-    def body_loads_device_ptr(self):
-        """fs_body_loads_device: the device address of the 8 x 5 64-bit words, by slot, for a consumer on the handle's stream."""
-        p = C.c_void_p()
-        self._call("body_loads_device", C.byref(p))
-        return p.value
 
     def export_handle(self, which=_abi.FS_EXPORT_PARTICLES):
         """fs_export_handle: interprocess handle of the AoS particle view (switches on the live view) or of start_indices."""

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (FS_MATH_IEEE, MESH_VERTEX_DTYPE, PARTICLE3_DTYPE, SAMPLE3_DTYPE, SURFACE_HIT_DTYPE, BodyMotion3, Camera3,
+from ._abi import (FS_MATH_IEEE, MESH_VERTEX_DTYPE, PARTICLE3_DTYPE, SAMPLE3_DTYPE, SURFACE_HIT_DTYPE, Body3Load, BodyMotion3, Camera3,
                    Nozzle3, Settings3, TickSettings3, Vec3, load_library)
 from ._handle import _Bodies, _check, _Count, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec3
 
@@ -226,6 +226,51 @@ class FluidSimulation3D(_Count, _Tracking, _SurfaceTension, _Bodies, _Simulation
         self._call("body_get_motion", int(body), C.byref(m))
         v = lambda a: np.array([a.x, a.y, a.z], dtype=np.float32)      # noqa: E731
         return v(m.centre), np.array(list(m.rot), dtype=np.float32).reshape(3, 3), v(m.velocity), v(m.angular_velocity)
+
+    # -- 3D body loads (build extension): enable, enabled and the device pointer are _Bodies' ---
+    def body_loads(self, body, reset=False):
+        """What the fluid handed body `body` since its words were last zeroed: a BodyLoads3D record.  Blocking (one sync);
+        reset=True zeroes the slot's words behind the read."""
+        out = Body3Load()
+        self._call("body_loads", int(body), C.byref(out), 1 if reset else 0)
+        return BodyLoads3D([int(q) for q in out.impulse_q], [int(q) for q in out.angular_q], int(out.hits), int(out.dropped),
+                           int(out.steps))
+
+
+class BodyLoads3D:
+    """One body's load words (include/fluidsim.h "3D body loads"): the raw integers impulse_q (x, y, z) and angular_q (x, y, z,
+    about the body's centre, world frame) in units of 2^-20 velocity (and velocity * length) per unit particle mass, `hits`,
+    `dropped`, and `steps`, the steps they were summed over.  The float64 views multiply by 2^-20 and the mass of one particle."""
+    SCALE = 2.0 ** -_abi.FS_BODY_LOAD_SHIFT
+
+    def __init__(self, impulse_q, angular_q, hits, dropped, steps):
+        self.impulse_q, self.angular_q, self.hits, self.dropped, self.steps = tuple(impulse_q), tuple(angular_q), hits, dropped, steps
+        if len(self.impulse_q) != 3 or len(self.angular_q) != 3:
+            raise ValueError("BodyLoads3D: impulse_q and angular_q have three components each")
+
+    def words(self):
+        """the eight device words as Python ints modulo 2^64, in the device's order"""
+        m = (1 << 64) - 1
+        return [q & m for q in self.impulse_q + self.angular_q] + [self.hits, self.dropped]
+
+    def impulse(self, mass):
+        """momentum handed to the body, float64 [3]"""
+        return np.array([q * self.SCALE * float(mass) for q in self.impulse_q], dtype=np.float64)
+
+    def angular_impulse(self, mass):
+        """angular momentum about the body's centre handed to the body, world frame, float64 [3]"""
+        return np.array([q * self.SCALE * float(mass) for q in self.angular_q], dtype=np.float64)
+
+    def mean_force(self, mass, dt):
+        """the impulse divided by steps * dt (zero steps: zero)"""
+        return self.impulse(mass) / (self.steps * float(dt)) if self.steps else np.zeros(3)
+
+    def mean_torque(self, mass, dt):
+        return self.angular_impulse(mass) / (self.steps * float(dt)) if self.steps else np.zeros(3)
+
+    def __repr__(self):
+        return (f"BodyLoads3D(impulse_q={self.impulse_q}, angular_q={self.angular_q}, hits={self.hits}, dropped={self.dropped}, "
+                f"steps={self.steps})")
 
 
 def rigid_motion(centre0, velocity, axis, rate, t):

@@ -1115,6 +1115,58 @@ fs_status fs3_body_download(fs_sim3* sim, uint32_t body, fs_vec3* dst, size_t n)
 fs_status fs3_body_destroy(fs_sim3* sim, uint32_t body);
 uint32_t  fs3_body_count(const fs_sim3* sim);                                                /* 0 for a NULL handle */
 
+/* ------------------------------------------------ 3D body loads (build extension, opt-in per handle) */
+/* The 3D form of "2D body loads": the impulse and the angular impulse the fluid gives each body of "3D moving bodies", summed on
+ * the GPU inside the bodies' own pass.  fs3_body_loads_enable(sim, on) turns them on or off.  While off, a step launches exactly
+ * the kernels it launches without this section and leaves the same bytes.  While on, the particle state is still byte for byte
+ * that of "3D moving bodies": loads only observe.
+ *
+ * A HIT of body b is a particle that reaches the line `p.a = p.a + f.a` of the operator B_b above.  With that section's names:
+ *   v0   the velocity on entry to B_b: after the step, after the static collider C if one is set, and after the operators of the
+ *        lower slots (their wall re-clamp included);
+ *   v1.a = us.a + (r.a - k*n.a): the velocity B_b computes, BEFORE its wall re-clamp — what the wall does is not the body's load;
+ *   s.a  = p.a - c.a: the pushed position relative to the centre, before the re-clamp.
+ * f32 without contraction, one operation per line:
+ *     j.a = v0.a - v1.a                                     (a = x, y, z; impulse on the body per unit particle mass)
+ *     t.x = s.y*j.z - s.z*j.y     (two products, then one subtraction; the same for the others)
+ *     t.y = s.z*j.x - s.x*j.z
+ *     t.z = s.x*j.y - s.y*j.x     (angular impulse about the body's centre, world frame)
+ * The positional push p += f carries no momentum and is not counted.
+ *
+ * Fixed point: Q and the drop rule are those of "2D body loads", FS_BODY_LOAD_SHIFT reused: Q(x) is the signed 64-bit integer
+ * nearest to x * 2^20, ties to even.  If any of the SIX values j.x, j.y, j.z, t.x, t.y, t.z is NaN or fails
+ * fabsf(x) < 16384.0f, the hit adds nothing to the six sums and is counted in `dropped`; its particle is moved exactly as
+ * without loads.  Per body the engine keeps EIGHT 64-bit words, in this order:
+ *     sum Q(j.x), sum Q(j.y), sum Q(j.z), sum Q(t.x), sum Q(t.y), sum Q(t.z), hits (dropped ones included), dropped
+ * each modulo 2^64 over all hits of all steps since the words were last zeroed.  Integer sums are associative, so the words are
+ * ONE defined value whatever the order of lanes, waves and workgroups.  Momentum handed to body b = impulse_q * 2^-20 * (the mass
+ * of one particle); angular momentum about its centre likewise from angular_q.
+ *
+ * Enabling (also when already on) zeroes every slot's words and `steps`.  A body created while loads are on starts at zero; a
+ * destroyed slot's words are zeroed before the slot can be reused.  Steps taken while loads are off count nothing, and disabling
+ * keeps the words (they cannot be read until the next enable, which zeroes them).  fs3_body_loads is blocking and ordered on
+ * fs3_stream(sim): it returns the words behind every step enqueued so far; reset != 0 zeroes that slot's words and `steps` behind
+ * the read, on the stream.  fs3_body_loads_device hands out the device address of FS3_MAX_BODIES x 8 64-bit words, by slot, in the
+ * order above, for a consumer on the stream: it holds the finished values once any step has completed (the step's last launch
+ * folds the pass's partial sums into it; the address is stable until the handle is destroyed).
+ *
+ * Checks, in this order, all FS_ERR_INVALID (a 3D handle has no slab form); a refused call changes nothing:
+ *  1. NULL handle (fs3_body_loads_enabled: 0).
+ *  2. NULL out pointer (`out`, `words`).
+ *  3. fs3_body_loads: a slot that holds no body.
+ *  4. fs3_body_loads, fs3_body_loads_device: loads are not enabled ("not enabled").
+ * The time of both launches falls inside FS_PASS_FORCE.  FS_ABI_VERSION is unchanged.  See DESIGN.md §26. */
+typedef struct fs3_body_load {
+    int64_t  impulse_q[3];   /* sum Q(j.x), sum Q(j.y), sum Q(j.z) */
+    int64_t  angular_q[3];   /* sum Q(t.x), sum Q(t.y), sum Q(t.z) */
+    uint64_t hits, dropped;
+    uint64_t steps;          /* steps enqueued with loads on since the words were zeroed (host-side count), as in 2D */
+} fs3_body_load;             /* 72 bytes */
+fs_status fs3_body_loads_enable(fs_sim3* sim, int on);
+int       fs3_body_loads_enabled(const fs_sim3* sim);                                        /* 0 for a NULL handle */
+fs_status fs3_body_loads(fs_sim3* sim, uint32_t body, fs3_body_load* out, int reset);        /* blocking */
+fs_status fs3_body_loads_device(fs_sim3* sim, const void** words);
+
 /* ------------------------------------------------ 3D surface tension (build extension, opt-in) */
 /* The 3D form of the 2D step's opt-in surface tension above: a colour-field continuum-surface-force pass (Mueller, Charypar &
  * Gross 2003, §4.4) with the 3D poly6 kernel of the 3D step, W = C (h^2 - r^2)^3, C = 315/(64 pi h^9).  Enabled, every step runs

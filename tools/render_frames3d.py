@@ -1,6 +1,11 @@
 """Render a few frames of the 3D dam break to PNG through the ray-marched G-buffer, headless:
   python tools/render_frames3d.py [n] [frame,frame,...] [outdir] [width] [height] [--box x0,y0,z0,x1,y1,z1[,voxels]]
-                                  [--surface-tension SIGMA[,TAU]] [--dye] [--faucet K[,NU,NV]] [--paddle [AMPLITUDE,PERIOD]]
+                                  [--surface-tension SIGMA[,TAU]] [--dye] [--faucet K[,NU,NV]] [--paddle [AMPLITUDE,PERIOD]] [--float]
+--float: a dynamic body — a cube of half the fluid's density, a quarter of the block's side, released above the
+block falls onto the dam break; the handle's body loads are on and BodyDynamics3D integrates them on the host between the steps
+(one sync per step): the fluid's impulses slow and turn it (the bodies' contact model hands over momentum where particles are
+pushed out of the box, it is no pressure integral), and the host stops it at the floor.  Prints the box's pose with every frame;
+the box itself is not drawn.
 --paddle: a moving rigid body: a plate across the tank, as high and deep as the box and 3 h thick, that swings along
 x about the middle of the tank, x(t) = AMPLITUDE * sin(2 pi t / PERIOD) (default a twentieth of the box's width, 2 s); its pose and
 velocity are set before every step.  The dam breaks against it and it keeps making waves; the plate itself is not drawn.
@@ -38,6 +43,9 @@ if "--paddle" in sys.argv:
     given = k + 1 < len(sys.argv) and "," in sys.argv[k + 1]
     paddle = [float(x) for x in sys.argv[k + 1].split(",")] if given else []
     del sys.argv[k:k + (2 if given else 1)]
+floating = "--float" in sys.argv
+if floating:
+    sys.argv.remove("--float")
 dye = "--dye" in sys.argv
 if dye:
     sys.argv.remove("--dye")
@@ -61,6 +69,23 @@ if paddle is not None:
     mask[:, :, [0, -1]] = 0
     plate = sim.add_body_mask(mask, (5 * st.smoothing_radius, sy, sz))
     print("paddle: body", plate, sim.body_dims(plate), "amplitude", amp, "period", period, flush=True)
+if floating:
+    sp = st.particle_spacing
+    L = round(n ** (1.0 / 3.0)) * sp
+    side = 0.25 * L
+    cube = np.full((8, 8, 8), 255, dtype=np.uint8)       # solid but its rim: the field pushes out of every face
+    for axis in range(3):
+        rim = [slice(None)] * 3
+        rim[axis] = [0, -1]
+        cube[tuple(rim)] = 0
+    floater = sim.add_body_mask(cube, (side, side, side))
+    mass = 0.5 * tick.mass * (side / sp) ** 3            # half as dense as the fluid it displaces (one particle per sp^3)
+    inertia = mass * side * side / 6.0
+    dyn = g.BodyDynamics3D(mass, (inertia, inertia, inertia), (-sx / 2 + 0.5 * L + 0.5 * sp, sy / 2 - L - side, 0.0),
+                           gravity=(tick.gravity.x, tick.gravity.y, tick.gravity.z), particle_mass=tick.mass)
+    sim.enable_body_loads()
+    sim.set_body_motion(floater, *dyn.motion())
+    print("float: body", floater, sim.body_dims(floater), "mass", mass, flush=True)
 if tension is not None:
     sim.set_surface_tension(tension[0], tension[1] if len(tension) > 1 else 1.0)
     print("surface tension", sim.surface_tension_params, flush=True)
@@ -87,6 +112,11 @@ for f in frames:
             t = (done + 1) * tick.delta                 # the pose at the end of the step that is about to run
             sim.set_body_motion(plate, (amp * np.sin(om * t), 0.0, 0.0), velocity=(amp * om * np.cos(om * t), 0.0, 0.0))
         sim.tick(tick); done += 1
+        if floating:
+            dyn.advance(sim, floater, tick)
+            if dyn.centre[1] > 0.5 * (sy - side):           # +y is down: the floor
+                dyn.centre[1], dyn.velocity[1] = 0.5 * (sy - side), 0.0
+                sim.set_body_motion(floater, *dyn.motion())
     if faucet is not None:
         print("frame", f, "particles", sim.particle_count, "of", sim.capacity, flush=True)
     iso = 0.5 * float(np.median(sim.download_particles()["density"]))
@@ -105,4 +135,6 @@ for f in frames:
     g.write_png(os.path.join(outdir, f"dam3d_{n}_{f:05d}.png"), rgba, background=(0.04, 0.04, 0.06))
     print("frame", f, "coverage", round(float((hits["hit"] != 0).mean()), 4), "mean march index of hits",
           round(float(hits["steps"][hits["hit"] != 0].mean()), 1), flush=True)
+    if floating:
+        print("  box centre", dyn.centre.tolist(), "velocity", dyn.velocity.tolist(), "angular velocity", dyn.angular_velocity.tolist(), flush=True)
 sim.close()
