@@ -341,6 +341,11 @@ PROTOTYPES = {
     "fs_body_loads_enabled": (C.c_int, [_P]),
     "fs_body_loads": (C.c_int, [_P, C.c_uint32, C.POINTER(BodyLoad), C.c_int]),
     "fs_body_loads_device": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
+    "fs_set_diffusion": (C.c_int, [_P, C.c_int, C.c_float]),
+    "fs_get_diffusion": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
+    "fs_set_buoyancy": (C.c_int, [_P, C.c_int, C.c_float, C.c_float]),
+    "fs_get_buoyancy": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "fs_download_buoyancy": (C.c_int, [_P, _P, C.c_size_t]),
     "fs_export_handle": (C.c_int, [_P, C.c_int, _P]),
     "fs_import_open": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "fs_import_read": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t]),

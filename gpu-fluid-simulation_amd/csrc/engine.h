@@ -1,7 +1,7 @@
 // engine.h — what the host files of the C ABI share beyond fs_host.h: the 2D simulation handle and the state of each of its
 // features, the step parameters, and the device check and create-time proofs (also used by the 3D handle's files through
 // engine_3d.h).  The handle's files:
-// engine.hip (life cycle, step, transfers, renderer hand-off), engine_features.hip (surface tension, particle tracking, moving bodies;
+// engine.hip (life cycle, step, transfers, renderer hand-off), engine_features.hip (surface tension, particle tracking, channel diffusion, moving bodies;
 // what the bodies share with the 3D handle's engine_3d_features.hip: engine_bodies.h, and BodySlots and BodyLoads below),
 // engine_query.hip (density render, field sampling), engine_count.hip (a particle count that changes at run time; what it
 // shares with the 3D handle's engine_3d_count.hip: engine_count.h, and Tracking and RemoveScratch below),
@@ -189,6 +189,52 @@ struct Tracking {
     static void scatter_by_id(const std::vector<uint32_t>& ids, const std::vector<Rec>& rec, Rec* dst, size_t n) {
         for (size_t i = 0; i < ids.size(); ++i)
             if (ids[i] < n) dst[ids[i]] = rec[i];
+    }
+};
+
+// Opt-in diffusion and buoyancy of the tracking channels (build extension; single-domain 2D handles):
+// fs_set_diffusion / fs_set_buoyancy in engine_features.hip.  Host settings only, until a buoyancy channel is first set: then
+// `fb`, 8 B per slot.  Nothing set: no launch, no allocation.
+struct Diffusion {
+    float kappa[FS_TRACK_MAX_CHANNELS] = {};   // conductivity per channel; 0: the channel does not diffuse
+    int buoy = -1;                  // the buoyancy channel, -1: none
+    float beta = 0.0f, reference = 0.0f;
+    DevArray<float2> fb;            // per sorted slot: what the last buoyancy step handed the force pass (st + b, or b)
+    bool valid = false;             // a buoyancy step has been enqueued since the channel was last set (and the count has not changed)
+    // fs_track_enable / fs_track_disable: every setting goes
+    void clear() {
+        for (float& k : kappa) k = 0.0f;
+        buoy = -1; beta = reference = 0.0f;
+        valid = false;
+    }
+    // This step's pass, after surface tension's and before the force launches: the diffusing channels are advanced in place (through
+    // the spare tracking set, which is free once the carry has run, and one device-to-device copy per row back), and with a buoyancy
+    // channel the force launch's `st` operand becomes fb.  Returns that operand: st_in itself when there is no buoyancy channel.
+    const float2* enqueue(hipStream_t st, const StepParams& P, const StepArrays& A, const fs_uniform& u, const Tracking& trk,
+                          uint32_t capacity, const float2* st_in) {
+        if (!trk.on()) return st_in;
+        DiffusePlan D;
+        for (int c = 0; c < trk.channels; ++c)
+            if (kappa[c] != 0.0f) {
+                D.channel[D.count] = c;
+                D.g[D.count++] = (2.0f * kappa[c]) * u.delta;
+            }
+        if (buoy >= 0 && buoy < trk.channels) {
+            D.buoyancy_channel = buoy;
+            D.beta = beta; D.reference = reference;
+            D.gravity_x = u.gravity.x; D.gravity_y = u.gravity.y;
+        }
+        if (!D.count && D.buoyancy_channel < 0) return st_in;
+        float* const cur = trk.attr[trk.cur].p;
+        float* const spare = trk.attr[trk.cur ^ 1].p;
+        launch_diffuse(st, P, A, D, u.poly6_kernel_derivative, cur, spare, capacity, st_in, fb.p);
+        for (int k = 0; k < D.count && P.n; ++k) {
+            const size_t row = (size_t)D.channel[k] * capacity;
+            (void)hipMemcpyAsync(cur + row, spare + row, (size_t)P.n * sizeof(float), hipMemcpyDeviceToDevice, st);   // errors: the step's hipGetLastError
+        }
+        if (D.buoyancy_channel < 0) return st_in;
+        valid = true;
+        return fb.p;
     }
 };
 
@@ -407,6 +453,7 @@ struct fs_sim : fsd::HandleQueues, fsd::ParticleArrays {
     uint32_t aos_tick = 0xFFFFFFFFu;   // tick whose state the AoS view holds (only meaningful with aos_live)
     fsd::SurfaceTension st;         // the opt-in features' state: one line each in enqueue_step
     fsd::Tracking trk;
+    fsd::Diffusion dif;
     fsd::Bodies bodies;
     fsd::RemoveScratch removal;     // (not a per-step feature: emission and removal happen between steps)
     // what walks the cell table off the step path (engine_query.hip: fs_render_density; field sampling): the records

@@ -341,6 +341,7 @@ static fs_status enqueue_step(fs_sim* s, const fs_tick_settings* t) {
     if (prof) FS_HIP(hipEventRecord(ev[4], st));
     fsd::ForceLaunch L = s->force_launch();
     L.st_in = s->st.enqueue(st, P, A, s->uniform);       // surface tension, if on (inside the FS_PASS_FORCE interval)
+    L.st_in = s->dif.enqueue(st, P, A, s->uniform, s->trk, s->capacity, L.st_in);   // channel diffusion and buoyancy, if set (likewise)
     A.rho = s->rho.p;                  // (the force kernels take the array whatever the mode)
     if (pos_by_src) { A.pos_s = s->pos.p; A.pos_out = s->pos_s.p; }    // the role swap described above
     if (s->aos_live) L.aos_out = s->aos.p;

@@ -36,6 +36,7 @@ fs_status count_changed(fs_sim* s, uint32_t new_n) {
     s->n = new_n;
     s->walk_ready = false;
     s->st.valid = false;
+    s->dif.valid = false;
     s->aos_tick = 0xFFFFFFFFu;
     return health;
 }
@@ -90,12 +91,12 @@ fs_status fs_reserve(fs_sim* s, uint32_t capacity) {
     ParticleArrays A;                                       // pos .. pairs (and an 8-word counter that is dropped again)
     DevArray<uint32_t> key, dirty, csort;
     DevArray<fs_particle> aos;
-    DevArray<float2> stf;
+    DevArray<float2> stf, fb;
     TrackingGrowth G;
     hipError_t e = hipSuccess;
     auto ok = [&e](hipError_t r) { e = r; return r == hipSuccess; };
     (void)(ok(A.alloc_common(cap)) && ok(key.alloc(cap)) && ok(dirty.alloc(sort_tile_count(capacity))) && ok(aos.alloc(cap)) &&
-           ok(csort.alloc(counting ? counting_sort_scratch_words(capacity, s->ncell) : 0)) && ok(stf.alloc(s->st.stf.p ? cap : 0)) &&
+           ok(csort.alloc(counting ? counting_sort_scratch_words(capacity, s->ncell) : 0)) && ok(stf.alloc(s->st.stf.p ? cap : 0)) && ok(fb.alloc(s->dif.fb.p ? cap : 0)) &&
            ok(G.alloc(s->trk, cap)));
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -118,6 +119,7 @@ fs_status fs_reserve(fs_sim* s, uint32_t capacity) {
     if (e == hipSuccess) e = carry(q, A.pairs, s->pairs, n);
     if (e == hipSuccess) e = carry(q, key, s->key, n);
     if (e == hipSuccess) e = carry(q, stf, s->st.stf, n);
+    if (e == hipSuccess) e = carry(q, fb, s->dif.fb, n);
     if (e == hipSuccess) e = G.carry_from(q, s->trk, n, s->capacity, cap);
     const hipError_t es = hipStreamSynchronize(q);                         // before anything is freed, whatever happened
     if (e == hipSuccess) e = es;
@@ -128,6 +130,7 @@ fs_status fs_reserve(fs_sim* s, uint32_t capacity) {
     s->key = std::move(key); s->sort_dirty = std::move(dirty); s->aos = std::move(aos);
     if (csort.p) s->csort = std::move(csort);
     if (stf.p) s->st.stf = std::move(stf);
+    if (fb.p) s->dif.fb = std::move(fb);
     G.commit(s->trk);
     s->removal.release();                                                   // sized by the capacity: the next removal allocates it again
     s->capacity = capacity;

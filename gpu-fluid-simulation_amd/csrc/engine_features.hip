@@ -1,6 +1,6 @@
 // engine_features.hip — the opt-in per-step features of a single-domain handle: surface tension, particle
-// tracking (§12), moving bodies (§24) and their loads (§25).  Their state and what the step enqueues for them: SurfaceTension /
-// Tracking / Bodies (engine.h).
+// tracking (§12), channel diffusion and buoyancy (§27), moving bodies (§24) and their loads (§25).  Their state and what the step
+// enqueues for them: SurfaceTension / Tracking / Diffusion / Bodies (engine.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -48,16 +48,84 @@ fs_status fs_track_enable(fs_sim* s, int channels) {
     if (s->slab) return fail(FS_ERR_UNSUPPORTED, "tracking: single-domain handles only (not built for slab handles)");
     FS_HIP(hipSetDevice(s->device));
     FS_TRY(s->trk.enable(s->stream, s->n, s->capacity, channels));
+    s->dif.clear();                 // the channels start over: so do their conductivities and the buoyancy channel
     return FS_OK;
 }
 
 fs_status fs_track_disable(fs_sim* s) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
     s->trk.channels = -1;           // the arrays stay allocated until the handle is destroyed
+    s->dif.clear();
     return FS_OK;
 }
 
 int fs_track_channels(const fs_sim* s) { return s ? s->trk.channels : -1; }
+
+}  // extern "C"
+
+// ---- channel diffusion and buoyancy ---------------------------------------------------------------------------
+namespace {
+const char* const DIF_SLAB = "diffusion: single-domain handles only (not built for slab handles)";
+
+// The checks every call of the feature starts with: the handle ("null"), the slab refusal, tracking on.
+fs_status diffusion_handle(const fs_sim* s) {
+    if (!s) return fail(FS_ERR_INVALID, "null argument");
+    if (s->slab) return fail(FS_ERR_UNSUPPORTED, DIF_SLAB);
+    if (!s->trk.on()) return fail(FS_ERR_INVALID, "diffusion: tracking is off (fs_track_enable with at least one channel first)");
+    return FS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+fs_status fs_set_diffusion(fs_sim* s, int channel, float conductivity) {
+    FS_TRY(diffusion_handle(s));
+    if (channel < 0 || channel >= s->trk.channels) return fail(FS_ERR_INVALID, "diffusion: no such channel");
+    if (!std::isfinite(conductivity) || conductivity < 0.0f) return fail(FS_ERR_INVALID, "diffusion: a conductivity that is negative or not finite");
+    s->dif.kappa[channel] = conductivity;       // host memory only: the next enqueue takes it by value
+    return FS_OK;
+}
+
+fs_status fs_get_diffusion(const fs_sim* s, int channel, float* conductivity) {
+    FS_TRY(diffusion_handle(s));
+    if (!conductivity) return fail(FS_ERR_INVALID, "null argument");
+    if (channel < 0 || channel >= s->trk.channels) return fail(FS_ERR_INVALID, "diffusion: no such channel");
+    *conductivity = s->dif.kappa[channel];
+    return FS_OK;
+}
+
+fs_status fs_set_buoyancy(fs_sim* s, int channel, float beta, float reference) {
+    FS_TRY(diffusion_handle(s));
+    if (channel < -1 || channel >= s->trk.channels) return fail(FS_ERR_INVALID, "buoyancy: no such channel");
+    if (!std::isfinite(beta) || !std::isfinite(reference)) return fail(FS_ERR_INVALID, "buoyancy: beta or reference not finite");
+    if (channel >= 0 && !s->dif.fb.p) {
+        FS_HIP(hipSetDevice(s->device));
+        if (s->dif.fb.alloc(s->capacity) != hipSuccess) { (void)hipGetLastError(); return fail(FS_ERR_OOM, "buoyancy: force buffer"); }
+    }
+    if (channel != s->dif.buoy) s->dif.valid = false;       // fs_download_buoyancy waits for a step of this setting
+    s->dif.buoy = channel;
+    s->dif.beta = channel >= 0 ? beta : 0.0f;
+    s->dif.reference = channel >= 0 ? reference : 0.0f;
+    return FS_OK;
+}
+
+fs_status fs_get_buoyancy(const fs_sim* s, int* channel, float* beta, float* reference) {
+    FS_TRY(diffusion_handle(s));
+    if (!channel || !beta || !reference) return fail(FS_ERR_INVALID, "null argument");
+    *channel = s->dif.buoy; *beta = s->dif.beta; *reference = s->dif.reference;
+    return FS_OK;
+}
+
+fs_status fs_download_buoyancy(fs_sim* s, fs_vec2* dst, size_t n) {
+    if (!s || !dst) return fail(FS_ERR_INVALID, "null argument");
+    if (s->slab) return fail(FS_ERR_UNSUPPORTED, DIF_SLAB);
+    if (!s->dif.valid) return fail(FS_ERR_INVALID, "buoyancy: no step with a buoyancy channel since the handle was created or the channel was last set");
+    if (n != s->n) return fail(FS_ERR_INVALID, "buoyancy: n must equal the particle count");
+    FS_HIP(hipSetDevice(s->device));
+    if (n) FS_HIP(hipMemcpyAsync(dst, s->dif.fb.p, n * sizeof(fs_vec2), hipMemcpyDeviceToHost, s->stream));
+    FS_HIP(hipStreamSynchronize(s->stream));
+    return sort_health(s);
+}
 
 }  // extern "C"
 

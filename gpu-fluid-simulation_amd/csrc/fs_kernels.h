@@ -72,6 +72,21 @@ void launch_force(hipStream_t st, const StepParams& P, const StepArrays& A, cons
 // densities (rho2; A.rho != nullptr: tolerance mode, densities in rho) over the density pass's neighbour walk.  Single-domain handles.
 // cg = poly6_kernel_derivative (24/(pi h^8)); sigma = surface_tension_coefficient, tau = surface_tension_treshold.
 void launch_surface_tension(hipStream_t st, const StepParams& P, const StepArrays& A, float sigma, float tau, float cg, float2* st_out);
+// Diffusion and buoyancy of the tracking channels (build extension; kernels_diffuse.hip), after launch_density and
+// launch_surface_tension, before launch_force.  The plan of one step, by value: channel[0 .. count) are the diffusing channels,
+// ascending, g[k] = (2 kappa) delta of channel[k]; buoyancy_channel >= 0: fb_out[i] = (st_in[i] +) (rho_i beta (reference - A_b[i]))
+// gravity, which the force launch takes as ForceLaunch::st_in.  attr_in: the channels as the carry delivered them (channel c at
+// c * stride); attr_out: the spare set, of which only the rows of the diffusing channels are written.  cg, A.rho: as for
+// launch_surface_tension.  count == 0 and no buoyancy channel: no launch.
+struct DiffusePlan {
+    int count = 0;
+    int channel[4] = {0, 0, 0, 0};
+    float g[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    int buoyancy_channel = -1;
+    float beta = 0.0f, reference = 0.0f, gravity_x = 0.0f, gravity_y = 0.0f;
+};
+void launch_diffuse(hipStream_t st, const StepParams& P, const StepArrays& A, const DiffusePlan& D, float cg, const float* attr_in,
+                    float* attr_out, uint32_t stride, const float2* st_in, float2* fb_out);
 // The opt-in moving bodies of a single-domain handle (include/fluidsim.h "2D moving bodies") as k_bodies takes
 // them, by value and apart from StepParams (kernels_bodies.hip).  Per body: the field of push vectors over the body's own box,
 // and the motion of this enqueue.  rij: row-major R, world = R * local.  body[0 .. count) are the slots in use, ascending.

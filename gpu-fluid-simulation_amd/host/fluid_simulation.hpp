@@ -92,6 +92,20 @@ public:
     // Build extension, NOT in the reference: colour-field surface tension (include/fluidsim.h), single-domain handles.
     void set_surface_tension(bool enable) { check(fs_set_surface_tension(h_, enable ? 1 : 0)); }
     bool surface_tension_enabled() const { return fs_surface_tension_enabled(h_) != 0; }
+    // channel diffusion and buoyancy: tracking must be on; track / untrack clear the settings
+    void set_diffusion(int channel, float conductivity) { check(fs_set_diffusion(h_, channel, conductivity)); }
+    float diffusion(int channel) const { float k = 0.0f; check(fs_get_diffusion(h_, channel, &k)); return k; }
+    void set_buoyancy(int channel, float beta, float reference = 0.0f) { check(fs_set_buoyancy(h_, channel, beta, reference)); }
+    void clear_buoyancy() { check(fs_set_buoyancy(h_, -1, 0.0f, 0.0f)); }
+    bool buoyancy(int* channel, float* beta, float* reference) const {      // false: no buoyancy channel
+        check(fs_get_buoyancy(h_, channel, beta, reference));
+        return *channel >= 0;
+    }
+    std::vector<fs_vec2> buoyancy_forces() {                                 // the last buoyancy step's fb per particle, download order
+        std::vector<fs_vec2> v(particle_count());
+        check(fs_download_buoyancy(h_, v.data(), v.size()));
+        return v;
+    }
     std::vector<fs_vec2> surface_tension_forces() {
         std::vector<fs_vec2> v(particle_count());
         check(fs_download_surface_tension(h_, v.data(), v.size()));

@@ -266,6 +266,11 @@ extern "C" {
     fn fs_set_surface_tension(sim: *mut fs_sim, enable: c_int) -> c_int;
     fn fs_surface_tension_enabled(sim: *const fs_sim) -> c_int;
     fn fs_download_surface_tension(sim: *mut fs_sim, dst: *mut Vec2, n: usize) -> c_int;
+    fn fs_set_diffusion(sim: *mut fs_sim, channel: c_int, conductivity: f32) -> c_int;
+    fn fs_get_diffusion(sim: *const fs_sim, channel: c_int, conductivity: *mut f32) -> c_int;
+    fn fs_set_buoyancy(sim: *mut fs_sim, channel: c_int, beta: f32, reference: f32) -> c_int;
+    fn fs_get_buoyancy(sim: *const fs_sim, channel: *mut c_int, beta: *mut f32, reference: *mut f32) -> c_int;
+    fn fs_download_buoyancy(sim: *mut fs_sim, dst: *mut Vec2, n: usize) -> c_int;
     // particle tracking (build extension, opt-in)
     fn fs_track_enable(sim: *mut fs_sim, channels: c_int) -> c_int;
     fn fs_track_disable(sim: *mut fs_sim) -> c_int;
@@ -467,6 +472,28 @@ impl FluidSimulation {
     pub fn surface_tension_forces(&mut self) -> Vec<Vec2> {
         let mut v = vec![Vec2 { x: 0.0, y: 0.0 }; self.particle_count() as usize];
         check(unsafe { fs_download_surface_tension(self.raw, v.as_mut_ptr(), v.len()) }); v
+    }
+    /// Build extension, NOT in the reference: diffusion and buoyancy of the tracking channels (include/fluidsim.h).  Channel
+    /// `channel` diffuses between neighbours with this conductivity (0: not at all) in the steps after the call.  Tracking must
+    /// be on; `track` and `untrack` clear every conductivity and the buoyancy channel.
+    pub fn set_diffusion(&mut self, channel: u32, conductivity: f32) { check(unsafe { fs_set_diffusion(self.raw, channel as c_int, conductivity) }); }
+    pub fn diffusion(&self, channel: u32) -> f32 {
+        let mut k = 0.0f32;
+        check(unsafe { fs_get_diffusion(self.raw, channel as c_int, &mut k) }); k
+    }
+    /// The buoyancy channel: a particle with value a gains -beta (a - reference) gravity delta of velocity per step.
+    pub fn set_buoyancy(&mut self, channel: u32, beta: f32, reference: f32) { check(unsafe { fs_set_buoyancy(self.raw, channel as c_int, beta, reference) }); }
+    pub fn clear_buoyancy(&mut self) { check(unsafe { fs_set_buoyancy(self.raw, -1, 0.0, 0.0) }); }
+    /// (channel, beta, reference) of the buoyancy channel, if one is set.
+    pub fn buoyancy(&self) -> Option<(u32, f32, f32)> {
+        let (mut c, mut b, mut r) = (0 as c_int, 0.0f32, 0.0f32);
+        check(unsafe { fs_get_buoyancy(self.raw, &mut c, &mut b, &mut r) });
+        if c < 0 { None } else { Some((c as u32, b, r)) }
+    }
+    /// What the last step with a buoyancy channel handed the force pass per particle, in `download_particles` order.
+    pub fn buoyancy_forces(&mut self) -> Vec<Vec2> {
+        let mut v = vec![Vec2 { x: 0.0, y: 0.0 }; self.particle_count() as usize];
+        check(unsafe { fs_download_buoyancy(self.raw, v.as_mut_ptr(), v.len()) }); v
     }
     /// Build extension, NOT in the reference: particle tracking (include/fluidsim.h).  Every particle gets an id (its current
     /// slot) and `channels` f32 attributes (all 0.0) that follow it through the sort of every later step.  Single-domain handles.

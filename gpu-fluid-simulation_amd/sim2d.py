@@ -86,6 +86,47 @@ class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Bodies, _Simulation):
         """Colour-field surface tension from the tick's surface_tension_coefficient / _treshold, for the steps after this call."""
         self._call("set_surface_tension", 1 if enable else 0)
 
+    # -- channel diffusion and buoyancy (build extension, opt-in; DESIGN.md §27) ---------
+    def set_diffusion(self, channel, conductivity):
+        """Channel `channel` diffuses between neighbours with conductivity kappa >= 0 (0: not at all, the default), for the steps
+        after this call.  Tracking must be on; track() and untrack() clear every conductivity and the buoyancy channel.  The
+        explicit update is stable while conductivity <= diffusion_limit(...)."""
+        self._call("set_diffusion", int(channel), float(conductivity))
+
+    def diffusion(self, channel):
+        k = C.c_float()
+        self._call("get_diffusion", int(channel), C.byref(k))
+        return float(k.value)
+
+    def set_buoyancy(self, channel, beta, reference=0.0):
+        """Channel `channel` becomes the buoyancy channel: a particle with value a gains -beta * (a - reference) * gravity * delta
+        of velocity per step (Boussinesq), for the steps after this call."""
+        self._call("set_buoyancy", int(channel), float(beta), float(reference))
+
+    def clear_buoyancy(self):
+        self._call("set_buoyancy", -1, 0.0, 0.0)
+
+    @property
+    def buoyancy(self):
+        """(channel, beta, reference) of the buoyancy channel, or None"""
+        c, b, r = C.c_int(), C.c_float(), C.c_float()
+        self._call("get_buoyancy", C.byref(c), C.byref(b), C.byref(r))
+        return None if c.value < 0 else (int(c.value), float(b.value), float(r.value))
+
+    def buoyancy_forces(self):
+        """What the last step with a buoyancy channel handed the force pass per particle (the buoyancy force, plus the surface
+        tension's when that is on): (N, 2) float32 in download_particles() order."""
+        out = np.empty((self.particle_count, 2), dtype=np.float32)
+        self._call("download_buoyancy", _ptr(out), out.shape[0])
+        return out
+
+    @staticmethod
+    def diffusion_limit(settings, tick, rest_density):
+        """rho0 h^2 / (16 delta): the largest conductivity at which the explicit update of a uniform fluid at density rho0 is a
+        convex combination of the neighbours' values.  The engine does not enforce it."""
+        h = float(settings.smoothing_radius)
+        return float(rest_density) * h * h / (16.0 * float(tick.delta))
+
     def sort_plan(self):
         """Diagnostics of the sort's late-stage plan (fs_sort_plan_read): dict of counts since create.  Blocking."""
         info = _abi.SortPlanInfo()

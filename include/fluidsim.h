@@ -1314,6 +1314,66 @@ typedef struct fs_sort_plan_info {
 } fs_sort_plan_info;
 fs_status fs_sort_plan_read(fs_sim* sim, fs_sort_plan_info* out);
 
+/* ------------------------------------------------ channel diffusion and buoyancy (build extension, opt-in) */
+/* NOT in the reference.  Without these calls a tracking channel is a passive label: nothing changes it, nothing reads it.  With
+ * them a channel may diffuse between neighbours (heat, dye, salinity) and one channel may feed back into the motion as a
+ * Boussinesq buoyancy force.  2D single-domain handles only; see DESIGN.md §27.
+ *
+ * Tracking must be on with C >= 1 channels.  Per channel c < C there is a conductivity kappa_c >= 0; 0, the default, means the
+ * channel does not diffuse.  At most one channel b is the buoyancy channel, with expansion coefficient beta and reference value
+ * A0; the default is none.  The pass runs in every step after the density pass — and after the surface-tension pass when that is
+ * on — and before the force pass.
+ *
+ * Inputs: the sorted slots' predicted positions q; this step's clamped densities rho, the values the force pass divides by; the
+ * channel values A_c as the step's carry (the tracking pass) delivered them; from the uniform h2 = sqr_radius, m = particle_mass,
+ * Cg = poly6_kernel_derivative = 24/(pi h^8), delta and gravity.
+ *
+ * Diffusion.  For slot i, over the neighbours j the density pass visits (same cells, same order, same start-index rules, the
+ * stale-start quirk under ref_quirks = 1 included, i itself included), in f32 without contraction, sums starting at +0.0f:
+ *     ox = q_j.x - q_i.x;  oy = q_j.y - q_i.y;  r2 = ox*ox + oy*oy
+ *     if (r2 > h2) skip                          (a NaN r2 is admitted, as by the surface-tension pass)
+ *     d  = h2 - r2
+ *     w  = m / rho_j                             (IEEE division; == |1/rho_j| as the density pass rounds it when m == 1)
+ *     wk = w * ((Cg * d) * d)
+ *     for each diffusing channel c:  acc_c += wk * (A_c[j] - A_c[i])
+ * and then, with u_i = 1.0f / rho_i (IEEE) and g_c = (2.0f * kappa_c) * delta formed once on the host in f32,
+ *     A_c'[i] = A_c[i] + (g_c * acc_c) * u_i
+ * Jacobi semantics: every A_c[j] read is the value before the pass.  A skipped candidate is skipped, not multiplied by zero: its
+ * A may be a NaN.  A channel with kappa_c = 0 is not written at all: NaN payloads, -0.0 and denormals survive bit for bit.
+ * This is the Cleary-Monaghan / Brookshaw form with the poly6 gradient, (x_ij . grad W_ij) / r^2 = -Cg d^2: no square root, no
+ * singularity at r = 0, non-negative weights, symmetric in i and j, so sum_i A_i is conserved in exact arithmetic where the
+ * neighbour relation is symmetric.  The second moment of the weight is 2 (the sum approximates the Laplacian of A) and the
+ * effective diffusivity is kappa_c / rho_i.  For a uniform fluid at rho0 the explicit update is a convex combination of the
+ * neighbours' values while kappa_c * delta <= rho0 h^2 / 16 (the weight integrates to 8 / h^2); the engine does not enforce it.
+ *
+ * Buoyancy.  With a = A_b[i], the value before the pass,
+ *     s  = beta * (A0 - a)
+ *     bx = (rho_i * s) * gravity.x;  by = (rho_i * s) * gravity.y
+ *     fb = surface tension on ? (st.x + bx, st.y + by) : (bx, by)
+ * and move_particle uses ax = (fp.x + fv.x) + fb.x (likewise y) where the surface-tension step uses st; everything after it is
+ * unchanged.  After the division by rho_i a hot particle gains -beta (a - A0) gravity delta of velocity.
+ *
+ * With buoyancy off the particle state, start_indices and ids are byte-identical with diffusion on or off, in every math mode
+ * and both sort modes.  With nothing set a handle launches what it always did and allocates nothing.  FS_MATH_WGSL_ULP and
+ * FS_MATH_TOLERANCE run this same IEEE pass (tolerance mode on its own densities).  The pass's time falls inside the
+ * FS_PASS_FORCE interval of fs_profile_read.
+ *
+ * fs_set_diffusion / fs_set_buoyancy: host settings, taking effect for the steps enqueued after the call (channel = -1 switches
+ *   buoyancy off; the first buoyancy channel allocates 8 B per particle).  fs_track_enable (also a re-initialising one) and
+ *   fs_track_disable clear every conductivity and the buoyancy channel.
+ * fs_get_diffusion / fs_get_buoyancy: the values in use (channel -1, beta 0, reference 0: no buoyancy channel).
+ * fs_download_buoyancy: the last step's fb, under the rules of fs_download_surface_tension: one fs_vec2 per particle in
+ *   fs_download_particles' slot order, n must equal the particle count, FS_ERR_INVALID when no step with a buoyancy channel has
+ *   been enqueued since the handle was created, since the channel was last chosen, or since the count changed.  Blocking.
+ * FS_ERR_INVALID: a NULL handle or argument ("null" in fs_last_error), tracking off, channel outside [0, C) (fs_set_buoyancy:
+ *   outside [-1, C)), a conductivity that is negative or not finite, a beta or reference that is not finite.  A slab handle gets
+ *   FS_ERR_UNSUPPORTED. */
+fs_status fs_set_diffusion(fs_sim* sim, int channel, float conductivity);
+fs_status fs_get_diffusion(const fs_sim* sim, int channel, float* conductivity);
+fs_status fs_set_buoyancy(fs_sim* sim, int channel, float beta, float reference);   /* channel = -1: off */
+fs_status fs_get_buoyancy(const fs_sim* sim, int* channel, float* beta, float* reference);
+fs_status fs_download_buoyancy(fs_sim* sim, fs_vec2* dst, size_t n);
+
 /* ----------------------------------------------------------------- errors */
 const char* fs_last_error(void);  /* thread-local, never NULL */
 int fs_abi_version(void);
