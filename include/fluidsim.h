@@ -497,6 +497,12 @@ uint32_t fs_track_next_id(const fs_sim* sim);
  * predicted_position, density and grid are not touched, and neither is start_indices.  All three math modes (FS_MATH_IEEE,
  * FS_MATH_WGSL_ULP, FS_MATH_TOLERANCE) run this same IEEE operator.  The engine does not check that rot is a rotation, only that
  * it is finite.  A pushed particle keeps the body surface's velocity along the normal, so a moving wall hands momentum over.
+ * The lines above hold at every operand a call accepts; nothing is flushed, ranged or special-cased.  f32 denormals count: an
+ * extent of 2^-149 gives hb = 0 (only q == 0 is inside), and with an extent of 1e-40 the quotient of two denormals is 0.5.  A
+ * vector whose squares overflow has len = +inf and n = 0: the particle is pushed (onto a wall) and keeps v = us + r.  damping is
+ * used as the tick gives it, also outside [0, 1].  The plain step zeroes a NaN velocity, clamps the speed and clamps a position
+ * onto the walls, so at an ordinary damping B_0 meets a finite velocity and a position that is finite or NaN; a later operator
+ * can meet the NaN, infinite or enormous velocity an earlier one left, and computes with it as written.
  *
  * fs_body_create: a field made by the caller.  fs_body_create_from_mask: the exact distance transform of "3D colliders" on a
  * w x h x 1 mask over the body's box, the z component dropped — the same passes, the same tie rules, s_a = extent.a / (float)W_a,
@@ -1075,7 +1081,9 @@ fs_status fs3_collider_download(fs_sim3* sim, fs_vec3* dst, size_t n);          
  *     v.a = us.a + (r.a - k*n.a)
  *     per axis, in x, y, z order: if fabsf(p.a) > b.a { p.a = b.a * sign(p.a); v.a *= -1.0f * damping }
  * predicted_position, density and grid are not touched.  FS_MATH_TOLERANCE handles run the same IEEE operator, as they do C.
- * The engine does not check that rot is a rotation, only that it is finite.
+ * The engine does not check that rot is a rotation, only that it is finite.  As in "2D moving bodies", the lines hold at every
+ * operand a call accepts: denormal extents are not flushed, a vector whose squares overflow has n = 0, damping is used as given,
+ * and an operator computes as written with the NaN, infinite or enormous velocity an earlier one left.
  *
  * fs3_body_create: a field made by the caller.  fs3_body_create_from_mask: the producer of "3D colliders" on the body's box —
  * the same three passes, the same tie rules, s_a = extent.a / (float)W_a; `field_host` (may be NULL) receives the field.

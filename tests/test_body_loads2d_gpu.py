@@ -9,6 +9,7 @@ import pytest
 from tests import bodies2d_ref as B
 from tests import body_loads2d_ref as L
 from tests import test_bodies2d_gpu as G
+from tests.handle_helpers import _same_but_nan_bits
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -261,16 +262,6 @@ def _run_pair(fs, p, tick, bodies, sort="bitonic"):
     sim.close()
     G._same(got, kinematic, "loads on against loads off, the same bodies")
     return after, got, words
-
-
-def _same_but_nan_bits(got, want, ctx):
-    """every field on its bits, except that a NaN need only be a NaN: inf - inf has no defined sign or payload"""
-    for name in want.dtype.names:
-        a, b = np.ascontiguousarray(got[name]), np.ascontiguousarray(want[name])
-        same = a.view(np.uint32) == b.view(np.uint32)
-        if a.dtype == np.float32:
-            same |= np.isnan(a) & np.isnan(b)
-        assert same.all(), f"{ctx}: {name} differs in {int((~same).sum())} values"
 
 
 def test_out_of_range_and_nan_hits_are_dropped(fs):

@@ -11,7 +11,7 @@ from tests import bodies3d_ref as B
 from tests import body_loads3d_ref as L
 from tests import collide3d_ref as CR
 from tests import test_bodies3d_gpu as G
-from tests.handle_helpers import _add, _same, _size
+from tests.handle_helpers import _add, _same, _same_but_nan_bits, _size
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -339,18 +339,6 @@ def _run_pair(fs, p, tick, bodies):
     sim.close()
     _same(got, kinematic, "loads on against loads off, the same bodies")
     return after, got, words
-
-
-def _same_but_nan_bits(got, want, ctx):
-    """every field on its bits, except that a NaN need only be a NaN: inf - inf has no defined sign or payload"""
-    for name in want.dtype.names:
-        if name == "pad":
-            continue
-        a, b = np.ascontiguousarray(got[name]), np.ascontiguousarray(want[name])
-        same = a.view(np.uint32) == b.view(np.uint32)
-        if a.dtype == np.float32:
-            same |= np.isnan(a) & np.isnan(b)
-        assert same.all(), f"{ctx}: {name} differs in {int((~same).sum())} values"
 
 
 def test_out_of_range_and_nan_hits_are_dropped(fs):
