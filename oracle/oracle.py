@@ -9,6 +9,9 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "_build", "libsph_oracle.so")
+# the code-generation flags of oracle/Makefile's CXXFLAGS (its warning options aside), for whoever compiles a translation unit
+# that includes the oracle's sources (tests/checker_lib.py); tests/test_support.py holds the two together
+FLAGS = ["-O2", "-std=c++17", "-fPIC", "-fopenmp", "-ffp-contract=off", "-fno-fast-math"]
 
 PARTICLE_DTYPE = np.dtype([("position", "<f4", (2,)), ("predicted_position", "<f4", (2,)),
                            ("velocity", "<f4", (2,)), ("density", "<f4"), ("grid", "<u4")])
@@ -34,7 +37,7 @@ def lib():
         L.orc_create.restype = P
         L.orc_create.argtypes = [P, C.c_float, C.c_float, C.c_int]
         L.orc_destroy.argtypes = [P]
-        for name in ("orc_predict", "orc_spatial_lookup", "orc_sort", "orc_cell_starts", "orc_move"):
+        for name in ("orc_predict", "orc_spatial_lookup", "orc_sort", "orc_sort_stable", "orc_cell_starts", "orc_move"):
             getattr(L, name).argtypes = [P]
             getattr(L, name).restype = None
         L.orc_begin_tick.argtypes = [P, P]

@@ -6,10 +6,13 @@ A registry run takes a case of tests/hard_states2d.py in one sort mode with four
     0  finite values of both signs up to 1e30 (hard_states2d.sample_channel_values), diffusing, and the buoyancy channel
     1  negative zeros, kappa = 0: must come back as a bit copy of what tracking alone gives
     2  finite values, diffusing four times as fast (g R up to 2: past the stable range, still bit for bit)
-    3  NaN payloads, +-inf, -0.0 and denormals (test_tracking_gpu.special_bits), diffusing
+    3  NaN payloads, +-inf, -0.0 and denormals (bitcmp.special_bits, the twelve-value pool at seed 99), diffusing
 kappa is chosen from the checker's R of the first step so that g R = 1/2 where R is largest among the finite ones."""
+import functools
+
 import numpy as np
 
+from tests import bitcmp
 from tests import hard_states2d as H
 
 f32 = np.float32
@@ -19,11 +22,7 @@ CHANNELS = 4
 BETA, REFERENCE = 0.01, 0.0
 
 
-def special_bits(n):
-    """tests/test_tracking_gpu.special_bits (that module is marked gpu as a whole; the pool is restated here)"""
-    pool = np.array([0x7FC00001, 0xFFC12345, 0x7F800001, 0xFF8ABCDE, 0x80000000, 0x00000001, 0x807FFFFF, 0x7F800000,
-                     0xFF800000, 0x3F800000, 0x00000000, 0xC2F6E979], dtype=np.uint32)
-    return pool[np.random.default_rng(99).integers(0, pool.size, size=n)].view(np.float32)
+special_bits = functools.partial(bitcmp.special_bits, seed=99, pool=bitcmp.POOL_TWELVE)      # special_bits(n), as the tracking tests draw it
 
 
 def kappa_for(R, delta, target):

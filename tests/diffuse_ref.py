@@ -1,75 +1,32 @@
 """ctypes loader of the diffusion / buoyancy checker (tests/diffuse_checker.cpp, which includes tests/st_checker.cpp and through
-it oracle/sph_oracle.cpp, both unchanged).  TEST INFRASTRUCTURE ONLY.  Built on first use with the oracle's flags into a
-per-user cache directory outside the tree (the checkout may be read-only), keyed by the sources' contents, as tests/st_ref.py
-does it.
+it oracle/sph_oracle.cpp, both unchanged).  TEST INFRASTRUCTURE ONLY.  Built and loaded on first use by tests/checker_lib.py:
+the oracle's flags, a per-user cache outside the tree, keyed by the sources' contents.
 
 DiffuseChecker steps the oracle pass by pass.  Between spatial_lookup and the sort it reads the keys and derives the permutation
 the sort is about to apply, exactly as tests/track_ref.TrackChecker does (oracle.bitonic_keys for the reference network,
 np.argsort(kind="stable") for the stable sort); ids and channels follow it (the carry), then the C side finishes the step:
 cell starts -> density -> optional surface tension -> diffusion / buoyancy -> the move with what the pass hands on."""
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from oracle import oracle as O
+from tests import checker_lib as CL
 from tests import st_ref
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SOURCES = [os.path.join(HERE, "diffuse_checker.cpp"), os.path.join(HERE, "st_checker.cpp"), os.path.join(ROOT, "oracle", "sph_oracle.cpp"),
-           os.path.join(ROOT, "include", "fluidsim.h")]
-FLAGS = st_ref.FLAGS
+P = C.c_void_p
+SOURCES = [CL.here("diffuse_checker.cpp")] + st_ref.SOURCES
+OWN = {"stc_surface_tension": st_ref.OWN["stc_surface_tension"], "stc_move": st_ref.OWN["stc_move"],
+       "dfc_diffuse": (None, [P] * 8), "dfc_finish_step": (None, [P] * 8)}
 MAX_CHANNELS = 4
-
-_lib = None
 
 
 class Settings(C.Structure):
     _fields_ = [("channels", C.c_int), ("kappa", C.c_float * 4), ("buoy", C.c_int), ("beta", C.c_float), ("reference", C.c_float)]
 
 
-def build():
-    h = hashlib.sha256()
-    for s in SOURCES:
-        with open(s, "rb") as f:
-            h.update(f.read())
-    h.update(" ".join(FLAGS).encode())
-    d = os.path.join(tempfile.gettempdir(), f"fs_diffuse_checker_{os.getuid()}")
-    os.makedirs(d, exist_ok=True)
-    out = os.path.join(d, f"libdiffuse_checker_{h.hexdigest()[:16]}.so")
-    if not os.path.exists(out):
-        tmp = f"{out}.{os.getpid()}.tmp"
-        subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + ["-o", tmp, SOURCES[0]])
-        os.replace(tmp, out)
-    return out
-
-
 def lib():
-    global _lib
-    if _lib is None:
-        L = C.CDLL(build())
-        for name, f in O.lib().__dict__.items():        # the oracle's entry points, same prototypes
-            if name.startswith("orc_") and not name.startswith("orc3_"):
-                g = getattr(L, name)
-                g.argtypes, g.restype = f.argtypes, f.restype
-        P = C.c_void_p
-        L.stc_surface_tension.argtypes = [P, P, P]
-        L.stc_surface_tension.restype = None
-        L.stc_move.argtypes = [P, P]
-        L.stc_move.restype = None
-        L.orc_sort_stable.argtypes = [P]
-        L.orc_sort_stable.restype = None
-        L.dfc_diffuse.argtypes = [P, P, P, P, P, P, P, P]
-        L.dfc_diffuse.restype = None
-        L.dfc_finish_step.argtypes = [P, P, P, P, P, P, P, P]
-        L.dfc_finish_step.restype = None
-        L.orc_set_threads(1)
-        _lib = L
-    return _lib
+    return CL.load("diffuse_checker", SOURCES, "orc_", OWN)
 
 
 def set_threads(n):

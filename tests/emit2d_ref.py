@@ -11,8 +11,6 @@ Emission is np.concatenate, the nozzle the header's formula in np.float32 with o
 With surface tension the oracle is tests/st_ref.STChecker at the current count; with tracking the step runs pass by pass as
 tests/track_ref.TrackChecker does and the ids and channels follow its permutation, are appended to on emission
 (id = next_id++, +0.0 per channel) and compacted on removal."""
-import ctypes as C
-
 import numpy as np
 
 from oracle import oracle as O
@@ -110,8 +108,6 @@ def hard_records(name, rec, settings):
 
 def step_passes(sim, tick, stable):
     """One oracle step pass by pass, exactly as orc_step / orc_step_stable (tests/track_ref.py); returns the sort's permutation."""
-    sim.L.orc_sort_stable.argtypes = [C.c_void_p]
-    sim.L.orc_sort_stable.restype = None
     sim.begin_tick(tick)
     sim.predict()
     sim.spatial_lookup()

@@ -1,22 +1,19 @@
 """ctypes loader of the 3D surface-extraction checker (tests/mesh3d_checker.cpp on top of tests/sample3d_checker.cpp and
-oracle/sph_oracle3d.cpp, both included unchanged).  TEST INFRASTRUCTURE ONLY.  Built on first use with the oracle's flags into
-a per-user cache directory outside the tree (the checkout may be read-only), keyed by the sources' contents.  Also here: a
+oracle/sph_oracle3d.cpp, both included unchanged).  TEST INFRASTRUCTURE ONLY.  Built and loaded on first use by
+tests/checker_lib.py: the oracle's flags, a per-user cache outside the tree, keyed by the sources' contents.  Also here: a
 numpy-f32 restatement of the statement (include/fluidsim.h "3D surface extraction") that shares no code with the checker, the
 mask arithmetic that ties the counts to a sampled density volume, and the views the CPU and the GPU tests share."""
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-from oracle import oracle as O
+from tests import checker_lib as CL
 from tests import sample3d_ref as S3
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = [os.path.join(HERE, "mesh3d_checker.cpp")] + S3.SOURCES
-FLAGS = S3.FLAGS
+P = C.c_void_p
+SOURCES = [CL.here("mesh3d_checker.cpp")] + S3.SOURCES
+OWN = {k: S3.OWN[k] for k in ("smp3_load", "smp3_sample", "smp3_sample_grid")}
+OWN["msh3_extract"] = (None, [P, P, C.c_float, P, C.c_uint32, P, C.c_uint32, P, P, P])
 
 MESH_VERTEX_DTYPE = np.dtype([("position", "<f4", (3,)), ("normal", "<f4", (3,)), ("velocity", "<f4", (3,)), ("density", "<f4")])
 assert MESH_VERTEX_DTYPE.itemsize == 40
@@ -33,44 +30,9 @@ class MeshVertex3(C.Structure):
 
 assert C.sizeof(MeshVertex3) == 40
 
-_lib = None
-
-
-def build():
-    h = hashlib.sha256()
-    for s in SOURCES:
-        with open(s, "rb") as fh:
-            h.update(fh.read())
-    h.update(" ".join(FLAGS).encode())
-    d = os.path.join(tempfile.gettempdir(), f"fs_sample_checker_{os.getuid()}")
-    os.makedirs(d, exist_ok=True)
-    out = os.path.join(d, f"libmesh3d_checker_{h.hexdigest()[:16]}.so")
-    if not os.path.exists(out):
-        tmp = f"{out}.{os.getpid()}.tmp"
-        subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + ["-o", tmp, SOURCES[0]])
-        os.replace(tmp, out)
-    return out
-
 
 def lib():
-    global _lib
-    if _lib is None:
-        L = C.CDLL(build())
-        for name, fn in O.lib().__dict__.items():       # the 3D oracle's entry points, same prototypes
-            if name.startswith("orc3_"):
-                g = getattr(L, name)
-                g.argtypes, g.restype = fn.argtypes, fn.restype
-        P = C.c_void_p
-        L.smp3_load.argtypes = [P, P, C.c_size_t, C.c_float]
-        L.smp3_load.restype = C.c_int
-        L.smp3_sample.argtypes = [P, P, C.c_size_t, P]
-        L.smp3_sample.restype = None
-        L.smp3_sample_grid.argtypes = [P, P, P]
-        L.smp3_sample_grid.restype = None
-        L.msh3_extract.argtypes = [P, P, C.c_float, P, C.c_uint32, P, C.c_uint32, P, P, P]
-        L.msh3_extract.restype = None
-        _lib = L
-    return _lib
+    return CL.load("mesh3d_checker", SOURCES, "orc3_", OWN)
 
 
 class Mesh3Checker(S3.Sample3Checker):

@@ -1,22 +1,18 @@
 """ctypes loader of the 3D surface-rendering checker (tests/render3d_checker.cpp on top of tests/sample3d_checker.cpp and
-oracle/sph_oracle3d.cpp, both included unchanged).  TEST INFRASTRUCTURE ONLY.  Built on first use with the oracle's flags into
-a per-user cache directory outside the tree (the checkout may be read-only), keyed by the sources' contents.  Also here: the
+oracle/sph_oracle3d.cpp, both included unchanged).  TEST INFRASTRUCTURE ONLY.  Built and loaded on first use by
+tests/checker_lib.py: the oracle's flags, a per-user cache outside the tree, keyed by the sources' contents.  Also here: the
 cameras and the iso rule that the CPU and the GPU tests share."""
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-from oracle import oracle as O
+from tests import checker_lib as CL
 from tests import sample3d_ref as S3
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SOURCES = [os.path.join(HERE, "render3d_checker.cpp")] + S3.SOURCES
-FLAGS = S3.FLAGS
+P = C.c_void_p
+SOURCES = [CL.here("render3d_checker.cpp")] + S3.SOURCES
+OWN = {"smp3_load": S3.OWN["smp3_load"], "smp3_sample": S3.OWN["smp3_sample"],
+       "rnd3_render": (None, [P, P, P, P]), "rnd3_ray": (None, [P, C.c_uint32, C.c_uint32, P])}
 
 SURFACE_HIT_DTYPE = np.dtype([("t", "<f4"), ("density", "<f4"), ("normal", "<f4", (3,)), ("velocity", "<f4", (3,)),
                               ("steps", "<u4"), ("hit", "<u4")])
@@ -39,44 +35,9 @@ class SurfaceParams3(C.Structure):
 
 assert C.sizeof(Camera3) == 64 and C.sizeof(SurfaceParams3) == 20
 
-_lib = None
-
-
-def build():
-    h = hashlib.sha256()
-    for s in SOURCES:
-        with open(s, "rb") as fh:
-            h.update(fh.read())
-    h.update(" ".join(FLAGS).encode())
-    d = os.path.join(tempfile.gettempdir(), f"fs_sample_checker_{os.getuid()}")
-    os.makedirs(d, exist_ok=True)
-    out = os.path.join(d, f"librender3d_checker_{h.hexdigest()[:16]}.so")
-    if not os.path.exists(out):
-        tmp = f"{out}.{os.getpid()}.tmp"
-        subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + ["-o", tmp, SOURCES[0]])
-        os.replace(tmp, out)
-    return out
-
 
 def lib():
-    global _lib
-    if _lib is None:
-        L = C.CDLL(build())
-        for name, fn in O.lib().__dict__.items():       # the 3D oracle's entry points, same prototypes
-            if name.startswith("orc3_"):
-                g = getattr(L, name)
-                g.argtypes, g.restype = fn.argtypes, fn.restype
-        P = C.c_void_p
-        L.smp3_load.argtypes = [P, P, C.c_size_t, C.c_float]
-        L.smp3_load.restype = C.c_int
-        L.smp3_sample.argtypes = [P, P, C.c_size_t, P]
-        L.smp3_sample.restype = None
-        L.rnd3_render.argtypes = [P, P, P, P]
-        L.rnd3_render.restype = None
-        L.rnd3_ray.argtypes = [P, C.c_uint32, C.c_uint32, P]
-        L.rnd3_ray.restype = None
-        _lib = L
-    return _lib
+    return CL.load("render3d_checker", SOURCES, "orc3_", OWN)
 
 
 def as_camera(cam):

@@ -1,21 +1,17 @@
-"""ctypes loader of the 3D field-sampling checker (tests/sample3d_checker.cpp, which includes oracle/sph_oracle3d.cpp
-unchanged).  TEST INFRASTRUCTURE ONLY.  Built on first use with the oracle's flags into a per-user cache directory outside
-the tree (the checkout may be read-only), keyed by the sources' contents."""
+"""ctypes binding of the 3D field-sampling checker (tests/sample3d_checker.cpp, which includes oracle/sph_oracle3d.cpp
+unchanged).  TEST INFRASTRUCTURE ONLY.  Built and loaded on first use by tests/checker_lib.py: the oracle's flags, a per-user
+cache outside the tree, keyed by the sources' contents."""
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from oracle import oracle as O
+from tests import checker_lib as CL
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SOURCES = [os.path.join(HERE, "sample3d_checker.cpp"), os.path.join(ROOT, "oracle", "sph_oracle3d.cpp"),
-           os.path.join(ROOT, "include", "fluidsim.h")]
-FLAGS = ["-O2", "-std=c++17", "-fPIC", "-fopenmp", "-ffp-contract=off", "-fno-fast-math", "-shared"]   # oracle/Makefile
+P = C.c_void_p
+SOURCES = [CL.here("sample3d_checker.cpp")] + CL.ORACLE_3D
+OWN = {"smp3_load": (C.c_int, [P, P, C.c_size_t, C.c_float]), "smp3_sample": (None, [P, P, C.c_size_t, P]),
+       "smp3_grid_points": (None, [P, P]), "smp3_sample_grid": (None, [P, P, P])}
 
 SAMPLE3_DTYPE = np.dtype([("density", "<f4"), ("weight", "<f4"), ("velocity", "<f4", (3,)), ("gradient", "<f4", (3,)),
                           ("neighbours", "<u4"), ("cell", "<u4")])
@@ -27,44 +23,8 @@ class View3(C.Structure):
                 ("depth", C.c_uint32)]
 
 
-_lib = None
-
-
-def build():
-    h = hashlib.sha256()
-    for s in SOURCES:
-        with open(s, "rb") as f:
-            h.update(f.read())
-    h.update(" ".join(FLAGS).encode())
-    d = os.path.join(tempfile.gettempdir(), f"fs_sample_checker_{os.getuid()}")
-    os.makedirs(d, exist_ok=True)
-    out = os.path.join(d, f"libsample3d_checker_{h.hexdigest()[:16]}.so")
-    if not os.path.exists(out):
-        tmp = f"{out}.{os.getpid()}.tmp"
-        subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + ["-o", tmp, SOURCES[0]])
-        os.replace(tmp, out)
-    return out
-
-
 def lib():
-    global _lib
-    if _lib is None:
-        L = C.CDLL(build())
-        for name, f in O.lib().__dict__.items():        # the 3D oracle's entry points, same prototypes
-            if name.startswith("orc3_"):
-                g = getattr(L, name)
-                g.argtypes, g.restype = f.argtypes, f.restype
-        P = C.c_void_p
-        L.smp3_load.argtypes = [P, P, C.c_size_t, C.c_float]
-        L.smp3_load.restype = C.c_int
-        L.smp3_sample.argtypes = [P, P, C.c_size_t, P]
-        L.smp3_sample.restype = None
-        L.smp3_grid_points.argtypes = [P, P]
-        L.smp3_grid_points.restype = None
-        L.smp3_sample_grid.argtypes = [P, P, P]
-        L.smp3_sample_grid.restype = None
-        _lib = L
-    return _lib
+    return CL.load("sample3d_checker", SOURCES, "orc3_", OWN)
 
 
 def _view(width, height, depth, world_min, world_max):

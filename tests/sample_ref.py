@@ -1,64 +1,26 @@
-"""ctypes loader of the field-sampling checker (tests/sample_checker.cpp, which includes oracle/sph_oracle.cpp unchanged).
-TEST INFRASTRUCTURE ONLY.  Built on first use with the oracle's flags into a per-user cache directory outside the tree
-(the checkout may be read-only), keyed by the sources' contents."""
+"""ctypes binding of the field-sampling checker (tests/sample_checker.cpp, which includes oracle/sph_oracle.cpp unchanged).
+TEST INFRASTRUCTURE ONLY.  Built and loaded on first use by tests/checker_lib.py: the oracle's flags, a per-user cache outside
+the tree, keyed by the sources' contents."""
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from oracle import oracle as O
+from tests import checker_lib as CL
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SOURCES = [os.path.join(HERE, "sample_checker.cpp"), os.path.join(ROOT, "oracle", "sph_oracle.cpp"),
-           os.path.join(ROOT, "include", "fluidsim.h")]
-FLAGS = ["-O2", "-std=c++17", "-fPIC", "-fopenmp", "-ffp-contract=off", "-fno-fast-math", "-shared"]   # oracle/Makefile
+P = C.c_void_p
+SOURCES = [CL.here("sample_checker.cpp")] + CL.ORACLE_2D
+OWN = {"smp_load": (C.c_int, [P, P, C.c_size_t, P, C.c_size_t, P]),
+       "smp_sample": (None, [P, P, C.c_size_t, C.c_int, P, P, P]),
+       "smp_grid_points": (None, [C.c_float] * 4 + [C.c_uint32, C.c_uint32, P]),
+       "smp_sample_grid": (None, [P] + [C.c_float] * 4 + [C.c_uint32, C.c_uint32, C.c_int, P, P, P])}
 
 SAMPLE_DTYPE = np.dtype([("density", "<f4"), ("weight", "<f4"), ("velocity", "<f4", (2,)), ("neighbours", "<u4"), ("cell", "<u4")])
 assert SAMPLE_DTYPE.itemsize == 24
 
-_lib = None
-
-
-def build():
-    h = hashlib.sha256()
-    for s in SOURCES:
-        with open(s, "rb") as f:
-            h.update(f.read())
-    h.update(" ".join(FLAGS).encode())
-    d = os.path.join(tempfile.gettempdir(), f"fs_sample_checker_{os.getuid()}")
-    os.makedirs(d, exist_ok=True)
-    out = os.path.join(d, f"libsample_checker_{h.hexdigest()[:16]}.so")
-    if not os.path.exists(out):
-        tmp = f"{out}.{os.getpid()}.tmp"
-        subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + ["-o", tmp, SOURCES[0]])
-        os.replace(tmp, out)
-    return out
-
 
 def lib():
-    global _lib
-    if _lib is None:
-        L = C.CDLL(build())
-        for name, f in O.lib().__dict__.items():        # the oracle's entry points, same prototypes
-            if name.startswith("orc_") and not name.startswith("orc3_"):
-                g = getattr(L, name)
-                g.argtypes, g.restype = f.argtypes, f.restype
-        P = C.c_void_p
-        L.smp_load.argtypes = [P, P, C.c_size_t, P, C.c_size_t, P]
-        L.smp_load.restype = C.c_int
-        L.smp_sample.argtypes = [P, P, C.c_size_t, C.c_int, P, P, P]
-        L.smp_sample.restype = None
-        L.smp_grid_points.argtypes = [C.c_float] * 4 + [C.c_uint32, C.c_uint32, P]
-        L.smp_grid_points.restype = None
-        L.smp_sample_grid.argtypes = [P] + [C.c_float] * 4 + [C.c_uint32, C.c_uint32, C.c_int, P, P, P]
-        L.smp_sample_grid.restype = None
-        L.orc_set_threads(1)
-        _lib = L
-    return _lib
+    return CL.load("sample_checker", SOURCES, "orc_", OWN)
 
 
 def set_threads(n):

@@ -1,56 +1,20 @@
-"""ctypes loader of the 3D surface-tension checker (tests/st3d_checker.cpp, which includes oracle/sph_oracle3d.cpp unchanged).
-TEST INFRASTRUCTURE ONLY.  Built on first use with the oracle's flags into a per-user cache directory outside the tree
-(the checkout may be read-only), keyed by the sources' contents."""
+"""ctypes binding of the 3D surface-tension checker (tests/st3d_checker.cpp, which includes oracle/sph_oracle3d.cpp unchanged).
+TEST INFRASTRUCTURE ONLY.  Built and loaded on first use by tests/checker_lib.py: the oracle's flags, a per-user cache outside
+the tree, keyed by the sources' contents."""
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from oracle import oracle as O
+from tests import checker_lib as CL
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SOURCES = [os.path.join(HERE, "st3d_checker.cpp"), os.path.join(ROOT, "oracle", "sph_oracle3d.cpp"),
-           os.path.join(ROOT, "include", "fluidsim.h")]
-FLAGS = ["-O2", "-std=c++17", "-fPIC", "-fopenmp", "-ffp-contract=off", "-fno-fast-math", "-shared"]   # oracle/Makefile
-
-_lib = None
-
-
-def build():
-    h = hashlib.sha256()
-    for s in SOURCES:
-        with open(s, "rb") as f:
-            h.update(f.read())
-    h.update(" ".join(FLAGS).encode())
-    d = os.path.join(tempfile.gettempdir(), f"fs_st3d_checker_{os.getuid()}")
-    os.makedirs(d, exist_ok=True)
-    out = os.path.join(d, f"libst3d_checker_{h.hexdigest()[:16]}.so")
-    if not os.path.exists(out):
-        tmp = f"{out}.{os.getpid()}.tmp"
-        subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + ["-o", tmp, SOURCES[0]])
-        os.replace(tmp, out)
-    return out
+P = C.c_void_p
+SOURCES = [CL.here("st3d_checker.cpp")] + CL.ORACLE_3D
+OWN = {"st3_step": (None, [P, P, C.c_int, C.c_float, C.c_float, P, P]), "st3_pass": (None, [P, C.c_float, C.c_float, P, P, P])}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        L = C.CDLL(build())
-        for name, fn in O.lib().__dict__.items():       # the 3D oracle's entry points, same prototypes
-            if name.startswith("orc3_"):
-                g = getattr(L, name)
-                g.argtypes, g.restype = fn.argtypes, fn.restype
-        P = C.c_void_p
-        L.st3_step.argtypes = [P, P, C.c_int, C.c_float, C.c_float, P, P]
-        L.st3_step.restype = None
-        L.st3_pass.argtypes = [P, C.c_float, C.c_float, P, P, P]
-        L.st3_pass.restype = None
-        _lib = L
-    return _lib
+    return CL.load("st3d_checker", SOURCES, "orc3_", OWN)
 
 
 class ST3Checker(O.OracleSim3D):

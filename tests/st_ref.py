@@ -1,61 +1,20 @@
-"""ctypes loader of the surface-tension checker (tests/st_checker.cpp, which includes oracle/sph_oracle.cpp unchanged).
-TEST INFRASTRUCTURE ONLY.  Built on first use with the oracle's flags into a per-user cache directory outside the tree
-(the checkout may be read-only), keyed by the sources' contents."""
+"""ctypes binding of the surface-tension checker (tests/st_checker.cpp, which includes oracle/sph_oracle.cpp unchanged).
+TEST INFRASTRUCTURE ONLY.  Built and loaded on first use by tests/checker_lib.py: the oracle's flags, a per-user cache outside
+the tree, keyed by the sources' contents."""
 import ctypes as C
-import hashlib
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from oracle import oracle as O
+from tests import checker_lib as CL
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SOURCES = [os.path.join(HERE, "st_checker.cpp"), os.path.join(ROOT, "oracle", "sph_oracle.cpp"),
-           os.path.join(ROOT, "include", "fluidsim.h")]
-FLAGS = ["-O2", "-std=c++17", "-fPIC", "-fopenmp", "-ffp-contract=off", "-fno-fast-math", "-shared"]   # oracle/Makefile
-
-_lib = None
-
-
-def build():
-    h = hashlib.sha256()
-    for s in SOURCES:
-        with open(s, "rb") as f:
-            h.update(f.read())
-    h.update(" ".join(FLAGS).encode())
-    d = os.path.join(tempfile.gettempdir(), f"fs_st_checker_{os.getuid()}")
-    os.makedirs(d, exist_ok=True)
-    out = os.path.join(d, f"libst_checker_{h.hexdigest()[:16]}.so")
-    if not os.path.exists(out):
-        tmp = f"{out}.{os.getpid()}.tmp"
-        subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + ["-o", tmp, SOURCES[0]])
-        os.replace(tmp, out)
-    return out
+P = C.c_void_p
+SOURCES = [CL.here("st_checker.cpp")] + CL.ORACLE_2D
+OWN = {"stc_surface_tension": (None, [P, P, P]), "stc_move": (None, [P, P]), "stc_step": (None, [P, P, C.c_int, P])}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        L = C.CDLL(build())
-        for name, f in O.lib().__dict__.items():        # the oracle's entry points, same prototypes
-            if name.startswith("orc_") and not name.startswith("orc3_"):
-                g = getattr(L, name)
-                g.argtypes, g.restype = f.argtypes, f.restype
-        P = C.c_void_p
-        L.stc_surface_tension.argtypes = [P, P, P]
-        L.stc_surface_tension.restype = None
-        L.stc_move.argtypes = [P, P]
-        L.stc_move.restype = None
-        L.stc_step.argtypes = [P, P, C.c_int, P]
-        L.stc_step.restype = None
-        L.orc_sort_stable.argtypes = [P]
-        L.orc_sort_stable.restype = None
-        L.orc_set_threads(1)
-        _lib = L
-    return _lib
+    return CL.load("st_checker", SOURCES, "orc_", OWN)
 
 
 def set_threads(n):

@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from tests.bitcmp import assert_records_equal as _assert_equal3     # the name this module and tests/test_3d_paths_gpu.py use
+
 FLOATS = ("position", "predicted_position", "velocity", "density")
 
 
@@ -50,15 +52,6 @@ def test_lattice3d_matches_oracle(fs, orc):
     want = np.zeros(9 ** 3, dtype=fs.PARTICLE3_DTYPE)
     orc.lib().orc3_lattice(C.addressof(st), off[0], off[1], off[2], want.ctypes.data, want.shape[0])
     assert np.array_equal(got.view(np.uint8), want.view(np.uint8))
-
-
-def _assert_equal3(got, want, ctx):
-    assert np.array_equal(got["grid"], want["grid"]), f"{ctx}: cell keys differ"
-    for f in FLOATS:
-        a, b = got[f].view(np.uint32), want[f].view(np.uint32)
-        if not np.array_equal(a, b):
-            err = np.abs(got[f].astype(np.float64) - want[f].astype(np.float64)).max()
-            raise AssertionError(f"{ctx}: {f} not bit-exact ({int((a != b).sum())} words), max abs err {err:g}")
 
 
 @pytest.mark.gpu

@@ -13,11 +13,11 @@ import pytest
 
 import paths3d
 from tests import features3d as F
+from tests.bitcmp import assert_records_equal
 from tests.test_3d_paths_gpu import _assert_tolerance
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-FIELDS = ("grid", "predicted_position", "density", "velocity", "position")
 
 
 def _same_words(got, want, ctx):
@@ -34,8 +34,7 @@ def _same_words(got, want, ctx):
 
 def assert_same(got, want, got_st, want_st, ctx):
     """all five record fields, and the surface-tension forces where the pass is on"""
-    for name in FIELDS:
-        _same_words(got[name], want[name], f"{ctx}: {name}")
+    assert_records_equal(got, want, ctx, nan_any=True)
     if want_st is not None:
         _same_words(got_st, want_st, f"{ctx}: st")
 

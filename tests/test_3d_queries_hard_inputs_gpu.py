@@ -14,8 +14,8 @@ import numpy as np
 import pytest
 
 from tests import hard_states3d as H
-from tests.test_3d_features_hard_inputs_gpu import FIELDS, _same_words
-from tests.test_render3d_gpu import same
+from tests.bitcmp import POOL_TWELVE, assert_identical, assert_records_equal, assert_track_equal, special_bits
+from tests.test_3d_features_hard_inputs_gpu import _same_words
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -39,21 +39,14 @@ def download(sim, case, step, ieee=True):
         for fld in H.FLOAT_FIELDS:
             assert np.isfinite(got[fld]).all(), f"{ctx}: non-finite {fld}"
         return got
-    for fld in FIELDS:
-        if case.stays_finite:
-            assert got[fld].tobytes() == want[fld].tobytes(), f"{ctx}: {fld} is not the oracle's"
-        else:
-            _same_words(got[fld], want[fld], f"{ctx}: {fld}")
+    assert_records_equal(got, want, f"{ctx}: not the oracle's", nan_any=not case.stays_finite)
     return got
 
 
 def same_sample_words(got, want, what):
     """fs3_sample records word for word, a NaN of the checker met by any NaN"""
     assert got.shape == want.shape and got.dtype == want.dtype, what
-    for fld in ("density", "weight", "velocity", "gradient"):
-        _same_words(got[fld], want[fld], f"{what}: {fld}")
-    for fld in ("neighbours", "cell"):
-        assert np.array_equal(got[fld], want[fld]), f"{what}: {fld}"
+    assert_records_equal(got, want, what, nan_any=True)
 
 
 def stepped(sim, case, ieee=True):
@@ -74,7 +67,7 @@ def check_sampler(sim, case, p, ctx, ieee):
     sets = H.query_sets3(case.st, p)
     out = {name: sim.sample(pts) for name, pts in sets.items()}
     for name, pts in sets.items():
-        same(out[name], chk.sample(pts), f"{ctx}: {name}")
+        assert_identical(out[name], chk.sample(pts), f"{ctx}: {name}")
     chk.close()
     own = out["own"]
     assert np.array_equal(own["cell"], p["grid"]), f"{ctx}: cell == grid at a particle's own position"
@@ -141,11 +134,10 @@ def test_sampler_in_tolerance_mode(fs, orc, cid):
 
 # ---- d. tracking and channels on the tie cases ----------------------------------------------------------------------------------
 def channel_values(n, channels):
-    """channels 0 and 1: the bit patterns of test_tracking3d_gpu.special_bits (NaN payloads, infinities, -0.0, denormals);
+    """channels 0 and 1: the bit patterns of bitcmp.special_bits's twelve-value pool (NaN payloads, infinities, -0.0, denormals);
     channels 2 and 3: the finite values of hard_states2d.sample_channel_values, whose sums are compared in bytes"""
     from tests.hard_states2d import sample_channel_values
-    from tests.test_tracking3d_gpu import special_bits
-    rows = [special_bits(n, seed=50), special_bits(n, seed=51)] + list(sample_channel_values(n, 2))
+    rows = [special_bits(n, 50, POOL_TWELVE), special_bits(n, 51, POOL_TWELVE)] + list(sample_channel_values(n, 2))
     return np.ascontiguousarray(np.stack(rows[:channels]))
 
 
@@ -154,7 +146,6 @@ def channel_values(n, channels):
 def test_tracking_and_channels_on_tie_cases(fs, orc, cid, channels):
     from tests.sample_attr3d_ref import sample_attr
     from tests.test_sample_attr3d_gpu import raw_points
-    from tests.test_tracking3d_gpu import assert_track_equal
     from tests.track3d_ref import Track3Checker
     case = H.case_by_id(fs, orc, cid)
     sim = engine(fs, case, track=channels)
@@ -210,7 +201,7 @@ def test_renderer(fs, orc, cid):
     kinds = set()
     for ctx, cam, sp in H.surface_renders(case.st, p):
         want = chk.render(cam, sp)
-        same(render(cam, sp), want, f"{cid}: {ctx}")
+        assert_identical(render(cam, sp), want, f"{cid}: {ctx}")
         kinds.update(np.unique(want["hit"]).tolist())
     print(f"[queries3d] {cid}: hit kinds {sorted(kinds)}")
     if cid.startswith("radius/"):
@@ -251,12 +242,11 @@ def test_renderer_admits_a_candidate_exactly_on_the_radius(fs, orc):
 
 # ---- f. the extractor -----------------------------------------------------------------------------------------------------------
 def check_mesh(sim, chk, dims, wmin, wmax, iso, ctx):
-    from tests.test_mesh3d_gpu import same as same_rows
     want_v, want_t, want_c = chk.extract(dims, wmin, wmax, iso)
     got_v, got_t = sim.extract_surface(*dims, iso, wmin, wmax)
     assert (got_v.shape[0], got_t.shape[0]) == want_c, f"{ctx}: counts {(got_v.shape[0], got_t.shape[0])} != {want_c}"
-    same_rows(got_v, want_v, ctx + " vertices")
-    same_rows(got_t, want_t, ctx + " triangles")
+    assert_identical(got_v, want_v, ctx + " vertices")
+    assert_identical(got_t, want_t, ctx + " triangles")
     return want_c
 
 

@@ -15,39 +15,21 @@ from tests import diffuse_cases as DC
 from tests import features2d as F
 from tests import hard_states2d as H
 from tests import parity_states as PS
+from tests.bitcmp import assert_records_equal, assert_track_equal, bits, same_words
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-FLOAT_FIELDS = ("position", "predicted_position", "velocity", "density")
 U = 2.0 ** -24
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def same_words(got, want):
-    """bit for bit, a NaN of `want` met by any NaN"""
-    got, want = np.ascontiguousarray(got, dtype=f32), np.ascontiguousarray(want, dtype=f32)
-    return (bits(got) == bits(want)) | (np.isnan(got) & np.isnan(want))
-
-
 def assert_step_equal(sim, ref, ctx, state=True):
-    got = sim.particle_ids()
-    assert np.array_equal(got, ref.ids), f"{ctx}: ids differ in {int((got != ref.ids).sum())} slots"
-    for c in range(ref.channels):
-        ok = same_words(sim.attribute(c), ref.attr[c])
-        assert ok.all(), f"{ctx}: channel {c} differs in {int((~ok).sum())} slots"
+    assert_track_equal(sim, ref, ctx, nan_any=True)
     if ref.fb is not None:
         ok = same_words(sim.buoyancy_forces(), ref.fb)
         assert ok.all(), f"{ctx}: fb differs in {int((~ok).sum())} words"
     if not state:
         return
-    rec, want = sim.download_particles(), ref.particles_view()
-    assert np.array_equal(rec["grid"], want["grid"]), f"{ctx}: cell keys differ"
-    for f in FLOAT_FIELDS:
-        ok = same_words(rec[f], want[f])
-        assert ok.all(), f"{ctx}: {f} differs in {int((~ok).sum())} words"
+    assert_records_equal(sim.download_particles(), ref.particles_view(), ctx, nan_any=True)
     assert np.array_equal(sim.download_start_indices(), ref.start_indices_view()), f"{ctx}: start_indices"
 
 

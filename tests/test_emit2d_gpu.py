@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 from tests import emit2d_ref as ER
+from tests.bitcmp import assert_records_equal, assert_track_equal, bits, set_channels
+from tests.bitcmp import expect_invalid as invalid
 
 pytestmark = pytest.mark.gpu
 
@@ -20,26 +22,15 @@ SORTS = ER.SORTS
 NOZZLE = dict(origin=(0.13, -0.21), u=(0.045, 0.004), v=(-0.003, 0.026), velocity=(0.5, 2.0))
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def assert_state(sim, chk, ctx):
     got, want = sim.download_particles(), chk.rec
     assert got.shape[0] == want.shape[0] == sim.particle_count, f"{ctx}: count {got.shape[0]} / {want.shape[0]}"
-    assert np.array_equal(got["grid"], want["grid"]), f"{ctx}: cell keys differ"
-    for fld in FIELDS:
-        a, b = bits(got[fld]), bits(want[fld])
-        assert np.array_equal(a, b), f"{ctx}: {fld} not bit-exact ({int((a != b).sum())} words differ)"
+    assert_records_equal(got, want, ctx)
     assert np.array_equal(sim.download_start_indices(), chk.start), f"{ctx}: start_indices differ"
 
 
 def assert_track(sim, chk, ctx):
-    got = sim.particle_ids()
-    assert np.array_equal(got, chk.ids), f"{ctx}: ids differ in {int((got != chk.ids).sum())} slots"
-    for c in range(chk.channels):
-        a, b = bits(sim.attribute(c)), bits(chk.attr[c])
-        assert np.array_equal(a, b), f"{ctx}: channel {c} not bit-exact ({int((a != b).sum())} words differ)"
+    assert_track_equal(sim, chk, ctx)
     assert sim.next_id == chk.next_id, ctx
 
 
@@ -77,26 +68,6 @@ def remove_slots(sim, chk, slots):
     kill = np.zeros(chk.n, dtype=np.uint8)
     kill[list(slots)] = 1
     assert sim.remove(kill) == len(slots) == chk.remove(kill)
-
-
-def invalid(fs, call):
-    with pytest.raises(fs.FluidSimError) as e:
-        call()
-    assert e.value.status == fs._abi.FS_ERR_INVALID, e.value
-
-
-def special_bits(n, seed):
-    """NaN payloads, -0.0, denormals, infinities and ordinary values, mixed."""
-    pool = np.array([0x7FC00001, 0xFFC12345, 0x7F800001, 0x80000000, 0x00000001, 0x807FFFFF, 0x7F800000, 0x3F800000, 0xC2F6E979],
-                    dtype=np.uint32)
-    return pool[np.random.default_rng(seed).integers(0, pool.size, size=n)].view(np.float32)
-
-
-def set_channels(sim, chk, seed):
-    for c in range(chk.channels):
-        v = special_bits(chk.n, seed + c)
-        sim.set_attribute(c, v)
-        chk.attr[c] = v
 
 
 def push_field(st, seed):
@@ -667,8 +638,7 @@ def test_tolerance_mode_keeps_its_contract_across_count_changes(fs):
 
     def one_step(ctx):
         start = sim.download_particles()
-        for fld in ("grid",) + FIELDS:
-            assert np.array_equal(bits(start[fld]), bits(chk.rec[fld])), f"{ctx}: the change itself is a bit copy ({fld})"
+        assert_records_equal(start, chk.rec, f"{ctx}: the change itself is a bit copy")
         sim.tick(tick)
         want = chk.step(tick)
         got = sim.download_particles()
@@ -728,7 +698,6 @@ def test_a_handle_that_never_calls_them_stays_the_oracle(fs, orc, capacity, sort
         sim.tick(tick)
         ref.step(tick, stable_sort=sort == "counting")
         got, want = sim.download_particles(), ref.particles_view()
-        for fld in ("grid",) + FIELDS:
-            assert np.array_equal(bits(got[fld]), bits(want[fld])), f"step {s + 1}: {fld}"
+        assert_records_equal(got, want, f"step {s + 1}")
         assert np.array_equal(sim.download_start_indices(), ref.start_indices_view())
     sim.close(); ref.close()

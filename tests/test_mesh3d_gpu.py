@@ -11,39 +11,16 @@ import sys
 import numpy as np
 import pytest
 
+from tests.bitcmp import assert_identical
+from tests.query3d_helpers import checker_of, make_sim
+from tests.mesh3d_ref import Mesh3Checker
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f = np.float32
 LATTICES = [(2, 2, 2), (5, 4, 3), (2, 65, 2), (65, 2, 2), (17, 9, 6), (33, 33, 33), (49, 49, 49)]
 LARGE = [(33, 33, 33), (49, 49, 49)]
-
-
-def make_sim(fs, n, mode, seed=7):
-    from tests.track_ref import jitter_velocities
-    st, off, tick = fs.dam_break_3d(n)
-    sim = fs.FluidSimulation3D(st, device=0, initial_offset=off, math_mode=mode)
-    sim.upload_particles(jitter_velocities(sim.download_particles(), seed))
-    return sim, st, off, tick
-
-
-def checker_of(sim, st, off, mass):
-    """-> (extraction checker loaded with the handle's state, that state), the state asserted finite."""
-    from tests.mesh3d_ref import Mesh3Checker
-    p = sim.download_particles()
-    for fld in ("position", "predicted_position", "velocity", "density"):
-        assert np.isfinite(p[fld]).all(), f"non-finite {fld}"
-    chk = Mesh3Checker(st, off).load(p, mass)
-    assert chk.grid_dims == sim.grid_dims
-    return chk, p
-
-
-def same(got, want, what):
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.shape} != {want.shape}"
-    if got.tobytes() != want.tobytes():
-        bad = np.flatnonzero([a.tobytes() != b.tobytes() for a, b in zip(got, want)])
-        k = bad[0]
-        raise AssertionError(f"{what}: {bad.size} of {got.shape[0]} records differ; first {k}: {got[k]} != {want[k]}")
 
 
 def raw_extract(fs, sim, dims, wmin, wmax, iso, vert_cap, tri_cap, sentinel=0xA5):
@@ -79,7 +56,7 @@ def test_meshes_match_checker(fs, n, mode):
         while done < steps:
             sim.tick(tick)
             done += 1
-        chk, p = checker_of(sim, st, off, tick.mass)
+        chk, p = checker_of(Mesh3Checker, sim, st, off, tick.mass)
         iso = iso_of(p)
         for name, (wmin, wmax) in scene_views(st, p).items():
             for dims in LATTICES:
@@ -87,8 +64,8 @@ def test_meshes_match_checker(fs, n, mode):
                 want_v, want_t, want_c = chk.extract(dims, wmin, wmax, iso)
                 got_v, got_t = sim.extract_surface(*dims, iso, wmin, wmax)
                 assert (got_v.shape[0], got_t.shape[0]) == want_c, ctx
-                same(got_v, want_v, ctx + " vertices")
-                same(got_t, want_t, ctx + " triangles")
+                assert_identical(got_v, want_v, ctx + " vertices")
+                assert_identical(got_t, want_t, ctx + " triangles")
                 if name == "outside":
                     assert want_c == (0, 0), ctx
                 if dims in LARGE and name != "outside":
@@ -117,7 +94,7 @@ def test_dense_cluster(fs):
     p["predicted_position"] = p["position"]
     sim.upload_particles(p)
     sim.tick(tick)
-    chk, q = checker_of(sim, st, off, tick.mass)
+    chk, q = checker_of(Mesh3Checker, sim, st, off, tick.mass)
     assert sim.sample(q["predicted_position"])["neighbours"].max() > 700
     c = lo.astype(np.float64) + [h, 0.5 * h, 0.5 * h]
     # a quarter of the cluster's central density: the few lattice particles left around it stay far below it
@@ -127,8 +104,8 @@ def test_dense_cluster(fs):
     want_v, want_t, want_c = chk.extract(dims, wmin, wmax, iso)
     assert want_c[0] > 100 and want_c[1] > 100
     got_v, got_t = sim.extract_surface(*dims, iso, wmin, wmax)
-    same(got_v, want_v, "cluster vertices")
-    same(got_t, want_t, "cluster triangles")
+    assert_identical(got_v, want_v, "cluster vertices")
+    assert_identical(got_t, want_t, "cluster triangles")
     chk.close(); sim.close()
 
 

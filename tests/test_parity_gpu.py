@@ -1,7 +1,7 @@
 """GPU parity tests: the HIP engine, called through the C ABI, against the CPU oracle on
 identical inputs.  Bar: integer artefacts (cell keys, sort permutation, start_indices incl.
 stale entries) bit-exact; floats bit-exact where asserted so, otherwise within
-rtol 1e-5 / atol 1e-4*h — the engine is built with -ffp-contract=off and
+rtol 1e-5 / atol 1e-4*h — the engine is built without FMA contraction, with
 IEEE divide/sqrt, so in practice every test here asserts bit equality."""
 import os
 
@@ -9,23 +9,12 @@ import numpy as np
 import pytest
 
 from tests import parity_states as PS
+from tests.bitcmp import assert_records_equal as assert_particles_equal      # the name its importers know
 from tests.dense_scene import dense_scene
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 FLOAT_FIELDS = ("position", "predicted_position", "velocity", "density")
-
-
-def assert_particles_equal(got, want, ctx=""):
-    assert np.array_equal(got["grid"], want["grid"]), f"{ctx}: cell keys differ"
-    for f in FLOAT_FIELDS:
-        a, b = got[f].view(np.uint32), want[f].view(np.uint32)
-        if not np.array_equal(a, b):
-            bad = np.argwhere(a != b)
-            i = bad[0][0]
-            err = np.abs(got[f].astype(np.float64) - want[f].astype(np.float64)).max()
-            raise AssertionError(f"{ctx}: {f} not bit-exact at {bad.shape[0]} entries; first idx {i}: "
-                                 f"{got[f][i]} vs {want[f][i]}; max abs err {err:g}")
 
 
 def make_pair(fs, orc, n, size=None, off=None, seed=None, vel=1.0, jitter=0.025, quirks=True, **tick_over):
@@ -258,10 +247,7 @@ def test_16m_full_state_matches_oracle(fs, orc):
             sim.tick(tick)
             ref.step(tick)
             got, want = sim.download_particles(), ref.particles_view()
-            assert np.array_equal(got["grid"], want["grid"]), f"16M step {step}: cell keys differ"
-            for f in ("position", "predicted_position", "velocity", "density"):
-                a, b = got[f].view(np.uint32), want[f].view(np.uint32)
-                assert np.array_equal(a, b), f"16M step {step}: {f} not bit-exact ({int((a != b).sum())} words differ)"
+            assert_particles_equal(got, want, f"16M step {step}")
             assert np.array_equal(sim.download_start_indices(), ref.start_indices_view()), f"16M step {step}: start_indices"
             del got
     finally:
@@ -290,9 +276,7 @@ def test_shuffled_upload_on_a_large_grid_takes_the_wide_tile_path(fs, orc):
         for step in (1, 2):
             sim.tick(tick); ref.step(tick)
             got, want = sim.download_particles(), ref.particles_view()
-            assert np.array_equal(got["grid"], want["grid"]), f"step {step} after the shuffled upload: cell keys differ"
-            for f in ("position", "predicted_position", "velocity", "density"):
-                assert np.array_equal(got[f].view(np.uint32), want[f].view(np.uint32)), f"step {step}: {f} not bit-exact"
+            assert_particles_equal(got, want, f"step {step} after the shuffled upload")
             assert np.array_equal(sim.download_start_indices(), ref.start_indices_view())
             if step == 1:
                 assert sim.sort_plan()["wide_tiles"] >= n // 4096 // 2, sim.sort_plan()
@@ -685,8 +669,6 @@ def test_counting_sort_scan_tile_boundaries(fs, orc, cells_side):
     for s in range(2):
         sim.tick(tick); ref.step(tick, stable_sort=True)
         got, want = sim.download_particles(), ref.particles()
-        assert np.array_equal(got["grid"], want["grid"]), f"step {s}: keys"
-        for f in ("position", "predicted_position", "velocity", "density"):
-            assert np.array_equal(got[f].view(np.uint32), want[f].view(np.uint32)), f"step {s}: {f}"
+        assert_particles_equal(got, want, f"step {s}")
         assert np.array_equal(sim.download_start_indices(), ref.start_indices()), f"step {s}: start_indices"
     sim.close()

@@ -11,6 +11,10 @@ import sys
 import numpy as np
 import pytest
 
+from tests.bitcmp import assert_identical
+from tests.query3d_helpers import checker_of, make_sim
+from tests.render3d_ref import Render3Checker
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,33 +22,6 @@ f = np.float32
 SIZES = [(64, 64), (37, 23), (1, 1), (65, 1), (1, 65)]
 MAX_STEPS = 64
 BOTH = ("ortho_front", "persp_oblique", "persp_fan", "ortho_overhang")        # cameras whose larger images hold hits and misses
-
-
-def make_sim(fs, n, mode, seed=7):
-    from tests.track_ref import jitter_velocities
-    st, off, tick = fs.dam_break_3d(n)
-    sim = fs.FluidSimulation3D(st, device=0, initial_offset=off, math_mode=mode)
-    sim.upload_particles(jitter_velocities(sim.download_particles(), seed))
-    return sim, st, off, tick
-
-
-def checker_of(sim, st, off, mass):
-    """-> (rendering checker loaded with the handle's state, that state), the state asserted finite."""
-    from tests.render3d_ref import Render3Checker
-    p = sim.download_particles()
-    for fld in ("position", "predicted_position", "velocity", "density"):
-        assert np.isfinite(p[fld]).all(), f"non-finite {fld}"
-    chk = Render3Checker(st, off).load(p, mass)
-    assert chk.grid_dims == sim.grid_dims
-    return chk, p
-
-
-def same(got, want, what):
-    assert got.shape == want.shape and got.dtype == want.dtype, what
-    if got.tobytes() != want.tobytes():
-        bad = np.flatnonzero([a.tobytes() != b.tobytes() for a, b in zip(got.ravel(), want.ravel())])
-        k = bad[0]
-        raise AssertionError(f"{what}: {bad.size} of {got.size} records differ; first {k}: {got.ravel()[k]} != {want.ravel()[k]}")
 
 
 def check_views(render, chk, st, p, ctx, sizes=SIZES):
@@ -57,7 +34,7 @@ def check_views(render, chk, st, p, ctx, sizes=SIZES):
             for refine in (0, 8):
                 sp = params(iso, t_near, 0.5 * st.smoothing_radius, MAX_STEPS, refine)
                 want = chk.render(cam, sp)
-                same(render(cam, sp), want, f"{ctx}: {name} {w}x{h} refine {refine}")
+                assert_identical(render(cam, sp), want, f"{ctx}: {name} {w}x{h} refine {refine}")
                 kinds.update(np.unique(want["hit"]).tolist())
                 if w * h > 65 and name in BOTH:
                     assert (want["hit"] == 1).any() and (want["hit"] == 0).any(), f"{ctx}: {name} {w}x{h}: hits and misses"
@@ -83,7 +60,7 @@ def test_views_match_checker(fs, n, mode):
         while done < steps:
             sim.tick(tick)
             done += 1
-        chk, p = checker_of(sim, st, off, tick.mass)
+        chk, p = checker_of(Render3Checker, sim, st, off, tick.mass)
         check_views(product_render(fs, sim), chk, st, p, f"n {n} mode {mode} step {steps}")
         chk.close()
     sim.close()
@@ -98,11 +75,11 @@ def test_mass_other_than_one(fs, mode):
     heavy.mass = 1.5
     for _ in range(5):
         sim.tick(heavy)
-    chk, p = checker_of(sim, st, off, heavy.mass)
+    chk, p = checker_of(Render3Checker, sim, st, off, heavy.mass)
     check_views(product_render(fs, sim), chk, st, p, f"mass 1.5 mode {mode}", sizes=SIZES[1:])
     chk.close()
     sim.tick(tick)                                  # the mass of the LAST step is what counts
-    chk, p = checker_of(sim, st, off, tick.mass)
+    chk, p = checker_of(Render3Checker, sim, st, off, tick.mass)
     check_views(product_render(fs, sim), chk, st, p, f"mass back to 1 mode {mode}", sizes=SIZES[1:])
     chk.close(); sim.close()
 
@@ -122,7 +99,7 @@ def test_dense_cluster(fs):
     p["predicted_position"] = p["position"]
     sim.upload_particles(p)
     sim.tick(tick)
-    chk, q = checker_of(sim, st, off, tick.mass)
+    chk, q = checker_of(Render3Checker, sim, st, off, tick.mass)
     assert sim.sample(q["predicted_position"])["neighbours"].max() > 700
     render = product_render(fs, sim)
     c = lo.astype(np.float64) + [h, 0.5 * h, 0.5 * h]
@@ -134,11 +111,11 @@ def test_dense_cluster(fs):
             sp = params(iso, 0.0, 0.5 * h, MAX_STEPS, refine)
             want = chk.render(cam, sp)
             assert (want["hit"] == 1).any() and (want["hit"] == 0).any()
-            same(render(cam, sp), want, f"cluster ortho {w}x{hh} refine {refine}")
+            assert_identical(render(cam, sp), want, f"cluster ortho {w}x{hh} refine {refine}")
             cam = camera(c - [2 * h, 1 * h, 5 * h], [0.4, 0.2, 1], [1.2 * w / hh, 0, 0], [0, 1.2, 0], w, hh, False)
             want = chk.render(cam, sp)
             assert (want["hit"] == 1).any() and (want["hit"] == 0).any()
-            same(render(cam, sp), want, f"cluster perspective {w}x{hh} refine {refine}")
+            assert_identical(render(cam, sp), want, f"cluster perspective {w}x{hh} refine {refine}")
     chk.close(); sim.close()
 
 

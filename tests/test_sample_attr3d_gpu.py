@@ -63,7 +63,7 @@ def state(fs):
     sim.close()
 
 
-def set_channels(sim, attr):
+def track_and_upload(sim, attr):
     sim.track(attr.shape[0])
     for c in range(attr.shape[0]):
         sim.set_attribute(c, attr[c])
@@ -73,7 +73,7 @@ def set_channels(sim, attr):
 @pytest.mark.parametrize("channels", [1, 2, 3, 4])
 def test_points_match_the_restatement(fs, state, channels):
     sim = state["sim"]
-    set_channels(sim, state["attr"][:channels])
+    track_and_upload(sim, state["attr"][:channels])
     for name, pts in state["sets"].items():
         want_w, want_a = state["want"][name]
         w, a = raw_points(fs, sim, pts, channels)
@@ -94,7 +94,7 @@ def test_points_match_the_restatement(fs, state, channels):
 def test_the_two_identities_against_the_devices_own_sampler(fs, state):
     """Channel 0 = 1.0f, channels 1-3 = the stored velocity: weight_out == a_0 == fs3_sample.weight, a_1..a_3 == its velocity."""
     sim, p = state["sim"], state["p"]
-    set_channels(sim, np.stack([np.ones(N, dtype=np.float32)] + [np.ascontiguousarray(p["velocity"][:, k]) for k in range(3)]))
+    track_and_upload(sim, np.stack([np.ones(N, dtype=np.float32)] + [np.ascontiguousarray(p["velocity"][:, k]) for k in range(3)]))
     for name, pts in state["sets"].items():
         rec = sim.sample(pts)
         w, a = raw_points(fs, sim, pts, 4)
@@ -112,7 +112,7 @@ def test_the_two_identities_against_the_devices_own_sampler(fs, state):
 def test_grid_forms_match_the_point_form(fs, state, channels):
     from tests.sample3d_ref import grid_points
     sim, st = state["sim"], state["st"]
-    set_channels(sim, state["attr"][:channels])
+    track_and_upload(sim, state["attr"][:channels])
     sx = st.size.x
     views = [(9, 7, 5, (-sx / 2, -sx / 2, -sx / 2), (sx / 2, sx / 2, sx / 2)),       # ragged against the 8 x 8 x 4 workgroup tile
              (17, 13, 1, (-1.2, -1.2, 0.05), (1.2, 1.2, 0.05)),                       # a slice: world_min.z == world_max.z

@@ -11,6 +11,10 @@ import sys
 import numpy as np
 import pytest
 
+from tests.bitcmp import assert_identical
+from tests.query3d_helpers import checker_of, make_sim
+from tests.sample3d_ref import Sample3Checker
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,38 +22,12 @@ EPSILON_F = np.float32(1.19209290e-07)
 f = np.float32
 
 
-def make_sim(fs, n, mode, seed=7):
-    from tests.track_ref import jitter_velocities
-    st, off, tick = fs.dam_break_3d(n)
-    sim = fs.FluidSimulation3D(st, device=0, initial_offset=off, math_mode=mode)
-    sim.upload_particles(jitter_velocities(sim.download_particles(), seed))
-    return sim, st, off, tick
-
-
-def checker_of(sim, st, off, mass):
-    """-> (checker loaded with the handle's state, that state), the state asserted finite."""
-    from tests.sample3d_ref import Sample3Checker
-    p = sim.download_particles()
-    for fld in ("position", "predicted_position", "velocity", "density"):
-        assert np.isfinite(p[fld]).all(), f"non-finite {fld}"
-    chk = Sample3Checker(st, off).load(p, mass)
-    assert chk.grid_dims == sim.grid_dims
-    return chk, p
-
-
-def same(got, want, what):
-    if got.tobytes() != want.tobytes():
-        bad = np.flatnonzero([a.tobytes() != b.tobytes() for a, b in zip(got.ravel(), want.ravel())])
-        k = bad[0]
-        raise AssertionError(f"{what}: {bad.size} of {got.size} records differ; first {k}: {got.ravel()[k]} != {want.ravel()[k]}")
-
-
 def check_query_sets(fs, sim, st, off, tick, mode, ctx):
     from tests.sample3d_ref import boundary_points, uniform_points
-    chk, p = checker_of(sim, st, off, tick.mass)
+    chk, p = checker_of(Sample3Checker, sim, st, off, tick.mass)
     own = p["predicted_position"].copy()
     out = sim.sample(own)
-    same(out, chk.sample(own), f"{ctx}: own positions")
+    assert_identical(out, chk.sample(own), f"{ctx}: own positions")
     assert np.array_equal(out["cell"], p["grid"]), ctx
     assert (out["neighbours"] >= 1).all(), ctx
     if mode == fs.FS_MATH_IEEE:
@@ -57,15 +35,15 @@ def check_query_sets(fs, sim, st, off, tick, mode, ctx):
         assert np.array_equal(got.view(np.uint32), p["density"].view(np.uint32)), f"{ctx}: density identity"
     rng = np.random.default_rng(1)
     shuffled = own[rng.permutation(own.shape[0])]
-    same(sim.sample(shuffled), chk.sample(shuffled), f"{ctx}: shuffled")
+    assert_identical(sim.sample(shuffled), chk.sample(shuffled), f"{ctx}: shuffled")
     uni = uniform_points(st, 4000, seed=2)
     out = sim.sample(uni)
     assert (out["neighbours"] > 0).sum() > 100 and (out["neighbours"] == 0).sum() > 100, ctx
-    same(out, chk.sample(uni), f"{ctx}: uniform")
+    assert_identical(out, chk.sample(uni), f"{ctx}: uniform")
     bnd = boundary_points(st, p, 300, seed=3)
-    same(sim.sample(bnd), chk.sample(bnd), f"{ctx}: boundary")
+    assert_identical(sim.sample(bnd), chk.sample(bnd), f"{ctx}: boundary")
     for m in (1, 63, 64, 65, 257):
-        same(sim.sample(own[100:100 + m]), chk.sample(own[100:100 + m]), f"{ctx}: {m} queries")
+        assert_identical(sim.sample(own[100:100 + m]), chk.sample(own[100:100 + m]), f"{ctx}: {m} queries")
     chk.close()
 
 
@@ -121,15 +99,15 @@ def test_dense_cluster(fs):
     p["predicted_position"] = p["position"]
     sim.upload_particles(p)
     sim.tick(tick)
-    chk, q = checker_of(sim, st, off, tick.mass)
+    chk, q = checker_of(Sample3Checker, sim, st, off, tick.mass)
     own = q["predicted_position"].copy()
     out = sim.sample(own)
     assert out["neighbours"].max() > 700
-    same(out, chk.sample(own), "cluster: own positions")
+    assert_identical(out, chk.sample(own), "cluster: own positions")
     near = (lo + rng.uniform(-0.5, 1.5, size=(1000, 3)) * np.float32([2 * h, h, h])).astype(np.float32)
     out = sim.sample(near)
     assert out["neighbours"].max() > 700
-    same(out, chk.sample(near), "cluster: nearby points")
+    assert_identical(out, chk.sample(near), "cluster: nearby points")
     chk.close(); sim.close()
 
 
@@ -139,7 +117,7 @@ def test_grid_equals_points_equals_checker(fs):
     sim, st, off, tick = make_sim(fs, 16 ** 3, fs.FS_MATH_IEEE)
     for _ in range(8):
         sim.tick(tick)
-    chk, p = checker_of(sim, st, off, tick.mass)
+    chk, p = checker_of(Sample3Checker, sim, st, off, tick.mass)
     sx, sy, sz = st.size.x, st.size.y, st.size.z
     c = p["predicted_position"].mean(axis=0)
     dom = ((-sx / 2, -sy / 2, -sz / 2), (sx / 2, sy / 2, sz / 2))
@@ -149,14 +127,14 @@ def test_grid_equals_points_equals_checker(fs):
              (33, 17, 1, (-sx / 2, -sy / 2, c[2]), (sx / 2, sy / 2, c[2])),                                 # a slice through the fluid
              (1, 1, 40, (c[0], c[1], -sz / 2), (c[0], c[1], sz / 2))]                                       # a line
     assert sim.sample_grid(4, 3).shape == (1, 3, 4)
-    same(sim.sample_grid(16, 12, 9), sim.sample_grid(*views[0]), "default view = the whole domain")
+    assert_identical(sim.sample_grid(16, 12, 9), sim.sample_grid(*views[0]), "default view = the whole domain")
     hit = 0
     for w, h, d, wmin, wmax in views:
         got = sim.sample_grid(w, h, d, wmin, wmax)
         assert got.shape == (d, h, w)
         pts = grid_points(w, h, d, wmin, wmax)
-        same(got.ravel(), sim.sample(pts), f"grid {w}x{h}x{d} against the point form")
-        same(got, chk.sample_grid(w, h, d, wmin, wmax), f"grid {w}x{h}x{d} against the checker")
+        assert_identical(got.ravel(), sim.sample(pts), f"grid {w}x{h}x{d} against the point form")
+        assert_identical(got, chk.sample_grid(w, h, d, wmin, wmax), f"grid {w}x{h}x{d} against the checker")
         if d == 1:
             assert wmin[2] == wmax[2] and (pts[:, 2] == f(wmin[2])).all()
         hit += int((got["neighbours"] > 0).any())

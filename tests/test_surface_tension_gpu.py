@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.bitcmp import assert_records_equal, bits
 from tests.dense_scene import dense_scene
 
 pytestmark = pytest.mark.gpu
@@ -15,14 +16,10 @@ FLOAT_FIELDS = ("position", "predicted_position", "velocity", "density")
 
 
 def assert_state_equal(sim, chk, ctx, st=True):
-    got, want = sim.download_particles(), chk.particles_view()
-    assert np.array_equal(got["grid"], want["grid"]), f"{ctx}: cell keys differ"
-    for f in FLOAT_FIELDS:
-        a, b = got[f].view(np.uint32), want[f].view(np.uint32)
-        assert np.array_equal(a, b), f"{ctx}: {f} not bit-exact ({int((a != b).sum())} words differ)"
+    assert_records_equal(sim.download_particles(), chk.particles_view(), ctx)
     assert np.array_equal(sim.download_start_indices(), chk.start_indices_view()), f"{ctx}: start_indices"
     if st:
-        a, b = sim.surface_tension_forces().view(np.uint32), chk.st.view(np.uint32)
+        a, b = bits(sim.surface_tension_forces()), bits(chk.st)
         assert np.array_equal(a, b), f"{ctx}: st not bit-exact ({int((a != b).sum())} words differ)"
 
 

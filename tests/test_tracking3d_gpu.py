@@ -9,28 +9,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.bitcmp import POOL_TWELVE, assert_records_equal, assert_track_equal, bits, special_bits
+
 pytestmark = pytest.mark.gpu
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def assert_state_equal(sim, chk, ctx):
-    got, want = sim.download_particles(), chk.particles_view()
-    assert np.array_equal(got["grid"], want["grid"]), f"{ctx}: cell keys differ"
-    for fld in ("position", "predicted_position", "velocity", "density"):
-        a, b = bits(got[fld]), bits(want[fld])
-        assert np.array_equal(a, b), f"{ctx}: {fld} not bit-exact ({int((a != b).sum())} words differ)"
-
-
-def assert_track_equal(sim, chk, ctx):
-    got = sim.particle_ids()
-    assert np.array_equal(got, chk.ids), f"{ctx}: ids differ in {int((got != chk.ids).sum())} slots"
-    assert sim.track_channels == chk.channels
-    for c in range(chk.channels):
-        a, b = bits(sim.attribute(c)), bits(chk.attr[c])
-        assert np.array_equal(a, b), f"{ctx}: channel {c} not bit-exact ({int((a != b).sum())} words differ)"
+    assert_records_equal(sim.download_particles(), chk.particles_view(), ctx)
 
 
 def assert_not_vacuous(chk, least=0.5):
@@ -49,13 +34,6 @@ def make_pair(fs, side, seed=7, channels=0, track=True, mode=None):
     chk.set_particles(p)
     sim.upload_particles(p)
     return sim, chk, tick
-
-
-def special_bits(n, seed=99):
-    """NaN payloads (quiet and signalling), -0.0, denormals, infinities and ordinary values, mixed."""
-    pool = np.array([0x7FC00001, 0xFFC12345, 0x7F800001, 0xFF8ABCDE, 0x80000000, 0x00000001, 0x807FFFFF, 0x7F800000,
-                     0xFF800000, 0x3F800000, 0x00000000, 0xC2F6E979], dtype=np.uint32)
-    return pool[np.random.default_rng(seed).integers(0, pool.size, size=n)].view(np.float32)
 
 
 # ---- 1. ids bit-exact against the checker, every step; the state stays the oracle's ------------------------------------
@@ -97,7 +75,7 @@ def test_every_channel_count_one_step(fs, channels):
     n = 17 ** 3
     sim, chk, tick = make_pair(fs, 17, seed=20 + channels, channels=channels)
     for c in range(channels):
-        v = special_bits(n, seed=50 + c)
+        v = special_bits(n, 50 + c, POOL_TWELVE)
         if c == 1:                                   # arbitrary words: whatever float they encode
             v = np.random.default_rng(c).integers(0, 1 << 32, size=n, dtype=np.uint64).astype(np.uint32).view(np.float32)
         sim.set_attribute(c, v)
@@ -154,7 +132,7 @@ def test_tracking_changes_no_bit_with_a_collider_and_surface_tension(fs):
         if tracked:
             sim.track(4)
             for c in range(4):
-                sim.set_attribute(c, special_bits(17 ** 3, seed=c))
+                sim.set_attribute(c, special_bits(17 ** 3, c, POOL_TWELVE))
         sims.append(sim)
     a, b = sims
     buf = np.zeros(17 ** 3, dtype=np.uint32)
@@ -258,8 +236,8 @@ def test_timed_steps_run_ahead(fs):
 
 def test_profiled_steps_carry_too(fs):
     sim, chk, tick = make_pair(fs, 17, channels=1)
-    sim.set_attribute(0, special_bits(17 ** 3))
-    chk.attr[0] = special_bits(17 ** 3)
+    sim.set_attribute(0, special_bits(17 ** 3, 99, POOL_TWELVE))
+    chk.attr[0] = special_bits(17 ** 3, 99, POOL_TWELVE)
     sim.profile(True)
     for _ in range(3):
         sim.tick(tick)
@@ -309,7 +287,7 @@ def test_download_by_id(fs):
 def test_one_tolerance_step_moves_the_ids_the_same_way(fs):
     """The keys come from the uploaded positions and velocities alone and stay bit-exact in FS_MATH_TOLERANCE."""
     sim, chk, tick = make_pair(fs, 17, channels=2, mode=fs.FS_MATH_TOLERANCE)
-    v = special_bits(17 ** 3)
+    v = special_bits(17 ** 3, 99, POOL_TWELVE)
     sim.set_attribute(0, v)
     chk.attr[0] = v
     sim.tick(tick)

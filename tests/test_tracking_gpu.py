@@ -9,30 +9,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.bitcmp import POOL_TWELVE, assert_records_equal, assert_track_equal, bits, special_bits
+
 pytestmark = pytest.mark.gpu
-FLOAT_FIELDS = ("position", "predicted_position", "velocity", "density")
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def assert_state_equal(sim, chk, ctx):
-    got, want = sim.download_particles(), chk.particles_view()
-    assert np.array_equal(got["grid"], want["grid"]), f"{ctx}: cell keys differ"
-    for f in FLOAT_FIELDS:
-        a, b = got[f].view(np.uint32), want[f].view(np.uint32)
-        assert np.array_equal(a, b), f"{ctx}: {f} not bit-exact ({int((a != b).sum())} words differ)"
+    assert_records_equal(sim.download_particles(), chk.particles_view(), ctx)
     assert np.array_equal(sim.download_start_indices(), chk.start_indices_view()), f"{ctx}: start_indices"
-
-
-def assert_track_equal(sim, chk, ctx):
-    got = sim.particle_ids()
-    assert np.array_equal(got, chk.ids), f"{ctx}: ids differ in {int((got != chk.ids).sum())} slots"
-    assert sim.track_channels == chk.channels
-    for c in range(chk.channels):
-        a, b = bits(sim.attribute(c)), bits(chk.attr[c])
-        assert np.array_equal(a, b), f"{ctx}: channel {c} not bit-exact ({int((a != b).sum())} words differ)"
 
 
 def assert_not_vacuous(chk):
@@ -50,13 +34,6 @@ def make_pair(fs, n, seed=7, quirks=True, sort_mode=None, channels=0, track=True
     chk.set_particles(p)
     sim.upload_particles(p)
     return sim, chk, tick
-
-
-def special_bits(n):
-    """NaN payloads (quiet and signalling), -0.0, denormals, infinities and ordinary values, mixed."""
-    pool = np.array([0x7FC00001, 0xFFC12345, 0x7F800001, 0xFF8ABCDE, 0x80000000, 0x00000001, 0x807FFFFF, 0x7F800000,
-                     0xFF800000, 0x3F800000, 0x00000000, 0xC2F6E979], dtype=np.uint32)
-    return pool[np.random.default_rng(99).integers(0, pool.size, size=n)].view(np.float32)
 
 
 # ---- 1. ids bit-exact against the checker, every step; the state stays the oracle's ------------------------------------
@@ -82,7 +59,7 @@ def test_channels_ride_along(fs, counting):
     n = 100_000
     sim, chk, tick = make_pair(fs, n, channels=4, sort_mode=fs.FS_SORT_COUNTING if counting else fs.FS_SORT_BITONIC)
     x0 = np.ascontiguousarray(chk.particles()["position"][:, 0])
-    vals = [np.arange(n, dtype=np.float32), x0, special_bits(n)]
+    vals = [np.arange(n, dtype=np.float32), x0, special_bits(n, 99, POOL_TWELVE)]
     for c, v in enumerate(vals):
         sim.set_attribute(c, v)
         chk.attr[c] = v
@@ -107,7 +84,7 @@ def test_fewer_channels_ride_along(fs, channels):
     n = 100_000
     sim, chk, tick = make_pair(fs, n, channels=channels)
     if channels:
-        v = special_bits(n)
+        v = special_bits(n, 99, POOL_TWELVE)
         sim.set_attribute(0, v)
         chk.attr[0] = v
     for s in range(8):
@@ -282,7 +259,7 @@ def test_one_step_of_the_other_step_variants(fs, variant):
     sim, chk, tick = make_pair(fs, n, channels=2, **kw)
     if variant == "surface_tension":
         tick.surface_tension_coefficient = 35.0
-    v = special_bits(n)
+    v = special_bits(n, 99, POOL_TWELVE)
     sim.set_attribute(0, v)
     chk.attr[0] = v
     sim.tick(tick)

@@ -15,7 +15,8 @@ import pytest
 
 from tests import hard_states2d as H
 from tests import parity_states as PS
-from tests.test_tracking_gpu import (assert_not_vacuous, assert_state_equal, assert_track_equal, bits, make_pair, special_bits)
+from tests.bitcmp import POOL_TWELVE, assert_track_equal, bits, special_bits
+from tests.test_tracking_gpu import assert_not_vacuous, assert_state_equal, make_pair
 
 pytestmark = pytest.mark.gpu
 CHANNELS = 4
@@ -35,10 +36,10 @@ class Ref:
 def channel_values(start):
     """arange(n), the start x, NaN payloads / -0.0 / denormals / infinities, and one channel left at the enable's +0.0"""
     n = start.shape[0]
-    return [np.arange(n, dtype=np.float32), np.ascontiguousarray(start["position"][:, 0]), special_bits(n)]
+    return [np.arange(n, dtype=np.float32), np.ascontiguousarray(start["position"][:, 0]), special_bits(n, 99, POOL_TWELVE)]
 
 
-def set_channels(sim, start):
+def upload_channel_values(sim, start):
     vals = channel_values(start)
     for c, v in enumerate(vals):
         sim.set_attribute(c, v)
@@ -66,7 +67,7 @@ def test_tracking_at_the_hard_inputs(fs, orc, cid):
     print(case.describe())
     sim = engine(fs, case)
     n = case.n
-    ids, attr = np.arange(n, dtype=np.uint32), set_channels(sim, case.start)
+    ids, attr = np.arange(n, dtype=np.uint32), upload_channel_values(sim, case.start)
     assert np.array_equal(sim.particle_ids(), ids)
     for s, step in enumerate(ref):
         sim.tick(case.tick)
@@ -124,7 +125,7 @@ def test_every_sort_launch_sequence_leaves_the_same_source_slots(fs, orc, monkey
         for k in env:
             monkeypatch.delenv(k)
         sim.upload_particles(p)
-        set_channels(sim, p)
+        upload_channel_values(sim, p)
         for s, want in enumerate(refs):
             if s == SEQ_SHUFFLE_BEFORE:
                 sim.upload_particles(sim.download_particles()[shuffle])
@@ -149,7 +150,7 @@ def test_capacity_above_n(fs, counting):
     sim, chk, tick = make_pair(fs, n, channels=CHANNELS, sort_mode=fs.FS_SORT_COUNTING if counting else fs.FS_SORT_BITONIC, capacity=cap)
     assert sim.particle_count == n
     assert sim.attribute_device_ptr(1) - sim.attribute_device_ptr(0) >= 4 * cap
-    chk.attr[:] = set_channels(sim, chk.particles())
+    chk.attr[:] = upload_channel_values(sim, chk.particles())
     for s in range(4):
         sim.tick(tick)
         chk.step(tick, stable_sort=counting)
@@ -171,7 +172,7 @@ def test_several_steps_of_the_other_step_variants(fs, variant):
     sim, chk, tick = make_pair(fs, n, channels=CHANNELS, **kw)
     if variant == "surface_tension":
         tick.surface_tension_coefficient = 35.0
-    chk.attr[:] = set_channels(sim, chk.particles())
+    chk.attr[:] = upload_channel_values(sim, chk.particles())
     moved = []
     for s in range(6):
         chk.set_particles(sim.download_particles())

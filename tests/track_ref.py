@@ -7,8 +7,6 @@ the permutation the sort is about to apply to the records:
   * stable sort:    np.argsort(keys, kind="stable"), the order of std::stable_sort (orc_sort_stable).
 Then ids = ids[perm], attr = attr[:, perm]: the statement of include/fluidsim.h.  `verify=True` also checks, at every step,
 that before[perm] IS the oracle's sorted array byte for byte, i.e. that the derived permutation is the one the oracle applied."""
-import ctypes as C
-
 import numpy as np
 
 from oracle import oracle as O
@@ -31,8 +29,6 @@ class TrackChecker:
         self.n = self.sim.n
         self.verify = verify
         self.last_perm = None
-        self.sim.L.orc_sort_stable.argtypes = [C.c_void_p]      # exported by the library; oracle.py gives it no prototype
-        self.sim.L.orc_sort_stable.restype = None
         self.reset(channels)
 
     def reset(self, channels=None):
