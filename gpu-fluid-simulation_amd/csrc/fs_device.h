@@ -238,6 +238,33 @@ __device__ __forceinline__ bool kin_safe(float2 pred, float2 vel) {
 #define FS_PRESSURE_HI 0x1p39f
 #define FS_HSPIKY_HI 0x1p19f
 
+// ---- wave priority for a kernel's load phase -----------------------------------------------------------------------
+// A SIMD's VALU issue is arbitrated between its resident waves by priority, then age: a freshly dispatched wave is the youngest
+// of up to eight and issues its prologue — address arithmetic in front of and between dependent global round trips — in the
+// slots the older, arithmetic-bound waves leave over.  A kernel family may raise a wave for that phase (wave_prio_raise in the
+// __global__ body) and drops it again in front of its sweep / network (wave_prio_lower).  LEVEL is the family's macro below:
+// 0 emits nothing at either end, so a build with all of them at 0 is the control, instruction for instruction.
+// s_setprio is a scalar instruction and ignores EXEC: every call sits in straight-line code that whole waves reach (a lower in
+// both arms of a block-uniform branch is harmless: 0 twice); a wave that returns needs no lowering.
+// Per family, the level that measured best on MI355X, or 0 (profiles/prio_bench_parent_vs_branch.txt, prio_rejected.md).
+#ifndef FS_PRIO_DENSITY
+#define FS_PRIO_DENSITY 1       // k_density
+#endif
+#ifndef FS_PRIO_FORCE
+#define FS_PRIO_FORCE 1         // k_force (the lean kernel only)
+#endif
+#ifndef FS_PRIO_SORT
+#define FS_PRIO_SORT 1          // k_bitonic_local32, the tile tails (k_bitonic_local<false>), k_bitonic_stage12
+#endif
+template <int P> __device__ __forceinline__ void wave_prio() { __builtin_amdgcn_s_setprio(P); }     // (the level is an immediate)
+template <int LEVEL> __device__ __forceinline__ void wave_prio_raise() {
+    static_assert(LEVEL >= 0 && LEVEL <= 3, "s_setprio takes 0..3");
+    if constexpr (LEVEL > 0) wave_prio<LEVEL>();
+}
+template <int LEVEL> __device__ __forceinline__ void wave_prio_lower() {
+    if constexpr (LEVEL > 0) wave_prio<0>();
+}
+
 // ---- XCD-aware block index ---------------------------------------------------------------------
 // Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share one; MI355X guide, "Workgroup
 // dispatch").  A strip of particles and the strips one grid row above/below it (~64 blocks away)

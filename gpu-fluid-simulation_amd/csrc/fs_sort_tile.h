@@ -163,7 +163,9 @@ __device__ __forceinline__ void lt_tail_regs(u64* s, u64 (&x)[1 << GB], uint32_t
 }
 
 // tail of a stage >= 12: plain steps on bits 11..0 of one tile; the top layout IS the coalesced global layout
-template <int GB>
+// PRIO: the priority level the calling kernel raised its waves to for these loads (fs_device.h wave_prio_raise), dropped
+// again in front of the network steps; 0 (the stand-by kernel): nothing.
+template <int GB, int PRIO = 0>
 __device__ __forceinline__ void lt_tail(const u64* __restrict__ pairs, uint32_t n, uint32_t base, u64* s, u64 (&x)[1 << GB],
                                         uint32_t t) {
 #pragma unroll
@@ -171,6 +173,7 @@ __device__ __forceinline__ void lt_tail(const u64* __restrict__ pairs, uint32_t 
         const uint32_t j = ((uint32_t)r << LT<GB>::TOPB) | t;
         x[r] = (base + j < n) ? pairs[base + j] : ~0ull;
     }
+    wave_prio_lower<PRIO>();
     lt_tail_regs<GB>(s, x, t, t);
 }
 

@@ -70,6 +70,7 @@ __device__ __forceinline__ void density_block(const StepParams& P, uint32_t blk,
         stage_rows_load(S, blo, bhi, [&](uint32_t k) { return pred[k]; });
         stage_rows_store(S, blo, bhi, [&](int r, uint32_t j, float2 q) { s_pred[r][j] = q; });
         __syncthreads();
+        wave_prio_lower<FS_PRIO_DENSITY>();     // the load phase is over (k_density raised it; k_density_edge never did)
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             // four candidates per trip (independent LDS reads and kernel evaluations give the wave
@@ -97,6 +98,7 @@ __device__ __forceinline__ void density_block(const StepParams& P, uint32_t blk,
             for (; k < hi; ++k) rho += density_term<MASS1>(P, h2, me, sp[k]);
         }
     } else {
+        wave_prio_lower<FS_PRIO_DENSITY>();
 #pragma unroll
         for (int r = 0; r < 3; ++r)
             for (uint32_t k = R.lo[r]; k < R.hi[r]; ++k) {
@@ -137,6 +139,7 @@ __global__ __launch_bounds__(FS_BLOCK) void k_density(FS_DENSITY_ARGS) {
     const uint32_t n = P.n_live ? *P.n_live : P.n;
     uint32_t blk;
     if (!xcd_block(P, (n + FS_BLOCK - 1) / FS_BLOCK, &blk)) return;   // uniform: no live particle in this block
+    wave_prio_raise<FS_PRIO_DENSITY>();          // for the prologue's round trips; density_block lowers it in front of its sweep
     density_block<TOL, MASS1>(P, blk, n, pred, cs, start_ref, pairs, safe, rho_out, rho2_out, force_defer, force_work, force_count, s_pred, s_red);
 }
 // Edge-first slab step, column-major ids (fs_device.h EdgeBlocks): the density of the columns the edge columns' force launch

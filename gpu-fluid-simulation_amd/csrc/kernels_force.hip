@@ -208,6 +208,7 @@ __device__ __forceinline__ void force_block(const StepParams& P, uint32_t blk, u
                 for (uint32_t j = tid; j < bhi[r] - blo[r]; j += FS_BLOCK) s_pred[r][j] = pred[blo[r] + j];
         }
         __syncthreads();
+        if constexpr (EARLY) wave_prio_lower<FS_PRIO_FORCE>();      // k_force raised it for the prologue's round trips
         const bool long_row = R.hi[0] - R.lo[0] > 32u || R.hi[1] - R.lo[1] > 32u || R.hi[2] - R.lo[2] > 32u;
         if (!__any(long_row))
             defer = force_sweep_masks<MODE, GENERAL>(P, R, blo, ii, me, mv, pressure, vel_s, rho2, &s_pred[0][0], me_ok, A);
@@ -217,6 +218,8 @@ __device__ __forceinline__ void force_block(const StepParams& P, uint32_t blk, u
             defer = true;
     } else if (GENERAL) {
         force_sweep_chunks<false, MODE>(P, R, blo, ii, me, mv, pressure, pred, vel_s, rho2, &s_pred[0][0], me_ok, A);
+    } else if constexpr (EARLY) {
+        wave_prio_lower<FS_PRIO_FORCE>();            // not staged: the lean wave defers below
     }
     defer = __any(defer);
     if (!GENERAL && defer) {                         // wave-uniform: hand this wave over (late list), write nothing
@@ -263,6 +266,7 @@ __global__ __launch_bounds__(FS_BLOCK) __attribute__((amdgpu_waves_per_eu(FS_FOR
     uint32_t blk;
     if (!xcd_block(P, (n + FS_BLOCK - 1) / FS_BLOCK, &blk)) return;   // uniform: no live particle in this block
     if (!block_may_advance(P, pairs, blk, n)) return;                 // uniform: none of its columns belongs to this launch
+    wave_prio_raise<FS_PRIO_FORCE>();            // for the prologue's round trips; force_block lowers it in front of the sweep
     force_block<MODE, AOS, false, ST, true>(P, blk, n, defer_bits[force_defer_word(blk, FS_LIST_PRE)], pos_s, vel_s, pred, rho2, cs, start_ref, pairs, tex,
                                       pos_out, vel_out, aos_out, rho_arr, defer_bits, worklist, work_count, st_in, s_pred, s_red);
 }

@@ -39,6 +39,7 @@ __global__ __launch_bounds__(LT<GB>::THREADS) void k_bitonic_local(u64* __restri
     const uint32_t base = blockIdx.x * SORT_T;
     const uint32_t t = threadIdx.x;
     if (!INIT) {
+        wave_prio_raise<FS_PRIO_SORT>();               // the tails: for the tile's loads (a wave that returns needs no lowering)
         if (gate_closed(gate, gate_lo, gate_hi)) return;   // uniform: this launch belongs to the other late-stage plan
         if (dirty[blockIdx.x] == 0) return;            // uniform: whole tile provably unchanged
     }
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(LT<GB>::THREADS) void k_bitonic_local(u64* __restri
         if (num_stages > 10) lt_stage<GB, 10>(s, x, t);
         if (num_stages > 11) lt_stage<GB, 11>(s, x, t);
     } else {
-        lt_tail<GB>(pairs, n, base, s, x, t);
+        lt_tail<GB, FS_PRIO_SORT>(pairs, n, base, s, x, t);      // (lowers the priority behind its loads)
     }
     lt_store<GB>(pairs, s, x, base, t, n);
     if (t == 0) dirty[blockIdx.x] = 0;                 // sorted again
@@ -132,6 +133,7 @@ __global__ __launch_bounds__(LT<GB>::THREADS) FS_SORT32_ATTR void k_bitonic_loca
     __shared__ uint32_t s_mm[2 * (LT<GB>::THREADS / 64)];
     const uint32_t base = blockIdx.x * SORT_T;
     const uint32_t t = threadIdx.x;
+    wave_prio_raise<FS_PRIO_SORT>();                                     // for the position / velocity loads and the key arithmetic
     if (KEYGEN != 0 && blockIdx.x == 0 && t == 0) *gap_counter = 0;      // consumed by k_reorder later in the stream
     uint32_t key[E];
     uint32_t kmin = 0xFFFFFFFFu, kmax = 0u;
@@ -148,6 +150,7 @@ __global__ __launch_bounds__(LT<GB>::THREADS) FS_SORT32_ATTR void k_bitonic_loca
         }
         key[r] = k;
     }
+    wave_prio_lower<FS_PRIO_SORT>();                                     // the loads are out and the keys formed
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const uint32_t a = __shfl_xor(kmin, o), b = __shfl_xor(kmax, o);
@@ -224,6 +227,7 @@ __global__ __launch_bounds__(LT<GB>::THREADS) void k_bitonic_stage12(u64* __rest
     __shared__ u64 s[LT<GB>::LDS];
     const uint32_t t = threadIdx.x;
     const uint32_t base_a = blockIdx.x * (2u * SORT_T), base_b = base_a + SORT_T;
+    wave_prio_raise<FS_PRIO_SORT>();                   // for the two tiles' loads
     if (base_b >= n) return;                           // B holds sentinels only: nothing can swap
     {
         const uint32_t last_a = (uint32_t)(pairs[base_b - 1u] >> 32), first_b = (uint32_t)(pairs[base_b] >> 32);
@@ -237,6 +241,7 @@ __global__ __launch_bounds__(LT<GB>::THREADS) void k_bitonic_stage12(u64* __rest
         const uint32_t pb = base_b + (SORT_T - 1u - j);
         xb[r] = pb < n ? pairs[pb] : ~0ull;
     }
+    wave_prio_lower<FS_PRIO_SORT>();
 #pragma unroll
     for (int r = 0; r < E; ++r) lt_cx(xa[r], xb[r]);               // A[j] vs B[4095 - j]: the stage's mirror step
     lt_tail_regs<GB>(s, xa, t, t);
