@@ -1,5 +1,6 @@
-// fs_neighbours.h — the neighbour walk of the 2D passes: the row ranges of the 3x3 sweep in the dense cell-start table, the
-// stale-start quirk, the block-wide candidate tiles.  RowRanges / block_tile_bounds (shared with the 3D kernels): fs_device.h.
+// fs_neighbours.h — the neighbour walk of the 2D passes: the row ranges of the 3x3 sweep in the dense cell-start table, the stale-start
+// quirk, the block-wide candidate tiles and their staging (the force pass stages for itself: kernels_force.hip), and the driver of the
+// passes that add per-candidate terms: walk_lane, walk_bounds, walk_rows.  RowRanges / block_tile_bounds (shared with 3D): fs_device.h.
 #pragma once
 #include "fs_device.h"
 
@@ -136,6 +137,84 @@ __device__ __forceinline__ void load_block_bounds(const StepParams& P, uint32_t 
 __device__ __forceinline__ bool recorded_tile_bounds(const StepParams& P, uint32_t blk, uint32_t* blo, uint32_t* bhi, uint32_t tile) {
     load_block_bounds(P, blk, blo, bhi);
     return bhi[0] - blo[0] <= tile && bhi[1] - blo[1] <= tile && bhi[2] - blo[2] <= tile;
+}
+
+// ------------------------------------------------------------ the driver
+// A pass that adds per-candidate terms over the rows the density pass visits (k_density / k_density_edge and k_surface_tension,
+// kernels_density.hip; k_diffuse, kernels_diffuse.hip) is its terms object plus walk_lane, walk_bounds and walk_rows, once each.
+// The 3D counterpart is fs_sweep3.h (sweep3_lane / sweep3_planes).
+// The lane of block `blk` of n particles: sorted slot i, its position, its cell — (u, v) of the cell-id layout: (x, y) unless the
+// handle is a transposed slab rank — and its three row ranges.  A dead lane (i >= n) shadows particle ii = n - 1: it loads what a
+// live lane loads, walks nothing (`live` goes into lane_row_ranges), reaches every barrier and stores nothing: the pass returns on
+// !live after walk_rows.  walk_lane is its two halves in a row; a pass with more to load of particle ii (k_diffuse: its channel
+// values) calls the halves itself and loads in between, in flight with `me` and ahead of the round trips to the cell table.
+struct WalkLane { uint32_t i, ii; bool live; float2 me; uint32_t lo_fix, cx, cy; int32_t cg; RowRanges R; };
+__device__ __forceinline__ WalkLane walk_lane_particle(uint32_t blk, uint32_t n, const float2* __restrict__ pred) {
+    WalkLane L;
+    L.i = blk * FS_BLOCK + threadIdx.x; L.live = L.i < n; L.ii = L.live ? L.i : n - 1;
+    L.me = pred[L.ii];              // issued first: the quirk's two dependent scalar loads run beside it
+    return L;
+}
+__device__ __forceinline__ void walk_lane_rows(const StepParams& P, const uint32_t* __restrict__ cs, const uint32_t* __restrict__ start_ref,
+                                               const u64* __restrict__ pairs, WalkLane& L) {
+    L.lo_fix = quirk_lo_fix(P, pairs, cs, start_ref);
+    uv_local(P, L.me, &L.cx, &L.cy, &L.cg);
+    L.R = lane_row_ranges(P, cs, L.lo_fix, L.cx, L.cy, L.live);
+}
+__device__ __forceinline__ WalkLane walk_lane(const StepParams& P, uint32_t blk, uint32_t n, const float2* __restrict__ pred,
+                                              const uint32_t* __restrict__ cs, const uint32_t* __restrict__ start_ref,
+                                              const u64* __restrict__ pairs) {
+    WalkLane L = walk_lane_particle(blk, n, pred);
+    walk_lane_rows(P, cs, start_ref, pairs, L);
+    return L;
+}
+
+// The block-wide ranges and whether all three fit a tile of `tile` entries.  RECORDED: the record of this step's density pass where there
+// is one (it reduced the same ranges over the same 256 particles), else reduced over s_red[24], as the density pass itself always does.
+template <bool RECORDED> __device__ __forceinline__ bool walk_bounds(const StepParams& P, uint32_t blk, const RowRanges& R, uint32_t* s_red,
+                                                                     uint32_t* blo, uint32_t* bhi, uint32_t tile) {
+    if (RECORDED && P.block_bounds) return recorded_tile_bounds(P, blk, blo, bhi, tile);
+    return block_tile_bounds(R, s_red, blo, bhi, tile);
+}
+
+// The walk: candidates row by row, index ascending.  `fit`: the three block-wide rows go to LDS in two halves (above) and, behind
+// the barrier, every lane's terms come from there; else every lane sweeps its own ranges in global memory.  Terms has
+//   fetch(k)        what is staged of candidate k, read from global memory
+//   put(r, j, c)    write it to slot j of row r in LDS
+//   row(r, k, hi)   the terms of the staged candidates in slots [k, hi) of row r: the pass's own unrolling, adds in index order
+//   one(k)          the terms of candidate k from global memory
+// PRIO: the level the kernel raised its waves to for the load phase, or 0 (fs_device.h); lowered where that phase ends.
+template <int PRIO, class Terms>
+__device__ __forceinline__ void walk_rows(const RowRanges& R, const uint32_t* blo, const uint32_t* bhi, bool fit, Terms& T) {
+    if (fit) {
+        StagedRows<decltype(T.fetch(0u))> S;
+        stage_rows_load(S, blo, bhi, [&](uint32_t k) { return T.fetch(k); });
+        stage_rows_store(S, blo, bhi, [&](int r, uint32_t j, const decltype(T.fetch(0u))& c) { T.put(r, j, c); });
+        __syncthreads();
+        wave_prio_lower<PRIO>();
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const bool any = R.lo[r] < R.hi[r];
+            const uint32_t hi = any ? R.hi[r] - blo[r] : 0u, k = any ? R.lo[r] - blo[r] : 0u;
+            T.row(r, k, hi);
+        }
+    } else {
+        wave_prio_lower<PRIO>();
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            for (uint32_t k = R.lo[r]; k < R.hi[r]; ++k) T.one(k);
+    }
+}
+
+// The neighbour weight w_j = m / rho_j of the passes behind the density pass, in two halves, so that the staging loads every
+// candidate's operand before it forms the first weight: the one word read per candidate, and the weight from it.
+template <bool MASS1> __device__ __forceinline__ float walk_weight_operand(const float2* __restrict__ rho2, const float* __restrict__ rho_arr, uint32_t j) {
+    if (MASS1) return rho2[j].y;                    // +-RN(1/rho_j): the sign is the density pass's safe bit
+    return rho_arr ? rho_arr[j] : rho2[j].x;        // rho_j.  rho_arr: tolerance mode (rho2 = {pressure, 1/rho})
+}
+template <bool MASS1> __device__ __forceinline__ float walk_weight_of(const StepParams& P, float d) {
+    if (MASS1) return fabsf(d);                     // RN(1/rho_j) == RN(1.0f / rho_j)
+    return __fdiv_rn(P.mass, d);
 }
 
 struct AosParticle { float2 position, predicted, velocity; float density; uint32_t grid; };   // ParticleInstance, 32 B

@@ -9,9 +9,10 @@
 //   acc_c += wk * (A_c[j] - A_c[i])                       for each diffusing channel c
 // then u_i = 1 / rho_i and A_c'[i] = A_c[i] + (g_c acc_c) u_i with g_c = (2 kappa_c) delta from the host.  Jacobi: every A_c[j] is
 // read from `attr_in` and every A_c' goes to the same row of `attr_out`, the spare tracking set; a channel that does not diffuse
-// is neither read nor written.  The walk is k_surface_tension's (kernels_density.hip): three rows staged in LDS where the block's
-// ranges fit, the unstaged global sweep where they do not; w_j is formed once per staged candidate (with MASS1 it is the density
-// pass's |rho2.y| = RN(1/rho_j)) and sits next to q_j and the D channel values in LDS: (12 + 4 D) x 3 x NB_TILE bytes.
+// is neither read nor written.  The walk is the driver's (fs_neighbours.h walk_lane / walk_bounds / walk_rows, as k_density and
+// k_surface_tension use it) with DiffuseTerms: three rows staged in LDS where the block's ranges fit, the unstaged global sweep where they
+// do not; w_j is formed once per staged candidate (with MASS1 it is the density pass's |rho2.y| = RN(1/rho_j)) and sits next to q_j and
+// the D channel values in LDS: (12 + 4 D) x 3 x NB_TILE bytes.
 // Buoyancy (channel b, may be one of the diffusing ones or not): a = A_b[i] before the pass,
 //   s = beta (A0 - a);  fb = (st_i +) ((rho_i s) g.x, (rho_i s) g.y)
 // which the force launch takes as the `st` operand of its ST instantiations.
@@ -31,29 +32,17 @@ struct DiffuseConsts {
     float beta, a0, gx, gy;
 };
 
-// (the two halves of kernels_density.hip's st_weight: the word read per candidate, the weight from it)
-template <bool MASS1>
-__device__ __forceinline__ float df_weight_operand(const float2* __restrict__ rho2, const float* __restrict__ rho_arr, uint32_t j) {
-    if (MASS1) return rho2[j].y;                    // +-RN(1/rho_j): the sign is the density pass's safe bit
-    return rho_arr ? rho_arr[j] : rho2[j].x;        // rho_j.  rho_arr: tolerance mode (rho2 = {pressure, 1/rho})
-}
-template <bool MASS1>
-__device__ __forceinline__ float df_weight_of(const StepParams& P, float d) {
-    if (MASS1) return fabsf(d);                     // RN(1/rho_j) == RN(1.0f / rho_j)
-    return __fdiv_rn(P.mass, d);
-}
-
-template <int D> struct DfCandidate { float2 q; float d; float a[D]; };
 template <int D> struct DfAcc { float v[D]; };
+template <int D> struct DfCandidate { float2 q; float d; DfAcc<D> a; };   // staged of a candidate: position, weight operand, channels
 
 template <int D>
-__device__ __forceinline__ void df_term(const DiffuseConsts& C, float2 me, const DfAcc<D>& mine, float2 q, float w, const DfAcc<D>& a,
+__device__ __forceinline__ void df_term(float h2, float cg, float2 me, const DfAcc<D>& mine, float2 q, float w, const DfAcc<D>& a,
                                         DfAcc<D>& acc) {
     const float ox = q.x - me.x, oy = q.y - me.y;
     const float r2 = ox * ox + oy * oy;
-    const bool in = !(r2 > C.h2);                   // a NaN candidate is not skipped (the statement's test, as written)
-    const float d = C.h2 - r2;
-    const float wk = w * ((C.cg * d) * d);
+    const bool in = !(r2 > h2);                     // a NaN candidate is not skipped (the statement's test, as written)
+    const float d = h2 - r2;
+    const float wk = w * ((cg * d) * d);
     // a select, not a product with zero: a skipped candidate's A may be a NaN.  An accumulator that starts at +0.0f is never
     // -0.0f, so adding +0.0f for a skipped candidate IS skipping it
 #pragma unroll
@@ -72,6 +61,47 @@ __device__ __forceinline__ float2 buoyancy_force(const DiffuseConsts& C, float a
     return make_float2(bx, by);
 }
 
+// The diffusion terms as walk_rows takes them (fs_neighbours.h).  `rows` (the D diffusing rows of attr_in), `mine` and `acc` are locals
+// of the kernel (as members they cost up to 10 SGPRs), which loads `mine` between the two halves of walk_lane.
+template <int D, bool MASS1> struct DiffuseTerms {
+    const StepParams& P; const DiffuseConsts& C;
+    const float2 *__restrict__ pred, *__restrict__ rho2;
+    const float* __restrict__ rho_arr;
+    float2 (*s_q)[NB_TILE]; float (*s_w)[NB_TILE]; float (*s_a)[3][NB_TILE];
+    float2 me;
+    const float* const* rows; const DfAcc<D>& mine; DfAcc<D>& acc;
+    __device__ __forceinline__ DfCandidate<D> fetch(uint32_t k) const {
+        DfCandidate<D> c;
+        c.q = pred[k]; c.d = walk_weight_operand<MASS1>(rho2, rho_arr, k);
+#pragma unroll
+        for (int e = 0; e < D; ++e) c.a.v[e] = rows[e][k];
+        return c;
+    }
+    __device__ __forceinline__ void put(int r, uint32_t j, const DfCandidate<D>& c) {
+        s_q[r][j] = c.q; s_w[r][j] = walk_weight_of<MASS1>(P, c.d);
+#pragma unroll
+        for (int e = 0; e < D; ++e) s_a[e][r][j] = c.a.v[e];
+    }
+    __device__ __forceinline__ DfAcc<D> staged_a(int r, uint32_t k) const {
+        DfAcc<D> a;
+#pragma unroll
+        for (int e = 0; e < D; ++e) a.v[e] = s_a[e][r][k];
+        return a;
+    }
+    __device__ __forceinline__ void row(int r, uint32_t k, uint32_t hi) {
+        // read once, in front of the loops: read inside them, every trip's LDS reads wait for a kernel-argument load (profiles/walk2d_ab.txt)
+        const float h2 = C.h2, cg = C.cg;
+        for (; k + 2u <= hi; k += 2u) {          // two candidates per trip: independent LDS reads, adds in index order
+            const float2 q0 = s_q[r][k], q1 = s_q[r][k + 1u]; const float w0 = s_w[r][k], w1 = s_w[r][k + 1u];
+            const DfAcc<D> a0 = staged_a(r, k), a1 = staged_a(r, k + 1u);
+            df_term<D>(h2, cg, me, mine, q0, w0, a0, acc);
+            df_term<D>(h2, cg, me, mine, q1, w1, a1, acc);
+        }
+        if (k < hi) df_term<D>(h2, cg, me, mine, s_q[r][k], s_w[r][k], staged_a(r, k), acc);
+    }
+    __device__ __forceinline__ void one(uint32_t k) { const DfCandidate<D> c = fetch(k); df_term<D>(C.h2, C.cg, me, mine, c.q, walk_weight_of<MASS1>(P, c.d), c.a, acc); }
+};
+
 template <int D, bool MASS1>
 __global__ __launch_bounds__(FS_BLOCK) void k_diffuse(StepParams P, DiffuseConsts C, const float2* __restrict__ pred,
                                                       const float2* __restrict__ rho2, const float* __restrict__ rho_arr,
@@ -83,84 +113,24 @@ __global__ __launch_bounds__(FS_BLOCK) void k_diffuse(StepParams P, DiffuseConst
     __shared__ float s_w[3][NB_TILE];
     __shared__ float s_a[D][3][NB_TILE];
     __shared__ uint32_t s_red[24];
-    const uint32_t n = P.n;
     uint32_t blk;
-    if (!xcd_block(P, (n + FS_BLOCK - 1) / FS_BLOCK, &blk)) return;   // uniform
-    const uint32_t i = blk * FS_BLOCK + threadIdx.x;
-    const bool live = i < n;
-    const uint32_t lo_fix = quirk_lo_fix(P, pairs, cs, start_ref);
-    const uint32_t ii = live ? i : n - 1;
-    const float2 me = pred[ii];
+    if (!xcd_block(P, (P.n + FS_BLOCK - 1) / FS_BLOCK, &blk)) return;   // uniform
+    WalkLane L = walk_lane_particle(blk, P.n, pred);
     const float* rows[D];
     DfAcc<D> mine, acc;
 #pragma unroll
-    for (int c = 0; c < D; ++c) {
+    for (int c = 0; c < D; ++c) {       // the particle's own channel values: in flight with its position
         rows[c] = attr_in + (size_t)C.ch[c] * stride;
-        mine.v[c] = rows[c][ii];
+        mine.v[c] = rows[c][L.ii];
         acc.v[c] = 0.0f;
     }
-    uint32_t cx, cy;
-    int32_t cg;
-    uv_local(P, me, &cx, &cy, &cg);
-    const RowRanges R = lane_row_ranges(P, cs, lo_fix, cx, cy, live);
+    walk_lane_rows(P, cs, start_ref, pairs, L);
+    DiffuseTerms<D, MASS1> T{P, C, pred, rho2, rho_arr, s_q, s_w, s_a, L.me, rows, mine, acc};
     uint32_t blo[3], bhi[3];
-    bool fit;
-    if (P.block_bounds) {       // this step's density pass reduced the same ranges over the same 256 particles
-        fit = recorded_tile_bounds(P, blk, blo, bhi, NB_TILE);
-    } else {
-        fit = block_tile_bounds(R, s_red, blo, bhi, NB_TILE);
-    }
-    auto fetch = [&](uint32_t k) {
-        DfCandidate<D> c;
-        c.q = pred[k];
-        c.d = df_weight_operand<MASS1>(rho2, rho_arr, k);
-#pragma unroll
-        for (int e = 0; e < D; ++e) c.a[e] = rows[e][k];
-        return c;
-    };
-    if (fit) {
-        StagedRows<DfCandidate<D>> S;   // all loads of the three rows, then the weights and the LDS writes (fs_neighbours.h)
-        stage_rows_load(S, blo, bhi, fetch);
-        stage_rows_store(S, blo, bhi, [&](int r, uint32_t j, const DfCandidate<D>& c) {
-            s_q[r][j] = c.q;
-            s_w[r][j] = df_weight_of<MASS1>(P, c.d);
-#pragma unroll
-            for (int e = 0; e < D; ++e) s_a[e][r][j] = c.a[e];
-        });
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const bool any = R.lo[r] < R.hi[r];
-            const uint32_t hi = any ? R.hi[r] - blo[r] : 0u;
-            uint32_t k = any ? R.lo[r] - blo[r] : 0u;
-            for (; k + 2u <= hi; k += 2u) {          // two candidates per trip: independent LDS reads, adds in index order
-                const float2 q0 = s_q[r][k], q1 = s_q[r][k + 1u];
-                const float w0 = s_w[r][k], w1 = s_w[r][k + 1u];
-                DfAcc<D> a0, a1;
-#pragma unroll
-                for (int e = 0; e < D; ++e) { a0.v[e] = s_a[e][r][k]; a1.v[e] = s_a[e][r][k + 1u]; }
-                df_term<D>(C, me, mine, q0, w0, a0, acc);
-                df_term<D>(C, me, mine, q1, w1, a1, acc);
-            }
-            if (k < hi) {
-                DfAcc<D> a0;
-#pragma unroll
-                for (int e = 0; e < D; ++e) a0.v[e] = s_a[e][r][k];
-                df_term<D>(C, me, mine, s_q[r][k], s_w[r][k], a0, acc);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            for (uint32_t k = R.lo[r]; k < R.hi[r]; ++k) {
-                const DfCandidate<D> c = fetch(k);
-                DfAcc<D> a0;
-#pragma unroll
-                for (int e = 0; e < D; ++e) a0.v[e] = c.a[e];
-                df_term<D>(C, me, mine, c.q, df_weight_of<MASS1>(P, c.d), a0, acc);
-            }
-    }
-    if (!live) return;
+    const bool fit = walk_bounds<true>(P, blk, L.R, s_red, blo, bhi, NB_TILE);
+    walk_rows<0>(L.R, blo, bhi, fit, T);
+    if (!L.live) return;
+    const uint32_t i = L.i;
     const float rho_i = rho_arr ? rho_arr[i] : rho2[i].x;
     const float u = __fdiv_rn(1.0f, rho_i);
 #pragma unroll

@@ -1,6 +1,7 @@
 """Scenes that put the prologue of the 2D density / force / surface-tension passes on its edges — TEST INFRASTRUCTURE, plain numpy.
 
-The prologue (csrc/fs_neighbours.h: lane_row_ranges, stage_rows_load / stage_rows_store; force_block and density_block) looks up
+The prologue (csrc/fs_neighbours.h: lane_row_ranges, stage_rows_load / stage_rows_store; force_block for the force pass, the driver
+walk_lane / walk_bounds / walk_rows for the density, surface-tension and diffusion passes) looks up
 the lane's three row ranges in the dense cell table and stages the block-wide ranges of a workgroup's 256 consecutive sorted
 particles in LDS, in up to three trips of 256 candidates per row.  The scenes choose cell keys through crafted positions
 (tests/csort_scenes.py's placement rules: h = 0.2, a point 0.01 .. 0.19 inside its cell, no motion in the predict step) so that

@@ -1,5 +1,5 @@
 """The load phase of the density, force and sort tile kernels, where their waves run at a raised priority (csrc/fs_device.h
-wave_prio_raise / wave_prio_lower), and the density pass's read of its "safe operand" word (density_block): three steps from a
+wave_prio_raise / wave_prio_lower; the density pass lowers inside csrc/fs_neighbours.h walk_rows), and the density pass's read of its "safe operand" word (density_block): three steps from a
 fresh handle against the oracle, bit for bit — every field of every record (position, predicted position, velocity, density,
 key) and start_indices — in both sort modes.  The stored reciprocal {rho, +-RN(1/rho)} is not downloadable; its value and its
 sign (the safe bit) are seen through the force pass that reads it: a pair with an unsafe particle that took the

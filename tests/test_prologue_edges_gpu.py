@@ -1,5 +1,6 @@
 """The prologue of the 2D density, surface-tension and force passes on its edges (csrc/fs_neighbours.h: lane_row_ranges,
-stage_rows_load / stage_rows_store; density_block, k_surface_tension, force_block): the scenes of tests/prologue_scenes.py, whose
+stage_rows_load / stage_rows_store; the driver walk_lane / walk_bounds / walk_rows under density_block and k_surface_tension;
+force_block): the scenes of tests/prologue_scenes.py, whose
 edges tests/test_prologue_scenes.py proves on the CPU from the oracle's sorted keys, run on the engine for two steps and compared
 with the oracle bit for bit — every field of every particle and start_indices — in both sort modes.
 

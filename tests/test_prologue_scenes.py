@@ -4,6 +4,9 @@ per-lane and the block-wide row ranges the kernels reduce) then says which corne
 row ranges touch, how many lanes of the last workgroup are live and how long block 0's rows are against the staging trips (256,
 512) and the two tiles (NBF_TILE = 544, NB_TILE = 640).  tests/test_prologue_edges_gpu.py runs the same scenes on the engine.
 No GPU."""
+import glob
+import os
+
 import numpy as np
 import pytest
 
@@ -108,3 +111,29 @@ def test_strip_block_zero_has_the_row_length_it_is_named_after(fs, orc, name, st
 def test_the_strip_cases_cover_every_interval(fs):
     lengths = sorted(S.strip_length(step, extra) for _, step, extra in S.STRIP_CASES)
     assert [sum(a < x <= b for x in lengths) for a, b in ((256, 512), (512, 544), (544, 640), (640, 1 << 30))] == [1, 1, 1, 1]
+
+
+def test_the_three_term_passes_share_one_walk():
+    """The prologue, the stage-and-barrier and the two row loops of k_density / k_density_edge, k_surface_tension and k_diffuse exist
+    once, as the driver of csrc/fs_neighbours.h (walk_lane, walk_bounds, walk_rows): the passes hold their terms and call it."""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpu-fluid-simulation_amd", "csrc")
+    text = {}
+    for path in glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.inc")):
+        with open(path) as fh:
+            text[os.path.basename(path)] = fh.read()
+    for name in ("kernels_density.hip", "kernels_diffuse.hip"):
+        for own in ("lane_row_ranges(", "stage_rows_load(", "stage_rows_store(", "block_tile_bounds(", "recorded_tile_bounds("):
+            assert own not in text[name], (name, own)
+    for name, fn in (("kernels_density.hip", "void density_block("), ("kernels_density.hip", "void k_surface_tension("),
+                     ("kernels_diffuse.hip", "void k_diffuse(")):
+        body = text[name][text[name].index(fn):]
+        body = body[:body.index("\n}\n")]
+        assert body.count("walk_rows<") == 1 and body.count("walk_bounds<") == 1, fn
+        assert body.count("walk_lane(") + body.count("walk_lane_particle(") == 1, fn
+    driver = text["fs_neighbours.h"]
+    walk = driver[driver.index("void walk_rows("):]
+    walk = walk[:walk.index("\n}\n")]
+    assert walk.count("stage_rows_load(") == 1 and walk.count("stage_rows_store(") == 1 and walk.count("__syncthreads()") == 1
+    assert driver.count("lane_row_ranges(P, cs, L.lo_fix") == 1
+    for name, t in text.items():
+        assert "df_weight_" not in t and "st_weight_" not in t, name
