@@ -160,8 +160,12 @@ StepParams fsd::make_params(const fs_sim& s, const fs_uniform& u, uint32_t own_l
     static const bool no_sharediv = getenv("FS_NO_SHAREDIV") != nullptr;
     // ... and the per-particle "safe operand" classification bounds the pressure numerators only if h * spiky <= 2^19
     const float hspiky = std::fabs(P.h * P.spiky);
+    // ... and force_terms_shared has no `dst <= h` test of its own: the scan's !(r2 > sqr_radius) decides it, which holds when
+    // sqr_radius is RN(h * h) (fs_force_pair.h); a handle for which it is not keeps the true-division path, as with any failed proof
+    const float hh = P.h * P.h;
+    P.half_h = 0.5f * P.h;
     P.share_div = (!no_sharediv && s.div_2h3.ok && s.div_h2.ok && s.rcp_ok && s.sqrt_ok && P.h >= 0x1p-19f && P.h <= 0x1p19f &&
-                   hspiky <= FS_HSPIKY_HI) ? 1 : 0;
+                   hspiky <= FS_HSPIKY_HI && P.sqr_radius == hh) ? 1 : 0;
     P.col_origin = 0;
     P.own_lo = 0; P.own_hi = s.grid_w;
     P.grid_w_global = s.grid_w;

@@ -68,6 +68,7 @@ struct StepParams {
     // same rows, so the force pass reads the density pass's result (eight scalar loads) instead of repeating the reduction
     // (ballots, readlanes, an LDS round trip and a barrier).  nullptr: every pass reduces for itself.
     uint32_t* block_bounds;
+    float half_h;              // 0.5f * h (exact), the numerator of the force pass's h / (2 dst) = (h/2) / dst (fs_force_pair.h)
 };
 
 // Slab mode: does the force pass of this launch advance a particle whose GLOBAL cell column is cg?  (Ghosts — columns outside

@@ -146,8 +146,11 @@ __device__ __forceinline__ ForceTerms force_terms_shared(const StepParams& P, co
     const float dx = div_by_rcp(ox, dst, ydst);
     const float dy = div_by_rcp(oyv, dst, ydst);
     const float npress = P.pressure_k * (nrho - P.rest_density);
-    const bool inside = dst <= h;
-    const float kern = inside ? (-(h - dst)) * P.spiky : 0.0f;
+    // no `dst <= h` test here (the exact body keeps the reference's): it cannot fail for a pair this path is answerable for.
+    // Every caller admits a pair by !(r2 > sqr_radius), `good` sends r2 < 2^-40 and NaN to the exact body, and share_div implies
+    // sqr_radius == RN(h * h) (engine.hip): sqrt is monotone and RN(sqrt(RN(h * h))) <= h for every f32 h of [2^-19, 2^19]
+    // (tests/test_force_identities.py enumerates them), so dst == RN(sqrt(r2)) <= h.
+    const float kern = (-(h - dst)) * P.spiky;
     const float shared = (pressure + npress) * 0.5f;
     const float apx = dx * kern * shared, apy = dy * kern * shared;
     const float dvx = nv.x - mv.x, dvy = nv.y - mv.y;
@@ -158,8 +161,10 @@ __device__ __forceinline__ ForceTerms force_terms_shared(const StepParams& P, co
     // share_div implies both constant-division proofs succeeded (engine.hip)
     const float a = div_const_fast(-(dst * dst * dst), P.div_2h3.c, P.div_2h3.y);
     const float b = div_const_fast(dst * dst, P.div_h2.c, P.div_h2.y);
-    const float hq = div_by_rcp(h, 2.0f * dst, 0.5f * ydst);           // RN(1/(2 dst)) == RN(1/dst)/2 exactly
-    const float kv = inside ? P.visc_k * (a + b + hq - 1.0f) : 0.0f;
+    // h / (2 dst) as (h/2) / dst: q0, the residual and the final fma are those of div_by_rcp(h, 2 dst, RN(1/dst)/2) halved, all
+    // exactly (h in [2^-19, 2^19], dst in [2^-20, h]: nothing underflows), and h/2 comes in a scalar register (StepParams::half_h) — three instructions per pair
+    const float hq = div_by_rcp(P.half_h, dst, ydst);
+    const float kv = P.visc_k * (a + b + hq - 1.0f);
     T.vx = div_by_rcp(dvx, nrho, yrho) * kv;
     T.vy = div_by_rcp(dvy, nrho, yrho) * kv;
     return T;

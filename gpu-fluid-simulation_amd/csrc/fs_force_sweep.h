@@ -73,7 +73,7 @@ __device__ __forceinline__ void force_sweep_chunks(const StepParams& P, const Ro
                 const uint32_t clen = cq < len ? (len - cq < 32u ? len - cq : 32u) : 0u;
                 const uint32_t boff = clen ? boff0 + 256u * (uint32_t)q : 0u;
                 uint32_t mask = 0, t = 0;
-                for (; __any(t < clen); t += 4u) {
+                if (__any(0u < clen)) do {              // tested at the bottom, as in force_sweep_masks
                     const float2 q0 = FS_CAND(boff, t), q1 = FS_CAND(boff, t + 1u), q2 = FS_CAND(boff, t + 2u), q3 = FS_CAND(boff, t + 3u);
                     const float2 qq[4] = {q0, q1, q2, q3};
 #pragma unroll
@@ -81,7 +81,8 @@ __device__ __forceinline__ void force_sweep_chunks(const StepParams& P, const Ro
                         const float ox = qq[u].x - me.x, oyv = qq[u].y - me.y;
                         shift_in_not_greater(mask, ox * ox + oyv * oyv, lim);
                     }
-                }
+                    t += 4u;
+                } while (__any(t < clen));
                 mask = t ? mask << (32u - t) : 0u;
                 mask &= clen ? 0xFFFFFFFFu << (32u - clen) : 0u;
                 const uint32_t g = g0 + 32u * (uint32_t)q;
@@ -109,10 +110,12 @@ __device__ __forceinline__ void force_sweep_chunks(const StepParams& P, const Ro
         }                                                                                                            \
     } while (0)
             FS_FETCH_NEXT1();
-            while (__any(pending)) {
+            wave_mask pendm = wm(pending);              // the loop test on the scalar unit, as in force_sweep_masks
+            while (pendm != 0) {
                 const bool cur_valid = have;
                 const float2 q0 = qn, v0 = vn, d0 = dn;
                 FS_FETCH_NEXT1();
+                pendm = wm(pending);
                 if (cur_valid && MODE == 2) {
                     force_accum_tol(P, TC, me, mv, pressure, q0, v0, d0, A);
                 } else if (cur_valid) {
@@ -162,7 +165,9 @@ __device__ __forceinline__ bool force_sweep_masks(const StepParams& P, const Row
         la[r] = (uint32_t)r * NBF_ROW + (len ? R.lo[r] - blo[r] : 0u);
         const float2* base = s_flat + la[r];
         uint32_t mask = 0, t = 0;
-        for (; __any(t < len); t += 4u) {                                 // t is wave-uniform
+        // t is wave-uniform.  Tested at the bottom: with the test on top the mask is copied out of and back into the register the
+        // asm operand is tied to on every trip (two v_mov of 32 issue slots)
+        if (__any(0u < len)) do {
             const float2 q0 = base[t], q1 = base[t + 1u], q2 = base[t + 2u], q3 = base[t + 3u];
             const float2 qq[4] = {q0, q1, q2, q3};
 #pragma unroll
@@ -170,7 +175,8 @@ __device__ __forceinline__ bool force_sweep_masks(const StepParams& P, const Row
                 const float ox = qq[u].x - me.x, oyv = qq[u].y - me.y;
                 shift_in_not_greater(mask, ox * ox + oyv * oyv, lim);
             }
-        }
+            t += 4u;
+        } while (__any(t < len));
         // candidate t sits at bit (trips - 1 - t): left-align, keep the lane's own len candidates
         mask = t ? mask << (32u - t) : 0u;
         mask &= len ? 0xFFFFFFFFu << (32u - len) : 0u;
@@ -229,10 +235,14 @@ __device__ __forceinline__ bool force_sweep_masks(const StepParams& P, const Row
     float2 qn = make_float2(0.0f, 0.0f), vn = qn, dn = qn;
     bool have = false;
     FS_FETCH(have, qn, vn, dn);
-    while (__any(have)) {
+    // "does any lane still hold a neighbour" as the ballot of the compare that formed `have`, tested on the scalar unit: through
+    // __any() the flag took a v_cndmask and a v_cmp per neighbour to reach the branch
+    wave_mask havem = wm(have);
+    while (havem != 0) {
         const bool cur_valid = have;
         const float2 q0 = qn, v0 = vn, d0 = dn;
         FS_FETCH(have, qn, vn, dn);
+        havem = wm(have);
         FS_PAIR(cur_valid, q0, v0, d0);
     }
     } else {
@@ -241,14 +251,17 @@ __device__ __forceinline__ bool force_sweep_masks(const StepParams& P, const Row
     FS_FETCH(hA, qA, vA, dA);
     FS_FETCH(hB, qB, vB, dB);
     FS_FETCH(hC, qC, vC, dC);
-    for (;;) {       // a slot is refilled right after its neighbour's terms: two bodies later it is consumed
-        if (!__any(hA)) break;
+    // A slot is refilled right after its neighbour's terms: two bodies later it is consumed.  The queue only drains, so an empty
+    // slot means the slots fetched after it are empty too: the loop has ONE exit (on A).  In the last trip B and C may be empty
+    // for the whole wave: their terms are skipped on the empty exec mask and their fetches find the queue empty again.  (With
+    // an exit in front of every body the accumulators were copied for the exits, three v_mov per neighbour.)
+    wave_mask mA = wm(hA);                   // the ballot of hA, for the scalar unit (see the loop above)
+    while (mA != 0) {
         { const bool cv = hA; const float2 q0 = qA, v0 = vA, d0 = dA; FS_PAIR(cv, q0, v0, d0); }
+        mA = wm(cur != 0u);                  // the hA of the fetch below (taken in front of it: behind it costs two v_mov a trip)
         FS_FETCH(hA, qA, vA, dA);
-        if (!__any(hB)) break;
         { const bool cv = hB; const float2 q0 = qB, v0 = vB, d0 = dB; FS_PAIR(cv, q0, v0, d0); }
         FS_FETCH(hB, qB, vB, dB);
-        if (!__any(hC)) break;
         { const bool cv = hC; const float2 q0 = qC, v0 = vC, d0 = dC; FS_PAIR(cv, q0, v0, d0); }
         FS_FETCH(hC, qC, vC, dC);
     }

@@ -44,15 +44,18 @@ template <bool TOL, bool MASS1> struct DensityTerms {
     __device__ __forceinline__ void add(float2 q) { rho = TOL ? density_cube_tol(h2, me, q, rho) : rho + density_term<MASS1>(P, h2, me, q); }
     // four candidates per trip (independent LDS reads and kernel evaluations give the wave ILP), adds in index order; then a scalar tail
     __device__ __forceinline__ void row(int r, uint32_t k, uint32_t hi) {
-        const float2* sp = s_pred[r];
-        for (; k + 4u <= hi; k += 4u) {
-            const float2 q0 = sp[k], q1 = sp[k + 1u], q2 = sp[k + 2u], q3 = sp[k + 3u];
+        // the trips' only bookkeeping is one LDS pointer and its compare with the end of the lane's whole fours (k <= hi: walk_rows)
+        const float2* sp = s_pred[r] + k;
+        const float2* const end4 = sp + ((hi - k) & ~3u);
+        const float2* const end = s_pred[r] + hi;
+        for (; sp != end4; sp += 4) {
+            const float2 q0 = sp[0], q1 = sp[1], q2 = sp[2], q3 = sp[3];
             if (TOL) { add(q0); add(q1); add(q2); add(q3); continue; }
             const float t0 = density_term<MASS1>(P, h2, me, q0), t1 = density_term<MASS1>(P, h2, me, q1);
             const float t2 = density_term<MASS1>(P, h2, me, q2), t3 = density_term<MASS1>(P, h2, me, q3);
             rho += t0; rho += t1; rho += t2; rho += t3;
         }
-        for (; k < hi; ++k) add(sp[k]);
+        for (; sp != end; ++sp) add(*sp);
     }
     __device__ __forceinline__ void one(uint32_t k) { add(pred[k]); }
 };

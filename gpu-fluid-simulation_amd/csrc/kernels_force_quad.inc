@@ -128,15 +128,18 @@ __global__ __launch_bounds__(FS_BLOCK) void k_force_quad(FS_FORCE_ARGS, uint32_t
                 float2 qA, vA, dA, qB, vB, dB, qC, vC, dC;
                 FS_QSELECT(hA, qA, vA, dA);
                 FS_QSELECT(hB, qB, vB, dB);
-                for (;;) {                                 // two rounds' gathers in flight behind the one being evaluated
-                    if (!__any(hA)) break;
-                    FS_QSELECT(hC, qC, vC, dC);
+                // two rounds' gathers in flight behind the one being evaluated; "does any lane hold a neighbour" as the ballot of
+                // the compare that formed the flag, tested on the scalar unit (fs_force_sweep.h)
+                wave_mask mA = wm(hA), mB = wm(hB), mC;
+                for (;;) {
+                    if (mA == 0) break;
+                    FS_QSELECT(hC, qC, vC, dC); mC = wm(hC);
                     FS_QROUND(hA, qA, vA, dA);
-                    if (!__any(hB)) break;
-                    FS_QSELECT(hA, qA, vA, dA);
+                    if (mB == 0) break;
+                    FS_QSELECT(hA, qA, vA, dA); mA = wm(hA);
                     FS_QROUND(hB, qB, vB, dB);
-                    if (!__any(hC)) break;
-                    FS_QSELECT(hB, qB, vB, dB);
+                    if (mC == 0) break;
+                    FS_QSELECT(hB, qB, vB, dB); mB = wm(hB);
                     FS_QROUND(hC, qC, vC, dC);
                 }
 #undef FS_QROUND
