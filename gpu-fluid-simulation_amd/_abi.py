@@ -429,6 +429,11 @@ PROTOTYPES = {
     "fs3_surface_tension_enabled": (C.c_int, [_P]),
     "fs3_surface_tension_params": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "fs3_download_surface_tension": (C.c_int, [_P, _P, C.c_size_t]),
+    "fs3_set_diffusion": (C.c_int, [_P, C.c_int, C.c_float]),
+    "fs3_get_diffusion": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
+    "fs3_set_buoyancy": (C.c_int, [_P, C.c_int, C.c_float, C.c_float]),
+    "fs3_get_buoyancy": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "fs3_download_buoyancy": (C.c_int, [_P, _P, C.c_size_t]),
     "fs3_reserve": (C.c_int, [_P, C.c_uint32]),
     "fs3_capacity": (C.c_uint32, [_P]),
     "fs3_emit_particles": (C.c_int, [_P, _P, C.c_size_t]),

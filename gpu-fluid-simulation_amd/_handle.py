@@ -148,6 +148,44 @@ class _SurfaceTension:
         return out
 
 
+class _Diffusion:
+    """Opt-in diffusion and buoyancy of the tracking channels (build extension; DESIGN.md §27, 3D: §28).  diffusion_limit stays
+    per class: the constant differs."""
+
+    def set_diffusion(self, channel, conductivity):
+        """Channel `channel` diffuses between neighbours with conductivity kappa >= 0 (0: not at all, the default), for the steps
+        after this call.  Tracking must be on; track() and untrack() clear every conductivity and the buoyancy channel.  The
+        explicit update is stable while conductivity <= diffusion_limit(...)."""
+        self._call("set_diffusion", int(channel), float(conductivity))
+
+    def diffusion(self, channel):
+        k = C.c_float()
+        self._call("get_diffusion", int(channel), C.byref(k))
+        return float(k.value)
+
+    def set_buoyancy(self, channel, beta, reference=0.0):
+        """Channel `channel` becomes the buoyancy channel: a particle with value a gains -beta * (a - reference) * gravity * delta
+        of velocity per step (Boussinesq), for the steps after this call."""
+        self._call("set_buoyancy", int(channel), float(beta), float(reference))
+
+    def clear_buoyancy(self):
+        self._call("set_buoyancy", -1, 0.0, 0.0)
+
+    @property
+    def buoyancy(self):
+        """(channel, beta, reference) of the buoyancy channel, or None"""
+        c, b, r = C.c_int(), C.c_float(), C.c_float()
+        self._call("get_buoyancy", C.byref(c), C.byref(b), C.byref(r))
+        return None if c.value < 0 else (int(c.value), float(b.value), float(r.value))
+
+    def buoyancy_forces(self):
+        """What the last step with a buoyancy channel handed the force pass per particle (the buoyancy force, plus the surface
+        tension's when that is on): (N, 2) float32 for the 2D simulation and (N, 3) for the 3D one, in download_particles() order."""
+        out = np.empty((self.particle_count, self._dim), dtype=np.float32)
+        self._call("download_buoyancy", _ptr(out), out.shape[0])
+        return out
+
+
 class _Count:
     """A particle count that changes at run time (build extension; DESIGN.md §22, 3D: §21).  `_nozzle` is the class's nozzle
     structure (fs_nozzle / fs3_nozzle); vectors have `_dim` components."""

@@ -151,6 +151,52 @@ struct fs_sim3 {
     // The opt-in particle tracking: the 2D engine's owner (engine.h), stride cap; never enabled: no allocation, no launch.
     fsd::Tracking trk;
     fsd::RemoveScratch removal;  // scratch of a removal: the 2D engine's owner too
+    // The opt-in diffusion and buoyancy of the tracking channels (fs3_set_diffusion / fs3_set_buoyancy in
+    // engine_3d_features.hip): the host settings of the 2D handle's fsd::Diffusion (engine.h).  Host settings only, until a
+    // buoyancy channel is first set: then `fb`, 16 B per slot.  Nothing set: no launch, no allocation.
+    struct Diffusion {
+        float kappa[FS_TRACK_MAX_CHANNELS] = {};   // conductivity per channel; 0: the channel does not diffuse
+        int buoy = -1;                  // the buoyancy channel, -1: none
+        float beta = 0.0f, reference = 0.0f;
+        fsd::DevArray<float4> fb;       // per sorted slot: what the last buoyancy step handed the force pass (st + b, or b), .w = 0
+        bool valid = false;             // a buoyancy step has been enqueued since the channel was last set (and the count has not changed)
+        // fs3_track_enable / fs3_track_disable: every setting goes
+        void clear() {
+            for (float& k : kappa) k = 0.0f;
+            buoy = -1; beta = reference = 0.0f;
+            valid = false;
+        }
+        // This step's pass, after surface tension's and before the force launch: the diffusing channels are advanced in place
+        // (through the spare tracking set, which is free once the carry has run, and one device-to-device copy per row back — behind
+        // every launch: the buoyancy tail reads the value before the pass), and with a buoyancy channel the force launch's `stf`
+        // operand becomes fb.  Returns that operand: stf itself when there is no buoyancy channel.
+        const float4* enqueue(hipStream_t st, const fsd::Params3& P, const fsd::Arrays3& A, const fs3_tick_settings& t,
+                              const fsd::Tracking& trk, uint32_t cap, const float4* stf) {
+            if (!trk.on()) return stf;
+            fsd::Diffuse3Plan D;
+            for (int c = 0; c < trk.channels; ++c)
+                if (kappa[c] != 0.0f) {
+                    D.channel[D.count] = c;
+                    D.g[D.count++] = (2.0f * kappa[c]) * t.delta;
+                }
+            if (buoy >= 0 && buoy < trk.channels) {
+                D.buoyancy_channel = buoy;
+                D.beta = beta; D.reference = reference;
+                D.gravity_x = t.gravity.x; D.gravity_y = t.gravity.y; D.gravity_z = t.gravity.z;
+            }
+            if (!D.count && D.buoyancy_channel < 0) return stf;
+            float* const cur = trk.attr[trk.cur].p;
+            float* const spare = trk.attr[trk.cur ^ 1].p;
+            fsd::launch3_diffuse(st, P, A, D, cur, spare, cap, stf, fb.p);
+            for (int k = 0; k < D.count && P.n; ++k) {
+                const size_t row = (size_t)D.channel[k] * cap;
+                (void)hipMemcpyAsync(cur + row, spare + row, (size_t)P.n * sizeof(float), hipMemcpyDeviceToDevice, st);   // errors: the step's hipGetLastError
+            }
+            if (D.buoyancy_channel < 0) return stf;
+            valid = true;
+            return fb.p;
+        }
+    } diffusion;
 
     // the arrays as the launchers see them (fs_3d.h): the force pass writes the new positions into the spare buffer
     fsd::Arrays3 arrays() const {

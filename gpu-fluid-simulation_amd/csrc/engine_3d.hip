@@ -90,6 +90,7 @@ fs_status enqueue3(fs_sim3* s, const fs3_tick_settings* t) {
     // the opt-in features' operands (engine_3d.h): the collider by value, and surface tension's pass ahead of the force pass
     Collide3 K;
     const float4* stf = s->tension.enqueue(st, P, A);
+    stf = s->diffusion.enqueue(st, P, A, *t, s->trk, s->cap, stf);   // channel diffusion and buoyancy, if set
     // with moving bodies their pass follows the force kernel and carries the completion event in its place; with
     // their loads on (§26) that is the pass's loads form and its fold
     Bodies3 BD;

@@ -11,13 +11,14 @@
 using namespace fsd;
 namespace {
 // The count becomes new_n (2 <= new_n <= cap, != n), the state arrays already hold it (or will, in stream order).  What every
-// change shares: the queries and surface tension's forces no longer belong to the state, and the sort's bookkeeping follows
+// change shares: the queries, surface tension's forces and buoyancy's no longer belong to the state, and the sort's bookkeeping follows
 // (sort_count_changed).
 fs_status count_changed(fs_sim3* s, uint32_t new_n) {
     const fs_status health = sort_count_changed(s->stream, s->sortp, s->dirty, s->n, new_n);
     s->n = new_n;
     s->sample_stale = true;
     s->tension.valid = false;
+    s->diffusion.valid = false;
     return health;
 }
 
@@ -61,7 +62,7 @@ fs_status fs3_reserve(fs_sim3* s, uint32_t capacity) {
     FS_HIP(hipSetDevice(s->device));
     const size_t cap = capacity, n = s->n;
     // everything new first: on failure the locals go and the handle is what it was
-    DevArray<float4> pos, vel, pos_s, vel_s, pred, st;
+    DevArray<float4> pos, vel, pos_s, vel_s, pred, st, fb;
     DevArray<uint32_t> key, dirty;
     DevArray<u64> pairs, masks;
     DevArray<fs3_particle> aos;
@@ -70,7 +71,7 @@ fs_status fs3_reserve(fs_sim3* s, uint32_t capacity) {
     auto ok = [&e](hipError_t r) { e = r; return r == hipSuccess; };
     (void)(ok(pos.alloc(cap)) && ok(vel.alloc(cap)) && ok(pos_s.alloc(cap)) && ok(vel_s.alloc(cap)) && ok(pred.alloc(cap + FS_PRED_SLACK)) &&
            ok(key.alloc(cap)) && ok(pairs.alloc(cap)) && ok(dirty.alloc(sort_tile_count(capacity))) && ok(aos.alloc(cap)) &&
-           ok(masks.alloc(s->masks.p ? 18 * cap : 0)) && ok(st.alloc(s->tension.st.p ? cap : 0)) &&
+           ok(masks.alloc(s->masks.p ? 18 * cap : 0)) && ok(st.alloc(s->tension.st.p ? cap : 0)) && ok(fb.alloc(s->diffusion.fb.p ? cap : 0)) &&
            ok(G.alloc(s->trk, cap)));
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -87,6 +88,7 @@ fs_status fs3_reserve(fs_sim3* s, uint32_t capacity) {
     if (e == hipSuccess) e = carry(q, pred, s->pred, n);
     if (e == hipSuccess) e = carry(q, key, s->key, n);
     if (e == hipSuccess) e = carry(q, st, s->tension.st, n);
+    if (e == hipSuccess) e = carry(q, fb, s->diffusion.fb, n);
     if (e == hipSuccess) e = G.carry_from(q, s->trk, n, s->cap, cap);
     const hipError_t es = hipStreamSynchronize(q);                         // before anything is freed, whatever happened
     if (e == hipSuccess) e = es;
@@ -95,6 +97,7 @@ fs_status fs3_reserve(fs_sim3* s, uint32_t capacity) {
     s->key = std::move(key); s->pairs = std::move(pairs); s->dirty = std::move(dirty); s->aos = std::move(aos);
     if (masks.p) s->masks = std::move(masks);
     if (st.p) s->tension.st = std::move(st);
+    if (fb.p) s->diffusion.fb = std::move(fb);
     G.commit(s->trk);
     s->removal.release();                                                  // sized by the capacity: the next removal allocates it again
     s->cap = capacity;

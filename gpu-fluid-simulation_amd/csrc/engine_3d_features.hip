@@ -1,5 +1,5 @@
 // engine_3d_features.hip — the opt-in features the 3D step enqueues for (their state: engine_3d.h, one struct each): colliders
-// (DESIGN.md §18), moving bodies (§23) and their loads (§26), surface tension (§19), particle tracking (§20) and, on top of tracking,
+// (DESIGN.md §18), moving bodies (§23) and their loads (§26), surface tension (§19), particle tracking (§20), channel diffusion and buoyancy (§28) and, on top of tracking,
 // fs3_download_particles_by_id.
 #include <hip/hip_runtime.h>
 
@@ -52,6 +52,13 @@ fs_status track3_copy(fs_sim3* s, int channel, bool attr, void* host, size_t n, 
     FS_HIP(hipSetDevice(s->device));
     FS_TRY(s->trk.copy(s->stream, s->n, s->cap, channel, attr, host, n, upload));
     return upload ? FS_OK : sort_health3(s);
+}
+
+// The checks every setter and getter of channel diffusion and buoyancy starts with: the handle and the pointers (`null`), then tracking on.
+fs_status diffusion3_handle(const fs_sim3* s, bool null) {
+    if (!s || null) return fail(FS_ERR_INVALID, "null argument");
+    if (!s->trk.on()) return fail(FS_ERR_INVALID, "diffusion: tracking is off (fs3_track_enable with at least one channel first)");
+    return FS_OK;
 }
 }  // namespace
 
@@ -287,12 +294,14 @@ fs_status fs3_track_enable(fs_sim3* s, int channels) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
     FS_HIP(hipSetDevice(s->device));
     FS_TRY(s->trk.enable(s->stream, s->n, s->cap, channels));
+    s->diffusion.clear();           // the channels start over: so do their conductivities and the buoyancy channel
     return FS_OK;
 }
 
 fs_status fs3_track_disable(fs_sim3* s) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
     s->trk.channels = -1;           // the arrays stay allocated until the handle is destroyed
+    s->diffusion.clear();
     return FS_OK;
 }
 
@@ -311,6 +320,58 @@ fs_status fs3_track_ids_device(fs_sim3* s, const uint32_t** out) {
 fs_status fs3_track_attr_device(fs_sim3* s, int channel, const float** out) {
     if (!s) return fail(FS_ERR_INVALID, "null argument");
     return s->trk.device_ptr(s->cap, channel, true, (const void**)out);
+}
+
+// ---- 3D channel diffusion and buoyancy ------------------------------------------------------------------
+fs_status fs3_set_diffusion(fs_sim3* s, int channel, float conductivity) {
+    FS_TRY(diffusion3_handle(s, false));
+    if (channel < 0 || channel >= s->trk.channels) return fail(FS_ERR_INVALID, "diffusion: no such channel");
+    if (!std::isfinite(conductivity) || conductivity < 0.0f) return fail(FS_ERR_INVALID, "diffusion: a conductivity that is negative or not finite");
+    s->diffusion.kappa[channel] = conductivity;     // host memory only: the next enqueue takes it by value
+    return FS_OK;
+}
+
+fs_status fs3_get_diffusion(const fs_sim3* s, int channel, float* conductivity) {
+    FS_TRY(diffusion3_handle(s, !conductivity));
+    if (channel < 0 || channel >= s->trk.channels) return fail(FS_ERR_INVALID, "diffusion: no such channel");
+    *conductivity = s->diffusion.kappa[channel];
+    return FS_OK;
+}
+
+fs_status fs3_set_buoyancy(fs_sim3* s, int channel, float beta, float reference) {
+    FS_TRY(diffusion3_handle(s, false));
+    if (channel < -1 || channel >= s->trk.channels) return fail(FS_ERR_INVALID, "buoyancy: no such channel");
+    if (!std::isfinite(beta) || !std::isfinite(reference)) return fail(FS_ERR_INVALID, "buoyancy: beta or reference not finite");
+    fs_sim3::Diffusion& d = s->diffusion;
+    if (channel >= 0 && !d.fb.p) {
+        FS_HIP(hipSetDevice(s->device));
+        if (d.fb.alloc(s->cap) != hipSuccess) {
+            (void)hipGetLastError();
+            d.fb.release();
+            return fail(FS_ERR_OOM, "buoyancy: force buffer");
+        }
+    }
+    if (channel != d.buoy) d.valid = false;         // fs3_download_buoyancy waits for a step of this setting
+    d.buoy = channel;
+    d.beta = channel >= 0 ? beta : 0.0f;
+    d.reference = channel >= 0 ? reference : 0.0f;
+    return FS_OK;
+}
+
+fs_status fs3_get_buoyancy(const fs_sim3* s, int* channel, float* beta, float* reference) {
+    FS_TRY(diffusion3_handle(s, !channel || !beta || !reference));
+    *channel = s->diffusion.buoy; *beta = s->diffusion.beta; *reference = s->diffusion.reference;
+    return FS_OK;
+}
+
+fs_status fs3_download_buoyancy(fs_sim3* s, fs_vec3* dst, size_t n) {
+    if (!s || !dst) return fail(FS_ERR_INVALID, "null argument");
+    if (s->diffusion.buoy < 0) return fail(FS_ERR_INVALID, "buoyancy: no channel is set");
+    if (!s->diffusion.valid) return fail(FS_ERR_INVALID, "buoyancy: no step with a buoyancy channel since the channel was last set");
+    if (n != s->n) return fail(FS_ERR_INVALID, "buoyancy: n must equal the particle count");
+    FS_HIP(hipSetDevice(s->device));
+    FS_TRY(fsd::download_vec3(s->stream, s->diffusion.fb.p, n, dst));
+    return sort_health3(s);
 }
 
 /* Off the step path: two downloads and a scatter on the host, so entries of dst that no id names are never written. */

@@ -82,6 +82,21 @@ struct Tension3 {
 // After launch3_density, before launch3_force: st[i] = {sx, sy, sz, 0} per sorted slot, from pred (.w = density), the cell table
 // and — A.masks non-null — the pass masks k3_density handed over.
 void launch3_surface_tension(hipStream_t st, const Params3& P, const Arrays3& A, const Tension3& T, float4* stf);
+// Diffusion and buoyancy of the tracking channels (include/fluidsim.h "3D channel diffusion and buoyancy", DESIGN.md §28;
+// kernels_diffuse3d.hip), after launch3_density and launch3_surface_tension, before launch3_force.  The plan of one step, by
+// value: channel[0 .. count) are the diffusing channels, ascending, g[k] = (2 kappa) delta of channel[k]; buoyancy_channel >= 0:
+// fb_out[i] = (st_in[i] +) (rho_i beta (reference - A_b[i])) gravity, .w = 0, which launch3_force takes as `stf`.  attr_in: the
+// channels as the carry delivered them (channel c at c * stride); attr_out: the spare set, of which only the rows of the diffusing
+// channels are written.  count == 0 and no buoyancy channel, or P.n == 0: no launch.
+struct Diffuse3Plan {
+    int count = 0;
+    int channel[4] = {0, 0, 0, 0};
+    float g[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    int buoyancy_channel = -1;
+    float beta = 0.0f, reference = 0.0f, gravity_x = 0.0f, gravity_y = 0.0f, gravity_z = 0.0f;
+};
+void launch3_diffuse(hipStream_t st, const Params3& P, const Arrays3& A, const Diffuse3Plan D, const float* attr_in, float* attr_out,
+                     uint32_t stride, const float4* st_in, float4* fb_out);
 // done (may be null): signalled by the kernel's completion.  K (may be null: no collider, today's instantiations): the push
 // operator runs in the kernel's tail, after the wall clamp.  stf (may be null: no surface tension, today's instantiations): the
 // forces of launch3_surface_tension, added to the force sum.

@@ -364,6 +364,20 @@ public:
         check(fs3_download_surface_tension(h_, v.data(), v.size()));
         return v;
     }
+    // 3D channel diffusion and buoyancy: tracking must be on; track / untrack clear the settings
+    void set_diffusion(int channel, float conductivity) { check(fs3_set_diffusion(h_, channel, conductivity)); }
+    float diffusion(int channel) const { float k = 0.0f; check(fs3_get_diffusion(h_, channel, &k)); return k; }
+    void set_buoyancy(int channel, float beta, float reference = 0.0f) { check(fs3_set_buoyancy(h_, channel, beta, reference)); }
+    void clear_buoyancy() { check(fs3_set_buoyancy(h_, -1, 0.0f, 0.0f)); }
+    bool buoyancy(int* channel, float* beta, float* reference) const {      // false: no buoyancy channel
+        check(fs3_get_buoyancy(h_, channel, beta, reference));
+        return *channel >= 0;
+    }
+    std::vector<fs_vec3> buoyancy_forces() {                                 // the last buoyancy step's fb per particle, download order
+        std::vector<fs_vec3> v(particle_count());
+        check(fs3_download_buoyancy(h_, v.data(), v.size()));
+        return v;
+    }
     // 3D particle count: `capacity` slots of which particle_count() are live.  reserve: grow-only, blocking, everything observable
     // is preserved.  emit / emit_nozzle append behind the live particles (count + n <= capacity), the nozzle's layer of nu x nv
     // records generated on the device.  remove_box (lo <= position <= hi on every axis) and remove (flags[i] != 0, one per

@@ -366,6 +366,11 @@ extern "C" {
     fn fs3_surface_tension_enabled(sim: *const fs_sim3) -> c_int;
     fn fs3_surface_tension_params(sim: *const fs_sim3, coefficient: *mut f32, threshold: *mut f32) -> c_int;
     fn fs3_download_surface_tension(sim: *mut fs_sim3, dst: *mut Vec3, n: usize) -> c_int;
+    fn fs3_set_diffusion(sim: *mut fs_sim3, channel: c_int, conductivity: f32) -> c_int;
+    fn fs3_get_diffusion(sim: *const fs_sim3, channel: c_int, conductivity: *mut f32) -> c_int;
+    fn fs3_set_buoyancy(sim: *mut fs_sim3, channel: c_int, beta: f32, reference: f32) -> c_int;
+    fn fs3_get_buoyancy(sim: *const fs_sim3, channel: *mut c_int, beta: *mut f32, reference: *mut f32) -> c_int;
+    fn fs3_download_buoyancy(sim: *mut fs_sim3, dst: *mut Vec3, n: usize) -> c_int;
     fn fs3_reserve(sim: *mut fs_sim3, capacity: u32) -> c_int;
     fn fs3_capacity(sim: *const fs_sim3) -> u32;
     fn fs3_emit_particles(sim: *mut fs_sim3, src: *const Particle3, n: usize) -> c_int;
@@ -945,6 +950,28 @@ impl FluidSimulation3D {
     pub fn surface_tension_forces(&mut self) -> Vec<Vec3> {
         let mut v = vec![Vec3::default(); self.particle_count() as usize];
         check(unsafe { fs3_download_surface_tension(self.raw, v.as_mut_ptr(), v.len()) }); v
+    }
+    /// Build extension: 3D channel diffusion and buoyancy (include/fluidsim.h).  Channel `channel` diffuses between neighbours
+    /// with this conductivity (0: not at all) in the steps after the call.  Tracking must be on; `track` and `untrack` clear
+    /// every conductivity and the buoyancy channel.
+    pub fn set_diffusion(&mut self, channel: u32, conductivity: f32) { check(unsafe { fs3_set_diffusion(self.raw, channel as c_int, conductivity) }); }
+    pub fn diffusion(&self, channel: u32) -> f32 {
+        let mut k = 0.0f32;
+        check(unsafe { fs3_get_diffusion(self.raw, channel as c_int, &mut k) }); k
+    }
+    /// The buoyancy channel: a particle with value a gains -beta (a - reference) gravity delta of velocity per step.
+    pub fn set_buoyancy(&mut self, channel: u32, beta: f32, reference: f32) { check(unsafe { fs3_set_buoyancy(self.raw, channel as c_int, beta, reference) }); }
+    pub fn clear_buoyancy(&mut self) { check(unsafe { fs3_set_buoyancy(self.raw, -1, 0.0, 0.0) }); }
+    /// (channel, beta, reference) of the buoyancy channel, if one is set.
+    pub fn buoyancy(&self) -> Option<(u32, f32, f32)> {
+        let (mut c, mut b, mut r) = (0 as c_int, 0.0f32, 0.0f32);
+        check(unsafe { fs3_get_buoyancy(self.raw, &mut c, &mut b, &mut r) });
+        if c < 0 { None } else { Some((c as u32, b, r)) }
+    }
+    /// What the last step with a buoyancy channel handed the force pass per particle, in `download_particles` order.
+    pub fn buoyancy_forces(&mut self) -> Vec<Vec3> {
+        let mut v = vec![Vec3::default(); self.particle_count() as usize];
+        check(unsafe { fs3_download_buoyancy(self.raw, v.as_mut_ptr(), v.len()) }); v
     }
     /// Build extension: 3D particle count (include/fluidsim.h).  `capacity` slots, of which `particle_count` are live.
     pub fn capacity(&self) -> u32 { unsafe { fs3_capacity(self.raw) } }

@@ -6,7 +6,7 @@ import numpy as np
 from . import _abi
 from ._abi import (FS_MATH_IEEE, FS_SORT_BITONIC, PARTICLE_DTYPE, SAMPLE_DTYPE, BodyLoad, BodyMotion, Nozzle, Options, Settings, SortStep, TickSettings,
                    Uniform, UVec2, Vec2, load_library)
-from ._handle import _Bodies, _check, _Count, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec2
+from ._handle import _Bodies, _check, _Count, _Diffusion, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec2
 
 
 def SimulationSettings(particle_count=100_000, particle_spacing=0.1, smoothing_radius=0.2, size=(53.0, 53.0),
@@ -45,7 +45,7 @@ def dam_break_2d(n):
     return settings, (float(off[0]), float(off[1])), tick
 
 
-class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Bodies, _Simulation):
+class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Diffusion, _Bodies, _Simulation):
     """FluidSimulation (src/simulation.rs:10-37) on one MI355X, driven through the C ABI."""
     _prefix = "fs_"
     _destroy = "fs_destroy"
@@ -86,40 +86,7 @@ class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Bodies, _Simulation):
         """Colour-field surface tension from the tick's surface_tension_coefficient / _treshold, for the steps after this call."""
         self._call("set_surface_tension", 1 if enable else 0)
 
-    # -- channel diffusion and buoyancy (build extension, opt-in; DESIGN.md §27) ---------
-    def set_diffusion(self, channel, conductivity):
-        """Channel `channel` diffuses between neighbours with conductivity kappa >= 0 (0: not at all, the default), for the steps
-        after this call.  Tracking must be on; track() and untrack() clear every conductivity and the buoyancy channel.  The
-        explicit update is stable while conductivity <= diffusion_limit(...)."""
-        self._call("set_diffusion", int(channel), float(conductivity))
-
-    def diffusion(self, channel):
-        k = C.c_float()
-        self._call("get_diffusion", int(channel), C.byref(k))
-        return float(k.value)
-
-    def set_buoyancy(self, channel, beta, reference=0.0):
-        """Channel `channel` becomes the buoyancy channel: a particle with value a gains -beta * (a - reference) * gravity * delta
-        of velocity per step (Boussinesq), for the steps after this call."""
-        self._call("set_buoyancy", int(channel), float(beta), float(reference))
-
-    def clear_buoyancy(self):
-        self._call("set_buoyancy", -1, 0.0, 0.0)
-
-    @property
-    def buoyancy(self):
-        """(channel, beta, reference) of the buoyancy channel, or None"""
-        c, b, r = C.c_int(), C.c_float(), C.c_float()
-        self._call("get_buoyancy", C.byref(c), C.byref(b), C.byref(r))
-        return None if c.value < 0 else (int(c.value), float(b.value), float(r.value))
-
-    def buoyancy_forces(self):
-        """What the last step with a buoyancy channel handed the force pass per particle (the buoyancy force, plus the surface
-        tension's when that is on): (N, 2) float32 in download_particles() order."""
-        out = np.empty((self.particle_count, 2), dtype=np.float32)
-        self._call("download_buoyancy", _ptr(out), out.shape[0])
-        return out
-
+    # -- channel diffusion and buoyancy (build extension, opt-in; DESIGN.md §27): _Diffusion, and the limit ---------
     @staticmethod
     def diffusion_limit(settings, tick, rest_density):
         """rho0 h^2 / (16 delta): the largest conductivity at which the explicit update of a uniform fluid at density rho0 is a

@@ -7,7 +7,7 @@ import numpy as np
 from . import _abi
 from ._abi import (FS_MATH_IEEE, MESH_VERTEX_DTYPE, PARTICLE3_DTYPE, SAMPLE3_DTYPE, SURFACE_HIT_DTYPE, Body3Load, BodyMotion3, Camera3,
                    Nozzle3, Settings3, TickSettings3, Vec3, load_library)
-from ._handle import _Bodies, _check, _Count, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec3
+from ._handle import _Bodies, _check, _Count, _Diffusion, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec3
 
 
 def dam_break_3d(n):
@@ -27,7 +27,7 @@ def dam_break_3d(n):
     return st, (float(off[0]), float(off[1]), float(off[2])), tick
 
 
-class FluidSimulation3D(_Count, _Tracking, _SurfaceTension, _Bodies, _Simulation):
+class FluidSimulation3D(_Count, _Tracking, _SurfaceTension, _Diffusion, _Bodies, _Simulation):
     """3D extension (include/fluidsim.h fs3_*); not in the reference."""
     _prefix = "fs3_"
     _destroy = "fs3_destroy"
@@ -72,6 +72,14 @@ class FluidSimulation3D(_Count, _Tracking, _SurfaceTension, _Bodies, _Simulation
         c, t = C.c_float(), C.c_float()
         self._call("surface_tension_params", C.byref(c), C.byref(t))
         return float(c.value), float(t.value)
+
+    # -- 3D channel diffusion and buoyancy (build extension): _Diffusion, and the limit ----
+    @staticmethod
+    def diffusion_limit(settings, tick, rest_density):
+        """rho0 h^2 / (18 delta): the largest conductivity at which the explicit update of a uniform fluid at density rho0 is a
+        convex combination of the neighbours' values.  The engine does not enforce it."""
+        h = float(settings.smoothing_radius)
+        return float(rest_density) * h * h / (18.0 * float(tick.delta))
 
     # -- 3D field sampling (build extension; DESIGN.md §14, the channels: §20) ----
     def sample(self, points, attributes=False, normalise=False):

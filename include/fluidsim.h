@@ -848,6 +848,64 @@ fs_status fs3_track_ids_device(fs_sim3* sim, const uint32_t** out);
 fs_status fs3_track_attr_device(fs_sim3* sim, int channel, const float** out);
 fs_status fs3_download_particles_by_id(fs_sim3* sim, fs3_particle* dst, size_t n);
 
+/* ------------------------------------------------ 3D channel diffusion and buoyancy (build extension, opt-in) */
+/* The 3D form of "channel diffusion and buoyancy" below: with these calls a tracking channel of an fs_sim3 may diffuse between
+ * neighbours (heat, dye, salinity) and one channel may feed back into the motion as a Boussinesq buoyancy force.  See DESIGN.md §28.
+ *
+ * Tracking must be on with C >= 1 channels.  Per channel c < C there is a conductivity kappa_c >= 0; 0, the default, means the
+ * channel does not diffuse.  At most one channel b is the buoyancy channel, with expansion coefficient beta and reference value
+ * A0; the default is none.  The pass runs in every step after the density pass — and after the surface-tension pass when that is
+ * on — and before the force pass.
+ *
+ * Inputs: the sorted slots' predicted positions q; this step's clamped densities rho, the values the force pass divides by; the
+ * channel values A_c as the step's carry delivered them; h2 = h * h, m = the tick's mass, Cg = 6.0f * poly6 (the Cg of "3D surface
+ * tension"), delta and gravity of the tick.
+ *
+ * Diffusion.  For sorted slot i with predicted position x, over the candidates j the density pass visits (27 cells, z outer, then
+ * y, x inner, ascending slots inside a cell, cells outside the grid skipped, i itself included), in f32 without contraction, `/`
+ * correctly rounded, sums starting at +0.0f:
+ *     ox = q_j.x - x.x;  oy = q_j.y - x.y;  oz = q_j.z - x.z;  r2 = ox*ox + oy*oy + oz*oz
+ *     if (r2 > h2) skip                          (a NaN r2 is admitted, as in "3D surface tension")
+ *     d  = h2 - r2
+ *     w  = m / rho_j
+ *     wk = w * ((Cg * d) * d)
+ *     for each diffusing channel c:  acc_c += wk * (A_c[j] - A_c[i])
+ * and then, with u_i = 1.0f / rho_i and g_c = (2.0f * kappa_c) * delta formed once on the host in f32,
+ *     A_c'[i] = A_c[i] + (g_c * acc_c) * u_i
+ * Jacobi semantics: every A_c[j] read is the value before the pass.  A skipped candidate is skipped by a select, never multiplied
+ * by zero: its A may be a NaN.  A channel with kappa_c = 0 is neither read nor written: NaN payloads, -0.0 and denormals survive
+ * bit for bit.  The weight is non-negative and symmetric in i and j; its second moment is 3 (twice the sum approximates the
+ * Laplacian of A) and it integrates to 9 / h^2: for a uniform fluid at rho0 the explicit update is a convex combination of the
+ * neighbours' values while kappa_c * delta <= rho0 h^2 / 18.  The engine does not enforce the limit.
+ *
+ * Buoyancy.  With a = A_b[i], the value before the pass,
+ *     s  = beta * (A0 - a);  rs = rho_i * s
+ *     bv = (rs * gravity.x, rs * gravity.y, rs * gravity.z)
+ *     fb = surface tension on ? (st.x + bv.x, st.y + bv.y, st.z + bv.z) : bv
+ * and the integrate line is that of "3D surface tension" with fb where it has st: acc.a = (fp.a + fv.a * viscosity_coefficient)
+ * + fb.a; everything after it is unchanged.  With no buoyancy channel the force pass gets what it gets without these calls.
+ *
+ * Bit-exact in FS_MATH_IEEE.  FS_MATH_TOLERANCE handles run this same IEEE pass on their own densities.  With nothing set a
+ * handle allocates nothing and launches exactly the kernels it launched before, with the same arguments.  The pass's time falls
+ * inside the FS_PASS_FORCE interval of fs3_profile_read.  FS_ABI_VERSION is unchanged.
+ *
+ * fs3_set_diffusion / fs3_set_buoyancy: host settings, taking effect for the steps enqueued after the call (channel = -1
+ *   switches buoyancy off and ignores the two floats' values; the first buoyancy channel allocates 16 B per slot, which
+ *   fs3_reserve grows).  fs3_track_enable (also a re-initialising one) and fs3_track_disable clear every conductivity and the
+ *   buoyancy channel.
+ * fs3_get_diffusion / fs3_get_buoyancy: the values in use (channel -1, beta 0, reference 0: no buoyancy channel).
+ * FS_ERR_INVALID for these four, in this order: a NULL handle or pointer; tracking off; channel outside [0, C) (fs3_set_buoyancy:
+ *   outside [-1, C)); a conductivity that is negative or not finite; a beta or reference that is not finite.
+ * fs3_download_buoyancy: the last step's fb, under the rules of fs3_download_surface_tension: one fs_vec3 per particle in
+ *   fs3_download_particles' slot order.  Blocking.  FS_ERR_INVALID, in this order: a NULL argument; no buoyancy channel is set; no
+ *   step has been enqueued since it was set (or since the particle count changed); n != the particle count.
+ *   fs3_download_surface_tension keeps returning st alone. */
+fs_status fs3_set_diffusion(fs_sim3* sim, int channel, float conductivity);
+fs_status fs3_get_diffusion(const fs_sim3* sim, int channel, float* conductivity);
+fs_status fs3_set_buoyancy(fs_sim3* sim, int channel, float beta, float reference);   /* channel = -1: off */
+fs_status fs3_get_buoyancy(const fs_sim3* sim, int* channel, float* beta, float* reference);
+fs_status fs3_download_buoyancy(fs_sim3* sim, fs_vec3* dst, size_t n);
+
 /* ------------------------------------------------ 3D channel sampling (build extension, opt-in by being called) */
 /* The SPH interpolant of the tracking channels at arbitrary points: what shows a carried dye, age or temperature on a slice, on a
  * ray-marched surface (sample at the hit points) or on a mesh (sample at the vertices).  The statement is that of "3D field

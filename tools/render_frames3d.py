@@ -1,6 +1,12 @@
 """Render a few frames of the 3D dam break to PNG through the ray-marched G-buffer, headless:
   python tools/render_frames3d.py [n] [frame,frame,...] [outdir] [width] [height] [--box x0,y0,z0,x1,y1,z1[,voxels]]
                                   [--surface-tension SIGMA[,TAU]] [--dye] [--faucet K[,NU,NV]] [--paddle [AMPLITUDE,PERIOD]] [--float]
+                                  [--heat [BETA]]
+--heat: one tracking channel is a temperature.  A patch of the floor (+y) under the middle of the initial block, a
+third of the block's side wide, holds the particles within 2 h of it at 1.0 (re-applied every tenth step from a download of the
+positions); the channel diffuses at a quarter of FluidSimulation3D.diffusion_limit and is the buoyancy channel with expansion
+coefficient BETA (default 0.5) about 0.0, so the warm fluid rises as a plume.  The shaded surface is tinted red by the channel's
+Shepard value at the hit points (sample_attr), as with --dye.
 --float: a dynamic body — a cube of half the fluid's density, a quarter of the block's side, released above the
 block falls onto the dam break; the handle's body loads are on and BodyDynamics3D integrates them on the host between the steps
 (one sync per step): the fluid's impulses slow and turn it (the bodies' contact model hands over momentum where particles are
@@ -46,6 +52,15 @@ if "--paddle" in sys.argv:
 floating = "--float" in sys.argv
 if floating:
     sys.argv.remove("--float")
+heat = None
+if "--heat" in sys.argv:
+    k = sys.argv.index("--heat")
+    try:                                            # BETA is written with a point: "--heat 64000" is a particle count
+        given = "." in sys.argv[k + 1] and np.isfinite(float(sys.argv[k + 1]))
+    except (IndexError, ValueError):
+        given = False
+    heat = float(sys.argv[k + 1]) if given else 0.5
+    del sys.argv[k:k + (2 if given else 1)]
 dye = "--dye" in sys.argv
 if dye:
     sys.argv.remove("--dye")
@@ -93,6 +108,23 @@ if dye:
     x0 = sim.download_particles()["position"][:, 0]
     sim.track(1)                                    # ids = the slots of this download
     sim.set_attribute(0, (x0 < np.median(x0)).astype(np.float32))
+if heat is not None:
+    L = round(n ** (1.0 / 3.0)) * st.particle_spacing
+    patch_x, patch_half = -sx / 2 + 0.5 * L, L / 6.0
+
+    def reheat():
+        p = sim.download_particles()["position"]
+        a = sim.attribute(0)
+        hot = (p[:, 1] > sy / 2 - 2 * st.smoothing_radius) & (np.abs(p[:, 0] - patch_x) < patch_half) & (np.abs(p[:, 2]) < patch_half)
+        a[hot] = 1.0
+        sim.set_attribute(0, a)
+        return int(hot.sum())
+    sim.track(1)
+    sim.tick(tick)                                     # densities exist after a step
+    rho0 = float(np.median(sim.download_particles()["density"]))
+    sim.set_diffusion(0, 0.25 * g.FluidSimulation3D.diffusion_limit(st, tick, rho0))
+    sim.set_buoyancy(0, heat, 0.0)
+    print("heat: conductivity", sim.diffusion(0), "buoyancy", sim.buoyancy, "hot particles", reheat(), flush=True)
 # gravity is +y: "up" is -y.  From in front of the -z wall, above the floor, looking at the middle of the tank.
 eye = (-0.15 * sx, -0.55 * sy, -0.5 * sz - 0.9 * sx)
 cam = g.look_at_camera(eye, (0.0, 0.15 * sy, 0.0), (0.0, -1.0, 0.0), np.radians(42.0), width, height)
@@ -102,7 +134,7 @@ if faucet is not None:
     sp = st.particle_spacing
     nozzle = dict(origin=(0.25 * sx, -0.5 * sy + 2 * h, 0.0), u=(sp, 0.0, 0.0), v=(0.0, 0.0, sp), velocity=(0.0, 3.0, 0.0),
                   nu=faucet[1], nv=faucet[2])
-done = 0
+done = 1 if heat is not None else 0
 for f in frames:
     while done < f:
         if faucet is not None and done % faucet[0] == 0 and sim.particle_count + faucet[1] * faucet[2] <= sim.capacity:
@@ -112,6 +144,8 @@ for f in frames:
             t = (done + 1) * tick.delta                 # the pose at the end of the step that is about to run
             sim.set_body_motion(plate, (amp * np.sin(om * t), 0.0, 0.0), velocity=(amp * om * np.cos(om * t), 0.0, 0.0))
         sim.tick(tick); done += 1
+        if heat is not None and done % 10 == 0:
+            reheat()
         if floating:
             dyn.advance(sim, floater, tick)
             if dyn.centre[1] > 0.5 * (sy - side):           # +y is down: the floor
@@ -123,15 +157,18 @@ for f in frames:
     reach = 1.2 * (abs(eye[2]) + 0.5 * sz) + sx
     hits = sim.render_surface(cam, g.SurfaceParams3(iso, 0.0, 0.5 * h, min(4096, int(reach / (0.5 * h)) + 1), 8))
     rgba = g.shade_surface(hits, max_speed=6.0)[::-1]                 # row 0 of the G-buffer is the image's bottom edge
-    if dye:                                         # visual only: the channel's Shepard value where the rays hit
+    if dye or heat is not None:                     # visual only: the channel's Shepard value where the rays hit
         lit = hits["hit"] != 0
         wgt, sums = sim.sample_attr(g.surface_hit_points(cam, hits)[lit], weights=True)
         c = np.zeros(hits.shape, dtype=np.float32)
         c[lit] = np.where(wgt > 0, sums[0] / np.where(wgt > 0, wgt, 1), 0)
         c = c[::-1, :, None]
+        print("frame", f, "mean temperature of the hits" if heat is not None else "dyed share of the hits", round(float(c[rgba[..., 3] > 0].mean()), 4),
+              "max", round(float(c.max()), 4), flush=True)
+        if heat is not None:                        # what reaches the surface has diffused: show a tenth of the patch's value as full red
+            c = np.clip(c * 10.0, 0.0, 1.0)
         shade = rgba[..., :3].max(axis=-1, keepdims=True)
         rgba[..., :3] = rgba[..., :3] * (1 - c) + np.float32([0.9, 0.15, 0.1]) * shade * c
-        print("frame", f, "dyed share of the hits", round(float(c[rgba[..., 3] > 0].mean()), 4), flush=True)
     g.write_png(os.path.join(outdir, f"dam3d_{n}_{f:05d}.png"), rgba, background=(0.04, 0.04, 0.06))
     print("frame", f, "coverage", round(float((hits["hit"] != 0).mean()), 4), "mean march index of hits",
           round(float(hits["steps"][hits["hit"] != 0].mean()), 1), flush=True)
