@@ -72,6 +72,7 @@ from .sim2d import (  # noqa: F401
 )
 from .sim3d import BodyLoads3D, FluidSimulation3D, box_mask3d, dam_break_3d, look_at_camera, reference_lattice_3d, rigid_motion  # noqa: F401
 from .slab import SlabSimulation  # noqa: F401
+from .stats import Stats, Stats3D  # noqa: F401
 
 __all__ = [
     "FluidSimulation", "ResizableBuffer", "SimulationSettings", "default_tick_settings", "dam_break_2d",

@@ -193,6 +193,32 @@ class Body3Load(C.Structure):
                 ("steps", C.c_uint64)]
 
 
+FS_STATS_SHIFT = 20
+
+
+class Stats(C.Structure):
+    """fs_stats (include/fluidsim.h "fluid diagnostics"): 208 bytes."""
+    _fields_ = [("count", C.c_uint64), ("nonfinite", C.c_uint64), ("dropped", C.c_uint64),
+                ("momentum_q", C.c_int64 * 2), ("energy_q", C.c_int64), ("position_q", C.c_int64 * 2), ("density_q", C.c_int64),
+                ("speed2_max", C.c_float), ("density_min", C.c_float), ("density_max", C.c_float),
+                ("pos_min", Vec2), ("pos_max", Vec2), ("tick", C.c_uint32),
+                ("attr_q", C.c_int64 * 4), ("attr_dropped", C.c_uint64 * 4), ("attr_min", C.c_float * 4), ("attr_max", C.c_float * 4),
+                ("channels", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class Stats3(C.Structure):
+    """fs3_stats (include/fluidsim.h "3D fluid diagnostics"): 232 bytes."""
+    _fields_ = [("count", C.c_uint64), ("nonfinite", C.c_uint64), ("dropped", C.c_uint64),
+                ("momentum_q", C.c_int64 * 3), ("energy_q", C.c_int64), ("position_q", C.c_int64 * 3), ("density_q", C.c_int64),
+                ("speed2_max", C.c_float), ("density_min", C.c_float), ("density_max", C.c_float),
+                ("pos_min", Vec3), ("pos_max", Vec3), ("tick", C.c_uint32),
+                ("attr_q", C.c_int64 * 4), ("attr_dropped", C.c_uint64 * 4), ("attr_min", C.c_float * 4), ("attr_max", C.c_float * 4),
+                ("channels", C.c_uint32), ("pad", C.c_uint32)]
+
+
+assert C.sizeof(Stats) == 208 and C.sizeof(Stats3) == 232
+
+
 class SurfaceHit3(C.Structure):
     """fs3_surface_hit (include/fluidsim.h): 40 bytes."""
     _fields_ = [("t", C.c_float), ("density", C.c_float), ("normal", Vec3), ("velocity", Vec3), ("steps", C.c_uint32),
@@ -346,6 +372,8 @@ PROTOTYPES = {
     "fs_set_buoyancy": (C.c_int, [_P, C.c_int, C.c_float, C.c_float]),
     "fs_get_buoyancy": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "fs_download_buoyancy": (C.c_int, [_P, _P, C.c_size_t]),
+    "fs_stats_read": (C.c_int, [_P, C.POINTER(Stats)]),
+    "fs_stats_device": (C.c_int, [_P, _P]),
     "fs_export_handle": (C.c_int, [_P, C.c_int, _P]),
     "fs_import_open": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "fs_import_read": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t]),
@@ -434,6 +462,8 @@ PROTOTYPES = {
     "fs3_set_buoyancy": (C.c_int, [_P, C.c_int, C.c_float, C.c_float]),
     "fs3_get_buoyancy": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "fs3_download_buoyancy": (C.c_int, [_P, _P, C.c_size_t]),
+    "fs3_stats_read": (C.c_int, [_P, C.POINTER(Stats3)]),
+    "fs3_stats_device": (C.c_int, [_P, _P]),
     "fs3_reserve": (C.c_int, [_P, C.c_uint32]),
     "fs3_capacity": (C.c_uint32, [_P]),
     "fs3_emit_particles": (C.c_int, [_P, _P, C.c_size_t]),

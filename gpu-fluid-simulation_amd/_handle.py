@@ -148,6 +148,25 @@ class _SurfaceTension:
         return out
 
 
+class _Stats:
+    """Fluid diagnostics reduced on the device (build extension).  `_stats` is the class's record object
+    (stats.Stats / stats.Stats3D)."""
+    _stats = None
+
+    def stats(self):
+        """fs_stats_read / fs3_stats_read: momentum, energy, centre of mass, density range, bounding box, channel sums and a
+        count of non-finite particles of the state behind everything enqueued so far, as exact integer words (blocking).  Works
+        in every state of the handle and changes none of it."""
+        raw = self._stats._ctype()
+        self._call("stats_read", C.byref(raw))
+        return self._stats(raw)
+
+    def stats_device_ptr(self, ptr):
+        """fs_stats_device / fs3_stats_device: the same record written to device memory at `ptr` (8-byte aligned, 208 bytes in
+        2D and 232 in 3D), stream-ordered on stream_ptr and without a host read; Stats.from_bytes reads it back."""
+        self._call("stats_device", C.c_void_p(int(ptr)))
+
+
 class _Diffusion:
     """Opt-in diffusion and buoyancy of the tracking channels (build extension; DESIGN.md §27, 3D: §28).  diffusion_limit stays
     per class: the constant differs."""

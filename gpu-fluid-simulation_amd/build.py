@@ -16,8 +16,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libfluidsim_hip.so")
-SOURCES = ["engine.hip", "engine_features.hip", "engine_query.hip", "engine_count.hip", "engine_selftest.hip", "engine_slab.hip", "comm.hip", "buffer.hip", "kernels_reorder.hip", "kernels_density.hip", "kernels_render.hip", "kernels_force.hip", "kernels_proof.hip", "kernels_sort.hip", "kernels_slab.hip", "kernels_strip.hip", "kernels_csort.hip", "kernels_field.hip", "kernels_track.hip", "kernels_diffuse.hip", "kernels_sample.hip", "kernels_count.hip", "kernels_bodies.hip", "kernels_3d.hip", "kernels_density3d.hip", "kernels_force3d.hip", "kernels_sample3d.hip", "kernels_sample_attr3d.hip", "kernels_render3d.hip", "kernels_mesh3d.hip", "kernels_collide3d.hip", "kernels_bodies3d.hip", "kernels_diffuse3d.hip", "engine_3d.hip", "engine_3d_features.hip", "engine_3d_query.hip", "engine_3d_count.hip"]
-HEADERS = ["engine.h", "engine_3d.h", "engine_bodies.h", "engine_count.h", "fs_3d.h", "fs_body_loads.h", "fs_count.h", "fs_csort_layout.h", "fs_device.h", "fs_field3.h", "fs_force_lists.h", "fs_force_pair.h", "fs_force_sweep.h", "fs_host.h", "fs_kernels.h", "fs_neighbours.h", "fs_sample3.h", "fs_scan.h", "fs_slab.h", "fs_sort.h", "fs_sort_tile.h", "fs_sweep3.h", "kernels_force_quad.inc", "kernels_sort_tile.inc", "kernels_sort_global.inc", "sort_policy.h", os.path.join("..", "..", "include", "fluidsim.h")]
+SOURCES = ["engine.hip", "engine_features.hip", "engine_query.hip", "engine_count.hip", "engine_selftest.hip", "engine_slab.hip", "comm.hip", "buffer.hip", "kernels_reorder.hip", "kernels_density.hip", "kernels_render.hip", "kernels_force.hip", "kernels_proof.hip", "kernels_sort.hip", "kernels_slab.hip", "kernels_strip.hip", "kernels_csort.hip", "kernels_field.hip", "kernels_track.hip", "kernels_diffuse.hip", "kernels_sample.hip", "kernels_count.hip", "kernels_bodies.hip", "kernels_3d.hip", "kernels_density3d.hip", "kernels_force3d.hip", "kernels_sample3d.hip", "kernels_sample_attr3d.hip", "kernels_render3d.hip", "kernels_mesh3d.hip", "kernels_collide3d.hip", "kernels_bodies3d.hip", "kernels_diffuse3d.hip", "kernels_stats.hip", "kernels_stats3d.hip", "engine_stats.hip", "engine_3d.hip", "engine_3d_features.hip", "engine_3d_query.hip", "engine_3d_count.hip", "engine_3d_stats.hip"]
+HEADERS = ["engine.h", "engine_3d.h", "engine_bodies.h", "engine_count.h", "fs_3d.h", "fs_body_loads.h", "fs_count.h", "fs_csort_layout.h", "fs_device.h", "fs_field3.h", "fs_force_lists.h", "fs_force_pair.h", "fs_force_sweep.h", "fs_host.h", "fs_kernels.h", "fs_neighbours.h", "fs_sample3.h", "fs_scan.h", "fs_slab.h", "fs_sort.h", "fs_sort_tile.h", "fs_stats.h", "fs_sweep3.h", "kernels_force_quad.inc", "kernels_sort_tile.inc", "kernels_sort_global.inc", "sort_policy.h", os.path.join("..", "..", "include", "fluidsim.h")]
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",
@@ -34,7 +34,7 @@ FLAGS = [
 # kernels_force_quad.inc likewise, as part of kernels_force.hip (it uses that file's integrator and parameter list).
 # float-heavy kernels only: the integer sort kernels measured ~1 % faster with the vectoriser on
 # (kernels_reorder.hip and kernels_proof.hip hold no such arithmetic; the flag is the one their kernels were measured with)
-NO_SLP = {"kernels_reorder.hip", "kernels_density.hip", "kernels_render.hip", "kernels_force.hip", "kernels_proof.hip", "kernels_3d.hip", "kernels_density3d.hip", "kernels_force3d.hip", "kernels_slab.hip", "kernels_strip.hip", "kernels_sample.hip", "kernels_sample3d.hip", "kernels_sample_attr3d.hip", "kernels_render3d.hip", "kernels_mesh3d.hip", "kernels_bodies3d.hip", "kernels_bodies.hip", "kernels_diffuse.hip", "kernels_diffuse3d.hip"}
+NO_SLP = {"kernels_reorder.hip", "kernels_density.hip", "kernels_render.hip", "kernels_force.hip", "kernels_proof.hip", "kernels_3d.hip", "kernels_density3d.hip", "kernels_force3d.hip", "kernels_slab.hip", "kernels_strip.hip", "kernels_sample.hip", "kernels_sample3d.hip", "kernels_sample_attr3d.hip", "kernels_render3d.hip", "kernels_mesh3d.hip", "kernels_bodies3d.hip", "kernels_bodies.hip", "kernels_diffuse.hip", "kernels_diffuse3d.hip", "kernels_stats.hip", "kernels_stats3d.hip"}
 
 
 def _flags(src):

@@ -5,6 +5,7 @@
 // what the bodies share with the 3D handle's engine_3d_features.hip: engine_bodies.h, and BodySlots and BodyLoads below),
 // engine_query.hip (density render, field sampling), engine_count.hip (a particle count that changes at run time; what it
 // shares with the 3D handle's engine_3d_count.hip: engine_count.h, and Tracking and RemoveScratch below),
+// engine_stats.hip (fluid diagnostics; what it shares with the 3D handle's engine_3d_stats.hip: StatsScratch below),
 // engine_selftest.hip (self-tests, read-outs), engine_slab.hip (the multi-GPU slab handles).  Internal: include/fluidsim.h is the interface.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -355,6 +356,30 @@ struct RemoveScratch {
     void release() { flags.release(); sums.release(); }
 };
 
+// Scratch of the fluid diagnostics of either handle (fs_stats_* in engine_stats.hip, fs3_stats_* in engine_3d_stats.hip; DESIGN.md
+// §29), allocated by the first call and kept for the life of the handle: the partials slab (STATS_MAX_BLOCKS rows, whatever the
+// count becomes; nothing in it needs to be zero) and the record the blocking form reads back.  Never called: no allocation, no launch.
+struct StatsScratch {
+    DevArray<unsigned long long> slab;
+    DevArray<unsigned long long> record;
+    fs_status reserve(int dims, size_t record_bytes) {
+        if (slab.p) return FS_OK;
+        if (slab.alloc((size_t)STATS_MAX_BLOCKS * stats_words(dims)) == hipSuccess && record.alloc((record_bytes + 7) / 8) == hipSuccess) return FS_OK;
+        (void)hipGetLastError();
+        slab.release(); record.release();
+        return fail(FS_ERR_OOM, "stats: device scratch");
+    }
+    // The blocking form behind its checks: `enqueue(out_dev)` puts the two launches on `st`; then one copy of the record and a
+    // synchronise.
+    template <class Rec, class Enqueue>
+    fs_status read(hipStream_t st, Rec* out, Enqueue enqueue) {
+        FS_TRY(enqueue((Rec*)record.p));
+        FS_HIP(hipMemcpyAsync(out, record.p, sizeof(Rec), hipMemcpyDeviceToHost, st));
+        FS_HIP(hipStreamSynchronize(st));
+        return FS_OK;
+    }
+};
+
 // Everything only a slab (multi-GPU) handle has: engine_slab.hip. Torn down like the handle itself, in reverse order of
 // declaration: the device arrays, then the events, the exchange stream last.
 struct SlabState {
@@ -456,6 +481,7 @@ struct fs_sim : fsd::HandleQueues, fsd::ParticleArrays {
     fsd::Diffusion dif;
     fsd::Bodies bodies;
     fsd::RemoveScratch removal;     // (not a per-step feature: emission and removal happen between steps)
+    fsd::StatsScratch stats;        // (nor this: fluid diagnostics are opt-in by being called)
     // what walks the cell table off the step path (engine_query.hip: fs_render_density; field sampling): the records
     // and the cell table belong together — a step has been enqueued since create and since the last fs_upload_particles /
     // fs_upload_start_indices

@@ -3,7 +3,7 @@
 // engine_3d.hip (lattice, life cycle, step, getters, transfers, timing), engine_3d_features.hip (what the step enqueues for:
 // colliders, moving bodies, surface tension, tracking), engine_3d_query.hip (everything behind sample_stale: sampling, rendering, extraction),
 // engine_3d_count.hip (a particle count that changes at run time: reserve, emit, remove; what it shares with the 2D handle's
-// engine_count.hip: engine_count.h).  What the bodies and the collider's mask producer share with the 2D handle's
+// engine_count.hip: engine_count.h), engine_3d_stats.hip (fluid diagnostics; the 2D engine's StatsScratch).  What the bodies and the collider's mask producer share with the 2D handle's
 // engine_features.hip: engine_bodies.h.
 // From the 2D engine (engine.h): the device check, the create-time proofs, the owners, the sort policy, Tracking, RemoveScratch
 // and BodySlots.
@@ -151,6 +151,7 @@ struct fs_sim3 {
     // The opt-in particle tracking: the 2D engine's owner (engine.h), stride cap; never enabled: no allocation, no launch.
     fsd::Tracking trk;
     fsd::RemoveScratch removal;  // scratch of a removal: the 2D engine's owner too
+    fsd::StatsScratch stats;     // scratch of the fluid diagnostics (engine_3d_stats.hip): likewise
     // The opt-in diffusion and buoyancy of the tracking channels (fs3_set_diffusion / fs3_set_buoyancy in
     // engine_3d_features.hip): the host settings of the 2D handle's fsd::Diffusion (engine.h).  Host settings only, until a
     // buoyancy channel is first set: then `fb`, 16 B per slot.  Nothing set: no launch, no allocation.

@@ -209,6 +209,20 @@ struct ColliderMask3 {
 };
 void launch3_collider_from_mask(hipStream_t st, const ColliderMask3& Q);
 
+// 3D fluid diagnostics (kernels_stats3d.hip): k3_stats over the arrays launch3_export reads (pred.w: the density),
+// one row of stats_words(3) words per block into `slab`, then the fold of fs_kernels.h into the 232-byte fs3_stats record at `out`.
+struct Stats3Input {
+    uint32_t n = 0;
+    const float4* pos = nullptr;
+    const float4* vel = nullptr;
+    const float4* pred = nullptr;
+    int channels = 0;
+    const float* attr = nullptr;       // channel c at attr + c * attr_stride
+    uint32_t attr_stride = 0;
+    uint32_t tick = 0;
+};
+void launch3_stats(hipStream_t st, const Stats3Input& I, unsigned long long* slab, void* out);
+
 // A particle count that changes at run time: fs_count.h, for both handles.
 
 }  // namespace fsd

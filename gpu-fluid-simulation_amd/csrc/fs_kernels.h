@@ -166,6 +166,34 @@ struct SampleState {
     uint32_t attr_stride = 0;
 };
 void launch_sample(hipStream_t st, const StepParams& P, const SampleQuery& Q, const SampleState& S);
+// Fluid diagnostics (build extension, include/fluidsim.h "fluid diagnostics"; kernels_stats.hip, device helpers
+// fs_stats.h): k_stats reads the arrays a download would export, in place, and stores one row of stats_words(2) 64-bit words per
+// block into `slab` (at most STATS_MAX_BLOCKS rows; nothing in it needs to be zero); k_stats_fold reduces the rows and writes the
+// 208-byte fs_stats record to `out`.  Device pointers; `out` is 8-byte aligned.
+constexpr uint32_t STATS_SHIFT = 20u;          // FS_STATS_SHIFT
+constexpr uint32_t STATS_THREADS = 256u;
+constexpr uint32_t STATS_CHUNK = 512u;         // particles a block takes per trip of its stride loop: two per lane
+constexpr uint32_t STATS_MAX_BLOCKS = 2048u;   // the grid cap (tests/test_stats_gpu.py states it too)
+constexpr uint32_t stats_words(int dims) { return 4u * (uint32_t)dims + 23u; }     // 31 in 2D, 35 in 3D (fs_stats.h has the layout)
+inline uint32_t stats_blocks(uint32_t n) {
+    const uint32_t chunks = (n + STATS_CHUNK - 1u) / STATS_CHUNK;
+    return chunks == 0u ? 1u : chunks < STATS_MAX_BLOCKS ? chunks : STATS_MAX_BLOCKS;
+}
+struct StatsInput {
+    uint32_t n = 0;
+    const float2* pos = nullptr;       // what launch_export_aos reads
+    const float2* vel = nullptr;
+    const float* rho = nullptr;        // the densities ...
+    const float2* rho2 = nullptr;      // ... or, != nullptr, {rho, +-RN(1/rho)} (a strict / ulp step)
+    int channels = 0;                  // 0 .. FS_TRACK_MAX_CHANNELS
+    const float* attr = nullptr;       // channel c at attr + c * attr_stride
+    uint32_t attr_stride = 0;
+    uint32_t tick = 0;
+};
+void launch_stats(hipStream_t st, const StatsInput& I, unsigned long long* slab, void* out);
+// The fold alone, for `rows` rows of stats_words(dims) words: the 3D launcher's second launch (kernels_stats3d.hip) is this one.
+void launch_stats_fold(hipStream_t st, int dims, const unsigned long long* slab, uint32_t rows, uint32_t n, uint32_t tick,
+                       int channels, void* out);
 // Obstacle push-out field (kernels_field.hip); h <= 1024, w < 65536.
 void launch_gradient_field(hipStream_t st, const unsigned char* image, uint32_t w, uint32_t h, float* dist,
                            uint32_t* nearest, float2* field);

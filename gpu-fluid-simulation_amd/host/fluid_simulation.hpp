@@ -182,6 +182,10 @@ public:
         return l;
     }
     const void* body_loads_device() { const void* p = nullptr; check(fs_body_loads_device(h_, &p)); return p; }
+    // Build extension: fluid diagnostics (include/fluidsim.h).  Momentum, energy, centre of mass, density range, bounding box,
+    // channel sums and a count of non-finite particles as exact integer words, reduced on the GPU; observing only.
+    fs_stats stats() { fs_stats r{}; check(fs_stats_read(h_, &r)); return r; }                 // blocking
+    void stats_device(fs_stats* out_dev) { check(fs_stats_device(h_, out_dev)); }              // stream-ordered, no host read
     // Build extension, NOT in the reference: field sampling (include/fluidsim.h), single-domain handles.  Density, Shepard weight,
     // un-normalised velocity sum, neighbour count and cell of the fluid at any points; `attr` (may be null) receives the channel
     // sums, channel c of query k at c * n + k.  Needs a tick since creation / the last upload.  Coherently ordered points are
@@ -350,6 +354,9 @@ public:
         return l;
     }
     const void* body_loads_device() { const void* p = nullptr; check(fs3_body_loads_device(h_, &p)); return p; }
+    // 3D fluid diagnostics (include/fluidsim.h "3D fluid diagnostics"): the 2D record with three components; observing only.
+    fs3_stats stats() { fs3_stats r{}; check(fs3_stats_read(h_, &r)); return r; }              // blocking
+    void stats_device(fs3_stats* out_dev) { check(fs3_stats_device(h_, out_dev)); }            // stream-ordered, no host read
     // 3D surface tension: colour-field CSF with coefficient sigma and threshold tau, for the ticks enqueued afterwards.
     void set_surface_tension(float coefficient, float threshold = 0.0f) { check(fs3_set_surface_tension(h_, 1, coefficient, threshold)); }
     void clear_surface_tension() { check(fs3_set_surface_tension(h_, 0, 0.0f, 0.0f)); }

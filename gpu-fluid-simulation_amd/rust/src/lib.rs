@@ -161,6 +161,46 @@ impl BodyLoad {
     /// Angular momentum about the body's centre handed to the body, counter-clockwise positive.
     pub fn angular_impulse(&self, mass: f64) -> f64 { self.angular_q as f64 * mass / (1u64 << BODY_LOAD_SHIFT) as f64 }
 }
+/// fs_stats: the fluid diagnostics of a 2D handle (build extension, include/fluidsim.h "fluid diagnostics"); 208 bytes.  The `_q`
+/// words are sums of Q(x) = rint(x * 2^STATS_SHIFT) over the records that are finite and in range.
+#[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct Stats {
+    pub count: u64, pub nonfinite: u64, pub dropped: u64,
+    pub momentum_q: [i64; 2], pub energy_q: i64, pub position_q: [i64; 2], pub density_q: i64,
+    pub speed2_max: f32, pub density_min: f32, pub density_max: f32,
+    pub pos_min: Vec2, pub pos_max: Vec2,
+    pub tick: u32,
+    pub attr_q: [i64; 4], pub attr_dropped: [u64; 4], pub attr_min: [f32; 4], pub attr_max: [f32; 4],
+    pub channels: u32, pub pad: u32,
+}
+const _: () = assert!(std::mem::size_of::<Stats>() == 208);
+/// fs3_stats: the same record with three components; 232 bytes.
+#[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct Stats3 {
+    pub count: u64, pub nonfinite: u64, pub dropped: u64,
+    pub momentum_q: [i64; 3], pub energy_q: i64, pub position_q: [i64; 3], pub density_q: i64,
+    pub speed2_max: f32, pub density_min: f32, pub density_max: f32,
+    pub pos_min: Vec3, pub pos_max: Vec3,
+    pub tick: u32,
+    pub attr_q: [i64; 4], pub attr_dropped: [u64; 4], pub attr_min: [f32; 4], pub attr_max: [f32; 4],
+    pub channels: u32, pub pad: u32,
+}
+const _: () = assert!(std::mem::size_of::<Stats3>() == 232);
+/// FS_STATS_SHIFT
+pub const STATS_SHIFT: u32 = 20;
+impl Stats {
+    /// The number of records in every sum: the one denominator of every mean.
+    pub fn summed(&self) -> u64 { self.count - self.nonfinite - self.dropped }
+    /// `sqrtf(speed2_max)`; 0 when no finite record contributed.
+    pub fn max_speed(&self) -> f32 { if self.speed2_max == f32::NEG_INFINITY { 0.0 } else { self.speed2_max.sqrt() } }
+    /// `0.5 * mass * energy_q * 2^-20`, `mass` the mass of one particle.
+    pub fn kinetic_energy(&self, mass: f64) -> f64 { 0.5 * mass * self.energy_q as f64 / (1u64 << STATS_SHIFT) as f64 }
+}
+impl Stats3 {
+    pub fn summed(&self) -> u64 { self.count - self.nonfinite - self.dropped }
+    pub fn max_speed(&self) -> f32 { if self.speed2_max == f32::NEG_INFINITY { 0.0 } else { self.speed2_max.sqrt() } }
+    pub fn kinetic_energy(&self, mass: f64) -> f64 { 0.5 * mass * self.energy_q as f64 / (1u64 << STATS_SHIFT) as f64 }
+}
 /// fs3_body_load: what the fluid handed one 3D body (build extension, include/fluidsim.h "3D body loads"); 72 bytes.  The six
 /// sums are in units of 2^-BODY_LOAD_SHIFT per unit particle mass, modulo 2^64; `angular_q` is about the body's centre, world frame.
 #[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq)]
@@ -258,6 +298,8 @@ extern "C" {
     fn fs_body_loads_enabled(sim: *const fs_sim) -> c_int;
     fn fs_body_loads(sim: *mut fs_sim, body: u32, out: *mut BodyLoad, reset: c_int) -> c_int;
     fn fs_body_loads_device(sim: *mut fs_sim, words: *mut *const c_void) -> c_int;
+    fn fs_stats_read(sim: *mut fs_sim, out: *mut Stats) -> c_int;
+    fn fs_stats_device(sim: *mut fs_sim, out_dev: *mut Stats) -> c_int;
     // profiling
     fn fs_profile_enable(sim: *mut fs_sim, enable: c_int) -> c_int;
     fn fs_profile_read(sim: *mut fs_sim, ms: *mut f64, steps: *mut u64, reset: c_int) -> c_int;
@@ -362,6 +404,8 @@ extern "C" {
     fn fs3_body_loads_enabled(sim: *const fs_sim3) -> c_int;
     fn fs3_body_loads(sim: *mut fs_sim3, body: u32, out: *mut Body3Load, reset: c_int) -> c_int;
     fn fs3_body_loads_device(sim: *mut fs_sim3, words: *mut *const c_void) -> c_int;
+    fn fs3_stats_read(sim: *mut fs_sim3, out: *mut Stats3) -> c_int;
+    fn fs3_stats_device(sim: *mut fs_sim3, out_dev: *mut Stats3) -> c_int;
     fn fs3_set_surface_tension(sim: *mut fs_sim3, enable: c_int, coefficient: f32, threshold: f32) -> c_int;
     fn fs3_surface_tension_enabled(sim: *const fs_sim3) -> c_int;
     fn fs3_surface_tension_params(sim: *const fs_sim3, coefficient: *mut f32, threshold: *mut f32) -> c_int;
@@ -601,6 +645,15 @@ impl FluidSimulation {
         check(unsafe { fs_body_loads_device(self.raw, &mut p) });
         p
     }
+    /// Build extension: fluid diagnostics (include/fluidsim.h).  The record behind everything enqueued so far (blocking); the
+    /// state is only read.
+    pub fn stats(&mut self) -> Stats {
+        let mut r = Stats::default();
+        check(unsafe { fs_stats_read(self.raw, &mut r) });
+        r
+    }
+    /// The same record to device memory at `out_dev` (8-byte aligned), stream-ordered and without a host read.
+    pub fn stats_device(&mut self, out_dev: *mut Stats) { check(unsafe { fs_stats_device(self.raw, out_dev) }); }
     /// `start_indices` to the host (the renderer's second storage binding; u32[grid_w * grid_h]).
     pub fn download_start_indices(&mut self) -> Vec<u32> {
         let (w, h) = self.grid_dims();
@@ -935,6 +988,14 @@ impl FluidSimulation3D {
         check(unsafe { fs3_body_loads_device(self.raw, &mut p) });
         p
     }
+    /// Build extension: 3D fluid diagnostics (include/fluidsim.h).  Blocking; the state is only read.
+    pub fn stats(&mut self) -> Stats3 {
+        let mut r = Stats3::default();
+        check(unsafe { fs3_stats_read(self.raw, &mut r) });
+        r
+    }
+    /// The same record to device memory at `out_dev` (8-byte aligned), stream-ordered and without a host read.
+    pub fn stats_device(&mut self, out_dev: *mut Stats3) { check(unsafe { fs3_stats_device(self.raw, out_dev) }); }
     /// Build extension: 3D surface tension (include/fluidsim.h), colour-field CSF with coefficient sigma and threshold tau,
     /// for the ticks enqueued afterwards.
     pub fn set_surface_tension(&mut self, coefficient: f32, threshold: f32) { check(unsafe { fs3_set_surface_tension(self.raw, 1, coefficient, threshold) }); }

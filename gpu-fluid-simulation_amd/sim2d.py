@@ -6,7 +6,8 @@ import numpy as np
 from . import _abi
 from ._abi import (FS_MATH_IEEE, FS_SORT_BITONIC, PARTICLE_DTYPE, SAMPLE_DTYPE, BodyLoad, BodyMotion, Nozzle, Options, Settings, SortStep, TickSettings,
                    Uniform, UVec2, Vec2, load_library)
-from ._handle import _Bodies, _check, _Count, _Diffusion, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec2
+from ._handle import _Bodies, _check, _Count, _Diffusion, _normalise_samples, _ptr, _Simulation, _Stats, _SurfaceTension, _Tracking, _vec2
+from .stats import Stats
 
 
 def SimulationSettings(particle_count=100_000, particle_spacing=0.1, smoothing_radius=0.2, size=(53.0, 53.0),
@@ -45,13 +46,14 @@ def dam_break_2d(n):
     return settings, (float(off[0]), float(off[1])), tick
 
 
-class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Diffusion, _Bodies, _Simulation):
+class FluidSimulation(_Count, _Tracking, _SurfaceTension, _Diffusion, _Bodies, _Stats, _Simulation):
     """FluidSimulation (src/simulation.rs:10-37) on one MI355X, driven through the C ABI."""
     _prefix = "fs_"
     _destroy = "fs_destroy"
     _record = PARTICLE_DTYPE
     _dim = 2
     _nozzle = Nozzle         # the particle count that changes at run time (DESIGN.md §22): _Count
+    _stats = Stats           # the fluid diagnostics (DESIGN.md §29): _Stats
 
     def __init__(self, settings, device=0, sort_mode=FS_SORT_BITONIC, ref_quirks=True, initial_offset=(0.0, 0.0),
                  capacity=0, math_mode=FS_MATH_IEEE, surface_tension=False, track=None):

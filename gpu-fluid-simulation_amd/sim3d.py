@@ -7,7 +7,8 @@ import numpy as np
 from . import _abi
 from ._abi import (FS_MATH_IEEE, MESH_VERTEX_DTYPE, PARTICLE3_DTYPE, SAMPLE3_DTYPE, SURFACE_HIT_DTYPE, Body3Load, BodyMotion3, Camera3,
                    Nozzle3, Settings3, TickSettings3, Vec3, load_library)
-from ._handle import _Bodies, _check, _Count, _Diffusion, _normalise_samples, _ptr, _Simulation, _SurfaceTension, _Tracking, _vec3
+from ._handle import _Bodies, _check, _Count, _Diffusion, _normalise_samples, _ptr, _Simulation, _Stats, _SurfaceTension, _Tracking, _vec3
+from .stats import Stats3D
 
 
 def dam_break_3d(n):
@@ -27,13 +28,14 @@ def dam_break_3d(n):
     return st, (float(off[0]), float(off[1]), float(off[2])), tick
 
 
-class FluidSimulation3D(_Count, _Tracking, _SurfaceTension, _Diffusion, _Bodies, _Simulation):
+class FluidSimulation3D(_Count, _Tracking, _SurfaceTension, _Diffusion, _Bodies, _Stats, _Simulation):
     """3D extension (include/fluidsim.h fs3_*); not in the reference."""
     _prefix = "fs3_"
     _destroy = "fs3_destroy"
     _record = PARTICLE3_DTYPE
     _dim = 3
     _nozzle = Nozzle3        # the particle count that changes at run time (DESIGN.md §21): _Count
+    _stats = Stats3D         # the fluid diagnostics (DESIGN.md §29): _Stats
 
     def __init__(self, settings, device=0, initial_offset=(0.0, 0.0, 0.0), math_mode=FS_MATH_IEEE, track=None):
         super().__init__()

@@ -1440,6 +1440,93 @@ fs_status fs_set_buoyancy(fs_sim* sim, int channel, float beta, float reference)
 fs_status fs_get_buoyancy(const fs_sim* sim, int* channel, float* beta, float* reference);
 fs_status fs_download_buoyancy(fs_sim* sim, fs_vec2* dst, size_t n);
 
+/* ------------------------------------------------ fluid diagnostics (build extension, opt-in by being called) */
+/* NOT in the reference.  What the fluid as a whole is doing, reduced on the GPU without a download: momentum, kinetic energy,
+ * centre of mass, density range, bounding box, the sums and ranges of the tracking channels, and a count of particles that are
+ * not finite.  Single-domain handles, 2D and 3D ("3D fluid diagnostics" below is this section with three components); see
+ * DESIGN.md §29.  A handle that never calls it launches exactly the kernels it launches without this section and allocates nothing.
+ *
+ * The result is a pure function of
+ *   - the n = fs_particle_count records r[i] that fs_download_particles would return at that point of the stream,
+ *   - with tracking on, the `channels` float arrays that fs_track_download_attr would return,
+ *   - the tick count,
+ * and of nothing else: no sort mode, no math mode, no order of particles, lanes, waves or workgroups.  All arithmetic is f32
+ * without contraction, one operation per line.
+ *
+ * Fixed point and ordering.  Q(x) is the Q of "2D body loads": the signed 64-bit integer nearest to x * 2^FS_STATS_SHIFT, ties to
+ * even; exact for |x| < 2^14.  |Q| < 2^34 and n <= 2^28, so no sum can wrap within one call.  in(x) means: not NaN and
+ * fabsf(x) < 16384.0f.  Extremes follow the total order of the bit patterns of non-NaN floats, so -0 is below +0: the engine maps a
+ * float to the usual order-preserving u32 key and reduces keys with integer min and max, and each extreme is ONE defined value
+ * too.  Maxima start from -inf and minima from +inf, and stay there when nothing contributes.
+ *
+ * Per record i, with p its position, v its velocity and rho its density:
+ *   - if any of the five floats is NaN or +-inf: nonfinite += 1, and the record contributes to nothing else;
+ *   - otherwise  a = v.x*v.x;  b = v.y*v.y;  e = a + b   (e may be +inf);
+ *     speed2_max takes e, density_min / density_max take rho, pos_min.a / pos_max.a take p.a, each as it is;
+ *   - if in() holds for v.x, v.y, p.x, p.y, e and rho:  momentum_q[a] += Q(v.a);  energy_q += Q(e);  position_q[a] += Q(p.a);
+ *     density_q += Q(rho);  otherwise dropped += 1 and the record is added to no sum.
+ * count = n, and count - nonfinite - dropped is the number of records in every sum: every mean has one denominator.
+ *
+ * Per tracking channel c < channels (channels = 0 with tracking off), over all n slots, whatever the record is: a NaN or +-inf value
+ * counts in attr_dropped[c] only; a finite value A enters attr_min[c] and attr_max[c]; with in(A) it adds Q(A) to attr_q[c],
+ * without it counts in attr_dropped[c].  Entries with c >= channels are 0 (integers) and the starting values (floats).
+ * tick = fs_tick_count; pad = 0.
+ *
+ * What a host derives from the words (mass and gravity are the step's):
+ *     momentum         = mass * momentum_q * 2^-20
+ *     kinetic energy   = 0.5 * mass * energy_q * 2^-20
+ *     potential energy = -mass * (gravity . position_q) * 2^-20
+ *     mean density, centre of mass = density_q, position_q * 2^-20 / (count - nonfinite - dropped)
+ *     largest speed    = sqrtf(speed2_max)      — with the cell side h, a CFL time step: delta = courant * h / largest speed
+ *
+ * The calls work in every state of a handle: before the first step (the lattice), after fs_upload_particles (partial uploads
+ * included), after steps in both sort modes and all three math modes, with a renderer hand-off live, after fs_reserve, fs_emit_* and
+ * fs_remove_* (n is the live count, not the capacity), with tracking on or off.  They never move or write particle state: the
+ * arrays are read in place, no record copy is made, and they may be called any number of times between steps.
+ *
+ * fs_stats_read: blocking; the record behind everything enqueued so far lands in `out`.
+ * fs_stats_device: stream-ordered on fs_stream(sim) and without a host read: two launches that leave the record at `out_dev`, which
+ *   is memory of the handle's device, 8-byte aligned, and must stay valid until the stream has passed the call.  The first call of
+ *   either form allocates the handle's scratch (under 1 MB), later calls allocate nothing.
+ * Checks, in this order; a refused call changes nothing:
+ *  1. NULL handle -> FS_ERR_INVALID.
+ *  2. A slab handle -> FS_ERR_UNSUPPORTED.
+ *  3. NULL out pointer -> FS_ERR_INVALID.
+ * FS_ABI_VERSION is unchanged. */
+#define FS_STATS_SHIFT 20
+typedef struct fs_stats {          /* 208 bytes */
+    uint64_t count, nonfinite, dropped;
+    int64_t  momentum_q[2], energy_q, position_q[2], density_q;
+    float    speed2_max, density_min, density_max;
+    fs_vec2  pos_min, pos_max;
+    uint32_t tick;
+    int64_t  attr_q[4];
+    uint64_t attr_dropped[4];
+    float    attr_min[4], attr_max[4];
+    uint32_t channels, pad;
+} fs_stats;
+fs_status fs_stats_read(fs_sim* sim, fs_stats* out);           /* blocking */
+fs_status fs_stats_device(fs_sim* sim, fs_stats* out_dev);     /* stream-ordered on fs_stream(sim), no host read */
+
+/* ------------------------------------------------ 3D fluid diagnostics (build extension, opt-in by being called) */
+/* "fluid diagnostics" above on an fs_sim3, with three components where 2D has two: seven floats decide nonfinite,
+ * c = v.z*v.z and e = (a + b) + c, in() is asked of v.x, v.y, v.z, p.x, p.y, p.z, e and rho, the records are those of
+ * fs3_download_particles and the channels those of fs3_track_download_attr.  The same rules for the calls; there is no 3D slab
+ * handle, so the checks are 1 and 3. */
+typedef struct fs3_stats {         /* 232 bytes */
+    uint64_t count, nonfinite, dropped;
+    int64_t  momentum_q[3], energy_q, position_q[3], density_q;
+    float    speed2_max, density_min, density_max;
+    fs_vec3  pos_min, pos_max;
+    uint32_t tick;
+    int64_t  attr_q[4];
+    uint64_t attr_dropped[4];
+    float    attr_min[4], attr_max[4];
+    uint32_t channels, pad;
+} fs3_stats;
+fs_status fs3_stats_read(fs_sim3* sim, fs3_stats* out);        /* blocking */
+fs_status fs3_stats_device(fs_sim3* sim, fs3_stats* out_dev);  /* stream-ordered on fs3_stream(sim), no host read */
+
 /* ----------------------------------------------------------------- errors */
 const char* fs_last_error(void);  /* thread-local, never NULL */
 int fs_abi_version(void);
